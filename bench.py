@@ -2,6 +2,7 @@
 """bench.py -- graph-windows/sec, fwd + loss + bwd of the MS-HGNN hot path (BASELINE.json metric).
 
   python bench.py --gpus N --steps K --warmup W [--config a1c2|mck4|solo|synth32] [--dtype bf16|x3|f32] [--surface flat|module]
+                  [--full] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path over one minibatch of synthetic windows that is already resident in HBM:
 forward (encoder, L message-passing layers, decoder) + wrapper loss + backward with every parameter gradient
@@ -12,13 +13,18 @@ Default workload = BASELINE.json configs[1]: A1 C2 GRF regression, bf16, h=128, 
 time-windows per GPU (weak scaling).  `--gpus N` with WORLD_SIZE unset starts the N rank processes itself (fresh
 children, before this process makes any GPU call); under torch.distributed.run it uses the ranks it is given.
 
-Timing: W warm-up steps, then blocks of EXACTLY K steps bracketed by barrier + synchronize on both sides, MAX over
-ranks per block; blocks are repeated until >= 0.5 s have been timed and the MEDIAN block is reported (`timing` holds
-the spread).  `roofline` is computed for the kernel with the largest share of the step from HIP events recorded
-around every kernel by the C-ABI (mshgnn_profile_*) in a separate pass; `roofline.step` prices the WHOLE step against
-SURVEY.md 8(d)'s algorithmic bytes / FLOPs.  `parity_plan` is the same workload on the parity-grade plan (<= 1e-4 of
-the fp64 oracle, checked here on a small batch).  `cpu_baseline` times the fp64 oracle (a port of the reference's CPU
-path, oracle/ms_hgnn_oracle.py) on the host cores on bounded samples (rank 0, N = 1).
+Timing: W warm-up steps, then ONE block of exactly K steps bracketed by barrier + synchronize on both sides, MAX over
+ranks: `ms_per_step` = that block / K.  `--dump-outputs DIR` then writes what the last timed step handed its caller
+(output, loss, flat parameter gradient; rank 0) as DIR/<name>.npy in float32; the inputs are seeded, so two builds run
+with the same arguments can be compared output for output.
+
+A plain run does only that.  `--full` adds every side measurement: `timing` repeats blocks of K steps until
+>= --min-time seconds have been timed (the spread of the headline); `roofline` is computed for the kernel with the
+largest share of the step from HIP events recorded around every kernel by the C-ABI (mshgnn_profile_*) in a separate
+pass; `roofline.step` prices the WHOLE step against SURVEY.md 8(d)'s algorithmic bytes / FLOPs.  `parity_plan` is the
+same workload on the parity-grade plan (<= 1e-4 of the fp64 oracle, checked here on a small batch).  `cpu_baseline`
+times the fp64 oracle (a port of the reference's CPU path, oracle/ms_hgnn_oracle.py) on the host cores on bounded
+samples (rank 0, N = 1).  --no-extras / --no-cpu-baseline trim a --full run.
 """
 import argparse
 import json
@@ -51,11 +57,16 @@ def parse():
     ap.add_argument("--layers", type=int, default=0, help="message-passing layers (default: 3 a1c2, 8 mck4, 8 solo, 6 synth32)")
     ap.add_argument("--hidden", type=int, default=0, help="hidden channels (default 128; 512 for synth32)")
     ap.add_argument("--dtype", default=os.environ.get("MSHGNN_BENCH_DTYPE", "bf16"), choices=["f32", "bf16", "x3"])
-    ap.add_argument("--surface", default="flat", choices=["flat", "module"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the parity-plan / L=8 / module-surface side measurements")
+    ap.add_argument("--surface", default="flat", choices=["flat", "module"], help="module: --full also times the nn.Module surface (`module_surface`)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement (timing spread, per-kernel times and roofline, parity plan, other sizes and configs, CPU baseline); "
+                         "off: set up, warm up, time the K steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the output, loss and flat gradient of the last timed step as DIR/<name>.npy (float32, <= 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the parity-plan / L=8 / module-surface side measurements")
     ap.add_argument("--cpu-batch", type=int, default=1024)
-    ap.add_argument("--min-time", type=float, default=0.5, help="seconds of timed blocks to accumulate")
+    ap.add_argument("--min-time", type=float, default=0.5, help="--full: seconds of timed blocks to accumulate for `timing`")
     ap.add_argument("--overlap", default=os.environ.get("MSHGNN_BENCH_OVERLAP", "auto"), choices=["auto", "0", "1"])
     ap.add_argument("--grad-exchange", default=os.environ.get("MSHGNN_BENCH_GRAD_EXCHANGE", "auto"), choices=["auto", "f32", "live", "bf16"],
                     help="N > 1: what the gradient all-reduce moves.  f32: the whole flat buffer; live: only the elements that can be non-zero at this depth, "
@@ -444,6 +455,33 @@ def median_step_s(step, sync, steps, warmup, min_time=0.25, max_blocks=50):
         sync(); dt = time.perf_counter() - t0
         blocks.append(dt / steps); total += dt
     return sorted(blocks)[len(blocks) // 2]
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6
+NPY_HEADER_BYTES = 256      # (np.save writes 128 for these arrays)
+
+
+def dump_outputs(outdir, arrays, limit=DUMP_LIMIT_BYTES):
+    """Write {name: tensor or array} as outdir/<name>.npy, float32 (float64 stays float64), `limit` bytes in all.  When the arrays do not fit, the smaller
+    ones are kept whole and each array larger than an equal share of what is left is replaced by a fixed sample of that many of its elements, flattened
+    (seeded indices, ascending: the same elements on every run)."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    arrs = {}
+    for name, v in arrays.items():
+        a = v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)
+        arrs[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    left = limit - NPY_HEADER_BYTES * len(arrs)
+    if sum(a.nbytes for a in arrs.values()) > left:
+        order = sorted(arrs, key=lambda k: arrs[k].nbytes)
+        for i, name in enumerate(order):
+            a, share = arrs[name], left // (len(order) - i)
+            if a.nbytes > share:
+                idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+                arrs[name] = a.reshape(-1)[idx]
+            left -= arrs[name].nbytes
+    for name, a in arrs.items():
+        np.save(os.path.join(outdir, f"{name}.npy"), a)
 
 
 def parity_golden(dtype, device, name="a1c2_h128_L3_d3_B3"):
@@ -856,37 +894,12 @@ def main():
             wl.overlap = False
             wl.overlap_choice["two_phase"] = False
         wl.use_live = live and not wl.overlap
-    med, blocks = wl.time_blocks(args.steps, args.warmup, args.min_time)
-    single = None
-    if wl.nb > 1 and world == 1:      # the same loop on ONE resident batch (what rounds 1-5 timed), reported beside the headline
-        nb_keep, wl.nb = wl.nb, 1
-        wl.xs, wl.y = wl.batches[0]
-        m1, _ = wl.time_blocks(args.steps, args.warmup, args.min_time / 2)
-        single = {"ms_per_step": m1 / args.steps * 1e3, "value": B * args.steps / m1}
-        wl.nb = nb_keep
-    value = world * B * args.steps / med
+    block, _ = wl.time_blocks(args.steps, args.warmup, 0.0, max_blocks=1)      # the headline: one block of exactly --steps timed steps
+    step_s = block / args.steps
+    value = world * B * args.steps / block
+    if args.dump_outputs and rank == 0:      # what the last timed step handed its caller (the gradient is the all-reduced one when N > 1)
+        dump_outputs(args.dump_outputs, {"out": wl.out, "loss": wl.loss, "grad_flat": wl.gflat})
     loss = float(wl.loss.item())
-
-    # per-kernel HIP events (separate pass) -> roofline of the dominant kernel
-    stats = wl.kernel_stats(args.steps)
-    roof = roofline_of(stats, args.steps, B, args.dtype, wl.e, args.config, L, hidden)
-    step_s = med / args.steps
-    if args.config == "a1c2" and L in (3, 8) and hidden == 128:
-        # the WHOLE step against SURVEY.md 8(d): inputs read once forward + once for the encoder's weight gradients
-        es = {"bf16": 1.0, "x3": 2.0, "f32": 2.0}[args.dtype]
-        sb = 2.0 * SURVEY_8D["bytes_in_bf16"] * es * B
-        sf = SURVEY_8D["flops_L3" if L == 3 else "flops_L8"] * B
-        roof["step"] = {"algorithmic_bytes": sb, "hbm_frac": sb / step_s / 1e9 / PEAK["hbm_GBs"],
-                        "algorithmic_flops": sf, "mfma_frac": sf / step_s / 1e12 / PEAK["mfma_TFLOPs"][args.dtype],
-                        "note": "SURVEY 8(d) per-window figures x windows / measured step time (they count every node; see step_live)"}
-        # what the plan really has to touch: inputs of the nodes that can reach the output at this depth (twice), FLOPs of the live nodes only
-        lb = 2.0 * float(wl.e.info.bytes_in_live) * B
-        lf = (wl.e.info.flops_fwd + wl.e.info.flops_bwd) * B
-        roof["step_live"] = {"algorithmic_bytes": lb, "hbm_frac": lb / step_s / 1e9 / PEAK["hbm_GBs"],
-                             "algorithmic_flops": lf, "mfma_frac": lf / step_s / 1e12 / PEAK["mfma_TFLOPs"][args.dtype],
-                             "note": "the same with node-level liveness: only nodes whose values can reach the decoder at this depth (A1-C2 at 3 layers: "
-                                     "not the base nodes -- four hops from the feet; the reference computes them and gets exact-zero gradients)"}
-    kernels = {s["name"]: round(s["total_ms"] / s["launches"] * 1e3, 2) for s in stats}
 
     names = {"a1c2": "A1-C2 GRF regression (3-D)", "mck4": "MiniCheetah-K4 contact classification", "solo": "Solo-12 K4 centroidal-momentum regression (COM_HGNN_K4)",
              "synth32": "synthetic 32-limb MI-HGNN GRF regression", "mcc2": "MiniCheetah-C2 contact classification", "solo_s4": "Solo-12 S4 centroidal-momentum regression (COM_HGNN_S4)", "mi_quad": "MI-HGNN quadruped contact classification (GRF_HGNN)"}
@@ -903,11 +916,9 @@ def main():
                        "grad_exchange_choice": wl.exchange_choice,
                        "collective": "stream (C-ABI ncclAllReduce on the step's stream)" if (wl.use_stream and not wl.overlap) else "torch.distributed",
                        "collective_choice": wl.collective_choice or {"mode": args.collective, "stream": bool(wl.use_stream)}} if dist is not None else {})},
-        "timing": {"blocks": len(blocks), "block_steps": args.steps, "median_ms": med * 1e3, "min_ms": min(blocks) * 1e3, "max_ms": max(blocks) * 1e3,
-                   "timed_s": sum(blocks)},
+        "timing": {"blocks": 1, "block_steps": args.steps, "timed_s": block},
         "overlap": wl.overlap_choice or {"mode": args.overlap, "two_phase": bool(wl.overlap)},
-        "roofline": roof, "kernel_us": kernels,
-        "resident_batches": wl.nb, "single_resident_batch": single,
+        "resident_batches": wl.nb,
         "step_kernel": {"specialised": getattr(wl.e, "specialised", ""),
                         "what": "compile-time program the one-call step's stack launch runs on (csrc/mshgnn_spec_tables.inc; '' = the plan tables are interpreted; "
                                 "MSHGNN_SPEC=0 forces that -- same bits, tests/test_spec_gpu.py)"},
@@ -919,8 +930,41 @@ def main():
                        "input_bytes_per_window": float(wl.e.info.bytes_in), "live_input_bytes_per_window": float(wl.e.info.bytes_in_live),
                        "what": "nodes whose output cannot reach the decoder within the model's depth are not computed (exact: the reference gives "
                                "their parameters zero gradients); MSHGNN_PRUNE=0 computes every node of every live type as rounds 1-3 did"}
-    extras = rank == 0 and world == 1 and not args.no_extras and args.config == "a1c2" and args.surface == "flat" and hidden == 128
-    if rank == 0 and world == 1 and not args.no_extras and args.config == "mck4" and args.dtype == "bf16" and args.surface == "flat" and hidden == 128:
+    if args.full:
+        # the spread of the headline: more blocks of K steps until >= --min-time seconds have been timed
+        med, blocks = wl.time_blocks(args.steps, 0, args.min_time)
+        res["timing"] = {"blocks": len(blocks), "block_steps": args.steps, "median_ms": med * 1e3, "min_ms": min(blocks) * 1e3, "max_ms": max(blocks) * 1e3,
+                         "timed_s": sum(blocks), "what": "blocks of K steps after the headline's block; the headline is the first block alone"}
+        single = None
+        if wl.nb > 1 and world == 1:      # the same loop on ONE resident batch (what rounds 1-5 timed), reported beside the headline
+            nb_keep, wl.nb = wl.nb, 1
+            wl.xs, wl.y = wl.batches[0]
+            m1, _ = wl.time_blocks(args.steps, args.warmup, args.min_time / 2)
+            single = {"ms_per_step": m1 / args.steps * 1e3, "value": B * args.steps / m1}
+            wl.nb = nb_keep
+        res["single_resident_batch"] = single
+        # per-kernel HIP events (separate pass) -> roofline of the dominant kernel
+        stats = wl.kernel_stats(args.steps)
+        roof = roofline_of(stats, args.steps, B, args.dtype, wl.e, args.config, L, hidden)
+        if args.config == "a1c2" and L in (3, 8) and hidden == 128:
+            # the WHOLE step against SURVEY.md 8(d): inputs read once forward + once for the encoder's weight gradients
+            es = {"bf16": 1.0, "x3": 2.0, "f32": 2.0}[args.dtype]
+            sb = 2.0 * SURVEY_8D["bytes_in_bf16"] * es * B
+            sf = SURVEY_8D["flops_L3" if L == 3 else "flops_L8"] * B
+            roof["step"] = {"algorithmic_bytes": sb, "hbm_frac": sb / step_s / 1e9 / PEAK["hbm_GBs"],
+                            "algorithmic_flops": sf, "mfma_frac": sf / step_s / 1e12 / PEAK["mfma_TFLOPs"][args.dtype],
+                            "note": "SURVEY 8(d) per-window figures x windows / measured step time (they count every node; see step_live)"}
+            # what the plan really has to touch: inputs of the nodes that can reach the output at this depth (twice), FLOPs of the live nodes only
+            lb = 2.0 * float(wl.e.info.bytes_in_live) * B
+            lf = (wl.e.info.flops_fwd + wl.e.info.flops_bwd) * B
+            roof["step_live"] = {"algorithmic_bytes": lb, "hbm_frac": lb / step_s / 1e9 / PEAK["hbm_GBs"],
+                                 "algorithmic_flops": lf, "mfma_frac": lf / step_s / 1e12 / PEAK["mfma_TFLOPs"][args.dtype],
+                                 "note": "the same with node-level liveness: only nodes whose values can reach the decoder at this depth (A1-C2 at 3 layers: "
+                                         "not the base nodes -- four hops from the feet; the reference computes them and gets exact-zero gradients)"}
+        res["roofline"] = roof
+        res["kernel_us"] = {s["name"]: round(s["total_ms"] / s["launches"] * 1e3, 2) for s in stats}
+    extras = args.full and rank == 0 and world == 1 and not args.no_extras and args.config == "a1c2" and args.surface == "flat" and hidden == 128
+    if args.full and rank == 0 and world == 1 and not args.no_extras and args.config == "mck4" and args.dtype == "bf16" and args.surface == "flat" and hidden == 128:
         del wl
         torch.cuda.empty_cache()
         res["end_to_end"] = end_to_end(spec, B, device, args.steps, args.warmup, "mck4")
@@ -1026,9 +1070,9 @@ def main():
             torch.cuda.empty_cache()
         if args.dtype == "bf16" and L == 3 and B == 8192:      # the other BASELINE configs, driver-visible
             res["configs"] = {c: side_config(c, device, args.steps, args.warmup) for c in ("mck4", "solo", "synth32")}
-    if args.surface == "module" and rank == 0 and world == 1:
+    if args.full and args.surface == "module" and rank == 0 and world == 1:
         res["module_surface"] = module_surface(spec, B, device, args.steps, args.warmup, args.dtype)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.config != "synth32":
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.config != "synth32":
         res["cpu_baseline"] = cpu_baseline(spec, args.cpu_batch)
         res["cpu_baseline_B32"] = cpu_baseline(spec, 32, budget_s=6.0, scan=False)     # the reference's own CPU-runnable case
     cfile = os.path.join(ROOT, ".build_commit")      # (tools/profile_round.sh runs: the commit the snapshot was taken at)

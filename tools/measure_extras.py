@@ -20,6 +20,6 @@ for _ in range(20):
 gms = sorted(gpu_ms)[len(gpu_ms) // 2]
 print(json.dumps({"window_assembly_ms_B8192_wall": dt * 1e3, "gpu_ms_events": gms, "windows_per_s_gpu": B / (gms * 1e-3), "GB_per_s_written_gpu": B * 14408 / (gms * 1e-3) / 1e9}))
 for cfg in (["--layers", "8"], ["--batch", "32768"], ["--dtype", "f32"], ["--batch", "2048"]):
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "15", "--warmup", "3", "--no-cpu-baseline"] + cfg, capture_output=True, text=True)
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "15", "--warmup", "3", "--no-cpu-baseline"] + cfg, capture_output=True, text=True)
     d = json.loads(r.stdout.strip().splitlines()[-1])
     print(json.dumps({"cfg": cfg, "windows_per_s": d["value"], "ms_per_step": d["ms_per_step"], "kernel_us": d["kernel_us"]}))
