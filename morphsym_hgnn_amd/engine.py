@@ -844,9 +844,14 @@ class PaddedEngine:
         self.inner = Engine(self.inner_spec, dtype=dtype, device=device)
         e = self.inner
         self.lib, self.device, self.dtype, self.torch_dtype, self.types, self.n_out = e.lib, e.device, e.dtype, e.torch_dtype, e.types, e.n_out
-        self.generic, self.storage, self.info = e.generic, e.storage, e.info
+        self.generic, self.storage = e.generic, e.storage
+        # the plan's summary in the caller's coordinates: a copy (not the inner engine's), with the two-phase split moved to the TRUE layout -- the offset of
+        # the first non-encoder parameter (-1, as the inner plan's, where there is no two-phase step)
+        self.info = MshgnnInfo.from_buffer_copy(e.info)
+        off_t = spec.param_offsets()
+        self.info.grad_split = min(o for k, (o, _) in off_t.items() if not k.startswith("encoder.")) if e.info.grad_split >= 0 else -1
         true_pos, pad_pos = [], []
-        shp_t, shp_p, off_t, off_p = spec.param_shapes(), self.inner_spec.param_shapes(), spec.param_offsets(), self.inner_spec.param_offsets()
+        shp_t, shp_p, off_p = spec.param_shapes(), self.inner_spec.param_shapes(), self.inner_spec.param_offsets()
         for k, st in shp_t.items():
             sp, (ot, nt_), (op, _) = shp_p[k], off_t[k], off_p[k]
             true_pos.append(torch.arange(ot, ot + nt_, dtype=torch.int64))
@@ -859,6 +864,10 @@ class PaddedEngine:
         self._pflat = torch.zeros(self.inner_spec.flat_size(), dtype=torch.float32, device=self.device)      # everything outside _pad_pos stays zero for ever
         self._pgrad = torch.empty_like(self._pflat)
         self._tmp = torch.empty(self._true_pos.numel(), dtype=torch.float32, device=self.device)
+        # the two regions of the two-phase step (true-layout positions and their padded twins): [grad_split:] after phase 0, [:grad_split] after phase 1
+        split = max(int(self.info.grad_split), 0)
+        hi = self._true_pos >= split
+        self._phase_pos = ((slice(split, None), self._true_pos[hi], self._pad_pos[hi]), (slice(0, split), self._true_pos[~hi], self._pad_pos[~hi]))
 
     # ---- layout translation ----
     def _pad(self, params_flat: torch.Tensor) -> torch.Tensor:
@@ -868,12 +877,17 @@ class PaddedEngine:
         self._pflat.index_copy_(0, self._pad_pos, self._tmp)
         return self._pflat
 
-    def _unpad_grad(self, grad_flat: Optional[torch.Tensor]) -> torch.Tensor:
+    def _unpad_grad(self, grad_flat: Optional[torch.Tensor], region=slice(None), true_pos=None, pad_pos=None) -> torch.Tensor:
+        """Gather the padded gradient into the caller's true layout: the whole buffer, or one region of it (`region`, whose parameters sit at
+        `true_pos` and their padded twins at `pad_pos`) -- nothing outside the region is written.  (The alignment gaps between parameters are zeros.)"""
         if grad_flat is None:
             grad_flat = torch.empty(self.spec.flat_size(), dtype=torch.float32, device=self.device)
-        torch.index_select(self._pgrad, 0, self._pad_pos, out=self._tmp)
-        grad_flat.zero_()
-        grad_flat.index_copy_(0, self._true_pos, self._tmp)
+        if true_pos is None:
+            true_pos, pad_pos = self._true_pos, self._pad_pos
+        tmp = self._tmp[:true_pos.numel()]
+        torch.index_select(self._pgrad, 0, pad_pos, out=tmp)
+        grad_flat[region].zero_()
+        grad_flat.index_copy_(0, true_pos, tmp)
         return grad_flat
 
     # ---- the Engine surface models.py / wrappers.py / tests use ----
@@ -930,10 +944,13 @@ class PaddedEngine:
         return self.inner.padded_width(t)
 
     def step_mse_phase(self, phase, xs, params_flat, y, B, out, grad_flat, loss):
-        """Two-phase step (multi-GPU overlap): phase 0 pads the parameters and runs the inner phase on the padded gradient buffer, phase 1 finishes it and unpads."""
+        """Two-phase step (multi-GPU overlap) with `Engine.step_mse_phase`'s contract in the true layout: phase 0 pads the parameters, runs the inner
+        phase on the padded gradient buffer and gathers grad_flat[self.info.grad_split:]; phase 1 finishes it and gathers grad_flat[:grad_split] only --
+        what the caller did to the first region in between (its all-reduce) stays."""
+        if grad_flat.dtype != torch.float32 or not grad_flat.is_cuda or grad_flat.numel() != self.spec.flat_size():
+            raise ValueError(f"grad_flat must be a contiguous fp32 device tensor of {self.spec.flat_size()} elements")
         r = self.inner.step_mse_phase(phase, xs, self._pad(params_flat) if phase == 0 else self._pflat, y, B, out, self._pgrad, loss)
-        if phase == 1:
-            self._unpad_grad(grad_flat)
+        self._unpad_grad(grad_flat, *self._phase_pos[1 if phase else 0])
         return r
 
     def hidden_state(self, B, layer):

@@ -137,26 +137,28 @@ def engine_relu_decisions(e, spec, B):
     [NN][hidden/32 column slices][ceil(B/16) tiles][4 groups][16 windows], bit j <-> feature 32 slice + 8 group + j) and
     {("t1", l): bool [B*n_base, hidden]} from the stashed base_transform activation T1 (its backward masks with T1 > 0)."""
     lay, ws = e.layout(B, True), e.workspace(B, True)
-    nn_, h, tiles = e.info.total_nodes, spec.hidden, (B + 15) // 16
+    # (a PaddedEngine's workspace holds the inner model's rows: read them at the padded width, hand back the true width's columns)
+    nn_, h, tiles = e.info.total_nodes, (e.inner_spec.hidden if getattr(e, "padded", False) else spec.hidden), (B + 15) // 16
+    ht = spec.hidden
     sl = node_slices(spec)
 
     def from_bytes(off):
         ns = h // 32                                                                    # column slices of 32 features
         raw = ws[off:off + nn_ * ns * tiles * 64].view(nn_, ns, tiles, 4, 16).cpu()
         bits = (raw.unsqueeze(-1) >> torch.arange(8, dtype=torch.uint8)) & 1            # [NN, slice, tile, group, win, bit]
-        return bits.permute(2, 4, 0, 1, 3, 5).reshape(tiles * 16, nn_, h)[:B].bool()  # [B, NN, 128]
+        return bits.permute(2, 4, 0, 1, 3, 5).reshape(tiles * 16, nn_, h)[:B, :, :ht].bool()  # [B, NN, hidden]
 
     out = {}
     # (a node the plan does not compute -- spec.node_liveness -- has no decision: its rows of the relu bytes are unwritten memory; run_engine_case
     #  gives the oracle the exact decision there, row_live_mask says which rows are real)
     m0 = from_bytes(lay.dd[0])
     for t in spec.node_types:
-        out[("enc", t)] = m0[:, sl[t]].reshape(-1, h)
+        out[("enc", t)] = m0[:, sl[t]].reshape(-1, ht)
     for l in range(spec.num_layers):
         ml = from_bytes(lay.mask[l])
         for t in spec.live_types(l):
             if not (spec.has_base_transform and t == "base"):
-                out[("layer", l, t)] = ml[:, sl[t]].reshape(-1, h)
+                out[("layer", l, t)] = ml[:, sl[t]].reshape(-1, ht)
         if spec.has_base_transform and spec.node_liveness()[0][l]["base"]:
             nb = spec.num_nodes["base"]
             n = nb * B * h
@@ -164,7 +166,7 @@ def engine_relu_decisions(e, spec, B):
                 t1 = ws[lay.t1[l]:lay.t1[l] + 4 * n].view(torch.bfloat16).view(nb, B, 2, h)[:, :, 0]      # rows of [hi | lo]: hi carries the sign
             else:
                 t1 = ws[lay.t1[l]:lay.t1[l] + n * (4 if e.storage == "f32" else 2)].view(torch.float32 if e.storage == "f32" else torch.bfloat16).view(nb, B, h)
-            out[("t1", l)] = (t1.permute(1, 0, 2).reshape(-1, h).float() > 0).cpu()
+            out[("t1", l)] = (t1[..., :ht].permute(1, 0, 2).reshape(-1, ht).float() > 0).cpu()
     return out
 
 
@@ -182,7 +184,7 @@ def row_live_mask(spec, key, B):
     return m.repeat(B)
 
 
-def run_engine_case(spec, x_dict, y, params, ei, B, dtype="f32", device="cuda:0", decision_tol=1e-4):
+def run_engine_case(spec, x_dict, y, params, ei, B, dtype="f32", device="cuda:0", decision_tol=1e-4, engine=None):
     """Run fwd + MSE/CE + bwd through the C-ABI and through the oracle; return dict of relative errors
     (max-abs error / max-abs reference) per stage, plus the raw engine results.
 
@@ -190,11 +192,12 @@ def run_engine_case(spec, x_dict, y, params, ei, B, dtype="f32", device="cuda:0"
     side in finite precision, and the gradient is discontinuous there (one flipped decision moves a tiny-batch weight gradient by
     1e-3..1e-2 of its scale on ANY plan, fp32 included).  Every decision that differs from the exact one must belong to a
     pre-activation within `decision_tol` x (max-abs of its tensor) of zero -- counted in errs["relu_decisions_outside_tolerance"],
-    which must be 0 -- and given the same decisions every hidden state, the output, the loss and every gradient must match."""
+    which must be 0 -- and given the same decisions every hidden state, the output, the loss and every gradient must match.
+    engine: run on this engine (e.g. an `engine.make_engine` PaddedEngine) instead of a fresh `Engine(spec, dtype, device)`."""
     from morphsym_hgnn_amd import engine as eng
     from oracle import ms_hgnn_oracle as orc
     cfg = oracle_config(spec)
-    e = eng.Engine(spec, dtype=dtype, device=device)
+    e = engine or eng.Engine(spec, dtype=dtype, device=device)
     xs = e.cast_inputs(x_dict)
     flat = eng.flatten_params(spec, params, device=e.device)
     out = e.forward(xs, flat, B, training=True)
@@ -257,6 +260,7 @@ def run_engine_case(spec, x_dict, y, params, ei, B, dtype="f32", device="cuda:0"
         else:
             errs["grad:" + k] = rel(grads[k], g)
     run_engine_case.last_decisions_differing = stats["differ"]
+    run_engine_case.last_reference = {"out": o_out.detach(), "loss": o_loss.detach(), "grads": o_grads}      # (the oracle's results under those decisions)
     return errs, out.detach().cpu(), (loss.detach().cpu() if loss is not None else o_loss.detach()), grads
 
 
@@ -336,5 +340,7 @@ def run_step_case(spec, x_dict, y, params, B, dtype="x3", device="cuda:0", decis
         ref_max = float(g.abs().max())
         errs["grad:" + k] = float(grads[k].abs().max()) if ref_max == 0.0 else rel(grads[k], g)
     run_step_case.last_decisions_differing = stats["differ"]
+    run_step_case.last_reference = {"out": o_out.detach(), "loss": o_loss.detach(),
+                                    "grads": {k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in leaves.items()}}
     run_step_case.last_decisions_total = stats["total"]
     return errs, out.detach().cpu(), loss.detach().cpu(), grads

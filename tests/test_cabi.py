@@ -96,6 +96,32 @@ def test_wide_and_many_node_models_compile_on_the_generic_engine(monkeypatch):
             assert info.kernel_sets == 4 and info.total_nodes == 1 + 4 * limbs
 
 
+def _small_mi_spec(hidden):
+    from morphsym_hgnn_amd import topology
+    from morphsym_hgnn_amd.spec import ModelSpec
+    return ModelSpec(kind="mi", topology=topology.synthetic_limbs(1), hidden=hidden, num_layers=2, widths={"base": 24, "joint": 9, "foot": 5},
+                     regression=True, grf_dimension=1, group=None, num_timesteps=3)
+
+
+@pytest.mark.parametrize("dt", ["bf16", "x3", "f32"])
+def test_plan_compiler_accepts_every_width_of_the_generic_range(dt):
+    """The widths the GPU width sweep (tests/test_widths_gpu.py) and engine.PaddedEngine rely on: every multiple of 128 from 128 to 2048 compiles for
+    every arithmetic mode; from 256 on it is the generic-width engine's plan (kernel_sets == 4), at 128 either engine's."""
+    for hidden in range(128, 2048 + 1, 128):
+        info = engine.compile_plan_host(_small_mi_spec(hidden), dt)
+        assert info.total_nodes == 5, hidden
+        if hidden >= 256:
+            assert info.kernel_sets == 4, (hidden, info.kernel_sets)
+
+
+@pytest.mark.parametrize("dt", ["bf16", "x3", "f32"])
+@pytest.mark.parametrize("hidden", [2176, 4096, 200, 129, 1, 2047])
+def test_plan_compiler_refuses_widths_outside_the_generic_range(hidden, dt):
+    """Above 2048 (2176 is where PaddedEngine would take hidden = 2049) and off the 128 grid: refused by both plan compilers, naming the range."""
+    with pytest.raises(engine.MshgnnError, match=r"128\.\.2048"):
+        engine.compile_plan_host(_small_mi_spec(hidden), dt)
+
+
 def test_engine_fails_loudly_without_gpu():
     import torch
     if torch.cuda.is_available():
