@@ -2513,6 +2513,7 @@ extern "C" int mshgnn_plan_create(const mshgnn_desc* desc, mshgnn_plan** out) {
     if (!desc) { delete p; return set_err(MSHGNN_EINVAL, "null descriptor"); }
     p->n_types = desc->n_types;
     if (const char* e = getenv("MSHGNN_STEP_CHUNK")) p->step_chunk = std::max<int64_t>(0, atoll(e));
+    if (const char* e = getenv("MSHGNN_STASH_NT")) p->stash_nt_force = atoi(e);      // (read per plan, like MSHGNN_SLAB / SPEC / FUSED)
     // Engine choice: the LDS-resident kernels (hidden == 128, <= 20 nodes, in-degree 1 on mean relations) where they apply, else the
     // generic-width engine of mshgnn_gen.hip.  MSHGNN_ENGINE=generic forces the latter (the GPU tests run the golden cases through both).
     const char* eng_env = getenv("MSHGNN_ENGINE");
@@ -2787,7 +2788,7 @@ static int forward_impl(const mshgnn_plan* p, const void* const* x, const int64_
             }
             a.stamps = stamp_ptr("MSHGNN_STAMPS");
             a.stagger = p->slab_for(tiles) && tiles > p->n_cu ? p->stagger : 0;
-            a.stash_nt = training ? stash_nt_for(B, stash_rows_of(hp), H * (int)sizeof(T)) : 0;
+            a.stash_nt = training ? stash_nt_for(p->stash_nt_force, B, stash_rows_of(hp), H * (int)sizeof(T)) : 0;
             // the tail's reduction scratch (one decoder slab per wave) must not touch the out-type nodes' blocks, which receive dX_L for the backward sweep: it sits
             // in the blocks in front of them, or (models whose out type comes first: the centroidal-momentum ones) in the blocks behind them
             const bool want_step = stack_step_done && p->use_step && (y_fused || labels_fused);
@@ -2894,7 +2895,7 @@ static int backward_impl(const mshgnn_plan* p, const void* const* x, const int64
             a.dbg = p->dbg;
             a.stamps = stamp_ptr("MSHGNN_STAMPS_BWD");
             a.stagger = p->slab_for(tiles) && tiles > p->n_cu ? p->stagger : 0;
-            a.stash_nt = stash_nt_for(B, stash_rows_of(hp), H * (int)sizeof(T));
+            a.stash_nt = stash_nt_for(p->stash_nt_force, B, stash_rows_of(hp), H * (int)sizeof(T));
             ProfScope ps(p, hp.ks_stack_bwd, st);
             const StackKernel bwd_spec = (p->use_slab && p->use_spec) ? slab_bwd_spec_kernel(hp, a.stash_nt, whole_tiles(B)) : nullptr;      // (at every whole-tile batch size, like the forward)
             if (bwd_spec || p->slab_for(tiles)) {

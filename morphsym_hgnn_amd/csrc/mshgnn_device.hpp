@@ -805,8 +805,7 @@ template <class A> __device__ __forceinline__ void stash_store_u(const A& a, gwc
     static_assert(A::nt_mode >= 0, "compile-time store policy");
     if constexpr (A::nt_mode == 1) gstore16_nt(base, off, v); else gstore16(base, off, v);
 }
-inline int stash_nt_for(int64_t B, int stash_rows, int row_bytes) {
-    static const int force = []() { const char* e = getenv("MSHGNN_STASH_NT"); return e ? atoi(e) : -1; }();
+inline int stash_nt_for(int force, int64_t B, int stash_rows, int row_bytes) {      // force: the plan's MSHGNN_STASH_NT (read when the plan is created), -1 = by size
     static const int64_t limit_mb = []() { const char* e = TUNE_ENV("MSHGNN_STASH_NT_MB"); return (int64_t)(e ? atoi(e) : 200); }();
     if (force == 0 || force == 1) return force;
     return (int64_t)stash_rows * B * row_bytes > (limit_mb << 20) ? 1 : 0;
@@ -1304,6 +1303,7 @@ struct mshgnn_plan {
     bool use_fused = false;             // bf16 plan: fused stack kernels (MSHGNN_FUSED=0 selects the per-layer kernels)
     bool use_slab = false;              // slab variant of the stack kernels (MSHGNN_SLAB=0 selects the 8-wave ones)
     bool slab_force = false; int n_cu = 256;
+    int stash_nt_force = -1;            // MSHGNN_STASH_NT when the plan was created: 0 / 1 force the stash store policy, -1 = by stash size (stash_nt_for)
     int64_t step_chunk = 32768;         // one-call steps over at least twice as many windows run as sub-steps of at least this many (StepChunk; MSHGNN_STEP_CHUNK, 0 = never)
     bool use_step = false;              // one-call steps on the slab kernels: k_slab_step (MSHGNN_STEP_KERNEL=0: two launches)
     bool use_spec = true;               // ... on the specialised kernel where the plan has one (MSHGNN_SPEC=0 at plan creation: the interpreting kernel)

@@ -1303,7 +1303,7 @@ static void x3_stack_args(const mshgnn_plan* p, const mshgnn_ws_layout& lay, cha
     a.wpack = ws + lay.wpack; a.bias = reinterpret_cast<const float*>(ws + lay.bias); a.tables = p->d_tables;
     a.B = B; a.NN = hp.NN; a.L = hp.L;
     a.lo_blk = hp.lo_blk; a.n_img = hp.n_img; a.scr0 = hp.x3_alias ? hp.NN - hp.n_mlp : hp.NN;
-    a.stash_nt = stash_nt_for(B, stash_rows_of(hp), H * 2);      // (counted per row, not per byte: stash_nt_for)
+    a.stash_nt = stash_nt_for(p->stash_nt_force, B, stash_rows_of(hp), H * 2);      // (counted per row, not per byte: stash_nt_for)
 }
 
 int x3_forward(const mshgnn_plan* p, const void* const* x, const int64_t* x_pitch, const float* params, float* out, char* ws, int64_t batch,

@@ -1,0 +1,308 @@
+"""Rounding-free test data for the bf16 plan (test infrastructure, host only).
+
+Every weight matrix has one signed entry per row (+-1, the relation weights scaled by 0.5 or 1), biases are integers, inputs small integers and the
+output gradient a few units of 2^-14.  On such data every value the kernels store in bf16 is exactly representable and every fp32 accumulation is exact
+in any order, so the bf16, split (x3) and fp32 plans must reproduce the fp64 oracle BIT FOR BIT -- at any batch size, on every kernel set.  A single wrong
+element anywhere (a dropped 16-window tile, a mis-indexed 32-feature column slice) is then a failure, where the bf16 plan's tolerance tests
+(tests/test_bf16_emulation.py, 1.5e-2 L2) cannot see it.
+
+`check_exact` proves the three preconditions on the host before it hands out the fp64 reference:
+  (a) bf16 closure: the rounding-point emulation with and without rounding and the oracle agree bit for bit, and every activation and activation gradient
+      of the kernels' algebra is a bf16 value (so a storage point the emulation does not model rounds nothing either);
+  (b) fp32 closure: for every accumulation the sum of the absolute values of its terms fits in 2^24 units of the finest dyadic grid of its terms;
+  (c) coverage: every gradient tensor that is live on random data is non-zero, every 32-feature column slice of every live X_l holds non-zero values,
+      and every layer has exact-zero relu pre-activations (relu'(0) = 0 is exercised).
+"""
+import math
+
+import numpy as np
+import torch
+
+from morphsym_hgnn_amd.spec import rel_key
+from oracle import ms_hgnn_oracle as orc
+from tests import helpers
+from tests.bf16_emulation import emulate_step
+
+GOUT_EXP = -14          # output gradients are k * 2^GOUT_EXP, |k| <= gout_range
+
+
+# ---------------------------------------------------------------------------------------------------
+# generator
+# ---------------------------------------------------------------------------------------------------
+def _signed_rows(g, out_f, in_f, scales, density=1.0):
+    """[out_f, in_f] with at most one entry per row (a row holds one with probability `density`): a random column, a random sign, a scale drawn from
+    `scales`."""
+    w = torch.zeros(out_f, in_f, dtype=torch.float64)
+    cols = torch.randint(0, in_f, (out_f,), generator=g)
+    sign = torch.randint(0, 2, (out_f,), generator=g).double() * 2 - 1
+    sc = torch.tensor(scales, dtype=torch.float64)[torch.randint(0, len(scales), (out_f,), generator=g)]
+    keep = (torch.rand(out_f, generator=g, dtype=torch.float64) < density).double()
+    w[torch.arange(out_f), cols] = sign * sc * keep
+    return w
+
+
+def exact_case(spec, B, seed, x_range=2, bias_range=(-1, 1), rel_scales=(0.5, 1.0), density=1.0, per_matrix=False, gout_range=2, mse=None):
+    """Rounding-free inputs, parameters and output gradient for `spec` at batch size B.
+    Returns a dict: x (reference convention, fp64 [B*n_t, F_t]), params, gout (fp64 [B*n_out*d], k * 2^-14), and for the one-call MSE step (mse=True, default
+    for regression models) y (fp32-exact targets) and gout_mse: the gradient the fused MSE computes from them, 2 (out - y) * fl32(1 / N) evaluated in fp32,
+    every element a short dyadic number (`_mse_targets`)."""
+    g = torch.Generator().manual_seed(seed)
+    params = {}
+    for name, shape in spec.param_shapes().items():
+        if len(shape) == 2:
+            rel = ".lin_rel." in name or ".lin_root." in name
+            sc = (rel_scales[int(torch.randint(0, len(rel_scales), (1,), generator=g))],) if (rel and per_matrix) else (rel_scales if rel else (1.0,))
+            params[name] = _signed_rows(g, shape[0], shape[1], sc, 1.0 if name.startswith(("encoder.", "decoder.")) else density)
+        else:
+            params[name] = torch.randint(bias_range[0], bias_range[1] + 1, shape, generator=g).double()
+    x = {t: torch.randint(-x_range, x_range + 1, (B * spec.num_nodes[t], spec.widths[t]), generator=g).double() for t in spec.node_types}
+    n = B * spec.num_nodes[spec.out_type] * spec.out_channels
+    gout = torch.randint(-gout_range, gout_range + 1, (n,), generator=g).double() * 2.0 ** GOUT_EXP
+    case = dict(spec=spec, B=B, seed=seed, x=x, params=params, gout=gout, y=None, gout_mse=None)
+    if mse if mse is not None else spec.regression:
+        out = reference(spec, case)["out"]
+        case["y"], case["gout_mse"] = _mse_targets(out, seed, gout_range)
+    return case
+
+
+def _mse_targets(out, seed, gout_range):
+    """Targets y for the fused MSE gradient 2 * (out - y) * inv_n (fp32, left to right, inv_n = fl32(1 / N): csrc/mshgnn.hip, the decoder-backward step
+    arguments).  Per element a wanted gradient k 2^-14 (|k| <= gout_range, drawn) and the fp32 targets near out - k N 2^-15 (that one and its neighbours,
+    a few ulps either way): the first whose fp32 formula, evaluated on the host as the kernels evaluate it, gives exactly k 2^-14 is kept (none: the
+    element keeps y = out, gradient 0).  The oracle is handed those gradients."""
+    f32 = np.float32
+    o = out.reshape(-1).numpy()
+    N = o.size
+    inv_n = f32(1.0) / f32(N)
+    o32 = o.astype(f32)
+    assert np.array_equal(o32.astype(np.float64), o), "the output is not an fp32 value"
+    rng = np.random.Generator(np.random.PCG64(seed + 977))
+    want = rng.integers(-gout_range, gout_range + 1, size=N).astype(np.float64) * 2.0 ** GOUT_EXP
+    base = (o - want * N / 2.0).astype(f32)
+    y, go, done = o32.copy(), np.zeros(N), want == 0
+    for m in (0, 1, -1, 2, -2, 3, -3, 4, -4, 5, -5, 6, -6, 7, -7, 8, -8):
+        ym = base
+        for _ in range(abs(m)):
+            ym = np.nextafter(ym, f32(np.inf) if m > 0 else f32(-np.inf))
+        r = (f32(2.0) * (o32 - ym) * inv_n).astype(np.float64)
+        ok = ~done & (r == want)
+        y[ok], go[ok] = ym[ok], r[ok]
+        done |= ok
+    return torch.from_numpy(y.astype(np.float64)), torch.from_numpy(go)
+
+
+# ---------------------------------------------------------------------------------------------------
+# fp64 reference (the oracle, plain torch.relu)
+# ---------------------------------------------------------------------------------------------------
+def reference(spec, case, gout=None):
+    """The oracle's output, hidden states X_0..X_L ([B, NN, h] in the engine's node order), parameter gradients for output gradient `gout` and, when the
+    case has targets, the MSE loss."""
+    B = case["B"]
+    cfg = helpers.oracle_config(spec)
+    leaves = {k: v.clone().requires_grad_(True) for k, v in case["params"].items()}
+    out, hidden = orc.forward(cfg, leaves, {k: v.clone() for k, v in case["x"].items()}, spec.topology.edge_index_dict(B), return_hidden=True)
+    res = {"out": out.detach().reshape(-1).clone(), "hidden": [helpers.dense_hidden(spec, {t: v.detach() for t, v in h.items()}, B) for h in hidden]}
+    if gout is not None:
+        out.backward(gout.reshape(out.shape))
+        res["grads"] = {k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in leaves.items()}
+    if case.get("y") is not None:
+        res["loss"] = float(((res["out"] - case["y"]) ** 2).mean())
+    return res
+
+
+# ---------------------------------------------------------------------------------------------------
+# the kernels' algebra (tests/bf16_emulation.py's restructuring, no rounding), with its intermediates
+# ---------------------------------------------------------------------------------------------------
+def _kernel_algebra(spec, P, x_dict, B, relu_masks=None, reseed=None):
+    """Forward of the kernels' algebra (root weights pre-summed per destination type, relation sums per edge) in fp64.  relu_masks=None: relu decisions
+    from the values (recorded); otherwise the given decisions.  Returns (out [B*n_out*d], intermediates {name: tensor (grad retained)}, masks, zero counts)."""
+    inter, masks, zeros = {}, {}, {}
+    nn_ = spec.num_nodes
+
+    def keep(name, v):
+        if reseed is not None:
+            return _Reseed.apply(v, name, reseed)
+        v.retain_grad()
+        inter[name] = v
+        return v
+
+    def relu(key, h):
+        if relu_masks is None:
+            m = h.detach() > 0
+            masks[key] = m
+            zeros[key] = int((h.detach() == 0).sum())
+        else:
+            m = relu_masks[key]
+        return h * m.to(h.dtype)
+
+    im = spec.input_masks()
+    X = {}
+    for t in spec.node_types:
+        x = x_dict[t].view(B, nn_[t], -1) * im[t].unsqueeze(0)
+        pre = keep(f"enc.{t}", x @ P[f"encoder.lins.{t}.weight"].t() + P[f"encoder.lins.{t}.bias"])
+        X[t] = keep(f"X0.{t}", relu(("enc", t), pre))
+    for l in range(spec.num_layers):
+        new = {}
+        for t in spec.live_types(l):
+            rels = [et for et in spec.edge_types if et[2] == t]
+            w_root = keep(f"wroot{l}.{t}", sum(P[f"convs.{l}.convs.{rel_key(et)}.lin_root.weight"] for et in rels))
+            H = X[t] @ w_root.t() + sum(P[f"convs.{l}.convs.{rel_key(et)}.lin_rel.bias"] for et in rels)
+            for et in rels:
+                e = spec.topology.edges(et)
+                if not e:
+                    continue
+                js = torch.tensor([j for j, _ in e]); is_ = torch.tensor([i for _, i in e])
+                H = H.index_add(1, is_, X[et[0]][:, js, :] @ P[f"convs.{l}.convs.{rel_key(et)}.lin_rel.weight"].t())
+            H = keep(f"H{l}.{t}", H)
+            if spec.has_base_transform and t == "base":
+                t1 = keep(f"T1pre{l}", H @ P["base_transform.0.weight"].t() + P["base_transform.0.bias"])
+                t1 = keep(f"T1{l}", relu(("t1", l), t1))
+                Y = keep(f"Y{l}", t1 @ P["base_transform.2.weight"].t() + P["base_transform.2.bias"])
+            else:
+                Y = keep(f"Y{l}.{t}", relu(("layer", l, t), H))
+            new[t] = keep(f"X{l + 1}.{t}", Y + X[t] if spec.residual else Y)
+        for t in spec.node_types:
+            new.setdefault(t, X[t])
+        X = new
+    out = X[spec.out_type] @ P["decoder.weight"].t() + P["decoder.bias"]
+    out = (out * spec.output_mask().unsqueeze(0)).reshape(-1)
+    return out, inter, masks, zeros
+
+
+class _Reseed(torch.autograd.Function):
+    """Sums of |terms|, one accumulation at a time: the absolute-value run of the kernels' algebra records what arrives here (forward: the sum of |terms|
+    of this intermediate's accumulation over the REAL operands' magnitudes; backward: the same for its gradient) and passes the real magnitudes on."""
+    @staticmethod
+    def forward(ctx, v, name, rs):
+        ctx.name, ctx.rs = name, rs
+        rs["fwd"][name] = float(v.max())
+        return rs["val"][name].abs().clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        ctx.rs["bwd"][ctx.name] = float(g.max())
+        real = ctx.rs["grad"][ctx.name]
+        return (real.abs() if real is not None else torch.zeros_like(g)), None, None
+
+
+def lsb_exponent(t):
+    """Smallest exponent e such that every non-zero element of `t` is an integer multiple of 2^e (+inf for an all-zero tensor)."""
+    t = t.detach().double().reshape(-1)
+    t = t[t != 0]
+    if t.numel() == 0:
+        return math.inf
+    m, e = torch.frexp(t)
+    mi = (m.abs() * 2.0 ** 53).long()
+    tz = torch.log2((mi & -mi).double()).long()
+    return int((e.long() - 53 + tz).min())
+
+
+def bf16_exact(t):
+    t = t.detach().double()
+    return bool(torch.equal(t.to(torch.bfloat16).double(), t))
+
+
+# ---------------------------------------------------------------------------------------------------
+# comparison
+# ---------------------------------------------------------------------------------------------------
+def first_difference(got, ref):
+    """None when `got` (any float dtype, any device) equals `ref` bit for bit after .double() (-0.0 == 0.0), else a description of the first differing
+    element and how many differ."""
+    got = got.detach().double().cpu().reshape(ref.shape)
+    ref = ref.detach().double().cpu()
+    if torch.equal(got, ref):
+        return None
+    bad = (got != ref) | (torch.isnan(got) != torch.isnan(ref))
+    idx = tuple(int(i) for i in bad.nonzero()[0])
+    return f"{int(bad.sum())} of {ref.numel()} elements differ; first at {idx}: got {float(got[idx])!r}, reference {float(ref[idx])!r}"
+
+
+def locate(idx, what):
+    """Where a hidden-state index (window, node, feature) sits in the kernels' tiling."""
+    w, n, f = idx
+    return f"{what}: window {w} (tile {w // 16}), node {n}, feature {f} (column slice {f // 32})"
+
+
+# ---------------------------------------------------------------------------------------------------
+# the preconditions
+# ---------------------------------------------------------------------------------------------------
+def _live_nonzero_in_random_case(spec):
+    """Gradient tensors that are non-zero for helpers.random_case at this spec (4 windows: which tensors are live depends on the model, not the batch)."""
+    x, y, params = helpers.random_case(spec, 4, seed=1)
+    _, _, grads = orc.step(helpers.oracle_config(spec), params, x, spec.topology.edge_index_dict(4), y, 4)
+    return {k for k, g in grads.items() if float(g.abs().max()) > 0}
+
+
+def check_exact(spec, case, gout=None, stats=None):
+    """The fp64 reference for `case` with output gradient `gout` (default: the case's `gout_mse` when it has targets, else its `gout`), after asserting
+    the preconditions (a) bf16 closure, (b) fp32 closure and (c) coverage (module docstring).  `stats`: a dict that receives what was measured."""
+    B = case["B"]
+    if gout is None:
+        gout = case["gout_mse"] if case.get("gout_mse") is not None else case["gout"]
+    stats = {} if stats is None else stats
+    ref = reference(spec, case, gout)
+    go = gout.clone()
+
+    # (a) bf16 closure: emulation with and without rounding and the oracle, bit for bit
+    def lg(out):
+        return (out.reshape(-1) * go).sum()
+    for quant in (True, False):
+        e_out, _, e_grads = emulate_step(spec, case["params"], case["x"], None, B, quant=quant, loss_grad=lg)
+        d = first_difference(e_out.reshape(-1), ref["out"])
+        assert d is None, f"(a) emulation (quant={quant}) output != oracle: {d}"
+        for k, gr in ref["grads"].items():
+            d = first_difference(e_grads[k], gr)
+            assert d is None, f"(a) emulation (quant={quant}) gradient {k} != oracle (mean aggregation over in-degree != 1, or a rounding): {d}"
+
+    # the kernels' algebra: real values (decisions, intermediates), then absolute values under the same decisions (sums of |terms|)
+    P = {k: v.clone().requires_grad_(True) for k, v in case["params"].items()}
+    out, inter, masks, zeros = _kernel_algebra(spec, P, case["x"], B)
+    assert torch.equal(out.detach(), ref["out"]), "the kernels' algebra != oracle"
+    out.backward(go)
+    for name, v in inter.items():
+        if name.startswith("wroot"):
+            continue
+        if name.startswith("X") or (name.startswith("T1") and not name.startswith("T1pre")):      # (the others are fp32 accumulators)
+            assert bf16_exact(v), f"(a) activation {name} is not a bf16 value"
+        if v.grad is not None:
+            assert bf16_exact(v.grad), f"(a) activation gradient d{name} is not a bf16 value"
+    # (b) fp32 closure
+    acts = [case["x"][t] for t in spec.node_types] + [v for v in inter.values()]
+    weights = [v for k, v in case["params"].items() if v.dim() == 2] + [v for k, v in inter.items() if k.startswith("wroot")]
+    biases = [v for v in case["params"].values() if v.dim() == 1]
+    agrads = [go] + [v.grad for k, v in inter.items() if v.grad is not None and not k.startswith("wroot")]
+    e_act, e_w, e_b, e_g = (min(lsb_exponent(t) for t in ts) for ts in (acts, weights, biases, agrads))
+    grid_f = min(e_act + e_w, e_b)                   # forward: activation x weight products, biases
+    grid_b = e_g + min(e_w, e_act, 0)                # backward: gradient x weight (activation gradients), gradient x activation (weight gradients), bias sums
+    Pa = {k: v.abs().clone().requires_grad_(True) for k, v in case["params"].items()}
+    rs = {"fwd": {}, "bwd": {}, "val": {k: v.detach() for k, v in inter.items()}, "grad": {k: v.grad for k, v in inter.items()}}
+    out_a, _, _, _ = _kernel_algebra(spec, Pa, {t: v.abs() for t, v in case["x"].items()}, B, relu_masks=masks, reseed=rs)
+    out_a.backward(go.abs())
+    fwd_max = max([float(out_a.detach().max())] + list(rs["fwd"].values()))
+    bwd_max = max(list(rs["bwd"].values()) + [float(v.grad.max()) for v in Pa.values() if v.grad is not None])
+    stats.update(fwd_sum_bound=fwd_max / 2.0 ** (24 + grid_f), bwd_sum_bound=bwd_max / 2.0 ** (24 + grid_b))
+    assert fwd_max <= 2.0 ** (24 + grid_f), f"(b) a forward sum of |terms| {fwd_max} exceeds 2^24 units of 2^{grid_f}"
+    assert bwd_max <= 2.0 ** (24 + grid_b), f"(b) a backward sum of |terms| {bwd_max} exceeds 2^24 units of 2^{grid_b}"
+
+    # (c) coverage
+    live_random = _live_nonzero_in_random_case(spec)
+    dead_here = sorted(k for k in live_random if float(ref["grads"][k].abs().max()) == 0)
+    assert not dead_here, f"(c) gradients live on random data are zero here: {dead_here}"
+    liv, need = spec.node_liveness()
+    sl = helpers.node_slices(spec)
+    for l, X in enumerate(ref["hidden"]):
+        nodes = need[0] if l == 0 else liv[l - 1]
+        for t in spec.node_types:
+            for n in nodes[t]:
+                xn = X[:, sl[t].start + n]
+                for c in range(0, xn.shape[-1], 32):      # (a width that is not a multiple of 32: a ragged last slice)
+                    assert bool((xn[:, c:c + 32] != 0).any()), f"(c) X{l} {t} node {n}: column slice {c // 32} is all zero"
+    per_layer = {}
+    for key, z in zeros.items():
+        per_layer[key[1] if key[0] != "enc" else -1] = per_layer.get(key[1] if key[0] != "enc" else -1, 0) + z
+    for l in [-1] + list(range(spec.num_layers)):
+        assert per_layer.get(l, 0) > 0, f"(c) no exact-zero relu pre-activation in {'the encoder' if l < 0 else f'layer {l}'}"
+    stats.update(zero_decisions=sum(zeros.values()), nonzero_grads=sum(1 for g in ref["grads"].values() if float(g.abs().max()) > 0),
+                 grads=len(ref["grads"]), nonzero_gout=int((go != 0).sum()), gout=go.numel())
+    ref["gout"] = go
+    return ref
