@@ -197,7 +197,10 @@ int mshgnn_forward(const mshgnn_plan* plan, const void* const* x, const int64_t*
 
 /* Backward of the forward that last ran on `workspace` with the same x/params.  grad_out: device fp32
  * [batch][n_out][out_channels] (dL/d out).  grad_params: device fp32 flat buffer, fully OVERWRITTEN with
- * dL/d params (parameters that cannot influence the output get exact zeros).                            */
+ * dL/d params (parameters that cannot influence the output get exact zeros).
+ * grad_params == NULL (here and on mshgnn_backward_mse / _ce): activation backward only -- the backward sweep runs and leaves the encoder's
+ * dY in the workspace for mshgnn_input_grad, the weight-gradient and finalize launches are skipped (frozen parameters; _mse / _ce still write
+ * loss_out).                                                                                            */
 int mshgnn_backward(const mshgnn_plan* plan, const void* const* x, const int64_t* x_pitch, const float* params,
                     const float* grad_out, float* grad_params, void* workspace, int64_t batch, void* stream);
 
@@ -238,6 +241,16 @@ int mshgnn_step_mse_phase(const mshgnn_plan* plan, const void* const* x, const i
 int mshgnn_backward_ce(const mshgnn_plan* plan, const void* const* x, const int64_t* x_pitch, const float* params,
                        const float* out, const int32_t* labels, float* loss_out, float* grad_params, void* workspace,
                        int64_t batch, void* stream);
+
+/* Gradients with respect to the INPUTS (torch.autograd on the reference's x_dict leaves, hgnn_c2.py:150-151 + apply_symmetry): after a training
+ * forward and mshgnn_backward / _mse / _ce (grad_params may be NULL) on the same workspace and batch,
+ *   dx[t][w n_t + i][f] = in_mask[t][i][f] . sum_j dY_enc[w, node i of type t][j] W_enc[t][j][f]
+ * for every type with dx[t] != NULL (NULL: skipped), written at dx_pitch[t] elements per row (NULL pitch array = dense F_t) as fp32 (dx_bytes 4) or fp64
+ * (dx_bytes 8; any other value: MSHGNN_EUNSUPPORTED).  Rows of nodes the plan does not compute (they cannot reach the output at this depth) and pad
+ * columns [F_t, pitch) are exact zeros.  One launch; arithmetic per plan (fp32 MFMA / bf16 operands / split-bf16 hi-lo products, fp32 accumulation),
+ * every element one K sum in one workgroup: deterministic.  params: the flat fp32 buffer of that forward.                               */
+int mshgnn_input_grad(const mshgnn_plan* plan, const float* params, void* const* dx, const int64_t* dx_pitch, int dx_bytes, const void* workspace,
+                      int64_t batch, void* stream);
 
 /* Adam on the flat fp32 buffers (configure_optimizers, gnnLightning.py:258-265; torch.optim.Adam defaults, no weight
  * decay / amsgrad).  step is 1-based; grads are multiplied by grad_scale first (1/world_size after a sum all-reduce).

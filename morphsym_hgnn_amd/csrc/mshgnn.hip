@@ -2411,6 +2411,7 @@ __global__ __launch_bounds__(256) void k_finalize(FinArgs a) {
         for (int m = 32; m >= 1; m >>= 1) l += __shfl_xor(l, m, 64);
         if (threadIdx.x == 0) *a.loss = l * a.inv_n + (a.accumulate ? *a.loss : 0.f);      // (accumulate: a later sub-step of a chunked step, mshgnn_device.hpp StepChunk)
     }
+    if (!a.grad) return;      // (the loss alone: a backward without parameter gradients)
     const bool is_mat = (kind == FIN_MATRIX || kind == FIN_DEC_W);
     if (kind == FIN_DEC_W || kind == FIN_DEC_B) {
         // decoder partials: NWG_DEC slabs per element -> one WAVE per element, 8 slabs per lane in flight, then a fixed
@@ -2604,6 +2605,7 @@ extern "C" void mshgnn_plan_destroy(mshgnn_plan* p) {
     if (p->d_out_mask) (void)hipFree(p->d_out_mask);
     if (p->d_packs) (void)hipFree(p->d_packs);
     if (p->d_biases) (void)hipFree(p->d_biases);
+    if (p->d_ig_nodes) (void)hipFree(p->d_ig_nodes);
     for (ProfRec& r : p->recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
     for (hipEvent_t e : p->free_events) (void)hipEventDestroy(e);
     delete p;
@@ -2679,6 +2681,11 @@ int run_finalize(const mshgnn_plan* p, const mshgnn_ws_layout& lay, char* ws, fl
     if (gw_phase == 0) nf = hp.n_fin_ph0;
     if (gw_phase == 1) { f0 = hp.n_fin_ph0; nf = hp.n_fin - hp.n_fin_ph0; a.loss = nullptr; }
     a.fin += (size_t)f0 * FIN_INTS;
+    if (!gparams) {      // activation backward only: no gradient to finalize, one workgroup for the fused loss (if any)
+        if (loss) hipLaunchKernelGGL(k_finalize, dim3(1, 1), dim3(256), 0, st, a);
+        HIPCHK(hipGetLastError());
+        return MSHGNN_OK;
+    }
     ProfScope ps(p, hp.ks_fin, st);
     if (nf > 0) hipLaunchKernelGGL(k_finalize, dim3(nf, 64), dim3(256), 0, st, a);
     HIPCHK(hipGetLastError());
@@ -2917,7 +2924,7 @@ static int backward_impl(const mshgnn_plan* p, const void* const* x, const int64
         hipLaunchKernelGGL(k_layer_bwd<T>, dim3(tiles), dim3(LAYER_THREADS), hp.n_blk * Prec<T>::BLK, st, a);
     }
     const int gw_parts = gw_parts_for(hp.n_parts, hp.n_lanes, hp.gw_ipl, B, sizeof(T) == 4 ? GW_KW : GWB_KW, p->n_cu);      // window parts of this batch's weight-gradient launch (<= the plan's)
-    {
+    if (gparams) {      // (NULL: activation backward only -- dX_0 for mshgnn_input_grad, no weight gradients)
         GradwArgs a{};
         a.ws = ws;
         for (int l = 0; l <= hp.L; ++l) { a.buf_off[BUF_X + l] = lay.x[l]; a.buf_off[BUF_DX + l] = lay.dx[l]; }
@@ -2969,7 +2976,7 @@ extern "C" int mshgnn_forward(const mshgnn_plan* p, const void* const* x, const 
 
 extern "C" int mshgnn_backward(const mshgnn_plan* p, const void* const* x, const int64_t* x_pitch, const float* params, const float* grad_out,
                                float* grad_params, void* workspace, int64_t batch, void* stream) {
-    if (!p || !x || !params || !grad_out || !grad_params || !workspace) return set_err(MSHGNN_EINVAL, "null argument to mshgnn_backward");
+    if (!p || !x || !params || !grad_out || !workspace) return set_err(MSHGNN_EINVAL, "null argument to mshgnn_backward");
     if (batch < 1 || batch > (1 << 24)) return set_err(MSHGNN_EINVAL, "batch must be in [1, 2^24]");
     if (p->gen) return gen_backward(p, x, x_pitch, params, grad_out, grad_params, (char*)workspace, batch, (hipStream_t)stream, nullptr, nullptr, nullptr, nullptr);
     if (p->hp.d.dtype == MSHGNN_BF16X3) return x3_backward(p, x, x_pitch, params, grad_out, grad_params, (char*)workspace, batch, (hipStream_t)stream, nullptr, nullptr, nullptr, nullptr, false, -1);
@@ -2979,7 +2986,7 @@ extern "C" int mshgnn_backward(const mshgnn_plan* p, const void* const* x, const
 
 extern "C" int mshgnn_backward_mse(const mshgnn_plan* p, const void* const* x, const int64_t* x_pitch, const float* params, const float* out,
                                    const float* y, float* loss_out, float* grad_params, void* workspace, int64_t batch, void* stream) {
-    if (!p || !x || !params || !out || !y || !loss_out || !grad_params || !workspace) return set_err(MSHGNN_EINVAL, "null argument to mshgnn_backward_mse");
+    if (!p || !x || !params || !out || !y || !loss_out || !workspace) return set_err(MSHGNN_EINVAL, "null argument to mshgnn_backward_mse");
     if (batch < 1 || batch > (1 << 24)) return set_err(MSHGNN_EINVAL, "batch must be in [1, 2^24]");
     if (p->gen) return gen_backward(p, x, x_pitch, params, nullptr, grad_params, (char*)workspace, batch, (hipStream_t)stream, out, y, loss_out, nullptr);
     if (p->hp.d.dtype == MSHGNN_BF16X3) return x3_backward(p, x, x_pitch, params, nullptr, grad_params, (char*)workspace, batch, (hipStream_t)stream, out, y, loss_out, nullptr, false, -1);
@@ -3153,7 +3160,7 @@ extern "C" int mshgnn_step_mse_phase(const mshgnn_plan* p, const void* const* x,
 
 extern "C" int mshgnn_backward_ce(const mshgnn_plan* p, const void* const* x, const int64_t* x_pitch, const float* params, const float* out,
                                   const int32_t* labels, float* loss_out, float* grad_params, void* workspace, int64_t batch, void* stream) {
-    if (!p || !x || !params || !out || !labels || !loss_out || !grad_params || !workspace) return set_err(MSHGNN_EINVAL, "null argument to mshgnn_backward_ce");
+    if (!p || !x || !params || !out || !labels || !loss_out || !workspace) return set_err(MSHGNN_EINVAL, "null argument to mshgnn_backward_ce");
     if (batch < 1 || batch > (1 << 24)) return set_err(MSHGNN_EINVAL, "batch must be in [1, 2^24]");
     if (p->hp.d.out_channels != 2) return set_err(MSHGNN_EINVAL, "mshgnn_backward_ce needs a 2-logit (contact classification) plan");
     if (p->gen) return gen_backward(p, x, x_pitch, params, nullptr, grad_params, (char*)workspace, batch, (hipStream_t)stream, out, nullptr, loss_out, labels);

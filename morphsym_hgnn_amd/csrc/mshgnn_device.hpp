@@ -1299,6 +1299,7 @@ struct mshgnn_plan {
     std::vector<hipEvent_t> free_events;
     int* d_tables = nullptr; uint8_t* d_signs = nullptr; float* d_out_mask = nullptr;
     PackDesc* d_packs = nullptr; BiasDesc* d_biases = nullptr;
+    int* d_ig_nodes = nullptr;          // mshgnn_input_grad: {plan node, sign offset | -1} per (type, node), from the encoder's weight-gradient items (uploaded on first use)
     bool attr_set = false;
     bool use_fused = false;             // bf16 plan: fused stack kernels (MSHGNN_FUSED=0 selects the per-layer kernels)
     bool use_slab = false;              // slab variant of the stack kernels (MSHGNN_SLAB=0 selects the 8-wave ones)
@@ -1398,6 +1399,9 @@ int launch_prep(const PrepArgs& a, bool split, hipStream_t st);
 int gen_create(mshgnn_plan* p, const mshgnn_desc* desc);
 void gen_destroy(mshgnn_plan* p);
 const mshgnn_info* gen_info(const mshgnn_plan* p);
+namespace mshgnn { namespace gen { struct GenPlan; } }
+const mshgnn::gen::GenPlan* gen_plan(const mshgnn_plan* p);      // (mshgnn_input_grad.hip reads the generic plan's tables)
+const uint8_t* gen_signs(const mshgnn_plan* p);
 const std::vector<mshgnn_kernel_stat>* gen_kstats(const mshgnn_plan* p);
 void gen_layout(const mshgnn_plan* p, int64_t batch, int training, mshgnn_ws_layout* out);
 int gen_host_compile(const mshgnn_desc* desc, mshgnn_info* info, int32_t* n_tables);

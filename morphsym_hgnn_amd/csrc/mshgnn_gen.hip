@@ -1335,6 +1335,7 @@ __global__ __launch_bounds__(256) void k_gfinalize(GFinArgs a) {
         for (int m = 32; m >= 1; m >>= 1) l += __shfl_xor(l, m, 64);
         if (threadIdx.x == 0) *a.loss = l * a.inv_n;
     }
+    if (!a.grad) return;      // (the loss alone: a backward without parameter gradients)
     if (kind == FIN_DEC_W || kind == FIN_DEC_B) {      // one decoder row piece: f[8] = its offset inside a decoder slab
         // one WAVE per element, elements dealt round-robin to the (gridDim.y x 4) waves of this op (four waves per op walked 32 elements each, one dependent round
         // trip per element: ~100 us, the tail of the whole launch)
@@ -1438,6 +1439,8 @@ void gen_destroy(mshgnn_plan* p) {
 }
 
 const mshgnn_info* gen_info(const mshgnn_plan* p) { return &p->gen->gp.info; }
+const GenPlan* gen_plan(const mshgnn_plan* p) { return &p->gen->gp; }
+const uint8_t* gen_signs(const mshgnn_plan* p) { return p->gen->d_signs; }
 const std::vector<mshgnn_kernel_stat>* gen_kstats(const mshgnn_plan* p) { return &p->gen->gp.kstats; }
 void gen_layout(const mshgnn_plan* p, int64_t batch, int training, mshgnn_ws_layout* out) { layout_gen_workspace(p->gen->gp, batch, training, out); }
 int gen_host_compile(const mshgnn_desc* desc, mshgnn_info* info, int32_t* n_tables) {
@@ -1725,6 +1728,15 @@ int gen_backward(const mshgnn_plan* p, const void* const* x, const int64_t* x_pi
     int rc = g_fill(p, lay, x, x_pitch, ws, B, 1, a);
     if (rc) return rc;
     for (const Launch& ln : gp.bwd) g_launch_jobs(p, ln, a, st);
+    if (!gparams) {      // activation backward only (dX_0 for mshgnn_input_grad): no weight gradients; one workgroup for the fused loss (if any)
+        if (y || labels) {
+            GFinArgs fa{g->d_tables + gp.fin_off, reinterpret_cast<const float*>(ws + lay.slabs), reinterpret_cast<const float*>(ws + lay.dec_slabs), nullptr,
+                        gp.n_units, gp.n_parts, gp.Hd, loss, 1.0f / (float)((int64_t)B * n_out * (labels ? 1 : d.out_channels))};
+            hipLaunchKernelGGL(k_gfinalize, dim3(1, 1), dim3(256), 0, st, fa);
+        }
+        HIPCHK(hipGetLastError());
+        return MSHGNN_OK;
+    }
     {
         ProfScope ps(p, gp.ks_gradw, st);
         const unsigned grid = (unsigned)gp.n_sunits * gp.n_parts;

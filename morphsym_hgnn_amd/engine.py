@@ -83,6 +83,7 @@ EXPORTS = [
     "mshgnn_step_mse_series", "mshgnn_step_ce_series", "mshgnn_step_ce", "mshgnn_op_gemm", "mshgnn_op_gemm_workspace", "mshgnn_op_aggregate", "mshgnn_op_colsum", "mshgnn_op_colsum_workspace",
     "mshgnn_abi_version", "mshgnn_struct_size", "mshgnn_forward_src", "mshgnn_step_mse_src", "mshgnn_step_ce_src",
     "mshgnn_comm_unique_id", "mshgnn_comm_create", "mshgnn_comm_destroy", "mshgnn_comm_allreduce_mean", "mshgnn_comm_allreduce_sum",
+    "mshgnn_input_grad",
 ]
 ABI_VERSION = 6      # include/mshgnn.h MSHGNN_ABI_VERSION: the ctypes structures above mirror THAT header
 
@@ -172,6 +173,8 @@ def load_library():
     lib.mshgnn_forward_src.argtypes = src6 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
     lib.mshgnn_step_mse_src.argtypes = src6 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     lib.mshgnn_step_ce_src.argtypes = src6 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    if hasattr(lib, "mshgnn_input_grad"):
+        lib.mshgnn_input_grad.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
     lib.mshgnn_struct_size.restype = C.c_size_t
     lib.mshgnn_struct_size.argtypes = [C.c_int]
     lib.mshgnn_comm_unique_id.argtypes = [C.c_char_p, C.c_void_p]
@@ -364,6 +367,7 @@ class Engine:
         self._tickets: Dict[int, int] = {}
         self._chunked: Dict[int, bool] = {}      # batch size -> the last training call on it was a one-call step (which the library may run as sub-steps)
         self._rows_gen: Dict[int, int] = {}      # batch size -> how many times the encoder has written the engine's input row buffers of that size
+        self._bwd_ticket: Dict[int, int] = {}    # batch size -> the stash ticket its last backward ran on (what input_grad reads)
         self._lay: Dict[Tuple[int, int], MshgnnWsLayout] = {}
         self._rows: Dict[int, List[torch.Tensor]] = {}      # plan-dtype input rows the encoder materialises from wide source tensors (WideInputs)
         self._pending_wide: Optional[WideInputs] = None     # the last WideInputs handed out whose rows have not been materialised yet
@@ -553,13 +557,17 @@ class Engine:
         return out
 
     def backward(self, xs: Sequence[torch.Tensor], params_flat: torch.Tensor, grad_out: torch.Tensor, B: int,
-                 grad_flat: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 grad_flat: Optional[torch.Tensor] = None, weights: bool = True) -> Optional[torch.Tensor]:
+        """weights=False: activation backward only (frozen parameters) -- the sweep leaves the encoder's dY for `input_grad`, no weight-gradient or
+        finalize launch runs and None is returned."""
         self._check_rows_fresh(xs, B)
         self._check_flat(params_flat, "params_flat")
         ptrs, pitch = self._xptrs(xs, B)
         if grad_out.dtype != torch.float32 or not grad_out.is_contiguous() or grad_out.numel() != B * self.n_out * self.spec.out_channels:
             raise ValueError("grad_out must be contiguous fp32 with B*n_out*out_channels elements")
-        if grad_flat is None:
+        if not weights:
+            grad_flat = None
+        elif grad_flat is None:
             grad_flat = torch.empty(self.spec.flat_size(), dtype=torch.float32, device=self.device)
         else:
             self._check_flat(grad_flat, "grad_flat")
@@ -567,8 +575,39 @@ class Engine:
         stream = torch.cuda.current_stream(self.device).cuda_stream
         with torch.cuda.device(self.device):
             _check(self.lib, self.lib.mshgnn_backward(self._plan, ptrs, pitch, params_flat.data_ptr(), grad_out.data_ptr(),
-                                                  grad_flat.data_ptr(), ws.data_ptr(), B, stream), "mshgnn_backward")
+                                                  grad_flat.data_ptr() if grad_flat is not None else None, ws.data_ptr(), B, stream), "mshgnn_backward")
+        self._bwd_ticket[B] = self._tickets.get(B, 0)
         return grad_flat
+
+    def input_grad(self, B: int, params_flat: torch.Tensor, types: Optional[Sequence[str]] = None, dtype: torch.dtype = torch.float32,
+                   pitches: Optional[Dict[str, int]] = None) -> Dict[str, torch.Tensor]:
+        """Gradients with respect to the inputs of the training forward whose backward (`backward` / `backward_mse` / `backward_ce`) last ran on batch
+        size B (mshgnn_input_grad): {type: [B * n_t, pitch] tensor of `dtype` (fp32 or fp64)} for the requested types (default: all), pitch = the
+        reference's width F_t unless `pitches` names another (>= F_t; the columns past F_t are exact zeros).  Rows of nodes the plan does not compute
+        are exact zeros, as the reference's autograd gives them.  params_flat: the flat buffer of that forward."""
+        if dtype not in (torch.float32, torch.float64):
+            raise ValueError("input_grad writes fp32 or fp64 gradients")
+        self._check_flat(params_flat, "params_flat")
+        if self._bwd_ticket.get(B) is None or self._bwd_ticket[B] != self._tickets.get(B, 0):
+            raise RuntimeError("the activation stash of this forward was overwritten by a later forward of the same "
+                               "batch size on the same engine; call backward before the next forward")
+        self._stash_is_whole(B)
+        types = list(self.types) if types is None else list(types)
+        n = len(self.types)
+        ptrs, pitch = (C.c_void_p * n)(), (C.c_int64 * n)()
+        out = {}
+        for i, t in enumerate(self.types):
+            P = int((pitches or {}).get(t, self.spec.widths[t]))
+            pitch[i] = P
+            if t in types:
+                out[t] = torch.empty(B * self.spec.num_nodes[t], P, dtype=dtype, device=self.device)
+                ptrs[i] = out[t].data_ptr()
+        ws = self.workspace(B, True)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        with torch.cuda.device(self.device):
+            _check(self.lib, self.lib.mshgnn_input_grad(self._plan, params_flat.data_ptr(), ptrs, pitch, 8 if dtype == torch.float64 else 4,
+                                                        ws.data_ptr(), B, stream), "mshgnn_input_grad")
+        return out
 
     def backward_mse(self, xs: Sequence[torch.Tensor], params_flat: torch.Tensor, out: torch.Tensor, y: torch.Tensor, B: int,
                      grad_flat: Optional[torch.Tensor] = None, loss: Optional[torch.Tensor] = None):
@@ -588,6 +627,7 @@ class Engine:
         with torch.cuda.device(self.device):
             _check(self.lib, self.lib.mshgnn_backward_mse(self._plan, ptrs, pitch, params_flat.data_ptr(), out.data_ptr(), y.data_ptr(),
                                                       loss.data_ptr(), grad_flat.data_ptr(), ws.data_ptr(), B, stream), "mshgnn_backward_mse")
+        self._bwd_ticket[B] = self._tickets.get(B, 0)
         return loss, grad_flat
 
     def step_mse(self, xs: Sequence[torch.Tensor], params_flat: torch.Tensor, y: torch.Tensor, B: int, out: Optional[torch.Tensor] = None,
@@ -747,6 +787,7 @@ class Engine:
         with torch.cuda.device(self.device):
             _check(self.lib, self.lib.mshgnn_backward_ce(self._plan, ptrs, pitch, params_flat.data_ptr(), out.data_ptr(), labels.data_ptr(),
                                                      loss.data_ptr(), grad_flat.data_ptr(), ws.data_ptr(), B, stream), "mshgnn_backward_ce")
+        self._bwd_ticket[B] = self._tickets.get(B, 0)
         return loss, grad_flat
 
     def adam_step(self, params_flat: torch.Tensor, grad_flat: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor,
@@ -906,9 +947,15 @@ class PaddedEngine:
     def forward(self, xs, params_flat, B, training=True, out=None):
         return self.inner.forward(xs, self._pad(params_flat), B, training=training, out=out)
 
-    def backward(self, xs, params_flat, grad_out, B, grad_flat=None):
+    def backward(self, xs, params_flat, grad_out, B, grad_flat=None, weights=True):
+        if not weights:
+            return self.inner.backward(xs, self._pad(params_flat), grad_out, B, weights=False)
         self.inner.backward(xs, self._pad(params_flat), grad_out, B, grad_flat=self._pgrad)
         return self._unpad_grad(grad_flat)
+
+    def input_grad(self, B, params_flat, types=None, dtype=torch.float32, pitches=None):
+        """The inner engine's, on the padded flat buffer: the added rows of W_enc are zero and the added features' dY are exact zeros -- the same gradient."""
+        return self.inner.input_grad(B, self._pad(params_flat), types, dtype, pitches)
 
     def backward_mse(self, xs, params_flat, out, y, B, grad_flat=None, loss=None):
         loss, _ = self.inner.backward_mse(xs, self._pad(params_flat), out, y, B, grad_flat=self._pgrad, loss=loss)

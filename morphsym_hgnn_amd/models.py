@@ -18,6 +18,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 import yaml
 from torch import nn
+from torch.autograd.function import once_differentiable
 
 from . import nn as pnn
 from .spec import ModelSpec, rel_key
@@ -121,6 +122,64 @@ class _EngineFnFast(torch.autograd.Function):
         g32 = gout.contiguous().to(torch.float32)
         _deliver_gradients(m, ctx.flat, lambda target: e.backward(ctx.xs, ctx.flat, g32, ctx.B, grad_flat=target))
         return (None, None, None, None, *([None] * len(ctx.xs)))
+
+
+class _EngineFnIn(torch.autograd.Function):
+    """Any route of forward() when some x_dict tensor requires grad: the autograd inputs are the CALLER's tensors (the engine's cast / re-pitched copies stay
+    out of the graph), and backward returns each one its gradient -- same shape, dtype and device -- from mshgnn_input_grad (models the reference's
+    autograd through apply_symmetry and the encoder, hgnn_c2.py:150-151).  The parameters travel as on the route without input gradients:
+      "fast": device views of the flat buffer, gradients delivered outside autograd (_EngineFnFast);  "p": the parameters as autograd inputs (_EngineFnP,
+      torch.distributed);  "flat": the _Flatten output of host parameters (_EngineFn);  None: every parameter frozen -- the backward passes no gradient
+      buffer (activation backward only) and no .grad is touched.
+    cfg: (model, engine, B, flat, cast inputs, route, offsets, ddp, number of parameter tensors); tensors: (*parameter tensors, *caller's inputs)."""
+
+    @staticmethod
+    def forward(ctx, cfg, *tensors):
+        model, engine, B, flat, xs, route, offsets, ddp, n_p = cfg
+        if route == "flat":
+            flat = tensors[0]
+        out = engine.forward(xs, flat, B, training=True)
+        ctx.cfg, ctx.flat, ctx.ticket = cfg, flat, engine.stash_ticket(B)
+        ctx.shapes = [p.shape for p in tensors[:n_p]]
+        ctx.xin = [(x.shape, x.dtype, x.device, x.requires_grad) for x in tensors[n_p:]]
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        model, e, B, _, xs, route, offsets, ddp, n_p = ctx.cfg
+        flat = ctx.flat
+        if e.stash_ticket(B) != ctx.ticket:
+            raise RuntimeError("the activation stash of this forward was overwritten by a later forward of the same "
+                               "batch size on the same engine; call backward before the next forward")
+        g32 = gout.contiguous().to(torch.float32)
+        pgrads = [None] * n_p
+        if route is None:
+            e.backward(xs, flat, g32, B, weights=False)
+        elif route == "fast":
+            _deliver_gradients(model, flat, lambda target: e.backward(xs, flat, g32, B, grad_flat=target))
+        elif route == "flat":
+            pgrads = [e.backward(xs, flat, g32, B)]
+        else:
+            n_flat = flat.numel()
+            full = torch.empty(n_flat + 16, dtype=torch.float32, device=flat.device)
+            gflat = e.backward(xs, flat, g32, B, grad_flat=full[:n_flat])
+            if ddp is not None:
+                from .ddp import exchange_flat_gradient_
+                group, weighted, live = (*ddp, None)[:3]
+                gflat.div_(exchange_flat_gradient_(full, n_flat, B, None if group is True else group, weighted, live))
+            pgrads = [gflat[o:o + n].view(shape) for (o, n), shape in zip(offsets, ctx.shapes)]
+        want = [t for t, (_, _, _, rg) in zip(e.types, ctx.xin) if rg]
+        direct = {t: dt for t, (shape, dt, dev, _) in zip(e.types, ctx.xin) if dt in (torch.float32, torch.float64)}
+        pitches = {t: shape[1] for t, (shape, _, _, _) in zip(e.types, ctx.xin)}
+        by_dtype = {}
+        for t in want:
+            by_dtype.setdefault(direct.get(t, torch.float32), []).append(t)
+        g = {}
+        for dt, ts in by_dtype.items():      # one launch per output dtype (one in practice: x_dict tensors share theirs)
+            g.update(e.input_grad(B, flat, ts, dt, pitches))
+        xgrads = [g[t].to(device=dev, dtype=dt) if t in g else None for t, (_, dt, dev, _) in zip(e.types, ctx.xin)]
+        return (None, *pgrads, *xgrads)
 
 
 def _deliver_gradients(m, flat, fresh, scale=None):
@@ -415,6 +474,8 @@ class _MSHGNNBase(nn.Module):
         params = self._params_in_flat_order()
         if e is None or not torch.is_grad_enabled() or params[0].device.type != "cuda" or not all(p.requires_grad for p in params):
             return None
+        if any(x_dict[t].requires_grad for t in self._node_types):      # the caller wants x.grad too: the two-call route (forward() + backward) delivers it
+            return None
         import torch.distributed as dist
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1 and self._flat_ddp is None:
             return None
@@ -477,6 +538,9 @@ class _MSHGNNBase(nn.Module):
         params = self._params_in_flat_order()
         offsets = list(spec.param_offsets().values())
         need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in params)
+        if torch.is_grad_enabled() and any(x_dict[t].requires_grad for t in self._node_types):
+            out = self._forward_input_grad(x_dict, xs, e, B, pdev, params, offsets, need_grad)
+            return self._shape_output(out, spec, B, in_dev, in_dtype)
         if params[0].device.type == "cuda":
             # parameters on the device: they are (made) views of the flat fp32 buffer -- no copy in, no copy out
             flat = self._flat_params(pdev)
@@ -502,6 +566,33 @@ class _MSHGNNBase(nn.Module):
                     torch._foreach_copy_(views, [p.detach() for p in params])
                     out = e.forward(xs, self._flat, B, training=False)
         return self._shape_output(out, spec, B, in_dev, in_dtype)
+
+    def _forward_input_grad(self, x_dict, xs, e, B, pdev, params, offsets, need_grad):
+        """forward() when some input requires grad (_EngineFnIn): the parameters take the route they take without input gradients, frozen ones none."""
+        spec = self._spec
+        xin = [x_dict[t] for t in self._node_types]
+        if params[0].device.type == "cuda":
+            flat = self._flat_params(pdev)
+            route, ptens, ddp = None, [], None
+            if need_grad:
+                import torch.distributed as dist
+                if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+                    route, ptens = "p", list(params)
+                    ddp = None if self._flat_ddp is None else (self._flat_ddp, self._flat_ddp_weighted, getattr(self, "_flat_ddp_live", None))
+                else:
+                    route = "fast"
+        else:
+            if self._flat is None or self._flat.device != pdev or self._flat_ok:
+                self._flat, self._flat_ok = torch.zeros(spec.flat_size(), dtype=torch.float32, device=pdev), False
+            if need_grad:
+                flat, route, ptens, ddp = None, "flat", [_Flatten.apply(spec.flat_size(), pdev, offsets, *params)], None
+            else:
+                with torch.no_grad():
+                    views = [self._flat[o:o + n].view(p.shape) for (o, n), p in zip(offsets, params)]
+                    torch._foreach_copy_(views, [p.detach() for p in params])
+                flat, route, ptens, ddp = self._flat, None, [], None
+        cfg = (self, e, B, flat, xs, route, offsets, ddp, len(ptens))
+        return _EngineFnIn.apply(cfg, *ptens, *xin)
 
     def _forward_operators(self, x_dict, edge_index_dict, B):
         """The reference's forward (hgnn_c2.py:133-182, hgnn_k4.py:146-196, hgnn.py:57-62, hgnn_*_com.py) operator by operator, for models built with
