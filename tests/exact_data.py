@@ -12,6 +12,10 @@ element anywhere (a dropped 16-window tile, a mis-indexed 32-feature column slic
   (b) fp32 closure: for every accumulation the sum of the absolute values of its terms fits in 2^24 units of the finest dyadic grid of its terms;
   (c) coverage: every gradient tensor that is live on random data is non-zero, every 32-feature column slice of every live X_l holds non-zero values,
       and every layer has exact-zero relu pre-activations (relu'(0) = 0 is exercised).
+With input_grads=True a fourth, for the gradient with respect to the inputs dx = m . (dY_enc @ W_enc) (csrc/mshgnn_input_grad.hip):
+  (d) input-gradient closure and coverage: dY_enc is bf16-exact, for every (window, node, feature) the sum of |dY_enc[j]| |W_enc[j][f]| fits in 2^24 units
+      of the finest dyadic grid of its terms, every input type the encoder computes has a non-zero dx in every 16-column tile of its width, and a negative
+      symmetry sign meets a non-zero element (apply_symmetry's negation is exercised).
 """
 import math
 
@@ -41,8 +45,11 @@ def _signed_rows(g, out_f, in_f, scales, density=1.0):
     return w
 
 
-def exact_case(spec, B, seed, x_range=2, bias_range=(-1, 1), rel_scales=(0.5, 1.0), density=1.0, per_matrix=False, gout_range=2, mse=None):
+def exact_case(spec, B, seed, x_range=2, bias_range=(-1, 1), rel_scales=(0.5, 1.0), density=1.0, per_matrix=False, gout_range=2, mse=None,
+               enc_cover=False):
     """Rounding-free inputs, parameters and output gradient for `spec` at batch size B.
+    enc_cover: dense encoder columns over zero inputs (`_cover_encoder_tiles`) -- with one entry per row, the few features that carry dY_enc reach only
+    a few input columns, and the input gradient of a 900-wide input would be zero in most of its column tiles.
     Returns a dict: x (reference convention, fp64 [B*n_t, F_t]), params, gout (fp64 [B*n_out*d], k * 2^-14), and for the one-call MSE step (mse=True, default
     for regression models) y (fp32-exact targets) and gout_mse: the gradient the fused MSE computes from them, 2 (out - y) * fl32(1 / N) evaluated in fp32,
     every element a short dyadic number (`_mse_targets`)."""
@@ -56,6 +63,8 @@ def exact_case(spec, B, seed, x_range=2, bias_range=(-1, 1), rel_scales=(0.5, 1.
         else:
             params[name] = torch.randint(bias_range[0], bias_range[1] + 1, shape, generator=g).double()
     x = {t: torch.randint(-x_range, x_range + 1, (B * spec.num_nodes[t], spec.widths[t]), generator=g).double() for t in spec.node_types}
+    if enc_cover:
+        _cover_encoder_tiles(spec, params, x, seed)
     n = B * spec.num_nodes[spec.out_type] * spec.out_channels
     gout = torch.randint(-gout_range, gout_range + 1, (n,), generator=g).double() * 2.0 ** GOUT_EXP
     case = dict(spec=spec, B=B, seed=seed, x=x, params=params, gout=gout, y=None, gout_mse=None)
@@ -63,6 +72,31 @@ def exact_case(spec, B, seed, x_range=2, bias_range=(-1, 1), rel_scales=(0.5, 1.
         out = reference(spec, case)["out"]
         case["y"], case["gout_mse"] = _mse_targets(out, seed, gout_range)
     return case
+
+
+def _cover_encoder_tiles(spec, params, x, seed):
+    """Give every encoder weight matrix a dense column in every 4-column group of the input width that no row's own entry uses: +-1, +-0.5 or +-0.25
+    in every row (a generator of its own), and set those input columns to 0 in every window.  Where every group has a free column, the forward, the
+    activation gradients and the parameter gradients outside those columns are the unchanged case's (the added weights multiply zeros), but every such
+    column of dx is a sum over all K rows of dY_enc."""
+    gc = torch.Generator().manual_seed(seed + 7919)
+    for t in spec.node_types:
+        w = params[f"encoder.lins.{t}.weight"]
+        H, F = w.shape
+        free = ~(w != 0).any(0)
+        cols = []
+        for c in range(0, F, 4):
+            idx = free[c:c + 4].nonzero()[:, 0] + c
+            if idx.numel() == 0 and F > 1:      # (every column of the group in use -- a hidden width above F: the rows using the one taken lose their input)
+                idx = torch.arange(c, min(c + 4, F))
+            if idx.numel():
+                cols.append(idx[torch.randint(0, idx.numel(), (1,), generator=gc)])
+        if not cols:
+            continue
+        z = torch.cat(cols)
+        sign = torch.randint(0, 2, (H, z.numel()), generator=gc).double() * 2 - 1
+        w[:, z] = sign * torch.tensor([1.0, 0.5, 0.25], dtype=torch.float64)[torch.randint(0, 3, (H, z.numel()), generator=gc)]
+        x[t][:, z] = 0.0
 
 
 def _mse_targets(out, seed, gout_range):
@@ -94,17 +128,21 @@ def _mse_targets(out, seed, gout_range):
 # ---------------------------------------------------------------------------------------------------
 # fp64 reference (the oracle, plain torch.relu)
 # ---------------------------------------------------------------------------------------------------
-def reference(spec, case, gout=None):
-    """The oracle's output, hidden states X_0..X_L ([B, NN, h] in the engine's node order), parameter gradients for output gradient `gout` and, when the
-    case has targets, the MSE loss."""
+def reference(spec, case, gout=None, input_grads=False):
+    """The oracle's output, hidden states X_0..X_L ([B, NN, h] in the engine's node order), parameter gradients for output gradient `gout`, with
+    input_grads=True the gradients with respect to the inputs (`xgrads`: {type: [B*n_t, F_t]}, the same `gout`) and, when the case has targets, the MSE
+    loss."""
     B = case["B"]
     cfg = helpers.oracle_config(spec)
     leaves = {k: v.clone().requires_grad_(True) for k, v in case["params"].items()}
-    out, hidden = orc.forward(cfg, leaves, {k: v.clone() for k, v in case["x"].items()}, spec.topology.edge_index_dict(B), return_hidden=True)
+    xl = {k: v.clone().requires_grad_(input_grads) for k, v in case["x"].items()}
+    out, hidden = orc.forward(cfg, leaves, xl, spec.topology.edge_index_dict(B), return_hidden=True)
     res = {"out": out.detach().reshape(-1).clone(), "hidden": [helpers.dense_hidden(spec, {t: v.detach() for t, v in h.items()}, B) for h in hidden]}
     if gout is not None:
         out.backward(gout.reshape(out.shape))
         res["grads"] = {k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in leaves.items()}
+        if input_grads:
+            res["xgrads"] = {k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in xl.items()}
     if case.get("y") is not None:
         res["loss"] = float(((res["out"] - case["y"]) ** 2).mean())
     return res
@@ -233,14 +271,15 @@ def _live_nonzero_in_random_case(spec):
     return {k for k, g in grads.items() if float(g.abs().max()) > 0}
 
 
-def check_exact(spec, case, gout=None, stats=None):
+def check_exact(spec, case, gout=None, stats=None, input_grads=False):
     """The fp64 reference for `case` with output gradient `gout` (default: the case's `gout_mse` when it has targets, else its `gout`), after asserting
-    the preconditions (a) bf16 closure, (b) fp32 closure and (c) coverage (module docstring).  `stats`: a dict that receives what was measured."""
+    the preconditions (a) bf16 closure, (b) fp32 closure and (c) coverage (module docstring); input_grads=True: also the gradients with respect to the
+    inputs (`xgrads`) after (d).  `stats`: a dict that receives what was measured."""
     B = case["B"]
     if gout is None:
         gout = case["gout_mse"] if case.get("gout_mse") is not None else case["gout"]
     stats = {} if stats is None else stats
-    ref = reference(spec, case, gout)
+    ref = reference(spec, case, gout, input_grads=input_grads)
     go = gout.clone()
 
     # (a) bf16 closure: emulation with and without rounding and the oracle, bit for bit
@@ -304,5 +343,35 @@ def check_exact(spec, case, gout=None, stats=None):
         assert per_layer.get(l, 0) > 0, f"(c) no exact-zero relu pre-activation in {'the encoder' if l < 0 else f'layer {l}'}"
     stats.update(zero_decisions=sum(zeros.values()), nonzero_grads=sum(1 for g in ref["grads"].values() if float(g.abs().max()) > 0),
                  grads=len(ref["grads"]), nonzero_gout=int((go != 0).sum()), gout=go.numel())
+    if input_grads:
+        _check_input_grads(spec, case, ref, inter, stats)
     ref["gout"] = go
     return ref
+
+
+def _check_input_grads(spec, case, ref, inter, stats):
+    """(d): dx = m . (dY_enc @ W_enc) closes in fp32 on every plan's operands and covers every 16-column tile and a negative symmetry sign."""
+    B = case["B"]
+    masks = spec.input_masks()
+    _, need = spec.node_liveness()
+    bound, neg = 0.0, 0
+    for t in spec.node_types:
+        dy = inter[f"enc.{t}"].grad                                  # [B, n_t, H]: relu'(X_0) . dX_0, the stash mshgnn_input_grad reads
+        assert dy is not None and bf16_exact(dy), f"(d) dY_enc {t} is not a bf16 value"
+        W = case["params"][f"encoder.lins.{t}.weight"]              # [H, F]
+        grid = lsb_exponent(dy) + lsb_exponent(W)
+        if math.isfinite(grid):
+            s = float((dy.detach().abs() @ W.abs()).max())
+            assert s <= 2.0 ** (24 + grid), f"(d) an input-gradient sum of |terms| {s} ({t}) exceeds 2^24 units of 2^{grid}"
+            bound = max(bound, s / 2.0 ** (24 + grid))
+        dx = ref["xgrads"][t].view(B, spec.num_nodes[t], -1)
+        assert torch.equal(dx, (dy.detach() @ W) * masks[t].unsqueeze(0)), f"(d) the oracle's dx {t} is not m . (dY_enc @ W_enc)"
+        if not need[0][t]:
+            assert float(dx.abs().max()) == 0.0, f"(d) {t}: the encoder computes no node of this type, yet its dx is non-zero"
+            continue
+        for c in range(0, dx.shape[-1], 16):
+            assert bool((dx[..., c:c + 16] != 0).any()), f"(d) {t}: the input gradient is all zero in column tile {c // 16}"
+        neg += int(((dx != 0) & (masks[t] < 0).unsqueeze(0)).sum())
+    if any(bool((masks[t] < 0).any()) for t in spec.node_types if need[0][t]):
+        assert neg > 0, "(d) no negative symmetry sign meets a non-zero input gradient"
+    stats.update(xgrad_sum_bound=bound, xgrad_negative=neg)

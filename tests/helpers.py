@@ -170,6 +170,62 @@ def engine_relu_decisions(e, spec, B):
     return out
 
 
+def check_input_grad_against_own_operands(e, spec, params, B, got):
+    """Engine.input_grad's output `got` ({type: [B * n_t, pitch]}, fp32 or fp64) against dx = m . (dY_enc @ W_enc) rebuilt in fp64 from the engine's
+    OWN operands: the dX_0 stash read straight from the workspace (split plan: its hi and lo halves; bf16 plan: the bf16 rows; fp32 plan: the fp32
+    rows) and W_enc in the plan's operand form (bf16: round to nearest even; split: hi + lo with exactly the kernel's products hi.hi, hi.lo, lo.hi;
+    fp32: as is).  Each element must lie within 2 n 2^-24 sum |terms| of it, n the products summed: K on the fp32 and bf16 plans, 3K on the split plan
+    (three products per k -- the recursive-summation count; a bound of 2 K 2^-24 there would assume fewer roundings than the kernel performs).  That
+    leaves the accumulation order as the only freedom; rows of nodes the plan does not compute and columns past F_t must be exact zeros.  Returns the largest error in units of that bound."""
+    lay, ws = e.layout(B, True), e.workspace(B, True)
+    nn_ = e.info.total_nodes
+    K = e.inner_spec.hidden if getattr(e, "padded", False) else spec.hidden
+    off, n = lay.dx[0], nn_ * B * K
+    if e.storage == "x3":
+        st = ws[off:off + 4 * n].view(torch.bfloat16).view(nn_, B, 2, K)
+        parts = [(st[:, :, 0], "hi"), (st[:, :, 1], "lo")]
+    elif e.storage == "bf16":
+        parts = [(ws[off:off + 2 * n].view(torch.bfloat16).view(nn_, B, K), "hi")]
+    else:
+        parts = [(ws[off:off + 4 * n].view(torch.float32).view(nn_, B, K), "hi")]
+    _, need = spec.node_liveness()
+    masks = spec.input_masks()
+    sl = node_slices(spec)
+    worst = 0.0
+    for t in spec.node_types:
+        F = spec.widths[t]
+        w32 = torch.zeros(K, F, dtype=torch.float32, device=e.device)
+        w32[:spec.hidden] = params[f"encoder.lins.{t}.weight"].to(e.device, torch.float32)
+        if e.storage == "f32":
+            wp = {"hi": w32.double()}
+        else:
+            wh = w32.to(torch.bfloat16)
+            wp = {"hi": wh.double(), "lo": (w32 - wh.float()).to(torch.bfloat16).double()}
+        prods = [("hi", "hi"), ("lo", "hi"), ("hi", "lo")] if e.storage == "x3" else [("hi", "hi")]
+        n_terms = K * len(prods)
+        g = got[t].view(B, spec.num_nodes[t], -1)
+        assert g.shape[-1] >= F
+        assert torch.count_nonzero(g[..., F:]) == 0 and not bool(torch.signbit(g[..., F:]).any()), f"{t}: pad columns are not +0.0"
+        for i in range(spec.num_nodes[t]):
+            gi = g[:, i, :F].double()
+            if i not in need[0][t]:
+                assert torch.count_nonzero(gi) == 0, f"{t} node {i}: the plan does not compute this node, yet its dx is non-zero"
+                continue
+            dy = {name: p[sl[t].start + i].double() for p, name in parts}      # [B, K]
+            ref = sum(dy[a] @ wp[b] for a, b in prods)
+            bound = sum(dy[a].abs() @ wp[b].abs() for a, b in prods)
+            m = masks[t][i].to(e.device)
+            err = (gi - ref * m).abs()
+            lim = 2.0 * n_terms * 2.0 ** -24 * bound
+            bad = err > lim
+            assert not bool(bad.any()), (f"{t} node {i}: {int(bad.sum())} elements outside 2 n 2^-24 sum|terms|; first at "
+                                         f"{bad.nonzero()[0].tolist()}: got {float(gi[bad][0])!r}, reference {float((ref * m)[bad][0])!r}")
+            nz = bound > 0
+            if bool(nz.any()):
+                worst = max(worst, float((err[nz] / lim[nz]).max()))
+    return worst
+
+
 def row_live_mask(spec, key, B):
     """bool [B * n_type] for a decision key of engine_relu_decisions: True where the engine really took that decision (the node is computed by the plan)."""
     live, need = spec.node_liveness()

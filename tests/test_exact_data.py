@@ -1,10 +1,13 @@
-"""The rounding-free data of tests/test_exact_gpu.py, checked on the host: for every (model, batch size) the GPU file uses, check_exact proves bf16 closure,
-fp32 closure and coverage (tests/exact_data.py) -- and the comparison the GPU file relies on flags a single-ulp change."""
+"""The rounding-free data of tests/test_exact_gpu.py and tests/test_input_grad_exact_gpu.py, checked on the host: for every (model, batch size) the GPU
+files use, check_exact proves bf16 closure, fp32 closure and coverage (tests/exact_data.py), for the second file also input-gradient closure and
+coverage -- and the comparison the GPU files rely on flags a single-ulp change."""
 import pytest
 import torch
 
 from tests import exact_data as xd
+from tests import helpers
 from tests import test_exact_gpu as gx
+from tests import test_input_grad_exact_gpu as igx
 
 CASES = sorted({("a1c2_L3", B) for B in gx.BATCHES + gx.TWO_CALL_BATCHES + [200]} | set(gx.WIDE_CASES) | {("a1c2_h200_L3", B) for B in gx.PADDED_BATCHES}
                | {("mck4_cls_L3", B) for B in gx.CLS_BATCHES})
@@ -43,3 +46,30 @@ def test_check_exact_refuses_a_rounding_case():
     with pytest.raises(AssertionError):
         xd.check_exact(spec, case, gout=case["gout"])
 
+
+
+@pytest.mark.parametrize("model,B", sorted(set(igx.CASES)))
+def test_input_grad_case_is_rounding_free_and_covering(model, B):
+    """(a)-(d) for every (model, batch) of tests/test_input_grad_exact_gpu.py, whose GPU references are the oracle alone."""
+    spec, case = igx.exact_case(model, B)
+    stats = {}
+    ref = xd.check_exact(spec, case, stats=stats, input_grads=True)
+    assert 0 < stats["xgrad_sum_bound"] <= 1.0
+    _, need = spec.node_liveness()
+    for t in spec.node_types:      # a non-zero dx only where the encoder computes the node
+        dx = ref["xgrads"][t].view(B, spec.num_nodes[t], -1)
+        assert set(i for i in range(spec.num_nodes[t]) if float(dx[:, i].abs().max()) > 0) <= set(need[0][t]), t
+
+
+def test_enc_cover_changes_nothing_but_the_input_gradient():
+    """The dense encoder columns of enc_cover multiply zero inputs: output, hidden states and parameter gradients are the plain case's."""
+    spec = helpers.make_spec(*gx.MODELS["a1c2_L3"]["spec"])
+    plain = xd.exact_case(spec, 17, gx.SEED, **gx.MODELS["a1c2_L3"]["knobs"])
+    cover = xd.exact_case(spec, 17, gx.SEED, enc_cover=True, **gx.MODELS["a1c2_L3"]["knobs"])
+    rp, rc = (xd.reference(spec, c, c["gout_mse"], input_grads=True) for c in (plain, cover))
+    assert torch.equal(rp["out"], rc["out"]) and all(torch.equal(a, b) for a, b in zip(rp["hidden"], rc["hidden"]))
+    for k in rp["grads"]:      # (the encoder weights' gradient differs only in the columns whose inputs enc_cover zeroes)
+        keep = slice(None) if not k.startswith("encoder.lins.") or not k.endswith(".weight") else (cover["x"][k.split(".")[2]] != 0).any(0)
+        assert torch.equal(rp["grads"][k][..., keep], rc["grads"][k][..., keep]), k
+    W = cover["params"]["encoder.lins.base.weight"]
+    assert int((W != 0).any(0).sum()) > int((plain["params"]["encoder.lins.base.weight"] != 0).any(0).sum())

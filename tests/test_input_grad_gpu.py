@@ -199,7 +199,9 @@ def test_layouts_dtypes_devices_and_determinism(monkeypatch):
 @pytest.mark.gpu
 @pytest.mark.parametrize("dtype,tol", [("f32", 1e-6), ("x3", 1e-4), ("bf16", 1e-2)])
 def test_engine_input_grad_is_the_encoder_product_of_its_own_stash(dtype, tol):
-    """Engine.input_grad after Engine.backward == (dY_enc @ W_enc) . mask rebuilt in torch from the engine's own dX_0 stash, at 1024 windows."""
+    """Engine.input_grad after Engine.backward == (dY_enc @ W_enc) . mask rebuilt in torch from the engine's own dX_0 stash, at 1024 windows: per node
+    within `tol` (relative to the node's largest element) of the product with the fp32 W, and per element within 2 n 2^-24 sum|terms| of the product
+    with W in the plan's operand form (helpers.check_input_grad_against_own_operands)."""
     from morphsym_hgnn_amd import engine as eng
     spec = helpers.make_spec("c2", "a1-c2", "a1-c2", 128, 2)
     B = 1024
@@ -225,9 +227,168 @@ def test_engine_input_grad_is_the_encoder_product_of_its_own_stash(dtype, tol):
             else:
                 assert torch.count_nonzero(g[:, i]) == 0, (t, i)
         base += spec.num_nodes[t]
+    for dt in (torch.float32, torch.float64):
+        assert helpers.check_input_grad_against_own_operands(e, spec, params, B, e.input_grad(B, flat, dtype=dt)) <= 1.0
     with pytest.raises(RuntimeError, match="overwritten"):
         e.forward(xs, flat, B, training=True)
         e.input_grad(B, flat)
+
+
+def _own_operands_case(spec, dtype, B, seed, dt=torch.float64):
+    from morphsym_hgnn_amd import engine as eng
+    x_dict, y, params = helpers.random_case(spec, B, seed)
+    e = eng.make_engine(spec, dtype)
+    xs = e.cast_inputs(x_dict)
+    flat = eng.flatten_params(spec, params, device=e.device)
+    out = e.forward(xs, flat, B, training=True)
+    gout = (torch.randn(out.numel(), generator=torch.Generator().manual_seed(seed + 1)) * 1e-3).float().cuda()
+    e.backward(xs, flat, gout, B)
+    got = e.input_grad(B, flat, dtype=dt)
+    torch.cuda.synchronize()
+    return e, x_dict, params, gout, got
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", ["bf16", "x3"])
+@pytest.mark.parametrize("hidden", [640, 1536, 2048])
+def test_wide_input_grad_is_the_product_of_the_engines_own_operands(hidden, dtype):
+    """The generic engine at hidden 640 (column chunks of 32 / 16), 1536 and 2048: every launch form of the kernel whose LDS exceeds 64 KB (bf16 at
+    2048: 65 792 bytes; split at 1536 / 2048: 98 816 / 131 584), at 70 and 300 windows, held to the engine's own operands; at 70 windows also to the
+    fp64 oracle under the engine's relu decisions (1e-4 split, 2e-2 bf16)."""
+    from oracle import ms_hgnn_oracle as orc
+    spec = helpers.make_spec("c2", "a1-c2", "a1-c2", hidden, 2)
+    for B in (70, 300):
+        e, x_dict, params, gout, got = _own_operands_case(spec, dtype, B, 5)
+        assert e.generic
+        assert helpers.check_input_grad_against_own_operands(e, spec, params, B, got) <= 1.0
+        if B == 70:
+            decisions = helpers.engine_relu_decisions(e, spec, B)
+
+            def relu_fn(key, h):
+                if key not in decisions:
+                    return torch.relu(h)
+                rows = helpers.row_live_mask(spec, key, B).view(-1, 1)
+                return h * torch.where(rows, decisions[key], h.detach() > 0).to(h.dtype)
+            xl = {k: v.clone().requires_grad_(True) for k, v in x_dict.items()}
+            o = orc.forward(helpers.oracle_config(spec), {k: v.double() for k, v in params.items()}, xl, spec.topology.edge_index_dict(B), relu_fn=relu_fn)
+            o.backward(gout.double().cpu().reshape(o.shape))
+            for t in spec.node_types:
+                ref = xl[t].grad if xl[t].grad is not None else torch.zeros_like(xl[t])
+                if float(ref.abs().max()) == 0.0:
+                    assert float(got[t].abs().max()) == 0.0, t
+                else:
+                    assert _rel(got[t], ref) < TOL[dtype], (t, _rel(got[t], ref))
+        del e
+
+
+@pytest.mark.gpu
+def test_input_grad_at_65536_windows_is_the_product_of_the_engines_own_operands():
+    """A1-C2 h128 split plan, two-call route (forward + backward: never chunked) at 65 536 windows: 64 row tiles per workgroup."""
+    spec = helpers.make_spec("c2", "a1-c2", "a1-c2", 128, 3)
+    e, _, params, _, got = _own_operands_case(spec, "x3", 65536, 7, dt=torch.float32)
+    assert helpers.check_input_grad_against_own_operands(e, spec, params, 65536, got) <= 1.0
+
+
+def _abi_setup(dtype="x3", B=37):
+    from morphsym_hgnn_amd import engine as eng
+    spec = helpers.make_spec("c2", "a1-c2", "a1-c2", 128, 4)
+    x_dict, y, params = helpers.random_case(spec, B, 13)
+    e = eng.Engine(spec, dtype, device="cuda:0")
+    xs = e.cast_inputs(x_dict)
+    flat = eng.flatten_params(spec, params, device=e.device)
+    out = e.forward(xs, flat, B, training=True)
+    e.backward(xs, flat, torch.randn(out.numel(), generator=torch.Generator().manual_seed(2)).float().cuda(), B)
+    return spec, e, flat
+
+
+def _abi_call(e, flat, B, bufs, pitches, dx_bytes, ws_B=None):
+    """mshgnn_input_grad through ctypes: bufs / pitches per type (None: NULL), pitches=None: a NULL dx_pitch; the workspace of batch ws_B (default B)."""
+    import ctypes as C
+    n = len(e.types)
+    ptrs = (C.c_void_p * n)(*[b if b is not None else None for b in bufs])
+    pitch = None if pitches is None else (C.c_int64 * n)(*pitches)
+    stream = torch.cuda.current_stream(e.device).cuda_stream
+    rc = e.lib.mshgnn_input_grad(e._plan, flat.data_ptr(), ptrs, pitch, dx_bytes, e.workspace(ws_B or B, True).data_ptr(), B, stream)
+    torch.cuda.synchronize()
+    return rc
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dt", [torch.float32, torch.float64])
+def test_c_abi_layouts_write_every_element_of_the_callers_rows(dt):
+    """NaN-filled buffers at pitches F, F + 1, F + 3 and ceil(F / 64) 64 + 5, base pointers one element off 16 bytes (no 16-byte stores), the last type
+    alone (type 0 NULL) and a NULL dx_pitch: columns [0, F) are the dense result's bits, [F, pitch) are +0.0, no NaN is left."""
+    B = 37
+    spec, e, flat = _abi_setup()
+    dense = e.input_grad(B, flat, dtype=dt)
+    es = torch.empty(0, dtype=dt).element_size()
+    types = list(e.types)
+    F = [spec.widths[t] for t in types]
+    rows = [B * spec.num_nodes[t] for t in types]
+
+    def run(pitches, shift, only=None, null_pitch=False):
+        store, ptrs = [], []
+        for k, t in enumerate(types):
+            if only is not None and k != only:
+                store.append(None)
+                ptrs.append(None)
+                continue
+            buf = torch.full((rows[k] * pitches[k] + shift + 8,), float("nan"), dtype=dt, device="cuda")
+            store.append(buf)
+            ptrs.append(buf.data_ptr() + shift * es)
+        assert _abi_call(e, flat, B, ptrs, None if null_pitch else pitches, es) == 0, e.lib.mshgnn_last_error()
+        for k, t in enumerate(types):
+            if store[k] is None:
+                continue
+            buf = store[k]
+            assert bool(torch.isnan(buf[:shift]).all()) and bool(torch.isnan(buf[shift + rows[k] * pitches[k]:]).all()), (t, "wrote outside its rows")
+            v = buf[shift:shift + rows[k] * pitches[k]].view(rows[k], pitches[k])
+            what = (t, pitches[k], shift)
+            assert not bool(torch.isnan(v).any()), what
+            assert torch.equal(v[:, :F[k]], dense[t]), what
+            pad = v[:, F[k]:]
+            assert torch.count_nonzero(pad) == 0 and not bool(torch.signbit(pad).any()), what
+
+    for extra in (lambda f: f, lambda f: f + 1, lambda f: f + 3, lambda f: (f + 63) // 64 * 64 + 5):
+        pitches = [extra(f) for f in F]
+        for shift in (0, 1):
+            run(pitches, shift)
+    run(F, 0, only=len(types) - 1)
+    run(F, 1, only=len(types) - 1)
+    run(F, 0, null_pitch=True)
+
+
+@pytest.mark.gpu
+def test_c_abi_error_returns_launch_nothing():
+    B = 37
+    spec, e, flat = _abi_setup()
+    types = list(e.types)
+    F = [spec.widths[t] for t in types]
+    bufs = [torch.full((B * spec.num_nodes[t] * F[k],), float("nan"), device="cuda") for k, t in enumerate(types)]
+    ptrs = [b.data_ptr() for b in bufs]
+    assert _abi_call(e, flat, B, ptrs, F, 2) == -2                                              # MSHGNN_EUNSUPPORTED
+    assert _abi_call(e, flat, B, ptrs, [F[0], F[1] - 1, F[2]], 4) == -1                        # MSHGNN_EINVAL: pitch < F
+    assert _abi_call(e, flat, 0, ptrs, F, 4, ws_B=B) == -1                                     # MSHGNN_EINVAL: batch 0
+    assert _abi_call(e, flat, B, [None] * len(types), F, 4) == 0                              # nothing requested
+    assert all(bool(torch.isnan(b).all()) for b in bufs), "an error return wrote"
+
+
+@pytest.mark.gpu
+def test_lds_attribute_holds_across_plans_of_different_modes_at_2048():
+    """bf16, then split, then bf16 again at hidden 2048 in one process (65 792 and 131 584 bytes of LDS: the attribute is set once per instantiation)."""
+    spec = helpers.make_spec("c2", "a1-c2", "a1-c2", 2048, 2)
+    for dtype in ("bf16", "x3", "bf16"):
+        e, _, params, _, got = _own_operands_case(spec, dtype, 40, 9)
+        assert helpers.check_input_grad_against_own_operands(e, spec, params, 40, got) <= 1.0
+        del e
+
+
+@pytest.mark.gpu
+def test_input_grad_at_8208_windows_is_deterministic():
+    spec, e, flat = _abi_setup("bf16", 8208)
+    a = e.input_grad(8208, flat, dtype=torch.float32)
+    b = e.input_grad(8208, flat, dtype=torch.float32)
+    assert all(torch.equal(a[t], b[t]) for t in a)
 
 
 @pytest.mark.gpu
