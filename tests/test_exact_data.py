@@ -1,16 +1,18 @@
-"""The rounding-free data of tests/test_exact_gpu.py and tests/test_input_grad_exact_gpu.py, checked on the host: for every (model, batch size) the GPU
-files use, check_exact proves bf16 closure, fp32 closure and coverage (tests/exact_data.py), for the second file also input-gradient closure and
-coverage -- and the comparison the GPU files rely on flags a single-ulp change."""
+"""The rounding-free data of tests/test_exact_gpu.py, tests/test_exact_families_gpu.py and tests/test_input_grad_exact_gpu.py, checked on the host: for
+every (model, batch size) the GPU files use, check_exact proves bf16 closure, fp32 closure and coverage (tests/exact_data.py), for the last file also
+input-gradient closure and coverage; the families' cases have the live base nodes their names claim, with non-zero gradients on the base paths -- and the
+comparison the GPU files rely on flags a single-ulp change, and a single wrong element of a base row or of a base-path gradient."""
 import pytest
 import torch
 
 from tests import exact_data as xd
 from tests import helpers
+from tests import test_exact_families_gpu as fam
 from tests import test_exact_gpu as gx
 from tests import test_input_grad_exact_gpu as igx
 
 CASES = sorted({("a1c2_L3", B) for B in gx.BATCHES + gx.TWO_CALL_BATCHES + [200]} | set(gx.WIDE_CASES) | {("a1c2_h200_L3", B) for B in gx.PADDED_BATCHES}
-               | {("mck4_cls_L3", B) for B in gx.CLS_BATCHES})
+               | {("mck4_cls_L3", B) for B in gx.CLS_BATCHES}) + fam.CASES
 
 
 @pytest.mark.parametrize("model,B", CASES)
@@ -20,6 +22,34 @@ def test_exact_case_is_rounding_free_and_covering(model, B):
     assert stats["fwd_sum_bound"] <= 1.0 and stats["bwd_sum_bound"] <= 1.0
     if spec.regression:      # the loss reference is the mean of squares over the chosen targets
         assert float(((ref["out"] - case["y"]) ** 2).mean()) == ref["loss"]
+    if model in fam.FAMILIES:
+        _check_live_base(model, spec, ref)
+
+
+def _base_path_tensors(spec):
+    """base_transform.*, every tensor of a relation into a base node, and the relation weight of one out of a base node (the root weight and the bias of a
+    relation act on its destination)."""
+    return [k for k in spec.param_shapes() if k.startswith("base_transform.") or "___base>" in k or ("<base___" in k and k.endswith("lin_rel.weight"))]
+
+
+def _check_live_base(model, spec, ref):
+    """What the family is in the matrix for: the encoder computes base nodes (every family but MiniCheetah-K4 regression at 3 layers, whose base is dead
+    as at every 3-layer GRF model), the base is a destination where the name says so, and every base-path tensor the oracle gives a gradient on random
+    data has a non-zero one here.  Coverage (c) implies the last; it is stated per family so that a change of knobs cannot go back to a dead base."""
+    live, need = spec.node_liveness()
+    dest = model.replace("_h256", "") in fam.BASE_IS_A_DESTINATION
+    assert bool(need[0]["base"]) == (model != "mck4_reg_L3"), (model, need[0]["base"])
+    if dest:
+        assert any(live[l]["base"] for l in range(spec.num_layers)), model
+    else:
+        assert not any(live[l]["base"] for l in range(spec.num_layers)), model
+    live_random = xd._live_nonzero_in_random_case(spec)
+    base_live = [k for k in _base_path_tensors(spec) if k in live_random]
+    assert bool(base_live) == bool(need[0]["base"]), model
+    if dest:
+        assert any("___base>" in k for k in base_live) and (not spec.has_base_transform or "base_transform.0.weight" in base_live), model
+    for k in base_live:
+        assert float(ref["grads"][k].abs().max()) > 0, f"{model}: {k} is live on random data and zero here"
 
 
 def test_comparison_flags_a_single_ulp():
@@ -34,6 +64,50 @@ def test_comparison_flags_a_single_ulp():
     got = ref.to(torch.bfloat16).clone()
     got[1] = 1.5 - 2.0 ** -7      # one bf16 ulp below 1.5
     assert xd.first_difference(got, ref) is not None
+
+
+@pytest.mark.parametrize("model", fam.BASE_IS_A_DESTINATION)
+def test_comparison_flags_one_element_of_the_base_destination_path(model):
+    """The comparisons of the GPU files, given the oracle's own reference with one element negated as "got": one element of a base row of X_1 (what a layer
+    with the base as a destination wrote), and one element of a gradient only that path feeds (base_transform.0.weight, on MI-HGNN a relation weight into
+    base).  Both must be reported, and nothing else: the family cases look at the base path."""
+    B = 17
+    spec, case, ref, _ = gx._reference.__wrapped__(model, B)
+    sl = helpers.node_slices(spec)
+    live, _ = spec.node_liveness()
+    assert live[0]["base"], model
+
+    class Got:      # (an engine whose stash holds the perturbed hidden states)
+        def __init__(self, hidden):
+            self.hidden = hidden
+
+        def hidden_state(self, B, l):
+            return self.hidden[l]
+
+    bad = []
+    gx._compare_hidden(bad, "ref", Got(ref["hidden"]), spec, ref, B, range(spec.num_layers + 1))
+    assert not bad
+    node = sl["base"].start + live[0]["base"][0]
+    row = ref["hidden"][1][:, node]
+    w, f = (int(i) for i in (row != 0).nonzero()[0])
+    hidden = [h.clone() for h in ref["hidden"]]
+    hidden[1][w, node, f] = -hidden[1][w, node, f]
+    gx._compare_hidden(bad, "negated", Got(hidden), spec, ref, B, range(spec.num_layers + 1))
+    assert len(bad) == 1 and "X1[base]" in bad[0] and "1 of " in bad[0] and f"window {w} (tile {w // 16}), node {node}, feature {f} " in bad[0], bad
+
+    key = "base_transform.0.weight" if spec.has_base_transform else next(k for k in ref["grads"] if "___base>" in k and k.endswith("lin_rel.weight")
+                                                                         and float(ref["grads"][k].abs().max()) > 0)
+    offs = spec.param_offsets()
+    flat = torch.zeros(spec.flat_size(), dtype=torch.float32)
+    for k, (off, n) in offs.items():
+        flat[off:off + n] = ref["grads"][k].reshape(-1).float()
+    bad = []
+    gx._compare_grads(bad, "ref", spec, flat, ref)
+    assert not bad
+    i = int((ref["grads"][key].reshape(-1) != 0).nonzero()[0])
+    flat[offs[key][0] + i] = -flat[offs[key][0] + i]
+    gx._compare_grads(bad, "negated", spec, flat, ref)
+    assert len(bad) == 1 and f"grad {key}:" in bad[0] and "1 of " in bad[0], bad
 
 
 def test_check_exact_refuses_a_rounding_case():
