@@ -377,7 +377,8 @@ int mshgnn_step_ce_series(const mshgnn_plan* plan, const mshgnn_window_desc* des
  * mshgnn_op_gemm: C[m ldc + n] (+)= sum_k A[m sAm + k sAk] B[n sBn + k sBk] (+ bias[n]) -- element strides, so the three products
  * of a Linear are one entry point: y = x W^T + b (A = x, B = W), dx = dy W (B = W with sBn = 1, sBk = in), dW = dy^T x (A = dy with
  * sAm = 1, sAk = out; B = x with sBn = 1, sBk = in: reduction over the rows, split-K with a fixed-order sum).
- * mshgnn_op_gemm_workspace: bytes of device workspace that shape needs (0: none).  accumulate != 0 adds into C.               */
+ * mshgnn_op_gemm_workspace: bytes of device workspace that shape needs (0: none).  accumulate != 0 adds into C.
+ * K == 0 is an empty sum (C (+)= bias; A and B are not read and may be null); M == 0 or N == 0 writes nothing.                   */
 int64_t mshgnn_op_gemm_workspace(int64_t M, int64_t N, int64_t K, int32_t* splits_out);
 int mshgnn_op_gemm(const float* A, int64_t sAm, int64_t sAk, const float* B, int64_t sBn, int64_t sBk, const float* bias,
                    float* C, int64_t ldc, int64_t M, int64_t N, int64_t K, int accumulate, void* workspace, void* stream);

@@ -146,7 +146,7 @@ extern "C" int mshgnn_op_gemm(const float* A, int64_t sAm, int64_t sAk, const fl
                               float* C, int64_t ldc, int64_t M, int64_t N, int64_t K, int accumulate, void* workspace, void* stream) {
     if (M < 0 || N < 0 || K < 0 || M > INT32_MAX || N > INT32_MAX || K > INT32_MAX) return set_err(MSHGNN_EINVAL, "mshgnn_op_gemm: bad shape");
     if (M == 0 || N == 0) return MSHGNN_OK;
-    if (!A || !B || !C) return set_err(MSHGNN_EINVAL, "mshgnn_op_gemm: null operand");
+    if (!C || (K > 0 && (!A || !B))) return set_err(MSHGNN_EINVAL, "mshgnn_op_gemm: null operand");      // (K == 0: A and B are never read -- the weight gradient of a Linear over zero rows)
     if (ldc < N) return set_err(MSHGNN_EINVAL, "mshgnn_op_gemm: ldc smaller than N");
     int32_t splits = 1;
     const int64_t need = mshgnn_op_gemm_workspace(M, N, K, &splits);

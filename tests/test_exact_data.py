@@ -10,6 +10,8 @@ from tests import helpers
 from tests import test_exact_families_gpu as fam
 from tests import test_exact_gpu as gx
 from tests import test_input_grad_exact_gpu as igx
+from tests import ops_reference as opr
+from tests import test_ops_exact_gpu as opx
 
 CASES = sorted({("a1c2_L3", B) for B in gx.BATCHES + gx.TWO_CALL_BATCHES + [200]} | set(gx.WIDE_CASES) | {("a1c2_h200_L3", B) for B in gx.PADDED_BATCHES}
                | {("mck4_cls_L3", B) for B in gx.CLS_BATCHES}) + fam.CASES
@@ -147,3 +149,24 @@ def test_enc_cover_changes_nothing_but_the_input_gradient():
         assert torch.equal(rp["grads"][k][..., keep], rc["grads"][k][..., keep]), k
     W = cover["params"]["encoder.lins.base.weight"]
     assert int((W != 0).any(0).sum()) > int((plain["params"]["encoder.lins.base.weight"] != 0).any(0).sum())
+
+
+@pytest.mark.parametrize("model,B", opx.MODEL_CASES)
+def test_operator_path_case_closes_in_the_operator_algebra(model, B):
+    """check_exact proves fp32 closure for the FUSED algebra (root weights pre-summed per destination type).  The operator-by-operator path
+    (models._forward_operators, tests/test_ops_exact_gpu.py) adds the same terms grouped per relation, so its sums of |terms| are larger: for exactly the
+    (family, batch, seed) triples that file runs, every Linear / GraphConv call proves, for its forward product(s), its aggregation and each of its backward
+    GEMMs and column sums, sum |terms| < 2^24 units of the terms' finest dyadic grid (ops_reference.operator_algebra raises otherwise) -- and the restated
+    algebra gives the oracle's output and gradients bit for bit, so it is the right algebra."""
+    spec, case, ref, _ = gx._reference.__wrapped__(model, B)
+    out, grads, worst = opr.operator_algebra(spec, case["params"], case["x"], spec.topology.edge_index_dict(B), B, ref["gout"])
+    assert torch.equal(out, ref["out"])
+    for k, r in ref["grads"].items():
+        g = grads[k] if grads[k] is not None else torch.zeros_like(r)
+        assert torch.equal(g, r), k
+    # (a call whose result cannot reach the output -- the last layer's relations into the other types -- has no backward and needs no proof: nothing compared
+    #  depends on it; every layer has calls that do)
+    assert "decoder" in worst and all(any(k.startswith(f"layer {l} ") for k in worst) for l in range(spec.num_layers)) and any(k.startswith("encoder.") for k in worst)
+    top = max(max(w.values()) for w in worst.values())
+    assert 0 < top < 1.0
+    print(f"\n{model} B={B}: {len(worst)} operator calls, largest sum of |terms| {top:.2e} of the fp32 limit")

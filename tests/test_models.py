@@ -247,6 +247,7 @@ def test_non_relu_activation_runs_operator_by_operator(name):
     assert abs(float(loss) - float(l_ref)) <= 1e-4 * abs(float(l_ref))
     for k, p in m.named_parameters():
         ref = leaves[k].grad
+        assert p.grad is None or not bool(torch.isnan(p.grad).any()), f"{k}: the gradient holds a NaN"      # (a max-abs comparison lets a NaN through)
         if ref is None or float(ref.abs().max()) == 0.0:
             assert p.grad is None or float(p.grad.abs().max()) == 0.0, k
         else:
