@@ -370,6 +370,26 @@ int mshgnn_step_ce_series(const mshgnn_plan* plan, const mshgnn_window_desc* des
                           void* const* x_out, const int64_t* x_pitch, float* y_out, int32_t* labels_out, void* run_ptrs,
                           const float* params, float* out, float* loss_out, float* grad_params, void* workspace, void* stream);
 
+/* Evaluation straight from a sequence's resident raw series: mshgnn_assemble_windows + mshgnn_forward(training = 0) in one call, with the window gather fused
+ * into the encoder and NO materialised windows at all -- results are bit-identical to that pair.  `workspace` is one laid out for training = 0; nothing is
+ * stashed.  Same plans as mshgnn_step_*_series: the bf16 plan with the fused stack kernels (src_bf16 as there) and the split plan MSHGNN_BF16X3 (fp32 series,
+ * src_bf16 may be NULL); the fp32 plan, the generic-width engine (MSHGNN_EUNSUPPORTED) and descriptors whose node types differ from the plan's (MSHGNN_EINVAL)
+ * are refused.  The stack launch is the one mshgnn_forward(training = 0) runs, compile-time programs included.
+ * By-products, each optional (NULL: not computed): y_out fp32 [batch][n_label], quat_out fp32 [batch][4], labels_out int32 [batch][n_label] (y != 0, the
+ * classification wrappers' contact flags; needs y_out).  A sequence without labels passes NULL for all three; the descriptor's label fields are then not read.
+ * STANDARDISED recipes (desc->normalize != 0, history in [2, 256]) are accepted here: every run with a source column is standardised over its window,
+ * (x - mean) / sd with Bessel's correction in fp64, NaN -> 0, then rounded to fp32 (and to bf16 on the bf16 plan) exactly as mshgnn_assemble_windows does --
+ * one shared device function computes both.  A pre-pass writes {mean, sd} of every (window, run) into `stats` (device scratch, 16-byte aligned,
+ * mshgnn_forward_series_stats_bytes(desc, batch) = batch * n_runs * 16 bytes; 0 and `stats` ignored for unstandardised recipes); the encoder then reads the
+ * FP32 series on both plans (src_bf16 may be NULL on the bf16 plan too).  The training entry points above keep refusing standardised recipes.
+ * run_ptrs / desc->run_ptrs_ready as in mshgnn_step_mse_series; the pointers are those of the series the encoder reads, so a scratch filled by a
+ * mshgnn_step_*_series call with the same (unstandardised) descriptor and sources may be vouched for here and the other way round.                        */
+int mshgnn_forward_series(const mshgnn_plan* plan, const mshgnn_window_desc* desc, const float* const* src, const void* const* src_bf16,
+                          const int64_t* src_cstride, const int64_t* src_rows, const int64_t* starts /* device int64[batch] */, int64_t batch,
+                          float* y_out /* nullable */, float* quat_out /* nullable */, int32_t* labels_out /* nullable */,
+                          void* run_ptrs, void* stats /* standardised recipes only */, const float* params, float* out, void* workspace, void* stream);
+int64_t mshgnn_forward_series_stats_bytes(const mshgnn_window_desc* desc, int64_t batch);
+
 /* ---- stand-alone operators behind the four torch_geometric.nn names ----------------------------------
  * For a maintainer who swaps only the PyG import (hgnn_c2.py:3): Linear / HeteroDictLinear (hgnn_c2.py:88,131), GraphConv
  * (hgnn_c2.py:100-112) and their autograd backward on arbitrary graphs and widths, fp32 operands, fp32 MFMA, no float atomics.

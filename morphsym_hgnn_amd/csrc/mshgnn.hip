@@ -109,8 +109,12 @@ __device__ __forceinline__ u32x4 splice8(u32x4 A, u32x4 B, int n0) {      // bf1
 }
 // SRC (bf16, ALIGNED; 8 / 4): the rows come from the caller's own fp64 / fp32 tensors at their dense pitch (WideSrc), are converted in registers and ALSO
 // written to a.x as plan-dtype rows for the weight-gradient kernel -- the cast + re-pitch pass fused into the encoder (mshgnn_*_src entry points).
-template <typename T, bool ALIGNED, bool SERIES = false, int SRC = 0> __global__ __launch_bounds__(256) void k_enc_fwd(EncArgs a, SeriesSrc ser, WideSrc wsrc) {
+// NORM (with SERIES; mshgnn_forward_series on a standardised recipe): the chunk's 8 elements come from the FP32 series (two 4-byte-aligned 16-byte loads per
+// piece, as k_enc_x3<.., SERIES>) and every run with a source column is standardised over its window with the statistics k_series_stats left in ser.stats --
+// fp64 -> fp32 -> bf16, the roundings of mshgnn_assemble_windows(normalize) (standardise_one, mshgnn_device.hpp); nothing is materialised.
+template <typename T, bool ALIGNED, bool SERIES = false, int SRC = 0, bool NORM = false> __global__ __launch_bounds__(256) void k_enc_fwd(EncArgs a, SeriesSrc ser, WideSrc wsrc) {
     using P = Prec<T>;
+    static_assert(!NORM || SERIES, "standardisation is part of the series gather");
     static_assert(!SERIES || (sizeof(T) == 2 && ALIGNED), "the series gather is a bf16 path");
     static_assert(SRC == 0 || (sizeof(T) == 2 && ALIGNED && !SERIES), "wide source rows: bf16 plan, aligned destination rows");
     constexpr int MB = P::ENC_MB;                       // row blocks (of 16 windows) per workgroup
@@ -160,6 +164,10 @@ template <typename T, bool ALIGNED, bool SERIES = false, int SRC = 0> __global__
     const int64_t spitch = SRC ? wsrc.pitch[t] : 0;
     // SERIES: first series row of this thread's window rows, the node row's first run
     int srow[SERIES ? MB / BPP : 1];
+    // NORM: the chunk's fp32 elements, the statistics of its two runs per window, and how the chunk divides between them (set by fetch, read by the next staging pass)
+    u32x4 vn[NORM ? MB / BPP : 1][2];
+    RunStats rsa[NORM ? MB / BPP : 1], rsb[NORM ? MB / BPP : 1];
+    int n_n0 = 8; bool n_has_a = false, n_has_b = false;
     __shared__ unsigned long long rp_s[SERIES ? 16 : 1];      // SERIES: the column pointers of this node row's first 16 runs (a chunk takes its pieces from runs j, j + 1)
     int rfirst = 0, rend = 0;
     if constexpr (SERIES) {
@@ -180,6 +188,35 @@ template <typename T, bool ALIGNED, bool SERIES = false, int SRC = 0> __global__
             // (runs past the 16th -- a node row of more than 16 T-long variables -- come from the global table: a dependent load, rare recipes only)
             auto run_ptr_of = [&](int jj) -> unsigned long long { return jj < 16 ? rp_s[jj] : (rfirst + jj < rend ? ser.run_ptr[rfirst + jj] : 0ull); };
             const unsigned long long pa = nvalid > 0 ? run_ptr_of(j) : 0ull, pb = second ? run_ptr_of(j + 1) : 0ull;
+            if constexpr (NORM) {
+                n_n0 = n0; n_has_a = pa != 0ull; n_has_b = pb != 0ull;
+                const u32x4 ones32 = u32x4{0x3f800000u, 0x3f800000u, 0x3f800000u, 0x3f800000u};      // the constant-1 run
+#pragma unroll
+                for (int mi = 0; mi < MB / BPP; ++mi) {
+                    u32x4 a0 = nvalid > 0 ? ones32 : u32x4{0, 0, 0, 0}, a1 = a0;
+                    // (the window of this thread's row: rows past the batch repeat the last window, as srow does)
+                    const double* sp2 = ser.stats + ((size_t)min(w0 + (mi * BPP + sub) * P::ROWS + r0, a.B - 1) * ser.n_runs + rfirst + j) * 2;
+                    rsa[mi] = RunStats{0.0, 1.0}; rsb[mi] = RunStats{0.0, 1.0};
+                    if (pa) {      // (4-byte aligned; the second load may run up to 7 elements past the window's last step: the columns' slack)
+                        const float* sp = reinterpret_cast<const float*>(pa) + srow[mi] + off;
+                        a0 = *reinterpret_cast<const u32x4*>(sp); a1 = *reinterpret_cast<const u32x4*>(sp + 4);
+                        const f64x2 sv = *reinterpret_cast<const f64x2*>(sp2);
+                        rsa[mi] = RunStats{sv[0], sv[1]};
+                    }
+                    if (second) {
+                        u32x4 b0 = ones32, b1 = ones32;
+                        if (pb) {
+                            const float* sp = reinterpret_cast<const float*>(pb) + srow[mi];
+                            b0 = *reinterpret_cast<const u32x4*>(sp); b1 = *reinterpret_cast<const u32x4*>(sp + 4);
+                            const f64x2 sv = *reinterpret_cast<const f64x2*>(sp2 + 2);
+                            rsb[mi] = RunStats{sv[0], sv[1]};
+                        }
+                        splice8f(a0, a1, b0, b1, n0);
+                    }
+                    vn[mi][0] = a0; vn[mi][1] = a1;
+                }
+                return;
+            }
             const u32x4 ones = u32x4{0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u};      // the constant-1 run (bf16 1.0)
 #pragma unroll
             for (int mi = 0; mi < MB / BPP; ++mi) {
@@ -234,6 +271,11 @@ template <typename T, bool ALIGNED, bool SERIES = false, int SRC = 0> __global__
                     f32x4 lo4, hi4;
                     wide_to_f32<SRC>(wv8[mi], nv, lo4, hi4);
                     raw = pack_oct(lo4, hi4);
+                } else if constexpr (NORM) {
+                    u32x4 a0 = vn[mi][0], a1 = vn[mi][1];
+                    standardise_oct(a0, a1, n_n0, n_has_a, n_has_b, rsa[mi], rsb[mi]);
+                    raw = pack_oct(__builtin_bit_cast(f32x4, a0), __builtin_bit_cast(f32x4, a1));
+                    if (kc + 1 == nkc) raw = chunk_keep_first<T>(raw, nv);
                 } else
                 raw = kc + 1 == nkc ? chunk_keep_first<T>(v[mi][it], nv) : v[mi][it];      // only the last K chunk has pad columns
                 *reinterpret_cast<u32x4*>(smem + lds_chunk<T>(mi * BPP + sub, r0 + it * (256 / P::CPR), c)) = raw ^ sx;
@@ -2759,8 +2801,10 @@ static int forward_impl(const mshgnn_plan* p, const void* const* x, const int64_
         if constexpr (sizeof(T) == 2) {
             if (series) {
                 if (x && !a.aligned) return set_err(MSHGNN_EINVAL, "the fused window assembly needs 16-byte aligned window rows (pitch a multiple of 8)");
+                if (series->stats && x) return set_err(MSHGNN_EINVAL, "the standardising series encoder materialises no windows");
                 enc_grid += (unsigned)((series->lab.B + 255) / 256);      // the label workgroups
-                hipLaunchKernelGGL((k_enc_fwd<T, true, true>), dim3(enc_grid), dim3(256), Prec<T>::ENC_MB * Prec<T>::BLK, st, a, *series, WideSrc{});
+                if (series->stats) hipLaunchKernelGGL((k_enc_fwd<T, true, true, 0, true>), dim3(enc_grid), dim3(256), Prec<T>::ENC_MB * Prec<T>::BLK, st, a, *series, WideSrc{});
+                else hipLaunchKernelGGL((k_enc_fwd<T, true, true>), dim3(enc_grid), dim3(256), Prec<T>::ENC_MB * Prec<T>::BLK, st, a, *series, WideSrc{});
             } else if (wide) {      // the caller's fp64 / fp32 rows: converted by the encoder, plan-dtype rows written to x on the side
                 if (x && !a.aligned) return set_err(MSHGNN_EINVAL, "wide source rows: the plan-dtype rows need 16-byte alignment and a pitch that is a multiple of 8");
                 if (wide->bytes == 8) hipLaunchKernelGGL((k_enc_fwd<T, true, false, 8>), dim3(enc_grid), dim3(256), Prec<T>::ENC_MB * Prec<T>::BLK, st, a, SeriesSrc{}, *wide);
@@ -3709,17 +3753,11 @@ template <typename T, int NSET> __global__ __launch_bounds__(256) void k_assembl
                 const bool has_src = (rl(v_lo, r) | rl(v_hi, r)) != 0;
                 T* dst = reinterpret_cast<T*>(a.x[t]) + (size_t)b * a.nodes[t] * a.x_pitch[t] + doff;
                 if (a.normalize && has_src) {
-                    // (x - mean) / std with the unbiased estimator, NaN -> 0 (flexibleDataset.py:390-396); fp64, two passes over registers
-                    double s1 = 0.0;
+                    // (x - mean) / std with the unbiased estimator, NaN -> 0 (flexibleDataset.py:390-396); fp64, two passes over registers.  The arithmetic
+                    // is run_stats / standardise_one (mshgnn_device.hpp), shared with the standardising series encoders of mshgnn_forward_series
+                    const RunStats rs = run_stats(v[i], len, lane);
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) if (2 * lane + 128 * (q >> 1) + (q & 1) < len) s1 += (double)v[i][q];
-                    const double mean = wave_sum(s1) / (double)len;
-                    double qs = 0.0;
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) if (2 * lane + 128 * (q >> 1) + (q & 1) < len) { const double dlt = (double)v[i][q] - mean; qs += dlt * dlt; }
-                    const double sd = sqrt(wave_sum(qs) / (double)(len - 1));
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) { const double z = ((double)v[i][q] - mean) / sd; v[i][q] = z == z ? (float)z : 0.0f; }
+                    for (int q = 0; q < 4; ++q) v[i][q] = standardise_one(v[i][q], rs.mean, rs.sd);
                 }
                 const bool even = ((doff | len) & 1) == 0;
 #pragma unroll
@@ -3978,5 +4016,110 @@ extern "C" int mshgnn_step_ce_series(const mshgnn_plan* p, const mshgnn_window_d
     if (!labels_out) return set_err(MSHGNN_EINVAL, "null argument to mshgnn_step_ce_series");
     return step_series(p, d, src, src_bf16, src_cstride, src_rows, starts, batch, x_out, x_pitch, y_out, nullptr, run_ptrs, params, out, loss_out, grad_params,
                        workspace, stream, labels_out);
+}
+// ------------------------------------------------------------------------------------------------------
+// mshgnn_forward_series: evaluation straight from a sequence's resident raw series -- mshgnn_assemble_windows + mshgnn_forward(training = 0) with the window
+// gather fused into the encoder and NO materialised windows (x = NULL: only the nodes whose X_0 can reach the output get encoder workgroups).  Labels,
+// quaternions and contact flags come out of the encoder launch's extra workgroups, each optional.  Standardised recipes: a pre-pass leaves {mean, sd} of every
+// (window, run) in the caller's scratch (k_series_stats: one wave per run, the per-lane partial sums and the wave_sum order of k_assemble_windows -- the same
+// function, run_stats), the NORM encoders apply them to the fp32 series (standardise_one).
+// ------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_series_stats(const int* runs, int n_runs, const unsigned long long* run_ptr, const int64_t* starts, int64_t B, double* stats) {
+    const int lane = threadIdx.x & 63;
+    const int64_t idx = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);      // (window, run): one wave each
+    if (idx >= B * n_runs) return;
+    const int64_t b = idx / n_runs; const int r = (int)(idx - b * n_runs);
+    const int len = runs[(size_t)r * 5 + 4];
+    const unsigned long long p = run_ptr[r];
+    RunStats rs{0.0, 1.0};      // constant-one runs are left alone (never applied)
+    if (p) {
+        const float* sp = reinterpret_cast<const float*>(p) + starts[b];
+        float v[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int k = 2 * lane + 128 * (q >> 1) + (q & 1);
+            v[q] = 1.0f;
+            if (k < len) v[q] = sp[k];
+        }
+        rs = run_stats(v, len, lane);
+    }
+    if (lane == 0) *reinterpret_cast<f64x2*>(stats + (size_t)idx * 2) = f64x2{rs.mean, rs.sd};
+}
+
+extern "C" int64_t mshgnn_forward_series_stats_bytes(const mshgnn_window_desc* d, int64_t batch) {
+    if (!d || batch < 1 || d->n_runs < 1 || !d->normalize) return 0;
+    return batch * (int64_t)d->n_runs * 2 * (int64_t)sizeof(double);
+}
+
+extern "C" int mshgnn_forward_series(const mshgnn_plan* p, const mshgnn_window_desc* d, const float* const* src, const void* const* src_bf16,
+                                     const int64_t* src_cstride, const int64_t* src_rows, const int64_t* starts, int64_t batch,
+                                     float* y_out, float* quat_out, int32_t* labels_out, void* run_ptrs, void* stats, const float* params, float* out,
+                                     void* workspace, void* stream) {
+    if (!p || !d || !src || !src_cstride || !src_rows || !starts || !run_ptrs || !params || !out || !workspace)
+        return set_err(MSHGNN_EINVAL, "null argument to mshgnn_forward_series");
+    if (batch < 1 || batch > (1 << 24)) return set_err(MSHGNN_EINVAL, "batch must be in [1, 2^24]");
+    const bool x3 = !p->gen && p->hp.d.dtype == MSHGNN_BF16X3;
+    if (p->gen || (!x3 && (p->hp.d.dtype != MSHGNN_BF16 || !p->use_fused)))
+        return set_err(MSHGNN_EUNSUPPORTED, "mshgnn_forward_series runs on the bf16 plan with the fused stack kernels or on the split plan; use mshgnn_assemble_windows + mshgnn_forward");
+    const bool norm = d->normalize != 0;
+    if (!x3 && !norm && !src_bf16) return set_err(MSHGNN_EINVAL, "null argument to mshgnn_forward_series (the bf16 plan gathers unstandardised windows from the bf16 copies)");
+    if (norm && !stats) return set_err(MSHGNN_EINVAL, "mshgnn_forward_series: a standardised recipe needs the stats scratch (mshgnn_forward_series_stats_bytes)");
+    if (norm && d->history < 2) return set_err(MSHGNN_EINVAL, "history must be >= 2 when normalising");
+    if (norm && d->history > 256) return set_err(MSHGNN_EUNSUPPORTED, "history longer than 256 steps is not supported by this build");
+    if (norm && ((uintptr_t)stats & 15)) return set_err(MSHGNN_EINVAL, "mshgnn_forward_series: the stats scratch must be 16-byte aligned");
+    const mshgnn_desc& md = p->hp.d;
+    const bool dtype_ok = x3 ? (d->dtype == MSHGNN_F32 || d->dtype == MSHGNN_BF16X3) : d->dtype == MSHGNN_BF16;
+    if (d->n_types != md.n_types || !dtype_ok || !d->fast_layout || d->n_src < 1 || d->n_src > WIN_MAX_SRC || d->n_runs < 1 || d->n_runs > WIN_MAX_RUNS || !d->runs ||
+        !d->rows || d->history < 1)
+        return set_err(MSHGNN_EINVAL, "mshgnn_forward_series: the window descriptor must be a fast_layout recipe at the plan's input dtype (bf16; split plan: fp32)");
+    int n_rows = 0;
+    for (int t = 0; t < d->n_types; ++t) {
+        if (d->type_nodes[t] != md.type_nodes[t] || d->type_width[t] != md.type_width[t]) return set_err(MSHGNN_EINVAL, "window recipe and plan disagree on a node type");
+        n_rows += d->type_nodes[t];
+    }
+    if (n_rows != d->n_rows) return set_err(MSHGNN_EINVAL, "window recipe: one node row per node expected");
+    // the encoders take a chunk's 8 elements from at most two runs: windows shorter than a chunk are taken only where every node row is a single run
+    if (d->history < 8 && d->n_runs > d->n_rows) return set_err(MSHGNN_EUNSUPPORTED, "mshgnn_forward_series: node rows of several runs need history >= 8; use mshgnn_assemble_windows + mshgnn_forward");
+    const bool want_y = y_out != nullptr;
+    if (labels_out && !want_y) return set_err(MSHGNN_EINVAL, "mshgnn_forward_series: labels_out comes with y_out");
+    if (want_y) {
+        if (d->n_label < 1 || !d->label_cols || d->label_src < 0 || d->label_src >= d->n_src) return set_err(MSHGNN_EINVAL, "bad label description");
+        // the label rows are the model's targets: per out node its out_channels values, or (labels_out: the classification wrappers) one contact flag
+        if (d->n_label != md.type_nodes[md.out_type] * (labels_out ? 1 : md.out_channels))
+            return set_err(MSHGNN_EINVAL, "window recipe: label count differs from the model's outputs");
+        if (d->label_rotate && (d->n_label % 3 != 0 || d->quat_src < 0)) return set_err(MSHGNN_EINVAL, "label rotation needs 3-D labels and a quaternion source");
+        if (labels_out && d->label_rotate) return set_err(MSHGNN_EINVAL, "mshgnn_forward_series: contact labels are not rotated");
+    }
+    if (d->quat_src >= d->n_src) return set_err(MSHGNN_EINVAL, "quat_src out of range");
+    const bool fp32_gather = x3 || norm;      // standardisation happens before the bf16 rounding: the bf16 plan's NORM encoder reads the fp32 series too
+    WindowArgs wa{};
+    for (int i = 0; i < d->n_src; ++i) {
+        // (8 elements of slack behind every column: a chunk's 16-byte loads may run past the window's last step)
+        if (!src[i] || (!fp32_gather && !src_bf16[i]) || src_rows[i] < d->history || src_cstride[i] < src_rows[i] + 8 || src_rows[i] >= (1ll << 31)) return set_err(MSHGNN_EINVAL, "bad source array (the gather needs cstride >= rows + 8)");
+        wa.src[i] = fp32_gather ? src[i] : reinterpret_cast<const float*>(src_bf16[i]); wa.src_cstride[i] = src_cstride[i];
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (!d->run_ptrs_ready)
+        hipLaunchKernelGGL(k_series_run_ptrs, dim3(1), dim3(256), 0, st, d->runs, d->n_runs, wa, fp32_gather ? 4 : 2, reinterpret_cast<unsigned long long*>(run_ptrs));
+    SeriesSrc ser{};
+    const bool want_q = quat_out != nullptr && d->quat_src >= 0;
+    if (want_y || want_q) {      // labels: extra workgroups of the encoder launch (a test sequence without labels: none)
+        LabelArgs& l = ser.lab;
+        const int ls = want_y ? d->label_src : 0;
+        l.lab = src[ls]; l.lab_cs = src_cstride[ls];
+        const bool q = d->quat_src >= 0 && (want_q || d->label_rotate);
+        l.quat_src = q ? src[d->quat_src] : nullptr; l.quat_cs = q ? src_cstride[d->quat_src] : 0;
+        l.starts = starts; l.B = batch; l.T = d->history; l.label_cols = d->label_cols; l.n_label = want_y ? d->n_label : 0; l.label_rotate = want_y ? d->label_rotate : 0;
+        l.y = y_out; l.quat = quat_out; l.labels_int = labels_out;
+    }
+    ser.run_ptr = reinterpret_cast<const unsigned long long*>(run_ptrs); ser.rows = d->rows; ser.starts = starts; ser.T = d->history;
+    { int r0 = 0; for (int t = 0; t < d->n_types; ++t) { ser.row0[t] = r0; r0 += d->type_nodes[t]; } }
+    if (norm) {
+        const int64_t waves = batch * d->n_runs;
+        hipLaunchKernelGGL(k_series_stats, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, d->runs, d->n_runs, ser.run_ptr, starts, batch, reinterpret_cast<double*>(stats));
+        ser.stats = reinterpret_cast<const double*>(stats); ser.n_runs = d->n_runs;
+    }
+    if (x3) return x3_forward(p, nullptr, nullptr, params, out, (char*)workspace, batch, 0, st, nullptr, &ser, nullptr, nullptr);
+    return forward_impl<__bf16>(p, nullptr, nullptr, params, out, (char*)workspace, batch, 0, st, nullptr, &ser, nullptr, nullptr);
 }
 #endif      // MSHGNN_SPEC_SHARD == 0

@@ -20,6 +20,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef double f64x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 // once-read streams (raw inputs): optional non-temporal loads, a build-time experiment switch (EXTRA=-DENC_NT=1 / -DGW_NT=1|2)
@@ -450,7 +451,75 @@ struct SeriesSrc {
     int row0[MSHGNN_MAX_TYPES];          // first node row of each type
     int T;
     LabelArgs lab;                       // the batch's labels: computed by extra workgroups of the fused-gather encoder launch (lab.B == 0: none)
+    const double* stats;                 // standardised recipes (mshgnn_forward_series): {mean, sd} of every (window, run), [B][n_runs][2] (k_series_stats)
+    int n_runs;
 };
+
+// Per-window standardisation of one run (flexibleDataset.py:390-396): (x - mean) / sd with the unbiased estimator, in fp64, NaN -> 0.  THE arithmetic of
+// mshgnn_assemble_windows(normalize) and of the standardising series encoders (mshgnn_forward_series): both call these two functions, so the bits agree by
+// construction -- contraction is off inside them and the one fused multiply-add is written out, so the compiler cannot fuse differently at two call sites.
+struct RunStats { double mean, sd; };
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+// lane `lane` of the wave holds elements 2 lane + 128 (q >> 1) + (q & 1), q = 0 .. 3, of the run's `len` (<= 256) elements
+__device__ __forceinline__ RunStats run_stats(const float (&v)[4], int len, int lane) {
+#pragma clang fp contract(off)
+    double s1 = 0.0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) if (2 * lane + 128 * (q >> 1) + (q & 1) < len) s1 += (double)v[q];
+    RunStats r;
+    r.mean = wave_sum_f64(s1) / (double)len;
+    double qs = 0.0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) if (2 * lane + 128 * (q >> 1) + (q & 1) < len) { const double dlt = (double)v[q] - r.mean; qs = fma(dlt, dlt, qs); }
+    r.sd = sqrt(wave_sum_f64(qs) / (double)(len - 1));
+    return r;
+}
+__device__ __forceinline__ float standardise_one(float x, double mean, double sd) {
+#pragma clang fp contract(off)
+    const double z = ((double)x - mean) / sd;
+    float f = z == z ? (float)z : 0.0f;
+    asm volatile("" : "+v"(f));      // the fp32 value must exist: a following bf16 conversion is a second rounding (as torch's), never folded into fp64 -> bf16
+    return f;
+}
+
+// out[e] = e < n0 ? a[e] : b[e - n0] over the 8 fp32 elements (a0 | a1), (b0 | b1): the second piece of a chunk that straddles two runs of a
+// window row (the fp32 series gathers); b is moved up by n0 elements in three conditional stages (4, 2, 1), n0 in [1, 7] is per thread
+__device__ __forceinline__ void splice8f(u32x4& a0, u32x4& a1, const u32x4 b0, const u32x4 b1, int n0) {
+    unsigned sft[8] = {b0[0], b0[1], b0[2], b0[3], b1[0], b1[1], b1[2], b1[3]};
+    if (n0 & 4) {
+#pragma unroll
+        for (int e = 7; e >= 4; --e) sft[e] = sft[e - 4];
+    }
+    if (n0 & 2) {
+#pragma unroll
+        for (int e = 7; e >= 2; --e) sft[e] = sft[e - 2];
+    }
+    if (n0 & 1) {
+#pragma unroll
+        for (int e = 7; e >= 1; --e) sft[e] = sft[e - 1];
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        a0[e] = e < n0 ? a0[e] : sft[e];
+        a1[e] = e + 4 < n0 ? a1[e] : sft[e + 4];
+    }
+}
+// 8 fp32 elements of a standardised window row: elements [0, n0) belong to a run with statistics sa, the rest to the next run (sb); has_a / has_b: the run
+// has a source column (constant-one runs are left alone)
+__device__ __forceinline__ void standardise_oct(u32x4& a0, u32x4& a1, int n0, bool has_a, bool has_b, RunStats sa, RunStats sb) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const bool first = e < n0;
+        const float x = __builtin_bit_cast(float, e < 4 ? a0[e & 3] : a1[e & 3]);
+        const float z = standardise_one(x, first ? sa.mean : sb.mean, first ? sa.sd : sb.sd);
+        const unsigned r = __builtin_bit_cast(unsigned, (first ? has_a : has_b) ? z : x);
+        if (e < 4) a0[e & 3] = r; else a1[e & 3] = r;
+    }
+}
 
 // WIDE SOURCE ROWS (mshgnn_*_src entry points): the encoder reads the reference's own tensors -- fp64 (the reference's default dtype, gnnLightning.py:1183) or fp32,
 // at their dense pitch -- converts in registers and writes the plan-dtype rows at the engine's pitch on the side (what the weight-gradient kernel reads

@@ -83,35 +83,15 @@ __global__ void k_prep_x3(PrepArgs a) { prep_one_x3(a, blockIdx.x * blockDim.x +
 // k_enc_x3: X_0[node] = relu((mask . x) W_enc^T + b) from fp32 inputs (hgnn_c2.py:143-147); one workgroup = 64 windows of ONE
 // node, K streamed in chunks of 128 through LDS (hi blocks [0, 4), lo blocks [4, 8)), the next chunk prefetched in registers
 // ------------------------------------------------------------------------------------------------------
-// out[e] = e < n0 ? a[e] : b[e - n0] over the 8 fp32 elements (a0 | a1), (b0 | b1): the second piece of a chunk that straddles two runs of a
-// window row (k_enc_x3<.., SERIES>); b is moved up by n0 elements in three conditional stages (4, 2, 1), n0 in [1, 7] is per thread
-__device__ __forceinline__ void splice8f(u32x4& a0, u32x4& a1, const u32x4 b0, const u32x4 b1, int n0) {
-    unsigned sft[8] = {b0[0], b0[1], b0[2], b0[3], b1[0], b1[1], b1[2], b1[3]};
-    if (n0 & 4) {
-#pragma unroll
-        for (int e = 7; e >= 4; --e) sft[e] = sft[e - 4];
-    }
-    if (n0 & 2) {
-#pragma unroll
-        for (int e = 7; e >= 2; --e) sft[e] = sft[e - 2];
-    }
-    if (n0 & 1) {
-#pragma unroll
-        for (int e = 7; e >= 1; --e) sft[e] = sft[e - 1];
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        a0[e] = e < n0 ? a0[e] : sft[e];
-        a1[e] = e + 4 < n0 ? a1[e] : sft[e + 4];
-    }
-}
-
 // SERIES (with ALIGNED): the fp32 inputs are gathered from the sequence's resident series like the bf16 encoder's (k_enc_fwd<.., SERIES>): element k
 // of a node row = element starts[w] + k % T of run k / T -- two 4-byte-aligned 16-byte loads per (window, chunk), four and a splice where the chunk
 // straddles two runs -- and the materialised window rows are written on the side for the weight-gradient pass (a.x: the window buffers).
 // SRC (8 / 4, with ALIGNED): the rows come from the caller's own fp64 / fp32 tensors at their dense pitch (WideSrc, mshgnn_device.hpp) and are also written to
 // a.x as fp32 rows at the engine's pitch for the weight-gradient kernel (mshgnn_*_src entry points)
-template <bool ALIGNED, bool SERIES = false, int SRC = 0> __global__ __launch_bounds__(256) void k_enc_x3(EncArgs a, int n_img, SeriesSrc ser, WideSrc wsrc) {
+// NORM (with SERIES; mshgnn_forward_series on a standardised recipe): every run with a source column is standardised over its window with the statistics
+// k_series_stats left in ser.stats (standardise_one, mshgnn_device.hpp: the arithmetic of mshgnn_assemble_windows(normalize)); nothing is materialised.
+template <bool ALIGNED, bool SERIES = false, int SRC = 0, bool NORM = false> __global__ __launch_bounds__(256) void k_enc_x3(EncArgs a, int n_img, SeriesSrc ser, WideSrc wsrc) {
+    static_assert(!NORM || SERIES, "standardisation is part of the series gather");
     static_assert(!SERIES || ALIGNED, "the series gather writes aligned window buffers");
     static_assert(SRC == 0 || (ALIGNED && !SERIES), "wide source rows: aligned destination rows, no series gather");
     using P = P16;
@@ -156,6 +136,9 @@ template <bool ALIGNED, bool SERIES = false, int SRC = 0> __global__ __launch_bo
     const bool unit_ok = SRC == 8 || (F & 1) == 0;
     const int64_t spitch = SRC ? wsrc.pitch[t] : 0;
     int srow[SERIES ? MB : 1]; int rfirst = 0;  // SERIES: first series row of this thread's window rows, the node row's first run
+    // NORM: the statistics of the chunk's two runs per window, and how the chunk divides between them (set by fetch, read by the next staging pass)
+    RunStats rsa[NORM ? MB : 1], rsb[NORM ? MB : 1];
+    int n_n0 = 8; bool n_has_a = false, n_has_b = false;
     if constexpr (SERIES) {
 #pragma unroll
         for (int m = 0; m < MB; ++m) srow[m] = (int)ser.starts[min(w0 + m * P::ROWS + r0, a.B - 1)];
@@ -170,9 +153,16 @@ template <bool ALIGNED, bool SERIES = false, int SRC = 0> __global__ __launch_bo
             const bool second = min(nv, 8) > n0;
             const unsigned long long pa = nv > 0 ? ser.run_ptr[rfirst + j] : 0ull, pb = second ? ser.run_ptr[rfirst + j + 1] : 0ull;
             const u32x4 ones = u32x4{0x3f800000u, 0x3f800000u, 0x3f800000u, 0x3f800000u};      // the constant-1 run
+            if constexpr (NORM) { n_n0 = n0; n_has_a = pa != 0ull; n_has_b = pb != 0ull; }
 #pragma unroll
             for (int m = 0; m < MB; ++m) {
                 u32x4 a0 = nv > 0 ? ones : u32x4{0, 0, 0, 0}, a1 = a0;
+                if constexpr (NORM) {      // (rows past the batch repeat the last window, as srow does)
+                    const double* sp2 = ser.stats + ((size_t)min(w0 + m * P::ROWS + r0, a.B - 1) * ser.n_runs + rfirst + j) * 2;
+                    rsa[m] = RunStats{0.0, 1.0}; rsb[m] = RunStats{0.0, 1.0};
+                    if (pa) { const f64x2 sv = *reinterpret_cast<const f64x2*>(sp2); rsa[m] = RunStats{sv[0], sv[1]}; }
+                    if (pb) { const f64x2 sv = *reinterpret_cast<const f64x2*>(sp2 + 2); rsb[m] = RunStats{sv[0], sv[1]}; }
+                }
                 if (pa) {      // (4-byte aligned; the second load may run up to 7 elements past the window's last step: the columns' slack)
                     const float* sp = reinterpret_cast<const float*>(pa) + srow[m] + off;
                     a0 = *reinterpret_cast<const u32x4*>(sp); a1 = *reinterpret_cast<const u32x4*>(sp + 4);
@@ -230,7 +220,10 @@ template <bool ALIGNED, bool SERIES = false, int SRC = 0> __global__ __launch_bo
                 wide_to_f32<SRC>(wv8[m], nv, lo4, hi4);
                 fa = __builtin_bit_cast(u32x4, lo4); fb = __builtin_bit_cast(u32x4, hi4);
             } else
-            if (kc + 1 == nkc) { fa = chunk_keep_first<float>(fa, nv); fb = chunk_keep_first<float>(fb, nv - 4); }     // only the last K chunk has pad columns
+            {
+                if constexpr (NORM) standardise_oct(fa, fb, n_n0, n_has_a, n_has_b, rsa[m], rsb[m]);
+                if (kc + 1 == nkc) { fa = chunk_keep_first<float>(fa, nv); fb = chunk_keep_first<float>(fb, nv - 4); }     // only the last K chunk has pad columns
+            }
             if constexpr (SERIES || SRC > 0) {      // the materialised window row (raw values: the sign mask is applied by whoever reads it)
                 const int w = w0 + m * P::ROWS + r0, k0 = kc * H + c * 8;
                 if (x != nullptr && w < a.B) {
@@ -1332,9 +1325,9 @@ int x3_forward(const mshgnn_plan* p, const void* const* x, const int64_t* x_pitc
         a.n_types = hp.NT; a.B = B; a.NN = hp.NN; a.tiles = (B + 63) / 64;
         a.wg_prefix[0] = 0;
         for (int t = 0; t < hp.NT; ++t) {
-            a.x[t] = x[t]; a.pitch[t] = x_pitch ? x_pitch[t] : d.type_width[t];
+            a.x[t] = x ? x[t] : nullptr; a.pitch[t] = x_pitch ? x_pitch[t] : d.type_width[t];      // (x == NULL: the series gather of mshgnn_forward_series, nothing materialised)
             if (a.pitch[t] < d.type_width[t]) return set_err(MSHGNN_EINVAL, "x_pitch smaller than the feature width");
-            a.vb[t] = vec_bytes(x[t], a.pitch[t], 4);
+            a.vb[t] = vec_bytes(a.x[t], a.pitch[t], 4);
             if (t == 0) a.aligned = 1;
             if (a.vb[t] != 16 || a.pitch[t] % 4) a.aligned = 0;
             a.width[t] = d.type_width[t]; a.tbase[t] = hp.type_base[t]; a.nkc[t] = hp.enc_nkc[t];
@@ -1363,9 +1356,11 @@ int x3_forward(const mshgnn_plan* p, const void* const* x, const int64_t* x_pitc
         }
         ProfScope ps(p, hp.ks_enc, st);
         if (series) {      // inputs gathered from the sequence's series; x = the window buffers the rows are materialised into
-            if (!a.aligned) return set_err(MSHGNN_EINVAL, "the series gather writes 16-byte-aligned window buffers whose pitch is a multiple of 4");
+            if (x && !a.aligned) return set_err(MSHGNN_EINVAL, "the series gather writes 16-byte-aligned window buffers whose pitch is a multiple of 4");
+            if (series->stats && x) return set_err(MSHGNN_EINVAL, "the standardising series encoder materialises no windows");
             enc_grid += (unsigned)((series->lab.B + 255) / 256);      // the label workgroups
-            hipLaunchKernelGGL((k_enc_x3<true, true>), dim3(enc_grid), dim3(256), 8 * P16::BLK, st, a, hp.n_img, *series, WideSrc{});
+            if (series->stats) hipLaunchKernelGGL((k_enc_x3<true, true, 0, true>), dim3(enc_grid), dim3(256), 8 * P16::BLK, st, a, hp.n_img, *series, WideSrc{});
+            else hipLaunchKernelGGL((k_enc_x3<true, true>), dim3(enc_grid), dim3(256), 8 * P16::BLK, st, a, hp.n_img, *series, WideSrc{});
         }
         else if (wide) {      // the caller's fp64 / fp32 rows: converted by the encoder, fp32 rows written to x on the side
             if (!a.aligned) return set_err(MSHGNN_EINVAL, "wide source rows: the fp32 rows need 16-byte alignment and a pitch that is a multiple of 4");

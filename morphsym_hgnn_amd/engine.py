@@ -83,7 +83,7 @@ EXPORTS = [
     "mshgnn_step_mse_series", "mshgnn_step_ce_series", "mshgnn_step_ce", "mshgnn_op_gemm", "mshgnn_op_gemm_workspace", "mshgnn_op_aggregate", "mshgnn_op_colsum", "mshgnn_op_colsum_workspace",
     "mshgnn_abi_version", "mshgnn_struct_size", "mshgnn_forward_src", "mshgnn_step_mse_src", "mshgnn_step_ce_src",
     "mshgnn_comm_unique_id", "mshgnn_comm_create", "mshgnn_comm_destroy", "mshgnn_comm_allreduce_mean", "mshgnn_comm_allreduce_sum",
-    "mshgnn_input_grad",
+    "mshgnn_input_grad", "mshgnn_forward_series", "mshgnn_forward_series_stats_bytes",
 ]
 ABI_VERSION = 6      # include/mshgnn.h MSHGNN_ABI_VERSION: the ctypes structures above mirror THAT header
 
@@ -175,6 +175,12 @@ def load_library():
     lib.mshgnn_step_ce_src.argtypes = src6 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     if hasattr(lib, "mshgnn_input_grad"):
         lib.mshgnn_input_grad.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
+    if hasattr(lib, "mshgnn_forward_series"):      # (absent from older builds of the library handed over through MSHGNN_LIB for A/B runs)
+        lib.mshgnn_forward_series.argtypes = [C.c_void_p, C.POINTER(MshgnnWindowDesc), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
+                                              C.POINTER(C.c_int64), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.mshgnn_forward_series_stats_bytes.restype = C.c_int64
+        lib.mshgnn_forward_series_stats_bytes.argtypes = [C.POINTER(MshgnnWindowDesc), C.c_int64]
     lib.mshgnn_struct_size.restype = C.c_size_t
     lib.mshgnn_struct_size.argtypes = [C.c_int]
     lib.mshgnn_comm_unique_id.argtypes = [C.c_char_p, C.c_void_p]
@@ -736,11 +742,7 @@ class Engine:
         ws = self.workspace(B, True)
         self._tickets[B] = self._tickets.get(B, 0) + 1; self._chunked[B] = True
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        # the runs' column pointers in the store's scratch depend only on the series' addresses and the element size: resolved by the first step of this
-        # store on this stream at this storage, vouched for afterwards (mshgnn_window_desc.run_ptrs_ready: one launch less in front of every encoder)
-        key = (self.storage == "x3", stream, tuple(a.data_ptr() for a in store.series))
-        store.desc.run_ptrs_ready = 1 if getattr(store, "_run_ptrs_key", None) == key else 0
-        store._run_ptrs_key = key
+        self._vouch_run_ptrs(store, self.storage == "x3", stream)
         with torch.cuda.device(self.device):
             if ce:
                 labels = torch.empty(B, self.n_out, dtype=torch.int32, device=self.device)
@@ -754,6 +756,46 @@ class Engine:
                                                          params_flat.data_ptr(), out.data_ptr(), loss.data_ptr(), grad_flat.data_ptr(), ws.data_ptr(), stream),
                    "mshgnn_step_mse_series")
         return xs, y, out, loss, grad_flat
+
+    @staticmethod
+    def _vouch_run_ptrs(store, fp32_gather: bool, stream):
+        """The runs' column pointers in the store's scratch depend only on the series' addresses and the element size the encoder gathers at: resolved by the
+        first call of this store on this stream at that element size, vouched for afterwards (mshgnn_window_desc.run_ptrs_ready: one launch less in
+        front of every encoder).  Shared by the training steps and `forward_series`."""
+        key = (bool(fp32_gather), stream, tuple(a.data_ptr() for a in store.series))
+        store.desc.run_ptrs_ready = 1 if getattr(store, "_run_ptrs_key", None) == key else 0
+        store._run_ptrs_key = key
+
+    def forward_series(self, store, starts: torch.Tensor, params_flat: torch.Tensor, out: Optional[torch.Tensor] = None, labels: bool = True):
+        """Evaluation straight from a `windows.SequenceStore` (mshgnn_forward_series): `store.assemble(starts)` + `forward(..., training=False)` in one
+        call, bit for bit, with no windows materialised -- the encoder gathers its inputs from the resident series.  Standardised recipes
+        (`recipe.normalize`) are taken too: a pre-pass computes every (window, run)'s mean and sd, the encoder applies them to the fp32 series.
+        starts: device int64 window start rows.  labels=False (or a recipe without labels: a test sequence) computes no by-products.
+        Returns (y | None, quat | None, labels_int | None, out): y fp32 [B, n_label], quat fp32 [B, 4] (recipes with a quaternion series), labels_int
+        int32 [B, n_out] (the contact flags y != 0, two-logit classification models only).  The by-products are the store's reusable buffers of
+        this batch size: consume them before the next call.  bf16 plan with the fused stack kernels or the split plan "x3"."""
+        if not hasattr(self.lib, "mshgnn_forward_series"):
+            raise MshgnnError("this build of the library has no mshgnn_forward_series")
+        self._check_flat(params_flat, "params_flat")
+        if not starts.is_cuda or starts.dtype != torch.int64:
+            raise ValueError("starts must be a device int64 tensor")
+        B = int(starts.numel())
+        r = store.recipe
+        y, q, li, stats = store.eval_buffers(B, labels, self.n_out if self.spec.out_channels == 2 else 0)
+        if out is None:
+            out = torch.empty(B * self.n_out, self.spec.out_channels, dtype=torch.float32, device=self.device)
+        fp32_gather = self.storage == "x3" or bool(r.normalize)
+        src16, run_ptrs = store.series_step_args(bf16=not fp32_gather)
+        ws = self.workspace(B, False)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        self._vouch_run_ptrs(store, fp32_gather, stream)
+        with torch.cuda.device(self.device):
+            _check(self.lib, self.lib.mshgnn_forward_series(self._plan, C.byref(store.desc), store._src, src16, store._pitch, store._rows, starts.data_ptr(), B,
+                                                            y.data_ptr() if y is not None else None, q.data_ptr() if q is not None else None,
+                                                            li.data_ptr() if li is not None else None, run_ptrs.data_ptr(),
+                                                            stats.data_ptr() if stats is not None else None, params_flat.data_ptr(), out.data_ptr(),
+                                                            ws.data_ptr(), stream), "mshgnn_forward_series")
+        return y, q, li, out
 
     def step_mse_phase(self, phase: int, xs: Sequence[torch.Tensor], params_flat: torch.Tensor, y: torch.Tensor, B: int, out: torch.Tensor,
                        grad_flat: torch.Tensor, loss: torch.Tensor):
@@ -952,6 +994,10 @@ class PaddedEngine:
             return self.inner.backward(xs, self._pad(params_flat), grad_out, B, weights=False)
         self.inner.backward(xs, self._pad(params_flat), grad_out, B, grad_flat=self._pgrad)
         return self._unpad_grad(grad_flat)
+
+    def forward_series(self, store, starts, params_flat, out=None, labels=True):
+        """The inner engine's, on the padded flat buffer (an evaluation forward needs nothing else translated)."""
+        return self.inner.forward_series(store, starts, self._pad(params_flat), out=out, labels=labels)
 
     def input_grad(self, B, params_flat, types=None, dtype=torch.float32, pitches=None):
         """The inner engine's, on the padded flat buffer: the added rows of W_enc are zero and the added features' dY are exact zeros -- the same gradient."""

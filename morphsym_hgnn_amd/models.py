@@ -529,6 +529,43 @@ class _MSHGNNBase(nn.Module):
         loss, out = _FusedStepFn.apply(self._anchor, self, run)
         return self._shape_output(out, spec, B, store.device, torch.float32), loss
 
+    def forward_windows(self, batch):
+        """The evaluation forward for a `windows.WindowBatch` without autograd: the encoder gathers the batch's inputs straight from the sequence's
+        resident series (mshgnn_forward_series -- no assembly pass, no materialised windows; standardised recipes included) and the labels are left
+        on the batch.  Returns the output as forward() does -- bit-identical to forward(batch.x_dict, ...) -- or None when this route does not
+        apply: gradients enabled, the model has not seen its lazy-initialising forward yet, a plan other than bf16 / split-bf16 on the LDS-resident
+        kernels, parameters on the host or another device, a store whose dtype is not the plan's input dtype or that is not fast-layout, or whose
+        recipe differs from the model's node types and widths."""
+        spec = self._spec
+        store, B = batch.store, batch.batch_size
+        r = store.recipe
+        if torch.is_grad_enabled() or spec is None or not self._fused_activation or store.dtype not in ("bf16", "x3", "f32") or not store.desc.fast_layout:
+            return None
+        if r.normalize and not 2 <= r.history <= 256:
+            return None
+        if list(r.node_types) != list(spec.node_types) or any(r.num_nodes[t] != spec.num_nodes[t] or r.width(t) != spec.widths[t] for t in r.node_types):
+            return None
+        params = self._params_in_flat_order()
+        if params[0].device.type != "cuda" or params[0].device != store.device:
+            return None
+        e = self._engine(store.device)
+        if e.generic or e.storage not in ("bf16", "x3") or (e.storage == "bf16") != (store.dtype == "bf16") or not hasattr(e.lib, "mshgnn_forward_series"):
+            return None
+        if r.label_cols and len(r.label_cols) != e.n_out * (spec.out_channels if spec.regression else 1):
+            return None
+        if r.history < 8 and store.desc.n_runs > store.desc.n_rows:      # (node rows of several runs shorter than a chunk: the Solo recipes -- assembled)
+            return None
+        if B not in self._checked_batches:   # one host-side check per batch size: B copies of the compiled graph
+            for et in self._edge_types:
+                s_, _, d_ = et
+                if infer_window_edges(batch.edge_index_dict[et], spec.num_nodes[s_], spec.num_nodes[d_], B) != spec.topology.edges(et):
+                    raise ValueError(f"edge_index_dict[{et}] differs from the topology this model was compiled for")
+            self._checked_batches.add(B)
+        y, q, _, out = e.forward_series(store, batch.starts, self._flat_params(store.device))
+        if y is not None:
+            batch._labels_from_step(None, y, q)
+        return self._shape_output(out, spec, B, store.device, torch.float32)
+
     def forward(self, x_dict, edge_index_dict):
         spec, B, e, pdev = self._prepare(x_dict, edge_index_dict)
         if e is None:

@@ -173,6 +173,7 @@ class SequenceStore:
         self._pitch = (C.c_int64 * len(self.series))(*[a.shape[1] for a in self.series])     # column stride (rows + slack)
         self._rows = (C.c_int64 * len(self.series))(*[a.shape[1] - 8 for a in self.series])
         self._src16 = None; self._run_ptrs = None
+        self._eval_cache = {}
 
     def __len__(self) -> int:
         """Number of windows (the reference's dataset length: rows - history + 1)."""
@@ -226,6 +227,23 @@ class SequenceStore:
         """A minibatch of window indices shaped like the PyG batch the wrappers take (see WindowBatch)."""
         return WindowBatch(self, starts, edge_index_dict)
 
+    def eval_buffers(self, B: int, labels: bool = True, n_flags: int = 0):
+        """The by-product buffers and the statistics scratch of `Engine.forward_series` for a batch of B windows, made once per batch size (one batch
+        size at a time, like `_buffers`): (y, quat, labels_int, stats).  labels=False or a recipe without labels (a test sequence): no y / quat /
+        labels_int.  labels_int (int32 contact flags) only when the recipe has one unrotated label per flag (n_flags = the model's out nodes).
+        stats: `mshgnn_forward_series_stats_bytes` of scratch for standardised recipes, else None."""
+        r = self.recipe
+        want = bool(labels and r.label_cols)
+        key = (B, want, n_flags)
+        if key not in self._eval_cache:
+            y = torch.empty(B, len(r.label_cols), dtype=torch.float32, device=self.device) if want else None
+            q = torch.empty(B, 4, dtype=torch.float32, device=self.device) if want and r.quat_series else None
+            li = torch.empty(B, n_flags, dtype=torch.int32, device=self.device) if want and n_flags and len(r.label_cols) == n_flags and not r.label_rotate else None
+            nbytes = int(self.lib.mshgnn_forward_series_stats_bytes(C.byref(self.desc), B))
+            stats = torch.empty(nbytes // 8, dtype=torch.float64, device=self.device) if nbytes else None
+            self._eval_cache = {key: (y, q, li, stats)}
+        return self._eval_cache[key]
+
     def series_step_args(self, bf16: bool = True):
         """What Engine.step_mse_series hands to mshgnn_step_mse_series: bf16 copies of the series (same strides; bf16=False, the split plan:
         none -- it gathers from the fp32 series themselves) and the run-pointer scratch."""
@@ -241,8 +259,9 @@ class WindowBatch:
     """One minibatch of window indices of a `SequenceStore`, with the attributes the reference's wrappers read off a PyG batch
     (`x_dict`, `edge_index_dict`, `y`, `r_o`, `batch_size`; gnnLightning.py:680-722).  Nothing is gathered when it is made: a wrapper's
     `training_step` hands the indices to the engine, whose encoder gathers its inputs from the resident series
-    (`models.fused_training_step_windows` -> `mshgnn_step_mse_series` / `mshgnn_step_ce_series`) and leaves the labels here; any other consumer
-    (validation, the two-call route) gets the windows assembled on first access (`SequenceStore.assemble`, the store's reusable buffers:
+    (`models.fused_training_step_windows` -> `mshgnn_step_mse_series` / `mshgnn_step_ce_series`) and leaves the labels here; the evaluation steps
+    under torch.no_grad() do the same without materialising anything (`models.forward_windows` -> `mshgnn_forward_series`); any other consumer
+    (the two-call route, a model the fused routes do not take) gets the windows assembled on first access (`SequenceStore.assemble`, the store's reusable buffers:
     consume a batch before asking the store for the next one)."""
 
     def __init__(self, store: SequenceStore, starts, edge_index_dict):

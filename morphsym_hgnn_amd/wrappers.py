@@ -54,6 +54,19 @@ def _model_fused_step(wrapper, batch):
     return wrapper.model.fused_training_step(batch.x_dict, batch.edge_index_dict, batch.y)
 
 
+def _model_forward(wrapper, batch):
+    """The model's output for a batch: for a `windows.WindowBatch` without autograd (validation, test, prediction) straight from the sequence's resident
+    series (models.forward_windows -- no assembled windows; the labels are left on the batch), else -- or where that route does not apply, or with
+    `fused_evaluation_step = False` -- the model's own forward over `batch.x_dict`.  Same bits either way."""
+    if wrapper.fused_evaluation_step and not torch.is_grad_enabled():
+        from .windows import WindowBatch
+        if isinstance(batch, WindowBatch) and hasattr(wrapper.model, "forward_windows"):
+            out = wrapper.model.forward_windows(batch)
+            if out is not None:
+                return out
+    return wrapper.model(x_dict=batch.x_dict, edge_index_dict=batch.edge_index_dict)
+
+
 class Base_Lightning(_Base):
     """Steps, epoch hooks, logging and the optimizer shared by every wrapper (gnnLightning.py:28-348)."""
 
@@ -62,6 +75,9 @@ class Base_Lightning(_Base):
     # gradients when backward() is called on it.  Same loss and gradients as the two-call route, which is taken when this is False
     # (an attribute, set per wrapper or on the class), under torch.distributed, with host parameters, or without autograd.
     fused_training_step = True
+    # validation_step / test_step / predict_step on a windows.WindowBatch under torch.no_grad(): the engine's encoder gathers the windows from the resident
+    # series (models.forward_windows, mshgnn_forward_series) instead of reading assembled ones; False: always assemble, then forward.  Same bits.
+    fused_evaluation_step = True
 
     def __init__(self, optimizer: str, lr: float, regression: bool):
         super().__init__()
@@ -204,7 +220,7 @@ class _HGNNWrapper(Base_Lightning):
         return y, y_pred
 
     def step_helper_function(self, batch):
-        return self._shape(batch, self.model(x_dict=batch.x_dict, edge_index_dict=batch.edge_index_dict))
+        return self._shape(batch, _model_forward(self, batch))
 
     def _fused_step(self, batch):
         """(y, y_pred, loss) from the one-call engine step, or None when that route does not apply."""
@@ -416,6 +432,7 @@ class COM_Base_Lightning(_Base):
         self._m().reset_all_metrics()
 
     fused_training_step = Base_Lightning.fused_training_step
+    fused_evaluation_step = Base_Lightning.fused_evaluation_step
 
     def training_step(self, batch, batch_idx):
         r = _model_fused_step(self, batch)
@@ -456,7 +473,7 @@ class COM_Base_Lightning(_Base):
 
     def step_helper_function(self, batch):
         """Outputs and labels per window, [batch, num_bases * 6] (gnnLightning_com.py:324-340, 394-409)."""
-        return self._shape(batch, self.model(x_dict=batch.x_dict, edge_index_dict=batch.edge_index_dict))
+        return self._shape(batch, _model_forward(self, batch))
 
     def _shape(self, batch, out_raw):
         batch_size = batch.batch_size if hasattr(batch, "batch_size") else 1
@@ -601,3 +618,43 @@ class GraphedTrainingStep:
             self.load(batch)
         self.graph.replay()
         return self.loss
+
+
+def evaluate_sequence(wrapper, store, edge_index_dict, batch_size: int, stride: int = 1) -> torch.Tensor:
+    """A test epoch over every window of one sequence, in order (the loop of the reference's `evaluate_model` without its dataset plumbing): windows
+    0, stride, 2 stride, ... of `store` in batches of `batch_size` (the last one ragged) through the wrapper's `test_step` under torch.no_grad() --
+    with `fused_evaluation_step` straight from the resident series.  `edge_index_dict`: the edges of ONE window (tiled per batch here) or a
+    callable batch size -> edge_index_dict.  Returns the predictions [n_windows, ...] in window order; the epoch's metrics are left in the
+    wrapper's state (`on_test_epoch_end` has run: `wrapper.logged`, the metric attributes)."""
+    if batch_size < 1 or stride < 1:
+        raise ValueError("batch_size and stride must be >= 1")
+    starts = torch.arange(0, len(store), stride, dtype=torch.int64, device=store.device)
+    r = store.recipe
+    edges = {}
+
+    def edges_for(B):
+        if B not in edges:
+            if callable(edge_index_dict):
+                edges[B] = edge_index_dict(B)
+            else:
+                edges[B] = {}
+                for et, ei in edge_index_dict.items():
+                    ei = torch.as_tensor(ei).to(store.device)
+                    off = torch.stack([torch.arange(B, device=store.device) * r.num_nodes[et[0]], torch.arange(B, device=store.device) * r.num_nodes[et[2]]])
+                    edges[B][et] = (ei[:, None, :] + off[:, :, None]).reshape(2, -1)
+        return edges[B]
+
+    preds = []
+    with torch.no_grad():
+        wrapper.on_test_epoch_start()
+        for i, lo in enumerate(range(0, int(starts.numel()), batch_size)):
+            st = starts[lo:lo + batch_size]
+            batch = store.batch(st, edges_for(int(st.numel())))
+            y, y_pred = wrapper.step_helper_function(batch)
+            if getattr(wrapper, "body_to_world_frame", False):
+                wrapper.calculate_losses_step_worldframe(y, y_pred, batch.r_o.view(batch.batch_size, 4))
+            else:
+                wrapper.calculate_losses_step(y, y_pred)
+            preds.append(y_pred.clone())
+        wrapper.on_test_epoch_end()
+    return torch.cat(preds, 0)
