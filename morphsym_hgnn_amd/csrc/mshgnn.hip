@@ -2711,14 +2711,16 @@ int launch_prep(const PrepArgs& a, bool split, hipStream_t st) {
     return MSHGNN_OK;
 }
 
-int run_finalize(const mshgnn_plan* p, const mshgnn_ws_layout& lay, char* ws, float* gparams, int B, float* loss, bool is_ce, bool dec_done,
-                 int gw_phase, hipStream_t st, int gw_parts) {
+int run_finalize(const mshgnn_plan* p, const StepCall& c, const mshgnn_ws_layout& lay, int gw_parts) {
     const HostPlan& hp = p->hp;
     const mshgnn_desc& d = hp.d;
+    char* ws = c.ws; float* gparams = c.grad_params; hipStream_t st = c.stream;
+    const int B = (int)c.batch, gw_phase = c.gw_phase;
+    float* loss = c.loss != LossKind::NONE ? c.loss_out : nullptr;
     FinArgs a{p->d_tables + hp.fin_off, p->d_tables + hp.fin_off, p->d_tables + hp.tgt_off, reinterpret_cast<const float*>(ws + lay.slabs),
               reinterpret_cast<const float*>(ws + lay.dec_slabs), gparams, hp.n_lanes, gw_parts, loss,
-              1.0f / (float)(loss_windows(B) * d.type_nodes[d.out_type] * (is_ce ? 1 : d.out_channels)),
-              dec_done ? (int)((B + TILE_ROWS - 1) / TILE_ROWS) : NWG_DEC, step_accumulates()};
+              1.0f / (float)(c.total_windows() * d.type_nodes[d.out_type] * (c.loss == LossKind::CE ? 1 : d.out_channels)),
+              c.dec_done ? (int)((B + TILE_ROWS - 1) / TILE_ROWS) : NWG_DEC, c.accumulates()};
     int f0 = 0, nf = hp.n_fin;
     if (gw_phase == 0) nf = hp.n_fin_ph0;
     if (gw_phase == 1) { f0 = hp.n_fin_ph0; nf = hp.n_fin - hp.n_fin_ph0; a.loss = nullptr; }
@@ -2735,15 +2737,18 @@ int run_finalize(const mshgnn_plan* p, const mshgnn_ws_layout& lay, char* ws, fl
 }
 
 template <typename T>
-static int forward_impl(const mshgnn_plan* p, const void* const* x, const int64_t* x_pitch, const float* params, float* out,
-                        char* ws, int64_t batch, int training, hipStream_t st, const float* y_fused = nullptr, const SeriesSrc* series = nullptr,
-                        const int32_t* labels_fused = nullptr, bool* stack_step_done = nullptr) {
-    // stack_step_done (one-call steps): where the slab kernels run and the loss is fused, the backward sweep of the stack runs in the same launch
-    // (k_slab_step) and *stack_step_done tells backward_impl to skip its own
+static int forward_impl(const mshgnn_plan* p, StepCall& c) {
+    // c.loss (one-call steps): the fused stack kernels run decoder, loss and decoder backward in their tail (c.dec_done); where the slab kernels run, the backward
+    // sweep of the stack runs in the same launch as well (k_slab_step) and c.stack_done tells backward_impl to skip its own
     const HostPlan& hp = p->hp;
     const mshgnn_desc& d = hp.d;
-    mshgnn_ws_layout lay; layout_workspace(hp, batch, training, &lay);
-    const int B = (int)batch;
+    const int training = c.training;
+    mshgnn_ws_layout lay; layout_workspace(hp, c.batch, training, &lay);
+    const int B = (int)c.batch;
+    const void* const* x = c.x; const int64_t* x_pitch = c.x_pitch;
+    const float* params = c.params; char* ws = c.ws; hipStream_t st = c.stream;
+    const SeriesSrc* series = c.series; const WideSrc* wide = c.wide;
+    const float* y_fused = c.y_fused(); const int32_t* labels_fused = c.labels_fused();
     // 1. weight images.  bf16 plan with few packs: only the encoder's packs (the last ones of the list) + the biases here; the layer packs are packed
     //    by extra workgroups of the encoder launch, under its tail (EncArgs.prep) -- the whole-list launch in front of the encoder cost 10.9 us
     PrepArgs pa{params, ws + lay.wpack, reinterpret_cast<float*>(ws + lay.bias), p->d_packs, p->d_biases, (int)hp.packs.size(), (int)hp.biases.size()};
@@ -2760,7 +2765,6 @@ static int forward_impl(const mshgnn_plan* p, const void* const* x, const int64_
         else hipLaunchKernelGGL(k_prep<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a);
     }
     // 2. encoder
-    const WideSrc* wide = series ? nullptr : g_wide_src;      // (mshgnn_*_src: the caller's fp64 / fp32 rows; x = the plan-dtype rows to materialise, may be null)
     {
         EncArgs a{};
         a.n_types = hp.NT; a.B = B; a.NN = hp.NN; a.tiles = (B + Prec<T>::ENC_MB * Prec<T>::ROWS - 1) / (Prec<T>::ENC_MB * Prec<T>::ROWS);
@@ -2805,7 +2809,7 @@ static int forward_impl(const mshgnn_plan* p, const void* const* x, const int64_
                 enc_grid += (unsigned)((series->lab.B + 255) / 256);      // the label workgroups
                 if (series->stats) hipLaunchKernelGGL((k_enc_fwd<T, true, true, 0, true>), dim3(enc_grid), dim3(256), Prec<T>::ENC_MB * Prec<T>::BLK, st, a, *series, WideSrc{});
                 else hipLaunchKernelGGL((k_enc_fwd<T, true, true>), dim3(enc_grid), dim3(256), Prec<T>::ENC_MB * Prec<T>::BLK, st, a, *series, WideSrc{});
-            } else if (wide) {      // the caller's fp64 / fp32 rows: converted by the encoder, plan-dtype rows written to x on the side
+            } else if (wide) {      // (mshgnn_*_src) the caller's fp64 / fp32 rows: converted by the encoder, plan-dtype rows written to x on the side (x may be null)
                 if (x && !a.aligned) return set_err(MSHGNN_EINVAL, "wide source rows: the plan-dtype rows need 16-byte alignment and a pitch that is a multiple of 8");
                 if (wide->bytes == 8) hipLaunchKernelGGL((k_enc_fwd<T, true, false, 8>), dim3(enc_grid), dim3(256), Prec<T>::ENC_MB * Prec<T>::BLK, st, a, SeriesSrc{}, *wide);
                 else hipLaunchKernelGGL((k_enc_fwd<T, true, false, 4>), dim3(enc_grid), dim3(256), Prec<T>::ENC_MB * Prec<T>::BLK, st, a, SeriesSrc{}, *wide);
@@ -2828,21 +2832,22 @@ static int forward_impl(const mshgnn_plan* p, const void* const* x, const int64_
             a.wpack = ws + lay.wpack; a.bias = reinterpret_cast<const float*>(ws + lay.bias); a.tables = p->d_tables;
             a.B = B; a.NN = hp.NN; a.L = hp.L; a.training = training;
             a.dbg = p->dbg;
-            a.params = params; a.out_mask = p->d_out_mask; a.out = out; a.off_dec_w = d.off_dec_w; a.off_dec_b = d.off_dec_b;
+            a.params = params; a.out_mask = p->d_out_mask; a.out = c.out; a.off_dec_w = d.off_dec_w; a.off_dec_b = d.off_dec_b;
             a.node0 = hp.type_base[d.out_type]; a.n_out = d.type_nodes[d.out_type]; a.dout = d.out_channels;
             if (y_fused) {
                 a.y = y_fused; a.dec_slabs = reinterpret_cast<float*>(ws + lay.dec_slabs); a.dx_off[hp.L] = lay.dx[hp.L];
-                a.inv_n = 1.0f / (float)(loss_windows(B) * a.n_out * a.dout);
+                a.inv_n = 1.0f / (float)(c.total_windows() * a.n_out * a.dout);
             } else if (labels_fused) {      // mshgnn_step_ce: cross entropy over the per-foot logit pairs, mean over B * n_out rows
                 a.labels = labels_fused; a.dec_slabs = reinterpret_cast<float*>(ws + lay.dec_slabs); a.dx_off[hp.L] = lay.dx[hp.L];
-                a.inv_n = 1.0f / (float)(loss_windows(B) * a.n_out);
+                a.inv_n = 1.0f / (float)(c.total_windows() * a.n_out);
             }
+            c.dec_done = y_fused || labels_fused;
             a.stamps = stamp_ptr("MSHGNN_STAMPS");
             a.stagger = p->slab_for(tiles) && tiles > p->n_cu ? p->stagger : 0;
             a.stash_nt = training ? stash_nt_for(p->stash_nt_force, B, stash_rows_of(hp), H * (int)sizeof(T)) : 0;
             // the tail's reduction scratch (one decoder slab per wave) must not touch the out-type nodes' blocks, which receive dX_L for the backward sweep: it sits
             // in the blocks in front of them, or (models whose out type comes first: the centroidal-momentum ones) in the blocks behind them
-            const bool want_step = stack_step_done && p->use_step && (y_fused || labels_fused);
+            const bool want_step = p->use_step && c.dec_done;
             // Slab or 8-wave kernels: the 8-wave ones take batches of at most one tile per CU -- unless the one-call step has a compile-time program for this plan
             // (whole tiles): a single tile's chain on the specialised slab kernel is 37-42 us where the interpreting 8-wave kernel takes 57-62 (A1-C2, 32 .. 4 096 windows;
             // 8 layers: 140-166 against 202-209), so the specialised step runs at every batch size.  MSHGNN_SLAB=0 / MSHGNN_SPEC=0 keep the 8-wave kernels there.
@@ -2869,7 +2874,7 @@ static int forward_impl(const mshgnn_plan* p, const void* const* x, const int64_
                     for (int l = 0; l < hp.L; ++l) { a.dh_off[l] = lay.dh[l]; a.du_off[l] = lay.du[l]; a.prog_off_b[l] = hp.sl_bwd_off[l]; }
                     a.mask0_off = lay.dd[0];
                     hipLaunchKernelGGL(slab_step_kernel(hp, B, a.stash_nt, p->use_spec), dim3(tiles), dim3(SL_THREADS), (hp.sl_blk + FS_EXTRA_BLK) * Prec<T>::BLK, st, a);
-                    *stack_step_done = true;
+                    c.stack_done = true;
                 } else
                 hipLaunchKernelGGL(fwd_spec ? fwd_spec : slab_fwd_kernel(hp), dim3(tiles), dim3(SL_THREADS), (hp.sl_blk + FS_EXTRA_BLK) * Prec<T>::BLK, st, a);
             } else if (step) {
@@ -2877,7 +2882,7 @@ static int forward_impl(const mshgnn_plan* p, const void* const* x, const int64_
                 for (int l = 0; l < hp.L; ++l) { a.dh_off[l] = lay.dh[l]; a.du_off[l] = lay.du[l]; a.prog_off_b[l] = hp.fs_bwd_off[l]; }
                 a.mask0_off = lay.dd[0];
                 hipLaunchKernelGGL(k_stack_step<T>, dim3(tiles), dim3(LAYER_THREADS), (hp.fs_blk + FS_EXTRA_BLK) * Prec<T>::BLK, st, a);
-                *stack_step_done = true;
+                c.stack_done = true;
             } else
             hipLaunchKernelGGL(k_stack_fwd<T>, dim3(tiles), dim3(LAYER_THREADS), (hp.fs_blk + FS_EXTRA_BLK) * Prec<T>::BLK, st, a);
             HIPCHK(hipGetLastError());
@@ -2896,7 +2901,7 @@ static int forward_impl(const mshgnn_plan* p, const void* const* x, const int64_
     // 4. decoder
     {
         DecArgs a{};
-        a.xl = ws + lay.x[hp.L]; a.params = params; a.out_mask = p->d_out_mask; a.out = out; a.off_w = d.off_dec_w; a.off_b = d.off_dec_b;
+        a.xl = ws + lay.x[hp.L]; a.params = params; a.out_mask = p->d_out_mask; a.out = c.out; a.off_w = d.off_dec_w; a.off_b = d.off_dec_b;
         a.B = B; a.NN = hp.NN; a.node0 = hp.type_base[d.out_type]; a.n_out = d.type_nodes[d.out_type]; a.dout = d.out_channels;
         const int64_t rows = (int64_t)B * a.n_out;
         ProfScope ps(p, hp.ks_dec_fwd, st);
@@ -2907,26 +2912,26 @@ static int forward_impl(const mshgnn_plan* p, const void* const* x, const int64_
 }
 
 template <typename T>
-static int backward_impl(const mshgnn_plan* p, const void* const* x, const int64_t* x_pitch, const float* params, const float* gout,
-                         float* gparams, char* ws, int64_t batch, hipStream_t st, const float* out = nullptr, const float* y = nullptr,
-                         float* loss = nullptr, const int32_t* labels = nullptr, bool dec_done = false, int gw_phase = -1, const SeriesSrc* series = nullptr,
-                         bool stack_done = false) {      // stack_done: k_slab_step already ran the backward sweep of the stack (forward_impl)
-    // gw_phase: -1 = everything; 0 = backward sweep + the weight gradients of every parameter but the encoder's; 1 = only the
-    // encoder's weight gradients (the sweep of phase 0 left dX_0 in the workspace)
+static int backward_impl(const mshgnn_plan* p, const StepCall& c) {
     const HostPlan& hp = p->hp;
     const mshgnn_desc& d = hp.d;
-    mshgnn_ws_layout lay; layout_workspace(hp, batch, 1, &lay);
-    const int B = (int)batch;
-    if (!dec_done && gw_phase != 1) {
+    mshgnn_ws_layout lay; layout_workspace(hp, c.batch, 1, &lay);
+    const int B = (int)c.batch;
+    const void* const* x = c.x; const int64_t* x_pitch = c.x_pitch;
+    char* ws = c.ws; hipStream_t st = c.stream;
+    const int gw_phase = c.gw_phase;
+    const bool stack_done = c.stack_done;      // k_slab_step already ran the backward sweep of the stack (forward_impl)
+    const SeriesSrc* series = c.gradw_from_series ? c.series : nullptr;
+    if (!c.dec_done && gw_phase != 1) {
         DecArgs a{};
-        a.xl = ws + lay.x[hp.L]; a.dxl = ws + lay.dx[hp.L]; a.params = params; a.out_mask = p->d_out_mask; a.gout = gout;
+        a.xl = ws + lay.x[hp.L]; a.dxl = ws + lay.dx[hp.L]; a.params = c.params; a.out_mask = p->d_out_mask; a.gout = c.grad_out;
         a.slabs = reinterpret_cast<float*>(ws + lay.dec_slabs); a.off_w = d.off_dec_w; a.off_b = d.off_dec_b;
         a.B = B; a.NN = hp.NN; a.node0 = hp.type_base[d.out_type]; a.n_out = d.type_nodes[d.out_type]; a.dout = d.out_channels; a.slab0 = 0;
-        if (y) {
-            a.y = y; a.out = const_cast<float*>(out); a.loss = loss; a.inv_n = 1.0f / (float)(loss_windows(B) * a.n_out * a.dout);
+        if (c.loss == LossKind::MSE) {
+            a.y = c.y; a.out = c.out; a.loss = c.loss_out; a.inv_n = 1.0f / (float)(c.total_windows() * a.n_out * a.dout);
         }
-        if (labels) {
-            a.labels = labels; a.out = const_cast<float*>(out); a.loss = loss; a.inv_n = 1.0f / (float)(loss_windows(B) * a.n_out);
+        if (c.loss == LossKind::CE) {
+            a.labels = c.labels; a.out = c.out; a.loss = c.loss_out; a.inv_n = 1.0f / (float)(c.total_windows() * a.n_out);
         }
         ProfScope ps(p, hp.ks_dec_bwd, st);
         hipLaunchKernelGGL(k_dec_bwd<T>, dim3(NWG_DEC), dim3(256), 0, st, a);
@@ -2968,7 +2973,7 @@ static int backward_impl(const mshgnn_plan* p, const void* const* x, const int64
         hipLaunchKernelGGL(k_layer_bwd<T>, dim3(tiles), dim3(LAYER_THREADS), hp.n_blk * Prec<T>::BLK, st, a);
     }
     const int gw_parts = gw_parts_for(hp.n_parts, hp.n_lanes, hp.gw_ipl, B, sizeof(T) == 4 ? GW_KW : GWB_KW, p->n_cu);      // window parts of this batch's weight-gradient launch (<= the plan's)
-    if (gparams) {      // (NULL: activation backward only -- dX_0 for mshgnn_input_grad, no weight gradients)
+    if (c.grad_params) {      // (NULL: activation backward only -- dX_0 for mshgnn_input_grad, no weight gradients)
         GradwArgs a{};
         a.ws = ws;
         for (int l = 0; l <= hp.L; ++l) { a.buf_off[BUF_X + l] = lay.x[l]; a.buf_off[BUF_DX + l] = lay.dx[l]; }
@@ -3004,213 +3009,202 @@ static int backward_impl(const mshgnn_plan* p, const void* const* x, const int64
         //  evict each other's shared rows.)
         launch_gradw(a, st);
     }
-    return run_finalize(p, lay, ws, gparams, B, (y || labels) ? loss : nullptr, labels != nullptr, dec_done, gw_phase, st, gw_parts);
+    return run_finalize(p, c, lay, gw_parts);
+}
+
+// ------------------------------------------------------------------------------------------------------
+// The engine dispatch, once per operation.  Every extern "C" entry point below validates its own arguments, fills a StepCall (mshgnn_device.hpp) and
+// calls one of these three.
+// ------------------------------------------------------------------------------------------------------
+static int run_forward(const mshgnn_plan* p, StepCall& c) {
+    if (c.wide && c.series) return set_err(MSHGNN_EINVAL, "a call takes its encoder rows from wide sources or from a series, not from both");
+    if (p->gen) return gen_forward(p, c);
+    if (p->hp.d.dtype == MSHGNN_BF16X3) return x3_forward(p, c);
+    if (p->hp.d.dtype == MSHGNN_F32) return forward_impl<float>(p, c);
+    return forward_impl<__bf16>(p, c);
+}
+
+static int run_backward(const mshgnn_plan* p, const StepCall& c) {
+    if (p->gen) return gen_backward(p, c);
+    if (p->hp.d.dtype == MSHGNN_BF16X3) return x3_backward(p, c);
+    if (p->hp.d.dtype == MSHGNN_F32) return backward_impl<float>(p, c);
+    return backward_impl<__bf16>(p, c);
+}
+
+// Windows per sub-step of a one-call step, 0: the step runs whole.  Whole: batches under twice MSHGNN_STEP_CHUNK (read when the plan is created; default 32 768; 0 = always whole), the
+// generic-width engine (its finalize kernel overwrites), wide-source calls (their source pointers are not offset here) and the series routes (nor are their window starts).  Equal sub-steps of
+// whole 16-window tiles.
+static int64_t step_chunk_windows(const mshgnn_plan* p, const StepCall& c) {
+    const int64_t limit = p->step_chunk;
+    if (limit <= 0 || c.batch < 2 * limit || p->gen || c.wide || c.series) return 0;
+    const int64_t n = c.batch / limit;      // sub-steps of at least `limit` windows each (a step's cost per window is flat from there up; shorter ones cost ~5 % more)
+    return ((c.batch + n - 1) / n + TILE_ROWS - 1) / TILE_ROWS * TILE_ROWS;
+}
+
+// One training step with a fused loss: the forward, then the backward from whatever the forward left undone (c.dec_done, c.stack_done) -- on the generic engine, the fp32
+// plan and a bf16 plan without the fused stack kernels nothing, which makes it the two-call sequence.  A long batch runs as sub-steps over contiguous window
+// ranges into one gradient (StepChunk).
+static int run_step(const mshgnn_plan* p, StepCall& c) {
+    auto whole = [p](StepCall& s) { const int rc = run_forward(p, s); return rc ? rc : run_backward(p, s); };
+    const int64_t cw = step_chunk_windows(p, c);
+    if (!cw) return whole(c);
+    const mshgnn_desc& d = p->hp.d;
+    const int64_t eb = d.dtype == MSHGNN_BF16 ? 2 : 4;      // input rows: bf16 on the bf16 plan, fp32 on the split and fp32 plans
+    const int64_t n_out = d.type_nodes[d.out_type], orow = n_out * d.out_channels;
+    int idx = 0;
+    for (int64_t w0 = 0; w0 < c.batch; w0 += cw, ++idx) {
+        const void* xc[MSHGNN_MAX_TYPES] = {};
+        for (int t = 0; t < p->n_types; ++t)
+            xc[t] = static_cast<const char*>(c.x[t]) + w0 * d.type_nodes[t] * (c.x_pitch ? c.x_pitch[t] : (int64_t)d.type_width[t]) * eb;
+        StepCall sub = c;
+        sub.x = xc; sub.batch = std::min(cw, c.batch - w0); sub.chunk = StepChunk{c.batch, idx};
+        sub.out = c.out + w0 * orow;
+        if (c.loss == LossKind::MSE) sub.y = c.y + w0 * orow; else sub.labels = c.labels + w0 * n_out;
+        if (const int rc = whole(sub)) return rc;
+    }
+    return MSHGNN_OK;
+}
+
+// ---- the caller's own fp64 / fp32 tensors as inputs (the reference's datasets produce fp64, gnnLightning.py:1183): the encoder converts in registers and
+// writes the plan-dtype rows the weight-gradient kernel needs on the side -- no separate cast + re-pitch pass.  The _src entry points check the source
+// description into a WideSrc here and hand it to the encoder launch in their call (StepCall.wide).
+static int fill_wide_src(const mshgnn_plan* p, int src_bytes, const void* const* src, const int64_t* src_pitch, const char* who, WideSrc& w) {
+    if (!p || !src) return set_err(MSHGNN_EINVAL, std::string("null argument to ") + who);
+    if (src_bytes != 4 && src_bytes != 8) return set_err(MSHGNN_EINVAL, std::string(who) + ": src_bytes must be 4 (fp32) or 8 (fp64)");
+    if (p->gen || p->hp.d.dtype == MSHGNN_F32) return set_err(MSHGNN_EUNSUPPORTED, std::string(who) + ": wide source rows run on the bf16 and split-bf16 plans of the LDS-resident kernels");
+    w.bytes = src_bytes;
+    for (int t = 0; t < p->n_types; ++t) {
+        if (!src[t]) return set_err(MSHGNN_EINVAL, std::string(who) + ": null source tensor");
+        w.p[t] = src[t]; w.pitch[t] = src_pitch ? src_pitch[t] : p->hp.d.type_width[t];
+        if (w.pitch[t] < p->hp.d.type_width[t]) return set_err(MSHGNN_EINVAL, std::string(who) + ": src_pitch smaller than the feature width");
+        if (((uintptr_t)src[t] % (src_bytes == 8 ? 8 : 4)) != 0) return set_err(MSHGNN_EINVAL, std::string(who) + ": source tensor not aligned to its element size");
+        // fp32 rows are read in 8-byte units where the width allows it: rows must then start on 8 bytes
+        if (src_bytes == 4 && (p->hp.d.type_width[t] & 1) == 0 && ((((uintptr_t)src[t]) | (uintptr_t)(w.pitch[t] * 4)) & 7) != 0)
+            return set_err(MSHGNN_EINVAL, std::string(who) + ": fp32 source rows of an even width must start 8-byte aligned (base and pitch)");
+    }
+    return MSHGNN_OK;
+}
+
+// mshgnn_forward and mshgnn_forward_src behind their own checks (wide: null on the plain entry point; both report under the plain name)
+static int forward_entry(const mshgnn_plan* p, const WideSrc* wide, const void* const* x, const int64_t* x_pitch, const float* params, float* out,
+                         void* workspace, int64_t batch, int training, void* stream) {
+    if (!p || !x || !params || !out || !workspace) return set_err(MSHGNN_EINVAL, "null argument to mshgnn_forward");
+    if (batch < 1 || batch > (1 << 24)) return set_err(MSHGNN_EINVAL, "batch must be in [1, 2^24]");
+    for (int t = 0; t < p->n_types; ++t) if (!x[t]) return set_err(MSHGNN_EINVAL, "null input tensor");
+    StepCall c;
+    c.x = x; c.x_pitch = x_pitch; c.params = params; c.out = out; c.ws = (char*)workspace; c.batch = batch; c.training = training; c.stream = (hipStream_t)stream;
+    c.wide = wide;
+    return run_forward(p, c);
 }
 
 extern "C" int mshgnn_forward(const mshgnn_plan* p, const void* const* x, const int64_t* x_pitch, const float* params, float* out,
                               void* workspace, int64_t batch, int training, void* stream) {
-    if (!p || !x || !params || !out || !workspace) return set_err(MSHGNN_EINVAL, "null argument to mshgnn_forward");
+    return forward_entry(p, nullptr, x, x_pitch, params, out, workspace, batch, training, stream);
+}
+
+extern "C" int mshgnn_forward_src(const mshgnn_plan* p, int src_bytes, const void* const* src, const int64_t* src_pitch, void* const* x_rows, const int64_t* x_pitch,
+                                  const float* params, float* out, void* workspace, int64_t batch, int training, void* stream) {
+    if (!x_rows) return set_err(MSHGNN_EINVAL, "mshgnn_forward_src: x_rows is null (the plan-dtype rows the encoder materialises)");
+    WideSrc w{};
+    if (const int rc = fill_wide_src(p, src_bytes, src, src_pitch, "mshgnn_forward_src", w)) return rc;
+    return forward_entry(p, &w, x_rows, x_pitch, params, out, workspace, batch, training, stream);
+}
+
+// the backward entry points: from the output's gradient (grad_out), or from a loss fused into the decoder backward (out + y / labels -> loss_out)
+static int backward_entry(const mshgnn_plan* p, const void* const* x, const int64_t* x_pitch, const float* params, float* grad_params, void* workspace,
+                          int64_t batch, void* stream, StepCall& c) {
     if (batch < 1 || batch > (1 << 24)) return set_err(MSHGNN_EINVAL, "batch must be in [1, 2^24]");
-    for (int t = 0; t < p->n_types; ++t) if (!x[t]) return set_err(MSHGNN_EINVAL, "null input tensor");
-    if (p->gen) return gen_forward(p, x, x_pitch, params, out, (char*)workspace, batch, training, (hipStream_t)stream);
-    if (p->hp.d.dtype == MSHGNN_BF16X3) return x3_forward(p, x, x_pitch, params, out, (char*)workspace, batch, training, (hipStream_t)stream, nullptr);
-    if (p->hp.d.dtype == MSHGNN_F32) return forward_impl<float>(p, x, x_pitch, params, out, (char*)workspace, batch, training, (hipStream_t)stream);
-    return forward_impl<__bf16>(p, x, x_pitch, params, out, (char*)workspace, batch, training, (hipStream_t)stream);
+    c.x = x; c.x_pitch = x_pitch; c.params = params; c.grad_params = grad_params; c.ws = (char*)workspace; c.batch = batch; c.stream = (hipStream_t)stream;
+    return MSHGNN_OK;
 }
 
 extern "C" int mshgnn_backward(const mshgnn_plan* p, const void* const* x, const int64_t* x_pitch, const float* params, const float* grad_out,
                                float* grad_params, void* workspace, int64_t batch, void* stream) {
     if (!p || !x || !params || !grad_out || !workspace) return set_err(MSHGNN_EINVAL, "null argument to mshgnn_backward");
-    if (batch < 1 || batch > (1 << 24)) return set_err(MSHGNN_EINVAL, "batch must be in [1, 2^24]");
-    if (p->gen) return gen_backward(p, x, x_pitch, params, grad_out, grad_params, (char*)workspace, batch, (hipStream_t)stream, nullptr, nullptr, nullptr, nullptr);
-    if (p->hp.d.dtype == MSHGNN_BF16X3) return x3_backward(p, x, x_pitch, params, grad_out, grad_params, (char*)workspace, batch, (hipStream_t)stream, nullptr, nullptr, nullptr, nullptr, false, -1);
-    if (p->hp.d.dtype == MSHGNN_F32) return backward_impl<float>(p, x, x_pitch, params, grad_out, grad_params, (char*)workspace, batch, (hipStream_t)stream);
-    return backward_impl<__bf16>(p, x, x_pitch, params, grad_out, grad_params, (char*)workspace, batch, (hipStream_t)stream);
+    StepCall c;
+    if (const int rc = backward_entry(p, x, x_pitch, params, grad_params, workspace, batch, stream, c)) return rc;
+    c.grad_out = grad_out;
+    return run_backward(p, c);
 }
 
 extern "C" int mshgnn_backward_mse(const mshgnn_plan* p, const void* const* x, const int64_t* x_pitch, const float* params, const float* out,
                                    const float* y, float* loss_out, float* grad_params, void* workspace, int64_t batch, void* stream) {
     if (!p || !x || !params || !out || !y || !loss_out || !workspace) return set_err(MSHGNN_EINVAL, "null argument to mshgnn_backward_mse");
-    if (batch < 1 || batch > (1 << 24)) return set_err(MSHGNN_EINVAL, "batch must be in [1, 2^24]");
-    if (p->gen) return gen_backward(p, x, x_pitch, params, nullptr, grad_params, (char*)workspace, batch, (hipStream_t)stream, out, y, loss_out, nullptr);
-    if (p->hp.d.dtype == MSHGNN_BF16X3) return x3_backward(p, x, x_pitch, params, nullptr, grad_params, (char*)workspace, batch, (hipStream_t)stream, out, y, loss_out, nullptr, false, -1);
-    if (p->hp.d.dtype == MSHGNN_F32) return backward_impl<float>(p, x, x_pitch, params, nullptr, grad_params, (char*)workspace, batch, (hipStream_t)stream, out, y, loss_out);
-    return backward_impl<__bf16>(p, x, x_pitch, params, nullptr, grad_params, (char*)workspace, batch, (hipStream_t)stream, out, y, loss_out);
-}
-
-// ---- long batches as sub-steps (StepChunk, mshgnn_device.hpp) ----
-// Windows per sub-step of a one-call step over `batch` windows, 0: the step runs whole.  Whole: batches under twice MSHGNN_STEP_CHUNK (read when the plan is created; default 32 768; 0 = always whole), the
-// generic-width engine (its finalize kernel overwrites), wide-source calls (their source pointers are not offset here) and the sub-steps themselves.  Equal sub-steps of
-// whole 16-window tiles.
-static int64_t step_chunk_windows(const mshgnn_plan* p, int64_t batch) {
-    const int64_t limit = p->step_chunk;
-    if (limit <= 0 || batch < 2 * limit || p->gen || g_wide_src || g_step_chunk) return 0;
-    const int64_t n = batch / limit;      // sub-steps of at least `limit` windows each (a step's cost per window is flat from there up; shorter ones cost ~5 % more)
-    return ((batch + n - 1) / n + TILE_ROWS - 1) / TILE_ROWS * TILE_ROWS;
-}
-template <typename F> static int chunked_step(const mshgnn_plan* p, const void* const* x, const int64_t* x_pitch, int64_t batch, int64_t cw, F&& sub_step) {
-    const mshgnn_desc& d = p->hp.d;
-    const int64_t eb = d.dtype == MSHGNN_BF16 ? 2 : 4;      // input rows: bf16 on the bf16 plan, fp32 on the split and fp32 plans
-    int idx = 0;
-    for (int64_t w0 = 0; w0 < batch; w0 += cw, ++idx) {
-        const void* xc[MSHGNN_MAX_TYPES] = {};
-        for (int t = 0; t < p->n_types; ++t)
-            xc[t] = static_cast<const char*>(x[t]) + w0 * d.type_nodes[t] * (x_pitch ? x_pitch[t] : (int64_t)d.type_width[t]) * eb;
-        const StepChunk ck{batch, idx};
-        g_step_chunk = &ck;
-        const int rc = sub_step(xc, w0, std::min(cw, batch - w0));
-        g_step_chunk = nullptr;
-        if (rc) return rc;
-    }
-    return MSHGNN_OK;
-}
-
-extern "C" int mshgnn_step_mse(const mshgnn_plan* p, const void* const* x, const int64_t* x_pitch, const float* params, const float* y,
-                               float* out, float* loss_out, float* grad_params, void* workspace, int64_t batch, void* stream) {
-    if (!p || !x || !params || !y || !out || !loss_out || !grad_params || !workspace) return set_err(MSHGNN_EINVAL, "null argument to mshgnn_step_mse");
-    if (batch < 1 || batch > (1 << 24)) return set_err(MSHGNN_EINVAL, "batch must be in [1, 2^24]");
-    for (int t = 0; t < p->n_types; ++t) if (!x[t]) return set_err(MSHGNN_EINVAL, "null input tensor");
-    if (const int64_t cw = step_chunk_windows(p, batch)) {      // a long batch: sub-steps over contiguous window ranges, one gradient (StepChunk)
-        const int64_t orow = (int64_t)p->hp.d.type_nodes[p->hp.d.out_type] * p->hp.d.out_channels;
-        return chunked_step(p, x, x_pitch, batch, cw, [&](const void* const* xc, int64_t w0, int64_t bc) {
-            return mshgnn_step_mse(p, xc, x_pitch, params, y + w0 * orow, out + w0 * orow, loss_out, grad_params, workspace, bc, stream); });
-    }
-    hipStream_t st = (hipStream_t)stream;
-    if (p->gen) {      // generic-width engine: the two-call sequence
-        const int rc = gen_forward(p, x, x_pitch, params, out, (char*)workspace, batch, 1, st);
-        if (rc) return rc;
-        return gen_backward(p, x, x_pitch, params, nullptr, grad_params, (char*)workspace, batch, st, out, y, loss_out, nullptr);
-    }
-    if (p->hp.d.dtype == MSHGNN_BF16X3) {      // split plan: decoder, loss and decoder backward in the tail of its fused forward kernel as well
-        bool stack_done = false;
-        int rc = x3_forward(p, x, x_pitch, params, out, (char*)workspace, batch, 1, st, y, nullptr, &stack_done);
-        if (rc) return rc;
-        return x3_backward(p, x, x_pitch, params, nullptr, grad_params, (char*)workspace, batch, st, out, y, loss_out, nullptr, true, -1, stack_done);
-    }
-    if (p->hp.d.dtype == MSHGNN_F32 || !p->use_fused) {      // no fused stack kernels on this plan: the two-call sequence
-        int rc = p->hp.d.dtype == MSHGNN_F32 ? forward_impl<float>(p, x, x_pitch, params, out, (char*)workspace, batch, 1, st)
-                                              : forward_impl<__bf16>(p, x, x_pitch, params, out, (char*)workspace, batch, 1, st);
-        if (rc) return rc;
-        return p->hp.d.dtype == MSHGNN_F32 ? backward_impl<float>(p, x, x_pitch, params, nullptr, grad_params, (char*)workspace, batch, st, out, y, loss_out)
-                                           : backward_impl<__bf16>(p, x, x_pitch, params, nullptr, grad_params, (char*)workspace, batch, st, out, y, loss_out);
-    }
-    bool stack_done = false;
-    int rc = forward_impl<__bf16>(p, x, x_pitch, params, out, (char*)workspace, batch, 1, st, y, nullptr, nullptr, &stack_done);
-    if (rc) return rc;
-    return backward_impl<__bf16>(p, x, x_pitch, params, nullptr, grad_params, (char*)workspace, batch, st, out, y, loss_out, nullptr, true, -1, nullptr, stack_done);
-}
-
-extern "C" int mshgnn_step_ce(const mshgnn_plan* p, const void* const* x, const int64_t* x_pitch, const float* params, const int32_t* labels,
-                              float* out, float* loss_out, float* grad_params, void* workspace, int64_t batch, void* stream) {
-    if (!p || !x || !params || !labels || !out || !loss_out || !grad_params || !workspace) return set_err(MSHGNN_EINVAL, "null argument to mshgnn_step_ce");
-    if (batch < 1 || batch > (1 << 24)) return set_err(MSHGNN_EINVAL, "batch must be in [1, 2^24]");
-    for (int t = 0; t < p->n_types; ++t) if (!x[t]) return set_err(MSHGNN_EINVAL, "null input tensor");
-    if (p->hp.d.out_channels != 2) return set_err(MSHGNN_EINVAL, "mshgnn_step_ce: the classification wrappers have two logits per foot");
-    if (const int64_t cw = step_chunk_windows(p, batch)) {
-        const int64_t n_out = p->hp.d.type_nodes[p->hp.d.out_type];
-        return chunked_step(p, x, x_pitch, batch, cw, [&](const void* const* xc, int64_t w0, int64_t bc) {
-            return mshgnn_step_ce(p, xc, x_pitch, params, labels + w0 * n_out, out + w0 * n_out * 2, loss_out, grad_params, workspace, bc, stream); });
-    }
-    hipStream_t st = (hipStream_t)stream;
-    // bf16 plan with the fused stack kernels: decoder, cross entropy and decoder backward in the tail of the forward kernel; every other plan: the
-    // two-call sequence (mshgnn_forward + mshgnn_backward_ce)
-    if (!p->gen && p->hp.d.dtype == MSHGNN_BF16 && p->use_fused) {
-        bool stack_done = false;
-        int rc = forward_impl<__bf16>(p, x, x_pitch, params, out, (char*)workspace, batch, 1, st, nullptr, nullptr, labels, &stack_done);
-        if (rc) return rc;
-        return backward_impl<__bf16>(p, x, x_pitch, params, nullptr, grad_params, (char*)workspace, batch, st, out, nullptr, loss_out, labels, true, -1, nullptr, stack_done);
-    }
-    if (!p->gen && p->hp.d.dtype == MSHGNN_BF16X3) {      // split plan: decoder, cross entropy and decoder backward in the tail of its fused forward kernel as well
-        bool stack_done = false;
-        int rc = x3_forward(p, x, x_pitch, params, out, (char*)workspace, batch, 1, st, nullptr, nullptr, &stack_done, labels);
-        if (rc) return rc;
-        return x3_backward(p, x, x_pitch, params, nullptr, grad_params, (char*)workspace, batch, st, out, nullptr, loss_out, labels, true, -1, stack_done);
-    }
-    int rc = mshgnn_forward(p, x, x_pitch, params, out, workspace, batch, 1, stream);
-    if (rc) return rc;
-    return mshgnn_backward_ce(p, x, x_pitch, params, out, labels, loss_out, grad_params, workspace, batch, stream);
-}
-
-// ---- the caller's own fp64 / fp32 tensors as inputs (the reference's datasets produce fp64, gnnLightning.py:1183): the encoder converts in registers and
-// writes the plan-dtype rows the weight-gradient kernel needs on the side -- no separate cast + re-pitch pass.  Thin wrappers: they publish the source
-// descriptor to the encoder launch of the plain entry point they forward to (same thread, synchronous on the host).
-namespace {
-struct WideGuard {
-    WideSrc w{};
-    int rc = MSHGNN_OK;
-    WideGuard(const mshgnn_plan* p, int src_bytes, const void* const* src, const int64_t* src_pitch, const char* who) {
-        if (!p || !src) { rc = set_err(MSHGNN_EINVAL, std::string("null argument to ") + who); return; }
-        if (src_bytes != 4 && src_bytes != 8) { rc = set_err(MSHGNN_EINVAL, std::string(who) + ": src_bytes must be 4 (fp32) or 8 (fp64)"); return; }
-        if (p->gen || p->hp.d.dtype == MSHGNN_F32) { rc = set_err(MSHGNN_EUNSUPPORTED, std::string(who) + ": wide source rows run on the bf16 and split-bf16 plans of the LDS-resident kernels"); return; }
-        w.bytes = src_bytes;
-        for (int t = 0; t < p->n_types; ++t) {
-            if (!src[t]) { rc = set_err(MSHGNN_EINVAL, std::string(who) + ": null source tensor"); return; }
-            w.p[t] = src[t]; w.pitch[t] = src_pitch ? src_pitch[t] : p->hp.d.type_width[t];
-            if (w.pitch[t] < p->hp.d.type_width[t]) { rc = set_err(MSHGNN_EINVAL, std::string(who) + ": src_pitch smaller than the feature width"); return; }
-            if (((uintptr_t)src[t] % (src_bytes == 8 ? 8 : 4)) != 0) { rc = set_err(MSHGNN_EINVAL, std::string(who) + ": source tensor not aligned to its element size"); return; }
-            // fp32 rows are read in 8-byte units where the width allows it: rows must then start on 8 bytes
-            if (src_bytes == 4 && (p->hp.d.type_width[t] & 1) == 0 && ((((uintptr_t)src[t]) | (uintptr_t)(w.pitch[t] * 4)) & 7) != 0) {
-                rc = set_err(MSHGNN_EINVAL, std::string(who) + ": fp32 source rows of an even width must start 8-byte aligned (base and pitch)"); return; }
-        }
-        g_wide_src = &w;
-    }
-    ~WideGuard() { g_wide_src = nullptr; }
-};
-}  // namespace
-extern "C" int mshgnn_forward_src(const mshgnn_plan* p, int src_bytes, const void* const* src, const int64_t* src_pitch, void* const* x_rows, const int64_t* x_pitch,
-                                  const float* params, float* out, void* workspace, int64_t batch, int training, void* stream) {
-    if (!x_rows) return set_err(MSHGNN_EINVAL, "mshgnn_forward_src: x_rows is null (the plan-dtype rows the encoder materialises)");
-    WideGuard g(p, src_bytes, src, src_pitch, "mshgnn_forward_src");
-    if (g.rc) return g.rc;
-    return mshgnn_forward(p, x_rows, x_pitch, params, out, workspace, batch, training, stream);
-}
-extern "C" int mshgnn_step_mse_src(const mshgnn_plan* p, int src_bytes, const void* const* src, const int64_t* src_pitch, void* const* x_rows, const int64_t* x_pitch,
-                                   const float* params, const float* y, float* out, float* loss_out, float* grad_params, void* workspace, int64_t batch, void* stream) {
-    if (!x_rows) return set_err(MSHGNN_EINVAL, "mshgnn_step_mse_src: x_rows is null (the plan-dtype rows the encoder materialises)");
-    WideGuard g(p, src_bytes, src, src_pitch, "mshgnn_step_mse_src");
-    if (g.rc) return g.rc;
-    return mshgnn_step_mse(p, x_rows, x_pitch, params, y, out, loss_out, grad_params, workspace, batch, stream);
-}
-extern "C" int mshgnn_step_ce_src(const mshgnn_plan* p, int src_bytes, const void* const* src, const int64_t* src_pitch, void* const* x_rows, const int64_t* x_pitch,
-                                  const float* params, const int32_t* labels, float* out, float* loss_out, float* grad_params, void* workspace, int64_t batch, void* stream) {
-    if (!x_rows) return set_err(MSHGNN_EINVAL, "mshgnn_step_ce_src: x_rows is null (the plan-dtype rows the encoder materialises)");
-    WideGuard g(p, src_bytes, src, src_pitch, "mshgnn_step_ce_src");
-    if (g.rc) return g.rc;
-    return mshgnn_step_ce(p, x_rows, x_pitch, params, labels, out, loss_out, grad_params, workspace, batch, stream);
-}
-
-extern "C" int mshgnn_step_mse_phase(const mshgnn_plan* p, const void* const* x, const int64_t* x_pitch, const float* params, const float* y,
-                                     float* out, float* loss_out, float* grad_params, void* workspace, int64_t batch, int phase, void* stream) {
-    if (!p || !x || !params || !y || !out || !loss_out || !grad_params || !workspace) return set_err(MSHGNN_EINVAL, "null argument to mshgnn_step_mse_phase");
-    if (batch < 1 || batch > (1 << 24)) return set_err(MSHGNN_EINVAL, "batch must be in [1, 2^24]");
-    if (phase != 0 && phase != 1) return set_err(MSHGNN_EINVAL, "phase must be 0 or 1");
-    if (p->gen || p->hp.grad_split < 0) return set_err(MSHGNN_EUNSUPPORTED, "this plan has no two-phase gradient split");
-    for (int t = 0; t < p->n_types; ++t) if (!x[t]) return set_err(MSHGNN_EINVAL, "null input tensor");
-    hipStream_t st = (hipStream_t)stream;
-    if (p->hp.d.dtype == MSHGNN_BF16X3) {
-        if (phase == 0) { int rc = x3_forward(p, x, x_pitch, params, out, (char*)workspace, batch, 1, st, y); if (rc) return rc; }
-        return x3_backward(p, x, x_pitch, params, nullptr, grad_params, (char*)workspace, batch, st, out, y, loss_out, nullptr, true, phase);
-    }
-    const bool f32 = p->hp.d.dtype == MSHGNN_F32, fused = !f32 && p->use_fused;
-    bool stack_done = false;      // phase 0 on the fused plans: both sweeps of the stack in the one-launch step kernel, as mshgnn_step_mse (the specialised one where the plan has it)
-    if (phase == 0) {
-        int rc = f32 ? forward_impl<float>(p, x, x_pitch, params, out, (char*)workspace, batch, 1, st)
-                     : forward_impl<__bf16>(p, x, x_pitch, params, out, (char*)workspace, batch, 1, st, fused ? y : nullptr, nullptr, nullptr, fused ? &stack_done : nullptr);
-        if (rc) return rc;
-    }
-    return f32 ? backward_impl<float>(p, x, x_pitch, params, nullptr, grad_params, (char*)workspace, batch, st, out, y, loss_out, nullptr, false, phase)
-               : backward_impl<__bf16>(p, x, x_pitch, params, nullptr, grad_params, (char*)workspace, batch, st, out, y, loss_out, nullptr, fused, phase, nullptr, stack_done);
+    StepCall c;
+    if (const int rc = backward_entry(p, x, x_pitch, params, grad_params, workspace, batch, stream, c)) return rc;
+    c.loss = LossKind::MSE; c.out = const_cast<float*>(out); c.y = y; c.loss_out = loss_out;      // (the backward only reads out)
+    return run_backward(p, c);
 }
 
 extern "C" int mshgnn_backward_ce(const mshgnn_plan* p, const void* const* x, const int64_t* x_pitch, const float* params, const float* out,
                                   const int32_t* labels, float* loss_out, float* grad_params, void* workspace, int64_t batch, void* stream) {
     if (!p || !x || !params || !out || !labels || !loss_out || !workspace) return set_err(MSHGNN_EINVAL, "null argument to mshgnn_backward_ce");
-    if (batch < 1 || batch > (1 << 24)) return set_err(MSHGNN_EINVAL, "batch must be in [1, 2^24]");
+    StepCall c;
+    if (const int rc = backward_entry(p, x, x_pitch, params, grad_params, workspace, batch, stream, c)) return rc;
     if (p->hp.d.out_channels != 2) return set_err(MSHGNN_EINVAL, "mshgnn_backward_ce needs a 2-logit (contact classification) plan");
-    if (p->gen) return gen_backward(p, x, x_pitch, params, nullptr, grad_params, (char*)workspace, batch, (hipStream_t)stream, out, nullptr, loss_out, labels);
-    if (p->hp.d.dtype == MSHGNN_BF16X3) return x3_backward(p, x, x_pitch, params, nullptr, grad_params, (char*)workspace, batch, (hipStream_t)stream, out, nullptr, loss_out, labels, false, -1);
-    if (p->hp.d.dtype == MSHGNN_F32) return backward_impl<float>(p, x, x_pitch, params, nullptr, grad_params, (char*)workspace, batch, (hipStream_t)stream, out, nullptr, loss_out, labels);
-    return backward_impl<__bf16>(p, x, x_pitch, params, nullptr, grad_params, (char*)workspace, batch, (hipStream_t)stream, out, nullptr, loss_out, labels);
+    c.loss = LossKind::CE; c.out = const_cast<float*>(out); c.labels = labels; c.loss_out = loss_out;
+    return run_backward(p, c);
+}
+
+// The one-call steps (mshgnn_step_mse / _ce, their _src twins with `wide`, mshgnn_step_mse_phase): the checks they share, under the name of the plain entry point
+// (`who`: the _src twins always reported under it), and the call they fill.  target: y (MSE) or the int32 labels (CE).
+static int step_call(const mshgnn_plan* p, const char* who, const void* const* x, const int64_t* x_pitch, const float* params, LossKind kind, const void* target,
+                     float* out, float* loss_out, float* grad_params, void* workspace, int64_t batch, void* stream, StepCall& c) {
+    if (!p || !x || !params || !target || !out || !loss_out || !grad_params || !workspace) return set_err(MSHGNN_EINVAL, std::string("null argument to ") + who);
+    if (batch < 1 || batch > (1 << 24)) return set_err(MSHGNN_EINVAL, "batch must be in [1, 2^24]");
+    c.x = x; c.x_pitch = x_pitch; c.params = params; c.out = out; c.ws = (char*)workspace; c.batch = batch; c.training = 1; c.stream = (hipStream_t)stream;
+    c.loss = kind; c.loss_out = loss_out; c.grad_params = grad_params;
+    if (kind == LossKind::MSE) c.y = static_cast<const float*>(target); else c.labels = static_cast<const int32_t*>(target);
+    return MSHGNN_OK;
+}
+static int step_entry(const mshgnn_plan* p, const WideSrc* wide, const void* const* x, const int64_t* x_pitch, const float* params, LossKind kind, const void* target,
+                      float* out, float* loss_out, float* grad_params, void* workspace, int64_t batch, void* stream) {
+    StepCall c;
+    if (const int rc = step_call(p, kind == LossKind::CE ? "mshgnn_step_ce" : "mshgnn_step_mse", x, x_pitch, params, kind, target, out, loss_out, grad_params, workspace, batch, stream, c)) return rc;
+    for (int t = 0; t < p->n_types; ++t) if (!x[t]) return set_err(MSHGNN_EINVAL, "null input tensor");
+    if (kind == LossKind::CE && p->hp.d.out_channels != 2) return set_err(MSHGNN_EINVAL, "mshgnn_step_ce: the classification wrappers have two logits per foot");
+    c.wide = wide;
+    return run_step(p, c);
+}
+
+extern "C" int mshgnn_step_mse(const mshgnn_plan* p, const void* const* x, const int64_t* x_pitch, const float* params, const float* y,
+                               float* out, float* loss_out, float* grad_params, void* workspace, int64_t batch, void* stream) {
+    return step_entry(p, nullptr, x, x_pitch, params, LossKind::MSE, y, out, loss_out, grad_params, workspace, batch, stream);
+}
+
+extern "C" int mshgnn_step_ce(const mshgnn_plan* p, const void* const* x, const int64_t* x_pitch, const float* params, const int32_t* labels,
+                              float* out, float* loss_out, float* grad_params, void* workspace, int64_t batch, void* stream) {
+    return step_entry(p, nullptr, x, x_pitch, params, LossKind::CE, labels, out, loss_out, grad_params, workspace, batch, stream);
+}
+
+extern "C" int mshgnn_step_mse_src(const mshgnn_plan* p, int src_bytes, const void* const* src, const int64_t* src_pitch, void* const* x_rows, const int64_t* x_pitch,
+                                   const float* params, const float* y, float* out, float* loss_out, float* grad_params, void* workspace, int64_t batch, void* stream) {
+    if (!x_rows) return set_err(MSHGNN_EINVAL, "mshgnn_step_mse_src: x_rows is null (the plan-dtype rows the encoder materialises)");
+    WideSrc w{};
+    if (const int rc = fill_wide_src(p, src_bytes, src, src_pitch, "mshgnn_step_mse_src", w)) return rc;
+    return step_entry(p, &w, x_rows, x_pitch, params, LossKind::MSE, y, out, loss_out, grad_params, workspace, batch, stream);
+}
+extern "C" int mshgnn_step_ce_src(const mshgnn_plan* p, int src_bytes, const void* const* src, const int64_t* src_pitch, void* const* x_rows, const int64_t* x_pitch,
+                                  const float* params, const int32_t* labels, float* out, float* loss_out, float* grad_params, void* workspace, int64_t batch, void* stream) {
+    if (!x_rows) return set_err(MSHGNN_EINVAL, "mshgnn_step_ce_src: x_rows is null (the plan-dtype rows the encoder materialises)");
+    WideSrc w{};
+    if (const int rc = fill_wide_src(p, src_bytes, src, src_pitch, "mshgnn_step_ce_src", w)) return rc;
+    return step_entry(p, &w, x_rows, x_pitch, params, LossKind::CE, labels, out, loss_out, grad_params, workspace, batch, stream);
+}
+
+// The MSE step in two halves (gw_phase): phase 0 = forward, backward sweep and every weight gradient but the encoder's; phase 1 = the encoder's alone, from the dX_0
+// phase 0 left in the workspace -- no forward, so what the forward would have told the backward is said here.  Never chunked.
+extern "C" int mshgnn_step_mse_phase(const mshgnn_plan* p, const void* const* x, const int64_t* x_pitch, const float* params, const float* y,
+                                     float* out, float* loss_out, float* grad_params, void* workspace, int64_t batch, int phase, void* stream) {
+    StepCall c;
+    if (const int rc = step_call(p, "mshgnn_step_mse_phase", x, x_pitch, params, LossKind::MSE, y, out, loss_out, grad_params, workspace, batch, stream, c)) return rc;
+    if (phase != 0 && phase != 1) return set_err(MSHGNN_EINVAL, "phase must be 0 or 1");
+    if (p->gen || p->hp.grad_split < 0) return set_err(MSHGNN_EUNSUPPORTED, "this plan has no two-phase gradient split");
+    for (int t = 0; t < p->n_types; ++t) if (!x[t]) return set_err(MSHGNN_EINVAL, "null input tensor");
+    c.gw_phase = phase;
+    if (phase == 0) { if (const int rc = run_forward(p, c)) return rc; }
+    else c.dec_done = p->hp.d.dtype == MSHGNN_BF16X3 || (p->hp.d.dtype == MSHGNN_BF16 && p->use_fused);      // (as phase 0's forward found: the plans whose stack kernel has the fused tail)
+    return run_backward(p, c);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -3929,26 +3923,37 @@ __global__ void k_series_run_ptrs(const int* runs, int n_runs, WindowArgs wa, in
     run_ptr[r] = p;
 }
 
-static int step_series(const mshgnn_plan* p, const mshgnn_window_desc* d, const float* const* src, const void* const* src_bf16,
-                       const int64_t* src_cstride, const int64_t* src_rows, const int64_t* starts, int64_t batch,
-                       void* const* x_out, const int64_t* x_pitch, float* y_out, float* quat_out, void* run_ptrs,
-                       const float* params, float* out, float* loss_out, float* grad_params, void* workspace, void* stream, int32_t* labels_out) {
-    const bool ce = labels_out != nullptr;      // classification wrappers: cross entropy over the per-foot logit pairs, labels = the window labels != 0
-    if (!p || !d || !src || !src_cstride || !src_rows || !starts || !y_out || !run_ptrs || !params || !out || !loss_out ||
-        !grad_params || !workspace || (x_out && !x_pitch)) return set_err(MSHGNN_EINVAL, "null argument to mshgnn_step_mse_series / mshgnn_step_ce_series");
-    if (batch < 1 || batch > (1 << 24)) return set_err(MSHGNN_EINVAL, "batch must be in [1, 2^24]");
-    // bf16 plan (fused stack kernels): bf16 copies of the series, optional materialisation.  Split plan (MSHGNN_BF16X3): the fp32 series
-    // themselves, windows always materialised (fp32) for its weight-gradient kernel.
-    const bool x3 = !p->gen && p->hp.d.dtype == MSHGNN_BF16X3;
-    if (p->gen || (!x3 && (p->hp.d.dtype != MSHGNN_BF16 || !p->use_fused)))
-        return set_err(MSHGNN_EUNSUPPORTED, "mshgnn_step_mse_series runs on the bf16 plan with the fused stack kernels or on the split plan; use mshgnn_assemble_windows + mshgnn_step_mse");
-    if (!x3 && !src_bf16) return set_err(MSHGNN_EINVAL, "null argument to mshgnn_step_mse_series / mshgnn_step_ce_series");
-    if (x3 && !x_out) return set_err(MSHGNN_EUNSUPPORTED, "the split plan's weight-gradient kernel reads materialised windows: x_out must be given");
+// ---- what the series routes share: the caller's description of the sequence and the windows, one check of the window descriptor against the plan, one fill of
+// SeriesSrc / LabelArgs.  Training = mshgnn_step_mse_series / mshgnn_step_ce_series, evaluation = mshgnn_forward_series.
+struct SeriesArgs {      // as the entry points receive them
+    const mshgnn_window_desc* d;
+    const float* const* src; const void* const* src_bf16; const int64_t* src_cstride; const int64_t* src_rows;
+    const int64_t* starts; int64_t batch;
+    float* y_out; float* quat_out; int32_t* labels_out;      // labels_out: the classification routes (contact flags = labels != 0)
+    void* run_ptrs;
+};
+struct SeriesChecks {      // where training and evaluation differ
+    const char* who;                  // the route's name in messages (who_ce: where a message is the classification step's own)
+    const char* who_ce;
+    bool labels_required;             // training: the recipe must describe labels; evaluation: only when y_out is given
+    bool takes_normalize;             // evaluation takes standardised recipes (the NORM encoders); training refuses them
+    bool ce_needs_two_logits;         // training checks the plan's logit pairs here; evaluation leaves them to the caller's loss
+    // node rows of several runs need history >= 8 (the encoders take a chunk's 8 elements from at most two runs).  Only evaluation checks it.  Training lacks the
+    // check: closing that changes what the wrappers must fall back on and belongs in a change of its own -- until then this stays false there.
+    bool several_runs_need_history8;
+};
+
+// the window descriptor against the plan (x_out: the window buffers training materialises into, or null), then the label description against the model's outputs
+static int check_window_desc(const mshgnn_plan* p, const SeriesArgs& s, const SeriesChecks& k, void* const* x_out, const int64_t* x_pitch) {
+    const mshgnn_window_desc* d = s.d;
     const mshgnn_desc& md = p->hp.d;
+    const bool x3 = md.dtype == MSHGNN_BF16X3, want_y = s.y_out != nullptr, ce = s.labels_out != nullptr;
     const bool dtype_ok = x3 ? (d->dtype == MSHGNN_F32 || d->dtype == MSHGNN_BF16X3) : d->dtype == MSHGNN_BF16;
-    if (d->n_types != md.n_types || !dtype_ok || d->normalize || !d->fast_layout || d->n_src < 1 || d->n_src > WIN_MAX_SRC || d->n_runs < 1 ||
-        d->n_runs > WIN_MAX_RUNS || !d->runs || !d->rows || d->history < 1 || d->n_label < 1 || !d->label_cols || d->label_src < 0 || d->label_src >= d->n_src)
-        return set_err(MSHGNN_EINVAL, "mshgnn_step_mse_series: the window descriptor must be a fast_layout, unstandardised recipe with labels at the plan's input dtype (bf16; split plan: fp32)");
+    const bool labels_ok = d->n_label >= 1 && d->label_cols && d->label_src >= 0 && d->label_src < d->n_src;
+    if (d->n_types != md.n_types || !dtype_ok || (d->normalize && !k.takes_normalize) || !d->fast_layout || d->n_src < 1 || d->n_src > WIN_MAX_SRC || d->n_runs < 1 ||
+        d->n_runs > WIN_MAX_RUNS || !d->runs || !d->rows || d->history < 1 || (k.labels_required && !labels_ok))
+        return set_err(MSHGNN_EINVAL, std::string(k.who) + ": the window descriptor must be a fast_layout" + (k.takes_normalize ? "" : ", unstandardised") + " recipe" +
+                                          (k.labels_required ? " with labels" : "") + " at the plan's input dtype (bf16; split plan: fp32)");
     const int epc = x3 ? 4 : 8;      // elements per 16 bytes of the window buffers
     int n_rows = 0;
     for (int t = 0; t < d->n_types; ++t) {
@@ -3957,56 +3962,91 @@ static int step_series(const mshgnn_plan* p, const mshgnn_window_desc* d, const 
         n_rows += d->type_nodes[t];
     }
     if (n_rows != d->n_rows) return set_err(MSHGNN_EINVAL, "window recipe: one node row per node expected");
-    if (d->n_label != md.type_nodes[md.out_type] * (ce ? 1 : md.out_channels)) return set_err(MSHGNN_EINVAL, "window recipe: label count differs from the model's outputs");
-    if (ce && md.out_channels != 2) return set_err(MSHGNN_EINVAL, "mshgnn_step_ce_series: the classification wrappers have two logits per foot");
-    WindowArgs wa{};
-    for (int i = 0; i < d->n_src; ++i) {
-        // (the bf16 copies need 8 elements of slack behind every column: a chunk's 16-byte load may run past the window's last step)
-        if (!src[i] || (!x3 && !src_bf16[i]) || src_rows[i] < d->history || src_cstride[i] < src_rows[i] + 8 || src_rows[i] >= (1ll << 31)) return set_err(MSHGNN_EINVAL, "bad source array (the gather needs cstride >= rows + 8)");
-        wa.src[i] = x3 ? src[i] : reinterpret_cast<const float*>(src_bf16[i]); wa.src_cstride[i] = src_cstride[i];
+    if (k.several_runs_need_history8 && d->history < 8 && d->n_runs > d->n_rows)
+        return set_err(MSHGNN_EUNSUPPORTED, std::string(k.who) + ": node rows of several runs need history >= 8; use mshgnn_assemble_windows + mshgnn_forward");
+    if (ce && !want_y) return set_err(MSHGNN_EINVAL, std::string(k.who) + ": labels_out comes with y_out");
+    if (want_y) {
+        if (!labels_ok) return set_err(MSHGNN_EINVAL, "bad label description");
+        // the label rows are the model's targets: per out node its out_channels values, or (classification) one contact flag
+        if (d->n_label != md.type_nodes[md.out_type] * (ce ? 1 : md.out_channels)) return set_err(MSHGNN_EINVAL, "window recipe: label count differs from the model's outputs");
+        if (k.ce_needs_two_logits && ce && md.out_channels != 2) return set_err(MSHGNN_EINVAL, std::string(k.who_ce) + ": the classification wrappers have two logits per foot");
     }
-    hipStream_t st = (hipStream_t)stream;
-    // labels (fp32 series)
-    WindowArgs la{};
-    for (int i = 0; i < d->n_src; ++i) { la.src[i] = src[i]; la.src_cstride[i] = src_cstride[i]; }
-    la.starts = starts; la.B = batch; la.T = d->history; la.label_cols = d->label_cols; la.n_label = d->n_label; la.label_src = d->label_src;
-    la.label_rotate = d->label_rotate; la.quat_src = d->quat_src; la.y = y_out; la.quat = quat_out;
-    if (d->label_rotate && (d->n_label % 3 != 0 || d->quat_src < 0)) return set_err(MSHGNN_EINVAL, "label rotation needs 3-D labels and a quaternion source");
+    return MSHGNN_OK;
+}
+static int check_label_rotation(const SeriesArgs& s, const SeriesChecks& k) {
+    if (!s.y_out) return MSHGNN_OK;
+    if (s.d->label_rotate && (s.d->n_label % 3 != 0 || s.d->quat_src < 0)) return set_err(MSHGNN_EINVAL, "label rotation needs 3-D labels and a quaternion source");
+    if (s.labels_out && s.d->label_rotate) return set_err(MSHGNN_EINVAL, std::string(k.who_ce) + ": contact labels are not rotated");
+    return MSHGNN_OK;
+}
+// the source arrays the gather reads: the fp32 series (split plan, standardised recipes) or their bf16 copies
+static int check_series_sources(const SeriesArgs& s, bool fp32_gather, WindowArgs& wa) {
+    for (int i = 0; i < s.d->n_src; ++i) {
+        // (8 elements of slack behind every column: a chunk's 16-byte loads may run past the window's last step)
+        if (!s.src[i] || (!fp32_gather && !s.src_bf16[i]) || s.src_rows[i] < s.d->history || s.src_cstride[i] < s.src_rows[i] + 8 || s.src_rows[i] >= (1ll << 31))
+            return set_err(MSHGNN_EINVAL, "bad source array (the gather needs cstride >= rows + 8)");
+        wa.src[i] = fp32_gather ? s.src[i] : reinterpret_cast<const float*>(s.src_bf16[i]); wa.src_cstride[i] = s.src_cstride[i];
+    }
+    return MSHGNN_OK;
+}
+// The run-pointer pre-launch (in front of the encoder, same stream) and the encoder's description of the series.  Labels, quaternions and contact flags come out of extra
+// workgroups of the encoder launch (want_y / want_q; a test sequence without labels: none).
+static void fill_series_src(const SeriesArgs& s, const WindowArgs& wa, bool fp32_gather, bool want_q, hipStream_t st, SeriesSrc& ser) {
+    const mshgnn_window_desc* d = s.d;
     static_assert(WIN_MAX_RUNS <= 256, "k_series_run_ptrs resolves the runs in one 256-thread workgroup");
-    if (ce && d->label_rotate) return set_err(MSHGNN_EINVAL, "mshgnn_step_ce_series: contact labels are not rotated");
     if (!d->run_ptrs_ready)      // (the caller vouches for the scratch's contents otherwise: same descriptor, same source arrays as the call that filled it)
-        hipLaunchKernelGGL(k_series_run_ptrs, dim3(1), dim3(256), 0, st, d->runs, d->n_runs, wa, x3 ? 4 : 2, reinterpret_cast<unsigned long long*>(run_ptrs));
-    SeriesSrc ser{};
-    {   // labels: extra workgroups of the encoder launch
+        hipLaunchKernelGGL(k_series_run_ptrs, dim3(1), dim3(256), 0, st, d->runs, d->n_runs, wa, fp32_gather ? 4 : 2, reinterpret_cast<unsigned long long*>(s.run_ptrs));
+    const bool want_y = s.y_out != nullptr;
+    if (want_y || want_q) {
         LabelArgs& l = ser.lab;
-        l.lab = la.src[la.label_src]; l.lab_cs = la.src_cstride[la.label_src];
-        l.quat_src = la.quat_src >= 0 ? la.src[la.quat_src] : nullptr; l.quat_cs = la.quat_src >= 0 ? la.src_cstride[la.quat_src] : 0;
-        l.starts = starts; l.B = batch; l.T = d->history; l.label_cols = d->label_cols; l.n_label = d->n_label; l.label_rotate = d->label_rotate;
-        l.y = y_out; l.quat = quat_out; l.labels_int = ce ? labels_out : nullptr;
+        const int ls = want_y ? d->label_src : 0;
+        l.lab = s.src[ls]; l.lab_cs = s.src_cstride[ls];
+        const bool q = d->quat_src >= 0 && (want_q || d->label_rotate);
+        l.quat_src = q ? s.src[d->quat_src] : nullptr; l.quat_cs = q ? s.src_cstride[d->quat_src] : 0;
+        l.starts = s.starts; l.B = s.batch; l.T = d->history; l.label_cols = d->label_cols; l.n_label = want_y ? d->n_label : 0; l.label_rotate = want_y ? d->label_rotate : 0;
+        l.y = s.y_out; l.quat = s.quat_out; l.labels_int = s.labels_out;
     }
-    ser.run_ptr = reinterpret_cast<const unsigned long long*>(run_ptrs); ser.rows = d->rows; ser.starts = starts; ser.T = d->history;
+    ser.run_ptr = reinterpret_cast<const unsigned long long*>(s.run_ptrs); ser.rows = d->rows; ser.starts = s.starts; ser.T = d->history;
     { int r0 = 0; for (int t = 0; t < d->n_types; ++t) { ser.row0[t] = r0; r0 += d->type_nodes[t]; } }
-    if (x3) {      // (the split plan fuses the MSE into its forward kernel's tail; cross entropy: forward, then the fused-loss backward)
-        bool x3_stack_done = false;
-        int rc = x3_forward(p, x_out, x_pitch, params, out, (char*)workspace, batch, 1, st, ce ? nullptr : y_out, &ser, &x3_stack_done, ce ? labels_out : nullptr);
-        if (rc) return rc;
-        return x3_backward(p, x_out, x_pitch, params, nullptr, grad_params, (char*)workspace, batch, st, out, ce ? nullptr : y_out, loss_out,
-                           ce ? labels_out : nullptr, true, -1, x3_stack_done);
-    }
-    bool stack_done = false;
-    int rc = forward_impl<__bf16>(p, x_out, x_pitch, params, out, (char*)workspace, batch, 1, st, ce ? nullptr : y_out, &ser, ce ? labels_out : nullptr, &stack_done);
-    if (rc) return rc;
-    // x_out == NULL: no materialised windows at all -- the weight-gradient kernel gathers its raw-input operands from the series as well
-    return backward_impl<__bf16>(p, x_out, x_pitch, params, nullptr, grad_params, (char*)workspace, batch, st, out, ce ? nullptr : y_out, loss_out,
-                                 ce ? labels_out : nullptr, true, -1, x_out ? nullptr : &ser, stack_done);
+}
+// the plans the series routes run on: the bf16 plan with the fused stack kernels and the split plan
+static bool series_plan_ok(const mshgnn_plan* p) { return !p->gen && (p->hp.d.dtype == MSHGNN_BF16X3 || (p->hp.d.dtype == MSHGNN_BF16 && p->use_fused)); }
+
+static int step_series(const mshgnn_plan* p, const SeriesArgs& s, void* const* x_out, const int64_t* x_pitch, const float* params, float* out, float* loss_out,
+                       float* grad_params, void* workspace, void* stream) {
+    const bool ce = s.labels_out != nullptr;      // classification wrappers: cross entropy over the per-foot logit pairs, labels = the window labels != 0
+    if (!p || !s.d || !s.src || !s.src_cstride || !s.src_rows || !s.starts || !s.y_out || !s.run_ptrs || !params || !out || !loss_out ||
+        !grad_params || !workspace || (x_out && !x_pitch)) return set_err(MSHGNN_EINVAL, "null argument to mshgnn_step_mse_series / mshgnn_step_ce_series");
+    if (s.batch < 1 || s.batch > (1 << 24)) return set_err(MSHGNN_EINVAL, "batch must be in [1, 2^24]");
+    // bf16 plan (fused stack kernels): bf16 copies of the series, optional materialisation.  Split plan (MSHGNN_BF16X3): the fp32 series
+    // themselves, windows always materialised (fp32) for its weight-gradient kernel.
+    if (!series_plan_ok(p))
+        return set_err(MSHGNN_EUNSUPPORTED, "mshgnn_step_mse_series runs on the bf16 plan with the fused stack kernels or on the split plan; use mshgnn_assemble_windows + mshgnn_step_mse");
+    const bool x3 = p->hp.d.dtype == MSHGNN_BF16X3;
+    if (!x3 && !s.src_bf16) return set_err(MSHGNN_EINVAL, "null argument to mshgnn_step_mse_series / mshgnn_step_ce_series");
+    if (x3 && !x_out) return set_err(MSHGNN_EUNSUPPORTED, "the split plan's weight-gradient kernel reads materialised windows: x_out must be given");
+    const SeriesChecks k{"mshgnn_step_mse_series", "mshgnn_step_ce_series", /*labels_required*/ true, /*takes_normalize*/ false, /*ce_needs_two_logits*/ true,
+                         /*several_runs_need_history8*/ false};
+    WindowArgs wa{};
+    if (const int rc = check_window_desc(p, s, k, x_out, x_pitch)) return rc;
+    if (const int rc = check_series_sources(s, x3, wa)) return rc;
+    if (const int rc = check_label_rotation(s, k)) return rc;
+    SeriesSrc ser{};
+    fill_series_src(s, wa, x3, /*want_q: the quaternion travels with the labels wherever the recipe has one*/ true, (hipStream_t)stream, ser);
+    StepCall c;
+    c.x = x_out; c.x_pitch = x_pitch; c.params = params; c.out = out; c.ws = (char*)workspace; c.batch = s.batch; c.training = 1; c.stream = (hipStream_t)stream;
+    c.loss = ce ? LossKind::CE : LossKind::MSE; c.y = s.y_out; c.labels = s.labels_out; c.loss_out = loss_out; c.grad_params = grad_params;
+    c.series = &ser;
+    c.gradw_from_series = !x_out;      // no materialised windows at all (bf16 plan only, see above): the weight-gradient kernel gathers its raw-input operands from the series as well
+    return run_step(p, c);
 }
 
 extern "C" int mshgnn_step_mse_series(const mshgnn_plan* p, const mshgnn_window_desc* d, const float* const* src, const void* const* src_bf16,
                                       const int64_t* src_cstride, const int64_t* src_rows, const int64_t* starts, int64_t batch,
                                       void* const* x_out, const int64_t* x_pitch, float* y_out, float* quat_out, void* run_ptrs,
                                       const float* params, float* out, float* loss_out, float* grad_params, void* workspace, void* stream) {
-    return step_series(p, d, src, src_bf16, src_cstride, src_rows, starts, batch, x_out, x_pitch, y_out, quat_out, run_ptrs, params, out, loss_out, grad_params,
-                       workspace, stream, nullptr);
+    const SeriesArgs s{d, src, src_bf16, src_cstride, src_rows, starts, batch, y_out, quat_out, nullptr, run_ptrs};
+    return step_series(p, s, x_out, x_pitch, params, out, loss_out, grad_params, workspace, stream);
 }
 
 extern "C" int mshgnn_step_ce_series(const mshgnn_plan* p, const mshgnn_window_desc* d, const float* const* src, const void* const* src_bf16,
@@ -4014,8 +4054,8 @@ extern "C" int mshgnn_step_ce_series(const mshgnn_plan* p, const mshgnn_window_d
                                      void* const* x_out, const int64_t* x_pitch, float* y_out, int32_t* labels_out, void* run_ptrs,
                                      const float* params, float* out, float* loss_out, float* grad_params, void* workspace, void* stream) {
     if (!labels_out) return set_err(MSHGNN_EINVAL, "null argument to mshgnn_step_ce_series");
-    return step_series(p, d, src, src_bf16, src_cstride, src_rows, starts, batch, x_out, x_pitch, y_out, nullptr, run_ptrs, params, out, loss_out, grad_params,
-                       workspace, stream, labels_out);
+    const SeriesArgs s{d, src, src_bf16, src_cstride, src_rows, starts, batch, y_out, nullptr, labels_out, run_ptrs};
+    return step_series(p, s, x_out, x_pitch, params, out, loss_out, grad_params, workspace, stream);
 }
 // ------------------------------------------------------------------------------------------------------
 // mshgnn_forward_series: evaluation straight from a sequence's resident raw series -- mshgnn_assemble_windows + mshgnn_forward(training = 0) with the window
@@ -4058,68 +4098,35 @@ extern "C" int mshgnn_forward_series(const mshgnn_plan* p, const mshgnn_window_d
     if (!p || !d || !src || !src_cstride || !src_rows || !starts || !run_ptrs || !params || !out || !workspace)
         return set_err(MSHGNN_EINVAL, "null argument to mshgnn_forward_series");
     if (batch < 1 || batch > (1 << 24)) return set_err(MSHGNN_EINVAL, "batch must be in [1, 2^24]");
-    const bool x3 = !p->gen && p->hp.d.dtype == MSHGNN_BF16X3;
-    if (p->gen || (!x3 && (p->hp.d.dtype != MSHGNN_BF16 || !p->use_fused)))
+    if (!series_plan_ok(p))
         return set_err(MSHGNN_EUNSUPPORTED, "mshgnn_forward_series runs on the bf16 plan with the fused stack kernels or on the split plan; use mshgnn_assemble_windows + mshgnn_forward");
+    const bool x3 = p->hp.d.dtype == MSHGNN_BF16X3;
     const bool norm = d->normalize != 0;
     if (!x3 && !norm && !src_bf16) return set_err(MSHGNN_EINVAL, "null argument to mshgnn_forward_series (the bf16 plan gathers unstandardised windows from the bf16 copies)");
     if (norm && !stats) return set_err(MSHGNN_EINVAL, "mshgnn_forward_series: a standardised recipe needs the stats scratch (mshgnn_forward_series_stats_bytes)");
     if (norm && d->history < 2) return set_err(MSHGNN_EINVAL, "history must be >= 2 when normalising");
     if (norm && d->history > 256) return set_err(MSHGNN_EUNSUPPORTED, "history longer than 256 steps is not supported by this build");
     if (norm && ((uintptr_t)stats & 15)) return set_err(MSHGNN_EINVAL, "mshgnn_forward_series: the stats scratch must be 16-byte aligned");
-    const mshgnn_desc& md = p->hp.d;
-    const bool dtype_ok = x3 ? (d->dtype == MSHGNN_F32 || d->dtype == MSHGNN_BF16X3) : d->dtype == MSHGNN_BF16;
-    if (d->n_types != md.n_types || !dtype_ok || !d->fast_layout || d->n_src < 1 || d->n_src > WIN_MAX_SRC || d->n_runs < 1 || d->n_runs > WIN_MAX_RUNS || !d->runs ||
-        !d->rows || d->history < 1)
-        return set_err(MSHGNN_EINVAL, "mshgnn_forward_series: the window descriptor must be a fast_layout recipe at the plan's input dtype (bf16; split plan: fp32)");
-    int n_rows = 0;
-    for (int t = 0; t < d->n_types; ++t) {
-        if (d->type_nodes[t] != md.type_nodes[t] || d->type_width[t] != md.type_width[t]) return set_err(MSHGNN_EINVAL, "window recipe and plan disagree on a node type");
-        n_rows += d->type_nodes[t];
-    }
-    if (n_rows != d->n_rows) return set_err(MSHGNN_EINVAL, "window recipe: one node row per node expected");
-    // the encoders take a chunk's 8 elements from at most two runs: windows shorter than a chunk are taken only where every node row is a single run
-    if (d->history < 8 && d->n_runs > d->n_rows) return set_err(MSHGNN_EUNSUPPORTED, "mshgnn_forward_series: node rows of several runs need history >= 8; use mshgnn_assemble_windows + mshgnn_forward");
-    const bool want_y = y_out != nullptr;
-    if (labels_out && !want_y) return set_err(MSHGNN_EINVAL, "mshgnn_forward_series: labels_out comes with y_out");
-    if (want_y) {
-        if (d->n_label < 1 || !d->label_cols || d->label_src < 0 || d->label_src >= d->n_src) return set_err(MSHGNN_EINVAL, "bad label description");
-        // the label rows are the model's targets: per out node its out_channels values, or (labels_out: the classification wrappers) one contact flag
-        if (d->n_label != md.type_nodes[md.out_type] * (labels_out ? 1 : md.out_channels))
-            return set_err(MSHGNN_EINVAL, "window recipe: label count differs from the model's outputs");
-        if (d->label_rotate && (d->n_label % 3 != 0 || d->quat_src < 0)) return set_err(MSHGNN_EINVAL, "label rotation needs 3-D labels and a quaternion source");
-        if (labels_out && d->label_rotate) return set_err(MSHGNN_EINVAL, "mshgnn_forward_series: contact labels are not rotated");
-    }
+    const SeriesArgs s{d, src, src_bf16, src_cstride, src_rows, starts, batch, y_out, quat_out, labels_out, run_ptrs};
+    const SeriesChecks k{"mshgnn_forward_series", "mshgnn_forward_series", /*labels_required*/ false, /*takes_normalize*/ true, /*ce_needs_two_logits*/ false,
+                         /*several_runs_need_history8*/ true};
+    if (const int rc = check_window_desc(p, s, k, nullptr, nullptr)) return rc;
+    if (const int rc = check_label_rotation(s, k)) return rc;
     if (d->quat_src >= d->n_src) return set_err(MSHGNN_EINVAL, "quat_src out of range");
     const bool fp32_gather = x3 || norm;      // standardisation happens before the bf16 rounding: the bf16 plan's NORM encoder reads the fp32 series too
     WindowArgs wa{};
-    for (int i = 0; i < d->n_src; ++i) {
-        // (8 elements of slack behind every column: a chunk's 16-byte loads may run past the window's last step)
-        if (!src[i] || (!fp32_gather && !src_bf16[i]) || src_rows[i] < d->history || src_cstride[i] < src_rows[i] + 8 || src_rows[i] >= (1ll << 31)) return set_err(MSHGNN_EINVAL, "bad source array (the gather needs cstride >= rows + 8)");
-        wa.src[i] = fp32_gather ? src[i] : reinterpret_cast<const float*>(src_bf16[i]); wa.src_cstride[i] = src_cstride[i];
-    }
+    if (const int rc = check_series_sources(s, fp32_gather, wa)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (!d->run_ptrs_ready)
-        hipLaunchKernelGGL(k_series_run_ptrs, dim3(1), dim3(256), 0, st, d->runs, d->n_runs, wa, fp32_gather ? 4 : 2, reinterpret_cast<unsigned long long*>(run_ptrs));
     SeriesSrc ser{};
-    const bool want_q = quat_out != nullptr && d->quat_src >= 0;
-    if (want_y || want_q) {      // labels: extra workgroups of the encoder launch (a test sequence without labels: none)
-        LabelArgs& l = ser.lab;
-        const int ls = want_y ? d->label_src : 0;
-        l.lab = src[ls]; l.lab_cs = src_cstride[ls];
-        const bool q = d->quat_src >= 0 && (want_q || d->label_rotate);
-        l.quat_src = q ? src[d->quat_src] : nullptr; l.quat_cs = q ? src_cstride[d->quat_src] : 0;
-        l.starts = starts; l.B = batch; l.T = d->history; l.label_cols = d->label_cols; l.n_label = want_y ? d->n_label : 0; l.label_rotate = want_y ? d->label_rotate : 0;
-        l.y = y_out; l.quat = quat_out; l.labels_int = labels_out;
-    }
-    ser.run_ptr = reinterpret_cast<const unsigned long long*>(run_ptrs); ser.rows = d->rows; ser.starts = starts; ser.T = d->history;
-    { int r0 = 0; for (int t = 0; t < d->n_types; ++t) { ser.row0[t] = r0; r0 += d->type_nodes[t]; } }
+    fill_series_src(s, wa, fp32_gather, quat_out != nullptr && d->quat_src >= 0, st, ser);
     if (norm) {
         const int64_t waves = batch * d->n_runs;
         hipLaunchKernelGGL(k_series_stats, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, d->runs, d->n_runs, ser.run_ptr, starts, batch, reinterpret_cast<double*>(stats));
         ser.stats = reinterpret_cast<const double*>(stats); ser.n_runs = d->n_runs;
     }
-    if (x3) return x3_forward(p, nullptr, nullptr, params, out, (char*)workspace, batch, 0, st, nullptr, &ser, nullptr, nullptr);
-    return forward_impl<__bf16>(p, nullptr, nullptr, params, out, (char*)workspace, batch, 0, st, nullptr, &ser, nullptr, nullptr);
+    StepCall c;      // evaluation, nothing materialised (x = null): only the nodes whose X_0 can reach the output get encoder workgroups
+    c.params = params; c.out = out; c.ws = (char*)workspace; c.batch = batch; c.training = 0; c.stream = st;
+    c.series = &ser;
+    return run_forward(p, c);
 }
 #endif      // MSHGNN_SPEC_SHARD == 0

@@ -531,15 +531,11 @@ struct WideSrc {
     const void* p[MSHGNN_MAX_TYPES];         // per type: [B][n_t][pitch] source rows
     int64_t pitch[MSHGNN_MAX_TYPES];         // elements
 };
-inline thread_local const WideSrc* g_wide_src = nullptr;      // set by the _src entry points around the plain call they forward to (host side, same thread)
 // One-call steps over at least twice MSHGNN_STEP_CHUNK windows (default 32 768) run as a sequence of equal sub-steps of at least that many windows over contiguous window ranges on the same workspace
-// (mshgnn_step_mse / mshgnn_step_ce): every sub-step scales its loss terms by the WHOLE batch's element count and the finalize launches after the first add to the
+// (run_step, mshgnn.hip): every sub-step scales its loss terms by the WHOLE batch's element count and the finalize launches after the first add to the
 // flat gradient and the loss instead of overwriting them.  Measured on Solo-12 K4 (BASELINE configs[3], 65 536 windows): the weight-gradient launch of one 65 536-window
-// step costs 1.03x (bf16) / 1.21x (split plan) two 32 768-window ones, and the step's stash footprint halves.  Set by the entry point around its sub-steps (host side).
-struct StepChunk { int64_t total_windows; int index; };
-inline thread_local const StepChunk* g_step_chunk = nullptr;
-inline int64_t loss_windows(int64_t B) { return g_step_chunk ? g_step_chunk->total_windows : B; }
-inline int step_accumulates() { return g_step_chunk && g_step_chunk->index > 0 ? 1 : 0; }
+// step costs 1.03x (bf16) / 1.21x (split plan) two 32 768-window ones, and the step's stash footprint halves.
+struct StepChunk { int64_t total_windows; int index; };      // total_windows == 0: the call is no sub-step (the batch itself, index 0)
 // 8 source elements held as 8-byte units -> 8 fp32 values (two f32x4); units past `nvalid` elements were not requested: zero
 template <int SB> __device__ __forceinline__ void wide_to_f32(const u32x2 (&u)[SB], int nvalid, f32x4& lo, f32x4& hi) {
     float f[8];
@@ -1450,17 +1446,49 @@ inline int gw_parts_for(int plan_parts, int lanes, int ipl, int64_t B, int chunk
     return best_cost < 0.97 * cost(qmax) ? best : qmax;
 }
 
+// ONE CALL, BY NAME: everything a forward, a backward or a one-call step needs on its way from an extern "C" entry point (which validates and fills it) through the
+// engine dispatch (run_forward / run_backward / run_step, mshgnn.hip) to the launches.  Pointers a route does not use stay null.
+enum class LossKind { NONE, MSE, CE };
+struct StepCall {
+    // operands
+    const void* const* x = nullptr;      // per type: the plan-dtype input rows (series / wide routes: the rows the encoder materialises, null where the route materialises none)
+    const int64_t* x_pitch = nullptr;
+    const float* params = nullptr;
+    float* out = nullptr;
+    char* ws = nullptr;
+    int64_t batch = 0;
+    int training = 1;
+    hipStream_t stream = nullptr;
+    // what the backward starts from: the output's gradient, or a loss fused into the decoder backward (forward: into its tail, where the engine has one)
+    const float* grad_out = nullptr;
+    LossKind loss = LossKind::NONE;
+    const float* y = nullptr;             // LossKind::MSE
+    const int32_t* labels = nullptr;      // LossKind::CE
+    float* loss_out = nullptr;
+    float* grad_params = nullptr;         // null: activation backward only (dX_0 for mshgnn_input_grad)
+    // where the encoder's rows come from: x, or at most one of these two
+    const WideSrc* wide = nullptr;        // the caller's fp64 / fp32 rows (mshgnn_*_src)
+    const SeriesSrc* series = nullptr;    // a sequence's resident series (mshgnn_*_series)
+    bool gradw_from_series = false;       // nothing was materialised (x == null): the weight-gradient kernel gathers its raw-input operands from the series as well
+    int gw_phase = -1;                    // -1 = everything; 0 = backward sweep + every weight gradient but the encoder's; 1 = only the encoder's (phase 0 left dX_0 in the workspace)
+    StepChunk chunk{0, 0};
+    // what the forward tells the backward
+    bool dec_done = false;                // decoder, loss and decoder backward ran in the tail of the forward's stack kernel
+    bool stack_done = false;              // the one-launch step kernel ran the backward sweep of the stack as well
+
+    const float* y_fused() const { return loss == LossKind::MSE ? y : nullptr; }
+    const int32_t* labels_fused() const { return loss == LossKind::CE ? labels : nullptr; }
+    int64_t total_windows() const { return chunk.total_windows ? chunk.total_windows : batch; }      // the windows the loss is a mean over
+    int accumulates() const { return chunk.index > 0 ? 1 : 0; }                                      // sub-steps after the first add to the gradient and the loss
+};
+
 // k_finalize launch of a step (mshgnn.hip): fixed-order slab sums -> flat gradient (+ fused loss)
-int run_finalize(const mshgnn_plan* p, const mshgnn_ws_layout& lay, char* ws, float* gparams, int B, float* loss, bool is_ce, bool dec_done,
-                 int gw_phase, hipStream_t st, int gw_parts);
+int run_finalize(const mshgnn_plan* p, const StepCall& c, const mshgnn_ws_layout& lay, int gw_parts);
 // split-bf16 parity plan (mshgnn_x3.hip)
 int x3_set_attrs(mshgnn_plan* p);
 int x3_attach_program(mshgnn_plan* p, void* selector);
-int x3_forward(const mshgnn_plan* p, const void* const* x, const int64_t* x_pitch, const float* params, float* out, char* ws, int64_t batch,
-               int training, hipStream_t st, const float* y_fused, const SeriesSrc* series = nullptr, bool* stack_step_done = nullptr,
-               const int32_t* labels_fused = nullptr);
-int x3_backward(const mshgnn_plan* p, const void* const* x, const int64_t* x_pitch, const float* params, const float* gout, float* gparams, char* ws,
-                int64_t batch, hipStream_t st, const float* out, const float* y, float* loss, const int32_t* labels, bool dec_done, int gw_phase, bool stack_done = false);
+int x3_forward(const mshgnn_plan* p, StepCall& c);
+int x3_backward(const mshgnn_plan* p, const StepCall& c);
 int x3_launch_prep(const PrepArgs& a, hipStream_t st);
 // weight-image packing for the other engines (mshgnn.hip): k_prep<__bf16> or the hi / lo images of k_prep_x3
 int launch_prep(const PrepArgs& a, bool split, hipStream_t st);
@@ -1474,7 +1502,5 @@ const uint8_t* gen_signs(const mshgnn_plan* p);
 const std::vector<mshgnn_kernel_stat>* gen_kstats(const mshgnn_plan* p);
 void gen_layout(const mshgnn_plan* p, int64_t batch, int training, mshgnn_ws_layout* out);
 int gen_host_compile(const mshgnn_desc* desc, mshgnn_info* info, int32_t* n_tables);
-int gen_forward(const mshgnn_plan* p, const void* const* x, const int64_t* x_pitch, const float* params, float* out, char* ws, int64_t batch,
-                int training, hipStream_t st);
-int gen_backward(const mshgnn_plan* p, const void* const* x, const int64_t* x_pitch, const float* params, const float* gout, float* gparams, char* ws,
-                 int64_t batch, hipStream_t st, const float* out, const float* y, float* loss, const int32_t* labels);
+int gen_forward(const mshgnn_plan* p, StepCall& c);
+int gen_backward(const mshgnn_plan* p, const StepCall& c);

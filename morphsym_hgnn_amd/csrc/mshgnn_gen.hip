@@ -1674,25 +1674,25 @@ static void g_launch_jobs(const mshgnn_plan* p, const Launch& ln, GArgs a, hipSt
     }
 }
 
-int gen_forward(const mshgnn_plan* p, const void* const* x, const int64_t* x_pitch, const float* params, float* out, char* ws, int64_t batch,
-                int training, hipStream_t st) {
+int gen_forward(const mshgnn_plan* p, StepCall& c) {      // (no fused tail on this engine: the loss, if any, is the backward's; c.dec_done / c.stack_done stay false)
     const mshgnn_gen_state* g = p->gen;
     const GenPlan& gp = g->gp;
     const mshgnn_desc& d = gp.d;
-    mshgnn_ws_layout lay; layout_gen_workspace(gp, batch, training, &lay);
-    const int B = (int)batch;
+    mshgnn_ws_layout lay; layout_gen_workspace(gp, c.batch, c.training, &lay);
+    const int B = (int)c.batch;
+    char* ws = c.ws; hipStream_t st = c.stream;
     {
-        PrepArgs a{params, ws + lay.wpack, reinterpret_cast<float*>(ws + lay.bias), g->d_packs, g->d_biases, gp.n_img, (int)gp.biases.size()};
+        PrepArgs a{c.params, ws + lay.wpack, reinterpret_cast<float*>(ws + lay.bias), g->d_packs, g->d_biases, gp.n_img, (int)gp.biases.size()};
         ProfScope ps(p, gp.ks_prep, st);
         launch_prep(a, gp.split, st);
     }
     GArgs a{};
-    int rc = g_fill(p, lay, x, x_pitch, ws, B, training, a);
+    int rc = g_fill(p, lay, c.x, c.x_pitch, ws, B, c.training, a);
     if (rc) return rc;
     for (const Launch& ln : gp.fwd) g_launch_jobs(p, ln, a, st);
     {
         GDecArgs da{};
-        da.xl = ws + lay.x[gp.L]; da.params = params; da.out_mask = g->d_out_mask; da.out = out; da.off_w = d.off_dec_w; da.off_b = d.off_dec_b;
+        da.xl = ws + lay.x[gp.L]; da.params = c.params; da.out_mask = g->d_out_mask; da.out = c.out; da.off_w = d.off_dec_w; da.off_b = d.off_dec_b;
         da.B = B; da.Hd = gp.Hd; da.node0 = gp.type_base[d.out_type]; da.n_out = d.type_nodes[d.out_type]; da.dout = d.out_channels;
         const int64_t rows = (int64_t)B * da.n_out;
         ProfScope ps(p, gp.ks_dec_fwd, st);
@@ -1703,35 +1703,36 @@ int gen_forward(const mshgnn_plan* p, const void* const* x, const int64_t* x_pit
     return MSHGNN_OK;
 }
 
-int gen_backward(const mshgnn_plan* p, const void* const* x, const int64_t* x_pitch, const float* params, const float* gout, float* gparams, char* ws,
-                 int64_t batch, hipStream_t st, const float* out, const float* y, float* loss, const int32_t* labels) {
+int gen_backward(const mshgnn_plan* p, const StepCall& c) {
     const mshgnn_gen_state* g = p->gen;
     const GenPlan& gp = g->gp;
     const mshgnn_desc& d = gp.d;
-    mshgnn_ws_layout lay; layout_gen_workspace(gp, batch, 1, &lay);
-    const int B = (int)batch;
+    mshgnn_ws_layout lay; layout_gen_workspace(gp, c.batch, 1, &lay);
+    const int B = (int)c.batch;
+    char* ws = c.ws; hipStream_t st = c.stream;
+    const float* y = c.y_fused(); const int32_t* labels = c.labels_fused();
     const int n_out = d.type_nodes[d.out_type];
     {
         GDecArgs da{};
-        da.xl = ws + lay.x[gp.L]; da.dxl = ws + lay.dx[gp.L]; da.params = params; da.out_mask = g->d_out_mask; da.gout = gout;
+        da.xl = ws + lay.x[gp.L]; da.dxl = ws + lay.dx[gp.L]; da.params = c.params; da.out_mask = g->d_out_mask; da.gout = c.grad_out;
         if (gp.dhm && gp.L >= 1 && !((d.flags & MSHGNN_FLAG_BASE_MLP) && d.out_type == d.mlp_type)) { da.dhl = ws + lay.dh[gp.L - 1]; da.maskb = reinterpret_cast<const uint8_t*>(ws + lay.mask[gp.L - 1]); da.dh_only = (d.flags & MSHGNN_FLAG_RESIDUAL) ? 0 : 1; }
         da.slabs = reinterpret_cast<float*>(ws + lay.dec_slabs); da.off_w = d.off_dec_w; da.off_b = d.off_dec_b;
         da.B = B; da.Hd = gp.Hd; da.node0 = gp.type_base[d.out_type]; da.n_out = n_out; da.dout = d.out_channels;
-        if (y) { da.y = y; da.out = const_cast<float*>(out); da.inv_n = 1.0f / (float)((int64_t)B * n_out * d.out_channels); }
-        if (labels) { da.labels = labels; da.out = const_cast<float*>(out); da.inv_n = 1.0f / (float)((int64_t)B * n_out); }
+        if (y) { da.y = y; da.out = c.out; da.inv_n = 1.0f / (float)((int64_t)B * n_out * d.out_channels); }
+        if (labels) { da.labels = labels; da.out = c.out; da.inv_n = 1.0f / (float)((int64_t)B * n_out); }
         const int dec_lds = 16 * 8 * TW * 4;
         ProfScope ps(p, gp.ks_dec_bwd, st);
         if (gp.split) hipLaunchKernelGGL(k_gdec_bwd<true>, dim3(NWG_DEC), dim3(256), dec_lds, st, da);
         else hipLaunchKernelGGL(k_gdec_bwd<false>, dim3(NWG_DEC), dim3(256), dec_lds, st, da);
     }
     GArgs a{};
-    int rc = g_fill(p, lay, x, x_pitch, ws, B, 1, a);
+    int rc = g_fill(p, lay, c.x, c.x_pitch, ws, B, 1, a);
     if (rc) return rc;
     for (const Launch& ln : gp.bwd) g_launch_jobs(p, ln, a, st);
-    if (!gparams) {      // activation backward only (dX_0 for mshgnn_input_grad): no weight gradients; one workgroup for the fused loss (if any)
+    if (!c.grad_params) {      // activation backward only (dX_0 for mshgnn_input_grad): no weight gradients; one workgroup for the fused loss (if any)
         if (y || labels) {
             GFinArgs fa{g->d_tables + gp.fin_off, reinterpret_cast<const float*>(ws + lay.slabs), reinterpret_cast<const float*>(ws + lay.dec_slabs), nullptr,
-                        gp.n_units, gp.n_parts, gp.Hd, loss, 1.0f / (float)((int64_t)B * n_out * (labels ? 1 : d.out_channels))};
+                        gp.n_units, gp.n_parts, gp.Hd, c.loss_out, 1.0f / (float)((int64_t)B * n_out * (labels ? 1 : d.out_channels))};
             hipLaunchKernelGGL(k_gfinalize, dim3(1, 1), dim3(256), 0, st, fa);
         }
         HIPCHK(hipGetLastError());
@@ -1758,8 +1759,8 @@ int gen_backward(const mshgnn_plan* p, const void* const* x, const int64_t* x_pi
         else hipLaunchKernelGGL((k_ggradw<false, 1>), dim3(grid), dim3(512), ggw_lds_bytes(false, 1), st, a);
     }
     {
-        GFinArgs fa{g->d_tables + gp.fin_off, reinterpret_cast<const float*>(ws + lay.slabs), reinterpret_cast<const float*>(ws + lay.dec_slabs), gparams,
-                    gp.n_units, gp.n_parts, gp.Hd, (y || labels) ? loss : nullptr, 1.0f / (float)((int64_t)B * n_out * (labels ? 1 : d.out_channels))};
+        GFinArgs fa{g->d_tables + gp.fin_off, reinterpret_cast<const float*>(ws + lay.slabs), reinterpret_cast<const float*>(ws + lay.dec_slabs), c.grad_params,
+                    gp.n_units, gp.n_parts, gp.Hd, (y || labels) ? c.loss_out : nullptr, 1.0f / (float)((int64_t)B * n_out * (labels ? 1 : d.out_channels))};
         ProfScope ps(p, gp.ks_fin, st);
         hipLaunchKernelGGL(k_gfinalize, dim3(gp.n_fin, 8), dim3(256), 0, st, fa);
     }

@@ -1299,14 +1299,18 @@ static void x3_stack_args(const mshgnn_plan* p, const mshgnn_ws_layout& lay, cha
     a.stash_nt = stash_nt_for(p->stash_nt_force, B, stash_rows_of(hp), H * 2);      // (counted per row, not per byte: stash_nt_for)
 }
 
-int x3_forward(const mshgnn_plan* p, const void* const* x, const int64_t* x_pitch, const float* params, float* out, char* ws, int64_t batch,
-               int training, hipStream_t st, const float* y_fused, const SeriesSrc* series, bool* stack_step_done, const int32_t* labels_fused) {
+int x3_forward(const mshgnn_plan* p, StepCall& c) {
     const HostPlan& hp = p->hp;
     const mshgnn_desc& d = hp.d;
-    mshgnn_ws_layout lay; layout_workspace(hp, batch, training, &lay);
-    const int B = (int)batch;
+    const int training = c.training;
+    mshgnn_ws_layout lay; layout_workspace(hp, c.batch, training, &lay);
+    const int B = (int)c.batch;
+    const void* const* x = c.x; const int64_t* x_pitch = c.x_pitch;
+    char* ws = c.ws; hipStream_t st = c.stream;
+    const SeriesSrc* series = c.series; const WideSrc* wide = c.wide;
+    const float* y_fused = c.y_fused(); const int32_t* labels_fused = c.labels_fused();
     // 1. hi / lo weight images; few packs: only the encoder's packs + biases here, the layer packs under the encoder's tail (as forward_impl of mshgnn.hip)
-    PrepArgs pa{params, ws + lay.wpack, reinterpret_cast<float*>(ws + lay.bias), p->d_packs, p->d_biases, hp.n_img, (int)hp.biases.size()};
+    PrepArgs pa{c.params, ws + lay.wpack, reinterpret_cast<float*>(ws + lay.bias), p->d_packs, p->d_biases, hp.n_img, (int)hp.biases.size()};
     int enc_pack0 = hp.n_img;
     for (int t = 0; t < hp.NT; ++t) if (hp.pack_enc_base[t] >= 0) enc_pack0 = std::min(enc_pack0, hp.pack_enc_base[t]);
     static const bool embed_off = TUNE_ENV("MSHGNN_PREP_EMBED") && atoi(TUNE_ENV("MSHGNN_PREP_EMBED")) == 0;
@@ -1319,7 +1323,6 @@ int x3_forward(const mshgnn_plan* p, const void* const* x, const int64_t* x_pitc
         if (prep_use_tiled(a.n_packs)) hipLaunchKernelGGL((k_prep_tiled<__bf16, true>), dim3(prep_tiled_grid(a.n_packs, a.n_biases)), dim3(256), 0, st, a);
         else hipLaunchKernelGGL(k_prep_x3, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a);
     }
-    const WideSrc* wide = series ? nullptr : g_wide_src;      // (mshgnn_*_src: the caller's fp64 / fp32 rows; x = the fp32 rows to materialise)
     {   // 2. encoder (fp32 inputs)
         EncArgs a{};
         a.n_types = hp.NT; a.B = B; a.NN = hp.NN; a.tiles = (B + 63) / 64;
@@ -1362,7 +1365,7 @@ int x3_forward(const mshgnn_plan* p, const void* const* x, const int64_t* x_pitc
             if (series->stats) hipLaunchKernelGGL((k_enc_x3<true, true, 0, true>), dim3(enc_grid), dim3(256), 8 * P16::BLK, st, a, hp.n_img, *series, WideSrc{});
             else hipLaunchKernelGGL((k_enc_x3<true, true>), dim3(enc_grid), dim3(256), 8 * P16::BLK, st, a, hp.n_img, *series, WideSrc{});
         }
-        else if (wide) {      // the caller's fp64 / fp32 rows: converted by the encoder, fp32 rows written to x on the side
+        else if (wide) {      // (mshgnn_*_src) the caller's fp64 / fp32 rows: converted by the encoder, fp32 rows written to x on the side
             if (!a.aligned) return set_err(MSHGNN_EINVAL, "wide source rows: the fp32 rows need 16-byte alignment and a pitch that is a multiple of 4");
             if (wide->bytes == 8) hipLaunchKernelGGL((k_enc_x3<true, false, 8>), dim3(enc_grid), dim3(256), 8 * P16::BLK, st, a, hp.n_img, SeriesSrc{}, *wide);
             else hipLaunchKernelGGL((k_enc_x3<true, false, 4>), dim3(enc_grid), dim3(256), 8 * P16::BLK, st, a, hp.n_img, SeriesSrc{}, *wide);
@@ -1375,15 +1378,16 @@ int x3_forward(const mshgnn_plan* p, const void* const* x, const int64_t* x_pitc
         x3_stack_args(p, lay, ws, B, a);
         a.tile_in = ws + lay.x[0]; a.training = training;
         for (int l = 0; l < hp.L; ++l) a.prog_off[l] = hp.fs_fwd_off[l];
-        a.params = params; a.out_mask = p->d_out_mask; a.out = out; a.off_dec_w = d.off_dec_w; a.off_dec_b = d.off_dec_b;
+        a.params = c.params; a.out_mask = p->d_out_mask; a.out = c.out; a.off_dec_w = d.off_dec_w; a.off_dec_b = d.off_dec_b;
         a.node0 = hp.type_base[d.out_type]; a.n_out = d.type_nodes[d.out_type]; a.dout = d.out_channels;
         if (y_fused) {
             a.y = y_fused; a.dec_slabs = reinterpret_cast<float*>(ws + lay.dec_slabs);
-            a.inv_n = 1.0f / (float)(loss_windows(B) * a.n_out * a.dout);
+            a.inv_n = 1.0f / (float)(c.total_windows() * a.n_out * a.dout);
         } else if (labels_fused) {      // mshgnn_step_ce: cross entropy over the per-foot logit pairs, mean over B * n_out rows (the tail is the bf16 plan's)
             a.labels = labels_fused; a.dec_slabs = reinterpret_cast<float*>(ws + lay.dec_slabs);
-            a.inv_n = 1.0f / (float)(loss_windows(B) * a.n_out);
+            a.inv_n = 1.0f / (float)(c.total_windows() * a.n_out);
         }
+        c.dec_done = y_fused || labels_fused;
         const int tiles = (B + P16::ROWS - 1) / P16::ROWS;
         a.stamps = stamp_ptr("MSHGNN_STAMPS");
         // one-call step: the backward sweep in the same launch.  The tail's reduction scratch (one decoder slab per wave) must not touch the out-type nodes' blocks
@@ -1392,7 +1396,8 @@ int x3_forward(const mshgnn_plan* p, const void* const* x, const int64_t* x_pitc
         const size_t red_need = (size_t)(LAYER_THREADS / 64) * DEC_SLAB_FLOATS * sizeof(float);
         const size_t red_back = (size_t)(a.node0 + a.n_out) * P16::BLK, plane = (size_t)hp.fs_blk * P16::BLK;
         const bool red_front_ok = (size_t)a.node0 * P16::BLK >= red_need, red_back_ok = red_back + red_need <= plane;
-        const bool step = stack_step_done && (y_fused || labels_fused) && p->use_step && (red_front_ok || red_back_ok);
+        // (a two-phase step, c.gw_phase >= 0, keeps the backward sweep a launch of its own on this plan)
+        const bool step = c.gw_phase < 0 && c.dec_done && p->use_step && (red_front_ok || red_back_ok);
         if (step && !red_front_ok) a.red_off = (int)red_back;
         ProfScope ps(p, step ? hp.ks_stack_step : hp.ks_stack_fwd, st);
         if (step) {
@@ -1402,7 +1407,7 @@ int x3_forward(const mshgnn_plan* p, const void* const* x, const int64_t* x_pitc
             if (ks) hipLaunchKernelGGL(ks, dim3(tiles), dim3(LAYER_THREADS), x3_lds_stack(hp), st, a);
             else if (hp.x3_alias) hipLaunchKernelGGL(k_stack_step_x3<true>, dim3(tiles), dim3(LAYER_THREADS), x3_lds_stack(hp), st, a);
             else hipLaunchKernelGGL(k_stack_step_x3<false>, dim3(tiles), dim3(LAYER_THREADS), x3_lds_stack(hp), st, a);
-            *stack_step_done = true;
+            c.stack_done = true;
         } else
         if (StackKernelX3 kf = p->use_spec ? x3_spec_kernel(hp, 1) : nullptr) hipLaunchKernelGGL(kf, dim3(tiles), dim3(LAYER_THREADS), x3_lds_stack(hp), st, a);
         else if (hp.x3_alias) hipLaunchKernelGGL(k_stack_fwd_x3<true>, dim3(tiles), dim3(LAYER_THREADS), x3_lds_stack(hp), st, a);
@@ -1412,23 +1417,25 @@ int x3_forward(const mshgnn_plan* p, const void* const* x, const int64_t* x_pitc
     return MSHGNN_OK;
 }
 
-int x3_backward(const mshgnn_plan* p, const void* const* x, const int64_t* x_pitch, const float* params, const float* gout, float* gparams, char* ws,
-                int64_t batch, hipStream_t st, const float* out, const float* y, float* loss, const int32_t* labels, bool dec_done, int gw_phase, bool stack_done) {
+int x3_backward(const mshgnn_plan* p, const StepCall& c) {
     const HostPlan& hp = p->hp;
     const mshgnn_desc& d = hp.d;
-    mshgnn_ws_layout lay; layout_workspace(hp, batch, 1, &lay);
-    const int B = (int)batch;
-    if (!dec_done && gw_phase != 1) {
+    mshgnn_ws_layout lay; layout_workspace(hp, c.batch, 1, &lay);
+    const int B = (int)c.batch;
+    const void* const* x = c.x; const int64_t* x_pitch = c.x_pitch;
+    char* ws = c.ws; hipStream_t st = c.stream;
+    const int gw_phase = c.gw_phase;
+    if (!c.dec_done && gw_phase != 1) {
         DecArgs a{};
-        a.xl = ws + lay.x[hp.L]; a.dxl = ws + lay.dx[hp.L]; a.params = params; a.out_mask = p->d_out_mask; a.gout = gout;
+        a.xl = ws + lay.x[hp.L]; a.dxl = ws + lay.dx[hp.L]; a.params = c.params; a.out_mask = p->d_out_mask; a.gout = c.grad_out;
         a.slabs = reinterpret_cast<float*>(ws + lay.dec_slabs); a.off_w = d.off_dec_w; a.off_b = d.off_dec_b;
         a.B = B; a.NN = hp.NN; a.node0 = hp.type_base[d.out_type]; a.n_out = d.type_nodes[d.out_type]; a.dout = d.out_channels; a.slab0 = 0;
-        if (y) { a.y = y; a.out = const_cast<float*>(out); a.loss = loss; a.inv_n = 1.0f / (float)(loss_windows(B) * a.n_out * a.dout); }
-        if (labels) { a.labels = labels; a.out = const_cast<float*>(out); a.loss = loss; a.inv_n = 1.0f / (float)(loss_windows(B) * a.n_out); }
+        if (c.loss == LossKind::MSE) { a.y = c.y; a.out = c.out; a.loss = c.loss_out; a.inv_n = 1.0f / (float)(c.total_windows() * a.n_out * a.dout); }
+        if (c.loss == LossKind::CE) { a.labels = c.labels; a.out = c.out; a.loss = c.loss_out; a.inv_n = 1.0f / (float)(c.total_windows() * a.n_out); }
         ProfScope ps(p, hp.ks_dec_bwd, st);
         hipLaunchKernelGGL(k_dec_bwd_x3, dim3(NWG_DEC), dim3(256), 0, st, a);
     }
-    if (gw_phase != 1 && !stack_done) {
+    if (gw_phase != 1 && !c.stack_done) {
         StackArgs a{};
         x3_stack_args(p, lay, ws, B, a);
         a.tile_in = ws + lay.dx[hp.L]; a.training = 1; a.mask0_off = lay.dd[0];
@@ -1439,7 +1446,7 @@ int x3_backward(const mshgnn_plan* p, const void* const* x, const int64_t* x_pit
         else hipLaunchKernelGGL(k_stack_bwd_x3, dim3(tiles), dim3(LAYER_THREADS), x3_lds_stack(hp), st, a);
     }
     const int gw_parts = gw_parts_for(hp.n_parts, hp.n_lanes, hp.gw_ipl, B, 32, p->n_cu);      // window parts of this batch's weight-gradient launch (32-window steps)
-    if (gparams) {      // (NULL: activation backward only)
+    if (c.grad_params) {      // (NULL: activation backward only)
         GradwArgs a{};
         a.ws = ws;
         for (int l = 0; l <= hp.L; ++l) { a.buf_off[BUF_X + l] = lay.x[l]; a.buf_off[BUF_DX + l] = lay.dx[l]; }
@@ -1465,6 +1472,6 @@ int x3_backward(const mshgnn_plan* p, const void* const* x, const int64_t* x_pit
             else hipLaunchKernelGGL(k_gradw_x3_lean<false>, dim3(a.n_pad * gw_parts), dim3(256), 0, st, a);
         }
     }
-    return run_finalize(p, lay, ws, gparams, B, (y || labels) ? loss : nullptr, labels != nullptr, dec_done, gw_phase, st, gw_parts);
+    return run_finalize(p, c, lay, gw_parts);
 }
 #endif      // MSHGNN_SPEC_SHARD == 0

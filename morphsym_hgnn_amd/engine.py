@@ -538,6 +538,28 @@ class Engine:
             raise ValueError(f"{name} must be a contiguous fp32 device tensor of {self.spec.flat_size()} elements")
 
     # ---- hot path ------------------------------------------------------------------------------
+    def _call(self, name: str, xs, B: int, ptrs, pitch, *tail):
+        """lib.<name>(plan, ptrs, pitch, *tail, stream) on the current stream of this engine's device -- or, where `xs` is the caller's fp64 / fp32 tensors still to be
+        converted (a pending WideInputs), lib.<name>_src: the encoder converts them and writes the plan-dtype rows `xs` holds."""
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        with torch.cuda.device(self.device):
+            if isinstance(xs, WideInputs) and xs.pending:
+                self._rows_written(xs, B)
+                _check(self.lib, getattr(self.lib, name + "_src")(self._plan, *self._src_args(xs), ptrs, pitch, *tail, stream), name + "_src")
+                xs.pending = False
+            else:
+                _check(self.lib, getattr(self.lib, name)(self._plan, ptrs, pitch, *tail, stream), name)
+
+    def _results(self, B: int, out, grad_flat, loss):
+        """The result tensors of a step the caller did not bring: (out, grad_flat, loss[1])."""
+        if out is None:
+            out = torch.empty(B * self.n_out, self.spec.out_channels, dtype=torch.float32, device=self.device)
+        if grad_flat is None:
+            grad_flat = torch.empty(self.spec.flat_size(), dtype=torch.float32, device=self.device)
+        if loss is None:
+            loss = torch.empty(1, dtype=torch.float32, device=self.device)
+        return out, grad_flat, loss
+
     def forward(self, xs: Sequence[torch.Tensor], params_flat: torch.Tensor, B: int, training: bool = True,
                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
         xs = self._rewrap(xs)
@@ -549,17 +571,7 @@ class Engine:
         ws = self.workspace(B, training)
         if training:
             self._tickets[B] = self._tickets.get(B, 0) + 1; self._chunked[B] = False
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        with torch.cuda.device(self.device):
-            if isinstance(xs, WideInputs) and xs.pending:      # the caller's fp64 / fp32 tensors: the encoder converts them and writes the plan-dtype rows `xs` holds
-                self._rows_written(xs, B)
-                sb, sp, spitch = self._src_args(xs)
-                _check(self.lib, self.lib.mshgnn_forward_src(self._plan, sb, sp, spitch, ptrs, pitch, params_flat.data_ptr(), out.data_ptr(),
-                                                             ws.data_ptr(), B, int(training), stream), "mshgnn_forward_src")
-                xs.pending = False
-            else:
-                _check(self.lib, self.lib.mshgnn_forward(self._plan, ptrs, pitch, params_flat.data_ptr(), out.data_ptr(),
-                                                         ws.data_ptr(), B, int(training), stream), "mshgnn_forward")
+        self._call("mshgnn_forward", xs, B, ptrs, pitch, params_flat.data_ptr(), out.data_ptr(), ws.data_ptr(), B, int(training))
         return out
 
     def backward(self, xs: Sequence[torch.Tensor], params_flat: torch.Tensor, grad_out: torch.Tensor, B: int,
@@ -578,10 +590,8 @@ class Engine:
         else:
             self._check_flat(grad_flat, "grad_flat")
         ws = self.workspace(B, True)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.mshgnn_backward(self._plan, ptrs, pitch, params_flat.data_ptr(), grad_out.data_ptr(),
-                                                  grad_flat.data_ptr() if grad_flat is not None else None, ws.data_ptr(), B, stream), "mshgnn_backward")
+        self._call("mshgnn_backward", None, B, ptrs, pitch, params_flat.data_ptr(), grad_out.data_ptr(),
+                   grad_flat.data_ptr() if grad_flat is not None else None, ws.data_ptr(), B)
         self._bwd_ticket[B] = self._tickets.get(B, 0)
         return grad_flat
 
@@ -615,89 +625,56 @@ class Engine:
                                                         ws.data_ptr(), B, stream), "mshgnn_input_grad")
         return out
 
-    def backward_mse(self, xs: Sequence[torch.Tensor], params_flat: torch.Tensor, out: torch.Tensor, y: torch.Tensor, B: int,
-                     grad_flat: Optional[torch.Tensor] = None, loss: Optional[torch.Tensor] = None):
-        """Fused wrapper-MSE + backward (gnnLightning.py:633-639 + autograd): returns (loss[1], grad_flat)."""
+    def _backward_loss(self, name: str, xs, params_flat, out, target, B: int, grad_flat, loss, refuse: Optional[str]):
+        """`backward_mse` / `backward_ce` behind their own check of `out` and the target (`refuse`: its ValueError message when it failed): returns (loss[1], grad_flat)."""
         self._check_rows_fresh(xs, B)
         self._check_flat(params_flat, "params_flat")
         ptrs, pitch = self._xptrs(xs, B)
-        n = B * self.n_out * self.spec.out_channels
-        if out.dtype != torch.float32 or y.dtype != torch.float32 or out.numel() != n or y.numel() != n:
-            raise ValueError("out and y must be fp32 with B*n_out*out_channels elements")
-        if grad_flat is None:
-            grad_flat = torch.empty(self.spec.flat_size(), dtype=torch.float32, device=self.device)
-        if loss is None:
-            loss = torch.empty(1, dtype=torch.float32, device=self.device)
+        if refuse:
+            raise ValueError(refuse)
+        _, grad_flat, loss = self._results(B, out, grad_flat, loss)
         ws = self.workspace(B, True)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.mshgnn_backward_mse(self._plan, ptrs, pitch, params_flat.data_ptr(), out.data_ptr(), y.data_ptr(),
-                                                      loss.data_ptr(), grad_flat.data_ptr(), ws.data_ptr(), B, stream), "mshgnn_backward_mse")
+        self._call(name, None, B, ptrs, pitch, params_flat.data_ptr(), out.data_ptr(), target.data_ptr(), loss.data_ptr(), grad_flat.data_ptr(), ws.data_ptr(), B)
         self._bwd_ticket[B] = self._tickets.get(B, 0)
         return loss, grad_flat
+
+    def backward_mse(self, xs: Sequence[torch.Tensor], params_flat: torch.Tensor, out: torch.Tensor, y: torch.Tensor, B: int,
+                     grad_flat: Optional[torch.Tensor] = None, loss: Optional[torch.Tensor] = None):
+        """Fused wrapper-MSE + backward (gnnLightning.py:633-639 + autograd): returns (loss[1], grad_flat)."""
+        n = B * self.n_out * self.spec.out_channels
+        bad = out.dtype != torch.float32 or y.dtype != torch.float32 or out.numel() != n or y.numel() != n
+        return self._backward_loss("mshgnn_backward_mse", xs, params_flat, out, y, B, grad_flat, loss,
+                                   "out and y must be fp32 with B*n_out*out_channels elements" if bad else None)
+
+    def _step(self, name: str, xs, params_flat, target, B: int, out, grad_flat, loss, refuse: Optional[str]):
+        """`step_mse` / `step_ce` behind their own check of the target (`refuse`: its ValueError message when it failed): returns (out, loss[1], grad_flat)."""
+        xs = self._rewrap(xs)
+        self._check_rows_fresh(xs, B)
+        self._check_flat(params_flat, "params_flat")
+        ptrs, pitch = self._xptrs(xs, B)
+        if refuse:
+            raise ValueError(refuse)
+        out, grad_flat, loss = self._results(B, out, grad_flat, loss)
+        ws = self.workspace(B, True)
+        self._tickets[B] = self._tickets.get(B, 0) + 1; self._chunked[B] = True      # the activation stash of this batch size is overwritten
+        self._call(name, xs, B, ptrs, pitch, params_flat.data_ptr(), target.data_ptr(), out.data_ptr(), loss.data_ptr(), grad_flat.data_ptr(), ws.data_ptr(), B)
+        return out, loss, grad_flat
 
     def step_mse(self, xs: Sequence[torch.Tensor], params_flat: torch.Tensor, y: torch.Tensor, B: int, out: Optional[torch.Tensor] = None,
                  grad_flat: Optional[torch.Tensor] = None, loss: Optional[torch.Tensor] = None):
         """One training step of the regression wrappers in one call (forward + MSE + backward, mshgnn_step_mse):
         returns (out, loss[1], grad_flat)."""
-        xs = self._rewrap(xs)
-        self._check_rows_fresh(xs, B)
-        self._check_flat(params_flat, "params_flat")
-        ptrs, pitch = self._xptrs(xs, B)
-        n = B * self.n_out * self.spec.out_channels
-        if y.dtype != torch.float32 or y.numel() != n or not y.is_contiguous():
-            raise ValueError("y must be contiguous fp32 with B*n_out*out_channels elements")
-        if out is None:
-            out = torch.empty(B * self.n_out, self.spec.out_channels, dtype=torch.float32, device=self.device)
-        if grad_flat is None:
-            grad_flat = torch.empty(self.spec.flat_size(), dtype=torch.float32, device=self.device)
-        if loss is None:
-            loss = torch.empty(1, dtype=torch.float32, device=self.device)
-        ws = self.workspace(B, True)
-        self._tickets[B] = self._tickets.get(B, 0) + 1; self._chunked[B] = True      # the activation stash of this batch size is overwritten
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        with torch.cuda.device(self.device):
-            if isinstance(xs, WideInputs) and xs.pending:
-                self._rows_written(xs, B)
-                sb, sp, spitch = self._src_args(xs)
-                _check(self.lib, self.lib.mshgnn_step_mse_src(self._plan, sb, sp, spitch, ptrs, pitch, params_flat.data_ptr(), y.data_ptr(), out.data_ptr(),
-                                                              loss.data_ptr(), grad_flat.data_ptr(), ws.data_ptr(), B, stream), "mshgnn_step_mse_src")
-                xs.pending = False
-            else:
-                _check(self.lib, self.lib.mshgnn_step_mse(self._plan, ptrs, pitch, params_flat.data_ptr(), y.data_ptr(), out.data_ptr(), loss.data_ptr(),
-                                                          grad_flat.data_ptr(), ws.data_ptr(), B, stream), "mshgnn_step_mse")
-        return out, loss, grad_flat
+        bad = y.dtype != torch.float32 or y.numel() != B * self.n_out * self.spec.out_channels or not y.is_contiguous()
+        return self._step("mshgnn_step_mse", xs, params_flat, y, B, out, grad_flat, loss,
+                          "y must be contiguous fp32 with B*n_out*out_channels elements" if bad else None)
 
     def step_ce(self, xs: Sequence[torch.Tensor], params_flat: torch.Tensor, labels: torch.Tensor, B: int, out: Optional[torch.Tensor] = None,
                 grad_flat: Optional[torch.Tensor] = None, loss: Optional[torch.Tensor] = None):
         """One training step of the classification wrappers in one call (forward + cross entropy + backward, mshgnn_step_ce):
         returns (out, loss[1], grad_flat).  labels: int32 [B, n_out] in {0, 1}."""
-        xs = self._rewrap(xs)
-        self._check_rows_fresh(xs, B)
-        self._check_flat(params_flat, "params_flat")
-        ptrs, pitch = self._xptrs(xs, B)
-        if labels.dtype != torch.int32 or labels.numel() != B * self.n_out or not labels.is_contiguous():
-            raise ValueError("labels must be contiguous int32 with B*n_out elements")
-        if out is None:
-            out = torch.empty(B * self.n_out, self.spec.out_channels, dtype=torch.float32, device=self.device)
-        if grad_flat is None:
-            grad_flat = torch.empty(self.spec.flat_size(), dtype=torch.float32, device=self.device)
-        if loss is None:
-            loss = torch.empty(1, dtype=torch.float32, device=self.device)
-        ws = self.workspace(B, True)
-        self._tickets[B] = self._tickets.get(B, 0) + 1; self._chunked[B] = True
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        with torch.cuda.device(self.device):
-            if isinstance(xs, WideInputs) and xs.pending:
-                self._rows_written(xs, B)
-                sb, sp, spitch = self._src_args(xs)
-                _check(self.lib, self.lib.mshgnn_step_ce_src(self._plan, sb, sp, spitch, ptrs, pitch, params_flat.data_ptr(), labels.data_ptr(), out.data_ptr(),
-                                                             loss.data_ptr(), grad_flat.data_ptr(), ws.data_ptr(), B, stream), "mshgnn_step_ce_src")
-                xs.pending = False
-            else:
-                _check(self.lib, self.lib.mshgnn_step_ce(self._plan, ptrs, pitch, params_flat.data_ptr(), labels.data_ptr(), out.data_ptr(), loss.data_ptr(),
-                                                         grad_flat.data_ptr(), ws.data_ptr(), B, stream), "mshgnn_step_ce")
-        return out, loss, grad_flat
+        bad = labels.dtype != torch.int32 or labels.numel() != B * self.n_out or not labels.is_contiguous()
+        return self._step("mshgnn_step_ce", xs, params_flat, labels, B, out, grad_flat, loss,
+                          "labels must be contiguous int32 with B*n_out elements" if bad else None)
 
     def step_ce_series(self, store, starts: torch.Tensor, params_flat: torch.Tensor, out: Optional[torch.Tensor] = None,
                        grad_flat: Optional[torch.Tensor] = None, loss: Optional[torch.Tensor] = None, materialize: bool = True):
@@ -726,12 +703,7 @@ class Engine:
         xs, y, q = store._buffers(B)
         if y is None:
             raise ValueError("the recipe has no labels")
-        if out is None:
-            out = torch.empty(B * self.n_out, self.spec.out_channels, dtype=torch.float32, device=self.device)
-        if grad_flat is None:
-            grad_flat = torch.empty(self.spec.flat_size(), dtype=torch.float32, device=self.device)
-        if loss is None:
-            loss = torch.empty(1, dtype=torch.float32, device=self.device)
+        out, grad_flat, loss = self._results(B, out, grad_flat, loss)
         src16, run_ptrs = store.series_step_args(bf16=self.storage != "x3")
         if self.storage == "x3" and not materialize:
             raise ValueError("the split plan's weight-gradient kernel reads materialised windows: materialize=False is a bf16-plan option")
@@ -806,31 +778,16 @@ class Engine:
         ws = self.workspace(B, True)
         if phase == 0:
             self._tickets[B] = self._tickets.get(B, 0) + 1
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.mshgnn_step_mse_phase(self._plan, ptrs, pitch, params_flat.data_ptr(), y.data_ptr(), out.data_ptr(),
-                                                        loss.data_ptr(), grad_flat.data_ptr(), ws.data_ptr(), B, phase, stream), "mshgnn_step_mse_phase")
+        self._call("mshgnn_step_mse_phase", None, B, ptrs, pitch, params_flat.data_ptr(), y.data_ptr(), out.data_ptr(), loss.data_ptr(), grad_flat.data_ptr(),
+                   ws.data_ptr(), B, phase)
 
     def backward_ce(self, xs: Sequence[torch.Tensor], params_flat: torch.Tensor, out: torch.Tensor, labels: torch.Tensor, B: int,
                     grad_flat: Optional[torch.Tensor] = None, loss: Optional[torch.Tensor] = None):
         """Fused wrapper cross entropy + backward (gnnLightning.py:640-648 + autograd): labels int32 [B, n_out] in {0,1};
         returns (loss[1], grad_flat)."""
-        self._check_rows_fresh(xs, B)
-        self._check_flat(params_flat, "params_flat")
-        ptrs, pitch = self._xptrs(xs, B)
-        if out.dtype != torch.float32 or out.numel() != B * self.n_out * 2 or labels.dtype != torch.int32 or labels.numel() != B * self.n_out:
-            raise ValueError("out must be fp32 [B*n_out, 2] and labels int32 [B, n_out]")
-        if grad_flat is None:
-            grad_flat = torch.empty(self.spec.flat_size(), dtype=torch.float32, device=self.device)
-        if loss is None:
-            loss = torch.empty(1, dtype=torch.float32, device=self.device)
-        ws = self.workspace(B, True)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.mshgnn_backward_ce(self._plan, ptrs, pitch, params_flat.data_ptr(), out.data_ptr(), labels.data_ptr(),
-                                                     loss.data_ptr(), grad_flat.data_ptr(), ws.data_ptr(), B, stream), "mshgnn_backward_ce")
-        self._bwd_ticket[B] = self._tickets.get(B, 0)
-        return loss, grad_flat
+        bad = out.dtype != torch.float32 or out.numel() != B * self.n_out * 2 or labels.dtype != torch.int32 or labels.numel() != B * self.n_out
+        return self._backward_loss("mshgnn_backward_ce", xs, params_flat, out, labels, B, grad_flat, loss,
+                                   "out must be fp32 [B*n_out, 2] and labels int32 [B, n_out]" if bad else None)
 
     def adam_step(self, params_flat: torch.Tensor, grad_flat: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor,
                   step: int, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, grad_scale: float = 1.0):

@@ -153,3 +153,91 @@ def test_comm_entry_points_reject_bad_arguments_without_touching_rccl():
     assert lib.mshgnn_comm_unique_id(None, None) == -1
     assert lib.mshgnn_comm_allreduce_mean(None, None, 4, None) == -1
     lib.mshgnn_comm_destroy(None)      # a null communicator is a no-op
+
+
+def _header_prototypes():
+    """{name: [class of every parameter]} for every function include/mshgnn.h declares; class = "ptr", "i64" (int64_t / size_t), "int" or "float"."""
+    hdr = open(os.path.join(ROOT, "include", "mshgnn.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
+    hdr = re.sub(r"//[^\n]*", " ", hdr)
+    protos = {}
+    for name, args in re.findall(r"\b(mshgnn_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", hdr):
+        classes = []
+        for a in [a.strip() for a in args.split(",")]:
+            if a == "void" or not a:
+                continue
+            if "*" in a:
+                classes.append("ptr")
+            elif re.match(r"(const\s+)?(int64_t|size_t|uint64_t)\b", a):
+                classes.append("i64")
+            elif re.match(r"(const\s+)?(int|int32_t)\b", a):
+                classes.append("int")
+            elif re.match(r"(const\s+)?float\b", a):
+                classes.append("float")
+            else:
+                raise AssertionError(f"{name}: parameter '{a}' is of a class this test does not know")
+        protos[name] = classes
+    return protos
+
+
+def test_argtypes_match_the_header_prototypes():
+    """load_library()'s hand-written argtypes against include/mshgnn.h: for every function that has argtypes, the parameter count and per parameter the
+    class (pointer / 64-bit integer / int / float).  A pointer bound as an int, or a missing parameter, would pass garbage silently."""
+    import ctypes as C
+    lib = engine.load_library()
+    protos = _header_prototypes()
+    assert len(protos) >= len(engine.EXPORTS) - 2, sorted(protos)
+
+    def cls(t):
+        if t in (C.c_void_p, C.c_char_p) or issubclass(t, C._Pointer):
+            return "ptr"
+        if t in (C.c_int64, C.c_uint64, C.c_size_t):      # (c_size_t is c_uint64 here; c_long is c_int64 on LP64)
+            return "i64"
+        if t in (C.c_int, C.c_int32):
+            return "int"
+        if t is C.c_float:
+            return "float"
+        raise AssertionError(f"argtype {t} is of a class this test does not know")
+
+    checked = 0
+    for name, want in sorted(protos.items()):
+        argtypes = getattr(getattr(lib, name), "argtypes", None)
+        if argtypes is None:
+            continue
+        got = [cls(t) for t in argtypes]
+        assert len(got) == len(want), f"{name}: {len(got)} argtypes, {len(want)} parameters in the header"
+        assert got == want, f"{name}: argtypes {got} != header {want}"
+        checked += 1
+    assert checked >= 40, checked      # (the table binds nearly every export: a parser that silently matched nothing must not pass)
+
+
+def test_hot_path_entry_points_name_themselves_on_a_null_plan():
+    """Every forward / backward / step entry point called with a null plan (and nothing else) returns MSHGNN_EINVAL and names itself in mshgnn_last_error().
+    The strings are the library's before the entry points were moved onto one call descriptor: the route through the shared checks must not rename anyone.
+    (The _src entry points look at x_rows first, the classification series step at labels_out: given here, so that the null plan is what they meet.)"""
+    import ctypes as C
+    lib = engine.load_library()
+    some = (C.c_void_p * 4)()      # a non-null pointer argument; never dereferenced behind a null plan
+    n = None
+    cases = [
+        ("mshgnn_forward", (n, n, n, n, n, n, 1, 1, n), "null argument to mshgnn_forward"),
+        ("mshgnn_backward", (n, n, n, n, n, n, n, 1, n), "null argument to mshgnn_backward"),
+        ("mshgnn_backward_mse", (n, n, n, n, n, n, n, n, n, 1, n), "null argument to mshgnn_backward_mse"),
+        ("mshgnn_backward_ce", (n, n, n, n, n, n, n, n, n, 1, n), "null argument to mshgnn_backward_ce"),
+        ("mshgnn_step_mse", (n, n, n, n, n, n, n, n, n, 1, n), "null argument to mshgnn_step_mse"),
+        ("mshgnn_step_ce", (n, n, n, n, n, n, n, n, n, 1, n), "null argument to mshgnn_step_ce"),
+        ("mshgnn_step_mse_phase", (n, n, n, n, n, n, n, n, n, 1, 0, n), "null argument to mshgnn_step_mse_phase"),
+        ("mshgnn_forward_src", (n, 8, n, n, some, n, n, n, n, 1, 1, n), "null argument to mshgnn_forward_src"),
+        ("mshgnn_step_mse_src", (n, 8, n, n, some, n, n, n, n, n, n, n, 1, n), "null argument to mshgnn_step_mse_src"),
+        ("mshgnn_step_ce_src", (n, 8, n, n, some, n, n, n, n, n, n, n, 1, n), "null argument to mshgnn_step_ce_src"),
+        ("mshgnn_step_mse_series", (n, n, n, n, n, n, n, 1, n, n, n, n, n, n, n, n, n, n, n), "null argument to mshgnn_step_mse_series / mshgnn_step_ce_series"),
+        ("mshgnn_step_ce_series", (n, n, n, n, n, n, n, 1, n, n, n, some, n, n, n, n, n, n, n), "null argument to mshgnn_step_mse_series / mshgnn_step_ce_series"),
+        ("mshgnn_step_ce_series", (n, n, n, n, n, n, n, 1, n, n, n, n, n, n, n, n, n, n, n), "null argument to mshgnn_step_ce_series"),
+        ("mshgnn_forward_series", (n, n, n, n, n, n, n, 1, n, n, n, n, n, n, n, n, n), "null argument to mshgnn_forward_series"),
+        ("mshgnn_forward_src", (n, 8, n, n, n, n, n, n, n, 1, 1, n), "mshgnn_forward_src: x_rows is null (the plan-dtype rows the encoder materialises)"),
+        ("mshgnn_step_mse_src", (n, 8, n, n, n, n, n, n, n, n, n, n, 1, n), "mshgnn_step_mse_src: x_rows is null (the plan-dtype rows the encoder materialises)"),
+        ("mshgnn_step_ce_src", (n, 8, n, n, n, n, n, n, n, n, n, n, 1, n), "mshgnn_step_ce_src: x_rows is null (the plan-dtype rows the encoder materialises)"),
+    ]
+    for name, args, text in cases:
+        assert getattr(lib, name)(*args) == -1, name
+        assert lib.mshgnn_last_error().decode() == text, (name, lib.mshgnn_last_error())
