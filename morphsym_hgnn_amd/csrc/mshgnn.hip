@@ -12,12 +12,13 @@
 //     engine on the transposed graph with transposed weight images; weight gradients are one split-K MFMA launch
 //     over all layers with deterministic slab reduction (no float atomics).
 //
+// This file, top to bottom: (1) the kernels of the fp32 / bf16 plans -- prep, encoder, per-layer, 8-wave stack, the slab interpreters (the slab templates
+// themselves: mshgnn_slab.hpp), decoder, weight gradient, finalize; (2) kernel selection; (3) plan lifecycle; (4) forward_impl / backward_impl; (5) the dispatch
+// over plans and chunks; (6) the entry points, the series routes last.  Elsewhere: the split plan (mshgnn_x3.hip), the generic-width engine (mshgnn_gen.hip),
+// the compile-time programs' kernels (mshgnn_spec_shard.hip), the plan-independent entry points (mshgnn_train_ops.hip) and window assembly (mshgnn_windows.hip).
+//
 // No CPU fallback exists: every entry point launches HIP kernels or fails loudly.
-#include "mshgnn_device.hpp"
-#ifndef MSHGNN_SPEC_SHARD
-#define MSHGNN_SPEC_SHARD 0      // 1..7: this source compiled as one of the translation units that only instantiate the compile-time programs' kernels (csrc/Makefile; see spec_shard1 below)
-#endif
-#if MSHGNN_SPEC_SHARD == 0
+#include "mshgnn_slab.hpp"
 extern "C" const char* mshgnn_last_error(void) { return g_err.c_str(); }
 extern "C" const char* mshgnn_version(void) { return "mshgnn 0.5 (gfx950)"; }
 extern "C" int mshgnn_abi_version(void) { return MSHGNN_ABI_VERSION; }
@@ -31,7 +32,6 @@ extern "C" size_t mshgnn_struct_size(int which) {
         default: return 0;
     }
 }
-#endif
 
 // ------------------------------------------------------------------------------------------------------
 // k_prep: pack weights into MFMA B-fragment images (root-sum, transpose, dtype) and sum biases
@@ -849,294 +849,6 @@ template <typename T> __global__ __launch_bounds__(LAYER_THREADS, 2) void k_stac
     stack_fwd_body<T, false>(a, smem);
 }
 
-// ------------------------------------------------------------------------------------------------------
-// Slab variant of the forward stack kernel: 4 waves per workgroup, two workgroups per CU.  Wave wn owns columns
-// [32 wn, 32 wn + 32) of EVERY node, so each weight pack is pulled through the CU's vector L1 once per tile (the 8-wave
-// kernel pulls it once per wave half, and its MAC phase is bound by that path), and the second workgroup's epilogues run
-// under this one's MAC phases.  The destination nodes are processed in two groups (mshgnn_plan.hpp, SL_HA / SL_HB) so that
-// the accumulators stay in registers; group A's new activations wait, packed, while group B is multiplied.
-// ------------------------------------------------------------------------------------------------------
-template <typename T, int HS, int Q0, int NM = 4, bool PRE = false, class A = StackArgs, class FH = FHdr, class FP = FProg>     // one group: slots q = Q0 + u of the slab header; NM: compile-time bound on the base_transform nodes; PRE: (*pre) = the run's first two weight fragments, already requested
-__device__ __forceinline__ void slab_group_fwd(const A& a, const FH& fh, const FP& wp, char* smem, const T* wpack, int wn, int lane,
-                                               int slot_base, int nmlp, bool residual, u32x4 (&keep)[HS], unsigned (&bits)[(HS + 3) / 4], typename Prec<T>::BFrag (*pre)[2] = nullptr) {
-    using P = Prec<T>;
-    const int win = c_win(lane), col = wn * 32 + c_oct(lane);
-    if (fh[FH_FLAGS] & (Q0 == 0 ? FF_A_EMPTY : FF_B_EMPTY)) {      // no live node in this group in this layer (uniform): nothing to compute or keep
-#pragma unroll
-        for (int u = 0; u < HS; ++u) keep[u] = u32x4{0, 0, 0, 0};
-#pragma unroll
-        for (int i = 0; i < (HS + 3) / 4; ++i) bits[i] = 0;
-        return;
-    }
-    typename P::Acc acc[HS];
-    const unsigned boff = (unsigned)c_oct(opaque(lane)) * 4u;      // (compile-time programs) this lane's 8 floats in a wave's 32-float slice of a bias row
-#pragma unroll
-    for (int u = 0; u < HS; ++u) {
-        if (fh[FH_KIND + Q0 + u] != NK_DEAD) {
-            if constexpr (FH::is_static) acc_init_bias_u<T>(acc[u], a.bias + (size_t)fh[FH_BIAS + Q0 + u] * H, wn, boff);
-            else acc_init_bias<T>(acc[u], a.bias + (size_t)fh[FH_BIAS + Q0 + u] * H, wn, lane);
-        } else acc_fill(acc[u], 0.f);
-    }
-    if constexpr (PRE) fs_run_static<T, HS, (Q0 == 0 ? SL_CBA : SL_CBB), FP, true>(acc, smem, wpack, wn, lane, *pre);
-    else fs_run<T, HS, (Q0 == 0 ? SL_CBA : SL_CBB)>(wp, acc, smem, wpack, wn, lane, a.dbg);      // (a.dbg: timing ablations, compiled out of the product build)
-    if constexpr (Q0 > 0) if (nmlp > 0) {
-        // base_transform: Y = W2 relu(W1 H + b1) + b2 on the first nmlp slots of this group (hgnn_c2.py:117-121,156); scratch
-        // blocks NN + u.  The H / T1 stashes go out packed, behind the chain's last load.
-        static_assert(sizeof(T) == 2, "fused stack kernels are bf16");
-        typename P::BFrag bf, bf2;
-        typename P::AFrag af;
-        u32x4 hpk[NM], tpk[NM];
-        // scratch blocks: behind the tile, or (FF_SCR_ALIAS) the blocks of the first group-A nodes -- every wave must then be done with ALL
-        // its MACs (and group A's residual reads) before H lands in them
-        const bool alias = (fh[FH_FLAGS] & FF_SCR_ALIAS) != 0;
-        int scr[NM];
-#pragma unroll
-        for (int u = 0; u < NM; ++u) scr[u] = alias ? fh[FH_SLOTA + u] : a.NN + u;
-        if (alias) __syncthreads();
-        load_bfrag<T>(bf, wpack, fh[FH_W1], wn, lane);
-        load_bfrag<T>(bf2, wpack, fh[FH_W2], wn, lane);
-#pragma unroll
-        for (int u = 0; u < NM && u < HS; ++u) {
-            if (u < nmlp) {
-                hpk[u] = pack_oct(acc[u].c[0], acc[u].c[1]);
-                *reinterpret_cast<u32x4*>(smem + lds_chunk<T>(scr[u], win, col / P::EPC)) = hpk[u];
-                acc_init_bias<T>(acc[u], a.bias + (size_t)fh[FH_B1] * H, wn, lane);
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < NM && u < HS; ++u) {
-            if (u < nmlp) { load_afrag<T>(af, smem, scr[u], lane); mac(acc[u], af, bf); }
-        }
-        __syncthreads();   // all reads of H done before T1 overwrites the scratch blocks
-#pragma unroll
-        for (int u = 0; u < NM && u < HS; ++u) {
-            if (u < nmlp) {
-                tpk[u] = pack_oct(relu4(acc[u].c[0]), relu4(acc[u].c[1]));
-                *reinterpret_cast<u32x4*>(smem + lds_chunk<T>(scr[u], win, col / P::EPC)) = tpk[u];
-                acc_init_bias<T>(acc[u], a.bias + (size_t)fh[FH_B2] * H, wn, lane);
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < NM && u < HS; ++u) {
-            if (u < nmlp) { load_afrag<T>(af, smem, scr[u], lane); mac(acc[u], af, bf2); }
-        }
-        __builtin_amdgcn_s_waitcnt((7 << 4) | (15 << 8));      // every load has landed before the first store
-        if (a.training) {
-            const int w = blockIdx.x * P::ROWS + win;
-            if (A::full || w < a.B) {
-                T* hb = reinterpret_cast<T*>(a.ws + a.hb_off[slot_base >> 8]);
-                T* t1 = reinterpret_cast<T*>(a.ws + a.t1_off[slot_base >> 8]);
-                const unsigned roff = (unsigned)((w * H + col) * (int)sizeof(T));
-#pragma unroll
-                for (int u = 0; u < NM && u < HS; ++u) {
-                    if (u < nmlp) {
-                        if constexpr (FH::is_static) {
-                            gstore16(uniform_wptr(reinterpret_cast<char*>(hb + act_idx(0, u, a.B))), roff, hpk[u]);
-                            gstore16(uniform_wptr(reinterpret_cast<char*>(t1 + act_idx(0, u, a.B))), roff, tpk[u]);
-                        } else {
-                            *reinterpret_cast<u32x4*>(hb + act_idx(w, u, a.B) + col) = hpk[u];
-                            *reinterpret_cast<u32x4*>(t1 + act_idx(w, u, a.B) + col) = tpk[u];
-                        }
-                    }
-                }
-            }
-        }
-    }
-    // X_{l+1}[n] = f(H[n]) (+ X_l[n]), kept packed in registers (X_l is still being read by the other waves)
-#pragma unroll
-    for (int i = 0; i < (HS + 3) / 4; ++i) bits[i] = 0;
-#pragma unroll
-    for (int u = 0; u < HS; ++u) {
-        keep[u] = u32x4{0, 0, 0, 0};
-        const int kind = fh[FH_KIND + Q0 + u];
-        if (kind != NK_DEAD) {
-            const int n = fh[(slot_base & 255) + u];
-            if (kind == NK_RELU) bits[u >> 2] |= relu_with_bits<T>(acc[u]) << (8 * (u & 3));
-            f32x4 y0 = acc[u].c[0], y1 = acc[u].c[1];
-            if (residual) {
-                const u32x4 r = *reinterpret_cast<const u32x4*>(smem + lds_chunk<T>(n, win, col / P::EPC));
-                f32x4 r0, r1; unpack_oct(r, r0, r1);
-                y0 += r0; y1 += r1;
-            }
-            keep[u] = pack_oct(y0, y1);
-            pad_valu();
-        }
-    }
-}
-// write one group's new activations: LDS block, stash, relu bytes
-template <typename T, int HS, int Q0, class A = StackArgs, class FH = FHdr>
-__device__ __forceinline__ void slab_group_store(const A& a, const FH& fh, char* smem, int wn, int lane, int slot_arr, int l,
-                                                 const u32x4 (&keep)[HS], const unsigned (&bits)[(HS + 3) / 4], bool stash_x = true) {
-    using P = Prec<T>;
-    const int win = c_win(lane), col = wn * 32 + c_oct(lane), w = blockIdx.x * P::ROWS + win;
-    T* xo = reinterpret_cast<T*>(a.ws + a.x_off[l + 1]);
-    uint8_t* maskbytes = reinterpret_cast<uint8_t*>(a.ws + a.mask_off[l]);
-    if constexpr (FH::is_static) {
-        // compile-time program: the LDS rows and relu bytes of every live slot first, then all stash rows under ONE lane predicate (one exec switch per group
-        // instead of a compare + branch per node)
-        // every global address = a scalar base (layer, node) + this lane's 32-bit offset, rebuilt from an opaque copy of the lane id per call: per-node 64-bit
-        // addresses would be shared between the unrolled layers and live (two registers per node) through the whole kernel
-        const int lq = opaque(lane);
-        const unsigned roff = (unsigned)(((blockIdx.x * P::ROWS + c_win(lq)) * H + wn * 32 + c_oct(lq)) * (int)sizeof(T));      // this lane's octet in a [B][128] row block
-#pragma unroll
-        for (int u = 0; u < HS; ++u) {
-            const int kind = fh[FH_KIND + Q0 + u];
-            if (kind != NK_DEAD) {
-                const int n = fh[slot_arr + u];
-                *reinterpret_cast<u32x4*>(smem + lds_chunk<T>(n, win, col / P::EPC)) = keep[u];
-                if (a.training && kind == NK_RELU) gstore1(uniform_wptr(reinterpret_cast<char*>(maskbytes) + relu_tile_base(n, a.B, blockIdx.x, wn)), (unsigned)lq, bits[u >> 2] >> (8 * (u & 3)));
-            }
-        }
-        if (a.training && stash_x && (A::full || w < a.B)) {
-#ifdef MSHGNN_STASH_ALIAS      // timing experiment (wrong results): every tile's stash rows land on the rows of 32 tiles, a footprint the L2 holds -- is the store phase bound by HBM writes?
-            const unsigned soff = (unsigned)((((blockIdx.x & 31) * P::ROWS + c_win(lq)) * H + wn * 32 + c_oct(lq)) * (int)sizeof(T));
-#else
-            const unsigned soff = roff;
-#endif
-#pragma unroll
-            for (int u = 0; u < HS; ++u)
-                if (fh[FH_KIND + Q0 + u] != NK_DEAD) stash_store_u(a, uniform_wptr(reinterpret_cast<char*>(xo + act_idx(0, fh[slot_arr + u], a.B))), soff, keep[u]);
-        }
-        return;
-    }
-#pragma unroll
-    for (int u = 0; u < HS; ++u) {
-        const int kind = fh[FH_KIND + Q0 + u];
-        if (kind != NK_DEAD) {
-            const int n = fh[slot_arr + u];
-            *reinterpret_cast<u32x4*>(smem + lds_chunk<T>(n, win, col / P::EPC)) = keep[u];
-            if (a.training) {
-                if (kind == NK_RELU) maskbytes[relu_tile_base(n, a.B, blockIdx.x, wn) + lane] = (uint8_t)(bits[u >> 2] >> (8 * (u & 3)));
-                if (w < a.B && stash_x) stash_store(xo + act_idx(w, n, a.B) + col, keep[u], a.stash_nt != 0);
-            }
-        }
-    }
-}
-
-// one forward layer of a slab workgroup: both groups' MAC passes, then the layer's stores.  FH / FP: the layer's header and wave programs, interpreted (FHdr /
-// FProg: plan tables in VGPRs) or compile-time (SHdr / SProg: specialised kernels); mid(): what has to settle between the MACs and the stores
-// PRE (compile-time programs): (*pre) holds the first two weight fragments of the layer's first pass, requested before the previous store phase; bits_out: the
-// layer's relu bits (12 + HB bytes in 3 + 2 registers) for the backward sweep of the same launch
-template <typename T, int NM, int HB, bool STEP, bool PRE = false, class A, class FH, class FP, class FPB, class Mid>
-__device__ __forceinline__ void slab_fwd_layer(const A& a, char* smem, const T* wpack, int wn, int lane, int l, int L, const FH& fh, const FP& wa, const FPB& wb, Mid&& mid,
-                                               typename Prec<T>::BFrag (*pre)[2] = nullptr, unsigned* bits_out = nullptr) {
-    const int tid = threadIdx.x;
-    const int nmlp = fh[FH_NMLP];
-    const bool residual = (fh[FH_FLAGS] & FF_RESIDUAL) != 0;
-    u32x4 keepA[SL_HA], keepB[HB]; unsigned bitsA[(SL_HA + 3) / 4], bitsB[(HB + 3) / 4];
-    if constexpr (PRE) {      // the requested fragments belong to the first group with work
-        constexpr bool a_first = !(FH{}[FH_FLAGS] & FF_A_EMPTY);
-        slab_group_fwd<T, SL_HA, 0, 4, a_first>(a, fh, wa, smem, wpack, wn, lane, FH_SLOTA | (l << 8), 0, residual, keepA, bitsA, pre);
-        FS_STAMP(2 + 4 * l);
-        slab_group_fwd<T, HB, SL_HA, NM, !a_first>(a, fh, wb, smem, wpack, wn, lane, FH_SLOTB | (l << 8), nmlp, residual, keepB, bitsB, pre);
-    } else {
-        slab_group_fwd<T, SL_HA, 0>(a, fh, wa, smem, wpack, wn, lane, FH_SLOTA | (l << 8), 0, residual, keepA, bitsA);
-        FS_STAMP(2 + 4 * l);
-        slab_group_fwd<T, HB, SL_HA, NM>(a, fh, wb, smem, wpack, wn, lane, FH_SLOTB | (l << 8), nmlp, residual, keepB, bitsB);
-    }
-    if (bits_out) {
-#pragma unroll
-        for (int i = 0; i < (SL_HA + 3) / 4; ++i) bits_out[i] = bitsA[i];
-#pragma unroll
-        for (int i = 0; i < (HB + 3) / 4; ++i) bits_out[(SL_HA + 3) / 4 + i] = bitsB[i];
-    }
-    FS_STAMP(3 + 4 * l);
-    __syncthreads();   // every wave is done reading X_l: the node blocks may be overwritten
-    FS_STAMP(4 + 4 * l);
-    mid();      // the next header / programs have landed before the stores go out (no drain at the top of the next layer)
-    const bool stash_x = !(STEP && l + 1 == L);      // X_L of a one-launch step is read by nobody (the decoder's gradients come from the tile in LDS)
-    slab_group_store<T, SL_HA, 0>(a, fh, smem, wn, lane, FH_SLOTA, l, keepA, bitsA, stash_x);
-    slab_group_store<T, HB, SL_HA>(a, fh, smem, wn, lane, FH_SLOTB, l, keepB, bitsB, stash_x);
-    __syncthreads();
-    FS_STAMP(5 + 4 * l);
-}
-// the layers of a compile-time program SP, unrolled
-// the first pass with work of forward (DIR 0) / backward (DIR 1) layer l of a compile-time program: request its first two weight fragments
-template <typename T, class SP, int DIR, int l> __device__ __forceinline__ void slab_prefetch_static(typename Prec<T>::BFrag (&pre)[2], const T* wpack, int wn, int lane) {
-    if constexpr (!(SHdr<SP, DIR, l>{}[FH_FLAGS] & FF_A_EMPTY)) fs_prefetch_static<T, SProg<SP, DIR, l, 0>>(pre, wpack, wn, lane);
-    else fs_prefetch_static<T, SProg<SP, DIR, l, 1>>(pre, wpack, wn, lane);
-}
-// Between a layer's MACs and its stores a compile-time program requests what the phase AFTER the stores starts with -- the next layer's first two weight
-// fragments, or (last layer) the decoder tail's operands -- so that phase begins under the store drain instead of behind it.
-template <typename T, int NM, int HB, bool STEP, class SP, int l = 0, class A>
-__device__ __forceinline__ void slab_fwd_layers_static(const A& a, char* smem, const T* wpack, int wn, int lane, typename Prec<T>::BFrag (&pre)[2],
-                                                       unsigned* lastbits, DecOps<SP::DMAX, DEC_NPP_STATIC>& dops) {
-    if constexpr (l < SP::L) {
-        auto mid = [&] {
-            if constexpr (l + 1 < SP::L) { if constexpr ((SP::PRE & 1) != 0) slab_prefetch_static<T, SP, 0, l + 1>(pre, wpack, wn, lane); }
-            else if constexpr ((SP::PRE & 4) != 0) decoder_ops_load<SL_THREADS, SP::DMAX, DEC_NPP_STATIC>(args_of(a), threadIdx.x, blockIdx.x * Prec<T>::ROWS, a.B, threadIdx.x >> 8, true, dops);
-        };
-        slab_fwd_layer<T, NM, HB, STEP, (SP::PRE & 1) != 0>(a, smem, wpack, wn, lane, l, SP::L, SHdr<SP, 0, l>{}, SProg<SP, 0, l, 0>{}, SProg<SP, 0, l, 1>{}, mid, &pre,
-                                                            l + 1 == SP::L ? lastbits : nullptr);
-        slab_fwd_layers_static<T, NM, HB, STEP, SP, l + 1>(a, smem, wpack, wn, lane, pre, lastbits, dops);
-    }
-}
-
-// STEP: part of k_slab_step -- the decoder tail leaves dX_L in the out-type nodes' LDS blocks for the backward sweep that follows in the same launch
-// SP: void = the plan's tables are interpreted; else the compile-time program of one (topology, depth) (mshgnn_spec_tables.inc)
-template <typename T, int NM, int HB, bool STEP, class SP = void, class A = StackArgs> __device__ __forceinline__ void slab_fwd_body(const A& a, char* smem, unsigned* lastbits = nullptr) {
-    using P = Prec<T>;
-    constexpr bool DYN = std::is_void<SP>::value;
-    const int tid = threadIdx.x, lane = tid & 63, wn = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int w0 = blockIdx.x * P::ROWS, B = a.B, NN = a.NN;
-    const T* wpack = reinterpret_cast<const T*>(a.wpack);
-    stack_stagger(a);
-    FS_STAMP(0);
-
-    // layer 0's header and programs stream in under the tile load
-    FHdr fhn; FProg wan, wbn;
-    typename P::BFrag pre[2];
-    if constexpr (DYN) {
-        fhn = FHdr(a.tables + a.prog_off[0], lane);
-        wan = FProg(a.tables + a.prog_off[0] + FH_SIZE, lane); wbn = FProg(a.tables + a.prog_off[0] + FH_SIZE + FPROG_LEN, lane);
-    } else if constexpr ((SP::PRE & 1) != 0) slab_prefetch_static<T, SP, 0, 0>(pre, wpack, wn, lane);      // layer 0's first weight fragments stream in under the tile load
-    {   // X_0 tile -> LDS: thread = (row, 16-byte chunk), one node per pass, 6 loads in flight
-        const T* src = reinterpret_cast<const T*>(a.tile_in);
-        const int row = tid >> 4, c = tid & 15;
-        constexpr int BATCH = 6;
-        for (int nb = 0; nb < NN; nb += BATCH) {
-            u32x4 v[BATCH];
-#pragma unroll
-            for (int i = 0; i < BATCH; ++i) {
-                v[i] = u32x4{0, 0, 0, 0};
-                // (read once by this kernel: non-temporal -- 0.2026 -> 0.2004 ms/step over six alternating runs at 3 layers, nothing at 8)
-                if (nb + i < NN && (A::full || w0 + row < B)) v[i] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(src + act_idx(w0 + row, nb + i, B) + c * P::EPC));
-            }
-#pragma unroll
-            for (int i = 0; i < BATCH; ++i)
-                if (nb + i < NN) *reinterpret_cast<u32x4*>(smem + lds_chunk<T>(nb + i, row, c)) = v[i];
-        }
-    }
-    __syncthreads();
-    FS_STAMP(1);
-
-    if constexpr (DYN) {
-        fhn.settle(); wan.settle(); wbn.settle();      // (waited for here, not by a vmcnt(0) at the top of every layer)
-        for (int l = 0; l < a.L; ++l) {
-            const FHdr fh = fhn;
-            const FProg wa = wan, wb = wbn;
-            if (l + 1 < a.L) {    // the next layer's header and wave programs stream in under this layer's MACs
-                fhn = FHdr(a.tables + a.prog_off[l + 1], lane);
-                wan = FProg(a.tables + a.prog_off[l + 1] + FH_SIZE, lane);
-                wbn = FProg(a.tables + a.prog_off[l + 1] + FH_SIZE + FPROG_LEN, lane);
-            }
-            slab_fwd_layer<T, NM, HB, STEP>(a, smem, wpack, wn, lane, l, a.L, fh, wa, wb, [&] { fhn.settle(); wan.settle(); wbn.settle(); });
-        }
-        decoder_tail<T, SL_THREADS, false, STEP>(args_of(a), smem, tid, lane, wn, w0, B);
-    } else {
-        DecOps<SP::DMAX, DEC_NPP_STATIC> dops;
-        slab_fwd_layers_static<T, NM, HB, STEP, SP>(a, smem, wpack, wn, lane, pre, lastbits, dops);
-        decoder_tail_impl<T, SL_THREADS, SP::DMAX, false, STEP, DEC_NPP_STATIC, (SP::PRE & 4) != 0>(args_of(a), smem, tid, lane, wn, w0, B, &dops);
-    }
-    FS_STAMP(30);
-}
-template <typename T, int NM, int HB> __global__ __launch_bounds__(SL_THREADS, 2) void k_slab_fwd(StackArgs a) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    slab_fwd_body<T, NM, HB, false>(a, smem);
-}
-
 // STEP: part of k_stack_step -- the forward's decoder tail of the same launch left the dX_L tile in LDS; the layers' programs are a.prog_off_b
 template <typename T, bool STEP> __device__ __forceinline__ void stack_bwd_body(const StackArgs& a, char* smem) {
     using P = Prec<T>;
@@ -1328,474 +1040,16 @@ template <typename T> __global__ __launch_bounds__(LAYER_THREADS, 2) void k_stac
 }
 
 // ------------------------------------------------------------------------------------------------------
-// Slab variant of the backward stack kernel (see k_slab_fwd): wave wn owns columns [32 wn, 32 wn + 32) of every node; the
-// nodes whose dX_l is produced are processed in two groups.  A group's accumulators start at the residual term, which is the
-// packed dX_{l+1} row this wave produced one layer earlier and kept in registers (for the last layer: the decoder
-// backward's dX_L, read once before the loop).
+// The slab stack kernels (mshgnn_slab.hpp: 4 waves per workgroup, two workgroups per CU) over the plan's run-time tables: the interpreters.
+// Those over the compile-time programs are mshgnn_spec_shard.hip's.
 // ------------------------------------------------------------------------------------------------------
-template <typename T, int HS, int Q0, bool PRE = false, class A = StackArgs, class FH = FHdr, class FP = FProg>
-__device__ __forceinline__ void slab_group_bwd(const A& a, const FH& bh, const FP& wp, char* smem, const T* wpack, int wn, int lane,
-                                               int slot_arr, const T* xact, bool enc_mask, u32x4 (&keep)[HS], typename Prec<T>::BFrag (*pre)[2] = nullptr) {
-    using P = Prec<T>;
-    if (bh[FH_FLAGS] & (Q0 == 0 ? FF_A_EMPTY : FF_B_EMPTY)) {      // no dX row of this group is produced in this layer (uniform)
-#pragma unroll
-        for (int u = 0; u < HS; ++u) keep[u] = u32x4{0, 0, 0, 0};
-        return;
-    }
-    const int lq = opaque(lane);      // per-node global addresses are rebuilt per call: hoisted out of the layer loop they cost ~40 VGPRs and spill
-    const int win = c_win(lq), col = wn * 32 + c_oct(lq), w = min(blockIdx.x * P::ROWS + win, a.B - 1);
-    // The accumulators start at the residual term G_{l+1}[n]: `keep` holds it on entry -- the packed dX_{l+1} rows this wave
-    // produced one layer earlier (or the decoder backward's dX_L), carried in registers from layer to layer.  (Re-reading them
-    // from the stash instead cost 12 us per launch: 70 MB of fabric traffic and an exposed latency per group.)
-    typename P::Acc acc[HS];
-#pragma unroll
-    for (int u = 0; u < HS; ++u) {
-        if (bh[FH_KIND + Q0 + u] != NK_DEAD && bh[FH_RES + Q0 + u]) unpack_oct(keep[u], acc[u].c[0], acc[u].c[1]);
-        else acc_fill(acc[u], 0.f);
-    }
-    if constexpr (PRE) fs_run_static<T, HS, (Q0 == 0 ? SL_CBA : SL_CBB), FP, true>(acc, smem, wpack, wn, lane, *pre);
-    else fs_run<T, HS, (Q0 == 0 ? SL_CBA : SL_CBB)>(wp, acc, smem, wpack, wn, lane, a.dbg);      // (a.dbg: timing ablations, compiled out of the product build)
-    // layer 0: x relu'(X_0) (encoder activation) from the encoder's relu bytes (one per lane, written by k_enc_fwd): a byte per
-    // node instead of the 16-byte X_0 octet (38 MB per launch, 4 VGPRs per node), all requested back to back
-    const uint8_t* m0 = reinterpret_cast<const uint8_t*>(a.ws + a.mask0_off);
-    unsigned xb[HS];
-    if (enc_mask) {
-#pragma unroll
-        for (int u = 0; u < HS; ++u) {
-            xb[u] = 0;
-            if (bh[FH_OUT + Q0 + u]) {
-                if constexpr (FH::is_static) xb[u] = gload1(uniform_ptr(reinterpret_cast<const char*>(m0) + relu_tile_base(bh[slot_arr + u], a.B, blockIdx.x, wn)), (unsigned)lq);
-                else xb[u] = m0[relu_tile_base(bh[slot_arr + u], a.B, blockIdx.x, wn) + lq];
-            }
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < HS; ++u) {
-        keep[u] = u32x4{0, 0, 0, 0};
-        if (bh[FH_OUT + Q0 + u]) {
-            const u32x4 pk = pack_oct(acc[u].c[0], acc[u].c[1]);
-            keep[u] = enc_mask ? chunk_mask_bits<T>(pk, xb[u]) : pk;
-            pad_valu();
-        }
-    }
-}
-
-// one backward layer of a slab workgroup (FH / FP / mid: see slab_fwd_layer); keepA / keepB carry the packed dX rows from layer to layer
-// PRE (compile-time programs): mbq holds this layer's relu bytes (requested before the previous store phase, or the forward's own bits for the last layer) and
-// (*pre) the first two weight fragments of the layer's first pass with work; mid() requests the same for the layer that follows
-template <typename T, int NM, int HB, bool PRE = false, bool PREM = false, class A, class FH, class FP, class FPB, class Mid>
-__device__ __forceinline__ void slab_bwd_layer(const A& a, char* smem, const T* wpack, int wn, int lane, int l, int li, const FH& bh, const FP& wa, const FPB& wb,
-                                               u32x4 (&keepA)[SL_HA], u32x4 (&keepB)[HB], Mid&& mid, unsigned* mbq = nullptr, typename Prec<T>::BFrag (*pre)[2] = nullptr) {
-    using P = Prec<T>;
-    const int tid = threadIdx.x, w0 = blockIdx.x * P::ROWS, B = a.B;
-    const int nmlp = bh[FH_NMLP], flags = bh[FH_FLAGS];
-    const uint8_t* maskbytes = reinterpret_cast<const uint8_t*>(a.ws + a.mask_off[l]);
-    // lane constants rebuilt per layer from an opaque copy of the lane id: the per-node global addresses derived from them
-    // would otherwise be hoisted out of the layer loop (dozens of VGPRs, spilled)
-    const int lq = opaque(lane);
-    const int win = c_win(lq), w = w0 + win, col = wn * 32 + c_oct(lq), wc = min(w, B - 1);
-    const bool w_ok = A::full || w < B;
-
-    // mask phase (each lane on the octets it owns): relu nodes are masked in place -> dH_l[n]; group A's accumulators start
-    // at the residual term G_{l+1}[n].  Every relu byte and every LDS read is issued before the first use.
-    {
-        // (the unmasked rows are the carried `keep` registers: the packed dX_{l+1} this wave wrote into the blocks itself)
-        unsigned mb[SL_HA + HB];
-#pragma unroll
-        for (int q = 0; q < SL_HA + HB; ++q) {
-            mb[q] = 0xffu;
-            if (bh[FH_KIND + q] == NK_RELU) {
-                if constexpr (PREM) mb[q] = mbq[q];
-                else if constexpr (FH::is_static) mb[q] = gload1(uniform_ptr(reinterpret_cast<const char*>(maskbytes) + relu_tile_base(bh[(q < SL_HA ? FH_SLOTA : FH_SLOTB - SL_HA) + q], B, blockIdx.x, wn)), (unsigned)lq);
-                else mb[q] = maskbytes[relu_tile_base(bh[(q < SL_HA ? FH_SLOTA : FH_SLOTB - SL_HA) + q], B, blockIdx.x, wn) + lane];
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < SL_HA + HB; ++q) {
-            if (bh[FH_KIND + q] == NK_RELU) {
-                const u32x4 raw = q < SL_HA ? keepA[q < SL_HA ? q : 0] : keepB[q < SL_HA ? 0 : q - SL_HA];
-                *reinterpret_cast<u32x4*>(smem + lds_chunk<T>(bh[(q < SL_HA ? FH_SLOTA : FH_SLOTB - SL_HA) + q], win, col / P::EPC)) = chunk_mask_bits<T>(raw, mb[q]);
-            }
-        }
-    }
-    __syncthreads();
-    FS_STAMP2(1 + 6 * li);
-
-    if (nmlp > 0) {
-        // dT1 = dY W2 ; dU = dT1 . (T1 > 0) ; dH = dU W1     (backward of base_transform, in place on nodes 0..nmlp-1 = the
-        // first slots of group B); the dU / dH stashes go out behind the chain's last load
-        const T* t1 = reinterpret_cast<const T*>(a.ws + a.t1_off[l]);
-        T* du = reinterpret_cast<T*>(a.ws + a.du_off[l]);
-        T* dh = reinterpret_cast<T*>(a.ws + a.dh_off[l]);
-        // Two nodes at a time (K4 has four base_transform nodes: all four at once need 16 accumulator + 16 staging registers the kernel does not have next
-        // to the carried residual rows; each pair pays its own three barriers -- the chain is a few hundred cycles, the spills were round trips)
-        typename P::BFrag bf;      // one buffer for both weights: a carried residual (72 VGPRs) lives through this chain
-        typename P::AFrag af;
-        for (int u0 = 0; u0 < NM; u0 += 2) {
-            if (u0 >= nmlp) break;      // (uniform)
-            typename P::Acc tm[2];
-            u32x4 traw[2], dupk[2];
-            load_bfrag<T>(bf, wpack, bh[FH_W2], wn, lane);
-#pragma unroll
-            for (int v = 0; v < 2; ++v) {
-                const int u = u0 + v;
-                traw[v] = u32x4{0, 0, 0, 0};
-                if (u < nmlp) {
-                    if constexpr (FH::is_static) traw[v] = gload16(uniform_ptr(reinterpret_cast<const char*>(t1 + act_idx(0, u, B))), (unsigned)((wc * H + col) * (int)sizeof(T)));
-                    else traw[v] = *reinterpret_cast<const u32x4*>(t1 + act_idx(wc, u, B) + col);
-                    acc_fill(tm[v], 0.f);
-                    load_afrag<T>(af, smem, u, lane);
-                    mac(tm[v], af, bf);
-                }
-            }
-            load_bfrag<T>(bf, wpack, bh[FH_W1], wn, lane);
-            __syncthreads();   // all reads of the dY blocks done
-#pragma unroll
-            for (int v = 0; v < 2; ++v) {
-                const int u = u0 + v;
-                dupk[v] = u32x4{0, 0, 0, 0};
-                if (u < nmlp) {
-                    f32x4 t0, t1v, r0, r1; unpack_oct(traw[v], t0, t1v);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) { r0[j] = t0[j] > 0.f ? tm[v].c[0][j] : 0.f; r1[j] = t1v[j] > 0.f ? tm[v].c[1][j] : 0.f; }
-                    dupk[v] = pack_oct(r0, r1);
-                    *reinterpret_cast<u32x4*>(smem + lds_chunk<T>(u, win, col / P::EPC)) = dupk[v];
-                }
-            }
-            __syncthreads();
-#pragma unroll
-            for (int v = 0; v < 2; ++v) {
-                const int u = u0 + v;
-                if (u < nmlp) { acc_fill(tm[v], 0.f); load_afrag<T>(af, smem, u, lane); mac(tm[v], af, bf); }
-            }
-            __syncthreads();   // all reads of the dU blocks done
-#pragma unroll
-            for (int v = 0; v < 2; ++v) {
-                const int u = u0 + v;
-                if (u < nmlp) {
-                    const u32x4 hp = pack_oct(tm[v].c[0], tm[v].c[1]);
-                    *reinterpret_cast<u32x4*>(smem + lds_chunk<T>(u, win, col / P::EPC)) = hp;
-                    if (w_ok) {
-                        if constexpr (FH::is_static) {
-                            gstore16(uniform_wptr(reinterpret_cast<char*>(du + act_idx(0, u, B))), (unsigned)((w * H + col) * (int)sizeof(T)), dupk[v]);
-                            gstore16(uniform_wptr(reinterpret_cast<char*>(dh + act_idx(0, u, B))), (unsigned)((w * H + col) * (int)sizeof(T)), hp);
-                        } else {
-                            *reinterpret_cast<u32x4*>(du + act_idx(w, u, B) + col) = dupk[v];
-                            *reinterpret_cast<u32x4*>(dh + act_idx(w, u, B) + col) = hp;
-                        }
-                    }
-                }
-            }
-        }
-        __syncthreads();
-    }
-
-    // dX_l[j] = (residual) + dH_j W_rootsum + sum_r sum_{j->i} dH_i W_rel^r, group A then group B
-    const T* xact = reinterpret_cast<const T*>(a.ws + a.x_off[0]);
-    const bool enc_mask = (flags & FF_ENC_MASK) != 0;
-    FS_STAMP2(2 + 6 * li);
-    if constexpr (PRE) {
-        constexpr bool a_first = !(FH{}[FH_FLAGS] & FF_A_EMPTY);
-        slab_group_bwd<T, SL_HA, 0, a_first>(a, bh, wa, smem, wpack, wn, lane, FH_SLOTA, xact, enc_mask, keepA, pre);
-        FS_STAMP2(3 + 6 * li);
-        slab_group_bwd<T, HB, SL_HA, !a_first>(a, bh, wb, smem, wpack, wn, lane, FH_SLOTB, xact, enc_mask, keepB, pre);
-    } else {
-        slab_group_bwd<T, SL_HA, 0>(a, bh, wa, smem, wpack, wn, lane, FH_SLOTA, xact, enc_mask, keepA);
-        FS_STAMP2(3 + 6 * li);
-        slab_group_bwd<T, HB, SL_HA>(a, bh, wb, smem, wpack, wn, lane, FH_SLOTB, xact, enc_mask, keepB);
-    }
-    FS_STAMP2(4 + 6 * li);
-    __syncthreads();   // every wave is done reading dH_l
-    FS_STAMP2(5 + 6 * li);
-    mid();      // next header / programs landed before the stores go out (FProg::settle)
-    T* dxo = reinterpret_cast<T*>(a.ws + a.dx_off[l]);
-    if constexpr (FH::is_static) {      // (as slab_group_store: LDS rows first, then every stash row under one lane predicate)
-        if (l > 0) {
-#pragma unroll
-            for (int q = 0; q < SL_HA + HB; ++q)
-                if (bh[FH_OUT + q])
-                    *reinterpret_cast<u32x4*>(smem + lds_chunk<T>(bh[(q < SL_HA ? FH_SLOTA : FH_SLOTB - SL_HA) + q], win, col / P::EPC)) = q < SL_HA ? keepA[q < SL_HA ? q : 0] : keepB[q < SL_HA ? 0 : q - SL_HA];
-        }
-        if (w_ok) {
-#ifdef MSHGNN_STASH_ALIAS
-            const unsigned soff = (unsigned)((((blockIdx.x & 31) * P::ROWS + win) * H + col) * (int)sizeof(T));
-#else
-            const unsigned soff = (unsigned)((w * H + col) * (int)sizeof(T));
-#endif
-#pragma unroll
-            for (int q = 0; q < SL_HA + HB; ++q)
-                if (bh[FH_OUT + q])
-                    stash_store_u(a, uniform_wptr(reinterpret_cast<char*>(dxo + act_idx(0, bh[(q < SL_HA ? FH_SLOTA : FH_SLOTB - SL_HA) + q], B))), soff, q < SL_HA ? keepA[q < SL_HA ? q : 0] : keepB[q < SL_HA ? 0 : q - SL_HA]);
-        }
-    } else {
-#pragma unroll
-        for (int q = 0; q < SL_HA + HB; ++q) {
-            if (bh[FH_OUT + q]) {
-                const int n = bh[(q < SL_HA ? FH_SLOTA : FH_SLOTB - SL_HA) + q];
-                const u32x4 v = q < SL_HA ? keepA[q < SL_HA ? q : 0] : keepB[q < SL_HA ? 0 : q - SL_HA];
-                if (l > 0) *reinterpret_cast<u32x4*>(smem + lds_chunk<T>(n, win, col / P::EPC)) = v;
-                if (w_ok) stash_store(dxo + act_idx(w, n, B) + col, v, a.stash_nt != 0);
-            }
-        }
-    }
-    __syncthreads();
-    FS_STAMP2(6 + 6 * li);
-}
-// the layers of a compile-time program SP, last to first, unrolled
-template <typename T, int NM, int HB, class SP, int l, class A>
-__device__ __forceinline__ void slab_bwd_layers_static(const A& a, char* smem, const T* wpack, int wn, int lane, u32x4 (&keepA)[SL_HA], u32x4 (&keepB)[HB],
-                                                       unsigned (&mbq)[SL_HA + HB], typename Prec<T>::BFrag (&pre)[2]) {
-    if constexpr (l >= 0) {
-        auto mid = [&] {      // before layer l's stores: layer l - 1's relu bytes (written by the forward sweep long ago) and first weight fragments
-            if constexpr (l > 0) {
-                if constexpr ((SP::PRE & 2) != 0) {
-                    constexpr SHdr<SP, 1, l - 1> nh{};
-                    const uint8_t* mbn = reinterpret_cast<const uint8_t*>(a.ws + a.mask_off[l - 1]);
-#pragma unroll
-                    for (int q = 0; q < SL_HA + HB; ++q) {
-                        mbq[q] = 0xffu;
-                        if (nh[FH_KIND + q] == NK_RELU) mbq[q] = gload1(uniform_ptr(reinterpret_cast<const char*>(mbn) + relu_tile_base(nh[(q < SL_HA ? FH_SLOTA : FH_SLOTB - SL_HA) + q], a.B, blockIdx.x, wn)), (unsigned)lane);
-                    }
-                }
-                if constexpr ((SP::PRE & 1) != 0) slab_prefetch_static<T, SP, 1, l - 1>(pre, wpack, wn, lane);
-            }
-        };
-        // (the last layer's bytes are the forward's own bits whatever SP::PRE says)
-        slab_bwd_layer<T, NM, HB, (SP::PRE & 1) != 0, (SP::PRE & 2) != 0 || l == SP::L - 1>(a, smem, wpack, wn, lane, l, SP::L - 1 - l, SHdr<SP, 1, l>{}, SProg<SP, 1, l, 0>{}, SProg<SP, 1, l, 1>{},
-                                                                                              keepA, keepB, mid, mbq, &pre);
-        slab_bwd_layers_static<T, NM, HB, SP, l - 1>(a, smem, wpack, wn, lane, keepA, keepB, mbq, pre);
-    }
-}
-// the last layer's relu bytes of a one-launch step are the forward's own bits (same wave, same lane, same slots): no load
-template <class SP, int HB> __device__ __forceinline__ void slab_bits_to_bytes(const unsigned* lastbits, unsigned (&mbq)[SL_HA + HB]) {
-    constexpr SHdr<SP, 1, SP::L - 1> bh{};
-    constexpr SHdr<SP, 0, SP::L - 1> fh{};
-#pragma unroll
-    for (int q = 0; q < SL_HA + HB; ++q) {
-        mbq[q] = 0xffu;
-        if (bh[FH_KIND + q] == NK_RELU) {
-            const int u = q < SL_HA ? q : q - SL_HA;
-            const unsigned word = lastbits[(q < SL_HA ? 0 : (SL_HA + 3) / 4) + (u >> 2)];
-            mbq[q] = (word >> (8 * (u & 3))) & 0xffu;
-        }
-    }
-}
-template <class SP, int HB> constexpr bool slab_bits_consistent() {      // a node masked by the backward's last layer was a relu node of the forward's last layer, in the same slot
-    for (int q = 0; q < SL_HA + HB; ++q)
-        if (SP::bwd[SP::L - 1][FH_KIND + q] == NK_RELU && SP::fwd[SP::L - 1][FH_KIND + q] != NK_RELU) return false;
-    for (int u = 0; u < 16; ++u)
-        if (SP::bwd[SP::L - 1][FH_SLOTA + u] != SP::fwd[SP::L - 1][FH_SLOTA + u] || SP::bwd[SP::L - 1][FH_SLOTB + u] != SP::fwd[SP::L - 1][FH_SLOTB + u]) return false;
-    return true;
-}
-// the carried rows at the start of the sweep: the decoder backward's dX_L, read back from the tile in LDS (rows past the batch are zero there)
-template <typename T, int HB, class FH>
-__device__ __forceinline__ void slab_bwd_keep_init(const FH& bh, const char* smem, int wn, int lane, u32x4 (&keepA)[SL_HA], u32x4 (&keepB)[HB]) {
-    using P = Prec<T>;
-    const int loffq = lds_chunk<T>(0, c_win(lane), (wn * 32 + c_oct(lane)) / P::EPC);
-#pragma unroll
-    for (int u = 0; u < SL_HA; ++u) {
-        keepA[u] = u32x4{0, 0, 0, 0};
-        const int n = bh[FH_SLOTA + u];
-        if (n >= 0 && bh[FH_KIND + u] != NK_DEAD) keepA[u] = *reinterpret_cast<const u32x4*>(smem + n * P::BLK + loffq);
-    }
-#pragma unroll
-    for (int u = 0; u < HB; ++u) {
-        keepB[u] = u32x4{0, 0, 0, 0};
-        const int n = bh[FH_SLOTB + u];
-        if (n >= 0 && bh[FH_KIND + SL_HA + u] != NK_DEAD) keepB[u] = *reinterpret_cast<const u32x4*>(smem + n * P::BLK + loffq);
-    }
-}
-
-// STEP: part of k_slab_step -- the forward's decoder tail of the same launch left the dX_L tile in LDS; the layers' programs are a.prog_off_b
-// SP: void = the plan's tables are interpreted; else the compile-time program of one (topology, depth)
-template <typename T, int NM, int HB, bool STEP, class SP = void, class A = StackArgs> __device__ __forceinline__ void slab_bwd_body(const A& a, char* smem, const unsigned* lastbits = nullptr) {
-    using P = Prec<T>;
-    constexpr bool DYN = std::is_void<SP>::value;
-    const int tid = threadIdx.x, lane = tid & 63, wn = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int w0 = blockIdx.x * P::ROWS, B = a.B, NN = a.NN;
-    const T* wpack = reinterpret_cast<const T*>(a.wpack);
-    static_assert(sizeof(T) == 2, "fused stack kernels are bf16");
-    auto prog_of = [&](int l) { return STEP ? a.prog_off_b[l] : a.prog_off[l]; };
-    if constexpr (!STEP) stack_stagger(a);
-
-    // the last layer's header and programs stream in under the tile load
-    FHdr bhn; FProg wan, wbn;
-    if constexpr (DYN) {
-        bhn = FHdr(a.tables + prog_of(a.L - 1), lane);
-        wan = FProg(a.tables + prog_of(a.L - 1) + FH_SIZE, lane); wbn = FProg(a.tables + prog_of(a.L - 1) + FH_SIZE + FPROG_LEN, lane);
-    }
-    // dX_L tile: only the nodes that are live in the last layer carry a gradient -- the output type's [node0, node0 + n_out), known from the arguments, so
-    // the loads do not wait for the header; four nodes per round trip
-    if constexpr (!STEP) {
-        const T* src = reinterpret_cast<const T*>(a.tile_in);
-        const int row = tid >> 4, c = tid & 15;
-        for (int f0 = 0; f0 < a.n_out; f0 += 4) {
-            u32x4 v[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                v[i] = u32x4{0, 0, 0, 0};
-                if (f0 + i < a.n_out && w0 + row < B) v[i] = *reinterpret_cast<const u32x4*>(src + act_idx(w0 + row, a.node0 + f0 + i, B) + c * P::EPC);
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                if (f0 + i < a.n_out) *reinterpret_cast<u32x4*>(smem + lds_chunk<T>(a.node0 + f0 + i, row, c)) = v[i];
-        }
-    }
-    __syncthreads();
-
-    // group A's residual term travels from layer to layer in registers (the packed dX rows of the previous epilogue); for the
-    // last layer it is the decoder backward's dX_L
-    u32x4 keepA[SL_HA], keepB[HB];
-    if constexpr (DYN) {
-        slab_bwd_keep_init<T, HB>(bhn, smem, wn, lane, keepA, keepB);
-        bhn.settle(); wan.settle(); wbn.settle();
-        FS_STAMP2(0);
-        for (int l = a.L - 1; l >= 0; --l) {
-            const FHdr bh = bhn;
-            const FProg wa = wan, wb = wbn;
-            if (l > 0) {
-                bhn = FHdr(a.tables + prog_of(l - 1), lane);
-                wan = FProg(a.tables + prog_of(l - 1) + FH_SIZE, lane);
-                wbn = FProg(a.tables + prog_of(l - 1) + FH_SIZE + FPROG_LEN, lane);
-            }
-            slab_bwd_layer<T, NM, HB>(a, smem, wpack, wn, lane, l, a.L - 1 - l, bh, wa, wb, keepA, keepB, [&] { bhn.settle(); wan.settle(); wbn.settle(); });
-        }
-    } else {
-        static_assert(slab_bits_consistent<SP, HB>(), "forward / backward tables of the last layer disagree");
-        typename P::BFrag pre[2];
-        if constexpr ((SP::PRE & 1) != 0) slab_prefetch_static<T, SP, 1, SP::L - 1>(pre, wpack, wn, lane);      // (nothing is stored between here and the first pass: the mask phase writes LDS only)
-        slab_bwd_keep_init<T, HB>(SHdr<SP, 1, SP::L - 1>{}, smem, wn, lane, keepA, keepB);
-        unsigned mbq[SL_HA + HB];
-        if constexpr (STEP) slab_bits_to_bytes<SP, HB>(lastbits, mbq);
-        else {      // the backward launch alone: the last layer's relu bytes come from the forward launch's stash, like every other layer's
-            constexpr SHdr<SP, 1, SP::L - 1> nh{};
-            const uint8_t* mbn = reinterpret_cast<const uint8_t*>(a.ws + a.mask_off[SP::L - 1]);
-#pragma unroll
-            for (int q = 0; q < SL_HA + HB; ++q) {
-                mbq[q] = 0xffu;
-                if (nh[FH_KIND + q] == NK_RELU) mbq[q] = gload1(uniform_ptr(reinterpret_cast<const char*>(mbn) + relu_tile_base(nh[(q < SL_HA ? FH_SLOTA : FH_SLOTB - SL_HA) + q], a.B, blockIdx.x, wn)), (unsigned)lane);
-            }
-        }
-        FS_STAMP2(0);
-        slab_bwd_layers_static<T, NM, HB, SP, SP::L - 1>(a, smem, wpack, wn, lane, keepA, keepB, mbq, pre);
-    }
+template <typename T, int NM, int HB> __global__ __launch_bounds__(SL_THREADS, 2) void k_slab_fwd(StackArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    slab_fwd_body<T, NM, HB, false>(a, smem);
 }
 template <typename T, int NM, int HB> __global__ __launch_bounds__(SL_THREADS, 2) void k_slab_bwd(StackArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     slab_bwd_body<T, NM, HB, false>(a, smem);
-}
-// The backward launch alone (second call of the two-call training route: mshgnn_backward / _mse / _ce after mshgnn_forward(training = 1)) over the compile-time programs:
-// whole tiles, NT = the stash store policy.  Same MACs, same order as k_slab_bwd: identical bits.
-template <typename T, int NM, int HB, class SP, int NT> __global__ __launch_bounds__(SL_THREADS, 2) void k_slab_bwd_spec(StackArgs a) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const StackView<NT> v(a, true);
-    slab_bwd_body<T, NM, HB, false, SP>(v, smem);
-}
-// One-call training step (mshgnn_step_mse / mshgnn_step_ce): the forward layers, decoder + loss + decoder backward and the backward layers of a tile in ONE
-// launch.  The tail leaves dX_L in the node blocks, so the backward sweep starts without a launch boundary, without the header / tile round trips of
-// k_slab_bwd's start and without re-reading dX_L (stamps: 16 k of its 163 k cycles).  Same code, same order of every accumulation: identical bits.
-template <typename T, int NM, int HB, class SP = void, int NT = 0, bool FULL = true> __global__ __launch_bounds__(SL_THREADS, 2) void k_slab_step(StackArgs a) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    if constexpr (!std::is_void<SP>::value) {      // compile-time program; NT: the stash store policy; FULL: whole tiles only, unpredicated stores (else any batch size)
-        const StackView<NT, FULL> v(a, true);
-        unsigned lastbits[(SL_HA + 3) / 4 + (HB + 3) / 4];
-        slab_fwd_body<T, NM, HB, true, SP>(v, smem, lastbits);
-        __syncthreads();
-        slab_bwd_body<T, NM, HB, true, SP>(v, smem, lastbits);
-    } else {
-        slab_fwd_body<T, NM, HB, true, SP>(a, smem);
-        __syncthreads();      // the tile's dX_L rows are in the out-type blocks, the tail's reduction scratch has been read
-        slab_bwd_body<T, NM, HB, true, SP>(a, smem);
-    }
-}
-
-// the slab instantiation of a plan: NM = bound on the base_transform nodes (2 / 4), HB = group-B slots (6 / 8)
-using StackKernel = void (*)(StackArgs);
-// Specialised step kernels: k_slab_step over the COMPILE-TIME program of one (topology, depth) -- mshgnn_spec_tables.inc, generated from this library's own plan
-// compiler by tools/gen_spec_tables.py.  A plan takes one only when its slab tables are exactly the ints the kernel was compiled from (same packs, same
-// slots, same liveness), so a stale table file costs speed, never results; MSHGNN_SPEC=0 keeps the interpreting kernel (A/B runs, bit-identity tests).
-#include "mshgnn_spec_tables.inc"
-template <class SP> static bool spec_matches(const HostPlan& hp) {
-    if (!hp.slab || hp.L != SP::L || hp.NN != SP::NN || hp.sl_hb != SP::HB || (hp.n_mlp <= 2 ? 2 : 4) != SP::NM || (hp.d.out_channels <= 4 ? 4 : 8) != SP::DMAX) return false;
-    for (int l = 0; l < SP::L; ++l) {
-        if (hp.sl_fwd_off[l] + SP::ROW > (int)hp.tables.size() || hp.sl_bwd_off[l] + SP::ROW > (int)hp.tables.size()) return false;
-        if (memcmp(hp.tables.data() + hp.sl_fwd_off[l], SP::fwd[l], sizeof(int32_t) * SP::ROW) != 0) return false;
-        if (memcmp(hp.tables.data() + hp.sl_bwd_off[l], SP::bwd[l], sizeof(int32_t) * SP::ROW) != 0) return false;
-    }
-    return true;
-}
-// The forward launch alone (mshgnn_forward: evaluation, or the first call of the two-call training route) over the same compile-time programs: whole tiles; TR (training:
-// stashes and relu bytes written) and NT (their store policy) are template parameters like the step kernels' NT -- with them at run time the 8-layer programs keep their
-// store addresses live across the unrolled layers and spill (256-492 B of scratch: slower than the interpreter at 8 192 windows).  The decoder tail runs without the fused
-// loss.  Same MACs, same order: the interpreter's bits.
-template <typename T, int NM, int HB, class SP, int TR, int NT, bool FULL = true> __global__ __launch_bounds__(SL_THREADS, 2) void k_slab_fwd_spec(StackArgs a) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    StackView<NT, FULL> v(a, false);
-    v.training = TR;
-    unsigned lastbits[(SL_HA + 3) / 4 + (HB + 3) / 4];
-    slab_fwd_body<T, NM, HB, false, SP>(v, smem, lastbits);
-}
-// The kernels over the compile-time programs are instantiated in their own translation units -- this source compiled with -DMSHGNN_SPEC_SHARD=1..7 (csrc/Makefile:
-// mshgnn_spec<k>.o), one program each (MSHGNN_SPEC_LIST_<k>), side by side with the rest of the library (shard 0: everything else).  A shard exports one
-// selector: kind 0 = one-call step, 1 = forward alone (tr: training), 2 = backward alone; nt = the launch's stash store policy (stash_nt_for); name: the program's name.
-#define SPEC_SHARD_LIST(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7)      // one program per shard (tools/gen_spec_tables.py SHARDS)
-#define SPEC_SHARD_DECL(k) StackKernel spec_shard##k(const HostPlan& hp, int kind, int tr, int nt, int full, const char** name);
-SPEC_SHARD_LIST(SPEC_SHARD_DECL)
-// full (the batch is whole 16-window tiles): the unpredicated kernels, both store policies.  Else: the predicated forms that exist -- the one-call step with plain stash stores
-// (a ragged batch whose stash wants non-temporal stores keeps the interpreter: the weight-gradient launch behind plain stores loses more than the program wins at 8 layers)
-// and the evaluation forward; the two-call training route of a ragged batch keeps the interpreters (nullptr).
-#if MSHGNN_SPEC_SHARD != 0
-#define MSHGNN_SPEC_TRY(SP) if (spec_matches<SP>(hp)) { \
-        if (name) *name = #SP; \
-        if (kind == 0 && !full) return nt ? nullptr : k_slab_step<__bf16, SP::NM, SP::HB, SP, 0, false>; \
-        if (kind == 0) return nt ? k_slab_step<__bf16, SP::NM, SP::HB, SP, 1> : k_slab_step<__bf16, SP::NM, SP::HB, SP, 0>; \
-        if (kind == 1 && !tr) return full ? k_slab_fwd_spec<__bf16, SP::NM, SP::HB, SP, 0, 0> : k_slab_fwd_spec<__bf16, SP::NM, SP::HB, SP, 0, 0, false>; \
-        if (!full) return nullptr; \
-        if (kind == 1) return nt ? k_slab_fwd_spec<__bf16, SP::NM, SP::HB, SP, 1, 1> : k_slab_fwd_spec<__bf16, SP::NM, SP::HB, SP, 1, 0>; \
-        return nt ? k_slab_bwd_spec<__bf16, SP::NM, SP::HB, SP, 1> : k_slab_bwd_spec<__bf16, SP::NM, SP::HB, SP, 0>; }
-#define SPEC_CAT2(a, b) a##b
-#define SPEC_CAT(a, b) SPEC_CAT2(a, b)
-#if MSHGNN_SPEC_SHARD == 99
-// Shard 99 is not part of the library: it is this source compiled AFTER the build, for one plan's own tables (morphsym_hgnn_amd/jit.py renders them as MSHGNN_JIT_TABLES -- a
-// struct spec::JIT_<hash> and MSHGNN_SPEC_LIST_99 -- and compiles a small shared library of the program's kernels), for topologies the build has no program for.  The library
-// takes its selector through mshgnn_plan_attach_program and checks the tables like every shard does.
-#include MSHGNN_JIT_TABLES
-#endif
-StackKernel SPEC_CAT(spec_shard, MSHGNN_SPEC_SHARD)(const HostPlan& hp, int kind, int tr, int nt, int full, const char** name) { SPEC_CAT(MSHGNN_SPEC_LIST_, MSHGNN_SPEC_SHARD)(MSHGNN_SPEC_TRY) return nullptr; }
-#if MSHGNN_SPEC_SHARD == 99
-extern "C" StackKernel mshgnn_jit_program(const HostPlan& hp, int kind, int tr, int nt, int full, const char** name) { return spec_shard99(hp, kind, tr, nt, full, name); }
-#endif
-#undef MSHGNN_SPEC_TRY
-#else      // MSHGNN_SPEC_SHARD == 0: the library proper, to the end of this file
-static StackKernel slab_fwd_kernel(const HostPlan& hp) {
-    if (hp.sl_hb <= SL_HB) return hp.n_mlp <= 2 ? k_slab_fwd<__bf16, 2, SL_HB> : k_slab_fwd<__bf16, 4, SL_HB>;
-    return hp.n_mlp <= 2 ? k_slab_fwd<__bf16, 2, SL_HB_MAX> : k_slab_fwd<__bf16, 4, SL_HB_MAX>;
-}
-using SpecSelector = StackKernel (*)(const HostPlan& hp, int kind, int tr, int nt, int full, const char** name);
-static StackKernel spec_kernel(const HostPlan& hp, int kind, int tr, int nt, int full, const char** name = nullptr) {
-    const char* nm = nullptr;      // (a shard that holds the plan's program sets the name even where it has no kernel of that kind: stop there)
-    if (hp.jit_prog) {             // a program compiled for this plan after the build
-        StackKernel kk = reinterpret_cast<SpecSelector>(hp.jit_prog)(hp, kind, tr, nt, full, &nm);
-        if (nm) { if (name) *name = nm; return kk; }
-    }
-#define SPEC_SHARD_TRY(k) { StackKernel kk = spec_shard##k(hp, kind, tr, nt, full, &nm); if (nm) { if (name) *name = nm; return kk; } }
-    SPEC_SHARD_LIST(SPEC_SHARD_TRY)
-#undef SPEC_SHARD_TRY
-    return nullptr;
-}
-inline bool whole_tiles(int64_t B) { return B > 0 && B % TILE_ROWS == 0; }
-static StackKernel slab_step_spec_kernel(const HostPlan& hp, int nt, const char** name = nullptr, bool full = true) { return spec_kernel(hp, 0, 1, nt, full, name); }
-static StackKernel slab_fwd_spec_kernel(const HostPlan& hp, int training, int nt, bool full = true) { return spec_kernel(hp, 1, training, nt, full); }
-static StackKernel slab_bwd_spec_kernel(const HostPlan& hp, int nt, bool full = true) { return spec_kernel(hp, 2, 1, nt, full); }
-// the step kernel of a launch: the specialised one where the plan has one and the batch is whole tiles (its stores are unpredicated), else the interpreter
-static StackKernel slab_step_kernel(const HostPlan& hp, int64_t B = -1, int nt = 0, bool use_spec = false) {
-    if (use_spec && B > 0) if (StackKernel k = slab_step_spec_kernel(hp, nt, nullptr, whole_tiles(B))) return k;
-    if (hp.sl_hb <= SL_HB) return hp.n_mlp <= 2 ? k_slab_step<__bf16, 2, SL_HB> : k_slab_step<__bf16, 4, SL_HB>;
-    return hp.n_mlp <= 2 ? k_slab_step<__bf16, 2, SL_HB_MAX> : k_slab_step<__bf16, 4, SL_HB_MAX>;
-}
-static StackKernel slab_bwd_kernel(const HostPlan& hp) {
-    if (hp.sl_hb <= SL_HB) return hp.n_mlp <= 2 ? k_slab_bwd<__bf16, 2, SL_HB> : k_slab_bwd<__bf16, 4, SL_HB>;
-    return hp.n_mlp <= 2 ? k_slab_bwd<__bf16, 2, SL_HB_MAX> : k_slab_bwd<__bf16, 4, SL_HB_MAX>;
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -1890,22 +1144,6 @@ template <typename T> __global__ __launch_bounds__(256) void k_dec_bwd(DecArgs a
         for (int r = 0; r < 16; ++r) s2 += red[r][i];
         slab[i] = s2;
     }
-}
-
-__global__ void k_mse(const float* out, const float* y, int64_t n, float* loss, float* gout) {
-    __shared__ float red[4];
-    float s = 0.f;
-    const float inv = 1.0f / (float)n;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float dlt = out[i] - y[i];
-        s += dlt * dlt;
-        if (gout) gout[i] = 2.0f * dlt * inv;
-    }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(loss, (red[0] + red[1] + red[2] + red[3]) * inv);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -2504,6 +1742,40 @@ __global__ __launch_bounds__(256) void k_finalize(FinArgs a) {
             for (int k = 0; k < nm; ++k) a.grad[((int64_t)(unsigned)more[1 + 2 * k] | ((int64_t)more[2 + 2 * k] << 32)) + (int64_t)r * ld + cidx] = s;
         }
     }
+}
+
+// ------------------------------------------------------------------------------------------------------
+// Kernel selection: the slab kernel of a plan and a launch -- a compile-time program's where a shard (or the plan's attached program) has one, else the interpreter
+// ------------------------------------------------------------------------------------------------------
+static StackKernel slab_fwd_kernel(const HostPlan& hp) {
+    if (hp.sl_hb <= SL_HB) return hp.n_mlp <= 2 ? k_slab_fwd<__bf16, 2, SL_HB> : k_slab_fwd<__bf16, 4, SL_HB>;
+    return hp.n_mlp <= 2 ? k_slab_fwd<__bf16, 2, SL_HB_MAX> : k_slab_fwd<__bf16, 4, SL_HB_MAX>;
+}
+using SpecSelector = StackKernel (*)(const HostPlan& hp, int kind, int tr, int nt, int full, const char** name);
+static StackKernel spec_kernel(const HostPlan& hp, int kind, int tr, int nt, int full, const char** name = nullptr) {
+    const char* nm = nullptr;      // (a shard that holds the plan's program sets the name even where it has no kernel of that kind: stop there)
+    if (hp.jit_prog) {             // a program compiled for this plan after the build
+        StackKernel kk = reinterpret_cast<SpecSelector>(hp.jit_prog)(hp, kind, tr, nt, full, &nm);
+        if (nm) { if (name) *name = nm; return kk; }
+    }
+#define SPEC_SHARD_TRY(k) { StackKernel kk = spec_shard##k(hp, kind, tr, nt, full, &nm); if (nm) { if (name) *name = nm; return kk; } }
+    SPEC_SHARD_LIST(SPEC_SHARD_TRY)
+#undef SPEC_SHARD_TRY
+    return nullptr;
+}
+inline bool whole_tiles(int64_t B) { return B > 0 && B % TILE_ROWS == 0; }
+static StackKernel slab_step_spec_kernel(const HostPlan& hp, int nt, const char** name = nullptr, bool full = true) { return spec_kernel(hp, 0, 1, nt, full, name); }
+static StackKernel slab_fwd_spec_kernel(const HostPlan& hp, int training, int nt, bool full = true) { return spec_kernel(hp, 1, training, nt, full); }
+static StackKernel slab_bwd_spec_kernel(const HostPlan& hp, int nt, bool full = true) { return spec_kernel(hp, 2, 1, nt, full); }
+// the step kernel of a launch: the specialised one where the plan has one and the batch is whole tiles (its stores are unpredicated), else the interpreter
+static StackKernel slab_step_kernel(const HostPlan& hp, int64_t B = -1, int nt = 0, bool use_spec = false) {
+    if (use_spec && B > 0) if (StackKernel k = slab_step_spec_kernel(hp, nt, nullptr, whole_tiles(B))) return k;
+    if (hp.sl_hb <= SL_HB) return hp.n_mlp <= 2 ? k_slab_step<__bf16, 2, SL_HB> : k_slab_step<__bf16, 4, SL_HB>;
+    return hp.n_mlp <= 2 ? k_slab_step<__bf16, 2, SL_HB_MAX> : k_slab_step<__bf16, 4, SL_HB_MAX>;
+}
+static StackKernel slab_bwd_kernel(const HostPlan& hp) {
+    if (hp.sl_hb <= SL_HB) return hp.n_mlp <= 2 ? k_slab_bwd<__bf16, 2, SL_HB> : k_slab_bwd<__bf16, 4, SL_HB>;
+    return hp.n_mlp <= 2 ? k_slab_bwd<__bf16, 2, SL_HB_MAX> : k_slab_bwd<__bf16, 4, SL_HB_MAX>;
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -3208,703 +2480,6 @@ extern "C" int mshgnn_step_mse_phase(const mshgnn_plan* p, const void* const* x,
 }
 
 // ------------------------------------------------------------------------------------------------------
-// Adam on the flat fp32 buffers (configure_optimizers: optim.Adam(self.parameters(), lr), gnnLightning.py:258-265;
-// torch defaults beta=(0.9, 0.999), eps=1e-8, no weight decay, no amsgrad).  SURVEY.md section 8(f) row 2.
-// ------------------------------------------------------------------------------------------------------
-__global__ void k_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps,
-                       float bc1, float bc2_sqrt, float gscale) {
-    for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += (int64_t)gridDim.x * blockDim.x * 4) {
-        if (i + 4 <= n) {
-            f32x4 pp = *reinterpret_cast<f32x4*>(p + i), gg = *reinterpret_cast<const f32x4*>(g + i) * gscale;
-            f32x4 mm = *reinterpret_cast<f32x4*>(m + i), vv = *reinterpret_cast<f32x4*>(v + i);
-            mm = b1 * mm + (1.f - b1) * gg;
-            vv = b2 * vv + (1.f - b2) * gg * gg;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) pp[e] -= lr / bc1 * mm[e] / (sqrtf(vv[e]) / bc2_sqrt + eps);
-            *reinterpret_cast<f32x4*>(p + i) = pp; *reinterpret_cast<f32x4*>(m + i) = mm; *reinterpret_cast<f32x4*>(v + i) = vv;
-        } else {
-            for (int64_t k = i; k < n; ++k) {
-                const float gg = g[k] * gscale;
-                m[k] = b1 * m[k] + (1.f - b1) * gg; v[k] = b2 * v[k] + (1.f - b2) * gg * gg;
-                p[k] -= lr / bc1 * m[k] / (sqrtf(v[k]) / bc2_sqrt + eps);
-            }
-        }
-    }
-}
-
-extern "C" int mshgnn_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, int64_t step,
-                                float lr, float beta1, float beta2, float eps, float grad_scale, void* stream) {
-    if (!params || !grads || !exp_avg || !exp_avg_sq || n < 1 || step < 1) return set_err(MSHGNN_EINVAL, "bad argument to mshgnn_adam_step");
-    if (((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) return set_err(MSHGNN_EINVAL, "adam buffers must be 16-byte aligned");
-    const float bc1 = 1.0f - powf(beta1, (float)step), bc2 = 1.0f - powf(beta2, (float)step);
-    const int blocks = (int)std::min<int64_t>((n / 4 + 255) / 256 + 1, 2048);
-    hipLaunchKernelGGL(k_adam, dim3(blocks), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps,
-                       bc1, sqrtf(bc2), grad_scale);
-    HIPCHK(hipGetLastError());
-    return MSHGNN_OK;
-}
-
-// The same update with the step count on the DEVICE (capturable in a HIP graph: nothing of the bias corrections is baked into the launch arguments).  The kernel
-// reads t = *step_count + 1 and derives 1 - beta^t itself; a one-thread launch behind it stores t.  FlatAdam(graph_safe=True), wrappers.GraphedTrainingStep.
-__global__ void k_adam_counted(float* p, const float* g, float* m, float* v, int64_t n, const int64_t* step_count, float lr, float b1, float b2, float eps, float gscale) {
-    const float t = (float)(*step_count + 1);
-    const float bc1 = 1.0f - powf(b1, t), bc2_sqrt = sqrtf(1.0f - powf(b2, t));
-    for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += (int64_t)gridDim.x * blockDim.x * 4) {
-        if (i + 4 <= n) {
-            f32x4 pp = *reinterpret_cast<f32x4*>(p + i), gg = *reinterpret_cast<const f32x4*>(g + i) * gscale;
-            f32x4 mm = *reinterpret_cast<f32x4*>(m + i), vv = *reinterpret_cast<f32x4*>(v + i);
-            mm = b1 * mm + (1.f - b1) * gg;
-            vv = b2 * vv + (1.f - b2) * gg * gg;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) pp[e] -= lr / bc1 * mm[e] / (sqrtf(vv[e]) / bc2_sqrt + eps);
-            *reinterpret_cast<f32x4*>(p + i) = pp; *reinterpret_cast<f32x4*>(m + i) = mm; *reinterpret_cast<f32x4*>(v + i) = vv;
-        } else {
-            for (int64_t k = i; k < n; ++k) {
-                const float gg = g[k] * gscale;
-                m[k] = b1 * m[k] + (1.f - b1) * gg; v[k] = b2 * v[k] + (1.f - b2) * gg * gg;
-                p[k] -= lr / bc1 * m[k] / (sqrtf(v[k]) / bc2_sqrt + eps);
-            }
-        }
-    }
-}
-__global__ void k_step_count_inc(int64_t* step_count) { *step_count += 1; }
-
-extern "C" int mshgnn_adam_step_counted(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, int64_t* step_count,
-                                        float lr, float beta1, float beta2, float eps, float grad_scale, void* stream) {
-    if (!params || !grads || !exp_avg || !exp_avg_sq || !step_count || n < 1) return set_err(MSHGNN_EINVAL, "bad argument to mshgnn_adam_step_counted");
-    if (((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) return set_err(MSHGNN_EINVAL, "adam buffers must be 16-byte aligned");
-    const int blocks = (int)std::min<int64_t>((n / 4 + 255) / 256 + 1, 2048);
-    hipLaunchKernelGGL(k_adam_counted, dim3(blocks), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg, exp_avg_sq, n, step_count, lr, beta1, beta2, eps, grad_scale);
-    hipLaunchKernelGGL(k_step_count_inc, dim3(1), dim3(1), 0, (hipStream_t)stream, step_count);
-    HIPCHK(hipGetLastError());
-    return MSHGNN_OK;
-}
-
-extern "C" int mshgnn_mse_loss(const float* out, const float* y, int64_t n, float* loss_out, float* grad_out, void* stream) {
-    if (!out || !y || !loss_out || n < 1) return set_err(MSHGNN_EINVAL, "bad argument to mshgnn_mse_loss");
-    hipStream_t st = (hipStream_t)stream;
-    HIPCHK(hipMemsetAsync(loss_out, 0, sizeof(float), st));
-    const int blocks = (int)std::min<int64_t>((n + 255) / 256, 1024);
-    hipLaunchKernelGGL(k_mse, dim3(blocks), dim3(256), 0, st, out, y, n, loss_out, grad_out);
-    HIPCHK(hipGetLastError());
-    return MSHGNN_OK;
-}
-
-// Stand-alone contact cross entropy of the classification wrappers (gnnLightning.py:640-648, customMetrics.py:6-25: CrossEntropyLoss over
-// the [rows, 2] per-foot logits, batch value = sum / rows) with its gradient (softmax - onehot) / rows.  One thread per row.
-__global__ void k_ce(const float* logits, const int32_t* labels, int64_t rows, float* loss, float* gout) {
-    __shared__ float red[4];
-    float s = 0.f;
-    const float inv = 1.0f / (float)rows;
-    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += (int64_t)gridDim.x * blockDim.x) {
-        const float l0 = logits[2 * r], l1 = logits[2 * r + 1];
-        const float m = fmaxf(l0, l1);
-        const float e0 = expf(l0 - m), e1 = expf(l1 - m), z = e0 + e1;
-        const int lab = labels[r] != 0;
-        s += logf(z) + m - (lab ? l1 : l0);
-        if (gout) {
-            gout[2 * r] = (e0 / z - (lab ? 0.f : 1.f)) * inv;
-            gout[2 * r + 1] = (e1 / z - (lab ? 1.f : 0.f)) * inv;
-        }
-    }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(loss, (red[0] + red[1] + red[2] + red[3]) * inv);
-}
-
-extern "C" int mshgnn_ce_loss(const float* logits, const int32_t* labels, int64_t rows, float* loss_out, float* grad_out, void* stream) {
-    if (!logits || !labels || !loss_out || rows < 1) return set_err(MSHGNN_EINVAL, "bad argument to mshgnn_ce_loss");
-    hipStream_t st = (hipStream_t)stream;
-    HIPCHK(hipMemsetAsync(loss_out, 0, sizeof(float), st));
-    const int blocks = (int)std::min<int64_t>((rows + 255) / 256, 1024);
-    hipLaunchKernelGGL(k_ce, dim3(blocks), dim3(256), 0, st, logits, labels, rows, loss_out, grad_out);
-    HIPCHK(hipGetLastError());
-    return MSHGNN_OK;
-}
-
-// ------------------------------------------------------------------------------------------------------
-// Step metrics of the Lightning wrappers, on device.  The reference keeps
-// torchmetrics states that are plain sums across steps (gnnLightning.py:52-63, customMetrics.py:11-54); these kernels
-// ADD one step's sums into caller-owned state buffers.  One workgroup, fixed reduction order: deterministic.
-// ------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-__device__ __forceinline__ long long wave_sum(long long v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
-// Both kernels run on up to MET_BLOCKS workgroups: every workgroup leaves its partial sums in the caller's scratch, takes a ticket, and the
-// workgroup that draws the last ticket adds the partials IN INDEX ORDER (bit-reproducible whatever the arrival order) and resets the
-// ticket.  The one-workgroup entry points (mshgnn_metrics_regression / _classification, no scratch) run the same kernels with one block.
-constexpr int MET_COUNTS = 18, MET_BLOCKS = 64, MET_THREADS = 256;
-struct MetScratch {
-    unsigned int ticket, pad;
-    double f[MET_BLOCKS][2];
-    long long c[MET_BLOCKS][MET_COUNTS];
-};
-static_assert(sizeof(MetScratch) <= MSHGNN_METRICS_SCRATCH_BYTES, "include/mshgnn.h promises this scratch size");
-
-__device__ __forceinline__ void met_store(double* p, double v) { __hip_atomic_store(reinterpret_cast<long long*>(p), __double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ double met_load(const double* p) { return __longlong_as_double(__hip_atomic_load(reinterpret_cast<const long long*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)); }
-__device__ __forceinline__ void met_store(long long* p, long long v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ long long met_load(const long long* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// thread 0 of every workgroup, after its partials are stored: true in the workgroup that arrives last (sc == nullptr: a one-block launch)
-__device__ __forceinline__ bool met_last_block(MetScratch* sc) {
-    if (!sc) return true;
-    __atomic_thread_fence(__ATOMIC_RELEASE);        // (agent scope: the partials reach memory every XCD's L2 sees)
-    const unsigned int t = __hip_atomic_fetch_add(&sc->ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-    if (t != gridDim.x - 1) return false;
-    __atomic_thread_fence(__ATOMIC_ACQUIRE);
-    return true;
-}
-
-// regression (calculate_losses_step, gnnLightning.py:124-130): sums of (pred - y)^2, |pred - y| and n; `batch` (nullable) receives this
-// step's sums (overwritten), `epoch` (nullable) has them added; gout (nullable) = d mean((pred - y)^2) / d pred = 2 (pred - y) / n
-template <int NT> __global__ __launch_bounds__(NT) void k_metrics_reg(const float* pred, const float* y, int64_t n, double* batch, double* epoch, float* gout,
-                                                             MetScratch* sc) {
-    __shared__ double r0[NT / 64], r1[NT / 64], pf[MET_BLOCKS][2];
-    __shared__ int s_last;
-    double s = 0.0, a = 0.0;
-    const double inv2 = 2.0 / (double)n;
-    for (int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * NT) {
-        const double dlt = (double)pred[i] - (double)y[i];
-        s += dlt * dlt; a += fabs(dlt);
-        if (gout) gout[i] = (float)(dlt * inv2);
-    }
-    s = wave_sum(s); a = wave_sum(a);
-    if ((threadIdx.x & 63) == 0) { r0[threadIdx.x >> 6] = s; r1[threadIdx.x >> 6] = a; }
-    __syncthreads();
-    double ts = 0.0, ta = 0.0;
-    if (threadIdx.x == 0) {
-        for (int k = 0; k < NT / 64; ++k) { ts += r0[k]; ta += r1[k]; }
-        if (sc) { met_store(&sc->f[blockIdx.x][0], ts); met_store(&sc->f[blockIdx.x][1], ta); }
-        s_last = met_last_block(sc) ? 1 : 0;
-    }
-    if (sc) {
-        __syncthreads();
-        if (!s_last) return;
-        __atomic_thread_fence(__ATOMIC_ACQUIRE);
-        // the last workgroup: one partial per thread (all loads in flight at once), then thread 0 adds them in workgroup order
-        if (threadIdx.x < gridDim.x) { pf[threadIdx.x][0] = met_load(&sc->f[threadIdx.x][0]); pf[threadIdx.x][1] = met_load(&sc->f[threadIdx.x][1]); }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            ts = ta = 0.0;
-            for (unsigned b = 0; b < gridDim.x; ++b) { ts += pf[b][0]; ta += pf[b][1]; }
-            __hip_atomic_store(&sc->ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-    if (threadIdx.x == 0) {
-        if (batch) {      // the sums, then the step's published values: MSE, RMSE, L1 (gnnLightning.py:124-130)
-            batch[0] = ts; batch[1] = ta; batch[2] = (double)n; batch[3] = ts / (double)n; batch[4] = sqrt(ts / (double)n); batch[5] = ta / (double)n;
-            batch[6] = batch[7] = 0.0;
-        }
-        if (epoch) { epoch[0] += ts; epoch[1] += ta; epoch[2] += (double)n; }
-    }
-}
-
-// classification (gnnLightning.py:132-151, 285-348): logits [B*4][2], labels [B][4] in {0,1}.
-//   ce_state[0] += sum of per-foot cross entropies, ce_state[1] += 4 B                      (customMetrics.py:17-24)
-//   counts[0] += B, counts[1] += windows whose 16-class argmax equals the label state       (Accuracy, 16 classes)
-//   counts[2 + 4 k + {0,1,2,3}] += tp, fp, fn, tn of leg k                                   (BinaryF1Score)
-// The 16-class probabilities are the reference's products (p or 1 - p per foot, ((f0 f1)(f2 f3)), first maximum wins).
-// ce_b / counts_b (nullable): this step's sums, overwritten; ce_state / counts (nullable): added into; gout (nullable) [B*4][2] = d ce / d logits
-// = (softmax - onehot) / (4 B)
-template <int NT> __global__ __launch_bounds__(NT) void k_metrics_cls(const float* logits, const int32_t* y, int64_t B, double* ce_b, long long* counts_b,
-                                                             double* ce_state, long long* counts, float* gout, MetScratch* sc) {
-    __shared__ double rce[NT / 64];
-    __shared__ long long rc[NT / 64][MET_COUNTS], pc[MET_BLOCKS][MET_COUNTS];
-    __shared__ double pce[MET_BLOCKS];
-    __shared__ int s_last;
-    double ce = 0.0;
-    long long c[MET_COUNTS];
-#pragma unroll
-    for (int k = 0; k < MET_COUNTS; ++k) c[k] = 0;
-    for (int64_t w = (int64_t)blockIdx.x * NT + threadIdx.x; w < B; w += (int64_t)gridDim.x * NT) {
-        double p1[4];
-        int state = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const double l0 = (double)logits[(w * 4 + k) * 2], l1 = (double)logits[(w * 4 + k) * 2 + 1];
-            const double m = fmax(l0, l1), e0 = exp(l0 - m), e1 = exp(l1 - m), se = e0 + e1;
-            const int lab = y[w * 4 + k] != 0;
-            ce += (m + log(se)) - (lab ? l1 : l0);
-            const double p0 = e0 / se; p1[k] = e1 / se;
-            if (gout) {
-                const double inv = 1.0 / (double)(4 * B);
-                gout[(w * 4 + k) * 2] = (float)((p0 - (lab ? 0.0 : 1.0)) * inv);
-                gout[(w * 4 + k) * 2 + 1] = (float)((p1[k] - (lab ? 1.0 : 0.0)) * inv);
-            }
-            const int pred = p1[k] > p0 ? 1 : 0;             // argmax over (p0, p1): the first maximum wins
-            const int cell = pred ? (lab ? 0 : 1) : (lab ? 2 : 3);      // tp, fp, fn, tn -- added by compare, not by a run-time index (the counters stay in registers)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) c[2 + 4 * k + j] += (cell == j);
-            state = state * 2 + lab;
-        }
-        int best = 0; double bestv = -1.0;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const double f0 = (j & 8) ? p1[0] : 1.0 - p1[0], f1 = (j & 4) ? p1[1] : 1.0 - p1[1];
-            const double f2 = (j & 2) ? p1[2] : 1.0 - p1[2], f3 = (j & 1) ? p1[3] : 1.0 - p1[3];
-            const double v = (f0 * f1) * (f2 * f3);
-            if (v > bestv) { bestv = v; best = j; }
-        }
-        c[0] += 1; c[1] += (best == state);
-    }
-    ce = wave_sum(ce);
-#pragma unroll
-    for (int k = 0; k < MET_COUNTS; ++k) c[k] = wave_sum(c[k]);
-    if ((threadIdx.x & 63) == 0) {
-        rce[threadIdx.x >> 6] = ce;
-#pragma unroll
-        for (int k = 0; k < MET_COUNTS; ++k) rc[threadIdx.x >> 6][k] = c[k];
-    }
-    __syncthreads();
-    // this workgroup's sums: thread 0 the cross entropy, threads 0..17 one count each
-    double tce = 0.0; long long tc = 0;
-    if (threadIdx.x == 0) for (int k = 0; k < NT / 64; ++k) tce += rce[k];
-    if (threadIdx.x < MET_COUNTS) for (int k = 0; k < NT / 64; ++k) tc += rc[k][threadIdx.x];
-    if (sc) {
-        if (threadIdx.x == 0) met_store(&sc->f[blockIdx.x][0], tce);
-        if (threadIdx.x < MET_COUNTS) met_store(&sc->c[blockIdx.x][threadIdx.x], tc);
-        __syncthreads();                                    // every partial of this workgroup is stored before thread 0 takes the ticket
-        if (threadIdx.x == 0) s_last = met_last_block(sc) ? 1 : 0;
-        __syncthreads();
-        if (!s_last) return;
-        __atomic_thread_fence(__ATOMIC_ACQUIRE);
-        // the last workgroup: thread b fetches workgroup b's partials (all loads in flight at once), then one thread per sum adds them in workgroup order
-        if (threadIdx.x < gridDim.x) {
-            pce[threadIdx.x] = met_load(&sc->f[threadIdx.x][0]);
-#pragma unroll
-            for (int k = 0; k < MET_COUNTS; ++k) pc[threadIdx.x][k] = met_load(&sc->c[threadIdx.x][k]);
-        }
-        __syncthreads();
-        tce = 0.0; tc = 0;
-        if (threadIdx.x == 0) for (unsigned b = 0; b < gridDim.x; ++b) tce += pce[b];
-        if (threadIdx.x < MET_COUNTS) for (unsigned b = 0; b < gridDim.x; ++b) tc += pc[b][threadIdx.x];
-        if (threadIdx.x == 0) __hip_atomic_store(&sc->ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    if (threadIdx.x == 0) {
-        if (ce_b) { ce_b[0] = tce; ce_b[1] = (double)(4 * B); ce_b[2] = (double)(float)tce / (double)(4 * B); }      // [2]: this step's CE, `summed_loss.float() / total_num` (customMetrics.py:24)
-        if (ce_state) { ce_state[0] += tce; ce_state[1] += (double)(4 * B); }
-    }
-    if (threadIdx.x < MET_COUNTS) {
-        if (counts_b) counts_b[threadIdx.x] = tc;
-        if (counts) counts[threadIdx.x] += tc;
-        if (ce_b) pc[0][threadIdx.x] = tc;                  // (pc: free again -- every partial has been added)
-    }
-    if (ce_b) {      // the step's published values next to its sums: [3] 16-class accuracy, [4..7] F1 of leg 0..3 (customMetrics.py:51-54, 0/0 -> 0)
-        __syncthreads();
-        if (threadIdx.x == 0) ce_b[3] = (double)pc[0][1] / (double)pc[0][0];
-        if (threadIdx.x >= 1 && threadIdx.x <= 4) {
-            const int k = threadIdx.x - 1;
-            const double tp = (double)pc[0][2 + 4 * k], fp = (double)pc[0][3 + 4 * k], fn = (double)pc[0][4 + 4 * k];
-            const double precision = tp / (tp + fp), recall = tp / (tp + fn);
-            const double f1 = 2.0 * (precision * recall) / (precision + recall);
-            ce_b[4 + k] = f1 != f1 ? 0.0 : f1;
-        }
-    }
-}
-
-// centroidal-momentum wrappers (gnnLightning_com.py:96-121): y / y_pred [B][nb][6] = per base node (lin(3) | ang(3)), standardised.
-//   state[0] += sum sq err of the lin halves, [1] += of the ang halves, [2] += 3 nb B, [3] += 3 nb B,
-//   [4] += sum over windows of cos(lin_pred, lin) of base node 0 after un-standardising (v * y_std + y_mean), [5] += the same for ang,
-//   [6] += B.  Cosine similarity as torch.nn.CosineSimilarity(dim=1, eps=1e-8): sum (a / max(|a|, eps)) (b / max(|b|, eps))
-//   (customMetrics.py:56-95).  One thread per window; multi-workgroup with the ticket scheme above.
-struct MetScratchCom { unsigned int ticket, pad; double f[MET_BLOCKS][4]; };
-static_assert(sizeof(MetScratchCom) <= MSHGNN_METRICS_SCRATCH_BYTES, "include/mshgnn.h promises this scratch size");
-struct ComStats { double mean[6], std[6]; };
-
-__global__ __launch_bounds__(MET_THREADS) void k_metrics_com(const float* pred, const float* y, int64_t B, int nb, ComStats st, double* batch, double* epoch,
-                                                             MetScratchCom* sc) {
-    __shared__ double r[MET_THREADS / 64][4], pf[MET_BLOCKS][4];
-    __shared__ int s_last;
-    double a[4] = {0.0, 0.0, 0.0, 0.0};      // sq lin, sq ang, cos lin, cos ang
-    for (int64_t w = (int64_t)blockIdx.x * MET_THREADS + threadIdx.x; w < B; w += (int64_t)gridDim.x * MET_THREADS) {
-        for (int b = 0; b < nb; ++b)
-#pragma unroll
-            for (int k = 0; k < 6; ++k) {
-                const double d = (double)pred[(w * nb + b) * 6 + k] - (double)y[(w * nb + b) * 6 + k];
-                a[k < 3 ? 0 : 1] += d * d;
-            }
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            double pp = 0.0, yy = 0.0, py = 0.0, pv[3], yv[3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                pv[k] = (double)pred[w * nb * 6 + 3 * h + k] * st.std[3 * h + k] + st.mean[3 * h + k];
-                yv[k] = (double)y[w * nb * 6 + 3 * h + k] * st.std[3 * h + k] + st.mean[3 * h + k];
-                pp += pv[k] * pv[k]; yy += yv[k] * yv[k];
-            }
-            const double pn = fmax(sqrt(pp), 1e-8), yn = fmax(sqrt(yy), 1e-8);
-#pragma unroll
-            for (int k = 0; k < 3; ++k) py += (pv[k] / pn) * (yv[k] / yn);
-            a[2 + h] += py;
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) a[k] = wave_sum(a[k]);
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) r[threadIdx.x >> 6][k] = a[k];
-    __syncthreads();
-    double t[4] = {0.0, 0.0, 0.0, 0.0};
-    if (threadIdx.x == 0) {
-        for (int v = 0; v < MET_THREADS / 64; ++v)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) t[k] += r[v][k];
-        if (sc)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) met_store(&sc->f[blockIdx.x][k], t[k]);
-        s_last = 1;
-        if (sc) {
-            __atomic_thread_fence(__ATOMIC_RELEASE);
-            const unsigned int tk = __hip_atomic_fetch_add(&sc->ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-            s_last = tk == gridDim.x - 1;
-        }
-    }
-    if (sc) {
-        __syncthreads();
-        if (!s_last) return;
-        __atomic_thread_fence(__ATOMIC_ACQUIRE);
-        if (threadIdx.x < gridDim.x)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) pf[threadIdx.x][k] = met_load(&sc->f[threadIdx.x][k]);
-        __syncthreads();
-        if (threadIdx.x == 0) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) t[k] = 0.0;
-            for (unsigned b = 0; b < gridDim.x; ++b)
-#pragma unroll
-                for (int k = 0; k < 4; ++k) t[k] += pf[b][k];
-            __hip_atomic_store(&sc->ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-    if (threadIdx.x == 0) {
-        const double n3 = 3.0 * (double)nb * (double)B;
-        const double v[8] = {t[0], t[1], n3, n3, t[2], t[3], (double)B, 0.0};
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            if (batch) batch[k] = v[k];
-            if (epoch) epoch[k] += v[k];
-        }
-    }
-}
-
-// GRF body frame -> world frame (gnnLightning.py:663-676): quat = world->body rotation, scalar-last (x, y, z, w) as scipy's
-// Rotation.from_quat takes it (normalised here as scipy does); world = R(quat)^-1 f for each of the 4 feet.
-__global__ void k_grf_to_world(const float* quat, const float* body, float* world, int64_t B) {
-    const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (w >= B) return;
-    double x = quat[w * 4], yq = quat[w * 4 + 1], z = quat[w * 4 + 2], s = quat[w * 4 + 3];
-    const double nrm = sqrt(x * x + yq * yq + z * z + s * s);
-    x /= nrm; yq /= nrm; z /= nrm; s /= nrm;
-    // R = matrix of the unit quaternion; its inverse is the transpose
-    const double R[3][3] = {{1 - 2 * (yq * yq + z * z), 2 * (x * yq - z * s), 2 * (x * z + yq * s)},
-                            {2 * (x * yq + z * s), 1 - 2 * (x * x + z * z), 2 * (yq * z - x * s)},
-                            {2 * (x * z - yq * s), 2 * (yq * z + x * s), 1 - 2 * (x * x + yq * yq)}};
-    for (int f = 0; f < 4; ++f) {
-        const double b0 = body[w * 12 + f * 3], b1 = body[w * 12 + f * 3 + 1], b2 = body[w * 12 + f * 3 + 2];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) world[w * 12 + f * 3 + i] = (float)(R[0][i] * b0 + R[1][i] * b1 + R[2][i] * b2);
-    }
-}
-
-static int met_blocks(int64_t items, int per_thread) {
-    return (int)std::max<int64_t>(1, std::min<int64_t>(MET_BLOCKS, (items + per_thread * MET_THREADS - 1) / (per_thread * MET_THREADS)));
-}
-
-extern "C" int mshgnn_metrics_regression(const float* y_pred, const float* y, int64_t n, double* state, void* stream) {
-    if (!y_pred || !y || !state || n < 1) return set_err(MSHGNN_EINVAL, "bad argument to mshgnn_metrics_regression");
-    hipLaunchKernelGGL(k_metrics_reg<1024>, dim3(1), dim3(1024), 0, (hipStream_t)stream, y_pred, y, n, (double*)nullptr, state, (float*)nullptr, (MetScratch*)nullptr);
-    HIPCHK(hipGetLastError());
-    return MSHGNN_OK;
-}
-
-extern "C" int mshgnn_metrics_regression_step(const float* y_pred, const float* y, int64_t n, double* batch_state, double* epoch_state, float* grad_out,
-                                              void* scratch, void* stream) {
-    if (!y_pred || !y || (!batch_state && !epoch_state) || !scratch || n < 1) return set_err(MSHGNN_EINVAL, "bad argument to mshgnn_metrics_regression_step");
-    hipLaunchKernelGGL(k_metrics_reg<MET_THREADS>, dim3(met_blocks(n, 16)), dim3(MET_THREADS), 0, (hipStream_t)stream, y_pred, y, n, batch_state, epoch_state, grad_out,
-                       reinterpret_cast<MetScratch*>(scratch));
-    HIPCHK(hipGetLastError());
-    return MSHGNN_OK;
-}
-
-extern "C" int mshgnn_metrics_classification(const float* logits, const int32_t* y, int64_t batch, double* ce_state, int64_t* counts, void* stream) {
-    if (!logits || !y || !ce_state || !counts || batch < 1) return set_err(MSHGNN_EINVAL, "bad argument to mshgnn_metrics_classification");
-    hipLaunchKernelGGL(k_metrics_cls<1024>, dim3(1), dim3(1024), 0, (hipStream_t)stream, logits, y, batch, (double*)nullptr, (long long*)nullptr, ce_state,
-                       reinterpret_cast<long long*>(counts), (float*)nullptr, (MetScratch*)nullptr);
-    HIPCHK(hipGetLastError());
-    return MSHGNN_OK;
-}
-
-extern "C" int mshgnn_metrics_classification_step(const float* logits, const int32_t* y, int64_t batch, double* batch_ce, int64_t* batch_counts,
-                                                  double* epoch_ce, int64_t* epoch_counts, float* grad_out, void* scratch, void* stream) {
-    if (!logits || !y || batch < 1 || !scratch || (!batch_ce != !batch_counts) || (!epoch_ce != !epoch_counts) || (!batch_ce && !epoch_ce))
-        return set_err(MSHGNN_EINVAL, "bad argument to mshgnn_metrics_classification_step");
-    hipLaunchKernelGGL(k_metrics_cls<MET_THREADS>, dim3(met_blocks(batch, 1)), dim3(MET_THREADS), 0, (hipStream_t)stream, logits, y, batch, batch_ce,
-                       reinterpret_cast<long long*>(batch_counts), epoch_ce, reinterpret_cast<long long*>(epoch_counts), grad_out,
-                       reinterpret_cast<MetScratch*>(scratch));
-    HIPCHK(hipGetLastError());
-    return MSHGNN_OK;
-}
-
-extern "C" int mshgnn_metrics_com_step(const float* y_pred, const float* y, int64_t batch, int n_bases, const double* y_mean, const double* y_std,
-                                       double* batch_state, double* epoch_state, void* scratch, void* stream) {
-    if (!y_pred || !y || !y_mean || !y_std || batch < 1 || n_bases < 1 || !scratch || (!batch_state && !epoch_state))
-        return set_err(MSHGNN_EINVAL, "bad argument to mshgnn_metrics_com_step");
-    ComStats st;
-    for (int k = 0; k < 6; ++k) { st.mean[k] = y_mean[k]; st.std[k] = y_std[k]; }
-    hipLaunchKernelGGL(k_metrics_com, dim3(met_blocks(batch, 1)), dim3(MET_THREADS), 0, (hipStream_t)stream, y_pred, y, batch, n_bases, st, batch_state,
-                       epoch_state, reinterpret_cast<MetScratchCom*>(scratch));
-    HIPCHK(hipGetLastError());
-    return MSHGNN_OK;
-}
-
-extern "C" int mshgnn_grf_body_to_world(const float* quat, const float* grf_body, float* grf_world, int64_t batch, void* stream) {
-    if (!quat || !grf_body || !grf_world || batch < 1) return set_err(MSHGNN_EINVAL, "bad argument to mshgnn_grf_body_to_world");
-    hipLaunchKernelGGL(k_grf_to_world, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, (hipStream_t)stream, quat, grf_body, grf_world, batch);
-    HIPCHK(hipGetLastError());
-    return MSHGNN_OK;
-}
-
-// ------------------------------------------------------------------------------------------------------
-// On-device window assembly: the raw time series of a sequence stay in HBM and a batch of
-// windows [start, start + T) is gathered straight into the engine's input layout [B][n_t][pitch] at the plan dtype --
-// what the reference does per window in Python (quadSDKDataset_Morph.py:304-369: axis-major flatten('F') of each
-// variable, joint re-ordering, base tiling, all-ones feet) followed by PyG's collate.
-// One wave per RUN = T consecutive features of one node row: feature f0 + t = src[start + t][col] (optionally
-// standardised over the window like flexibleDataset.py:390-396), or the constant 1.
-// ------------------------------------------------------------------------------------------------------
-constexpr int WIN_MAX_SRC = 12;
-constexpr int WIN_ROW_RUNS = 8;          // runs per node row handled with all loads in flight
-struct WindowArgs {
-    const float* src[WIN_MAX_SRC]; int64_t src_cstride[WIN_MAX_SRC];       // series are COLUMN-major: element (row, col) at col * cstride + row
-    void* x[MSHGNN_MAX_TYPES]; int64_t x_pitch[MSHGNN_MAX_TYPES]; int nodes[MSHGNN_MAX_TYPES];
-    const int* runs; int n_runs;            // per run: type, node, first feature, source (-1: ones) << 8 | column, length; sorted by (type, node)
-    const int* rows; int n_rows;            // per node row: first run, end run
-    const int64_t* starts; int64_t B; int T, normalize;
-    const int* label_cols; int n_label, label_src, label_rotate, quat_src;
-    float* y; float* quat;
-};
-
-// one WORKGROUP per window, its 4 waves take the node rows round-robin.  Lane r resolves run r ONCE (source pointer, destination
-// offset, length) and the waves fetch those with v_readlane, so there is no dependent descriptor load per run; every run
-// of a row is a contiguous stretch of a column-major series, read coalesced with all of the row's loads in flight.
-template <typename T, int NSET> __global__ __launch_bounds__(256) void k_assemble_windows(WindowArgs a) {
-    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t b = blockIdx.x;
-    const int64_t start = a.starts[b];
-    // lane r & 63 of register set r >> 6 <- run r (n_runs <= 64 NSET, checked by the host)
-    int v_lo[NSET], v_hi[NSET], v_doff[NSET], v_len[NSET], v_t[NSET];
-#pragma unroll
-    for (int set = 0; set < NSET; ++set) {
-        const int* run = a.runs + (size_t)min(lane + 64 * set, a.n_runs - 1) * 5;
-        const int t = run[0], node = run[1], f0 = run[2], sc = run[3];
-        const float* sp = nullptr;
-#pragma unroll
-        for (int k = 0; k < WIN_MAX_SRC; ++k) if (sc >= 0 && (sc >> 8) == k) sp = a.src[k] + (size_t)(sc & 0xff) * a.src_cstride[k] + start;
-        int nodes = 0; int64_t pitch = 0;
-#pragma unroll
-        for (int k = 0; k < MSHGNN_MAX_TYPES; ++k) if (t == k) { nodes = a.nodes[k]; pitch = a.x_pitch[k]; }
-        v_lo[set] = (int)((uintptr_t)sp & 0xffffffffu); v_hi[set] = (int)((uintptr_t)sp >> 32);
-        v_doff[set] = (int)(((size_t)b * nodes + node) * pitch + f0 - (size_t)b * nodes * pitch);     // offset inside the window's block of this type
-        v_len[set] = run[4]; v_t[set] = t;
-    }
-    auto rl = [&](const int (&v)[NSET], int r) {
-        if constexpr (NSET == 1) return __builtin_amdgcn_readlane(v[0], r);
-        else return r < 64 ? __builtin_amdgcn_readlane(v[0], r & 63) : __builtin_amdgcn_readlane(v[NSET - 1], r & 63);
-    };
-    // lane handles the element pairs (2 lane + 128 j, +1), j = 0, 1: one packed store per pair (runs start at even features
-    // and node rows are 16-byte aligned, so pairs are 4-byte (bf16) / 8-byte (fp32) aligned); lengths up to 256
-    for (int row = wv; row < a.n_rows; row += 4) {
-        const int r_begin = a.rows[2 * row], r_end = a.rows[2 * row + 1];
-        for (int rb = r_begin; rb < r_end; rb += WIN_ROW_RUNS) {
-            float v[WIN_ROW_RUNS][4];
-#pragma unroll
-            for (int i = 0; i < WIN_ROW_RUNS; ++i) {
-                const int r = min(rb + i, r_end - 1);
-                const float* sp = reinterpret_cast<const float*>((uintptr_t)(unsigned)rl(v_lo, r) | ((uintptr_t)(unsigned)rl(v_hi, r) << 32));
-                const int len = rl(v_len, r);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int k = 2 * lane + 128 * (q >> 1) + (q & 1);
-                    v[i][q] = 1.0f;
-                    if (rb + i < r_end && sp != nullptr && k < len) v[i][q] = sp[k];
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < WIN_ROW_RUNS; ++i) {
-                if (rb + i >= r_end) break;
-                const int r = rb + i;
-                const int t = rl(v_t, r), len = rl(v_len, r), doff = rl(v_doff, r);
-                const bool has_src = (rl(v_lo, r) | rl(v_hi, r)) != 0;
-                T* dst = reinterpret_cast<T*>(a.x[t]) + (size_t)b * a.nodes[t] * a.x_pitch[t] + doff;
-                if (a.normalize && has_src) {
-                    // (x - mean) / std with the unbiased estimator, NaN -> 0 (flexibleDataset.py:390-396); fp64, two passes over registers.  The arithmetic
-                    // is run_stats / standardise_one (mshgnn_device.hpp), shared with the standardising series encoders of mshgnn_forward_series
-                    const RunStats rs = run_stats(v[i], len, lane);
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) v[i][q] = standardise_one(v[i][q], rs.mean, rs.sd);
-                }
-                const bool even = ((doff | len) & 1) == 0;
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    const int k = 2 * lane + 128 * j;
-                    if (even && k < len) {
-                        if constexpr (sizeof(T) == 2) {
-                            union { unsigned u; __bf16 e[2]; } pk; pk.e[0] = (__bf16)v[i][2 * j]; pk.e[1] = (__bf16)v[i][2 * j + 1];
-                            *reinterpret_cast<unsigned*>(dst + k) = pk.u;
-                        } else *reinterpret_cast<f32x2*>(dst + k) = f32x2{v[i][2 * j], v[i][2 * j + 1]};
-                    } else {
-                        if (k < len) dst[k] = from_f32<T>(v[i][2 * j]);
-                        if (k + 1 < len) dst[k + 1] = from_f32<T>(v[i][2 * j + 1]);
-                    }
-                }
-            }
-        }
-    }
-}
-
-// Fast path of the same gather (no standardisation, 16-byte aligned output rows whose runs all have one length -- what SequenceStore builds):
-// a thread owns one 16-BYTE CHUNK of one node row -- EPC consecutive features, which live in at most two runs of that length -- gathers them
-// with EPC scalar loads (consecutive lanes read consecutive elements of a column-major series) and writes ONE 16-byte store; all chunks of a
-// window are independent, so every load of the window is in flight at once.  The general kernel above writes 4 bytes per lane and walks a row's
-// runs in turn: 0.12 ms for 8192 A1 windows against 0.03-0.04 ms here.  Pad columns inside a row's last chunk are written as zeros.
-constexpr int WIN_MAX_ROWS = 64, WIN_MAX_RUNS = 128;
-template <typename T> __global__ __launch_bounds__(256) void k_assemble_windows_fast(WindowArgs a) {
-    constexpr int EPC = 16 / (int)sizeof(T);
-    __shared__ unsigned long long s_src[WIN_MAX_RUNS];                    // source pointer of run r at this window's first step (0: the constant 1)
-    __shared__ int s_first[WIN_MAX_ROWS + 1];                             // chunk prefix per node row
-    __shared__ int s_run0[WIN_MAX_ROWS], s_len[WIN_MAX_ROWS], s_width[WIN_MAX_ROWS];
-    __shared__ unsigned long long s_dst[WIN_MAX_ROWS];                    // destination of the row's first element
-    const int tid = threadIdx.x;
-    const int64_t b = blockIdx.x, start = a.starts[b];
-    if (tid < a.n_runs) {
-        const int sc = a.runs[(size_t)tid * 5 + 3];
-        const float* sp = nullptr;
-#pragma unroll
-        for (int k = 0; k < WIN_MAX_SRC; ++k) if (sc >= 0 && (sc >> 8) == k) sp = a.src[k] + (size_t)(sc & 0xff) * a.src_cstride[k] + start;
-        s_src[tid] = (unsigned long long)sp;
-    }
-    if (tid < a.n_rows) {
-        const int r0 = a.rows[2 * tid], r1 = a.rows[2 * tid + 1];
-        const int* run = a.runs + (size_t)r0 * 5;
-        const int t = run[0], node = run[1], len = run[4];
-        int nodes = 0; int64_t pitch = 0; char* xb = nullptr;
-#pragma unroll
-        for (int k = 0; k < MSHGNN_MAX_TYPES; ++k) if (t == k) { nodes = a.nodes[k]; pitch = a.x_pitch[k]; xb = reinterpret_cast<char*>(a.x[k]); }
-        s_run0[tid] = r0; s_len[tid] = len; s_width[tid] = (r1 - r0) * len;
-        s_dst[tid] = (unsigned long long)(xb + (((size_t)b * nodes + node) * pitch + run[2]) * sizeof(T));
-    }
-    __syncthreads();
-    if (tid == 0) {
-        int acc = 0;
-        for (int r = 0; r < a.n_rows; ++r) { s_first[r] = acc; acc += (s_width[r] + EPC - 1) / EPC; }
-        s_first[a.n_rows] = acc;
-    }
-    __syncthreads();
-    const int total = s_first[a.n_rows];
-    int row = 0;
-    for (int task = tid; task < total; task += 256) {
-        while (task >= s_first[row + 1]) ++row;                            // (tasks of a thread ascend)
-        const int j = task - s_first[row], len = s_len[row], width = s_width[row];
-        const int k0 = j * EPC;
-        int run = s_run0[row] + k0 / len, off = k0 % len;
-        float v[EPC];
-#pragma unroll
-        for (int e = 0; e < EPC; ++e) {
-            v[e] = 0.f;
-            if (k0 + e < width) {
-                const float* sp = reinterpret_cast<const float*>(s_src[run]);
-                v[e] = sp ? sp[off] : 1.0f;
-            }
-            if (++off == len) { off = 0; ++run; }
-        }
-        T* dst = reinterpret_cast<T*>(s_dst[row]) + k0;
-        if constexpr (sizeof(T) == 2) {
-            union { u32x4 u; __bf16 e[8]; } pk;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) pk.e[e] = (__bf16)v[e];
-            *reinterpret_cast<u32x4*>(dst) = pk.u;
-        } else *reinterpret_cast<f32x4*>(dst) = f32x4{v[0], v[1], v[2], v[3]};
-    }
-}
-
-// labels of a window = the label row of its LAST time step (quadSDKDataset.py: grfs[-1]); with label_rotate the world-frame
-// GRFs are taken into the body frame with the world->body quaternion of that step, R f per foot (the as_matrix() @ grfs_T
-// branch of load_data_at_dataset_seq_3d); quat out = that quaternion (data.r_o, quadSDKDataset_Morph.py:365-367)
-// (window_labels_one itself lives in mshgnn_device.hpp: the fused-gather encoders run it in extra workgroups of their own launch)
-__device__ __forceinline__ LabelArgs label_args_of(const WindowArgs& a, int32_t* labels_int) {
-    LabelArgs l{};
-    l.lab = a.src[a.label_src]; l.lab_cs = a.src_cstride[a.label_src];
-    l.quat_src = a.quat_src >= 0 ? a.src[a.quat_src] : nullptr; l.quat_cs = a.quat_src >= 0 ? a.src_cstride[a.quat_src] : 0;
-    l.starts = a.starts; l.B = a.B; l.T = a.T; l.label_cols = a.label_cols; l.n_label = a.n_label; l.label_rotate = a.label_rotate;
-    l.y = a.y; l.quat = a.quat; l.labels_int = labels_int;
-    return l;
-}
-
-__global__ void k_window_labels(WindowArgs a) {
-    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < a.B) window_labels_one(label_args_of(a, nullptr), b);
-}
-
-extern "C" int mshgnn_assemble_windows(const mshgnn_window_desc* d, const float* const* src, const int64_t* src_cstride, const int64_t* src_rows,
-                                       const int64_t* starts, int64_t batch, void* const* x_out, const int64_t* x_pitch, float* y_out,
-                                       float* quat_out, void* stream) {
-    if (!d || !src || !src_cstride || !src_rows || !starts || !x_out || !x_pitch || batch < 1) return set_err(MSHGNN_EINVAL, "null argument to mshgnn_assemble_windows");
-    if (d->n_types < 1 || d->n_types > MSHGNN_MAX_TYPES || d->n_src < 1 || d->n_src > WIN_MAX_SRC || d->n_runs < 1 || !d->runs || d->n_rows < 1 || !d->rows)
-        return set_err(MSHGNN_EINVAL, "bad window descriptor");
-    if (d->history < 1 || (d->normalize && d->history < 2)) return set_err(MSHGNN_EINVAL, "history must be >= 1 (>= 2 when normalising)");
-    if (d->dtype != MSHGNN_F32 && d->dtype != MSHGNN_BF16 && d->dtype != MSHGNN_BF16X3) return set_err(MSHGNN_EINVAL, "dtype must be MSHGNN_F32, MSHGNN_BF16 or MSHGNN_BF16X3");
-    if (d->n_label > 0 && (!d->label_cols || !y_out || d->label_src < 0 || d->label_src >= d->n_src)) return set_err(MSHGNN_EINVAL, "bad label description");
-    if (d->label_rotate && (d->n_label % 3 != 0 || d->quat_src < 0)) return set_err(MSHGNN_EINVAL, "label rotation needs 3-D labels and a quaternion source");
-    if (d->quat_src >= d->n_src) return set_err(MSHGNN_EINVAL, "quat_src out of range");
-    WindowArgs a{};
-    for (int i = 0; i < d->n_src; ++i) {
-        if (!src[i] || src_cstride[i] < src_rows[i] || src_rows[i] < d->history) return set_err(MSHGNN_EINVAL, "bad source array");
-        a.src[i] = src[i]; a.src_cstride[i] = src_cstride[i];
-    }
-    for (int t = 0; t < d->n_types; ++t) {
-        if (!x_out[t] || d->type_nodes[t] < 1 || x_pitch[t] < d->type_width[t]) return set_err(MSHGNN_EINVAL, "bad output tensor");
-        a.x[t] = x_out[t]; a.x_pitch[t] = x_pitch[t]; a.nodes[t] = d->type_nodes[t];
-    }
-    if (d->history > 256) return set_err(MSHGNN_EUNSUPPORTED, "history longer than 256 steps is not supported by this build");
-    a.runs = d->runs; a.n_runs = d->n_runs; a.rows = d->rows; a.n_rows = d->n_rows; a.starts = starts; a.B = batch; a.T = d->history; a.normalize = d->normalize;
-    a.label_cols = d->label_cols; a.n_label = d->n_label; a.label_src = d->label_src; a.label_rotate = d->label_rotate; a.quat_src = d->quat_src;
-    a.y = y_out; a.quat = quat_out;
-    hipStream_t st = (hipStream_t)stream;
-    if (d->n_runs > 128) return set_err(MSHGNN_EUNSUPPORTED, "more than 128 feature runs per window are not supported by this build");
-    // fast path: no standardisation, every row's runs of one length starting at the row's first feature 0, 16-byte aligned rows whose pitch covers whole chunks
-    const bool f32 = d->dtype == MSHGNN_F32 || d->dtype == MSHGNN_BF16X3;      // the split plan takes fp32 inputs
-    bool fast = !d->normalize && d->n_rows <= WIN_MAX_ROWS && d->n_runs <= WIN_MAX_RUNS && d->fast_layout != 0;
-    for (int t = 0; t < d->n_types && fast; ++t) {
-        const int epc = f32 ? 4 : 8;
-        if (((uintptr_t)x_out[t] & 15) || x_pitch[t] % epc || x_pitch[t] < (d->type_width[t] + epc - 1) / epc * epc) fast = false;
-    }
-    if (fast) {
-        if (f32) hipLaunchKernelGGL(k_assemble_windows_fast<float>, dim3((unsigned)batch), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL(k_assemble_windows_fast<__bf16>, dim3((unsigned)batch), dim3(256), 0, st, a);
-    } else if (f32) {
-        if (d->n_runs <= 64) hipLaunchKernelGGL((k_assemble_windows<float, 1>), dim3((unsigned)batch), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((k_assemble_windows<float, 2>), dim3((unsigned)batch), dim3(256), 0, st, a);
-    } else {
-        if (d->n_runs <= 64) hipLaunchKernelGGL((k_assemble_windows<__bf16, 1>), dim3((unsigned)batch), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((k_assemble_windows<__bf16, 2>), dim3((unsigned)batch), dim3(256), 0, st, a);
-    }
-    if (d->n_label > 0 || (quat_out && d->quat_src >= 0))
-        hipLaunchKernelGGL(k_window_labels, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, st, a);
-    HIPCHK(hipGetLastError());
-    return MSHGNN_OK;
-}
-
-// ------------------------------------------------------------------------------------------------------
 // mshgnn_step_mse_series: one training step straight from a sequence's resident raw series -- the window gather of mshgnn_assemble_windows
 // fused into the encoder (k_enc_fwd<.., SERIES>), which also writes the materialised windows for the weight-gradient kernel; labels by
 // k_window_labels.  bf16 plan with the fused stack kernels; everything after the encoder is mshgnn_step_mse.
@@ -4129,4 +2704,3 @@ extern "C" int mshgnn_forward_series(const mshgnn_plan* p, const mshgnn_window_d
     c.series = &ser;
     return run_forward(p, c);
 }
-#endif      // MSHGNN_SPEC_SHARD == 0

@@ -1,5 +1,5 @@
 // Shared device helpers, argument structs and the plan object of libmshgnn (included by every .hip translation unit of the
-// library: mshgnn.hip = fp32 / bf16 plans + C-ABI, mshgnn_x3.hip = split-bf16 parity plan, mshgnn_gen.hip = generic-width engine).
+// library: mshgnn.hip = fp32 / bf16 plans + C-ABI (mshgnn_train_ops.hip, mshgnn_windows.hip: the entry points that read no plan), mshgnn_x3.hip = split-bf16 parity plan, mshgnn_gen.hip = generic-width engine).
 #pragma once
 #include <type_traits>
 #include <hip/hip_runtime.h>
@@ -453,6 +453,20 @@ struct SeriesSrc {
     LabelArgs lab;                       // the batch's labels: computed by extra workgroups of the fused-gather encoder launch (lab.B == 0: none)
     const double* stats;                 // standardised recipes (mshgnn_forward_series): {mean, sd} of every (window, run), [B][n_runs][2] (k_series_stats)
     int n_runs;
+};
+
+// The caller's sequence and windows as mshgnn_assemble_windows (mshgnn_windows.hip) gathers them; the series entry points (mshgnn.hip) fill the same structure
+// for their checks and for k_series_run_ptrs.
+constexpr int WIN_MAX_SRC = 12;
+constexpr int WIN_MAX_RUNS = 128;
+struct WindowArgs {
+    const float* src[WIN_MAX_SRC]; int64_t src_cstride[WIN_MAX_SRC];       // series are COLUMN-major: element (row, col) at col * cstride + row
+    void* x[MSHGNN_MAX_TYPES]; int64_t x_pitch[MSHGNN_MAX_TYPES]; int nodes[MSHGNN_MAX_TYPES];
+    const int* runs; int n_runs;            // per run: type, node, first feature, source (-1: ones) << 8 | column, length; sorted by (type, node)
+    const int* rows; int n_rows;            // per node row: first run, end run
+    const int64_t* starts; int64_t B; int T, normalize;
+    const int* label_cols; int n_label, label_src, label_rotate, quat_src;
+    float* y; float* quat;
 };
 
 // Per-window standardisation of one run (flexibleDataset.py:390-396): (x - mean) / sd with the unbiased estimator, in fp64, NaN -> 0.  THE arithmetic of
@@ -1481,6 +1495,12 @@ struct StepCall {
     int64_t total_windows() const { return chunk.total_windows ? chunk.total_windows : batch; }      // the windows the loss is a mean over
     int accumulates() const { return chunk.index > 0 ? 1 : 0; }                                      // sub-steps after the first add to the gradient and the loss
 };
+
+// The kernels over the compile-time programs (mshgnn_spec_tables.inc) live in translation units of their own, one program each: mshgnn_spec_shard.hip (bf16 plan) and
+// mshgnn_x3_spec_shard.hip (split plan), each compiled once per shard with -DMSHGNN_SPEC_SHARD=k.  The shard numbers, and the pasting that names shard k's selector and list:
+#define SPEC_SHARD_LIST(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7)      // one program per shard and plan (tools/gen_spec_tables.py SHARDS / X3_SHARDS; a split-plan step kernel compiles for 75-95 s)
+#define SPEC_CAT2(a, b) a##b
+#define SPEC_CAT(a, b) SPEC_CAT2(a, b)
 
 // k_finalize launch of a step (mshgnn.hip): fixed-order slab sums -> flat gradient (+ fused loss)
 int run_finalize(const mshgnn_plan* p, const StepCall& c, const mshgnn_ws_layout& lay, int gw_parts);

@@ -1,0 +1,487 @@
+// Plan-independent entry points of libmshgnn (include/mshgnn.h): what a training loop runs around the engine's step, kernels and entry points together --
+// Adam on the flat parameter buffer, the stand-alone MSE / cross-entropy losses, the step metrics of the Lightning wrappers and the GRF body -> world rotation.
+// None of it reads a plan; it shares only the error string with the rest of the library.
+#include "mshgnn_device.hpp"
+
+// ------------------------------------------------------------------------------------------------------
+// Adam on the flat fp32 buffers (configure_optimizers: optim.Adam(self.parameters(), lr), gnnLightning.py:258-265;
+// torch defaults beta=(0.9, 0.999), eps=1e-8, no weight decay, no amsgrad).  SURVEY.md section 8(f) row 2.
+// ------------------------------------------------------------------------------------------------------
+__global__ void k_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps,
+                       float bc1, float bc2_sqrt, float gscale) {
+    for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += (int64_t)gridDim.x * blockDim.x * 4) {
+        if (i + 4 <= n) {
+            f32x4 pp = *reinterpret_cast<f32x4*>(p + i), gg = *reinterpret_cast<const f32x4*>(g + i) * gscale;
+            f32x4 mm = *reinterpret_cast<f32x4*>(m + i), vv = *reinterpret_cast<f32x4*>(v + i);
+            mm = b1 * mm + (1.f - b1) * gg;
+            vv = b2 * vv + (1.f - b2) * gg * gg;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) pp[e] -= lr / bc1 * mm[e] / (sqrtf(vv[e]) / bc2_sqrt + eps);
+            *reinterpret_cast<f32x4*>(p + i) = pp; *reinterpret_cast<f32x4*>(m + i) = mm; *reinterpret_cast<f32x4*>(v + i) = vv;
+        } else {
+            for (int64_t k = i; k < n; ++k) {
+                const float gg = g[k] * gscale;
+                m[k] = b1 * m[k] + (1.f - b1) * gg; v[k] = b2 * v[k] + (1.f - b2) * gg * gg;
+                p[k] -= lr / bc1 * m[k] / (sqrtf(v[k]) / bc2_sqrt + eps);
+            }
+        }
+    }
+}
+
+extern "C" int mshgnn_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, int64_t step,
+                                float lr, float beta1, float beta2, float eps, float grad_scale, void* stream) {
+    if (!params || !grads || !exp_avg || !exp_avg_sq || n < 1 || step < 1) return set_err(MSHGNN_EINVAL, "bad argument to mshgnn_adam_step");
+    if (((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) return set_err(MSHGNN_EINVAL, "adam buffers must be 16-byte aligned");
+    const float bc1 = 1.0f - powf(beta1, (float)step), bc2 = 1.0f - powf(beta2, (float)step);
+    const int blocks = (int)std::min<int64_t>((n / 4 + 255) / 256 + 1, 2048);
+    hipLaunchKernelGGL(k_adam, dim3(blocks), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps,
+                       bc1, sqrtf(bc2), grad_scale);
+    HIPCHK(hipGetLastError());
+    return MSHGNN_OK;
+}
+
+// The same update with the step count on the DEVICE (capturable in a HIP graph: nothing of the bias corrections is baked into the launch arguments).  The kernel
+// reads t = *step_count + 1 and derives 1 - beta^t itself; a one-thread launch behind it stores t.  FlatAdam(graph_safe=True), wrappers.GraphedTrainingStep.
+__global__ void k_adam_counted(float* p, const float* g, float* m, float* v, int64_t n, const int64_t* step_count, float lr, float b1, float b2, float eps, float gscale) {
+    const float t = (float)(*step_count + 1);
+    const float bc1 = 1.0f - powf(b1, t), bc2_sqrt = sqrtf(1.0f - powf(b2, t));
+    for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += (int64_t)gridDim.x * blockDim.x * 4) {
+        if (i + 4 <= n) {
+            f32x4 pp = *reinterpret_cast<f32x4*>(p + i), gg = *reinterpret_cast<const f32x4*>(g + i) * gscale;
+            f32x4 mm = *reinterpret_cast<f32x4*>(m + i), vv = *reinterpret_cast<f32x4*>(v + i);
+            mm = b1 * mm + (1.f - b1) * gg;
+            vv = b2 * vv + (1.f - b2) * gg * gg;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) pp[e] -= lr / bc1 * mm[e] / (sqrtf(vv[e]) / bc2_sqrt + eps);
+            *reinterpret_cast<f32x4*>(p + i) = pp; *reinterpret_cast<f32x4*>(m + i) = mm; *reinterpret_cast<f32x4*>(v + i) = vv;
+        } else {
+            for (int64_t k = i; k < n; ++k) {
+                const float gg = g[k] * gscale;
+                m[k] = b1 * m[k] + (1.f - b1) * gg; v[k] = b2 * v[k] + (1.f - b2) * gg * gg;
+                p[k] -= lr / bc1 * m[k] / (sqrtf(v[k]) / bc2_sqrt + eps);
+            }
+        }
+    }
+}
+__global__ void k_step_count_inc(int64_t* step_count) { *step_count += 1; }
+
+extern "C" int mshgnn_adam_step_counted(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, int64_t* step_count,
+                                        float lr, float beta1, float beta2, float eps, float grad_scale, void* stream) {
+    if (!params || !grads || !exp_avg || !exp_avg_sq || !step_count || n < 1) return set_err(MSHGNN_EINVAL, "bad argument to mshgnn_adam_step_counted");
+    if (((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) return set_err(MSHGNN_EINVAL, "adam buffers must be 16-byte aligned");
+    const int blocks = (int)std::min<int64_t>((n / 4 + 255) / 256 + 1, 2048);
+    hipLaunchKernelGGL(k_adam_counted, dim3(blocks), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg, exp_avg_sq, n, step_count, lr, beta1, beta2, eps, grad_scale);
+    hipLaunchKernelGGL(k_step_count_inc, dim3(1), dim3(1), 0, (hipStream_t)stream, step_count);
+    HIPCHK(hipGetLastError());
+    return MSHGNN_OK;
+}
+
+__global__ void k_mse(const float* out, const float* y, int64_t n, float* loss, float* gout) {
+    __shared__ float red[4];
+    float s = 0.f;
+    const float inv = 1.0f / (float)n;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float dlt = out[i] - y[i];
+        s += dlt * dlt;
+        if (gout) gout[i] = 2.0f * dlt * inv;
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) atomicAdd(loss, (red[0] + red[1] + red[2] + red[3]) * inv);
+}
+
+extern "C" int mshgnn_mse_loss(const float* out, const float* y, int64_t n, float* loss_out, float* grad_out, void* stream) {
+    if (!out || !y || !loss_out || n < 1) return set_err(MSHGNN_EINVAL, "bad argument to mshgnn_mse_loss");
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(hipMemsetAsync(loss_out, 0, sizeof(float), st));
+    const int blocks = (int)std::min<int64_t>((n + 255) / 256, 1024);
+    hipLaunchKernelGGL(k_mse, dim3(blocks), dim3(256), 0, st, out, y, n, loss_out, grad_out);
+    HIPCHK(hipGetLastError());
+    return MSHGNN_OK;
+}
+
+// Stand-alone contact cross entropy of the classification wrappers (gnnLightning.py:640-648, customMetrics.py:6-25: CrossEntropyLoss over
+// the [rows, 2] per-foot logits, batch value = sum / rows) with its gradient (softmax - onehot) / rows.  One thread per row.
+__global__ void k_ce(const float* logits, const int32_t* labels, int64_t rows, float* loss, float* gout) {
+    __shared__ float red[4];
+    float s = 0.f;
+    const float inv = 1.0f / (float)rows;
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += (int64_t)gridDim.x * blockDim.x) {
+        const float l0 = logits[2 * r], l1 = logits[2 * r + 1];
+        const float m = fmaxf(l0, l1);
+        const float e0 = expf(l0 - m), e1 = expf(l1 - m), z = e0 + e1;
+        const int lab = labels[r] != 0;
+        s += logf(z) + m - (lab ? l1 : l0);
+        if (gout) {
+            gout[2 * r] = (e0 / z - (lab ? 0.f : 1.f)) * inv;
+            gout[2 * r + 1] = (e1 / z - (lab ? 1.f : 0.f)) * inv;
+        }
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) atomicAdd(loss, (red[0] + red[1] + red[2] + red[3]) * inv);
+}
+
+extern "C" int mshgnn_ce_loss(const float* logits, const int32_t* labels, int64_t rows, float* loss_out, float* grad_out, void* stream) {
+    if (!logits || !labels || !loss_out || rows < 1) return set_err(MSHGNN_EINVAL, "bad argument to mshgnn_ce_loss");
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(hipMemsetAsync(loss_out, 0, sizeof(float), st));
+    const int blocks = (int)std::min<int64_t>((rows + 255) / 256, 1024);
+    hipLaunchKernelGGL(k_ce, dim3(blocks), dim3(256), 0, st, logits, labels, rows, loss_out, grad_out);
+    HIPCHK(hipGetLastError());
+    return MSHGNN_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------
+// Step metrics of the Lightning wrappers, on device.  The reference keeps
+// torchmetrics states that are plain sums across steps (gnnLightning.py:52-63, customMetrics.py:11-54); these kernels
+// ADD one step's sums into caller-owned state buffers.  One workgroup, fixed reduction order: deterministic.
+// ------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+__device__ __forceinline__ long long wave_sum(long long v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+
+// Both kernels run on up to MET_BLOCKS workgroups: every workgroup leaves its partial sums in the caller's scratch, takes a ticket, and the
+// workgroup that draws the last ticket adds the partials IN INDEX ORDER (bit-reproducible whatever the arrival order) and resets the
+// ticket.  The one-workgroup entry points (mshgnn_metrics_regression / _classification, no scratch) run the same kernels with one block.
+constexpr int MET_COUNTS = 18, MET_BLOCKS = 64, MET_THREADS = 256;
+struct MetScratch {
+    unsigned int ticket, pad;
+    double f[MET_BLOCKS][2];
+    long long c[MET_BLOCKS][MET_COUNTS];
+};
+static_assert(sizeof(MetScratch) <= MSHGNN_METRICS_SCRATCH_BYTES, "include/mshgnn.h promises this scratch size");
+
+__device__ __forceinline__ void met_store(double* p, double v) { __hip_atomic_store(reinterpret_cast<long long*>(p), __double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ double met_load(const double* p) { return __longlong_as_double(__hip_atomic_load(reinterpret_cast<const long long*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)); }
+__device__ __forceinline__ void met_store(long long* p, long long v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ long long met_load(const long long* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// thread 0 of every workgroup, after its partials are stored: true in the workgroup that arrives last (sc == nullptr: a one-block launch)
+__device__ __forceinline__ bool met_last_block(MetScratch* sc) {
+    if (!sc) return true;
+    __atomic_thread_fence(__ATOMIC_RELEASE);        // (agent scope: the partials reach memory every XCD's L2 sees)
+    const unsigned int t = __hip_atomic_fetch_add(&sc->ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    if (t != gridDim.x - 1) return false;
+    __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    return true;
+}
+
+// regression (calculate_losses_step, gnnLightning.py:124-130): sums of (pred - y)^2, |pred - y| and n; `batch` (nullable) receives this
+// step's sums (overwritten), `epoch` (nullable) has them added; gout (nullable) = d mean((pred - y)^2) / d pred = 2 (pred - y) / n
+template <int NT> __global__ __launch_bounds__(NT) void k_metrics_reg(const float* pred, const float* y, int64_t n, double* batch, double* epoch, float* gout,
+                                                             MetScratch* sc) {
+    __shared__ double r0[NT / 64], r1[NT / 64], pf[MET_BLOCKS][2];
+    __shared__ int s_last;
+    double s = 0.0, a = 0.0;
+    const double inv2 = 2.0 / (double)n;
+    for (int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * NT) {
+        const double dlt = (double)pred[i] - (double)y[i];
+        s += dlt * dlt; a += fabs(dlt);
+        if (gout) gout[i] = (float)(dlt * inv2);
+    }
+    s = wave_sum(s); a = wave_sum(a);
+    if ((threadIdx.x & 63) == 0) { r0[threadIdx.x >> 6] = s; r1[threadIdx.x >> 6] = a; }
+    __syncthreads();
+    double ts = 0.0, ta = 0.0;
+    if (threadIdx.x == 0) {
+        for (int k = 0; k < NT / 64; ++k) { ts += r0[k]; ta += r1[k]; }
+        if (sc) { met_store(&sc->f[blockIdx.x][0], ts); met_store(&sc->f[blockIdx.x][1], ta); }
+        s_last = met_last_block(sc) ? 1 : 0;
+    }
+    if (sc) {
+        __syncthreads();
+        if (!s_last) return;
+        __atomic_thread_fence(__ATOMIC_ACQUIRE);
+        // the last workgroup: one partial per thread (all loads in flight at once), then thread 0 adds them in workgroup order
+        if (threadIdx.x < gridDim.x) { pf[threadIdx.x][0] = met_load(&sc->f[threadIdx.x][0]); pf[threadIdx.x][1] = met_load(&sc->f[threadIdx.x][1]); }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            ts = ta = 0.0;
+            for (unsigned b = 0; b < gridDim.x; ++b) { ts += pf[b][0]; ta += pf[b][1]; }
+            __hip_atomic_store(&sc->ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    if (threadIdx.x == 0) {
+        if (batch) {      // the sums, then the step's published values: MSE, RMSE, L1 (gnnLightning.py:124-130)
+            batch[0] = ts; batch[1] = ta; batch[2] = (double)n; batch[3] = ts / (double)n; batch[4] = sqrt(ts / (double)n); batch[5] = ta / (double)n;
+            batch[6] = batch[7] = 0.0;
+        }
+        if (epoch) { epoch[0] += ts; epoch[1] += ta; epoch[2] += (double)n; }
+    }
+}
+
+// classification (gnnLightning.py:132-151, 285-348): logits [B*4][2], labels [B][4] in {0,1}.
+//   ce_state[0] += sum of per-foot cross entropies, ce_state[1] += 4 B                      (customMetrics.py:17-24)
+//   counts[0] += B, counts[1] += windows whose 16-class argmax equals the label state       (Accuracy, 16 classes)
+//   counts[2 + 4 k + {0,1,2,3}] += tp, fp, fn, tn of leg k                                   (BinaryF1Score)
+// The 16-class probabilities are the reference's products (p or 1 - p per foot, ((f0 f1)(f2 f3)), first maximum wins).
+// ce_b / counts_b (nullable): this step's sums, overwritten; ce_state / counts (nullable): added into; gout (nullable) [B*4][2] = d ce / d logits
+// = (softmax - onehot) / (4 B)
+template <int NT> __global__ __launch_bounds__(NT) void k_metrics_cls(const float* logits, const int32_t* y, int64_t B, double* ce_b, long long* counts_b,
+                                                             double* ce_state, long long* counts, float* gout, MetScratch* sc) {
+    __shared__ double rce[NT / 64];
+    __shared__ long long rc[NT / 64][MET_COUNTS], pc[MET_BLOCKS][MET_COUNTS];
+    __shared__ double pce[MET_BLOCKS];
+    __shared__ int s_last;
+    double ce = 0.0;
+    long long c[MET_COUNTS];
+#pragma unroll
+    for (int k = 0; k < MET_COUNTS; ++k) c[k] = 0;
+    for (int64_t w = (int64_t)blockIdx.x * NT + threadIdx.x; w < B; w += (int64_t)gridDim.x * NT) {
+        double p1[4];
+        int state = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const double l0 = (double)logits[(w * 4 + k) * 2], l1 = (double)logits[(w * 4 + k) * 2 + 1];
+            const double m = fmax(l0, l1), e0 = exp(l0 - m), e1 = exp(l1 - m), se = e0 + e1;
+            const int lab = y[w * 4 + k] != 0;
+            ce += (m + log(se)) - (lab ? l1 : l0);
+            const double p0 = e0 / se; p1[k] = e1 / se;
+            if (gout) {
+                const double inv = 1.0 / (double)(4 * B);
+                gout[(w * 4 + k) * 2] = (float)((p0 - (lab ? 0.0 : 1.0)) * inv);
+                gout[(w * 4 + k) * 2 + 1] = (float)((p1[k] - (lab ? 1.0 : 0.0)) * inv);
+            }
+            const int pred = p1[k] > p0 ? 1 : 0;             // argmax over (p0, p1): the first maximum wins
+            const int cell = pred ? (lab ? 0 : 1) : (lab ? 2 : 3);      // tp, fp, fn, tn -- added by compare, not by a run-time index (the counters stay in registers)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) c[2 + 4 * k + j] += (cell == j);
+            state = state * 2 + lab;
+        }
+        int best = 0; double bestv = -1.0;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const double f0 = (j & 8) ? p1[0] : 1.0 - p1[0], f1 = (j & 4) ? p1[1] : 1.0 - p1[1];
+            const double f2 = (j & 2) ? p1[2] : 1.0 - p1[2], f3 = (j & 1) ? p1[3] : 1.0 - p1[3];
+            const double v = (f0 * f1) * (f2 * f3);
+            if (v > bestv) { bestv = v; best = j; }
+        }
+        c[0] += 1; c[1] += (best == state);
+    }
+    ce = wave_sum(ce);
+#pragma unroll
+    for (int k = 0; k < MET_COUNTS; ++k) c[k] = wave_sum(c[k]);
+    if ((threadIdx.x & 63) == 0) {
+        rce[threadIdx.x >> 6] = ce;
+#pragma unroll
+        for (int k = 0; k < MET_COUNTS; ++k) rc[threadIdx.x >> 6][k] = c[k];
+    }
+    __syncthreads();
+    // this workgroup's sums: thread 0 the cross entropy, threads 0..17 one count each
+    double tce = 0.0; long long tc = 0;
+    if (threadIdx.x == 0) for (int k = 0; k < NT / 64; ++k) tce += rce[k];
+    if (threadIdx.x < MET_COUNTS) for (int k = 0; k < NT / 64; ++k) tc += rc[k][threadIdx.x];
+    if (sc) {
+        if (threadIdx.x == 0) met_store(&sc->f[blockIdx.x][0], tce);
+        if (threadIdx.x < MET_COUNTS) met_store(&sc->c[blockIdx.x][threadIdx.x], tc);
+        __syncthreads();                                    // every partial of this workgroup is stored before thread 0 takes the ticket
+        if (threadIdx.x == 0) s_last = met_last_block(sc) ? 1 : 0;
+        __syncthreads();
+        if (!s_last) return;
+        __atomic_thread_fence(__ATOMIC_ACQUIRE);
+        // the last workgroup: thread b fetches workgroup b's partials (all loads in flight at once), then one thread per sum adds them in workgroup order
+        if (threadIdx.x < gridDim.x) {
+            pce[threadIdx.x] = met_load(&sc->f[threadIdx.x][0]);
+#pragma unroll
+            for (int k = 0; k < MET_COUNTS; ++k) pc[threadIdx.x][k] = met_load(&sc->c[threadIdx.x][k]);
+        }
+        __syncthreads();
+        tce = 0.0; tc = 0;
+        if (threadIdx.x == 0) for (unsigned b = 0; b < gridDim.x; ++b) tce += pce[b];
+        if (threadIdx.x < MET_COUNTS) for (unsigned b = 0; b < gridDim.x; ++b) tc += pc[b][threadIdx.x];
+        if (threadIdx.x == 0) __hip_atomic_store(&sc->ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (threadIdx.x == 0) {
+        if (ce_b) { ce_b[0] = tce; ce_b[1] = (double)(4 * B); ce_b[2] = (double)(float)tce / (double)(4 * B); }      // [2]: this step's CE, `summed_loss.float() / total_num` (customMetrics.py:24)
+        if (ce_state) { ce_state[0] += tce; ce_state[1] += (double)(4 * B); }
+    }
+    if (threadIdx.x < MET_COUNTS) {
+        if (counts_b) counts_b[threadIdx.x] = tc;
+        if (counts) counts[threadIdx.x] += tc;
+        if (ce_b) pc[0][threadIdx.x] = tc;                  // (pc: free again -- every partial has been added)
+    }
+    if (ce_b) {      // the step's published values next to its sums: [3] 16-class accuracy, [4..7] F1 of leg 0..3 (customMetrics.py:51-54, 0/0 -> 0)
+        __syncthreads();
+        if (threadIdx.x == 0) ce_b[3] = (double)pc[0][1] / (double)pc[0][0];
+        if (threadIdx.x >= 1 && threadIdx.x <= 4) {
+            const int k = threadIdx.x - 1;
+            const double tp = (double)pc[0][2 + 4 * k], fp = (double)pc[0][3 + 4 * k], fn = (double)pc[0][4 + 4 * k];
+            const double precision = tp / (tp + fp), recall = tp / (tp + fn);
+            const double f1 = 2.0 * (precision * recall) / (precision + recall);
+            ce_b[4 + k] = f1 != f1 ? 0.0 : f1;
+        }
+    }
+}
+
+// centroidal-momentum wrappers (gnnLightning_com.py:96-121): y / y_pred [B][nb][6] = per base node (lin(3) | ang(3)), standardised.
+//   state[0] += sum sq err of the lin halves, [1] += of the ang halves, [2] += 3 nb B, [3] += 3 nb B,
+//   [4] += sum over windows of cos(lin_pred, lin) of base node 0 after un-standardising (v * y_std + y_mean), [5] += the same for ang,
+//   [6] += B.  Cosine similarity as torch.nn.CosineSimilarity(dim=1, eps=1e-8): sum (a / max(|a|, eps)) (b / max(|b|, eps))
+//   (customMetrics.py:56-95).  One thread per window; multi-workgroup with the ticket scheme above.
+struct MetScratchCom { unsigned int ticket, pad; double f[MET_BLOCKS][4]; };
+static_assert(sizeof(MetScratchCom) <= MSHGNN_METRICS_SCRATCH_BYTES, "include/mshgnn.h promises this scratch size");
+struct ComStats { double mean[6], std[6]; };
+
+__global__ __launch_bounds__(MET_THREADS) void k_metrics_com(const float* pred, const float* y, int64_t B, int nb, ComStats st, double* batch, double* epoch,
+                                                             MetScratchCom* sc) {
+    __shared__ double r[MET_THREADS / 64][4], pf[MET_BLOCKS][4];
+    __shared__ int s_last;
+    double a[4] = {0.0, 0.0, 0.0, 0.0};      // sq lin, sq ang, cos lin, cos ang
+    for (int64_t w = (int64_t)blockIdx.x * MET_THREADS + threadIdx.x; w < B; w += (int64_t)gridDim.x * MET_THREADS) {
+        for (int b = 0; b < nb; ++b)
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+                const double d = (double)pred[(w * nb + b) * 6 + k] - (double)y[(w * nb + b) * 6 + k];
+                a[k < 3 ? 0 : 1] += d * d;
+            }
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            double pp = 0.0, yy = 0.0, py = 0.0, pv[3], yv[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                pv[k] = (double)pred[w * nb * 6 + 3 * h + k] * st.std[3 * h + k] + st.mean[3 * h + k];
+                yv[k] = (double)y[w * nb * 6 + 3 * h + k] * st.std[3 * h + k] + st.mean[3 * h + k];
+                pp += pv[k] * pv[k]; yy += yv[k] * yv[k];
+            }
+            const double pn = fmax(sqrt(pp), 1e-8), yn = fmax(sqrt(yy), 1e-8);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) py += (pv[k] / pn) * (yv[k] / yn);
+            a[2 + h] += py;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) a[k] = wave_sum(a[k]);
+    if ((threadIdx.x & 63) == 0)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) r[threadIdx.x >> 6][k] = a[k];
+    __syncthreads();
+    double t[4] = {0.0, 0.0, 0.0, 0.0};
+    if (threadIdx.x == 0) {
+        for (int v = 0; v < MET_THREADS / 64; ++v)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) t[k] += r[v][k];
+        if (sc)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) met_store(&sc->f[blockIdx.x][k], t[k]);
+        s_last = 1;
+        if (sc) {
+            __atomic_thread_fence(__ATOMIC_RELEASE);
+            const unsigned int tk = __hip_atomic_fetch_add(&sc->ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+            s_last = tk == gridDim.x - 1;
+        }
+    }
+    if (sc) {
+        __syncthreads();
+        if (!s_last) return;
+        __atomic_thread_fence(__ATOMIC_ACQUIRE);
+        if (threadIdx.x < gridDim.x)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) pf[threadIdx.x][k] = met_load(&sc->f[threadIdx.x][k]);
+        __syncthreads();
+        if (threadIdx.x == 0) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) t[k] = 0.0;
+            for (unsigned b = 0; b < gridDim.x; ++b)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) t[k] += pf[b][k];
+            __hip_atomic_store(&sc->ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    if (threadIdx.x == 0) {
+        const double n3 = 3.0 * (double)nb * (double)B;
+        const double v[8] = {t[0], t[1], n3, n3, t[2], t[3], (double)B, 0.0};
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            if (batch) batch[k] = v[k];
+            if (epoch) epoch[k] += v[k];
+        }
+    }
+}
+
+// GRF body frame -> world frame (gnnLightning.py:663-676): quat = world->body rotation, scalar-last (x, y, z, w) as scipy's
+// Rotation.from_quat takes it (normalised here as scipy does); world = R(quat)^-1 f for each of the 4 feet.
+__global__ void k_grf_to_world(const float* quat, const float* body, float* world, int64_t B) {
+    const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= B) return;
+    double x = quat[w * 4], yq = quat[w * 4 + 1], z = quat[w * 4 + 2], s = quat[w * 4 + 3];
+    const double nrm = sqrt(x * x + yq * yq + z * z + s * s);
+    x /= nrm; yq /= nrm; z /= nrm; s /= nrm;
+    // R = matrix of the unit quaternion; its inverse is the transpose
+    const double R[3][3] = {{1 - 2 * (yq * yq + z * z), 2 * (x * yq - z * s), 2 * (x * z + yq * s)},
+                            {2 * (x * yq + z * s), 1 - 2 * (x * x + z * z), 2 * (yq * z - x * s)},
+                            {2 * (x * z - yq * s), 2 * (yq * z + x * s), 1 - 2 * (x * x + yq * yq)}};
+    for (int f = 0; f < 4; ++f) {
+        const double b0 = body[w * 12 + f * 3], b1 = body[w * 12 + f * 3 + 1], b2 = body[w * 12 + f * 3 + 2];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) world[w * 12 + f * 3 + i] = (float)(R[0][i] * b0 + R[1][i] * b1 + R[2][i] * b2);
+    }
+}
+
+static int met_blocks(int64_t items, int per_thread) {
+    return (int)std::max<int64_t>(1, std::min<int64_t>(MET_BLOCKS, (items + per_thread * MET_THREADS - 1) / (per_thread * MET_THREADS)));
+}
+
+extern "C" int mshgnn_metrics_regression(const float* y_pred, const float* y, int64_t n, double* state, void* stream) {
+    if (!y_pred || !y || !state || n < 1) return set_err(MSHGNN_EINVAL, "bad argument to mshgnn_metrics_regression");
+    hipLaunchKernelGGL(k_metrics_reg<1024>, dim3(1), dim3(1024), 0, (hipStream_t)stream, y_pred, y, n, (double*)nullptr, state, (float*)nullptr, (MetScratch*)nullptr);
+    HIPCHK(hipGetLastError());
+    return MSHGNN_OK;
+}
+
+extern "C" int mshgnn_metrics_regression_step(const float* y_pred, const float* y, int64_t n, double* batch_state, double* epoch_state, float* grad_out,
+                                              void* scratch, void* stream) {
+    if (!y_pred || !y || (!batch_state && !epoch_state) || !scratch || n < 1) return set_err(MSHGNN_EINVAL, "bad argument to mshgnn_metrics_regression_step");
+    hipLaunchKernelGGL(k_metrics_reg<MET_THREADS>, dim3(met_blocks(n, 16)), dim3(MET_THREADS), 0, (hipStream_t)stream, y_pred, y, n, batch_state, epoch_state, grad_out,
+                       reinterpret_cast<MetScratch*>(scratch));
+    HIPCHK(hipGetLastError());
+    return MSHGNN_OK;
+}
+
+extern "C" int mshgnn_metrics_classification(const float* logits, const int32_t* y, int64_t batch, double* ce_state, int64_t* counts, void* stream) {
+    if (!logits || !y || !ce_state || !counts || batch < 1) return set_err(MSHGNN_EINVAL, "bad argument to mshgnn_metrics_classification");
+    hipLaunchKernelGGL(k_metrics_cls<1024>, dim3(1), dim3(1024), 0, (hipStream_t)stream, logits, y, batch, (double*)nullptr, (long long*)nullptr, ce_state,
+                       reinterpret_cast<long long*>(counts), (float*)nullptr, (MetScratch*)nullptr);
+    HIPCHK(hipGetLastError());
+    return MSHGNN_OK;
+}
+
+extern "C" int mshgnn_metrics_classification_step(const float* logits, const int32_t* y, int64_t batch, double* batch_ce, int64_t* batch_counts,
+                                                  double* epoch_ce, int64_t* epoch_counts, float* grad_out, void* scratch, void* stream) {
+    if (!logits || !y || batch < 1 || !scratch || (!batch_ce != !batch_counts) || (!epoch_ce != !epoch_counts) || (!batch_ce && !epoch_ce))
+        return set_err(MSHGNN_EINVAL, "bad argument to mshgnn_metrics_classification_step");
+    hipLaunchKernelGGL(k_metrics_cls<MET_THREADS>, dim3(met_blocks(batch, 1)), dim3(MET_THREADS), 0, (hipStream_t)stream, logits, y, batch, batch_ce,
+                       reinterpret_cast<long long*>(batch_counts), epoch_ce, reinterpret_cast<long long*>(epoch_counts), grad_out,
+                       reinterpret_cast<MetScratch*>(scratch));
+    HIPCHK(hipGetLastError());
+    return MSHGNN_OK;
+}
+
+extern "C" int mshgnn_metrics_com_step(const float* y_pred, const float* y, int64_t batch, int n_bases, const double* y_mean, const double* y_std,
+                                       double* batch_state, double* epoch_state, void* scratch, void* stream) {
+    if (!y_pred || !y || !y_mean || !y_std || batch < 1 || n_bases < 1 || !scratch || (!batch_state && !epoch_state))
+        return set_err(MSHGNN_EINVAL, "bad argument to mshgnn_metrics_com_step");
+    ComStats st;
+    for (int k = 0; k < 6; ++k) { st.mean[k] = y_mean[k]; st.std[k] = y_std[k]; }
+    hipLaunchKernelGGL(k_metrics_com, dim3(met_blocks(batch, 1)), dim3(MET_THREADS), 0, (hipStream_t)stream, y_pred, y, batch, n_bases, st, batch_state,
+                       epoch_state, reinterpret_cast<MetScratchCom*>(scratch));
+    HIPCHK(hipGetLastError());
+    return MSHGNN_OK;
+}
+
+extern "C" int mshgnn_grf_body_to_world(const float* quat, const float* grf_body, float* grf_world, int64_t batch, void* stream) {
+    if (!quat || !grf_body || !grf_world || batch < 1) return set_err(MSHGNN_EINVAL, "bad argument to mshgnn_grf_body_to_world");
+    hipLaunchKernelGGL(k_grf_to_world, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, (hipStream_t)stream, quat, grf_body, grf_world, batch);
+    HIPCHK(hipGetLastError());
+    return MSHGNN_OK;
+}

@@ -1,0 +1,223 @@
+// mshgnn_assemble_windows (include/mshgnn.h): a batch of windows gathered from a sequence's resident raw series into the engine's input layout, and their labels.
+// The series entry points that fuse this gather into the encoder are mshgnn.hip's; WindowArgs (mshgnn_device.hpp) is what the two share.
+#include "mshgnn_device.hpp"
+
+// ------------------------------------------------------------------------------------------------------
+// On-device window assembly: the raw time series of a sequence stay in HBM and a batch of
+// windows [start, start + T) is gathered straight into the engine's input layout [B][n_t][pitch] at the plan dtype --
+// what the reference does per window in Python (quadSDKDataset_Morph.py:304-369: axis-major flatten('F') of each
+// variable, joint re-ordering, base tiling, all-ones feet) followed by PyG's collate.
+// One wave per RUN = T consecutive features of one node row: feature f0 + t = src[start + t][col] (optionally
+// standardised over the window like flexibleDataset.py:390-396), or the constant 1.
+// ------------------------------------------------------------------------------------------------------
+constexpr int WIN_ROW_RUNS = 8;          // runs per node row handled with all loads in flight
+
+// one WORKGROUP per window, its 4 waves take the node rows round-robin.  Lane r resolves run r ONCE (source pointer, destination
+// offset, length) and the waves fetch those with v_readlane, so there is no dependent descriptor load per run; every run
+// of a row is a contiguous stretch of a column-major series, read coalesced with all of the row's loads in flight.
+template <typename T, int NSET> __global__ __launch_bounds__(256) void k_assemble_windows(WindowArgs a) {
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t b = blockIdx.x;
+    const int64_t start = a.starts[b];
+    // lane r & 63 of register set r >> 6 <- run r (n_runs <= 64 NSET, checked by the host)
+    int v_lo[NSET], v_hi[NSET], v_doff[NSET], v_len[NSET], v_t[NSET];
+#pragma unroll
+    for (int set = 0; set < NSET; ++set) {
+        const int* run = a.runs + (size_t)min(lane + 64 * set, a.n_runs - 1) * 5;
+        const int t = run[0], node = run[1], f0 = run[2], sc = run[3];
+        const float* sp = nullptr;
+#pragma unroll
+        for (int k = 0; k < WIN_MAX_SRC; ++k) if (sc >= 0 && (sc >> 8) == k) sp = a.src[k] + (size_t)(sc & 0xff) * a.src_cstride[k] + start;
+        int nodes = 0; int64_t pitch = 0;
+#pragma unroll
+        for (int k = 0; k < MSHGNN_MAX_TYPES; ++k) if (t == k) { nodes = a.nodes[k]; pitch = a.x_pitch[k]; }
+        v_lo[set] = (int)((uintptr_t)sp & 0xffffffffu); v_hi[set] = (int)((uintptr_t)sp >> 32);
+        v_doff[set] = (int)(((size_t)b * nodes + node) * pitch + f0 - (size_t)b * nodes * pitch);     // offset inside the window's block of this type
+        v_len[set] = run[4]; v_t[set] = t;
+    }
+    auto rl = [&](const int (&v)[NSET], int r) {
+        if constexpr (NSET == 1) return __builtin_amdgcn_readlane(v[0], r);
+        else return r < 64 ? __builtin_amdgcn_readlane(v[0], r & 63) : __builtin_amdgcn_readlane(v[NSET - 1], r & 63);
+    };
+    // lane handles the element pairs (2 lane + 128 j, +1), j = 0, 1: one packed store per pair (runs start at even features
+    // and node rows are 16-byte aligned, so pairs are 4-byte (bf16) / 8-byte (fp32) aligned); lengths up to 256
+    for (int row = wv; row < a.n_rows; row += 4) {
+        const int r_begin = a.rows[2 * row], r_end = a.rows[2 * row + 1];
+        for (int rb = r_begin; rb < r_end; rb += WIN_ROW_RUNS) {
+            float v[WIN_ROW_RUNS][4];
+#pragma unroll
+            for (int i = 0; i < WIN_ROW_RUNS; ++i) {
+                const int r = min(rb + i, r_end - 1);
+                const float* sp = reinterpret_cast<const float*>((uintptr_t)(unsigned)rl(v_lo, r) | ((uintptr_t)(unsigned)rl(v_hi, r) << 32));
+                const int len = rl(v_len, r);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int k = 2 * lane + 128 * (q >> 1) + (q & 1);
+                    v[i][q] = 1.0f;
+                    if (rb + i < r_end && sp != nullptr && k < len) v[i][q] = sp[k];
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < WIN_ROW_RUNS; ++i) {
+                if (rb + i >= r_end) break;
+                const int r = rb + i;
+                const int t = rl(v_t, r), len = rl(v_len, r), doff = rl(v_doff, r);
+                const bool has_src = (rl(v_lo, r) | rl(v_hi, r)) != 0;
+                T* dst = reinterpret_cast<T*>(a.x[t]) + (size_t)b * a.nodes[t] * a.x_pitch[t] + doff;
+                if (a.normalize && has_src) {
+                    // (x - mean) / std with the unbiased estimator, NaN -> 0 (flexibleDataset.py:390-396); fp64, two passes over registers.  The arithmetic
+                    // is run_stats / standardise_one (mshgnn_device.hpp), shared with the standardising series encoders of mshgnn_forward_series
+                    const RunStats rs = run_stats(v[i], len, lane);
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) v[i][q] = standardise_one(v[i][q], rs.mean, rs.sd);
+                }
+                const bool even = ((doff | len) & 1) == 0;
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const int k = 2 * lane + 128 * j;
+                    if (even && k < len) {
+                        if constexpr (sizeof(T) == 2) {
+                            union { unsigned u; __bf16 e[2]; } pk; pk.e[0] = (__bf16)v[i][2 * j]; pk.e[1] = (__bf16)v[i][2 * j + 1];
+                            *reinterpret_cast<unsigned*>(dst + k) = pk.u;
+                        } else *reinterpret_cast<f32x2*>(dst + k) = f32x2{v[i][2 * j], v[i][2 * j + 1]};
+                    } else {
+                        if (k < len) dst[k] = from_f32<T>(v[i][2 * j]);
+                        if (k + 1 < len) dst[k + 1] = from_f32<T>(v[i][2 * j + 1]);
+                    }
+                }
+            }
+        }
+    }
+}
+
+// Fast path of the same gather (no standardisation, 16-byte aligned output rows whose runs all have one length -- what SequenceStore builds):
+// a thread owns one 16-BYTE CHUNK of one node row -- EPC consecutive features, which live in at most two runs of that length -- gathers them
+// with EPC scalar loads (consecutive lanes read consecutive elements of a column-major series) and writes ONE 16-byte store; all chunks of a
+// window are independent, so every load of the window is in flight at once.  The general kernel above writes 4 bytes per lane and walks a row's
+// runs in turn: 0.12 ms for 8192 A1 windows against 0.03-0.04 ms here.  Pad columns inside a row's last chunk are written as zeros.
+constexpr int WIN_MAX_ROWS = 64;
+template <typename T> __global__ __launch_bounds__(256) void k_assemble_windows_fast(WindowArgs a) {
+    constexpr int EPC = 16 / (int)sizeof(T);
+    __shared__ unsigned long long s_src[WIN_MAX_RUNS];                    // source pointer of run r at this window's first step (0: the constant 1)
+    __shared__ int s_first[WIN_MAX_ROWS + 1];                             // chunk prefix per node row
+    __shared__ int s_run0[WIN_MAX_ROWS], s_len[WIN_MAX_ROWS], s_width[WIN_MAX_ROWS];
+    __shared__ unsigned long long s_dst[WIN_MAX_ROWS];                    // destination of the row's first element
+    const int tid = threadIdx.x;
+    const int64_t b = blockIdx.x, start = a.starts[b];
+    if (tid < a.n_runs) {
+        const int sc = a.runs[(size_t)tid * 5 + 3];
+        const float* sp = nullptr;
+#pragma unroll
+        for (int k = 0; k < WIN_MAX_SRC; ++k) if (sc >= 0 && (sc >> 8) == k) sp = a.src[k] + (size_t)(sc & 0xff) * a.src_cstride[k] + start;
+        s_src[tid] = (unsigned long long)sp;
+    }
+    if (tid < a.n_rows) {
+        const int r0 = a.rows[2 * tid], r1 = a.rows[2 * tid + 1];
+        const int* run = a.runs + (size_t)r0 * 5;
+        const int t = run[0], node = run[1], len = run[4];
+        int nodes = 0; int64_t pitch = 0; char* xb = nullptr;
+#pragma unroll
+        for (int k = 0; k < MSHGNN_MAX_TYPES; ++k) if (t == k) { nodes = a.nodes[k]; pitch = a.x_pitch[k]; xb = reinterpret_cast<char*>(a.x[k]); }
+        s_run0[tid] = r0; s_len[tid] = len; s_width[tid] = (r1 - r0) * len;
+        s_dst[tid] = (unsigned long long)(xb + (((size_t)b * nodes + node) * pitch + run[2]) * sizeof(T));
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int acc = 0;
+        for (int r = 0; r < a.n_rows; ++r) { s_first[r] = acc; acc += (s_width[r] + EPC - 1) / EPC; }
+        s_first[a.n_rows] = acc;
+    }
+    __syncthreads();
+    const int total = s_first[a.n_rows];
+    int row = 0;
+    for (int task = tid; task < total; task += 256) {
+        while (task >= s_first[row + 1]) ++row;                            // (tasks of a thread ascend)
+        const int j = task - s_first[row], len = s_len[row], width = s_width[row];
+        const int k0 = j * EPC;
+        int run = s_run0[row] + k0 / len, off = k0 % len;
+        float v[EPC];
+#pragma unroll
+        for (int e = 0; e < EPC; ++e) {
+            v[e] = 0.f;
+            if (k0 + e < width) {
+                const float* sp = reinterpret_cast<const float*>(s_src[run]);
+                v[e] = sp ? sp[off] : 1.0f;
+            }
+            if (++off == len) { off = 0; ++run; }
+        }
+        T* dst = reinterpret_cast<T*>(s_dst[row]) + k0;
+        if constexpr (sizeof(T) == 2) {
+            union { u32x4 u; __bf16 e[8]; } pk;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) pk.e[e] = (__bf16)v[e];
+            *reinterpret_cast<u32x4*>(dst) = pk.u;
+        } else *reinterpret_cast<f32x4*>(dst) = f32x4{v[0], v[1], v[2], v[3]};
+    }
+}
+
+// labels of a window = the label row of its LAST time step (quadSDKDataset.py: grfs[-1]); with label_rotate the world-frame
+// GRFs are taken into the body frame with the world->body quaternion of that step, R f per foot (the as_matrix() @ grfs_T
+// branch of load_data_at_dataset_seq_3d); quat out = that quaternion (data.r_o, quadSDKDataset_Morph.py:365-367)
+// (window_labels_one itself lives in mshgnn_device.hpp: the fused-gather encoders run it in extra workgroups of their own launch)
+__device__ __forceinline__ LabelArgs label_args_of(const WindowArgs& a, int32_t* labels_int) {
+    LabelArgs l{};
+    l.lab = a.src[a.label_src]; l.lab_cs = a.src_cstride[a.label_src];
+    l.quat_src = a.quat_src >= 0 ? a.src[a.quat_src] : nullptr; l.quat_cs = a.quat_src >= 0 ? a.src_cstride[a.quat_src] : 0;
+    l.starts = a.starts; l.B = a.B; l.T = a.T; l.label_cols = a.label_cols; l.n_label = a.n_label; l.label_rotate = a.label_rotate;
+    l.y = a.y; l.quat = a.quat; l.labels_int = labels_int;
+    return l;
+}
+
+__global__ void k_window_labels(WindowArgs a) {
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < a.B) window_labels_one(label_args_of(a, nullptr), b);
+}
+
+extern "C" int mshgnn_assemble_windows(const mshgnn_window_desc* d, const float* const* src, const int64_t* src_cstride, const int64_t* src_rows,
+                                       const int64_t* starts, int64_t batch, void* const* x_out, const int64_t* x_pitch, float* y_out,
+                                       float* quat_out, void* stream) {
+    if (!d || !src || !src_cstride || !src_rows || !starts || !x_out || !x_pitch || batch < 1) return set_err(MSHGNN_EINVAL, "null argument to mshgnn_assemble_windows");
+    if (d->n_types < 1 || d->n_types > MSHGNN_MAX_TYPES || d->n_src < 1 || d->n_src > WIN_MAX_SRC || d->n_runs < 1 || !d->runs || d->n_rows < 1 || !d->rows)
+        return set_err(MSHGNN_EINVAL, "bad window descriptor");
+    if (d->history < 1 || (d->normalize && d->history < 2)) return set_err(MSHGNN_EINVAL, "history must be >= 1 (>= 2 when normalising)");
+    if (d->dtype != MSHGNN_F32 && d->dtype != MSHGNN_BF16 && d->dtype != MSHGNN_BF16X3) return set_err(MSHGNN_EINVAL, "dtype must be MSHGNN_F32, MSHGNN_BF16 or MSHGNN_BF16X3");
+    if (d->n_label > 0 && (!d->label_cols || !y_out || d->label_src < 0 || d->label_src >= d->n_src)) return set_err(MSHGNN_EINVAL, "bad label description");
+    if (d->label_rotate && (d->n_label % 3 != 0 || d->quat_src < 0)) return set_err(MSHGNN_EINVAL, "label rotation needs 3-D labels and a quaternion source");
+    if (d->quat_src >= d->n_src) return set_err(MSHGNN_EINVAL, "quat_src out of range");
+    WindowArgs a{};
+    for (int i = 0; i < d->n_src; ++i) {
+        if (!src[i] || src_cstride[i] < src_rows[i] || src_rows[i] < d->history) return set_err(MSHGNN_EINVAL, "bad source array");
+        a.src[i] = src[i]; a.src_cstride[i] = src_cstride[i];
+    }
+    for (int t = 0; t < d->n_types; ++t) {
+        if (!x_out[t] || d->type_nodes[t] < 1 || x_pitch[t] < d->type_width[t]) return set_err(MSHGNN_EINVAL, "bad output tensor");
+        a.x[t] = x_out[t]; a.x_pitch[t] = x_pitch[t]; a.nodes[t] = d->type_nodes[t];
+    }
+    if (d->history > 256) return set_err(MSHGNN_EUNSUPPORTED, "history longer than 256 steps is not supported by this build");
+    a.runs = d->runs; a.n_runs = d->n_runs; a.rows = d->rows; a.n_rows = d->n_rows; a.starts = starts; a.B = batch; a.T = d->history; a.normalize = d->normalize;
+    a.label_cols = d->label_cols; a.n_label = d->n_label; a.label_src = d->label_src; a.label_rotate = d->label_rotate; a.quat_src = d->quat_src;
+    a.y = y_out; a.quat = quat_out;
+    hipStream_t st = (hipStream_t)stream;
+    if (d->n_runs > 128) return set_err(MSHGNN_EUNSUPPORTED, "more than 128 feature runs per window are not supported by this build");
+    // fast path: no standardisation, every row's runs of one length starting at the row's first feature 0, 16-byte aligned rows whose pitch covers whole chunks
+    const bool f32 = d->dtype == MSHGNN_F32 || d->dtype == MSHGNN_BF16X3;      // the split plan takes fp32 inputs
+    bool fast = !d->normalize && d->n_rows <= WIN_MAX_ROWS && d->n_runs <= WIN_MAX_RUNS && d->fast_layout != 0;
+    for (int t = 0; t < d->n_types && fast; ++t) {
+        const int epc = f32 ? 4 : 8;
+        if (((uintptr_t)x_out[t] & 15) || x_pitch[t] % epc || x_pitch[t] < (d->type_width[t] + epc - 1) / epc * epc) fast = false;
+    }
+    if (fast) {
+        if (f32) hipLaunchKernelGGL(k_assemble_windows_fast<float>, dim3((unsigned)batch), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL(k_assemble_windows_fast<__bf16>, dim3((unsigned)batch), dim3(256), 0, st, a);
+    } else if (f32) {
+        if (d->n_runs <= 64) hipLaunchKernelGGL((k_assemble_windows<float, 1>), dim3((unsigned)batch), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((k_assemble_windows<float, 2>), dim3((unsigned)batch), dim3(256), 0, st, a);
+    } else {
+        if (d->n_runs <= 64) hipLaunchKernelGGL((k_assemble_windows<__bf16, 1>), dim3((unsigned)batch), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((k_assemble_windows<__bf16, 2>), dim3((unsigned)batch), dim3(256), 0, st, a);
+    }
+    if (d->n_label > 0 || (quat_out && d->quat_src >= 0))
+        hipLaunchKernelGGL(k_window_labels, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, st, a);
+    HIPCHK(hipGetLastError());
+    return MSHGNN_OK;
+}
