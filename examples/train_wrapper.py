@@ -25,7 +25,7 @@ from morphsym_hgnn_amd import wrappers  # noqa: E402
 from morphsym_hgnn_amd.windows import SequenceStore, quadsdk_a1_c2_recipe  # noqa: E402
 
 
-def train(steps=200, batch=8192, dtype="bf16", layers=3, lr=1e-3, rows=100_000, log_every=50, quiet=False, assemble=False):
+def train(steps=200, batch=8192, dtype="bf16", layers=3, lr=1e-3, rows=100_000, log_every=50, quiet=False, assemble=False, normalize=False):
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
     dist = None
     if world > 1:      # one process per GPU (torchrun): every rank trains on its own windows, one all-reduce of the flat gradient per step
@@ -35,7 +35,7 @@ def train(steps=200, batch=8192, dtype="bf16", layers=3, lr=1e-3, rows=100_000, 
         dist.init_process_group("nccl")
     dev = torch.device("cuda", torch.cuda.current_device())
     spec = bench.build_spec(layers)
-    store = SequenceStore(synthetic_sequence(rows, seed=rank), quadsdk_a1_c2_recipe(range(12), range(4), 150, 3), dtype=dtype, device=dev)
+    store = SequenceStore(synthetic_sequence(rows, seed=rank), quadsdk_a1_c2_recipe(range(12), range(4), 150, 3, normalize=normalize), dtype=dtype, device=dev)      # normalize: windows standardised per run, as the reference's datasets default to
     ei = spec.topology.edge_index_dict(batch, device=dev)
     gen = torch.Generator(device=dev).manual_seed(1234 + rank)
 
@@ -88,5 +88,6 @@ if __name__ == "__main__":
     ap.add_argument("--steps", type=int, default=200); ap.add_argument("--batch", type=int, default=8192)
     ap.add_argument("--dtype", default="bf16", choices=["f32", "bf16", "x3"]); ap.add_argument("--layers", type=int, default=3)
     ap.add_argument("--lr", type=float, default=1e-3); ap.add_argument("--assemble", action="store_true")
+    ap.add_argument("--normalize", action="store_true", help="standardise every run over its window (the reference's normalize=True); the encoder does it on the fly")
     a = ap.parse_args()
-    train(a.steps, a.batch, a.dtype, a.layers, a.lr, assemble=a.assemble)
+    train(a.steps, a.batch, a.dtype, a.layers, a.lr, assemble=a.assemble, normalize=a.normalize)

@@ -370,6 +370,25 @@ int mshgnn_step_ce_series(const mshgnn_plan* plan, const mshgnn_window_desc* des
                           void* const* x_out, const int64_t* x_pitch, float* y_out, int32_t* labels_out, void* run_ptrs,
                           const float* params, float* out, float* loss_out, float* grad_params, void* workspace, void* stream);
 
+/* The two steps above on a STANDARDISED recipe (desc->normalize != 0, history in [2, 256]): mshgnn_assemble_windows + mshgnn_step_mse / mshgnn_step_ce on the
+ * standardised windows, bit for bit, in one call.  A pre-pass writes {mean, sd} of every (window, run) into `stats` (device scratch, 16-byte aligned,
+ * mshgnn_forward_series_stats_bytes(desc, batch) bytes), the encoder standardises the FP32 series with the arithmetic of mshgnn_assemble_windows (one shared
+ * device function) on BOTH plans -- src_bf16 may be NULL, run_ptrs are resolved for 4-byte elements -- and writes the standardised windows to x_out in the
+ * plan's input dtype (bf16 plan: bf16 rows, pitch a multiple of 8; split plan: fp32 rows, pitch a multiple of 4; pad columns beyond the last 16-byte chunk
+ * untouched).  The weight-gradient pass reads those windows and nothing else: x_out == NULL is MSHGNN_EUNSUPPORTED on either plan.  Refused before anything is
+ * launched: an unstandardised descriptor (MSHGNN_EINVAL: use the plain entry points), stats NULL or misaligned, history < 2 (MSHGNN_EINVAL), history > 256,
+ * history < 8 with node rows of several runs, the fp32 plan, the generic-width engine, the per-layer kernels (MSHGNN_EUNSUPPORTED), and whatever the plain
+ * entry points refuse in the label description.  Every launch goes on `stream`.  run_ptrs / desc->run_ptrs_ready as in mshgnn_step_mse_series; a scratch
+ * filled by mshgnn_forward_series on the same standardised descriptor and sources may be vouched for here and the other way round.                        */
+int mshgnn_step_mse_series_std(const mshgnn_plan* plan, const mshgnn_window_desc* desc, const float* const* src, const void* const* src_bf16,
+                               const int64_t* src_cstride, const int64_t* src_rows, const int64_t* starts /* device int64[batch] */, int64_t batch,
+                               void* const* x_out, const int64_t* x_pitch, float* y_out, float* quat_out, void* run_ptrs, void* stats,
+                               const float* params, float* out, float* loss_out, float* grad_params, void* workspace, void* stream);
+int mshgnn_step_ce_series_std(const mshgnn_plan* plan, const mshgnn_window_desc* desc, const float* const* src, const void* const* src_bf16,
+                              const int64_t* src_cstride, const int64_t* src_rows, const int64_t* starts, int64_t batch,
+                              void* const* x_out, const int64_t* x_pitch, float* y_out, int32_t* labels_out, void* run_ptrs, void* stats,
+                              const float* params, float* out, float* loss_out, float* grad_params, void* workspace, void* stream);
+
 /* Evaluation straight from a sequence's resident raw series: mshgnn_assemble_windows + mshgnn_forward(training = 0) in one call, with the window gather fused
  * into the encoder and NO materialised windows at all -- results are bit-identical to that pair.  `workspace` is one laid out for training = 0; nothing is
  * stashed.  Same plans as mshgnn_step_*_series: the bf16 plan with the fused stack kernels (src_bf16 as there) and the split plan MSHGNN_BF16X3 (fp32 series,
@@ -381,7 +400,7 @@ int mshgnn_step_ce_series(const mshgnn_plan* plan, const mshgnn_window_desc* des
  * (x - mean) / sd with Bessel's correction in fp64, NaN -> 0, then rounded to fp32 (and to bf16 on the bf16 plan) exactly as mshgnn_assemble_windows does --
  * one shared device function computes both.  A pre-pass writes {mean, sd} of every (window, run) into `stats` (device scratch, 16-byte aligned,
  * mshgnn_forward_series_stats_bytes(desc, batch) = batch * n_runs * 16 bytes; 0 and `stats` ignored for unstandardised recipes); the encoder then reads the
- * FP32 series on both plans (src_bf16 may be NULL on the bf16 plan too).  The training entry points above keep refusing standardised recipes.
+ * FP32 series on both plans (src_bf16 may be NULL on the bf16 plan too).  The plain training entry points keep refusing standardised recipes (their _std forms take them).
  * run_ptrs / desc->run_ptrs_ready as in mshgnn_step_mse_series; the pointers are those of the series the encoder reads, so a scratch filled by a
  * mshgnn_step_*_series call with the same (unstandardised) descriptor and sources may be vouched for here and the other way round.                        */
 int mshgnn_forward_series(const mshgnn_plan* plan, const mshgnn_window_desc* desc, const float* const* src, const void* const* src_bf16,

@@ -109,9 +109,10 @@ __device__ __forceinline__ u32x4 splice8(u32x4 A, u32x4 B, int n0) {      // bf1
 }
 // SRC (bf16, ALIGNED; 8 / 4): the rows come from the caller's own fp64 / fp32 tensors at their dense pitch (WideSrc), are converted in registers and ALSO
 // written to a.x as plan-dtype rows for the weight-gradient kernel -- the cast + re-pitch pass fused into the encoder (mshgnn_*_src entry points).
-// NORM (with SERIES; mshgnn_forward_series on a standardised recipe): the chunk's 8 elements come from the FP32 series (two 4-byte-aligned 16-byte loads per
+// NORM (with SERIES; mshgnn_forward_series / mshgnn_step_*_series_std on a standardised recipe): the chunk's 8 elements come from the FP32 series (two 4-byte-aligned 16-byte loads per
 // piece, as k_enc_x3<.., SERIES>) and every run with a source column is standardised over its window with the statistics k_series_stats left in ser.stats --
-// fp64 -> fp32 -> bf16, the roundings of mshgnn_assemble_windows(normalize) (standardise_one, mshgnn_device.hpp); nothing is materialised.
+// fp64 -> fp32 -> bf16, the roundings of mshgnn_assemble_windows(normalize) (standardise_one, mshgnn_device.hpp).  Evaluation materialises nothing (a.x null);
+// the training steps (mshgnn_step_*_series_std) get the standardised bf16 rows written to a.x like the plain SERIES rows, behind the next chunk's loads.
 template <typename T, bool ALIGNED, bool SERIES = false, int SRC = 0, bool NORM = false> __global__ __launch_bounds__(256) void k_enc_fwd(EncArgs a, SeriesSrc ser, WideSrc wsrc) {
     using P = Prec<T>;
     static_assert(!NORM || SERIES, "standardisation is part of the series gather");
@@ -2077,7 +2078,6 @@ static int forward_impl(const mshgnn_plan* p, StepCall& c) {
         if constexpr (sizeof(T) == 2) {
             if (series) {
                 if (x && !a.aligned) return set_err(MSHGNN_EINVAL, "the fused window assembly needs 16-byte aligned window rows (pitch a multiple of 8)");
-                if (series->stats && x) return set_err(MSHGNN_EINVAL, "the standardising series encoder materialises no windows");
                 enc_grid += (unsigned)((series->lab.B + 255) / 256);      // the label workgroups
                 if (series->stats) hipLaunchKernelGGL((k_enc_fwd<T, true, true, 0, true>), dim3(enc_grid), dim3(256), Prec<T>::ENC_MB * Prec<T>::BLK, st, a, *series, WideSrc{});
                 else hipLaunchKernelGGL((k_enc_fwd<T, true, true>), dim3(enc_grid), dim3(256), Prec<T>::ENC_MB * Prec<T>::BLK, st, a, *series, WideSrc{});
@@ -2499,7 +2499,7 @@ __global__ void k_series_run_ptrs(const int* runs, int n_runs, WindowArgs wa, in
 }
 
 // ---- what the series routes share: the caller's description of the sequence and the windows, one check of the window descriptor against the plan, one fill of
-// SeriesSrc / LabelArgs.  Training = mshgnn_step_mse_series / mshgnn_step_ce_series, evaluation = mshgnn_forward_series.
+// SeriesSrc / LabelArgs.  Training = mshgnn_step_mse_series / mshgnn_step_ce_series and their _std forms, evaluation = mshgnn_forward_series.
 struct SeriesArgs {      // as the entry points receive them
     const mshgnn_window_desc* d;
     const float* const* src; const void* const* src_bf16; const int64_t* src_cstride; const int64_t* src_rows;
@@ -2511,10 +2511,10 @@ struct SeriesChecks {      // where training and evaluation differ
     const char* who;                  // the route's name in messages (who_ce: where a message is the classification step's own)
     const char* who_ce;
     bool labels_required;             // training: the recipe must describe labels; evaluation: only when y_out is given
-    bool takes_normalize;             // evaluation takes standardised recipes (the NORM encoders); training refuses them
+    bool takes_normalize;             // evaluation and mshgnn_step_*_series_std take standardised recipes (the NORM encoders); the plain training steps refuse them
     bool ce_needs_two_logits;         // training checks the plan's logit pairs here; evaluation leaves them to the caller's loss
-    // node rows of several runs need history >= 8 (the encoders take a chunk's 8 elements from at most two runs).  Only evaluation checks it.  Training lacks the
-    // check: closing that changes what the wrappers must fall back on and belongs in a change of its own -- until then this stays false there.
+    // node rows of several runs need history >= 8 (the encoders take a chunk's 8 elements from at most two runs).  Evaluation and the standardised training steps check it.
+    // The plain training steps lack the check: closing that changes what the wrappers must fall back on and belongs in a change of its own -- until then this stays false there.
     bool several_runs_need_history8;
 };
 
@@ -2587,32 +2587,55 @@ static void fill_series_src(const SeriesArgs& s, const WindowArgs& wa, bool fp32
 // the plans the series routes run on: the bf16 plan with the fused stack kernels and the split plan
 static bool series_plan_ok(const mshgnn_plan* p) { return !p->gen && (p->hp.d.dtype == MSHGNN_BF16X3 || (p->hp.d.dtype == MSHGNN_BF16 && p->use_fused)); }
 
-static int step_series(const mshgnn_plan* p, const SeriesArgs& s, void* const* x_out, const int64_t* x_pitch, const float* params, float* out, float* loss_out,
-                       float* grad_params, void* workspace, void* stream) {
+// the statistics pre-pass of the standardised routes (defined with mshgnn_forward_series below)
+__global__ __launch_bounds__(256) void k_series_stats(const int* runs, int n_runs, const unsigned long long* run_ptr, const int64_t* starts, int64_t B, double* stats);
+
+// std_route (mshgnn_step_*_series_std): a standardised recipe -- k_series_stats leaves {mean, sd} of every (window, run) in `stats`, the NORM encoders apply them to the
+// FP32 series on both plans and write the standardised windows to x_out, which the weight-gradient pass then reads like assembled ones.
+static int step_series(const mshgnn_plan* p, const SeriesArgs& s, bool std_route, void* stats, void* const* x_out, const int64_t* x_pitch, const float* params, float* out,
+                       float* loss_out, float* grad_params, void* workspace, void* stream) {
     const bool ce = s.labels_out != nullptr;      // classification wrappers: cross entropy over the per-foot logit pairs, labels = the window labels != 0
+    const char* who = std_route ? "mshgnn_step_mse_series_std" : "mshgnn_step_mse_series", * who_ce = std_route ? "mshgnn_step_ce_series_std" : "mshgnn_step_ce_series";
     if (!p || !s.d || !s.src || !s.src_cstride || !s.src_rows || !s.starts || !s.y_out || !s.run_ptrs || !params || !out || !loss_out ||
-        !grad_params || !workspace || (x_out && !x_pitch)) return set_err(MSHGNN_EINVAL, "null argument to mshgnn_step_mse_series / mshgnn_step_ce_series");
+        !grad_params || !workspace || (x_out && !x_pitch)) return set_err(MSHGNN_EINVAL, std::string("null argument to ") + who + " / " + who_ce);
     if (s.batch < 1 || s.batch > (1 << 24)) return set_err(MSHGNN_EINVAL, "batch must be in [1, 2^24]");
     // bf16 plan (fused stack kernels): bf16 copies of the series, optional materialisation.  Split plan (MSHGNN_BF16X3): the fp32 series
     // themselves, windows always materialised (fp32) for its weight-gradient kernel.
     if (!series_plan_ok(p))
-        return set_err(MSHGNN_EUNSUPPORTED, "mshgnn_step_mse_series runs on the bf16 plan with the fused stack kernels or on the split plan; use mshgnn_assemble_windows + mshgnn_step_mse");
+        return set_err(MSHGNN_EUNSUPPORTED, std::string(who) + " runs on the bf16 plan with the fused stack kernels or on the split plan; use mshgnn_assemble_windows + mshgnn_step_mse");
     const bool x3 = p->hp.d.dtype == MSHGNN_BF16X3;
-    if (!x3 && !s.src_bf16) return set_err(MSHGNN_EINVAL, "null argument to mshgnn_step_mse_series / mshgnn_step_ce_series");
+    if (std_route) {
+        if (!s.d->normalize)
+            return set_err(MSHGNN_EINVAL, std::string(who) + ": the window descriptor is unstandardised; use mshgnn_step_mse_series / mshgnn_step_ce_series");
+        if (!stats) return set_err(MSHGNN_EINVAL, std::string(who) + ": a standardised recipe needs the stats scratch (mshgnn_forward_series_stats_bytes)");
+        if ((uintptr_t)stats & 15) return set_err(MSHGNN_EINVAL, std::string(who) + ": the stats scratch must be 16-byte aligned");
+        if (s.d->history < 2) return set_err(MSHGNN_EINVAL, "history must be >= 2 when normalising");
+        if (s.d->history > 256) return set_err(MSHGNN_EUNSUPPORTED, "history longer than 256 steps is not supported by this build");
+        // (a weight-gradient kernel that standardises its raw operands again is not built: it reads the windows the encoder wrote)
+        if (!x_out) return set_err(MSHGNN_EUNSUPPORTED, std::string(who) + ": the weight-gradient pass reads the materialised standardised windows: x_out must be given");
+    }
+    const bool fp32_gather = x3 || std_route;      // standardisation happens before the bf16 rounding: the bf16 plan's NORM encoder reads the fp32 series too
+    if (!fp32_gather && !s.src_bf16) return set_err(MSHGNN_EINVAL, "null argument to mshgnn_step_mse_series / mshgnn_step_ce_series");
     if (x3 && !x_out) return set_err(MSHGNN_EUNSUPPORTED, "the split plan's weight-gradient kernel reads materialised windows: x_out must be given");
-    const SeriesChecks k{"mshgnn_step_mse_series", "mshgnn_step_ce_series", /*labels_required*/ true, /*takes_normalize*/ false, /*ce_needs_two_logits*/ true,
-                         /*several_runs_need_history8*/ false};
+    // (the plain routes leave several_runs_need_history8 open, see SeriesChecks; the standardised ones are new and check it)
+    const SeriesChecks k{who, who_ce, /*labels_required*/ true, /*takes_normalize*/ std_route, /*ce_needs_two_logits*/ true, /*several_runs_need_history8*/ std_route};
     WindowArgs wa{};
     if (const int rc = check_window_desc(p, s, k, x_out, x_pitch)) return rc;
-    if (const int rc = check_series_sources(s, x3, wa)) return rc;
+    if (const int rc = check_series_sources(s, fp32_gather, wa)) return rc;
     if (const int rc = check_label_rotation(s, k)) return rc;
     SeriesSrc ser{};
-    fill_series_src(s, wa, x3, /*want_q: the quaternion travels with the labels wherever the recipe has one*/ true, (hipStream_t)stream, ser);
+    fill_series_src(s, wa, fp32_gather, /*want_q: the quaternion travels with the labels wherever the recipe has one*/ true, (hipStream_t)stream, ser);
+    if (std_route) {
+        const int64_t waves = s.batch * s.d->n_runs;
+        hipLaunchKernelGGL(k_series_stats, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, (hipStream_t)stream, s.d->runs, s.d->n_runs, ser.run_ptr, s.starts, s.batch,
+                           reinterpret_cast<double*>(stats));
+        ser.stats = reinterpret_cast<const double*>(stats); ser.n_runs = s.d->n_runs;
+    }
     StepCall c;
     c.x = x_out; c.x_pitch = x_pitch; c.params = params; c.out = out; c.ws = (char*)workspace; c.batch = s.batch; c.training = 1; c.stream = (hipStream_t)stream;
     c.loss = ce ? LossKind::CE : LossKind::MSE; c.y = s.y_out; c.labels = s.labels_out; c.loss_out = loss_out; c.grad_params = grad_params;
     c.series = &ser;
-    c.gradw_from_series = !x_out;      // no materialised windows at all (bf16 plan only, see above): the weight-gradient kernel gathers its raw-input operands from the series as well
+    c.gradw_from_series = !x_out;      // no materialised windows at all (plain bf16 route only, see above): the weight-gradient kernel gathers its raw-input operands from the series as well
     return run_step(p, c);
 }
 
@@ -2621,7 +2644,7 @@ extern "C" int mshgnn_step_mse_series(const mshgnn_plan* p, const mshgnn_window_
                                       void* const* x_out, const int64_t* x_pitch, float* y_out, float* quat_out, void* run_ptrs,
                                       const float* params, float* out, float* loss_out, float* grad_params, void* workspace, void* stream) {
     const SeriesArgs s{d, src, src_bf16, src_cstride, src_rows, starts, batch, y_out, quat_out, nullptr, run_ptrs};
-    return step_series(p, s, x_out, x_pitch, params, out, loss_out, grad_params, workspace, stream);
+    return step_series(p, s, false, nullptr, x_out, x_pitch, params, out, loss_out, grad_params, workspace, stream);
 }
 
 extern "C" int mshgnn_step_ce_series(const mshgnn_plan* p, const mshgnn_window_desc* d, const float* const* src, const void* const* src_bf16,
@@ -2630,7 +2653,25 @@ extern "C" int mshgnn_step_ce_series(const mshgnn_plan* p, const mshgnn_window_d
                                      const float* params, float* out, float* loss_out, float* grad_params, void* workspace, void* stream) {
     if (!labels_out) return set_err(MSHGNN_EINVAL, "null argument to mshgnn_step_ce_series");
     const SeriesArgs s{d, src, src_bf16, src_cstride, src_rows, starts, batch, y_out, nullptr, labels_out, run_ptrs};
-    return step_series(p, s, x_out, x_pitch, params, out, loss_out, grad_params, workspace, stream);
+    return step_series(p, s, false, nullptr, x_out, x_pitch, params, out, loss_out, grad_params, workspace, stream);
+}
+// The same steps on a STANDARDISED recipe (desc->normalize): mshgnn_assemble_windows(normalize) + mshgnn_step_mse / _ce, bit for bit.  stats: the scratch
+// mshgnn_forward_series_stats_bytes sizes.  The plain entry points above keep refusing such recipes.
+extern "C" int mshgnn_step_mse_series_std(const mshgnn_plan* p, const mshgnn_window_desc* d, const float* const* src, const void* const* src_bf16,
+                                          const int64_t* src_cstride, const int64_t* src_rows, const int64_t* starts, int64_t batch,
+                                          void* const* x_out, const int64_t* x_pitch, float* y_out, float* quat_out, void* run_ptrs, void* stats,
+                                          const float* params, float* out, float* loss_out, float* grad_params, void* workspace, void* stream) {
+    const SeriesArgs s{d, src, src_bf16, src_cstride, src_rows, starts, batch, y_out, quat_out, nullptr, run_ptrs};
+    return step_series(p, s, true, stats, x_out, x_pitch, params, out, loss_out, grad_params, workspace, stream);
+}
+
+extern "C" int mshgnn_step_ce_series_std(const mshgnn_plan* p, const mshgnn_window_desc* d, const float* const* src, const void* const* src_bf16,
+                                         const int64_t* src_cstride, const int64_t* src_rows, const int64_t* starts, int64_t batch,
+                                         void* const* x_out, const int64_t* x_pitch, float* y_out, int32_t* labels_out, void* run_ptrs, void* stats,
+                                         const float* params, float* out, float* loss_out, float* grad_params, void* workspace, void* stream) {
+    if (!labels_out) return set_err(MSHGNN_EINVAL, "null argument to mshgnn_step_ce_series_std");
+    const SeriesArgs s{d, src, src_bf16, src_cstride, src_rows, starts, batch, y_out, nullptr, labels_out, run_ptrs};
+    return step_series(p, s, true, stats, x_out, x_pitch, params, out, loss_out, grad_params, workspace, stream);
 }
 // ------------------------------------------------------------------------------------------------------
 // mshgnn_forward_series: evaluation straight from a sequence's resident raw series -- mshgnn_assemble_windows + mshgnn_forward(training = 0) with the window

@@ -77,8 +77,9 @@ __global__ void k_prep_x3(PrepArgs a) { prep_one_x3(a, blockIdx.x * blockDim.x +
 // straddles two runs -- and the materialised window rows are written on the side for the weight-gradient pass (a.x: the window buffers).
 // SRC (8 / 4, with ALIGNED): the rows come from the caller's own fp64 / fp32 tensors at their dense pitch (WideSrc, mshgnn_device.hpp) and are also written to
 // a.x as fp32 rows at the engine's pitch for the weight-gradient kernel (mshgnn_*_src entry points)
-// NORM (with SERIES; mshgnn_forward_series on a standardised recipe): every run with a source column is standardised over its window with the statistics
-// k_series_stats left in ser.stats (standardise_one, mshgnn_device.hpp: the arithmetic of mshgnn_assemble_windows(normalize)); nothing is materialised.
+// NORM (with SERIES; mshgnn_forward_series / mshgnn_step_*_series_std on a standardised recipe): every run with a source column is standardised over its window with the statistics
+// k_series_stats left in ser.stats (standardise_one, mshgnn_device.hpp: the arithmetic of mshgnn_assemble_windows(normalize)).  Evaluation materialises nothing
+// (a.x null); the training steps (mshgnn_step_*_series_std) get the standardised fp32 rows written to a.x like the plain SERIES rows.
 template <bool ALIGNED, bool SERIES = false, int SRC = 0, bool NORM = false> __global__ __launch_bounds__(256) void k_enc_x3(EncArgs a, int n_img, SeriesSrc ser, WideSrc wsrc) {
     static_assert(!NORM || SERIES, "standardisation is part of the series gather");
     static_assert(!SERIES || ALIGNED, "the series gather writes aligned window buffers");
@@ -889,7 +890,6 @@ int x3_forward(const mshgnn_plan* p, StepCall& c) {
         ProfScope ps(p, hp.ks_enc, st);
         if (series) {      // inputs gathered from the sequence's series; x = the window buffers the rows are materialised into
             if (x && !a.aligned) return set_err(MSHGNN_EINVAL, "the series gather writes 16-byte-aligned window buffers whose pitch is a multiple of 4");
-            if (series->stats && x) return set_err(MSHGNN_EINVAL, "the standardising series encoder materialises no windows");
             enc_grid += (unsigned)((series->lab.B + 255) / 256);      // the label workgroups
             if (series->stats) hipLaunchKernelGGL((k_enc_x3<true, true, 0, true>), dim3(enc_grid), dim3(256), 8 * P16::BLK, st, a, hp.n_img, *series, WideSrc{});
             else hipLaunchKernelGGL((k_enc_x3<true, true>), dim3(enc_grid), dim3(256), 8 * P16::BLK, st, a, hp.n_img, *series, WideSrc{});

@@ -83,7 +83,7 @@ EXPORTS = [
     "mshgnn_step_mse_series", "mshgnn_step_ce_series", "mshgnn_step_ce", "mshgnn_op_gemm", "mshgnn_op_gemm_workspace", "mshgnn_op_aggregate", "mshgnn_op_colsum", "mshgnn_op_colsum_workspace",
     "mshgnn_abi_version", "mshgnn_struct_size", "mshgnn_forward_src", "mshgnn_step_mse_src", "mshgnn_step_ce_src",
     "mshgnn_comm_unique_id", "mshgnn_comm_create", "mshgnn_comm_destroy", "mshgnn_comm_allreduce_mean", "mshgnn_comm_allreduce_sum",
-    "mshgnn_input_grad", "mshgnn_forward_series", "mshgnn_forward_series_stats_bytes",
+    "mshgnn_input_grad", "mshgnn_forward_series", "mshgnn_forward_series_stats_bytes", "mshgnn_step_mse_series_std", "mshgnn_step_ce_series_std",
 ]
 ABI_VERSION = 6      # include/mshgnn.h MSHGNN_ABI_VERSION: the ctypes structures above mirror THAT header
 
@@ -181,6 +181,9 @@ def load_library():
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.mshgnn_forward_series_stats_bytes.restype = C.c_int64
         lib.mshgnn_forward_series_stats_bytes.argtypes = [C.POINTER(MshgnnWindowDesc), C.c_int64]
+    if hasattr(lib, "mshgnn_step_mse_series_std"):      # the series steps' arguments + the stats scratch behind run_ptrs
+        lib.mshgnn_step_mse_series_std.argtypes = list(lib.mshgnn_step_mse_series.argtypes[:13]) + [C.c_void_p] + list(lib.mshgnn_step_mse_series.argtypes[13:])
+        lib.mshgnn_step_ce_series_std.argtypes = list(lib.mshgnn_step_mse_series_std.argtypes)
     lib.mshgnn_struct_size.restype = C.c_size_t
     lib.mshgnn_struct_size.argtypes = [C.c_int]
     lib.mshgnn_comm_unique_id.argtypes = [C.c_char_p, C.c_void_p]
@@ -694,40 +697,55 @@ class Engine:
         encoder gathers from the fp32 series and always materialises the windows)."""
         return self._step_series(False, store, starts, params_flat, out, grad_flat, loss, materialize)
 
-    def _step_series(self, ce: bool, store, starts, params_flat, out, grad_flat, loss, materialize):
+    def step_mse_series_std(self, store, starts: torch.Tensor, params_flat: torch.Tensor, out: Optional[torch.Tensor] = None,
+                            grad_flat: Optional[torch.Tensor] = None, loss: Optional[torch.Tensor] = None):
+        """`step_mse_series` on a STANDARDISED recipe (`recipe.normalize`, mshgnn_step_mse_series_std): a pre-pass leaves every (window, run)'s mean and
+        sd in the store's statistics scratch, the encoder standardises the fp32 series with them (both plans gather fp32: standardisation precedes the
+        bf16 rounding) and always materialises the standardised windows into the store's reusable buffers -- the weight-gradient pass reads them.
+        Returns (xs, y, out, loss[1], grad_flat) -- bit-identical to `store.assemble(starts)` followed by `step_mse`.  history in [2, 256]."""
+        return self._step_series(False, store, starts, params_flat, out, grad_flat, loss, True, std=True)
+
+    def step_ce_series_std(self, store, starts: torch.Tensor, params_flat: torch.Tensor, out: Optional[torch.Tensor] = None,
+                           grad_flat: Optional[torch.Tensor] = None, loss: Optional[torch.Tensor] = None):
+        """`step_mse_series_std` for the classification wrappers (mshgnn_step_ce_series_std).  Returns (xs, labels int32 [B, n_out], out, loss[1],
+        grad_flat) -- bit-identical to `store.assemble(starts)` followed by `step_ce`."""
+        return self._step_series(True, store, starts, params_flat, out, grad_flat, loss, True, std=True)
+
+    def _step_series(self, ce: bool, store, starts, params_flat, out, grad_flat, loss, materialize, std: bool = False):
+        name = ("mshgnn_step_ce_series" if ce else "mshgnn_step_mse_series") + ("_std" if std else "")
+        if not hasattr(self.lib, name):
+            raise MshgnnError(f"this build of the library has no {name}")
         self._check_flat(params_flat, "params_flat")
         if not starts.is_cuda or starts.dtype != torch.int64:
             raise ValueError("starts must be a device int64 tensor")
         B = int(starts.numel())
-        r = store.recipe
         xs, y, q = store._buffers(B)
         if y is None:
             raise ValueError("the recipe has no labels")
         out, grad_flat, loss = self._results(B, out, grad_flat, loss)
-        src16, run_ptrs = store.series_step_args(bf16=self.storage != "x3")
+        fp32_gather = std or self.storage == "x3"
+        src16, run_ptrs = store.series_step_args(bf16=not fp32_gather)
         if self.storage == "x3" and not materialize:
             raise ValueError("the split plan's weight-gradient kernel reads materialised windows: materialize=False is a bf16-plan option")
         xp = (C.c_void_p * len(xs))(*[x.data_ptr() for x in xs]) if materialize else None
         pitch = (C.c_int64 * len(xs))(*[x.shape[1] for x in xs]) if materialize else None
         if not materialize:
             xs = None
+        extra = []
+        if std:
+            stats = store._stats_buffer(B)
+            extra = [stats.data_ptr() if stats is not None else None]
         ws = self.workspace(B, True)
         self._tickets[B] = self._tickets.get(B, 0) + 1; self._chunked[B] = True
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        self._vouch_run_ptrs(store, self.storage == "x3", stream)
+        self._vouch_run_ptrs(store, fp32_gather, stream)
         with torch.cuda.device(self.device):
-            if ce:
-                labels = torch.empty(B, self.n_out, dtype=torch.int32, device=self.device)
-                _check(self.lib, self.lib.mshgnn_step_ce_series(self._plan, C.byref(store.desc), store._src, src16, store._pitch, store._rows, starts.data_ptr(), B,
-                                                            xp, pitch, y.data_ptr(), labels.data_ptr(), run_ptrs.data_ptr(),
-                                                            params_flat.data_ptr(), out.data_ptr(), loss.data_ptr(), grad_flat.data_ptr(), ws.data_ptr(), stream),
-                       "mshgnn_step_ce_series")
-                return xs, labels, out, loss, grad_flat
-            _check(self.lib, self.lib.mshgnn_step_mse_series(self._plan, C.byref(store.desc), store._src, src16, store._pitch, store._rows, starts.data_ptr(), B,
-                                                         xp, pitch, y.data_ptr(), q.data_ptr() if q is not None else None, run_ptrs.data_ptr(),
-                                                         params_flat.data_ptr(), out.data_ptr(), loss.data_ptr(), grad_flat.data_ptr(), ws.data_ptr(), stream),
-                   "mshgnn_step_mse_series")
-        return xs, y, out, loss, grad_flat
+            labels = torch.empty(B, self.n_out, dtype=torch.int32, device=self.device) if ce else None
+            by_product = labels if ce else q      # the contact flags, or the quaternion that travels with the regression labels
+            _check(self.lib, getattr(self.lib, name)(self._plan, C.byref(store.desc), store._src, src16, store._pitch, store._rows, starts.data_ptr(), B,
+                                                     xp, pitch, y.data_ptr(), by_product.data_ptr() if by_product is not None else None, run_ptrs.data_ptr(), *extra,
+                                                     params_flat.data_ptr(), out.data_ptr(), loss.data_ptr(), grad_flat.data_ptr(), ws.data_ptr(), stream), name)
+        return xs, (labels if ce else y), out, loss, grad_flat
 
     @staticmethod
     def _vouch_run_ptrs(store, fp32_gather: bool, stream):

@@ -492,14 +492,18 @@ class _MSHGNNBase(nn.Module):
 
     def fused_training_step_windows(self, batch):
         """`fused_training_step` for a `windows.WindowBatch`: the encoder gathers the batch's inputs straight from the sequence's resident
-        series (mshgnn_step_mse_series / mshgnn_step_ce_series -- no separate assembly pass over the windows); the labels (and the
-        materialised windows) are left on the batch.  Returns (out, loss) or None when this route does not apply: the model has not seen
-        its lazy-initialising forward yet, a plan other than bf16 / split-bf16 on the LDS-resident kernels, a store whose dtype is not the plan's
-        input dtype or that is not fast-layout / unstandardised, or whose recipe differs from the model's node types and widths, plus fused_training_step's own conditions."""
+        series (mshgnn_step_mse_series / mshgnn_step_ce_series, standardised recipes: mshgnn_step_mse_series_std / mshgnn_step_ce_series_std -- no
+        separate assembly pass over the windows); the labels (and the materialised windows) are left on the batch.  Returns (out, loss) or None when
+        this route does not apply: the model has not seen its lazy-initialising forward yet, a plan other than bf16 / split-bf16 on the LDS-resident
+        kernels, a store whose dtype is not the plan's input dtype or that is not fast-layout, a standardised recipe whose history is outside [2, 256]
+        or shorter than 8 with node rows of several runs, or a recipe that differs from the model's node types and widths, plus fused_training_step's
+        own conditions."""
         spec = self._spec
         store, B = batch.store, batch.batch_size
         r = store.recipe
-        if spec is None or not self._fused_activation or store.dtype not in ("bf16", "x3", "f32") or r.normalize or not store.desc.fast_layout or not r.label_cols:
+        if spec is None or not self._fused_activation or store.dtype not in ("bf16", "x3", "f32") or not store.desc.fast_layout or not r.label_cols:
+            return None
+        if r.normalize and (not 2 <= r.history <= 256 or (r.history < 8 and store.desc.n_runs > store.desc.n_rows)):      # (what the standardising encoders refuse: assembled)
             return None
         if list(r.node_types) != list(spec.node_types) or any(r.num_nodes[t] != spec.num_nodes[t] or r.width(t) != spec.widths[t] for t in r.node_types):
             return None
@@ -519,7 +523,10 @@ class _MSHGNNBase(nn.Module):
                     raise ValueError(f"edge_index_dict[{et}] differs from the topology this model was compiled for")
             self._checked_batches.add(B)
         self._flat_params(store.device)
-        step = e.step_mse_series if spec.regression else e.step_ce_series
+        if r.normalize:
+            step = e.step_mse_series_std if spec.regression else e.step_ce_series_std
+        else:
+            step = e.step_mse_series if spec.regression else e.step_ce_series
 
         def run(g):
             xs, y, out, loss, _ = step(store, batch.starts, self._flat, grad_flat=g)

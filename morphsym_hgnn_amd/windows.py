@@ -174,6 +174,7 @@ class SequenceStore:
         self._rows = (C.c_int64 * len(self.series))(*[a.shape[1] - 8 for a in self.series])
         self._src16 = None; self._run_ptrs = None
         self._eval_cache = {}
+        self._stats_cache = {}
 
     def __len__(self) -> int:
         """Number of windows (the reference's dataset length: rows - history + 1)."""
@@ -192,6 +193,15 @@ class SequenceStore:
             q = torch.empty(B, 4, dtype=torch.float32, device=self.device) if r.quat_series else None
             self._cache = {B: (xs, y, q)}          # one batch size at a time
         return self._cache[B]
+
+    def _stats_buffer(self, B: int) -> Optional[torch.Tensor]:
+        """The statistics scratch of the standardised training steps (`Engine.step_mse_series_std` / `step_ce_series_std`) for a batch of B windows:
+        `mshgnn_forward_series_stats_bytes` of fp64, made once per batch size (one batch size at a time, like `_buffers`); None for an
+        unstandardised recipe (the library refuses it there)."""
+        if B not in self._stats_cache:
+            nbytes = int(self.lib.mshgnn_forward_series_stats_bytes(C.byref(self.desc), B))
+            self._stats_cache = {B: torch.empty(nbytes // 8, dtype=torch.float64, device=self.device) if nbytes else None}
+        return self._stats_cache[B]
 
     def assemble(self, starts, reuse_buffers: bool = False) -> Tuple[List[torch.Tensor], Optional[torch.Tensor], Optional[torch.Tensor]]:
         """starts: window start rows (== the reference's dataset indices), a host sequence / tensor (checked on the host) or
@@ -259,7 +269,7 @@ class WindowBatch:
     """One minibatch of window indices of a `SequenceStore`, with the attributes the reference's wrappers read off a PyG batch
     (`x_dict`, `edge_index_dict`, `y`, `r_o`, `batch_size`; gnnLightning.py:680-722).  Nothing is gathered when it is made: a wrapper's
     `training_step` hands the indices to the engine, whose encoder gathers its inputs from the resident series
-    (`models.fused_training_step_windows` -> `mshgnn_step_mse_series` / `mshgnn_step_ce_series`) and leaves the labels here; the evaluation steps
+    (`models.fused_training_step_windows` -> `mshgnn_step_mse_series` / `mshgnn_step_ce_series`, standardised recipes: their `_std` forms) and leaves the labels here; the evaluation steps
     under torch.no_grad() do the same without materialising anything (`models.forward_windows` -> `mshgnn_forward_series`); any other consumer
     (the two-call route, a model the fused routes do not take) gets the windows assembled on first access (`SequenceStore.assemble`, the store's reusable buffers:
     consume a batch before asking the store for the next one)."""
