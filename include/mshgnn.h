@@ -348,6 +348,19 @@ int mshgnn_assemble_windows(const mshgnn_window_desc* desc, const float* const* 
                             const int64_t* src_rows, const int64_t* starts /* device int64[batch] */, int64_t batch,
                             void* const* x_out, const int64_t* x_pitch, float* y_out, float* quat_out, void* stream);
 
+/* Dataset indices -> window start rows, for a dataset of SEVERAL sequences whose series are concatenated row-wise into one set of source arrays (the
+ * reference's ConcatDataset of per-sequence Subsets, research/train_regression-grf_msgn.py:57-73).  A view of the dataset takes the windows [lo_s, hi_s) of
+ * sequence s, in sequence order: cum (DEVICE int64[n_seq + 1], cum[0] = 0, non-decreasing) holds the cumulative window counts, first_row (DEVICE
+ * int64[n_seq]) the row of the concatenated series at which window lo_s of sequence s starts.  One thread per index i = index[b]: it finds s with
+ * cum[s] <= i < cum[s + 1] (binary search over cum, staged in LDS for n_seq <= 1024, in global memory beyond) and writes
+ * starts_out[b] = first_row[s] + (i - cum[s]); empty ranges are never selected.  An index outside [0, cum[n_seq]) writes start row 0 and stores 1 to
+ * bad_out[0] (a plain store of the constant: every writer writes the same value).  bad_out is NOT cleared here -- the caller zeroes it and reads it
+ * when it likes, so that the flag accumulates over an epoch.  With start row 0 a whole window of the first sequence, every row written is safe to hand
+ * to the gathers above and below, which do not check `starts`.  MSHGNN_EINVAL before any launch: a null pointer, n_seq < 1, batch < 1 (cum and first_row
+ * live on the device and are not looked at by the host).  One launch on `stream`, no allocation, no host read: capturable in a HIP graph.          */
+int mshgnn_dataset_starts(const int64_t* cum, const int64_t* first_row, int32_t n_seq, const int64_t* index /* device int64[batch] */, int64_t batch,
+                          int64_t* starts_out /* device int64[batch] */, int32_t* bad_out /* device int32[1] */, void* stream);
+
 /* One training step straight from a sequence's resident raw series: mshgnn_assemble_windows + mshgnn_step_mse with the window gather FUSED INTO THE
  * ENCODER (no separate pass that writes and re-reads the batch's windows): the encoder kernel gathers its K chunks from bf16 copies of the series
  * (src_bf16: same shapes / column strides as src, every column followed by >= 8 elements of slack: src_cstride >= src_rows + 8), and writes the

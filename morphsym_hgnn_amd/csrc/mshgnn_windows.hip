@@ -1,4 +1,5 @@
 // mshgnn_assemble_windows (include/mshgnn.h): a batch of windows gathered from a sequence's resident raw series into the engine's input layout, and their labels.
+// mshgnn_dataset_starts: the dataset indices of several concatenated sequences -> the start rows the gathers take.
 // The series entry points that fuse this gather into the encoder are mshgnn.hip's; WindowArgs (mshgnn_device.hpp) is what the two share.
 #include "mshgnn_device.hpp"
 
@@ -218,6 +219,55 @@ extern "C" int mshgnn_assemble_windows(const mshgnn_window_desc* d, const float*
     }
     if (d->n_label > 0 || (quat_out && d->quat_src >= 0))
         hipLaunchKernelGGL(k_window_labels, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, st, a);
+    HIPCHK(hipGetLastError());
+    return MSHGNN_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------
+// A dataset of several sequences (train_regression-grf_msgn.py:57-73: ConcatDataset of per-sequence Subsets): the sequences' series are concatenated
+// row-wise, a view takes a window range per sequence, and a dataset index becomes a start row of the concatenated series.  One thread per index:
+// binary search for the sequence over the cumulative window counts (8 bytes each: up to DATASET_LDS_SEQ sequences they are staged in LDS once per
+// workgroup, ten dependent LDS reads per index instead of ten trips to L2; beyond that the search reads global memory), one load of the sequence's
+// first row, one store.  Invariant of the search: cum[lo] <= i < cum[hi], so an empty range (cum[s] == cum[s + 1]) is never the answer and lo stays
+// inside [0, n_seq - 1] whatever cum holds.  An index outside the view gets row 0 and raises the caller's flag with a plain store of 1.
+// ------------------------------------------------------------------------------------------------------
+constexpr int DATASET_LDS_SEQ = 1024;
+
+template <bool LDS> __global__ __launch_bounds__(256) void k_dataset_starts(const int64_t* __restrict__ cum, const int64_t* __restrict__ first_row, int n_seq,
+                                                                            const int64_t* __restrict__ index, int64_t batch, int64_t* __restrict__ starts,
+                                                                            int32_t* __restrict__ bad) {
+    __shared__ int64_t s_cum[LDS ? DATASET_LDS_SEQ + 1 : 1];
+    if constexpr (LDS) {
+        for (int k = threadIdx.x; k <= n_seq; k += 256) s_cum[k] = cum[k];
+        __syncthreads();
+    }
+    const int64_t* c = LDS ? s_cum : cum;
+    const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (b >= batch) return;
+    const int64_t i = index[b];
+    if (i < 0 || i >= c[n_seq]) {
+        starts[b] = 0;
+        bad[0] = 1;
+        return;
+    }
+    int lo = 0, hi = n_seq;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (c[mid] <= i) lo = mid; else hi = mid;
+    }
+    starts[b] = first_row[lo] + (i - c[lo]);
+}
+
+extern "C" int mshgnn_dataset_starts(const int64_t* cum, const int64_t* first_row, int32_t n_seq, const int64_t* index, int64_t batch, int64_t* starts_out,
+                                     int32_t* bad_out, void* stream) {
+    if (!cum || !first_row || !index || !starts_out || !bad_out) return set_err(MSHGNN_EINVAL, "null argument to mshgnn_dataset_starts");
+    if (n_seq < 1) return set_err(MSHGNN_EINVAL, "mshgnn_dataset_starts: n_seq must be >= 1");
+    if (batch < 1) return set_err(MSHGNN_EINVAL, "mshgnn_dataset_starts: batch must be >= 1");
+    if (batch > ((int64_t)1 << 31) * 256 - 256) return set_err(MSHGNN_EUNSUPPORTED, "mshgnn_dataset_starts: more than 2^39 indices in one call");
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)((batch + 255) / 256));
+    if (n_seq <= DATASET_LDS_SEQ) hipLaunchKernelGGL(k_dataset_starts<true>, grid, dim3(256), 0, st, cum, first_row, (int)n_seq, index, batch, starts_out, bad_out);
+    else hipLaunchKernelGGL(k_dataset_starts<false>, grid, dim3(256), 0, st, cum, first_row, (int)n_seq, index, batch, starts_out, bad_out);
     HIPCHK(hipGetLastError());
     return MSHGNN_OK;
 }

@@ -272,14 +272,19 @@ class WindowBatch:
     (`models.fused_training_step_windows` -> `mshgnn_step_mse_series` / `mshgnn_step_ce_series`, standardised recipes: their `_std` forms) and leaves the labels here; the evaluation steps
     under torch.no_grad() do the same without materialising anything (`models.forward_windows` -> `mshgnn_forward_series`); any other consumer
     (the two-call route, a model the fused routes do not take) gets the windows assembled on first access (`SequenceStore.assemble`, the store's reusable buffers:
-    consume a batch before asking the store for the next one)."""
+    consume a batch before asking the store for the next one).
+
+    Start rows given as a DEVICE tensor are not checked (see the constructor); indices that a sampler produces on the device go through a
+    `ResidentDataset` view (`DatasetView.batch`), whose mapping kernel bounds every one of them -- one sequence is a dataset of one."""
 
     def __init__(self, store: SequenceStore, starts, edge_index_dict):
         st = starts if isinstance(starts, torch.Tensor) else torch.as_tensor(np.asarray(starts), dtype=torch.int64)
         st = st.flatten().to(torch.int64)
         # Contract: every start index i satisfies 0 <= i and i + history <= store.n_rows (the fused-gather kernels read the series at
-        # [i, i + history) without a bound check).  Host indices are checked here; DEVICE indices are taken as they are, because checking them costs a
-        # host synchronisation per batch -- `store.check_starts = True` turns that check on (debugging a sampler).
+        # [i, i + history) without a bound check).  Host indices are checked here; DEVICE start rows are taken as they are, because checking them costs a
+        # host synchronisation per batch -- `store.check_starts = True` turns that check on (debugging a sampler).  The CHECKED route for indices made on
+        # the device is a `ResidentDataset` view: `view.batch(device_indices, ...)` maps dataset indices to start rows with `mshgnn_dataset_starts`, which
+        # sends every index outside the view to row 0 (always a whole window) and raises a flag that `view.check()` reads once per epoch.
         if not st.is_cuda or getattr(store, "check_starts", False):
             if st.numel() < 1 or int(st.min()) < 0 or int(st.max()) + store.recipe.history > store.n_rows:
                 raise IndexError("window index out of range")
@@ -316,3 +321,205 @@ class WindowBatch:
         if self._q is None:
             self._assemble()
         return self._q
+
+
+# --- a resident dataset of several sequences ------------------------------------------------------------------------------------------------------
+# The reference's scripts never train on one sequence: research/train_regression-grf_msgn.py:57-73 cuts each of eight sequences at
+# int(np.round((len - 1) * 0.85)) into a training and a validation Subset, joins them with ConcatDataset and shuffles minibatches across all of them.
+# Here the sequences' series are concatenated row-wise into ONE SequenceStore and a dataset index becomes a start row of the concatenated series
+# (host: `dataset_index_map` / `dataset_lookup`; device: mshgnn_dataset_starts), so every route that takes a store runs unchanged.
+
+def dataset_window_counts(lengths: Sequence[int], history: int) -> List[int]:
+    """Windows per sequence (rows - history + 1: the reference's dataset length); a sequence shorter than one window is refused, naming its position."""
+    for s, n in enumerate(lengths):
+        if int(n) < history:
+            raise ValueError(f"sequence {s} has {int(n)} rows: shorter than one window of {history} steps")
+    return [int(n) - history + 1 for n in lengths]
+
+
+def dataset_split_ranges(lengths: Sequence[int], history: int, fraction: float = 0.85, drop_last: bool = True) -> Tuple[List[Tuple[int, int]], List[Tuple[int, int]]]:
+    """The training and validation window ranges of the reference's scripts, per sequence (train_regression-grf_msgn.py:63-67): with len_s windows,
+    m = len_s - 1 (drop_last: "dynamics models can't use the last entry") or len_s, k = int(np.round(m * fraction)) -- numpy's round-half-even on the
+    float product --, train = [0, k), val = [k, m)."""
+    train, val = [], []
+    for n in dataset_window_counts(lengths, history):
+        m = n - 1 if drop_last else n
+        k = min(max(int(np.round(m * fraction)), 0), m)
+        train.append((0, k)); val.append((k, m))
+    return train, val
+
+
+def dataset_index_map(lengths: Sequence[int], history: int, ranges: Optional[Sequence[Tuple[int, int]]] = None) -> Tuple[List[int], List[int]]:
+    """(cum, first_row) of a view of a dataset whose sequences have `lengths` rows: sequence s contributes its windows [lo_s, hi_s) (`ranges`; None: all of
+    them, an empty range is allowed), in sequence order.  cum[s] .. cum[s + 1] are the view's indices that fall into sequence s (cum has one entry more
+    than there are sequences, cum[0] == 0), first_row[s] the row of the CONCATENATED series at which window lo_s of sequence s starts.  Index i with
+    cum[s] <= i < cum[s + 1] is the window that starts at first_row[s] + (i - cum[s]) -- what `ConcatDataset([Subset(d_s, arange(lo_s, hi_s))])[i]` is.
+    No window straddles two sequences: hi_s <= rows_s - history + 1."""
+    counts = dataset_window_counts(lengths, history)
+    if ranges is None:
+        ranges = [(0, n) for n in counts]
+    if len(ranges) != len(counts):
+        raise ValueError(f"{len(ranges)} ranges for {len(counts)} sequences")
+    cum, first_row, row0 = [0], [], 0
+    for s, ((lo, hi), n) in enumerate(zip(ranges, counts)):
+        lo, hi = int(lo), int(hi)
+        if not 0 <= lo <= hi <= n:
+            raise ValueError(f"range [{lo}, {hi}) of sequence {s} is outside its {n} windows")
+        cum.append(cum[-1] + hi - lo)
+        first_row.append(row0 + lo)
+        row0 += int(lengths[s])
+    return cum, first_row
+
+
+def dataset_lookup(cum: Sequence[int], first_row: Sequence[int], index: int) -> int:
+    """The start row of dataset index `index` (the host mirror of one thread of mshgnn_dataset_starts); IndexError outside [0, cum[-1])."""
+    i = int(index)
+    if not 0 <= i < cum[-1]:
+        raise IndexError(f"dataset index {i} out of range [0, {cum[-1]})")
+    lo, hi = 0, len(cum) - 1          # cum[lo] <= i < cum[hi]
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        if cum[mid] <= i:
+            lo = mid
+        else:
+            hi = mid
+    return first_row[lo] + (i - cum[lo])
+
+
+class ResidentDataset(SequenceStore):
+    """Several recorded sequences on the GPU as ONE `SequenceStore`: every named series is the row-wise concatenation of the sequences' series (column-major,
+    8 elements of slack behind every column as before -- a 16-byte load that runs past a window's last step lands in the next sequence's rows, whose
+    elements are cut or discarded like the slack's; only the last sequence relies on the slack).  Everything that takes a store takes this one and launches
+    the same kernels (`assemble`, the fused training and evaluation routes, `wrappers.evaluate_sequence`): their `starts` are rows of the concatenated
+    series.
+
+    Dataset indices are the reference's: sequence s with n_s rows has n_s - history + 1 windows, index i of sequence s starts at row i of that sequence,
+    no window straddles two sequences, `len(dataset)` is the sum.  `view()`, `subset(ranges)` and `split()` give `DatasetView`s that map indices to start
+    rows, on the host for host indices and with `mshgnn_dataset_starts` for device indices."""
+
+    def __init__(self, sequences: List[Dict[str, np.ndarray]], recipe: WindowRecipe, dtype: str = "bf16", device=None, fast: bool = True):
+        if len(sequences) < 1:
+            raise ValueError("a dataset needs at least one sequence")
+        names = recipe.series()
+        lengths, cols, parts = [], None, {s: [] for s in names}
+        for k, seq in enumerate(sequences):
+            arrs = {}
+            for s in names:
+                a = np.asarray(seq[s])
+                arrs[s] = a.reshape(a.shape[0], -1)
+            n = min(a.shape[0] for a in arrs.values())          # (a store's rows: the shortest of its series)
+            if n < recipe.history:
+                raise ValueError(f"sequence {k} has {n} rows: shorter than one window of {recipe.history} steps")
+            c = {s: a.shape[1] for s, a in arrs.items()}
+            if cols is None:
+                cols = c
+            elif c != cols:
+                bad = [s for s in names if c[s] != cols[s]]
+                raise ValueError(f"sequence {k}: series {bad} have {[c[s] for s in bad]} columns, sequence 0 has {[cols[s] for s in bad]}")
+            lengths.append(int(n))
+            for s in names:
+                parts[s].append(arrs[s][:n])
+        super().__init__({s: np.concatenate(parts[s], 0) for s in names}, recipe, dtype=dtype, device=device, fast=fast)
+        self.seq_rows = lengths
+        self.seq_windows = dataset_window_counts(lengths, recipe.history)
+        self.seq_first_row = [int(x) for x in np.concatenate([[0], np.cumsum(lengths)[:-1]])]
+
+    def __len__(self) -> int:
+        """Number of windows: the sum over the sequences (fewer than rows - history + 1 of the concatenated series: nothing straddles)."""
+        return sum(self.seq_windows)
+
+    def subset(self, ranges: Sequence[Tuple[int, int]]) -> "DatasetView":
+        """The windows [lo_s, hi_s) of every sequence s, concatenated in sequence order; an empty range is allowed."""
+        return DatasetView(self, ranges)
+
+    def view(self) -> "DatasetView":
+        """Every window of every sequence."""
+        return DatasetView(self, [(0, n) for n in self.seq_windows])
+
+    def split(self, fraction: float = 0.85, drop_last: bool = True) -> Tuple["DatasetView", "DatasetView"]:
+        """(train, val) views with the scripts' arithmetic per sequence (`dataset_split_ranges`)."""
+        train, val = dataset_split_ranges(self.seq_rows, self.recipe.history, fraction, drop_last)
+        return DatasetView(self, train), DatasetView(self, val)
+
+
+class DatasetView:
+    """A range of windows per sequence of a `ResidentDataset`, indexed 0 .. len(view) - 1 in sequence order like the reference's
+    `ConcatDataset` of `Subset`s.  Host indices are checked and mapped on the host; device indices are mapped by `mshgnn_dataset_starts`, which
+    writes start row 0 for an index outside the view and sets the view's `bad` word -- no host synchronisation per batch; `check()` reads the word."""
+
+    def __init__(self, dataset: ResidentDataset, ranges: Sequence[Tuple[int, int]]):
+        self.dataset = dataset
+        self.ranges = [(int(lo), int(hi)) for lo, hi in ranges]
+        self.cum, self.first_row = dataset_index_map(dataset.seq_rows, dataset.recipe.history, self.ranges)
+        dev = dataset.device
+        self._cum_np, self._first_np = np.asarray(self.cum, dtype=np.int64), np.asarray(self.first_row, dtype=np.int64)
+        self._cum = torch.from_numpy(self._cum_np).to(dev)
+        self._first = torch.from_numpy(self._first_np).to(dev)
+        self.bad = torch.zeros(1, dtype=torch.int32, device=dev)      # set by the mapping kernel, zeroed by check(): accumulates over an epoch
+
+    def __len__(self) -> int:
+        return self.cum[-1]
+
+    def starts(self, indices, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Start rows (device int64, rows of the dataset's concatenated series) of the view's `indices`.  A host sequence / tensor is checked here
+        (IndexError) and mapped on the host; a device int64 tensor goes through mshgnn_dataset_starts on the current stream (`out`: a device int64
+        tensor of the same size to write into -- a captured step's static buffer)."""
+        ds = self.dataset
+        ix = indices if isinstance(indices, torch.Tensor) else torch.as_tensor(np.asarray(indices), dtype=torch.int64)
+        if ix.numel() < 1:
+            raise ValueError("no window indices")
+        if not ix.is_cuda:
+            ix = ix.flatten().to(torch.int64).numpy()
+            if int(ix.min()) < 0 or int(ix.max()) >= len(self):
+                raise IndexError(f"dataset index out of range [0, {len(self)})")
+            s = np.searchsorted(self._cum_np, ix, side="right") - 1
+            st = torch.from_numpy(self._first_np[s] + (ix - self._cum_np[s])).to(ds.device)
+            if out is not None:
+                out.copy_(st)
+                return out
+            return st
+        if ix.dtype != torch.int64 or not ix.is_contiguous():
+            ix = ix.to(torch.int64).contiguous()
+        ix = ix.view(-1)
+        if out is None:
+            out = torch.empty_like(ix)
+        elif not out.is_cuda or out.dtype != torch.int64 or out.numel() != ix.numel() or not out.is_contiguous():
+            raise ValueError("out must be a contiguous device int64 tensor with one element per index")
+        if not hasattr(ds.lib, "mshgnn_dataset_starts"):
+            raise eng.MshgnnError("this build of the library has no mshgnn_dataset_starts")
+        with torch.cuda.device(ds.device):
+            rc = ds.lib.mshgnn_dataset_starts(self._cum.data_ptr(), self._first.data_ptr(), len(self.first_row), ix.data_ptr(), ix.numel(), out.data_ptr(),
+                                              self.bad.data_ptr(), C.c_void_p(torch.cuda.current_stream(ds.device).cuda_stream))
+        eng._check(ds.lib, rc, "mshgnn_dataset_starts")
+        return out
+
+    def check(self) -> None:
+        """One host synchronisation: IndexError if a device index mapped since the last check was outside the view (the flag is cleared)."""
+        if int(self.bad.item()) != 0:
+            self.bad.zero_()
+            raise IndexError(f"a device index given to this view was outside [0, {len(self)}): its window was replaced by the view's row 0")
+
+    def batch(self, indices, edge_index_dict) -> WindowBatch:
+        """An ordinary `WindowBatch` of the dataset whose `starts` are the mapped rows; `indices` (as given, on the device) stays on it."""
+        st = self.starts(indices)
+        wb = WindowBatch(self.dataset, st, edge_index_dict)
+        ix = indices if isinstance(indices, torch.Tensor) else torch.as_tensor(np.asarray(indices), dtype=torch.int64)
+        wb.indices = ix.reshape(-1).to(st.device, torch.int64)
+        return wb
+
+    def epoch(self, batch_size: int, generator: Optional[torch.Generator] = None, shuffle: bool = True, drop_last: bool = False):
+        """Device index tensors of one pass over the view: ONE torch.randperm per epoch (on the device; with a host generator it is drawn on the host
+        and copied once), then slices of it -- no host round trip per batch.  When the generator is exhausted, `check()` runs once."""
+        if batch_size < 1:
+            raise ValueError("batch_size must be >= 1")
+        n, dev = len(self), self.dataset.device
+        if not shuffle:
+            order = torch.arange(n, dtype=torch.int64, device=dev)
+        elif generator is not None and generator.device.type == "cpu":
+            order = torch.randperm(n, generator=generator).to(dev)
+        else:
+            order = torch.randperm(n, generator=generator, device=dev)
+        stop = n - n % batch_size if drop_last else n
+        for lo in range(0, stop, batch_size):
+            yield order[lo:lo + batch_size]
+        self.check()

@@ -538,9 +538,15 @@ class GraphedTrainingStep:
     before `configure_optimizers()`) or a `torch.optim` optimizer created with `capturable=True`.  The model's parameters, the optimizer state and the metric
     state are restored after the warm-up steps the capture needs, so constructing this object does not train.
 
-    Returns the step's loss as a device tensor (a static buffer: read it before the next call)."""
+    Returns the step's loss as a device tensor (a static buffer: read it before the next call).
 
-    def __init__(self, wrapper, optimizer, example_batch, warmup: int = 3):
+    `index_source` (a `windows.DatasetView`): the batch is a set of DATASET INDICES of that view.  `example_batch` is then `view.batch(indices, edge_index_dict)`
+    (or anything with `indices` and `edge_index_dict`); the static input is one device int64 tensor of indices, and the captured region runs the index
+    mapping (`mshgnn_dataset_starts`, which bounds every index) + the step straight from the resident series + the optimizer.  `load(indices)` /
+    `__call__(indices)` copy the next batch's indices (host or device, same count) into it; `index_source.check()` tells afterwards whether any was out
+    of range."""
+
+    def __init__(self, wrapper, optimizer, example_batch, warmup: int = 3, index_source=None):
         import copy
         from .optim import FlatAdam
         if isinstance(optimizer, FlatAdam) and not optimizer._graph_safe:
@@ -548,7 +554,14 @@ class GraphedTrainingStep:
         if not isinstance(optimizer, FlatAdam) and not all(g.get("capturable", False) for g in optimizer.param_groups):
             raise ValueError("GraphedTrainingStep needs an optimizer whose step count lives on the device (capturable=True)")
         self.wrapper, self.optimizer = wrapper, optimizer
-        self.batch = self._static_copy(example_batch)
+        self.index_source = index_source
+        if index_source is not None:
+            from .windows import WindowBatch
+            self.indices = torch.as_tensor(example_batch.indices).to(index_source.dataset.device, torch.int64).flatten().clone()
+            self._starts = index_source.starts(self.indices)      # (the static start rows the captured mapping kernel rewrites)
+            self.batch = WindowBatch(index_source.dataset, self._starts, example_batch.edge_index_dict)
+        else:
+            self.batch = self._static_copy(example_batch)
         dev = next(wrapper.parameters()).device
         snap_p = [p.detach().clone() for p in wrapper.parameters()]
         flat_opt = isinstance(optimizer, FlatAdam)
@@ -597,6 +610,9 @@ class GraphedTrainingStep:
         return out
 
     def _eager_step(self):
+        if self.index_source is not None:
+            self.index_source.starts(self.indices, out=self._starts)
+            self.batch._x = self.batch._y = self.batch._q = None      # (nothing of the previous step's batch is current)
         self.optimizer.zero_grad(set_to_none=True)
         loss = self.wrapper.training_step(self.batch, 0)
         loss.backward()
@@ -604,7 +620,14 @@ class GraphedTrainingStep:
         return loss.detach()
 
     def load(self, batch):
-        """Copy a batch's tensors into the static ones (host or device sources; same shapes)."""
+        """Copy a batch's tensors into the static ones (host or device sources; same shapes).  With an `index_source`: `batch` is the next batch's dataset
+        indices (or a batch that carries them as `indices`)."""
+        if self.index_source is not None:
+            ix = torch.as_tensor(batch if torch.is_tensor(batch) else getattr(batch, "indices", batch))      # (torch.Tensor has an `indices` of its own)
+            if ix.numel() != self.indices.numel():
+                raise ValueError(f"{ix.numel()} indices for a step captured on {self.indices.numel()}")
+            self.indices.copy_(ix.reshape(self.indices.shape), non_blocking=True)
+            return
         for k, v in vars(batch).items():
             dst = getattr(self.batch, k, None)
             if torch.is_tensor(v) and torch.is_tensor(dst):
@@ -625,10 +648,17 @@ def evaluate_sequence(wrapper, store, edge_index_dict, batch_size: int, stride: 
     0, stride, 2 stride, ... of `store` in batches of `batch_size` (the last one ragged) through the wrapper's `test_step` under torch.no_grad() --
     with `fused_evaluation_step` straight from the resident series.  `edge_index_dict`: the edges of ONE window (tiled per batch here) or a
     callable batch size -> edge_index_dict.  Returns the predictions [n_windows, ...] in window order; the epoch's metrics are left in the
-    wrapper's state (`on_test_epoch_end` has run: `wrapper.logged`, the metric attributes)."""
+    wrapper's state (`on_test_epoch_end` has run: `wrapper.logged`, the metric attributes).
+
+    `store` may be a `windows.DatasetView` (or a `ResidentDataset`: all of it): the view's indices 0, stride, 2 stride, ... are swept through `view.batch`,
+    the predictions come back in dataset-index order."""
     if batch_size < 1 or stride < 1:
         raise ValueError("batch_size and stride must be >= 1")
-    starts = torch.arange(0, len(store), stride, dtype=torch.int64, device=store.device)
+    from .windows import DatasetView, ResidentDataset
+    view = store.view() if isinstance(store, ResidentDataset) else store if isinstance(store, DatasetView) else None
+    if view is not None:
+        store = view.dataset
+    starts = torch.arange(0, len(view if view is not None else store), stride, dtype=torch.int64, device=store.device)      # (a view: its indices)
     r = store.recipe
     edges = {}
 
@@ -649,7 +679,7 @@ def evaluate_sequence(wrapper, store, edge_index_dict, batch_size: int, stride: 
         wrapper.on_test_epoch_start()
         for i, lo in enumerate(range(0, int(starts.numel()), batch_size)):
             st = starts[lo:lo + batch_size]
-            batch = store.batch(st, edges_for(int(st.numel())))
+            batch = (view if view is not None else store).batch(st, edges_for(int(st.numel())))
             y, y_pred = wrapper.step_helper_function(batch)
             if getattr(wrapper, "body_to_world_frame", False):
                 wrapper.calculate_losses_step_worldframe(y, y_pred, batch.r_o.view(batch.batch_size, 4))
@@ -657,4 +687,6 @@ def evaluate_sequence(wrapper, store, edge_index_dict, batch_size: int, stride: 
                 wrapper.calculate_losses_step(y, y_pred)
             preds.append(y_pred.clone())
         wrapper.on_test_epoch_end()
+    if view is not None:
+        view.check()
     return torch.cat(preds, 0)
