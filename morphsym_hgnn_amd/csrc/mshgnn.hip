@@ -19,6 +19,7 @@
 //
 // No CPU fallback exists: every entry point launches HIP kernels or fails loudly.
 #include "mshgnn_slab.hpp"
+#include "mshgnn_launch.hpp"
 extern "C" const char* mshgnn_last_error(void) { return g_err.c_str(); }
 extern "C" const char* mshgnn_version(void) { return "mshgnn 0.5 (gfx950)"; }
 extern "C" int mshgnn_abi_version(void) { return MSHGNN_ABI_VERSION; }
@@ -1253,210 +1254,12 @@ __global__ __launch_bounds__(256) void k_gradw_f32(GradwArgs a) {
 #ifndef GW_WPS
 #define GW_WPS 3
 #endif
-template <int IPL> __global__ __launch_bounds__(256, GW_WPS) void k_gradw_bf16(GradwArgs a) {
-    using T = __bf16;
-    constexpr int I1 = IPL - 1;       // index of a lane's second item (== 0 with one item per lane)
-    // two LDS stages: the staging writes of step s+1 go to the other stage while step s's MFMAs read this one -> one
-    // barrier per step and LDS writes overlap the MFMAs
-#ifndef GW_DEEP
-#define GW_DEEP 0   // measured: the shallow pipeline at 3 workgroups/CU (132 us) beats the deep one at 2 (153 us)
-#endif
-    __shared__ __attribute__((aligned(16))) __bf16 Pbuf[1 + GW_DEEP][GWB_KW * GWB_PITCH];
-    __shared__ __attribute__((aligned(16))) __bf16 Qbuf[1 + GW_DEEP][GWB_KW * GWB_PITCH];
-    __shared__ __attribute__((aligned(16))) u32x4 mlut[256];       // relu byte -> AND mask of 8 bf16
-    const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    mlut[tid] = chunk_mask_bits<__bf16>(u32x4{0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu}, (unsigned)tid);   // (256 threads; visible after the first barrier)
-    const int wr = wv >> 1, wc = wv & 1;
-    // blocks b and b+8 share an XCD (round-robin dispatch; speed only): lane_order puts the lanes that read the same
-    // dH / X rows on one XCD so they share its L2
-    const int ln = a.lane_order[blockIdx.x % a.n_pad], part = blockIdx.x / a.n_pad;
-    if (ln < 0) return;
-    const int* lh = a.lanes + ln * LANE_INTS;
-    const int it0 = lh[0], nit = lh[1] - lh[0], bias_flag = lh[3];
-    const int nchunks = (a.B + GWB_KW - 1) / GWB_KW;
-    const int ch0 = (int)((int64_t)part * nchunks / a.n_parts), ch1 = (int)((int64_t)(part + 1) * nchunks / a.n_parts);
-    const int nsteps = (ch1 - ch0) * nit;    // step s -> chunk ch0 + s / nit, item s % nit
-    const int c = tid & 15, r0 = tid >> 4;   // staging: 16 chunks of 8 bf16 per row, 16 rows per pass
 
-    // the lane's (<= IPL) items are resolved ONCE into per-thread base pointers: no dependent scalar loads
-    // inside the streaming loop
-    const T* pbase[IPL]; const T* qbase[IPL]; int64_t qstride[IPL]; int qvalid[IPL], qvb[IPL]; u32x4 qsign[IPL];
-    const uint8_t* mbase[IPL];    // relu-bit bytes of the P rows, at window 0 (nullptr: P is used as stored)
-#pragma unroll
-    for (int i = 0; i < IPL; ++i) {
-        const int* im = a.items + (it0 + min(i, nit - 1)) * ITEM_INTS;
-        pbase[i] = reinterpret_cast<const T*>(a.ws + a.buf_off[im[0]]) + act_idx(0, im[2], a.B) + c * 8;
-        mbase[i] = im[9] >= 0 ? reinterpret_cast<const uint8_t*>(a.ws + a.buf_off[im[9]]) + relu_byte(im[2], a.B, 0, c * 8) : nullptr;
-        qsign[i] = u32x4{0, 0, 0, 0};
-        if (im[4] >= 0) {
-            qbase[i] = reinterpret_cast<const T*>(a.ws + a.buf_off[im[3]]) + act_idx(0, im[5], a.B) + c * 8;
-            qstride[i] = H; qvalid[i] = 8; qvb[i] = 16;
-        } else {
-            const int t = im[3] - BUF_IN;
-            qbase[i] = reinterpret_cast<const T*>(a.x[t]) + (size_t)im[5] * a.pitch[t] + im[6] + c * 8;
-            qstride[i] = (int64_t)a.nodes[t] * a.pitch[t]; qvalid[i] = im[7] - c * 8; qvb[i] = a.vb[t];
-            qsign[i] = sign_xor<T>(a.signs + im[8] + c * 8);
-        }
-    }
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int q = 0; q < 16; ++q) acc[i][j][q] = 0.f;
-    float bsum[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) bsum[e] = 0.f;
-
-    struct Stage { u32x4 pv[4], qv[4]; unsigned mw[4]; };
-    auto fetch = [&](Stage& st, int s) {
-        const int w0 = (ch0 + (nit == 2 ? s >> 1 : s)) * GWB_KW;
-        const int it = (nit == 2) ? (s & 1) : 0;
-        const T* pb = it ? pbase[I1] : pbase[0];
-        const T* qb = it ? qbase[I1] : qbase[0];
-        const uint8_t* mb = it ? mbase[I1] : mbase[0];
-        const int64_t qs = it ? qstride[I1] : qstride[0];
-        const int qn = it ? qvalid[I1] : qvalid[0], vb = it ? qvb[I1] : qvb[0];
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            const int w = w0 + r0 + 16 * p;
-            st.pv[p] = u32x4{0, 0, 0, 0}; st.qv[p] = u32x4{0, 0, 0, 0}; st.mw[p] = 0xffffffffu;
-            if (w < a.B && !ABL(a.dbg & 1)) {
-                st.pv[p] = *reinterpret_cast<const u32x4*>(pb + (size_t)w * H);
-                if (mb) st.mw[p] = mb[((size_t)(w >> 4) << 6) + (w & 15)];
-                if (a.aligned) { if (qn > 0) st.qv[p] = *reinterpret_cast<const u32x4*>(qb + (size_t)w * qs); }   // raw: a use here would serialise the loads
-                else st.qv[p] = load_chunk<T>(qb + (size_t)w * qs, qn, vb);
-            }
-        }
-    };
-    // Lane-uniform kinds (the items of a lane belong to one target): P needs the relu mask only for items that carry one, Q needs
-    // pad-column clearing and the symmetry sign only when it is an encoder input.  The staging path is VALU-bound next to the
-    // loads (SQ counters: 29 M VALU instructions per launch against 1.4 M MFMAs), so the generic transforms are skipped where
-    // they are the identity, and the 8 relu bits expand to a 16-byte AND mask through a 256-entry table in LDS.
-    const bool p_masked = mbase[0] != nullptr, q_raw_input = qvb[0] != 16 || qvalid[0] != 8 || (qsign[0][0] | qsign[0][1] | qsign[0][2] | qsign[0][3] | qsign[nit == 2 ? I1 : 0][0] | qsign[nit == 2 ? I1 : 0][1] | qsign[nit == 2 ? I1 : 0][2] | qsign[nit == 2 ? I1 : 0][3]) != 0 || qvalid[nit == 2 ? I1 : 0] != 8;
-    auto stage_to_lds = [&](const Stage& st, const u32x4 sx, const int qn, __bf16* Ps, __bf16* Qs) {
-        if ABL(a.dbg & 2) { asm volatile("" :: "v"(st.pv[0][0]), "v"(st.qv[3][3])); return; }
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            const int row = r0 + 16 * p;
-            u32x4 pm = st.pv[p];
-            if (p_masked) pm &= mlut[st.mw[p] & 0xffu];                 // dH = dX . relu bits
-            *reinterpret_cast<u32x4*>(&Ps[gwb_elem(row, c * 8)]) = pm;
-            u32x4 qm = st.qv[p];
-            if (q_raw_input) qm = chunk_keep_first<T>(qm, qn) ^ sx;     // drop pad columns, symmetry sign mask of encoder inputs
-            *reinterpret_cast<u32x4*>(&Qs[gwb_elem(row, c * 8)]) = qm;
-            if (bias_flag) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    bsum[2 * e] += __builtin_bit_cast(float, pm[e] << 16);
-                    bsum[2 * e + 1] += __builtin_bit_cast(float, pm[e] & 0xffff0000u);
-                }
-            }
-        }
-    };
-    auto mfmas = [&](const __bf16* Ps, const __bf16* Qs) {
-        if ABL(a.dbg & 4) return;
-#pragma unroll
-        for (int ks = 0; ks < GWB_KW / 16; ++ks) {
-            bf16x8 af[2], bq[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                af[i] = tr_frag(Ps, ks * 16, wr * 64 + i * 32, lane);
-                bq[i] = tr_frag(Qs, ks * 16, wc * 64 + i * 32, lane);
-            }
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bq[j], acc[i][j], 0, 0, 0);
-        }
-    };
-    // register stages sa / sb hold the global loads of steps s+1, s+2 (in flight under the MFMAs); even steps use LDS
-    // stage 0, odd steps LDS stage 1.  Loop invariant at the top of step s: LDS[s&1] holds step s, registers hold s+1 (and
-    // s+2 is being fetched).
-    const u32x4 sx1 = nit == 2 ? qsign[I1] : qsign[0];
-    const int qn1 = nit == 2 ? qvalid[I1] : qvalid[0];
-#if GW_DEEP
-    Stage sa, sb;
-    if (nsteps > 0) fetch(sa, 0);
-    if (nsteps > 1) fetch(sb, 1);
-    if (nsteps > 0) stage_to_lds(sa, qsign[0], qvalid[0], Pbuf[0], Qbuf[0]);
-    if (nsteps > 2) fetch(sa, 2);
-    __syncthreads();
-    for (int s = 0; s < nsteps; s += 2) {
-        // step s (LDS 0): write step s+1 (registers sb) into LDS 1 while multiplying LDS 0
-        if (s + 1 < nsteps) stage_to_lds(sb, sx1, qn1, Pbuf[1], Qbuf[1]);
-        if (s + 3 < nsteps) fetch(sb, s + 3);
-        mfmas(Pbuf[0], Qbuf[0]);
-        __syncthreads();
-        if (s + 1 < nsteps) {
-            // step s+1 (LDS 1): write step s+2 (registers sa) into LDS 0
-            if (s + 2 < nsteps) stage_to_lds(sa, qsign[0], qvalid[0], Pbuf[0], Qbuf[0]);
-            if (s + 4 < nsteps) fetch(sa, s + 4);
-            mfmas(Pbuf[1], Qbuf[1]);
-            __syncthreads();
-        }
-    }
-#else
-    // shallow variant: one register stage, one LDS stage, two barriers per step -- fewer registers / less LDS, one more
-    // resident workgroup per CU
-    Stage sa;
-    if (nsteps > 0) fetch(sa, 0);
-#ifndef MSHGNN_GW_STAMPS
-#define MSHGNN_GW_STAMPS 0      // build with EXTRA=-DMSHGNN_GW_STAMPS=1 for tools/stamps_gradw.py (costs 6 VGPRs)
-#endif
-#if MSHGNN_GW_STAMPS
-    long long tph[5] = {0, 0, 0, 0, 0}, tprev = a.stamps ? clock64() : 0;
-    auto lap = [&](int k) { if (a.stamps) { const long long t = clock64(); tph[k] += t - tprev; tprev = t; } };
-#else
-    auto lap = [](int) {};
-#endif
-    for (int s = 0; s < nsteps; ++s) {
-        __syncthreads();
-        lap(0);      // waited for the previous MFMA phase of every wave
-        stage_to_lds(sa, (nit == 2 && (s & 1)) ? qsign[I1] : qsign[0], (nit == 2 && (s & 1)) ? qvalid[I1] : qvalid[0], Pbuf[0], Qbuf[0]);
-        lap(1);      // global loads landed + LDS written
-        __syncthreads();
-        lap(2);
-        if (s + 1 < nsteps) fetch(sa, s + 1);
-        lap(3);      // next step's loads issued
-        mfmas(Pbuf[0], Qbuf[0]);
-        lap(4);
-    }
-#if MSHGNN_GW_STAMPS
-    if (a.stamps && tid == 0) { for (int k = 0; k < 5; ++k) a.stamps[(size_t)blockIdx.x * 8 + k] = tph[k]; a.stamps[(size_t)blockIdx.x * 8 + 5] = nsteps; }
-#endif
-    (void)sx1; (void)qn1;
-#endif
-    float* slab = a.slabs + (size_t)(part * a.n_lanes + ln) * SLAB_FLOATS;
-    if (!ABL(a.dbg & 8))
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const int o = wr * 64 + i * 32 + (q & 3) + ((q >> 2) << 3) + ((lane >> 5) << 2), k = wc * 64 + j * 32 + (lane & 31);
-                slab[o * H + k] = acc[i][j][q];
-            }
-    if (bias_flag) {
-        float* red = reinterpret_cast<float*>(Pbuf[0]);   // 16 x 128 floats = 8 KB <= one LDS stage
-        __syncthreads();
-#pragma unroll
-        for (int e = 0; e < 8; ++e) red[r0 * H + c * 8 + e] = bsum[e];
-        __syncthreads();
-        if (tid < H) {
-            float s2 = 0.f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) s2 += red[r * H + tid];
-            slab[H * H + tid] = s2;
-        }
-    }
-}
-
-// k_gradw_bf16_lean: the same split-K step loop with a hot path that issues almost nothing but loads, LDS traffic and MFMAs.  The general kernel above
-// spends ~300 VALU instructions per wave and 64-window step on 64-bit row addresses, bound checks and per-row mask bytes (SQ counters: 29 M VALU
-// instructions per launch against 1.4 M MFMAs).  Here a thread owns FOUR CONSECUTIVE windows of one 16-byte column chunk, so that
+// k_gradw_bf16_lean: all weight gradients of the step as one split-K MFMA launch, dW[o][k] = sum_w P[w][o] Q[w][k] over 64-window steps staged through LDS (GWB_KW,
+// tr_frag), with a hot path that issues almost nothing but loads, LDS traffic and MFMAs.  Its predecessor of rounds 1-3 (one thread per row, 64-bit row addresses, bound
+// checks and per-row mask bytes) spent ~300 VALU instructions per wave and 64-window step on those (SQ counters: 29 M VALU instructions per launch against 1.4 M MFMAs);
+// its shallow pipeline at 3 workgroups per CU (132 us) beat a two-stage one at 2 (153 us), hence GW_WPS.  Here a thread owns FOUR CONSECUTIVE windows of one 16-byte
+// column chunk, so that
 //   * every global address is  wave-uniform stream pointer (SGPRs, advanced by scalar adds)  +  per-thread 32-bit offset  +  immediate (256 p),
 //   * the relu bytes of its four rows are ONE aligned 32-bit load (the byte layout keeps 16 consecutive windows together),
 //   * full chunks (all but the last one of the batch) carry no bound checks.
@@ -1464,8 +1267,8 @@ template <int IPL> __global__ __launch_bounds__(256, GW_WPS) void k_gradw_bf16(G
 // accumulators -- chunk-major, so that every workgroup of the launch sweeps the batch at the same pace and rows shared between lanes still meet in
 // L2 (item-major order was measured: 109 -> 160 us, the sharing is lost; more than two items per lane lose it too, see GW_IPL_MAX).  The items'
 // stream bases and sign masks sit in a small LDS table; a step reads its three 64-bit bases from it (broadcast reads, moved to scalar
-// registers).  ALIGNED: raw inputs in the engine's own 16-byte-aligned layout; the other instantiation reads them element-wise.  Same MFMA
-// sequence as the general kernel.
+// registers).  ALIGNED: raw inputs in the engine's own 16-byte-aligned layout; the other instantiation reads them element-wise.  32x32x16 bf16 MFMA,
+// wave = 64x64 of the 128x128 tile.
 // SERIES (with ALIGNED): a raw Q operand is gathered from the sequence's series like the encoder's input (k_enc_fwd<.., SERIES>): element k of a
 // node row = element starts[w] + k % T of run k / T -- one unaligned 16-byte load per (window, chunk), two and a splice where the chunk straddles
 // two runs; the four window starts of a thread are fetched one step ahead.  No materialised windows are read.
@@ -1863,7 +1666,7 @@ extern "C" int mshgnn_plan_create(const mshgnn_desc* desc, mshgnn_plan** out) {
         delete p; return set_err(MSHGNN_EHIP, "no HIP device: the MS-HGNN engine has no CPU fallback");
     }
 #ifdef MSHGNN_ABLATE
-    { const char* e = getenv("MSHGNN_DBG"); p->dbg = e ? atoi(e) : 0; e = getenv("MSHGNN_DBG_GW"); p->dbg_gw = e ? atoi(e) : 0; }
+    { const char* e = getenv("MSHGNN_DBG"); p->dbg = e ? atoi(e) : 0; }
 #endif
     HostPlan& hp = p->hp;
     auto up = [&](void** dptr, const void* src, size_t bytes) -> int {
@@ -1976,11 +1779,13 @@ extern "C" int mshgnn_workspace_layout(const mshgnn_plan* p, int64_t batch, int 
     return MSHGNN_OK;
 }
 
+// the weight-image launch of a plan of element type T: the tiled kernel from PREP_TILED_MIN packs up, else one thread per output vector of the launch's packs
+template <typename T> static void launch_prep_t(const PrepArgs& a, bool biases, hipStream_t st) {
+    if (prep_use_tiled(a.n_packs)) hipLaunchKernelGGL((k_prep_tiled<T, false>), dim3(prep_tiled_grid(a.n_packs, a.n_biases)), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_prep<T>, dim3(prep_grid(a, Prec<T>::EPC, biases)), dim3(256), 0, st, a);
+}
 int launch_prep(const PrepArgs& a, bool split, hipStream_t st) {
-    if (split) return x3_launch_prep(a, st);
-    const int64_t total = (int64_t)a.n_packs * (H * H / Prec<__bf16>::EPC) + (int64_t)a.n_biases * H;
-    if (prep_use_tiled(a.n_packs)) hipLaunchKernelGGL((k_prep_tiled<__bf16, false>), dim3(prep_tiled_grid(a.n_packs, a.n_biases)), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(k_prep<__bf16>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a);
+    if (split) x3_launch_prep(a, true, st); else launch_prep_t<__bf16>(a, true, st);
     return MSHGNN_OK;
 }
 
@@ -2009,88 +1814,40 @@ int run_finalize(const mshgnn_plan* p, const StepCall& c, const mshgnn_ws_layout
     return MSHGNN_OK;
 }
 
+// what differs between the fp32 and bf16 plans on the host side of a launch (mshgnn_launch.hpp; the split plan's: mshgnn_x3.hip)
+template <typename T> static constexpr LaunchTraits plan_traits{
+    (int)sizeof(T), Prec<T>::EPC, Prec<T>::EPC, Prec<T>::BLK, Prec<T>::ENC_MB * Prec<T>::ROWS, Prec<T>::ENC_MB * Prec<T>::BLK, sizeof(T) == 4 ? GW_KW : GWB_KW,
+    /*split*/ false, /*embed_prep*/ sizeof(T) == 2, /*src_routes*/ sizeof(T) == 2, /*wide_needs_rows*/ false, /*gradw_series*/ sizeof(T) == 2,
+    "the fused window assembly needs 16-byte aligned window rows (pitch a multiple of 8)",
+    "wide source rows: the plan-dtype rows need 16-byte alignment and a pitch that is a multiple of 8"};
+
 template <typename T>
 static int forward_impl(const mshgnn_plan* p, StepCall& c) {
     // c.loss (one-call steps): the fused stack kernels run decoder, loss and decoder backward in their tail (c.dec_done); where the slab kernels run, the backward
     // sweep of the stack runs in the same launch as well (k_slab_step) and c.stack_done tells backward_impl to skip its own
     const HostPlan& hp = p->hp;
     const mshgnn_desc& d = hp.d;
+    const LaunchTraits& tr = plan_traits<T>;
     const int training = c.training;
     mshgnn_ws_layout lay; layout_workspace(hp, c.batch, training, &lay);
     const int B = (int)c.batch;
-    const void* const* x = c.x; const int64_t* x_pitch = c.x_pitch;
-    const float* params = c.params; char* ws = c.ws; hipStream_t st = c.stream;
-    const SeriesSrc* series = c.series; const WideSrc* wide = c.wide;
-    const float* y_fused = c.y_fused(); const int32_t* labels_fused = c.labels_fused();
-    // 1. weight images.  bf16 plan with few packs: only the encoder's packs (the last ones of the list) + the biases here; the layer packs are packed
-    //    by extra workgroups of the encoder launch, under its tail (EncArgs.prep) -- the whole-list launch in front of the encoder cost 10.9 us
-    PrepArgs pa{params, ws + lay.wpack, reinterpret_cast<float*>(ws + lay.bias), p->d_packs, p->d_biases, (int)hp.packs.size(), (int)hp.biases.size()};
-    int enc_pack0 = (int)hp.packs.size();
-    for (int t = 0; t < hp.NT; ++t) if (hp.pack_enc_base[t] >= 0) enc_pack0 = std::min(enc_pack0, hp.pack_enc_base[t]);
-    static const bool embed_off = TUNE_ENV("MSHGNN_PREP_EMBED") && atoi(TUNE_ENV("MSHGNN_PREP_EMBED")) == 0;      // (A/B runs)
-    const bool embed = sizeof(T) == 2 && !series && !prep_use_tiled(pa.n_packs) && enc_pack0 > 0 && !embed_off;
+    char* ws = c.ws; hipStream_t st = c.stream;
+    int rc;
+    // 1. weight images (bf16 plan with few packs: the layer packs by extra workgroups of the encoder launch, enc_prep_split), 2. encoder
     {
-        PrepArgs a = pa;
-        if (embed) { a.pack0 = enc_pack0; a.pack_n = pa.n_packs - enc_pack0; }
-        const int64_t total = (int64_t)(embed ? a.pack_n : a.n_packs) * (H * H / Prec<T>::EPC) + (int64_t)hp.biases.size() * H;
-        ProfScope ps(p, hp.ks_prep, st);
-        if (prep_use_tiled(a.n_packs)) hipLaunchKernelGGL((k_prep_tiled<T, false>), dim3(prep_tiled_grid(a.n_packs, a.n_biases)), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL(k_prep<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a);
-    }
-    // 2. encoder
-    {
-        EncArgs a{};
-        a.n_types = hp.NT; a.B = B; a.NN = hp.NN; a.tiles = (B + Prec<T>::ENC_MB * Prec<T>::ROWS - 1) / (Prec<T>::ENC_MB * Prec<T>::ROWS);
-        a.wg_prefix[0] = 0;
-        for (int t = 0; t < hp.NT; ++t) {
-            a.x[t] = x ? x[t] : nullptr; a.pitch[t] = x_pitch ? x_pitch[t] : d.type_width[t];
-            if (a.pitch[t] < d.type_width[t]) return set_err(MSHGNN_EINVAL, "x_pitch smaller than the feature width");
-            a.vb[t] = vec_bytes(a.x[t], a.pitch[t], (int)sizeof(T));
-            if (t == 0) a.aligned = 1;
-            if (a.vb[t] != 16 || a.pitch[t] % Prec<T>::EPC) a.aligned = 0;
-            a.width[t] = d.type_width[t]; a.tbase[t] = hp.type_base[t]; a.nkc[t] = hp.enc_nkc[t];
-            a.pack0[t] = hp.pack_enc_base[t]; a.bias_idx[t] = hp.bias_enc[t]; a.sign_off[t] = hp.sign_off[t];
-            // the launch's nodes of this type: those whose X_0 can reach the output; with window rows to materialise (series route, x given) every node,
-            // the others marked in skip_mask
-            a.node_off[t] = t == 0 ? 0 : a.node_off[t - 1] + a.nodes[t - 1];
-            a.nodes[t] = 0;
-            const bool all_rows = series != nullptr && x != nullptr;
-            for (int i = 0; i < d.type_nodes[t]; ++i) {
-                const bool need = hp.need_n[0][hp.type_base[t] + i];
-                if (need || all_rows) a.node_list[a.node_off[t] + a.nodes[t]++] = (unsigned char)i;
-                if (!need) a.skip_mask |= 1ull << (hp.type_base[t] + i);
-            }
-            a.wg_prefix[t + 1] = a.wg_prefix[t] + a.nodes[t] * a.tiles;
-        }
-        a.tbase[hp.NT] = hp.NN;
-        a.wpack = ws + lay.wpack; a.bias = reinterpret_cast<const float*>(ws + lay.bias); a.signs = p->d_signs; a.x0 = ws + lay.x[0];
-        a.mask0 = (training && lay.dd[0]) ? reinterpret_cast<uint8_t*>(ws + lay.dd[0]) : nullptr;
-        unsigned enc_grid = (unsigned)a.wg_prefix[hp.NT];
-        if (embed) {
-            PrepArgs lp = pa; lp.pack0 = 0; lp.pack_n = enc_pack0;
-            if (a.aligned) { a.prep = lp; a.prep_vecs = enc_pack0 * (H * H / Prec<T>::EPC); enc_grid += (unsigned)((a.prep_vecs + 255) / 256); }
-            else {      // the element-wise encoder has no embedded prep: pack the layer images in front of it after all
-                ProfScope ps(p, hp.ks_prep, st);
-                hipLaunchKernelGGL(k_prep<T>, dim3((unsigned)(((int64_t)enc_pack0 * (H * H / Prec<T>::EPC) + 255) / 256)), dim3(256), 0, st, lp);
-            }
-        }
+        EncArgs a{}; unsigned enc_grid = 0; EncRoute route;
+        if ((rc = prep_and_enc_args(p, c, lay, tr, launch_prep_t<T>, a, enc_grid))) return rc;
         ProfScope ps(p, hp.ks_enc, st);
-        if constexpr (sizeof(T) == 2) {
-            if (series) {
-                if (x && !a.aligned) return set_err(MSHGNN_EINVAL, "the fused window assembly needs 16-byte aligned window rows (pitch a multiple of 8)");
-                enc_grid += (unsigned)((series->lab.B + 255) / 256);      // the label workgroups
-                if (series->stats) hipLaunchKernelGGL((k_enc_fwd<T, true, true, 0, true>), dim3(enc_grid), dim3(256), Prec<T>::ENC_MB * Prec<T>::BLK, st, a, *series, WideSrc{});
-                else hipLaunchKernelGGL((k_enc_fwd<T, true, true>), dim3(enc_grid), dim3(256), Prec<T>::ENC_MB * Prec<T>::BLK, st, a, *series, WideSrc{});
-            } else if (wide) {      // (mshgnn_*_src) the caller's fp64 / fp32 rows: converted by the encoder, plan-dtype rows written to x on the side (x may be null)
-                if (x && !a.aligned) return set_err(MSHGNN_EINVAL, "wide source rows: the plan-dtype rows need 16-byte alignment and a pitch that is a multiple of 8");
-                if (wide->bytes == 8) hipLaunchKernelGGL((k_enc_fwd<T, true, false, 8>), dim3(enc_grid), dim3(256), Prec<T>::ENC_MB * Prec<T>::BLK, st, a, SeriesSrc{}, *wide);
-                else hipLaunchKernelGGL((k_enc_fwd<T, true, false, 4>), dim3(enc_grid), dim3(256), Prec<T>::ENC_MB * Prec<T>::BLK, st, a, SeriesSrc{}, *wide);
-            } else if (a.aligned) hipLaunchKernelGGL((k_enc_fwd<T, true>), dim3(enc_grid), dim3(256), Prec<T>::ENC_MB * Prec<T>::BLK, st, a, SeriesSrc{}, WideSrc{});
-            else hipLaunchKernelGGL((k_enc_fwd<T, false>), dim3(enc_grid), dim3(256), Prec<T>::ENC_MB * Prec<T>::BLK, st, a, SeriesSrc{}, WideSrc{});
-        } else {
-            if (wide) return set_err(MSHGNN_EUNSUPPORTED, "wide source rows: not on the fp32 plan (cast the inputs)");
-            if (a.aligned) hipLaunchKernelGGL((k_enc_fwd<T, true>), dim3(enc_grid), dim3(256), Prec<T>::ENC_MB * Prec<T>::BLK, st, a, SeriesSrc{}, WideSrc{});
-            else hipLaunchKernelGGL((k_enc_fwd<T, false>), dim3(enc_grid), dim3(256), Prec<T>::ENC_MB * Prec<T>::BLK, st, a, SeriesSrc{}, WideSrc{});
+        if ((rc = pick_enc_route(c, a, tr, enc_grid, route))) return rc;
+        unsigned enc_lds = tr.enc_lds;
+        auto enc = [&](auto kernel, const SeriesSrc& ser, const WideSrc& wsrc) { hipLaunchKernelGGL(kernel, dim3(enc_grid), dim3(256), enc_lds, st, a, ser, wsrc); };
+        if (route == EncRoute::ALIGNED) enc(k_enc_fwd<T, true>, SeriesSrc{}, WideSrc{});
+        else if (route == EncRoute::ELEMENTWISE) enc(k_enc_fwd<T, false>, SeriesSrc{}, WideSrc{});
+        else if constexpr (sizeof(T) == 2) {      // (plan_traits<float>.src_routes is false: the fp32 plan takes no other route)
+            if (route == EncRoute::SERIES_STD) enc(k_enc_fwd<T, true, true, 0, true>, *c.series, WideSrc{});
+            else if (route == EncRoute::SERIES) enc(k_enc_fwd<T, true, true>, *c.series, WideSrc{});
+            else if (route == EncRoute::WIDE8) enc(k_enc_fwd<T, true, false, 8>, SeriesSrc{}, *c.wide);      // (x may be null: nothing written on the side)
+            else enc(k_enc_fwd<T, true, false, 4>, SeriesSrc{}, *c.wide);
         }
     }
     // 3. layers (+ decoder): one fused launch on the bf16 plan, else one kernel per layer and the decoder kernel
@@ -2098,65 +1855,37 @@ static int forward_impl(const mshgnn_plan* p, StepCall& c) {
     if constexpr (sizeof(T) == 2) {
         if (p->use_fused) {
             StackArgs a{};
-            a.tile_in = ws + lay.x[0]; a.ws = ws;
-            for (int l = 0; l <= hp.L; ++l) a.x_off[l] = lay.x[l];
-            for (int l = 0; l < hp.L; ++l) { a.mask_off[l] = lay.mask[l]; a.hb_off[l] = lay.hb[l]; a.t1_off[l] = lay.t1[l]; a.prog_off[l] = hp.fs_fwd_off[l]; }
-            a.wpack = ws + lay.wpack; a.bias = reinterpret_cast<const float*>(ws + lay.bias); a.tables = p->d_tables;
-            a.B = B; a.NN = hp.NN; a.L = hp.L; a.training = training;
-            a.dbg = p->dbg;
-            a.params = params; a.out_mask = p->d_out_mask; a.out = c.out; a.off_dec_w = d.off_dec_w; a.off_dec_b = d.off_dec_b;
-            a.node0 = hp.type_base[d.out_type]; a.n_out = d.type_nodes[d.out_type]; a.dout = d.out_channels;
-            if (y_fused) {
-                a.y = y_fused; a.dec_slabs = reinterpret_cast<float*>(ws + lay.dec_slabs); a.dx_off[hp.L] = lay.dx[hp.L];
-                a.inv_n = 1.0f / (float)(c.total_windows() * a.n_out * a.dout);
-            } else if (labels_fused) {      // mshgnn_step_ce: cross entropy over the per-foot logit pairs, mean over B * n_out rows
-                a.labels = labels_fused; a.dec_slabs = reinterpret_cast<float*>(ws + lay.dec_slabs); a.dx_off[hp.L] = lay.dx[hp.L];
-                a.inv_n = 1.0f / (float)(c.total_windows() * a.n_out);
-            }
-            c.dec_done = y_fused || labels_fused;
+            fill_stack_common(p, c, lay, a);
+            fill_stack_tail(p, c, lay, a);
+            a.tile_in = ws + lay.x[0]; a.training = training; a.dbg = p->dbg;
+            for (int l = 0; l < hp.L; ++l) a.prog_off[l] = hp.fs_fwd_off[l];
             a.stamps = stamp_ptr("MSHGNN_STAMPS");
             a.stagger = p->slab_for(tiles) && tiles > p->n_cu ? p->stagger : 0;
-            a.stash_nt = training ? stash_nt_for(p->stash_nt_force, B, stash_rows_of(hp), H * (int)sizeof(T)) : 0;
-            // the tail's reduction scratch (one decoder slab per wave) must not touch the out-type nodes' blocks, which receive dX_L for the backward sweep: it sits
-            // in the blocks in front of them, or (models whose out type comes first: the centroidal-momentum ones) in the blocks behind them
+            if (!training) a.stash_nt = 0;      // (an evaluation stashes nothing; the split plan leaves the policy set there)
             const bool want_step = p->use_step && c.dec_done;
             // Slab or 8-wave kernels: the 8-wave ones take batches of at most one tile per CU -- unless the one-call step has a compile-time program for this plan
             // (whole tiles): a single tile's chain on the specialised slab kernel is 37-42 us where the interpreting 8-wave kernel takes 57-62 (A1-C2, 32 .. 4 096 windows;
             // 8 layers: 140-166 against 202-209), so the specialised step runs at every batch size.  MSHGNN_SLAB=0 / MSHGNN_SPEC=0 keep the 8-wave kernels there.
             bool step_slab = p->slab_for(tiles);
             const bool spec_small = !step_slab && want_step && p->use_slab && p->use_spec && slab_step_spec_kernel(hp, a.stash_nt, nullptr, whole_tiles(B)) != nullptr;
-            bool red_front_ok = false, red_back_ok = false; size_t red_back = 0;
-            auto red_fits = [&](bool slab) {
-                const size_t red_need = (size_t)((slab ? SL_THREADS : LAYER_THREADS) / 64) * DEC_SLAB_FLOATS * sizeof(float);
-                const size_t lds_launch = (size_t)((slab ? hp.sl_blk : hp.fs_blk) + FS_EXTRA_BLK) * Prec<T>::BLK;
-                red_back = (size_t)(a.node0 + a.n_out) * Prec<T>::BLK;
-                red_front_ok = (size_t)a.node0 * Prec<T>::BLK >= red_need; red_back_ok = red_back + red_need <= lds_launch;
-                return red_front_ok || red_back_ok; };
+            auto lds_of = [&](bool slab) { return (size_t)((slab ? hp.sl_blk : hp.fs_blk) + FS_EXTRA_BLK) * tr.blk; };
+            auto red_fits = [&](bool slab) {      // the tail's reduction scratch of a one-launch step on that kernel family fits beside the out-type blocks (and is placed)
+                return place_red_scratch(a.node0, a.n_out, tr.blk, (size_t)((slab ? SL_THREADS : LAYER_THREADS) / 64) * DEC_SLAB_FLOATS * sizeof(float), lds_of(slab), a); };
             if (spec_small && red_fits(true)) step_slab = true;
             const bool step = want_step && red_fits(step_slab);
-            if (step && !red_front_ok) a.red_off = (int)red_back;
             // the forward launch alone (evaluation / two-call training) on its compile-time program, at every whole-tile batch size
             const StackKernel fwd_spec = (!step && p->use_slab && p->use_spec) ? slab_fwd_spec_kernel(hp, training, a.stash_nt, whole_tiles(B)) : nullptr;
             if (fwd_spec) step_slab = true;
-            ProfScope ps(p, step ? hp.ks_stack_step : hp.ks_stack_fwd, st);
-            if (step_slab) {
-                for (int l = 0; l < hp.L; ++l) a.prog_off[l] = hp.sl_fwd_off[l];
-                if (step) {
-                    for (int l = 0; l <= hp.L; ++l) a.dx_off[l] = lay.dx[l];
-                    for (int l = 0; l < hp.L; ++l) { a.dh_off[l] = lay.dh[l]; a.du_off[l] = lay.du[l]; a.prog_off_b[l] = hp.sl_bwd_off[l]; }
-                    a.mask0_off = lay.dd[0];
-                    hipLaunchKernelGGL(slab_step_kernel(hp, B, a.stash_nt, p->use_spec), dim3(tiles), dim3(SL_THREADS), (hp.sl_blk + FS_EXTRA_BLK) * Prec<T>::BLK, st, a);
-                    c.stack_done = true;
-                } else
-                hipLaunchKernelGGL(fwd_spec ? fwd_spec : slab_fwd_kernel(hp), dim3(tiles), dim3(SL_THREADS), (hp.sl_blk + FS_EXTRA_BLK) * Prec<T>::BLK, st, a);
-            } else if (step) {
-                for (int l = 0; l <= hp.L; ++l) a.dx_off[l] = lay.dx[l];
-                for (int l = 0; l < hp.L; ++l) { a.dh_off[l] = lay.dh[l]; a.du_off[l] = lay.du[l]; a.prog_off_b[l] = hp.fs_bwd_off[l]; }
+            if (step_slab) for (int l = 0; l < hp.L; ++l) a.prog_off[l] = hp.sl_fwd_off[l];
+            if (step) {      // the backward sweep in the same launch
+                for (int l = 0; l < hp.L; ++l) a.prog_off_b[l] = step_slab ? hp.sl_bwd_off[l] : hp.fs_bwd_off[l];
                 a.mask0_off = lay.dd[0];
-                hipLaunchKernelGGL(k_stack_step<T>, dim3(tiles), dim3(LAYER_THREADS), (hp.fs_blk + FS_EXTRA_BLK) * Prec<T>::BLK, st, a);
                 c.stack_done = true;
-            } else
-            hipLaunchKernelGGL(k_stack_fwd<T>, dim3(tiles), dim3(LAYER_THREADS), (hp.fs_blk + FS_EXTRA_BLK) * Prec<T>::BLK, st, a);
+            }
+            ProfScope ps(p, step ? hp.ks_stack_step : hp.ks_stack_fwd, st);
+            if (step_slab) hipLaunchKernelGGL(step ? slab_step_kernel(hp, B, a.stash_nt, p->use_spec) : fwd_spec ? fwd_spec : slab_fwd_kernel(hp), dim3(tiles), dim3(SL_THREADS), lds_of(true), st, a);
+            else if (step) hipLaunchKernelGGL(k_stack_step<T>, dim3(tiles), dim3(LAYER_THREADS), lds_of(false), st, a);
+            else hipLaunchKernelGGL(k_stack_fwd<T>, dim3(tiles), dim3(LAYER_THREADS), lds_of(false), st, a);
             HIPCHK(hipGetLastError());
             return MSHGNN_OK;
         }
@@ -2173,7 +1902,7 @@ static int forward_impl(const mshgnn_plan* p, StepCall& c) {
     // 4. decoder
     {
         DecArgs a{};
-        a.xl = ws + lay.x[hp.L]; a.params = params; a.out_mask = p->d_out_mask; a.out = c.out; a.off_w = d.off_dec_w; a.off_b = d.off_dec_b;
+        a.xl = ws + lay.x[hp.L]; a.params = c.params; a.out_mask = p->d_out_mask; a.out = c.out; a.off_w = d.off_dec_w; a.off_b = d.off_dec_b;
         a.B = B; a.NN = hp.NN; a.node0 = hp.type_base[d.out_type]; a.n_out = d.type_nodes[d.out_type]; a.dout = d.out_channels;
         const int64_t rows = (int64_t)B * a.n_out;
         ProfScope ps(p, hp.ks_dec_fwd, st);
@@ -2186,44 +1915,27 @@ static int forward_impl(const mshgnn_plan* p, StepCall& c) {
 template <typename T>
 static int backward_impl(const mshgnn_plan* p, const StepCall& c) {
     const HostPlan& hp = p->hp;
-    const mshgnn_desc& d = hp.d;
+    const LaunchTraits& tr = plan_traits<T>;
     mshgnn_ws_layout lay; layout_workspace(hp, c.batch, 1, &lay);
     const int B = (int)c.batch;
-    const void* const* x = c.x; const int64_t* x_pitch = c.x_pitch;
     char* ws = c.ws; hipStream_t st = c.stream;
     const int gw_phase = c.gw_phase;
-    const bool stack_done = c.stack_done;      // k_slab_step already ran the backward sweep of the stack (forward_impl)
-    const SeriesSrc* series = c.gradw_from_series ? c.series : nullptr;
     if (!c.dec_done && gw_phase != 1) {
         DecArgs a{};
-        a.xl = ws + lay.x[hp.L]; a.dxl = ws + lay.dx[hp.L]; a.params = c.params; a.out_mask = p->d_out_mask; a.gout = c.grad_out;
-        a.slabs = reinterpret_cast<float*>(ws + lay.dec_slabs); a.off_w = d.off_dec_w; a.off_b = d.off_dec_b;
-        a.B = B; a.NN = hp.NN; a.node0 = hp.type_base[d.out_type]; a.n_out = d.type_nodes[d.out_type]; a.dout = d.out_channels; a.slab0 = 0;
-        if (c.loss == LossKind::MSE) {
-            a.y = c.y; a.out = c.out; a.loss = c.loss_out; a.inv_n = 1.0f / (float)(c.total_windows() * a.n_out * a.dout);
-        }
-        if (c.loss == LossKind::CE) {
-            a.labels = c.labels; a.out = c.out; a.loss = c.loss_out; a.inv_n = 1.0f / (float)(c.total_windows() * a.n_out);
-        }
+        fill_dec_bwd_args(p, c, lay, a);
         ProfScope ps(p, hp.ks_dec_bwd, st);
         hipLaunchKernelGGL(k_dec_bwd<T>, dim3(NWG_DEC), dim3(256), 0, st, a);
     }
     const int tiles = (B + Prec<T>::ROWS - 1) / Prec<T>::ROWS;
-    bool fused_done = gw_phase == 1 || stack_done;
+    bool fused_done = gw_phase == 1 || c.stack_done;      // (stack_done: k_slab_step already ran the backward sweep of the stack, forward_impl)
     if constexpr (sizeof(T) == 2) {
-        if (p->use_fused && gw_phase != 1 && !stack_done) {
+        if (p->use_fused && !fused_done) {
             StackArgs a{};
-            a.tile_in = ws + lay.dx[hp.L]; a.ws = ws;
-            for (int l = 0; l <= hp.L; ++l) { a.x_off[l] = lay.x[l]; a.dx_off[l] = lay.dx[l]; }
-            for (int l = 0; l < hp.L; ++l) { a.mask_off[l] = lay.mask[l]; a.t1_off[l] = lay.t1[l]; a.dh_off[l] = lay.dh[l]; a.du_off[l] = lay.du[l]; a.prog_off[l] = hp.fs_bwd_off[l]; }
-            a.wpack = ws + lay.wpack; a.bias = reinterpret_cast<const float*>(ws + lay.bias); a.tables = p->d_tables;
-            a.B = B; a.NN = hp.NN; a.L = hp.L; a.training = 1;
-            a.node0 = hp.type_base[d.out_type]; a.n_out = d.type_nodes[d.out_type];      // the nodes that carry dX_L (the only live type of the last layer)
-            a.mask0_off = lay.dd[0];
-            a.dbg = p->dbg;
+            fill_stack_common(p, c, lay, a);
+            a.tile_in = ws + lay.dx[hp.L]; a.training = 1; a.mask0_off = lay.dd[0]; a.dbg = p->dbg;
+            for (int l = 0; l < hp.L; ++l) a.prog_off[l] = hp.fs_bwd_off[l];
             a.stamps = stamp_ptr("MSHGNN_STAMPS_BWD");
             a.stagger = p->slab_for(tiles) && tiles > p->n_cu ? p->stagger : 0;
-            a.stash_nt = stash_nt_for(p->stash_nt_force, B, stash_rows_of(hp), H * (int)sizeof(T));
             ProfScope ps(p, hp.ks_stack_bwd, st);
             const StackKernel bwd_spec = (p->use_slab && p->use_spec) ? slab_bwd_spec_kernel(hp, a.stash_nt, whole_tiles(B)) : nullptr;      // (at every whole-tile batch size, like the forward)
             if (bwd_spec || p->slab_for(tiles)) {
@@ -2244,42 +1956,20 @@ static int backward_impl(const mshgnn_plan* p, const StepCall& c) {
         ProfScope ps(p, hp.ks_layer_bwd0 + (hp.L - 1 - l), st);
         hipLaunchKernelGGL(k_layer_bwd<T>, dim3(tiles), dim3(LAYER_THREADS), hp.n_blk * Prec<T>::BLK, st, a);
     }
-    const int gw_parts = gw_parts_for(hp.n_parts, hp.n_lanes, hp.gw_ipl, B, sizeof(T) == 4 ? GW_KW : GWB_KW, p->n_cu);      // window parts of this batch's weight-gradient launch (<= the plan's)
+    const int gw_parts = gw_parts_for(hp.n_parts, hp.n_lanes, hp.gw_ipl, B, tr.gw_windows, p->n_cu);      // window parts of this batch's weight-gradient launch (<= the plan's)
     if (c.grad_params) {      // (NULL: activation backward only -- dX_0 for mshgnn_input_grad, no weight gradients)
         GradwArgs a{};
-        a.ws = ws;
-        for (int l = 0; l <= hp.L; ++l) { a.buf_off[BUF_X + l] = lay.x[l]; a.buf_off[BUF_DX + l] = lay.dx[l]; }
-        for (int l = 0; l < hp.L; ++l) a.buf_off[BUF_MASK + l] = lay.mask[l];
-        for (int l = 0; l < hp.L; ++l) { a.buf_off[BUF_DH + l] = lay.dh[l]; a.buf_off[BUF_HB + l] = lay.hb[l]; a.buf_off[BUF_T1 + l] = lay.t1[l]; a.buf_off[BUF_DU + l] = lay.du[l]; }
-        for (int t = 0; t < hp.NT; ++t) {
-            a.x[t] = x ? x[t] : nullptr; a.pitch[t] = x_pitch ? x_pitch[t] : d.type_width[t]; a.nodes[t] = d.type_nodes[t];
-            a.vb[t] = vec_bytes(a.x[t], a.pitch[t], (int)sizeof(T));
-            if (t == 0) a.aligned = 1;
-            if (a.vb[t] != 16 || a.pitch[t] % Prec<T>::EPC) a.aligned = 0;
-        }
-        if (series) a.ser = *series;
-        a.items = p->d_tables + hp.item_off; a.lanes = p->d_tables + hp.lane_off; a.lane_order = p->d_tables + hp.lane_order_off; a.n_pad = hp.n_lanes_pad;
-        if (gw_phase >= 0) { a.lane_order = p->d_tables + hp.order_ph_off[gw_phase]; a.n_pad = hp.npad_ph[gw_phase]; }
-        a.signs = p->d_signs; a.slabs = reinterpret_cast<float*>(ws + lay.slabs); a.B = B; a.n_lanes = hp.n_lanes; a.n_parts = gw_parts;
-        a.dbg = p->dbg_gw;
-        a.stamps = stamp_ptr("MSHGNN_STAMPS_GW");
+        fill_gradw_args(p, c, lay, tr, gw_parts, a);
         ProfScope ps(p, hp.ks_gradw, st);
-        auto launch_gradw = [&](const GradwArgs& ga, hipStream_t s_) {
-            [[maybe_unused]] static const bool gw_general = TUNE_ENV("MSHGNN_GRADW") && std::string(TUNE_ENV("MSHGNN_GRADW")) == "general";   // read once: the general kernel also where the lean one applies (A/B runs)
-            if (ga.n_pad <= 0) return;
-            if constexpr (sizeof(T) == 4) hipLaunchKernelGGL(k_gradw_f32, dim3(ga.n_pad * gw_parts), dim3(256), 0, s_, ga);
-#ifdef MSHGNN_TUNING      // (the general bf16 kernel of rounds 1-3: kept for A/B runs in tuning builds, not in the product binary)
-            else if (gw_general && hp.gw_ipl == 1) hipLaunchKernelGGL(k_gradw_bf16<1>, dim3(ga.n_pad * gw_parts), dim3(256), 0, s_, ga);
-            else if (gw_general && hp.gw_ipl == 2) hipLaunchKernelGGL(k_gradw_bf16<2>, dim3(ga.n_pad * gw_parts), dim3(256), 0, s_, ga);
-#endif
-            else if (series) hipLaunchKernelGGL((k_gradw_bf16_lean<true, true>), dim3(ga.n_pad * gw_parts), dim3(256), 0, s_, ga);      // raw operands from the series
-            else if (ga.aligned) hipLaunchKernelGGL(k_gradw_bf16_lean<true>, dim3(ga.n_pad * gw_parts), dim3(256), 0, s_, ga);
-            else hipLaunchKernelGGL(k_gradw_bf16_lean<false>, dim3(ga.n_pad * gw_parts), dim3(256), 0, s_, ga);
-        };
         // (round 6, measured and not kept: phase 1's lanes on a side stream BESIDE phase 0's -- forked behind the stack launch, joined by phase 1's finalize.  On a
         //  1-rank RCCL group the two-phase step took 0.306 ms that way against 0.268 back to back and 0.186 for the plain step: two concurrent sweeps of the batch
         //  evict each other's shared rows.)
-        launch_gradw(a, st);
+        const dim3 grid(std::max(a.n_pad, 0) * gw_parts);
+        if (a.n_pad <= 0) {}      // (a phase without lanes)
+        else if constexpr (sizeof(T) == 4) hipLaunchKernelGGL(k_gradw_f32, grid, dim3(256), 0, st, a);
+        else if (c.gradw_from_series && c.series) hipLaunchKernelGGL((k_gradw_bf16_lean<true, true>), grid, dim3(256), 0, st, a);      // raw operands from the series
+        else if (a.aligned) hipLaunchKernelGGL(k_gradw_bf16_lean<true>, grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL(k_gradw_bf16_lean<false>, grid, dim3(256), 0, st, a);
     }
     return run_finalize(p, c, lay, gw_parts);
 }

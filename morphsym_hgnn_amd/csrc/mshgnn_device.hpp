@@ -55,11 +55,6 @@ inline int set_err(int code, const std::string& m) { g_err = m; return code; }
 // Timing ablations and in-kernel stamps exist only in instrumented builds (make EXTRA=-DMSHGNN_ABLATE, -DMSHGNN_FS_STAMPS, ...):
 // in the product build every ABL() test is the constant false, so the branches fold away and no environment variable can
 // change what the kernels compute.
-#if defined(MSHGNN_GW_STAMPS) && MSHGNN_GW_STAMPS
-#define MSHGNN_GW_STAMPS_BUILD 1
-#else
-#define MSHGNN_GW_STAMPS_BUILD 0
-#endif
 #ifdef MSHGNN_ABLATE
 #define ABL(x) ((x) != 0)
 #else
@@ -1339,8 +1334,7 @@ struct GradwArgs {
     const void* x[MSHGNN_MAX_TYPES]; int64_t pitch[MSHGNN_MAX_TYPES]; int nodes[MSHGNN_MAX_TYPES]; int vb[MSHGNN_MAX_TYPES];
     const int* items; const int* lanes; const int* lane_order; const uint8_t* signs; float* slabs; int B, n_lanes, n_parts, n_pad;
     int aligned;   // all raw-input rows 16-byte aligned with whole-chunk pitch
-    int dbg;   // timing ablations (MSHGNN_DBG_GW): 1 no global loads, 2 no LDS staging, 4 no MFMA phase, 8 no slab store
-    long long* stamps;   // MSHGNN_STAMPS_GW: thread 0 of every workgroup accumulates clock64() deltas of the step phases
+    int dbg; long long* stamps;   // (ablation flags and phase clocks of the retired round 1-3 kernels: zero, read by no kernel; kept for the argument layout)
     SeriesSrc ser;       // raw-input operands gathered from the sequence's series (mshgnn_step_mse_series without materialised windows)
 };
 
@@ -1392,7 +1386,7 @@ struct mshgnn_plan {
     int stagger = 0;                             // StackArgs.stagger of the two-workgroups-per-CU stack kernels (MSHGNN_STAGGER)
     int n_types = 0;
     mshgnn_gen_state* gen = nullptr;    // set: this plan runs on the generic-width engine (hidden != 128, many nodes, ...), hp is unused
-    int dbg = 0, dbg_gw = 0;            // timing ablations (instrumented builds only: read once from MSHGNN_DBG / MSHGNN_DBG_GW at plan creation)
+    int dbg = 0;                        // timing ablations (instrumented builds only: read once from MSHGNN_DBG at plan creation)
     // a slab workgroup has 4 waves for a whole tile (a lone one is ~12 % slower than the 8-wave kernels' workgroup: 69 against 62 us at 3 layers), two fit a CU:
     // it pays off from the first tile the 8-wave kernels would need a second round for (257 .. 383 tiles, 8-wave against slab launch: 113 / 77 us at 3 layers,
     // 425 / 295 at 8, MiniCheetah-K4 440 / 330 -- tools/slab_threshold_sweep.py; rounds 3-4 switched at 1.5 tiles per CU)
@@ -1401,7 +1395,7 @@ struct mshgnn_plan {
 
 // in-kernel stamp buffers of the instrumented builds (tools/stamps_*.py pass a device pointer through the environment)
 inline long long* stamp_ptr(const char* name) {
-#if defined(MSHGNN_FS_STAMPS) || defined(MSHGNN_SEG_STAMPS) || MSHGNN_GW_STAMPS_BUILD
+#if defined(MSHGNN_FS_STAMPS) || defined(MSHGNN_SEG_STAMPS)
     const char* e = getenv(name);
     return e ? reinterpret_cast<long long*>((uintptr_t)strtoull(e, nullptr, 0)) : nullptr;
 #else
@@ -1509,7 +1503,7 @@ int x3_set_attrs(mshgnn_plan* p);
 int x3_attach_program(mshgnn_plan* p, void* selector);
 int x3_forward(const mshgnn_plan* p, StepCall& c);
 int x3_backward(const mshgnn_plan* p, const StepCall& c);
-int x3_launch_prep(const PrepArgs& a, hipStream_t st);
+void x3_launch_prep(const PrepArgs& a, bool biases, hipStream_t st);      // (biases: the grid of the per-thread kernel covers the bias sums too)
 // weight-image packing for the other engines (mshgnn.hip): k_prep<__bf16> or the hi / lo images of k_prep_x3
 int launch_prep(const PrepArgs& a, bool split, hipStream_t st);
 // generic-width engine (mshgnn_gen.hip)

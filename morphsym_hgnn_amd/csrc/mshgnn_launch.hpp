@@ -1,0 +1,180 @@
+// The host side of a launch, once for the three precisions of the LDS-resident engine: what turns a StepCall into kernel arguments.  The fp32 / bf16 plans
+// (forward_impl / backward_impl, mshgnn.hip) and the split-bf16 plan (x3_forward / x3_backward, mshgnn_x3.hip) keep their own kernel selection and their own
+// launches; every argument struct they pass is filled here.  What differs between the plans is a LaunchTraits constant, never a second copy of a fill.
+#pragma once
+#include "mshgnn_device.hpp"
+
+struct LaunchTraits {
+    int in_bytes;           // element size of the encoder's input rows (the split plan reads fp32)
+    int in_epc;             // ... and their elements per 16-byte chunk
+    int pack_epc;           // elements per 16-byte chunk of a weight image
+    int blk;                // bytes of one LDS node block
+    int enc_windows;        // windows per encoder workgroup
+    int enc_lds;            // dynamic LDS of the encoder launch
+    int gw_windows;         // windows per step of the weight-gradient kernel
+    bool split;             // hi / lo weight images: the plan's pack list holds both planes, a launch names the images of one (hp.n_img)
+    bool embed_prep;        // the encoder launch can pack the layer images under its tail (EncArgs.prep)
+    // kept differences between the plans
+    bool src_routes;        // the encoder gathers from a series or converts wide sources; fp32 plan: no series route, wide sources refused
+    bool wide_needs_rows;   // wide sources: aligned plan-dtype rows must be given (split plan); else they are checked only where x is given
+    bool gradw_series;      // the weight-gradient kernel can gather raw operands from the series (StepCall.gradw_from_series); split plan: always materialised rows
+    const char* series_rows_err;      // the series route's refusal of unaligned window rows
+    const char* wide_rows_err;        // the wide route's
+};
+
+inline int plan_packs(const HostPlan& hp, const LaunchTraits& tr) { return tr.split ? hp.n_img : (int)hp.packs.size(); }
+
+// ---- weight images: which packs the launch in front of the encoder takes, which ones the encoder's extra workgroups
+using PrepLaunch = void (*)(const PrepArgs&, bool biases, hipStream_t);      // the plan's k_prep* launch (per-thread or tiled kernel: prep_use_tiled)
+inline unsigned prep_grid(const PrepArgs& a, int pack_epc, bool biases) {      // per-thread kernel: one thread per output vector of the launch's packs (+ one per bias element)
+    const int64_t total = (int64_t)(a.pack_n < 0 ? a.n_packs : a.pack_n) * (H * H / pack_epc) + (biases ? (int64_t)a.n_biases * H : 0);
+    return (unsigned)((total + 255) / 256);
+}
+struct PrepSplit {
+    bool embed;             // few packs: only the encoder's packs (the last ones of the list) + the biases in front; the layer packs [0, enc_pack0) under the encoder's tail --
+    int enc_pack0;          // the whole-list launch in front of the encoder cost 10.9 us
+    PrepArgs front, layers; // the launch in front of the encoder; the embedded part (embed only)
+};
+inline PrepSplit enc_prep_split(const mshgnn_plan* p, const StepCall& c, const mshgnn_ws_layout& lay, const LaunchTraits& tr) {
+    const HostPlan& hp = p->hp;
+    PrepSplit s{};
+    const PrepArgs all{c.params, c.ws + lay.wpack, reinterpret_cast<float*>(c.ws + lay.bias), p->d_packs, p->d_biases, plan_packs(hp, tr), (int)hp.biases.size()};
+    s.enc_pack0 = all.n_packs;
+    for (int t = 0; t < hp.NT; ++t) if (hp.pack_enc_base[t] >= 0) s.enc_pack0 = std::min(s.enc_pack0, hp.pack_enc_base[t]);
+    static const bool embed_off = TUNE_ENV("MSHGNN_PREP_EMBED") && atoi(TUNE_ENV("MSHGNN_PREP_EMBED")) == 0;      // (A/B runs)
+    s.embed = tr.embed_prep && !c.series && !prep_use_tiled(all.n_packs) && s.enc_pack0 > 0 && !embed_off;
+    s.front = s.layers = all;
+    if (s.embed) { s.front.pack0 = s.enc_pack0; s.front.pack_n = all.n_packs - s.enc_pack0; s.layers.pack0 = 0; s.layers.pack_n = s.enc_pack0; }
+    return s;
+}
+
+// ---- encoder.  Returns the pitch error as the entry points report it; grid = the encoder's own workgroups + those of an embedded prep.  An embedded prep needs the
+// aligned encoder: where the rows are not aligned a.prep_vecs stays 0 and the layer images are packed in front of the encoder after all (prep_and_enc_args).
+inline int fill_enc_args(const mshgnn_plan* p, const StepCall& c, const mshgnn_ws_layout& lay, const LaunchTraits& tr, const PrepSplit& ps, EncArgs& a, unsigned& grid) {
+    const HostPlan& hp = p->hp;
+    const mshgnn_desc& d = hp.d;
+    char* ws = c.ws;
+    a.n_types = hp.NT; a.B = (int)c.batch; a.NN = hp.NN; a.tiles = (a.B + tr.enc_windows - 1) / tr.enc_windows;
+    a.wg_prefix[0] = 0;
+    const bool all_rows = c.series != nullptr && c.x != nullptr;
+    for (int t = 0; t < hp.NT; ++t) {
+        a.x[t] = c.x ? c.x[t] : nullptr; a.pitch[t] = c.x_pitch ? c.x_pitch[t] : d.type_width[t];      // (x == NULL: a series / wide route that materialises nothing)
+        if (a.pitch[t] < d.type_width[t]) return set_err(MSHGNN_EINVAL, "x_pitch smaller than the feature width");
+        a.vb[t] = vec_bytes(a.x[t], a.pitch[t], tr.in_bytes);
+        if (t == 0) a.aligned = 1;
+        if (a.vb[t] != 16 || a.pitch[t] % tr.in_epc) a.aligned = 0;
+        a.width[t] = d.type_width[t]; a.tbase[t] = hp.type_base[t]; a.nkc[t] = hp.enc_nkc[t];
+        a.pack0[t] = hp.pack_enc_base[t]; a.bias_idx[t] = hp.bias_enc[t]; a.sign_off[t] = hp.sign_off[t];
+        // the launch's nodes of this type: those whose X_0 can reach the output; with window rows to materialise (series route, x given) every node,
+        // the others marked in skip_mask
+        a.node_off[t] = t == 0 ? 0 : a.node_off[t - 1] + a.nodes[t - 1];
+        a.nodes[t] = 0;
+        for (int i = 0; i < d.type_nodes[t]; ++i) {
+            const bool need = hp.need_n[0][hp.type_base[t] + i];
+            if (need || all_rows) a.node_list[a.node_off[t] + a.nodes[t]++] = (unsigned char)i;
+            if (!need) a.skip_mask |= 1ull << (hp.type_base[t] + i);
+        }
+        a.wg_prefix[t + 1] = a.wg_prefix[t] + a.nodes[t] * a.tiles;
+    }
+    a.tbase[hp.NT] = hp.NN;
+    a.wpack = ws + lay.wpack; a.bias = reinterpret_cast<const float*>(ws + lay.bias); a.signs = p->d_signs; a.x0 = ws + lay.x[0];
+    a.mask0 = (c.training && lay.dd[0]) ? reinterpret_cast<uint8_t*>(ws + lay.dd[0]) : nullptr;
+    grid = (unsigned)a.wg_prefix[hp.NT];
+    if (ps.embed && a.aligned) { a.prep = ps.layers; a.prep_vecs = ps.enc_pack0 * (H * H / tr.pack_epc); grid += (unsigned)((a.prep_vecs + 255) / 256); }
+    return MSHGNN_OK;
+}
+
+// steps 1 and 2 of a forward up to the encoder launch: the prep launch(es) on the stream, the encoder's arguments and grid
+inline int prep_and_enc_args(const mshgnn_plan* p, const StepCall& c, const mshgnn_ws_layout& lay, const LaunchTraits& tr, PrepLaunch launch, EncArgs& a, unsigned& grid) {
+    const PrepSplit ps = enc_prep_split(p, c, lay, tr);
+    auto prep = [&](const PrepArgs& pa, bool biases) { ProfScope scope(p, p->hp.ks_prep, c.stream); launch(pa, biases, c.stream); };
+    prep(ps.front, true);
+    if (int rc = fill_enc_args(p, c, lay, tr, ps, a, grid)) return rc;
+    if (ps.embed && !a.prep_vecs) prep(ps.layers, false);      // the element-wise encoder has no embedded prep: pack the layer images in front of it after all
+    return MSHGNN_OK;
+}
+
+// where the encoder's rows come from: the plan's kernel ladder switches on this.  Adds the label workgroups of a series route to the grid.
+enum class EncRoute { SERIES_STD, SERIES, WIDE8, WIDE4, ALIGNED, ELEMENTWISE };
+inline int pick_enc_route(const StepCall& c, const EncArgs& a, const LaunchTraits& tr, unsigned& grid, EncRoute& route) {
+    route = a.aligned ? EncRoute::ALIGNED : EncRoute::ELEMENTWISE;
+    if (!tr.src_routes) return c.wide ? set_err(MSHGNN_EUNSUPPORTED, "wide source rows: not on the fp32 plan (cast the inputs)") : MSHGNN_OK;
+    if (c.series) {      // inputs gathered from the sequence's series; x = the window buffers the rows are materialised into (may be null)
+        if (c.x && !a.aligned) return set_err(MSHGNN_EINVAL, tr.series_rows_err);
+        grid += (unsigned)((c.series->lab.B + 255) / 256);      // the label workgroups
+        route = c.series->stats ? EncRoute::SERIES_STD : EncRoute::SERIES;
+    } else if (c.wide) {      // (mshgnn_*_src) the caller's fp64 / fp32 rows: converted by the encoder, plan-dtype rows written to x on the side
+        if ((c.x || tr.wide_needs_rows) && !a.aligned) return set_err(MSHGNN_EINVAL, tr.wide_rows_err);
+        route = c.wide->bytes == 8 ? EncRoute::WIDE8 : EncRoute::WIDE4;
+    }
+    return MSHGNN_OK;
+}
+
+// ---- decoder backward (the launch of its own: two-call training, plans without a fused tail)
+inline void fill_dec_bwd_args(const mshgnn_plan* p, const StepCall& c, const mshgnn_ws_layout& lay, DecArgs& a) {
+    const HostPlan& hp = p->hp;
+    const mshgnn_desc& d = hp.d;
+    char* ws = c.ws;
+    a.xl = ws + lay.x[hp.L]; a.dxl = ws + lay.dx[hp.L]; a.params = c.params; a.out_mask = p->d_out_mask; a.gout = c.grad_out;
+    a.slabs = reinterpret_cast<float*>(ws + lay.dec_slabs); a.off_w = d.off_dec_w; a.off_b = d.off_dec_b;
+    a.B = (int)c.batch; a.NN = hp.NN; a.node0 = hp.type_base[d.out_type]; a.n_out = d.type_nodes[d.out_type]; a.dout = d.out_channels; a.slab0 = 0;
+    if (c.loss == LossKind::MSE) { a.y = c.y; a.out = c.out; a.loss = c.loss_out; a.inv_n = 1.0f / (float)(c.total_windows() * a.n_out * a.dout); }
+    if (c.loss == LossKind::CE) { a.labels = c.labels; a.out = c.out; a.loss = c.loss_out; a.inv_n = 1.0f / (float)(c.total_windows() * a.n_out); }
+}
+
+// ---- stack kernels: what forward, backward and one-launch step share (offsets a launch does not read cost nothing).  tile_in, training, the programs (prog_off*),
+// mask0_off and the plan's own fields (bf16: dbg, stagger; split: lo_blk, n_img, scr0) stay with the caller.
+inline void fill_stack_common(const mshgnn_plan* p, const StepCall& c, const mshgnn_ws_layout& lay, StackArgs& a) {
+    const HostPlan& hp = p->hp;
+    a.ws = c.ws;
+    for (int l = 0; l <= hp.L; ++l) { a.x_off[l] = lay.x[l]; a.dx_off[l] = lay.dx[l]; }
+    for (int l = 0; l < hp.L; ++l) { a.mask_off[l] = lay.mask[l]; a.hb_off[l] = lay.hb[l]; a.t1_off[l] = lay.t1[l]; a.dh_off[l] = lay.dh[l]; a.du_off[l] = lay.du[l]; }
+    a.wpack = c.ws + lay.wpack; a.bias = reinterpret_cast<const float*>(c.ws + lay.bias); a.tables = p->d_tables;
+    a.B = (int)c.batch; a.NN = hp.NN; a.L = hp.L;
+    a.node0 = hp.type_base[hp.d.out_type]; a.n_out = hp.d.type_nodes[hp.d.out_type];      // the nodes that carry X_L / dX_L (the only live type of the last layer)
+    a.stash_nt = stash_nt_for(p->stash_nt_force, c.batch, stash_rows_of(hp), H * 2);      // (counted per row of 256 bytes on both plans: stash_nt_for)
+}
+// the forward's tail: decoder, and with a fused loss (one-call steps) loss and decoder backward -- c.dec_done tells the backward
+inline void fill_stack_tail(const mshgnn_plan* p, StepCall& c, const mshgnn_ws_layout& lay, StackArgs& a) {
+    const mshgnn_desc& d = p->hp.d;
+    a.params = c.params; a.out_mask = p->d_out_mask; a.out = c.out; a.off_dec_w = d.off_dec_w; a.off_dec_b = d.off_dec_b; a.dout = d.out_channels;
+    if (c.y_fused()) {
+        a.y = c.y_fused(); a.dec_slabs = reinterpret_cast<float*>(c.ws + lay.dec_slabs);
+        a.inv_n = 1.0f / (float)(c.total_windows() * a.n_out * a.dout);
+    } else if (c.labels_fused()) {      // mshgnn_step_ce: cross entropy over the per-foot logit pairs, mean over B * n_out rows
+        a.labels = c.labels_fused(); a.dec_slabs = reinterpret_cast<float*>(c.ws + lay.dec_slabs);
+        a.inv_n = 1.0f / (float)(c.total_windows() * a.n_out);
+    }
+    c.dec_done = c.y_fused() || c.labels_fused();
+}
+// One-launch step: the tail's reduction scratch (red_need bytes: one decoder slab per wave) must not touch the out-type nodes' blocks, which receive dX_L for the backward
+// sweep.  It sits in the blocks in front of them, or (models whose out type comes first: the centroidal-momentum ones) in the blocks behind them, inside lds_extent
+// (bf16: the launch's LDS; split plan: the hi plane).  False: neither fits, no one-launch step.
+inline bool place_red_scratch(int node0, int n_out, int blk_bytes, size_t red_need, size_t lds_extent, StackArgs& a) {
+    const size_t red_back = (size_t)(node0 + n_out) * blk_bytes;
+    const bool red_front_ok = (size_t)node0 * blk_bytes >= red_need, red_back_ok = red_back + red_need <= lds_extent;
+    if (!red_front_ok && !red_back_ok) return false;
+    a.red_off = red_front_ok ? 0 : (int)red_back;
+    return true;
+}
+
+// ---- weight gradients: every lane of the step, or the lanes of one phase of a two-phase step (c.gw_phase)
+inline void fill_gradw_args(const mshgnn_plan* p, const StepCall& c, const mshgnn_ws_layout& lay, const LaunchTraits& tr, int gw_parts, GradwArgs& a) {
+    const HostPlan& hp = p->hp;
+    const mshgnn_desc& d = hp.d;
+    a.ws = c.ws;
+    for (int l = 0; l <= hp.L; ++l) { a.buf_off[BUF_X + l] = lay.x[l]; a.buf_off[BUF_DX + l] = lay.dx[l]; }
+    for (int l = 0; l < hp.L; ++l) a.buf_off[BUF_MASK + l] = lay.mask[l];
+    for (int l = 0; l < hp.L; ++l) { a.buf_off[BUF_DH + l] = lay.dh[l]; a.buf_off[BUF_HB + l] = lay.hb[l]; a.buf_off[BUF_T1 + l] = lay.t1[l]; a.buf_off[BUF_DU + l] = lay.du[l]; }
+    for (int t = 0; t < hp.NT; ++t) {
+        a.x[t] = c.x ? c.x[t] : nullptr; a.pitch[t] = c.x_pitch ? c.x_pitch[t] : d.type_width[t]; a.nodes[t] = d.type_nodes[t];
+        a.vb[t] = vec_bytes(a.x[t], a.pitch[t], tr.in_bytes);
+        if (t == 0) a.aligned = 1;
+        if (a.vb[t] != 16 || a.pitch[t] % tr.in_epc) a.aligned = 0;
+    }
+    if (tr.gradw_series && c.gradw_from_series && c.series) a.ser = *c.series;      // (bf16 plan only: raw operands gathered from the series, nothing was materialised)
+    a.items = p->d_tables + hp.item_off; a.lanes = p->d_tables + hp.lane_off; a.lane_order = p->d_tables + hp.lane_order_off; a.n_pad = hp.n_lanes_pad;
+    if (c.gw_phase >= 0) { a.lane_order = p->d_tables + hp.order_ph_off[c.gw_phase]; a.n_pad = hp.npad_ph[c.gw_phase]; }
+    a.signs = p->d_signs; a.slabs = reinterpret_cast<float*>(c.ws + lay.slabs); a.B = (int)c.batch; a.n_lanes = hp.n_lanes; a.n_parts = gw_parts;
+    // (dbg / stamps stay zero: no weight-gradient kernel of this engine reads them)
+}

@@ -14,6 +14,7 @@
 //   * the MAC loop of the stack kernels is the bf16 plan's: the plan compiler (split_segs, mshgnn_plan.hpp) turns each
 //     segment into two -- the hi image with the hi and lo block of every source, the lo image with the hi block.
 #include "mshgnn_x3_stack.hpp"
+#include "mshgnn_launch.hpp"
 
 // ------------------------------------------------------------------------------------------------------
 // k_prep_x3: hi and lo MFMA B-fragment images of every weight pack (root-sum, transpose) + bias sums
@@ -373,207 +374,20 @@ __global__ __launch_bounds__(256) void k_dec_bwd_x3(DecArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------------
-// k_gradw_x3: all weight gradients of the step as one split-K MFMA launch, dW[o][k] = sum_w P[w][o] Q[w][k] with
-// P = P_hi + P_lo, Q = Q_hi + Q_lo: four staged tiles per 64-window step, P_hi Q_hi + P_hi Q_lo + P_lo Q_hi on the 32x32x16 bf16
-// MFMA.  Workgroup = (lane = one item, window part); raw encoder inputs (fp32) are split while they are staged.
+// weight gradients: all of the step as one split-K MFMA launch, dW[o][k] = sum_w P[w][o] Q[w][k] with P = P_hi + P_lo, Q = Q_hi + Q_lo: four staged tiles
+// per 32-window step (32 KB of tiles and three workgroups per CU; 64-window steps at two per CU: 339 vs 301 us), P_hi Q_hi + P_hi Q_lo + P_lo Q_hi on the
+// 32x32x16 bf16 MFMA.  Workgroup = (lane = its items, window part); raw encoder inputs (fp32) are split while they are staged.
 // ------------------------------------------------------------------------------------------------------
-#ifndef GWX3_KW
-#define GWX3_KW 32          // windows per staged step: 32 KB of tiles and three workgroups per CU (64-window steps at two per CU: 339 vs 301 us)
-#endif
 #ifndef GWX3_WPS
 #define GWX3_WPS 3
-#endif
-#ifndef GWX3_NST
-#define GWX3_NST 1          // register stages: global loads run NST steps ahead of the LDS writes
-#endif
-#ifdef MSHGNN_TUNING      // (the general split-plan weight-gradient kernel of round 2: A/B runs in tuning builds only; the lean kernel below is the product's)
-__global__ __launch_bounds__(256, GWX3_WPS) void k_gradw_x3(GradwArgs a) {
-    using T = T16;
-    constexpr int KW = GWX3_KW, NP = KW / 16, NST = GWX3_NST;      // NP: staging passes (16 rows each)
-    __shared__ __attribute__((aligned(16))) __bf16 Ph[KW * GWB_PITCH];
-    __shared__ __attribute__((aligned(16))) __bf16 Pl[KW * GWB_PITCH];
-    __shared__ __attribute__((aligned(16))) __bf16 Qh[KW * GWB_PITCH];
-    __shared__ __attribute__((aligned(16))) __bf16 Ql[KW * GWB_PITCH];
-    __shared__ __attribute__((aligned(16))) u32x4 mlut[256];       // relu byte -> AND mask of 8 bf16
-    const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    mlut[tid] = chunk_mask_bits<__bf16>(u32x4{0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu}, (unsigned)tid);   // (visible after the first barrier)
-    const int wr = wv >> 1, wc = wv & 1;
-    const int ln = a.lane_order[blockIdx.x % a.n_pad], part = blockIdx.x / a.n_pad;
-    if (ln < 0) return;
-    const int* lh = a.lanes + ln * LANE_INTS;
-    const int bias_flag = lh[3];
-    const int nchunks = (a.B + KW - 1) / KW;
-    const int ch0 = (int)((int64_t)part * nchunks / a.n_parts), ch1 = (int)((int64_t)(part + 1) * nchunks / a.n_parts);
-    const int nsteps = ch1 - ch0;            // one item per lane on the split plan
-    const int c = tid & 15, r0 = tid >> 4;   // staging: 16 chunks of 8 elements per row, 16 rows per pass
-
-    // Every operand address is a workgroup-uniform base (scalar registers, from the item table) + one small per-thread offset: the
-    // six 64-bit per-thread pointers this replaces were what pushed the kernel over its register budget.
-    const int* im = a.items + lh[0] * ITEM_INTS;
-    const T* p_hi = reinterpret_cast<const T*>(a.ws + a.buf_off[im[0]]) + x3_idx(0, im[2], a.B);      // rows of [hi 128 | lo 128]
-    const T* p_lo = p_hi + H;
-    const bool p_masked = im[9] >= 0;
-    const uint8_t* mb = p_masked ? reinterpret_cast<const uint8_t*>(a.ws + a.buf_off[im[9]]) + (((size_t)im[2] * 4) * ((a.B + 15) >> 4) << 6) : nullptr;
-    const int moff = (int)((((size_t)(c >> 2)) * ((a.B + 15) >> 4)) << 6) + ((c & 3) << 4) + r0;      // relu_byte(node, B, w, 8 c) = node base + moff + 64 (w >> 4)   (w & 15 == r0)
-    const bool q_act = im[4] >= 0;           // Q is an activation stash (two bf16 planes) / a raw fp32 input
-    const T* q_hi = nullptr; const T* q_lo = nullptr; const float* qf = nullptr;
-    int64_t qstride = H; int qvalid = 8, qvb = 16;
-    u32x4 sxa = u32x4{0, 0, 0, 0}, sxb = u32x4{0, 0, 0, 0};
-    if (q_act) {
-        q_hi = reinterpret_cast<const T*>(a.ws + a.buf_off[im[3]]) + x3_idx(0, im[5], a.B);
-        q_lo = q_hi + H;
-    } else {
-        const int t = im[3] - BUF_IN;
-        qf = reinterpret_cast<const float*>(a.x[t]) + (size_t)im[5] * a.pitch[t] + im[6];
-        qstride = (int64_t)a.nodes[t] * a.pitch[t]; qvalid = im[7] - c * 8; qvb = a.vb[t];
-        sxa = sign_xor<float>(a.signs + im[8] + c * 8); sxb = sign_xor<float>(a.signs + im[8] + c * 8 + 4);
-    }
-    const int loff = r0 * 2 * H + c * 8;                 // element offset of this thread inside a 16-row pass of an activation tensor
-    const int64_t qoff = (int64_t)r0 * qstride + c * 8;  // same for a raw input (floats)
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int q = 0; q < 16; ++q) acc[i][j][q] = 0.f;
-    float bsum[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) bsum[e] = 0.f;
-
-    struct Stage { u32x4 ph[NP], pl[NP], qa[NP], qb[NP]; unsigned mw[NP]; };     // qa / qb: the hi / lo plane rows, or the two fp32 halves of a raw row
-    auto fetch = [&](Stage& st, int s) {
-        const int w0 = (ch0 + s) * KW;       // uniform
-#pragma unroll
-        for (int p = 0; p < NP; ++p) {
-            const int wb = w0 + 16 * p, w = wb + r0;
-            st.ph[p] = u32x4{0, 0, 0, 0}; st.pl[p] = u32x4{0, 0, 0, 0}; st.qa[p] = u32x4{0, 0, 0, 0}; st.qb[p] = u32x4{0, 0, 0, 0}; st.mw[p] = 0xffffffffu;
-            if (w < a.B) {
-                st.ph[p] = ld16<(GW_NT > 1)>(p_hi + (size_t)wb * 2 * H + loff);
-                st.pl[p] = ld16<(GW_NT > 1)>(p_lo + (size_t)wb * 2 * H + loff);
-                if (p_masked) st.mw[p] = (mb + ((size_t)(wb >> 4) << 6))[moff];
-                if (q_act) {
-                    st.qa[p] = ld16<(GW_NT > 1)>(q_hi + (size_t)wb * 2 * H + loff);
-                    st.qb[p] = ld16<(GW_NT > 1)>(q_lo + (size_t)wb * 2 * H + loff);
-                } else if (a.aligned) {      // raw: a use here would serialise the loads
-                    const float* q = qf + (size_t)wb * qstride + qoff;
-                    if (qvalid > 0) st.qa[p] = ld16<(GW_NT > 0)>(q);
-                    if (qvalid > 4) st.qb[p] = ld16<(GW_NT > 0)>(q + 4);
-                } else {
-                    const float* q = qf + (size_t)wb * qstride + qoff;
-                    st.qa[p] = load_chunk<float>(q, qvalid, qvb);
-                    st.qb[p] = load_chunk<float>(q + 4, qvalid - 4, qvb);
-                }
-            }
-        }
-    };
-    auto stage_to_lds = [&](const Stage& st) {
-#pragma unroll
-        for (int p = 0; p < NP; ++p) {
-            const int row = r0 + 16 * p;
-            u32x4 ph = st.ph[p], pl = st.pl[p];
-            if (p_masked) { const u32x4 m = mlut[st.mw[p] & 0xffu]; ph &= m; pl &= m; }     // dH = dX . relu bits
-            *reinterpret_cast<u32x4*>(&Ph[gwb_elem(row, c * 8)]) = ph;
-            *reinterpret_cast<u32x4*>(&Pl[gwb_elem(row, c * 8)]) = pl;
-            u32x4 qh = st.qa[p], ql = st.qb[p];
-            if (!q_act) {      // drop pad columns, symmetry sign mask, fp32 -> hi / lo
-                const u32x4 fa = chunk_keep_first<float>(st.qa[p], qvalid) ^ sxa, fb = chunk_keep_first<float>(st.qb[p], qvalid - 4) ^ sxb;
-                split_oct(__builtin_bit_cast(f32x4, fa), __builtin_bit_cast(f32x4, fb), qh, ql);
-            }
-            *reinterpret_cast<u32x4*>(&Qh[gwb_elem(row, c * 8)]) = qh;
-            *reinterpret_cast<u32x4*>(&Ql[gwb_elem(row, c * 8)]) = ql;
-            if (bias_flag) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    bsum[2 * e] += __builtin_bit_cast(float, ph[e] << 16) + __builtin_bit_cast(float, pl[e] << 16);
-                    bsum[2 * e + 1] += __builtin_bit_cast(float, ph[e] & 0xffff0000u) + __builtin_bit_cast(float, pl[e] & 0xffff0000u);
-                }
-            }
-        }
-    };
-    auto mfmas = [&]() {
-#pragma unroll
-        for (int ks = 0; ks < KW / 16; ++ks) {
-            bf16x8 afh[2], afl[2], bqh[2], bql[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                afh[i] = tr_frag(Ph, ks * 16, wr * 64 + i * 32, lane);
-                afl[i] = tr_frag(Pl, ks * 16, wr * 64 + i * 32, lane);
-                bqh[i] = tr_frag(Qh, ks * 16, wc * 64 + i * 32, lane);
-                bql[i] = tr_frag(Ql, ks * 16, wc * 64 + i * 32, lane);
-            }
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afh[i], bqh[j], acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afh[i], bql[j], acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afl[i], bqh[j], acc[i][j], 0, 0, 0);
-                }
-        }
-    };
-    if constexpr (NST == 1) {
-        Stage sa;
-        if (nsteps > 0) fetch(sa, 0);
-        for (int s = 0; s < nsteps; ++s) {
-            __syncthreads();      // the previous MFMA phase of every wave is done reading the tiles
-            stage_to_lds(sa);
-            __syncthreads();
-            if (s + 1 < nsteps) fetch(sa, s + 1);
-            mfmas();
-        }
-    } else {
-        // two register stages: the loads of steps s + 1 and s + 2 are in flight while step s is multiplied
-        Stage sa, sb;
-        if (nsteps > 0) fetch(sa, 0);
-        if (nsteps > 1) fetch(sb, 1);
-        for (int s = 0; s < nsteps; s += 2) {
-            __syncthreads();
-            stage_to_lds(sa);
-            __syncthreads();
-            if (s + 2 < nsteps) fetch(sa, s + 2);
-            mfmas();
-            if (s + 1 < nsteps) {
-                __syncthreads();
-                stage_to_lds(sb);
-                __syncthreads();
-                if (s + 3 < nsteps) fetch(sb, s + 3);
-                mfmas();
-            }
-        }
-    }
-    float* slab = a.slabs + (size_t)(part * a.n_lanes + ln) * SLAB_FLOATS;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const int o = wr * 64 + i * 32 + (q & 3) + ((q >> 2) << 3) + ((lane >> 5) << 2), k = wc * 64 + j * 32 + (lane & 31);
-                slab[o * H + k] = acc[i][j][q];
-            }
-    if (bias_flag) {
-        float* red = reinterpret_cast<float*>(Ph);   // 16 x 128 floats = 8 KB <= one tile
-        __syncthreads();
-#pragma unroll
-        for (int e = 0; e < 8; ++e) red[r0 * H + c * 8 + e] = bsum[e];
-        __syncthreads();
-        if (tid < H) {
-            float s2 = 0.f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) s2 += red[r * H + tid];
-            slab[H * H + tid] = s2;
-        }
-    }
-}
 #endif
 
 // k_gradw_x3_lean: the same 32-window step loop with the addressing of k_gradw_bf16_lean (mshgnn.hip): a thread owns TWO CONSECUTIVE windows of
 // one 16-byte column chunk, so every global address is  workgroup-uniform stream pointer (scalar registers, advanced by scalar adds)  +  ONE
 // per-thread 32-bit offset  +  an immediate (the [hi | lo] row layout puts the four loads of an operand at +0 / +256 / +512 / +768), the relu
-// bytes of its two rows are one aligned 16-bit load, and full chunks carry no bound checks.  The general kernel above keeps six 64-bit
-// per-thread pointers alive and spills three of them (28 B of scratch per lane, reloaded inside the step loop in front of the loads that
-// need them).  A lane's items (all of one target) are swept one after the other over the lane's window part into the same accumulators (any
+// bytes of its two rows are one aligned 16-bit load, and full chunks carry no bound checks.  (Its predecessor of round 2 kept six 64-bit
+// per-thread pointers alive and spilled three of them: 28 B of scratch per lane, reloaded inside the step loop in front of the loads that
+// needed them.)  A lane's items (all of one target) are swept one after the other over the lane's window part into the same accumulators (any
 // number of items per lane: the plan picks the items-per-lane x window-parts split that fills the chip best).  ALIGNED: raw inputs in the
 // engine's own 16-byte-aligned layout; the other instantiation reads them element-wise.
 template <bool ALIGNED> __global__ __launch_bounds__(256, GWX3_WPS) void k_gradw_x3_lean(GradwArgs a) {
@@ -771,13 +585,11 @@ template <bool ALIGNED> __global__ __launch_bounds__(256, GWX3_WPS) void k_gradw
 }
 
 // ------------------------------------------------------------------------------------------------------
-// launch sequences (mirrors of forward_impl / backward_impl in mshgnn.hip)
+// launch sequences: this plan's kernel selection and launches; the argument structs are filled by mshgnn_launch.hpp, as for the fp32 / bf16 plans (mshgnn.hip)
 // ------------------------------------------------------------------------------------------------------
-int x3_launch_prep(const PrepArgs& a, hipStream_t st) {
-    const int64_t total = (int64_t)a.n_packs * (H * H / 8) + (int64_t)a.n_biases * H;
+void x3_launch_prep(const PrepArgs& a, bool biases, hipStream_t st) {
     if (prep_use_tiled(a.n_packs)) hipLaunchKernelGGL((k_prep_tiled<__bf16, true>), dim3(prep_tiled_grid(a.n_packs, a.n_biases)), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(k_prep_x3, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a);
-    return MSHGNN_OK;
+    else hipLaunchKernelGGL(k_prep_x3, dim3(prep_grid(a, 8, biases)), dim3(256), 0, st, a);
 }
 
 static int x3_lds_stack(const HostPlan& hp) { return 2 * hp.fs_blk * P16::BLK; }
@@ -818,116 +630,51 @@ int x3_set_attrs(mshgnn_plan* p) {
     return MSHGNN_OK;
 }
 
-static void x3_stack_args(const mshgnn_plan* p, const mshgnn_ws_layout& lay, char* ws, int B, StackArgs& a) {
+// what differs from the bf16 plan on the host side of a launch (mshgnn_launch.hpp): fp32 input rows, 64 windows per encoder workgroup, hi / lo weight images
+static constexpr LaunchTraits X3_TRAITS{
+    4, 4, 8, P16::BLK, 64, 8 * P16::BLK, 32,
+    /*split*/ true, /*embed_prep*/ true, /*src_routes*/ true, /*wide_needs_rows*/ true, /*gradw_series*/ false,
+    "the series gather writes 16-byte-aligned window buffers whose pitch is a multiple of 4",
+    "wide source rows: the fp32 rows need 16-byte alignment and a pitch that is a multiple of 4"};
+
+static void x3_stack_args(const mshgnn_plan* p, const StepCall& c, const mshgnn_ws_layout& lay, StackArgs& a) {
     const HostPlan& hp = p->hp;
-    a.ws = ws;
-    for (int l = 0; l <= hp.L; ++l) { a.x_off[l] = lay.x[l]; a.dx_off[l] = lay.dx[l]; }
-    for (int l = 0; l < hp.L; ++l) { a.mask_off[l] = lay.mask[l]; a.hb_off[l] = lay.hb[l]; a.t1_off[l] = lay.t1[l]; a.dh_off[l] = lay.dh[l]; a.du_off[l] = lay.du[l]; }
-    a.wpack = ws + lay.wpack; a.bias = reinterpret_cast<const float*>(ws + lay.bias); a.tables = p->d_tables;
-    a.B = B; a.NN = hp.NN; a.L = hp.L;
+    fill_stack_common(p, c, lay, a);
     a.lo_blk = hp.lo_blk; a.n_img = hp.n_img; a.scr0 = hp.x3_alias ? hp.NN - hp.n_mlp : hp.NN;
-    a.stash_nt = stash_nt_for(p->stash_nt_force, B, stash_rows_of(hp), H * 2);      // (counted per row, not per byte: stash_nt_for)
 }
 
 int x3_forward(const mshgnn_plan* p, StepCall& c) {
     const HostPlan& hp = p->hp;
-    const mshgnn_desc& d = hp.d;
-    const int training = c.training;
-    mshgnn_ws_layout lay; layout_workspace(hp, c.batch, training, &lay);
-    const int B = (int)c.batch;
-    const void* const* x = c.x; const int64_t* x_pitch = c.x_pitch;
-    char* ws = c.ws; hipStream_t st = c.stream;
-    const SeriesSrc* series = c.series; const WideSrc* wide = c.wide;
-    const float* y_fused = c.y_fused(); const int32_t* labels_fused = c.labels_fused();
-    // 1. hi / lo weight images; few packs: only the encoder's packs + biases here, the layer packs under the encoder's tail (as forward_impl of mshgnn.hip)
-    PrepArgs pa{c.params, ws + lay.wpack, reinterpret_cast<float*>(ws + lay.bias), p->d_packs, p->d_biases, hp.n_img, (int)hp.biases.size()};
-    int enc_pack0 = hp.n_img;
-    for (int t = 0; t < hp.NT; ++t) if (hp.pack_enc_base[t] >= 0) enc_pack0 = std::min(enc_pack0, hp.pack_enc_base[t]);
-    static const bool embed_off = TUNE_ENV("MSHGNN_PREP_EMBED") && atoi(TUNE_ENV("MSHGNN_PREP_EMBED")) == 0;
-    const bool embed = !prep_use_tiled(pa.n_packs) && enc_pack0 > 0 && !embed_off && !series;
-    {
-        PrepArgs a = pa;
-        if (embed) { a.pack0 = enc_pack0; a.pack_n = pa.n_packs - enc_pack0; }
-        const int64_t total = (int64_t)(embed ? a.pack_n : a.n_packs) * (H * H / 8) + (int64_t)hp.biases.size() * H;
-        ProfScope ps(p, hp.ks_prep, st);
-        if (prep_use_tiled(a.n_packs)) hipLaunchKernelGGL((k_prep_tiled<__bf16, true>), dim3(prep_tiled_grid(a.n_packs, a.n_biases)), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL(k_prep_x3, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a);
-    }
-    {   // 2. encoder (fp32 inputs)
-        EncArgs a{};
-        a.n_types = hp.NT; a.B = B; a.NN = hp.NN; a.tiles = (B + 63) / 64;
-        a.wg_prefix[0] = 0;
-        for (int t = 0; t < hp.NT; ++t) {
-            a.x[t] = x ? x[t] : nullptr; a.pitch[t] = x_pitch ? x_pitch[t] : d.type_width[t];      // (x == NULL: the series gather of mshgnn_forward_series, nothing materialised)
-            if (a.pitch[t] < d.type_width[t]) return set_err(MSHGNN_EINVAL, "x_pitch smaller than the feature width");
-            a.vb[t] = vec_bytes(a.x[t], a.pitch[t], 4);
-            if (t == 0) a.aligned = 1;
-            if (a.vb[t] != 16 || a.pitch[t] % 4) a.aligned = 0;
-            a.width[t] = d.type_width[t]; a.tbase[t] = hp.type_base[t]; a.nkc[t] = hp.enc_nkc[t];
-            a.pack0[t] = hp.pack_enc_base[t]; a.bias_idx[t] = hp.bias_enc[t]; a.sign_off[t] = hp.sign_off[t];
-            // the launch's nodes of this type (EncArgs.node_list): those whose X_0 can reach the output; with window rows to materialise every node
-            a.node_off[t] = t == 0 ? 0 : a.node_off[t - 1] + a.nodes[t - 1];
-            a.nodes[t] = 0;
-            for (int i = 0; i < d.type_nodes[t]; ++i) {
-                const bool need = hp.need_n[0][hp.type_base[t] + i];
-                if (need || (series != nullptr && x != nullptr)) a.node_list[a.node_off[t] + a.nodes[t]++] = (unsigned char)i;
-                if (!need) a.skip_mask |= 1ull << (hp.type_base[t] + i);
-            }
-            a.wg_prefix[t + 1] = a.wg_prefix[t] + a.nodes[t] * a.tiles;
-        }
-        a.tbase[hp.NT] = hp.NN;
-        a.wpack = ws + lay.wpack; a.bias = reinterpret_cast<const float*>(ws + lay.bias); a.signs = p->d_signs; a.x0 = ws + lay.x[0];
-        a.mask0 = (training && lay.dd[0]) ? reinterpret_cast<uint8_t*>(ws + lay.dd[0]) : nullptr;
-        unsigned enc_grid = (unsigned)a.wg_prefix[hp.NT];
-        if (embed) {
-            PrepArgs lp = pa; lp.pack0 = 0; lp.pack_n = enc_pack0;
-            if (a.aligned) { a.prep = lp; a.prep_vecs = enc_pack0 * (H * H / 8); enc_grid += (unsigned)((a.prep_vecs + 255) / 256); }
-            else {
-                ProfScope ps(p, hp.ks_prep, st);
-                hipLaunchKernelGGL(k_prep_x3, dim3((unsigned)(((int64_t)enc_pack0 * (H * H / 8) + 255) / 256)), dim3(256), 0, st, lp);
-            }
-        }
+    const LaunchTraits& tr = X3_TRAITS;
+    mshgnn_ws_layout lay; layout_workspace(hp, c.batch, c.training, &lay);
+    hipStream_t st = c.stream;
+    int rc;
+    {   // 1. hi / lo weight images (few packs: the layer packs under the encoder's tail, enc_prep_split), 2. encoder (fp32 inputs)
+        EncArgs a{}; unsigned enc_grid = 0; EncRoute route;
+        if ((rc = prep_and_enc_args(p, c, lay, tr, x3_launch_prep, a, enc_grid))) return rc;
         ProfScope ps(p, hp.ks_enc, st);
-        if (series) {      // inputs gathered from the sequence's series; x = the window buffers the rows are materialised into
-            if (x && !a.aligned) return set_err(MSHGNN_EINVAL, "the series gather writes 16-byte-aligned window buffers whose pitch is a multiple of 4");
-            enc_grid += (unsigned)((series->lab.B + 255) / 256);      // the label workgroups
-            if (series->stats) hipLaunchKernelGGL((k_enc_x3<true, true, 0, true>), dim3(enc_grid), dim3(256), 8 * P16::BLK, st, a, hp.n_img, *series, WideSrc{});
-            else hipLaunchKernelGGL((k_enc_x3<true, true>), dim3(enc_grid), dim3(256), 8 * P16::BLK, st, a, hp.n_img, *series, WideSrc{});
-        }
-        else if (wide) {      // (mshgnn_*_src) the caller's fp64 / fp32 rows: converted by the encoder, fp32 rows written to x on the side
-            if (!a.aligned) return set_err(MSHGNN_EINVAL, "wide source rows: the fp32 rows need 16-byte alignment and a pitch that is a multiple of 4");
-            if (wide->bytes == 8) hipLaunchKernelGGL((k_enc_x3<true, false, 8>), dim3(enc_grid), dim3(256), 8 * P16::BLK, st, a, hp.n_img, SeriesSrc{}, *wide);
-            else hipLaunchKernelGGL((k_enc_x3<true, false, 4>), dim3(enc_grid), dim3(256), 8 * P16::BLK, st, a, hp.n_img, SeriesSrc{}, *wide);
-        }
-        else if (a.aligned) hipLaunchKernelGGL(k_enc_x3<true>, dim3(enc_grid), dim3(256), 8 * P16::BLK, st, a, hp.n_img, SeriesSrc{}, WideSrc{});
-        else hipLaunchKernelGGL(k_enc_x3<false>, dim3(enc_grid), dim3(256), 8 * P16::BLK, st, a, hp.n_img, SeriesSrc{}, WideSrc{});
+        if ((rc = pick_enc_route(c, a, tr, enc_grid, route))) return rc;
+        unsigned enc_lds = tr.enc_lds;
+        auto enc = [&](auto kernel, const SeriesSrc& ser, const WideSrc& wsrc) { hipLaunchKernelGGL(kernel, dim3(enc_grid), dim3(256), enc_lds, st, a, hp.n_img, ser, wsrc); };
+        if (route == EncRoute::SERIES_STD) enc(k_enc_x3<true, true, 0, true>, *c.series, WideSrc{});
+        else if (route == EncRoute::SERIES) enc(k_enc_x3<true, true>, *c.series, WideSrc{});
+        else if (route == EncRoute::WIDE8) enc(k_enc_x3<true, false, 8>, SeriesSrc{}, *c.wide);
+        else if (route == EncRoute::WIDE4) enc(k_enc_x3<true, false, 4>, SeriesSrc{}, *c.wide);
+        else if (route == EncRoute::ALIGNED) enc(k_enc_x3<true>, SeriesSrc{}, WideSrc{});
+        else enc(k_enc_x3<false>, SeriesSrc{}, WideSrc{});
     }
-    {   // 3. all layers + decoder (+ MSE and decoder backward when y_fused)
+    {   // 3. all layers + decoder (+ loss and decoder backward with a fused loss)
         StackArgs a{};
-        x3_stack_args(p, lay, ws, B, a);
-        a.tile_in = ws + lay.x[0]; a.training = training;
+        x3_stack_args(p, c, lay, a);
+        fill_stack_tail(p, c, lay, a);
+        a.tile_in = c.ws + lay.x[0]; a.training = c.training;
         for (int l = 0; l < hp.L; ++l) a.prog_off[l] = hp.fs_fwd_off[l];
-        a.params = c.params; a.out_mask = p->d_out_mask; a.out = c.out; a.off_dec_w = d.off_dec_w; a.off_dec_b = d.off_dec_b;
-        a.node0 = hp.type_base[d.out_type]; a.n_out = d.type_nodes[d.out_type]; a.dout = d.out_channels;
-        if (y_fused) {
-            a.y = y_fused; a.dec_slabs = reinterpret_cast<float*>(ws + lay.dec_slabs);
-            a.inv_n = 1.0f / (float)(c.total_windows() * a.n_out * a.dout);
-        } else if (labels_fused) {      // mshgnn_step_ce: cross entropy over the per-foot logit pairs, mean over B * n_out rows (the tail is the bf16 plan's)
-            a.labels = labels_fused; a.dec_slabs = reinterpret_cast<float*>(ws + lay.dec_slabs);
-            a.inv_n = 1.0f / (float)(c.total_windows() * a.n_out);
-        }
-        c.dec_done = y_fused || labels_fused;
-        const int tiles = (B + P16::ROWS - 1) / P16::ROWS;
+        const int tiles = ((int)c.batch + P16::ROWS - 1) / P16::ROWS;
         a.stamps = stamp_ptr("MSHGNN_STAMPS");
-        // one-call step: the backward sweep in the same launch.  The tail's reduction scratch (one decoder slab per wave) must not touch the out-type nodes' blocks
-        // of either plane, which receive dX_L for the backward sweep: it sits in the hi plane's blocks in front of them, or (models whose out type comes first: the
-        // centroidal-momentum ones) in the hi plane's blocks behind them -- as on the bf16 plan (forward_impl, mshgnn.hip)
-        const size_t red_need = (size_t)(LAYER_THREADS / 64) * DEC_SLAB_FLOATS * sizeof(float);
-        const size_t red_back = (size_t)(a.node0 + a.n_out) * P16::BLK, plane = (size_t)hp.fs_blk * P16::BLK;
-        const bool red_front_ok = (size_t)a.node0 * P16::BLK >= red_need, red_back_ok = red_back + red_need <= plane;
-        // (a two-phase step, c.gw_phase >= 0, keeps the backward sweep a launch of its own on this plan)
-        const bool step = c.gw_phase < 0 && c.dec_done && p->use_step && (red_front_ok || red_back_ok);
-        if (step && !red_front_ok) a.red_off = (int)red_back;
+        // one-call step: the backward sweep in the same launch, the tail's reduction scratch in the hi plane (place_red_scratch)
+        // (a two-phase step, c.gw_phase >= 0, keeps the backward sweep a launch of its own on this plan; the bf16 plan has no such condition)
+        const bool step = c.gw_phase < 0 && c.dec_done && p->use_step &&
+                          place_red_scratch(a.node0, a.n_out, tr.blk, (size_t)(LAYER_THREADS / 64) * DEC_SLAB_FLOATS * sizeof(float), (size_t)hp.fs_blk * tr.blk, a);
         ProfScope ps(p, step ? hp.ks_stack_step : hp.ks_stack_fwd, st);
         if (step) {
             a.mask0_off = lay.dd[0];
@@ -948,58 +695,34 @@ int x3_forward(const mshgnn_plan* p, StepCall& c) {
 
 int x3_backward(const mshgnn_plan* p, const StepCall& c) {
     const HostPlan& hp = p->hp;
-    const mshgnn_desc& d = hp.d;
+    const LaunchTraits& tr = X3_TRAITS;
     mshgnn_ws_layout lay; layout_workspace(hp, c.batch, 1, &lay);
     const int B = (int)c.batch;
-    const void* const* x = c.x; const int64_t* x_pitch = c.x_pitch;
-    char* ws = c.ws; hipStream_t st = c.stream;
-    const int gw_phase = c.gw_phase;
-    if (!c.dec_done && gw_phase != 1) {
+    hipStream_t st = c.stream;
+    if (!c.dec_done && c.gw_phase != 1) {
         DecArgs a{};
-        a.xl = ws + lay.x[hp.L]; a.dxl = ws + lay.dx[hp.L]; a.params = c.params; a.out_mask = p->d_out_mask; a.gout = c.grad_out;
-        a.slabs = reinterpret_cast<float*>(ws + lay.dec_slabs); a.off_w = d.off_dec_w; a.off_b = d.off_dec_b;
-        a.B = B; a.NN = hp.NN; a.node0 = hp.type_base[d.out_type]; a.n_out = d.type_nodes[d.out_type]; a.dout = d.out_channels; a.slab0 = 0;
-        if (c.loss == LossKind::MSE) { a.y = c.y; a.out = c.out; a.loss = c.loss_out; a.inv_n = 1.0f / (float)(c.total_windows() * a.n_out * a.dout); }
-        if (c.loss == LossKind::CE) { a.labels = c.labels; a.out = c.out; a.loss = c.loss_out; a.inv_n = 1.0f / (float)(c.total_windows() * a.n_out); }
+        fill_dec_bwd_args(p, c, lay, a);
         ProfScope ps(p, hp.ks_dec_bwd, st);
         hipLaunchKernelGGL(k_dec_bwd_x3, dim3(NWG_DEC), dim3(256), 0, st, a);
     }
-    if (gw_phase != 1 && !c.stack_done) {
+    if (c.gw_phase != 1 && !c.stack_done) {
         StackArgs a{};
-        x3_stack_args(p, lay, ws, B, a);
-        a.tile_in = ws + lay.dx[hp.L]; a.training = 1; a.mask0_off = lay.dd[0];
+        x3_stack_args(p, c, lay, a);
+        a.tile_in = c.ws + lay.dx[hp.L]; a.training = 1; a.mask0_off = lay.dd[0];
         for (int l = 0; l < hp.L; ++l) a.prog_off[l] = hp.fs_bwd_off[l];
         const int tiles = (B + P16::ROWS - 1) / P16::ROWS;
         ProfScope ps(p, hp.ks_stack_bwd, st);
         if (StackKernelX3 kb = p->use_spec ? x3_spec_kernel(hp, 2) : nullptr) hipLaunchKernelGGL(kb, dim3(tiles), dim3(LAYER_THREADS), x3_lds_stack(hp), st, a);
         else hipLaunchKernelGGL(k_stack_bwd_x3, dim3(tiles), dim3(LAYER_THREADS), x3_lds_stack(hp), st, a);
     }
-    const int gw_parts = gw_parts_for(hp.n_parts, hp.n_lanes, hp.gw_ipl, B, 32, p->n_cu);      // window parts of this batch's weight-gradient launch (32-window steps)
+    const int gw_parts = gw_parts_for(hp.n_parts, hp.n_lanes, hp.gw_ipl, B, tr.gw_windows, p->n_cu);      // window parts of this batch's weight-gradient launch (32-window steps)
     if (c.grad_params) {      // (NULL: activation backward only)
         GradwArgs a{};
-        a.ws = ws;
-        for (int l = 0; l <= hp.L; ++l) { a.buf_off[BUF_X + l] = lay.x[l]; a.buf_off[BUF_DX + l] = lay.dx[l]; }
-        for (int l = 0; l < hp.L; ++l) a.buf_off[BUF_MASK + l] = lay.mask[l];
-        for (int l = 0; l < hp.L; ++l) { a.buf_off[BUF_DH + l] = lay.dh[l]; a.buf_off[BUF_HB + l] = lay.hb[l]; a.buf_off[BUF_T1 + l] = lay.t1[l]; a.buf_off[BUF_DU + l] = lay.du[l]; }
-        for (int t = 0; t < hp.NT; ++t) {
-            a.x[t] = x[t]; a.pitch[t] = x_pitch ? x_pitch[t] : d.type_width[t]; a.nodes[t] = d.type_nodes[t];
-            a.vb[t] = vec_bytes(x[t], a.pitch[t], 4);
-            if (t == 0) a.aligned = 1;
-            if (a.vb[t] != 16 || a.pitch[t] % 4) a.aligned = 0;
-        }
-        a.items = p->d_tables + hp.item_off; a.lanes = p->d_tables + hp.lane_off; a.lane_order = p->d_tables + hp.lane_order_off; a.n_pad = hp.n_lanes_pad;
-        if (gw_phase >= 0) { a.lane_order = p->d_tables + hp.order_ph_off[gw_phase]; a.n_pad = hp.npad_ph[gw_phase]; }
-        a.signs = p->d_signs; a.slabs = reinterpret_cast<float*>(ws + lay.slabs); a.B = B; a.n_lanes = hp.n_lanes; a.n_parts = gw_parts;
+        fill_gradw_args(p, c, lay, tr, gw_parts, a);
         ProfScope ps(p, hp.ks_gradw, st);
-        [[maybe_unused]] static const bool gw_general = TUNE_ENV("MSHGNN_GRADW") && std::string(TUNE_ENV("MSHGNN_GRADW")) == "general";   // read once: the general kernel also where the lean one applies (A/B runs)
-        if (a.n_pad > 0) {
-#ifdef MSHGNN_TUNING
-            if (gw_general && hp.gw_ipl == 1) hipLaunchKernelGGL(k_gradw_x3, dim3(a.n_pad * gw_parts), dim3(256), 0, st, a);
-            else
-#endif
-            if (a.aligned) hipLaunchKernelGGL(k_gradw_x3_lean<true>, dim3(a.n_pad * gw_parts), dim3(256), 0, st, a);
-            else hipLaunchKernelGGL(k_gradw_x3_lean<false>, dim3(a.n_pad * gw_parts), dim3(256), 0, st, a);
-        }
+        if (a.n_pad <= 0) {}      // (a phase without lanes)
+        else if (a.aligned) hipLaunchKernelGGL(k_gradw_x3_lean<true>, dim3(a.n_pad * gw_parts), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL(k_gradw_x3_lean<false>, dim3(a.n_pad * gw_parts), dim3(256), 0, st, a);
     }
     return run_finalize(p, c, lay, gw_parts);
 }
