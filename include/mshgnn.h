@@ -341,8 +341,23 @@ typedef struct mshgnn_window_desc {
     int32_t run_ptrs_ready;   /* mshgnn_step_*_series: != 0 = the caller states that the run_ptrs scratch still holds what an earlier call with THIS descriptor and
                                * THESE source arrays wrote there (the runs' column pointers depend on nothing else): the one-workgroup launch that resolves them
                                * in front of the encoder (4.8 us) is skipped.  0: resolve them (always safe).                                       */
-    int32_t reserved_;
+    int32_t sign_flags;       /* group-transformed windows (the field was reserved: ABI 6 as before, a zero means what it meant).  bit 0: the caller states that
+                               * `runs` source words and `label_cols` entries may carry MSHGNN_WINDOW_SIGN_FLAG (see below); with bit 0 clear the tables are read
+                               * as they always were.  bit 1: the caller vouches that an earlier call with THIS descriptor (same tables) returned MSHGNN_OK, so
+                               * the tables are not read back and checked again (the check is one small synchronous device-to-host copy: not capturable). */
 } mshgnn_window_desc;
+
+/* SIGNED RUNS AND LABELS (sign_flags bit 0): g . window for an element g of a morphological symmetry group is a choice of columns and a +-1 per column, so it
+ * is described by the same tables over the same resident series:
+ *   runs[r][3]     = MSHGNN_WINDOW_SIGN_FLAG | source << 8 | column   (sources are < 12, columns < 256: bit 30 is free) -- the run's elements are negated
+ *   label_cols[k]  = MSHGNN_WINDOW_SIGN_FLAG | column                 -- label k is negated (after the body-frame rotation; labels_out stays y != 0)
+ * The negation is an XOR of the element's sign bit (0x80000000 on fp32, 0x8000 on bf16), never a multiply: exact, it commutes bit for bit with the bf16
+ * rounding and -- up to the sign of a zero -- with the per-window standardisation, which is computed on the negated run.  Every gather applies it
+ * (mshgnn_assemble_windows, mshgnn_forward_series, mshgnn_step_*_series[_std], x_out == NULL included), and the windows a training step writes to x_out are the
+ * transformed ones.  quat_out is not transformed.  Refused with MSHGNN_EINVAL before any launch (unless bit 1 vouches): a negative source word other than -1
+ * (the constant-1 run is the word -1 and cannot carry a sign), a source >= n_src, a label column whose column part is outside [0, 256) -- and a stream that
+ * is being captured while the check is still due.                                                                                                        */
+#define MSHGNN_WINDOW_SIGN_FLAG (1 << 30)
 
 int mshgnn_assemble_windows(const mshgnn_window_desc* desc, const float* const* src, const int64_t* src_cstride,
                             const int64_t* src_rows, const int64_t* starts /* device int64[batch] */, int64_t batch,

@@ -114,9 +114,13 @@ __device__ __forceinline__ u32x4 splice8(u32x4 A, u32x4 B, int n0) {      // bf1
 // piece, as k_enc_x3<.., SERIES>) and every run with a source column is standardised over its window with the statistics k_series_stats left in ser.stats --
 // fp64 -> fp32 -> bf16, the roundings of mshgnn_assemble_windows(normalize) (standardise_one, mshgnn_device.hpp).  Evaluation materialises nothing (a.x null);
 // the training steps (mshgnn_step_*_series_std) get the standardised bf16 rows written to a.x like the plain SERIES rows, behind the next chunk's loads.
-template <typename T, bool ALIGNED, bool SERIES = false, int SRC = 0, bool NORM = false> __global__ __launch_bounds__(256) void k_enc_fwd(EncArgs a, SeriesSrc ser, WideSrc wsrc) {
+// SIGN (with SERIES; a descriptor with sign_flags): the run pointers may carry RUN_PTR_SIGN -- the chunk's elements are negated per element (sign_mask8_*: a chunk's
+// two runs may differ) before the standardisation and before the window rows are written out, so a.x receives g . window.  Unsigned descriptors launch the
+// instantiations without it: the code they always ran.
+template <typename T, bool ALIGNED, bool SERIES = false, int SRC = 0, bool NORM = false, bool SIGN = false> __global__ __launch_bounds__(256) void k_enc_fwd(EncArgs a, SeriesSrc ser, WideSrc wsrc) {
     using P = Prec<T>;
     static_assert(!NORM || SERIES, "standardisation is part of the series gather");
+    static_assert(!SIGN || SERIES, "signs are part of the series gather");
     static_assert(!SERIES || (sizeof(T) == 2 && ALIGNED), "the series gather is a bf16 path");
     static_assert(SRC == 0 || (sizeof(T) == 2 && ALIGNED && !SERIES), "wide source rows: bf16 plan, aligned destination rows");
     constexpr int MB = P::ENC_MB;                       // row blocks (of 16 windows) per workgroup
@@ -170,6 +174,7 @@ template <typename T, bool ALIGNED, bool SERIES = false, int SRC = 0, bool NORM 
     u32x4 vn[NORM ? MB / BPP : 1][2];
     RunStats rsa[NORM ? MB / BPP : 1], rsb[NORM ? MB / BPP : 1];
     int n_n0 = 8; bool n_has_a = false, n_has_b = false;
+    int g_n0 = 8; bool g_fa = false, g_fb = false;      // SIGN: how the fetched chunk divides between its two runs and their sign flags (set by fetch, read by the next staging pass)
     __shared__ unsigned long long rp_s[SERIES ? 16 : 1];      // SERIES: the column pointers of this node row's first 16 runs (a chunk takes its pieces from runs j, j + 1)
     int rfirst = 0, rend = 0;
     if constexpr (SERIES) {
@@ -189,7 +194,11 @@ template <typename T, bool ALIGNED, bool SERIES = false, int SRC = 0, bool NORM 
             const bool second = nvalid > n0;
             // (runs past the 16th -- a node row of more than 16 T-long variables -- come from the global table: a dependent load, rare recipes only)
             auto run_ptr_of = [&](int jj) -> unsigned long long { return jj < 16 ? rp_s[jj] : (rfirst + jj < rend ? ser.run_ptr[rfirst + jj] : 0ull); };
-            const unsigned long long pa = nvalid > 0 ? run_ptr_of(j) : 0ull, pb = second ? run_ptr_of(j + 1) : 0ull;
+            unsigned long long pa = nvalid > 0 ? run_ptr_of(j) : 0ull, pb = second ? run_ptr_of(j + 1) : 0ull;
+            if constexpr (SIGN) {
+                g_n0 = n0; g_fa = (pa & RUN_PTR_SIGN) != 0; g_fb = (pb & RUN_PTR_SIGN) != 0;
+                pa = run_ptr_addr(pa); pb = run_ptr_addr(pb);
+            }
             if constexpr (NORM) {
                 n_n0 = n0; n_has_a = pa != 0ull; n_has_b = pb != 0ull;
                 const u32x4 ones32 = u32x4{0x3f800000u, 0x3f800000u, 0x3f800000u, 0x3f800000u};      // the constant-1 run
@@ -263,6 +272,9 @@ template <typename T, bool ALIGNED, bool SERIES = false, int SRC = 0, bool NORM 
     for (int kc = 0; kc < nkc; ++kc) {
         const u32x4 sx = sign_xor<T>(sg + kc * H + c * P::EPC);   // apply_symmetry: +-1 mask as a sign-bit XOR
         const int nv = F - (kc * H + c * P::EPC);                  // valid elements of this thread's chunk (pad columns dropped)
+        u32x4 gm = u32x4{0, 0, 0, 0}, gm0 = gm, gm1 = gm;          // SIGN: the chunk's per-element sign masks (bf16 elements; NORM: the fp32 elements it standardises)
+        if constexpr (SIGN && NORM) sign_mask8_f32(g_n0, g_fa, g_fb, gm0, gm1);
+        else if constexpr (SIGN) gm = sign_mask8_bf16(g_n0, g_fa, g_fb);
         __syncthreads();   // previous chunk's MFMAs are done reading LDS
 #pragma unroll
         for (int mi = 0; mi < MB / BPP; ++mi)
@@ -275,10 +287,13 @@ template <typename T, bool ALIGNED, bool SERIES = false, int SRC = 0, bool NORM 
                     raw = pack_oct(lo4, hi4);
                 } else if constexpr (NORM) {
                     u32x4 a0 = vn[mi][0], a1 = vn[mi][1];
+                    if constexpr (SIGN) { a0 ^= gm0; a1 ^= gm1; }
                     standardise_oct(a0, a1, n_n0, n_has_a, n_has_b, rsa[mi], rsb[mi]);
                     raw = pack_oct(__builtin_bit_cast(f32x4, a0), __builtin_bit_cast(f32x4, a1));
                     if (kc + 1 == nkc) raw = chunk_keep_first<T>(raw, nv);
-                } else
+                } else if constexpr (SIGN)
+                raw = kc + 1 == nkc ? chunk_keep_first<T>(v[mi][it] ^ gm, nv) : v[mi][it] ^ gm;
+                else
                 raw = kc + 1 == nkc ? chunk_keep_first<T>(v[mi][it], nv) : v[mi][it];      // only the last K chunk has pad columns
                 *reinterpret_cast<u32x4*>(smem + lds_chunk<T>(mi * BPP + sub, r0 + it * (256 / P::CPR), c)) = raw ^ sx;
                 if constexpr (SERIES || SRC > 0) rawv[mi][it] = raw;
@@ -1321,7 +1336,10 @@ template <bool ALIGNED, bool SERIES = false> __global__ __launch_bounds__(256, G
         if constexpr (SERIES) {      // elements [k0, k0 + 8) of the node row: n0 from run j at time offset off, the rest from run j + 1 at offset 0
             const int k0 = im[6] + c * 8, j = k0 / a.ser.T, off = k0 - j * a.ser.T, n0 = min(8, a.ser.T - off);
             const int rfirst = a.ser.rows[2 * (a.ser.row0[qt] + im[5])];
-            const unsigned long long pa = qn > 0 ? a.ser.run_ptr[rfirst + j] : 0ull, pb = min(qn, 8) > n0 ? a.ser.run_ptr[rfirst + j + 1] : 0ull;
+            unsigned long long pa = qn > 0 ? a.ser.run_ptr[rfirst + j] : 0ull, pb = min(qn, 8) > n0 ? a.ser.run_ptr[rfirst + j + 1] : 0ull;
+            // negated runs (RUN_PTR_SIGN): the chunk's per-element sign mask joins the symmetry mask of (item, chunk) -- nothing changes in the loop
+            if ((pa | pb) & RUN_PTR_SIGN) qsign_t[tid >> 4][c] ^= chunk_keep_first<T>(sign_mask8_bf16(n0, (pa & RUN_PTR_SIGN) != 0, (pb & RUN_PTR_SIGN) != 0), qn);
+            pa = run_ptr_addr(pa); pb = run_ptr_addr(pb);
             sser[tid >> 4][c][0] = pa ? pa + (unsigned long long)off * sizeof(T) : 0ull;
             sser[tid >> 4][c][1] = pb;
         }
@@ -1844,7 +1862,9 @@ static int forward_impl(const mshgnn_plan* p, StepCall& c) {
         if (route == EncRoute::ALIGNED) enc(k_enc_fwd<T, true>, SeriesSrc{}, WideSrc{});
         else if (route == EncRoute::ELEMENTWISE) enc(k_enc_fwd<T, false>, SeriesSrc{}, WideSrc{});
         else if constexpr (sizeof(T) == 2) {      // (plan_traits<float>.src_routes is false: the fp32 plan takes no other route)
-            if (route == EncRoute::SERIES_STD) enc(k_enc_fwd<T, true, true, 0, true>, *c.series, WideSrc{});
+            if (route == EncRoute::SERIES_STD && c.series->sign) enc(k_enc_fwd<T, true, true, 0, true, true>, *c.series, WideSrc{});
+            else if (route == EncRoute::SERIES && c.series->sign) enc(k_enc_fwd<T, true, true, 0, false, true>, *c.series, WideSrc{});
+            else if (route == EncRoute::SERIES_STD) enc(k_enc_fwd<T, true, true, 0, true>, *c.series, WideSrc{});
             else if (route == EncRoute::SERIES) enc(k_enc_fwd<T, true, true>, *c.series, WideSrc{});
             else if (route == EncRoute::WIDE8) enc(k_enc_fwd<T, true, false, 8>, SeriesSrc{}, *c.wide);      // (x may be null: nothing written on the side)
             else enc(k_enc_fwd<T, true, false, 4>, SeriesSrc{}, *c.wide);
@@ -2180,12 +2200,13 @@ extern "C" int mshgnn_step_mse_phase(const mshgnn_plan* p, const void* const* x,
 __global__ void k_series_run_ptrs(const int* runs, int n_runs, WindowArgs wa, int elem_bytes, unsigned long long* run_ptr) {
     const int r = threadIdx.x;
     if (r >= n_runs) return;
-    const int sc = runs[(size_t)r * 5 + 3];
+    bool neg;
+    const int sc = run_source(runs[(size_t)r * 5 + 3], wa.sign, neg);
     unsigned long long p = 0ull;
 #pragma unroll
     for (int k = 0; k < WIN_MAX_SRC; ++k)
         if (sc >= 0 && (sc >> 8) == k) p = (unsigned long long)(reinterpret_cast<const char*>(wa.src[k]) + (size_t)(sc & 0xff) * wa.src_cstride[k] * elem_bytes);
-    run_ptr[r] = p;
+    run_ptr[r] = p | (neg && p ? RUN_PTR_SIGN : 0ull);      // a negated run: the flag rides in bit 63, masked off by every gather (run_ptr_addr)
 }
 
 // ---- what the series routes share: the caller's description of the sequence and the windows, one check of the window descriptor against the plan, one fill of
@@ -2246,6 +2267,7 @@ static int check_label_rotation(const SeriesArgs& s, const SeriesChecks& k) {
 }
 // the source arrays the gather reads: the fp32 series (split plan, standardised recipes) or their bf16 copies
 static int check_series_sources(const SeriesArgs& s, bool fp32_gather, WindowArgs& wa) {
+    wa.sign = s.d->sign_flags & 1;
     for (int i = 0; i < s.d->n_src; ++i) {
         // (8 elements of slack behind every column: a chunk's 16-byte loads may run past the window's last step)
         if (!s.src[i] || (!fp32_gather && !s.src_bf16[i]) || s.src_rows[i] < s.d->history || s.src_cstride[i] < s.src_rows[i] + 8 || s.src_rows[i] >= (1ll << 31))
@@ -2269,8 +2291,9 @@ static void fill_series_src(const SeriesArgs& s, const WindowArgs& wa, bool fp32
         const bool q = d->quat_src >= 0 && (want_q || d->label_rotate);
         l.quat_src = q ? s.src[d->quat_src] : nullptr; l.quat_cs = q ? s.src_cstride[d->quat_src] : 0;
         l.starts = s.starts; l.B = s.batch; l.T = d->history; l.label_cols = d->label_cols; l.n_label = want_y ? d->n_label : 0; l.label_rotate = want_y ? d->label_rotate : 0;
-        l.y = s.y_out; l.quat = s.quat_out; l.labels_int = s.labels_out;
+        l.y = s.y_out; l.quat = s.quat_out; l.labels_int = s.labels_out; l.sign = d->sign_flags & 1;
     }
+    ser.sign = d->sign_flags & 1;
     ser.run_ptr = reinterpret_cast<const unsigned long long*>(s.run_ptrs); ser.rows = d->rows; ser.starts = s.starts; ser.T = d->history;
     { int r0 = 0; for (int t = 0; t < d->n_types; ++t) { ser.row0[t] = r0; r0 += d->type_nodes[t]; } }
 }
@@ -2313,6 +2336,7 @@ static int step_series(const mshgnn_plan* p, const SeriesArgs& s, bool std_route
     if (const int rc = check_window_desc(p, s, k, x_out, x_pitch)) return rc;
     if (const int rc = check_series_sources(s, fp32_gather, wa)) return rc;
     if (const int rc = check_label_rotation(s, k)) return rc;
+    if (const int rc = check_sign_tables(s.d, true, (hipStream_t)stream)) return rc;
     SeriesSrc ser{};
     fill_series_src(s, wa, fp32_gather, /*want_q: the quaternion travels with the labels wherever the recipe has one*/ true, (hipStream_t)stream, ser);
     if (std_route) {
@@ -2379,13 +2403,14 @@ __global__ __launch_bounds__(256) void k_series_stats(const int* runs, int n_run
     const unsigned long long p = run_ptr[r];
     RunStats rs{0.0, 1.0};      // constant-one runs are left alone (never applied)
     if (p) {
-        const float* sp = reinterpret_cast<const float*>(p) + starts[b];
+        const float* sp = reinterpret_cast<const float*>(run_ptr_addr(p)) + starts[b];
+        const bool neg = (p & RUN_PTR_SIGN) != 0;      // the statistics of the NEGATED run, as mshgnn_assemble_windows computes them
         float v[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int k = 2 * lane + 128 * (q >> 1) + (q & 1);
             v[q] = 1.0f;
-            if (k < len) v[q] = sp[k];
+            if (k < len) v[q] = xor_sign(sp[k], neg);
         }
         rs = run_stats(v, len, lane);
     }
@@ -2423,6 +2448,7 @@ extern "C" int mshgnn_forward_series(const mshgnn_plan* p, const mshgnn_window_d
     WindowArgs wa{};
     if (const int rc = check_series_sources(s, fp32_gather, wa)) return rc;
     hipStream_t st = (hipStream_t)stream;
+    if (const int rc = check_sign_tables(d, d->n_label > 0 && d->label_cols != nullptr, st)) return rc;      // (the whole descriptor: the caller vouches for all of it afterwards)
     SeriesSrc ser{};
     fill_series_src(s, wa, fp32_gather, quat_out != nullptr && d->quat_src >= 0, st, ser);
     if (norm) {

@@ -384,12 +384,38 @@ struct EncArgs {
 // Labels of a batch of windows (mshgnn_assemble_windows / mshgnn_step_*_series): y[b][k] = label series column label_cols[k] at the window's last
 // step; label_rotate: the 3-D world-frame GRFs are taken into the body frame with the world->body quaternion of that step, R f per foot (the
 // as_matrix() @ grfs_T branch of load_data_at_dataset_seq_3d); quat out = that quaternion (data.r_o, quadSDKDataset_Morph.py:365-367).
+// GROUP-TRANSFORMED WINDOWS (mshgnn_window_desc.sign_flags, include/mshgnn.h): a run's source word and a label column may carry MSHGNN_WINDOW_SIGN_FLAG -- the
+// element is negated, as an XOR of its sign bit (exact; commutes with the bf16 rounding and with run_stats / standardise_one up to the sign of a zero).
+// k_series_run_ptrs carries a run's flag in bit 63 of its column pointer (RUN_PTR_SIGN), which every gather masks off before it forms an address.
+constexpr int WIN_SIGN_FLAG = MSHGNN_WINDOW_SIGN_FLAG;
+constexpr unsigned long long RUN_PTR_SIGN = 1ull << 63;
+__device__ __forceinline__ unsigned long long run_ptr_addr(unsigned long long p) { return p & ~RUN_PTR_SIGN; }
+__device__ __forceinline__ float xor_sign(float x, bool neg) { return __uint_as_float(__float_as_uint(x) ^ (neg ? 0x80000000u : 0u)); }
+// the source word of a run: sign_tables != 0 -> the flag is split off (neg); else the word means what it always meant
+__device__ __forceinline__ int run_source(int sc, int sign_tables, bool& neg) {
+    neg = sign_tables != 0 && sc >= 0 && (sc & WIN_SIGN_FLAG) != 0;
+    return neg ? (sc & ~WIN_SIGN_FLAG) : sc;
+}
+// Per-element sign masks of a 16-byte chunk of a node row: its first n0 elements come from a run with flag fa, the rest from the next run with flag fb (two
+// runs of one row may have opposite signs, and the split point is wherever the history length puts it).  8 bf16 / 8 fp32 elements.
+__device__ __forceinline__ u32x4 sign_mask8_bf16(int n0, bool fa, bool fb) {
+    u32x4 m;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) m[i] = ((2 * i < n0 ? fa : fb) ? 0x8000u : 0u) | ((2 * i + 1 < n0 ? fa : fb) ? 0x80000000u : 0u);
+    return m;
+}
+__device__ __forceinline__ void sign_mask8_f32(int n0, bool fa, bool fb, u32x4& m0, u32x4& m1) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { m0[e] = (e < n0 ? fa : fb) ? 0x80000000u : 0u; m1[e] = (e + 4 < n0 ? fa : fb) ? 0x80000000u : 0u; }
+}
+
 struct LabelArgs {
     const float* lab; int64_t lab_cs;            // the label series (column-major: element (row, c) at c * lab_cs + row)
     const float* quat_src; int64_t quat_cs;      // the quaternion series or nullptr
     const int64_t* starts; int64_t B; int T;
     const int* label_cols; int n_label, label_rotate;
     float* y; float* quat; int32_t* labels_int;  // labels_int (nullable): contact flags y != 0 for the fused cross entropy (mshgnn_step_ce_series)
+    int sign;                                    // label_cols entries may carry WIN_SIGN_FLAG: the label is negated AFTER the rotation (labels_int stays y != 0)
 };
 
 __device__ __forceinline__ void window_labels_one(const LabelArgs& a, int64_t b) {
@@ -417,21 +443,29 @@ __device__ __forceinline__ void window_labels_one(const LabelArgs& a, int64_t b)
     constexpr int LMAX = 24;
     for (int k0 = 0; k0 < a.n_label; k0 += LMAX) {
         float v[LMAX];
+        unsigned neg = 0;      // bit j: label k0 + j is negated
 #pragma unroll
-        for (int j = 0; j < LMAX; ++j) v[j] = k0 + j < a.n_label ? lab[a.label_cols[k0 + j] * lcs] : 0.f;
+        for (int j = 0; j < LMAX; ++j) {
+            v[j] = 0.f;
+            if (k0 + j < a.n_label) {
+                int lc = a.label_cols[k0 + j];
+                if (a.sign) { neg |= (unsigned)((lc >> 30) & 1) << j; lc &= ~WIN_SIGN_FLAG; }
+                v[j] = lab[lc * lcs];
+            }
+        }
         if (a.label_rotate) {
 #pragma unroll
             for (int j = 0; j + 2 < LMAX; j += 3) {
                 if (k0 + j + 2 >= a.n_label) break;
 #pragma unroll
                 for (int i = 0; i < 3; ++i)
-                    a.y[b * a.n_label + k0 + j + i] = (float)(R[i][0] * (double)v[j] + R[i][1] * (double)v[j + 1] + R[i][2] * (double)v[j + 2]);
+                    a.y[b * a.n_label + k0 + j + i] = xor_sign((float)(R[i][0] * (double)v[j] + R[i][1] * (double)v[j + 1] + R[i][2] * (double)v[j + 2]), (neg >> (j + i)) & 1u);
             }
         } else {
 #pragma unroll
             for (int j = 0; j < LMAX; ++j) {
                 if (k0 + j >= a.n_label) break;
-                a.y[b * a.n_label + k0 + j] = v[j];
+                a.y[b * a.n_label + k0 + j] = xor_sign(v[j], (neg >> j) & 1u);
                 if (a.labels_int) a.labels_int[b * a.n_label + k0 + j] = v[j] != 0.f;
             }
         }
@@ -448,6 +482,7 @@ struct SeriesSrc {
     LabelArgs lab;                       // the batch's labels: computed by extra workgroups of the fused-gather encoder launch (lab.B == 0: none)
     const double* stats;                 // standardised recipes (mshgnn_forward_series): {mean, sd} of every (window, run), [B][n_runs][2] (k_series_stats)
     int n_runs;
+    int sign;                            // the run pointers may carry RUN_PTR_SIGN (a descriptor with sign_flags): the SIGN instantiations of the encoders run
 };
 
 // The caller's sequence and windows as mshgnn_assemble_windows (mshgnn_windows.hip) gathers them; the series entry points (mshgnn.hip) fill the same structure
@@ -462,7 +497,10 @@ struct WindowArgs {
     const int64_t* starts; int64_t B; int T, normalize;
     const int* label_cols; int n_label, label_src, label_rotate, quat_src;
     float* y; float* quat;
+    int sign;                               // mshgnn_window_desc.sign_flags & 1: source words and label columns may carry WIN_SIGN_FLAG
 };
+// the sign tables of a descriptor read back and checked on the host (mshgnn_windows.hip): MSHGNN_OK when there is nothing to check or the caller vouches
+int check_sign_tables(const mshgnn_window_desc* d, bool labels, hipStream_t st);
 
 // Per-window standardisation of one run (flexibleDataset.py:390-396): (x - mean) / sd with the unbiased estimator, in fp64, NaN -> 0.  THE arithmetic of
 // mshgnn_assemble_windows(normalize) and of the standardising series encoders (mshgnn_forward_series): both call these two functions, so the bits agree by

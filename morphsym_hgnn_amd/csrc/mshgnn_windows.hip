@@ -25,7 +25,9 @@ template <typename T, int NSET> __global__ __launch_bounds__(256) void k_assembl
 #pragma unroll
     for (int set = 0; set < NSET; ++set) {
         const int* run = a.runs + (size_t)min(lane + 64 * set, a.n_runs - 1) * 5;
-        const int t = run[0], node = run[1], f0 = run[2], sc = run[3];
+        const int t = run[0], node = run[1], f0 = run[2];
+        bool neg;
+        const int sc = run_source(run[3], a.sign, neg);
         const float* sp = nullptr;
 #pragma unroll
         for (int k = 0; k < WIN_MAX_SRC; ++k) if (sc >= 0 && (sc >> 8) == k) sp = a.src[k] + (size_t)(sc & 0xff) * a.src_cstride[k] + start;
@@ -34,7 +36,7 @@ template <typename T, int NSET> __global__ __launch_bounds__(256) void k_assembl
         for (int k = 0; k < MSHGNN_MAX_TYPES; ++k) if (t == k) { nodes = a.nodes[k]; pitch = a.x_pitch[k]; }
         v_lo[set] = (int)((uintptr_t)sp & 0xffffffffu); v_hi[set] = (int)((uintptr_t)sp >> 32);
         v_doff[set] = (int)(((size_t)b * nodes + node) * pitch + f0 - (size_t)b * nodes * pitch);     // offset inside the window's block of this type
-        v_len[set] = run[4]; v_t[set] = t;
+        v_len[set] = run[4] | (neg ? WIN_SIGN_FLAG : 0); v_t[set] = t;      // (lengths are <= 256: the run's sign rides in bit 30)
     }
     auto rl = [&](const int (&v)[NSET], int r) {
         if constexpr (NSET == 1) return __builtin_amdgcn_readlane(v[0], r);
@@ -50,7 +52,7 @@ template <typename T, int NSET> __global__ __launch_bounds__(256) void k_assembl
             for (int i = 0; i < WIN_ROW_RUNS; ++i) {
                 const int r = min(rb + i, r_end - 1);
                 const float* sp = reinterpret_cast<const float*>((uintptr_t)(unsigned)rl(v_lo, r) | ((uintptr_t)(unsigned)rl(v_hi, r) << 32));
-                const int len = rl(v_len, r);
+                const int len = rl(v_len, r) & ~WIN_SIGN_FLAG;
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const int k = 2 * lane + 128 * (q >> 1) + (q & 1);
@@ -62,9 +64,13 @@ template <typename T, int NSET> __global__ __launch_bounds__(256) void k_assembl
             for (int i = 0; i < WIN_ROW_RUNS; ++i) {
                 if (rb + i >= r_end) break;
                 const int r = rb + i;
-                const int t = rl(v_t, r), len = rl(v_len, r), doff = rl(v_doff, r);
+                const int lw = rl(v_len, r), t = rl(v_t, r), len = lw & ~WIN_SIGN_FLAG, doff = rl(v_doff, r);
                 const bool has_src = (rl(v_lo, r) | rl(v_hi, r)) != 0;
                 T* dst = reinterpret_cast<T*>(a.x[t]) + (size_t)b * a.nodes[t] * a.x_pitch[t] + doff;
+                if (lw & WIN_SIGN_FLAG) {      // a negated run: the sign goes on before the statistics (uniform)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) v[i][q] = xor_sign(v[i][q], true);
+                }
                 if (a.normalize && has_src) {
                     // (x - mean) / std with the unbiased estimator, NaN -> 0 (flexibleDataset.py:390-396); fp64, two passes over registers.  The arithmetic
                     // is run_stats / standardise_one (mshgnn_device.hpp), shared with the standardising series encoders of mshgnn_forward_series
@@ -106,11 +112,12 @@ template <typename T> __global__ __launch_bounds__(256) void k_assemble_windows_
     const int tid = threadIdx.x;
     const int64_t b = blockIdx.x, start = a.starts[b];
     if (tid < a.n_runs) {
-        const int sc = a.runs[(size_t)tid * 5 + 3];
+        bool neg;
+        const int sc = run_source(a.runs[(size_t)tid * 5 + 3], a.sign, neg);
         const float* sp = nullptr;
 #pragma unroll
         for (int k = 0; k < WIN_MAX_SRC; ++k) if (sc >= 0 && (sc >> 8) == k) sp = a.src[k] + (size_t)(sc & 0xff) * a.src_cstride[k] + start;
-        s_src[tid] = (unsigned long long)sp;
+        s_src[tid] = (unsigned long long)sp | (neg && sp ? RUN_PTR_SIGN : 0ull);      // (a chunk's elements may come from two runs of opposite signs: per element)
     }
     if (tid < a.n_rows) {
         const int r0 = a.rows[2 * tid], r1 = a.rows[2 * tid + 1];
@@ -141,8 +148,9 @@ template <typename T> __global__ __launch_bounds__(256) void k_assemble_windows_
         for (int e = 0; e < EPC; ++e) {
             v[e] = 0.f;
             if (k0 + e < width) {
-                const float* sp = reinterpret_cast<const float*>(s_src[run]);
-                v[e] = sp ? sp[off] : 1.0f;
+                const unsigned long long p = s_src[run];
+                const float* sp = reinterpret_cast<const float*>(run_ptr_addr(p));
+                v[e] = sp ? xor_sign(sp[off], (p & RUN_PTR_SIGN) != 0) : 1.0f;
             }
             if (++off == len) { off = 0; ++run; }
         }
@@ -165,13 +173,38 @@ __device__ __forceinline__ LabelArgs label_args_of(const WindowArgs& a, int32_t*
     l.lab = a.src[a.label_src]; l.lab_cs = a.src_cstride[a.label_src];
     l.quat_src = a.quat_src >= 0 ? a.src[a.quat_src] : nullptr; l.quat_cs = a.quat_src >= 0 ? a.src_cstride[a.quat_src] : 0;
     l.starts = a.starts; l.B = a.B; l.T = a.T; l.label_cols = a.label_cols; l.n_label = a.n_label; l.label_rotate = a.label_rotate;
-    l.y = a.y; l.quat = a.quat; l.labels_int = labels_int;
+    l.y = a.y; l.quat = a.quat; l.labels_int = labels_int; l.sign = a.sign;
     return l;
 }
 
 __global__ void k_window_labels(WindowArgs a) {
     const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (b < a.B) window_labels_one(label_args_of(a, nullptr), b);
+}
+
+// The sign tables of a descriptor (sign_flags bit 0) are the caller's statement about DEVICE memory; before the first launch that reads them they are copied back
+// once and checked, afterwards the caller vouches (bit 1).  What is refused: see MSHGNN_WINDOW_SIGN_FLAG in include/mshgnn.h.
+int check_sign_tables(const mshgnn_window_desc* d, bool labels, hipStream_t st) {
+    if (!(d->sign_flags & 1) || (d->sign_flags & 2)) return MSHGNN_OK;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (st && hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+        return set_err(MSHGNN_EINVAL, "sign tables must be checked by a call outside a stream capture first (then vouch with sign_flags bit 1)");
+    if (d->n_runs < 1 || d->n_runs > WIN_MAX_RUNS || !d->runs) return set_err(MSHGNN_EINVAL, "bad window descriptor");
+    std::vector<int32_t> runs((size_t)d->n_runs * 5), lab(labels && d->n_label > 0 ? (size_t)d->n_label : 0);
+    HIPCHK(hipMemcpy(runs.data(), d->runs, runs.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (!lab.empty()) {
+        if (!d->label_cols) return set_err(MSHGNN_EINVAL, "bad label description");
+        HIPCHK(hipMemcpy(lab.data(), d->label_cols, lab.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+    for (int r = 0; r < d->n_runs; ++r) {
+        const int32_t w = runs[(size_t)r * 5 + 3];
+        if (w == -1) continue;
+        if (w < 0) return set_err(MSHGNN_EINVAL, "window run " + std::to_string(r) + ": a constant-1 run (source word -1) cannot carry a sign");
+        if (((w & ~MSHGNN_WINDOW_SIGN_FLAG) >> 8) >= d->n_src) return set_err(MSHGNN_EINVAL, "window run " + std::to_string(r) + ": source out of range");
+    }
+    for (size_t k = 0; k < lab.size(); ++k)
+        if (lab[k] < 0 || (lab[k] & ~MSHGNN_WINDOW_SIGN_FLAG) >= 256) return set_err(MSHGNN_EINVAL, "label column " + std::to_string(k) + ": column part out of range [0, 256)");
+    return MSHGNN_OK;
 }
 
 extern "C" int mshgnn_assemble_windows(const mshgnn_window_desc* d, const float* const* src, const int64_t* src_cstride, const int64_t* src_rows,
@@ -197,8 +230,9 @@ extern "C" int mshgnn_assemble_windows(const mshgnn_window_desc* d, const float*
     if (d->history > 256) return set_err(MSHGNN_EUNSUPPORTED, "history longer than 256 steps is not supported by this build");
     a.runs = d->runs; a.n_runs = d->n_runs; a.rows = d->rows; a.n_rows = d->n_rows; a.starts = starts; a.B = batch; a.T = d->history; a.normalize = d->normalize;
     a.label_cols = d->label_cols; a.n_label = d->n_label; a.label_src = d->label_src; a.label_rotate = d->label_rotate; a.quat_src = d->quat_src;
-    a.y = y_out; a.quat = quat_out;
+    a.y = y_out; a.quat = quat_out; a.sign = d->sign_flags & 1;
     hipStream_t st = (hipStream_t)stream;
+    if (const int rc = check_sign_tables(d, d->n_label > 0, st)) return rc;
     if (d->n_runs > 128) return set_err(MSHGNN_EUNSUPPORTED, "more than 128 feature runs per window are not supported by this build");
     // fast path: no standardisation, every row's runs of one length starting at the row's first feature 0, 16-byte aligned rows whose pitch covers whole chunks
     const bool f32 = d->dtype == MSHGNN_F32 || d->dtype == MSHGNN_BF16X3;      // the split plan takes fp32 inputs

@@ -81,8 +81,11 @@ __global__ void k_prep_x3(PrepArgs a) { prep_one_x3(a, blockIdx.x * blockDim.x +
 // NORM (with SERIES; mshgnn_forward_series / mshgnn_step_*_series_std on a standardised recipe): every run with a source column is standardised over its window with the statistics
 // k_series_stats left in ser.stats (standardise_one, mshgnn_device.hpp: the arithmetic of mshgnn_assemble_windows(normalize)).  Evaluation materialises nothing
 // (a.x null); the training steps (mshgnn_step_*_series_std) get the standardised fp32 rows written to a.x like the plain SERIES rows.
-template <bool ALIGNED, bool SERIES = false, int SRC = 0, bool NORM = false> __global__ __launch_bounds__(256) void k_enc_x3(EncArgs a, int n_img, SeriesSrc ser, WideSrc wsrc) {
+// SIGN (with SERIES; a descriptor with sign_flags): as k_enc_fwd's -- the chunk's fp32 elements are negated per element before the standardisation and before the
+// window rows are written out; unsigned descriptors launch the instantiations without it.
+template <bool ALIGNED, bool SERIES = false, int SRC = 0, bool NORM = false, bool SIGN = false> __global__ __launch_bounds__(256) void k_enc_x3(EncArgs a, int n_img, SeriesSrc ser, WideSrc wsrc) {
     static_assert(!NORM || SERIES, "standardisation is part of the series gather");
+    static_assert(!SIGN || SERIES, "signs are part of the series gather");
     static_assert(!SERIES || ALIGNED, "the series gather writes aligned window buffers");
     static_assert(SRC == 0 || (ALIGNED && !SERIES), "wide source rows: aligned destination rows, no series gather");
     using P = P16;
@@ -130,6 +133,7 @@ template <bool ALIGNED, bool SERIES = false, int SRC = 0, bool NORM = false> __g
     // NORM: the statistics of the chunk's two runs per window, and how the chunk divides between them (set by fetch, read by the next staging pass)
     RunStats rsa[NORM ? MB : 1], rsb[NORM ? MB : 1];
     int n_n0 = 8; bool n_has_a = false, n_has_b = false;
+    int g_n0 = 8; bool g_fa = false, g_fb = false;      // SIGN: how the fetched chunk divides between its two runs and their sign flags
     if constexpr (SERIES) {
 #pragma unroll
         for (int m = 0; m < MB; ++m) srow[m] = (int)ser.starts[min(w0 + m * P::ROWS + r0, a.B - 1)];
@@ -142,7 +146,11 @@ template <bool ALIGNED, bool SERIES = false, int SRC = 0, bool NORM = false> __g
             // elements [k0, k0 + 8) of the row: n0 of them from run j at time offset off, the rest from run j + 1 at offset 0
             const int j = k0 / ser.T, off = k0 - j * ser.T, n0 = min(8, ser.T - off);
             const bool second = min(nv, 8) > n0;
-            const unsigned long long pa = nv > 0 ? ser.run_ptr[rfirst + j] : 0ull, pb = second ? ser.run_ptr[rfirst + j + 1] : 0ull;
+            unsigned long long pa = nv > 0 ? ser.run_ptr[rfirst + j] : 0ull, pb = second ? ser.run_ptr[rfirst + j + 1] : 0ull;
+            if constexpr (SIGN) {
+                g_n0 = n0; g_fa = (pa & RUN_PTR_SIGN) != 0; g_fb = (pb & RUN_PTR_SIGN) != 0;
+                pa = run_ptr_addr(pa); pb = run_ptr_addr(pb);
+            }
             const u32x4 ones = u32x4{0x3f800000u, 0x3f800000u, 0x3f800000u, 0x3f800000u};      // the constant-1 run
             if constexpr (NORM) { n_n0 = n0; n_has_a = pa != 0ull; n_has_b = pb != 0ull; }
 #pragma unroll
@@ -202,6 +210,8 @@ template <bool ALIGNED, bool SERIES = false, int SRC = 0, bool NORM = false> __g
     for (int kc = 0; kc < nkc; ++kc) {
         const u32x4 sxa = sign_xor<float>(sg + kc * H + c * 8), sxb = sign_xor<float>(sg + kc * H + c * 8 + 4);   // apply_symmetry: +-1 mask as a sign-bit XOR
         const int nv = F - (kc * H + c * 8);
+        u32x4 gm0 = u32x4{0, 0, 0, 0}, gm1 = gm0;      // SIGN: the chunk's per-element sign masks
+        if constexpr (SIGN) sign_mask8_f32(g_n0, g_fa, g_fb, gm0, gm1);
         __syncthreads();   // previous chunk's MFMAs are done reading LDS
 #pragma unroll
         for (int m = 0; m < MB; ++m) {
@@ -212,6 +222,7 @@ template <bool ALIGNED, bool SERIES = false, int SRC = 0, bool NORM = false> __g
                 fa = __builtin_bit_cast(u32x4, lo4); fb = __builtin_bit_cast(u32x4, hi4);
             } else
             {
+                if constexpr (SIGN) { fa ^= gm0; fb ^= gm1; }
                 if constexpr (NORM) standardise_oct(fa, fb, n_n0, n_has_a, n_has_b, rsa[m], rsb[m]);
                 if (kc + 1 == nkc) { fa = chunk_keep_first<float>(fa, nv); fb = chunk_keep_first<float>(fb, nv - 4); }     // only the last K chunk has pad columns
             }
@@ -656,7 +667,9 @@ int x3_forward(const mshgnn_plan* p, StepCall& c) {
         if ((rc = pick_enc_route(c, a, tr, enc_grid, route))) return rc;
         unsigned enc_lds = tr.enc_lds;
         auto enc = [&](auto kernel, const SeriesSrc& ser, const WideSrc& wsrc) { hipLaunchKernelGGL(kernel, dim3(enc_grid), dim3(256), enc_lds, st, a, hp.n_img, ser, wsrc); };
-        if (route == EncRoute::SERIES_STD) enc(k_enc_x3<true, true, 0, true>, *c.series, WideSrc{});
+        if (route == EncRoute::SERIES_STD && c.series->sign) enc(k_enc_x3<true, true, 0, true, true>, *c.series, WideSrc{});
+        else if (route == EncRoute::SERIES && c.series->sign) enc(k_enc_x3<true, true, 0, false, true>, *c.series, WideSrc{});
+        else if (route == EncRoute::SERIES_STD) enc(k_enc_x3<true, true, 0, true>, *c.series, WideSrc{});
         else if (route == EncRoute::SERIES) enc(k_enc_x3<true, true>, *c.series, WideSrc{});
         else if (route == EncRoute::WIDE8) enc(k_enc_x3<true, false, 8>, SeriesSrc{}, *c.wide);
         else if (route == EncRoute::WIDE4) enc(k_enc_x3<true, false, 4>, SeriesSrc{}, *c.wide);

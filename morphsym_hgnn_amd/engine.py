@@ -63,7 +63,7 @@ class MshgnnWindowDesc(C.Structure):
         ("type_nodes", C.c_int32 * 4), ("type_width", C.c_int32 * 4),
         ("n_src", C.c_int32), ("n_runs", C.c_int32), ("n_rows", C.c_int32), ("fast_layout", C.c_int32), ("runs", C.c_void_p), ("rows", C.c_void_p),
         ("n_label", C.c_int32), ("label_src", C.c_int32), ("label_rotate", C.c_int32), ("quat_src", C.c_int32),
-        ("label_cols", C.c_void_p), ("run_ptrs_ready", C.c_int32), ("reserved_", C.c_int32),
+        ("label_cols", C.c_void_p), ("run_ptrs_ready", C.c_int32), ("sign_flags", C.c_int32),
     ]
 
 
@@ -748,6 +748,7 @@ class Engine:
             _check(self.lib, getattr(self.lib, name)(self._plan, C.byref(store.desc), store._src, src16, store._pitch, store._rows, starts.data_ptr(), B,
                                                      xp, pitch, y.data_ptr(), by_product.data_ptr() if by_product is not None else None, run_ptrs.data_ptr(), *extra,
                                                      params_flat.data_ptr(), out.data_ptr(), loss.data_ptr(), grad_flat.data_ptr(), ws.data_ptr(), stream), name)
+        self._vouch_sign_tables(store)
         return xs, (labels if ce else y), out, loss, grad_flat
 
     @staticmethod
@@ -758,6 +759,13 @@ class Engine:
         key = (bool(fp32_gather), stream, tuple(a.data_ptr() for a in store.series))
         store.desc.run_ptrs_ready = 1 if getattr(store, "_run_ptrs_key", None) == key else 0
         store._run_ptrs_key = key
+
+    @staticmethod
+    def _vouch_sign_tables(store):
+        """A descriptor whose tables carry sign flags (a `transformed` store; mshgnn_window_desc.sign_flags bit 0) has them read back and checked by the
+        library on its first call; the call succeeded, so later calls vouch for them (bit 1: no read-back, capturable)."""
+        if store.desc.sign_flags == 1:
+            store.desc.sign_flags = 3
 
     def forward_series(self, store, starts: torch.Tensor, params_flat: torch.Tensor, out: Optional[torch.Tensor] = None, labels: bool = True):
         """Evaluation straight from a `windows.SequenceStore` (mshgnn_forward_series): `store.assemble(starts)` + `forward(..., training=False)` in one
@@ -788,6 +796,7 @@ class Engine:
                                                             li.data_ptr() if li is not None else None, run_ptrs.data_ptr(),
                                                             stats.data_ptr() if stats is not None else None, params_flat.data_ptr(), out.data_ptr(),
                                                             ws.data_ptr(), stream), "mshgnn_forward_series")
+        self._vouch_sign_tables(store)
         return y, q, li, out
 
     def step_mse_phase(self, phase: int, xs: Sequence[torch.Tensor], params_flat: torch.Tensor, y: torch.Tensor, B: int, out: torch.Tensor,

@@ -13,6 +13,7 @@ A `WindowRecipe` says, per node type, which columns of which raw series become t
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -36,6 +37,60 @@ class WindowRecipe:
     label_rotate: bool = False                              # 3-D world-frame labels -> body frame (needs quat_series)
     quat_series: Optional[str] = None
     normalize: bool = False                                 # per-window standardisation (flexibleDataset.py:390-396)
+    # group-transformed windows (`transformed`): which part of the morphological symmetry group acts on a series' columns, and the +-1 a run / a label carries
+    symmetry_parts: Optional[Dict[str, str]] = None         # series name -> "js" | "fs" | "bs_lin" | "bs_ang" | "ls"
+    variable_signs: Optional[Dict[str, List[List[List[int]]]]] = None      # per type: [variable][node][axis] of +-1, mirroring `variables` (None: all +1)
+    label_signs: Optional[List[int]] = None                 # [n_label] of +-1 (None: all +1)
+
+    def transformed(self, operator: str, group: "GroupAction", mode: str = "MorphSym") -> "WindowRecipe":
+        """The recipe of g . window for g = operator in ("gs", "gt", "gr"): what the reference's dataset classes build with `symmetry_operator`
+        (quadSDKDataset_Morph.py:113-159, 177-239; LinTzuYaunDataset_Morph.py:294-333, 349-408) -- every sorted part X [T, n] becomes
+        X'[:, k] = c[k] X[:, P[k]] over its flat index k = node * n_axes + axis, BEFORE standardisation; labels likewise, AFTER the body-frame
+        rotation; the quaternion by-product is left alone.  The permutation is a choice of columns, the reflection a sign per run / label
+        (`variable_signs`, `label_signs`), so the transformed windows come out of the same resident series.  Composes: the result can be
+        transformed again."""
+        perm_of = {}
+        def table(part, n, what):
+            if part not in perm_of:
+                perm_of[part] = group.table(part, operator, mode)
+            P, c = perm_of[part]
+            if len(P) != n:
+                raise ValueError(f"{what}: {n} columns, but the group's '{part}' tables have {len(P)}")
+            return P, c
+        if operator not in GroupAction.OPERATORS:
+            raise ValueError(f"unknown symmetry operator {operator!r}: one of {GroupAction.OPERATORS}")
+        if mode not in GroupAction.MODES:
+            raise ValueError(f"unknown symmetry mode {mode!r}: one of {GroupAction.MODES}")
+        if self.symmetry_parts is None:
+            raise ValueError("this recipe does not say which part of the group acts on its series (symmetry_parts is None); the Solo-12 recipes are out of "
+                             "scope: the reference's own loader hands apply_symmetry a Python list there (soloDataset.py:619-623, 722-739)")
+        variables, signs = {}, {}
+        for t in self.node_types:
+            variables[t], signs[t] = [], []
+            old_signs = (self.variable_signs or {}).get(t)
+            for vi, (s, cols) in enumerate(self.variables.get(t, [])):
+                if s not in self.symmetry_parts:
+                    raise ValueError(f"series '{s}' has no entry in symmetry_parts")
+                na = len(cols[0])
+                flat = [c for node in cols for c in node]
+                fsig = [x for node in old_signs[vi] for x in node] if old_signs else [1] * len(flat)
+                P, c = table(self.symmetry_parts[s], len(flat), f"variable '{s}' of type '{t}'")
+                nflat = [flat[P[k]] for k in range(len(flat))]
+                nsig = [int(c[k]) * int(fsig[P[k]]) for k in range(len(flat))]
+                variables[t].append((s, [nflat[i:i + na] for i in range(0, len(nflat), na)]))
+                signs[t].append([nsig[i:i + na] for i in range(0, len(nsig), na)])
+        label_cols, label_signs = list(self.label_cols), self.label_signs
+        if self.label_cols:
+            if self.label_series not in self.symmetry_parts:
+                raise ValueError(f"label series '{self.label_series}' has no entry in symmetry_parts")
+            P, c = table(self.symmetry_parts[self.label_series], len(self.label_cols), f"labels '{self.label_series}'")
+            if self.label_rotate and any(P[3 * j + i] != P[3 * j] + i or P[3 * j] % 3 for j in range(len(P) // 3) for i in range(3)):
+                # the rotation acts on whole (x, y, z) triples of one foot BEFORE the transform: the permuted columns must still be such triples
+                raise ValueError("label_rotate: the label permutation must map foot triples to foot triples in axis order")
+            old = self.label_signs or [1] * len(self.label_cols)
+            label_cols = [self.label_cols[P[k]] for k in range(len(P))]
+            label_signs = [int(c[k]) * int(old[P[k]]) for k in range(len(P))]
+        return dataclasses.replace(self, variables=variables, variable_signs=signs, label_cols=label_cols, label_signs=label_signs)
 
     def width(self, t: str) -> int:
         w = sum(len(cols[0]) * self.history for _, cols in self.variables.get(t, []))
@@ -51,6 +106,61 @@ class WindowRecipe:
             if s is not None and s not in names:
                 names.append(s)
         return names
+
+
+@dataclass
+class GroupAction:
+    """The tables of a morphological symmetry group file (morphsym_hgnn_amd/cfg/*.yaml): per part an index permutation (`permutation_Q_*`) and a +-1
+    reflection (`reflection_Q_*`), row 0 = sagittal (gs), row 1 = transversal (gt).  The base has one permutation and two reflections (linear /
+    angular series)."""
+    permutation: Dict[str, List[List[int]]]      # "js" | "fs" | "bs" | "ls" -> [2][n]
+    reflection: Dict[str, List[List[int]]]       # "js" | "fs" | "bs_lin" | "bs_ang" | "ls" -> [2][n]
+    name: str = ""
+
+    OPERATORS = ("gs", "gt", "gr")
+    MODES = ("MorphSym", "Euclidean")
+    PARTS = {"js": "js", "fs": "fs", "bs_lin": "bs", "bs_ang": "bs", "ls": "ls"}      # reflection key -> permutation key
+
+    @classmethod
+    def load(cls, name_or_path: str) -> "GroupAction":
+        """A path, or the stem of a file in the package's cfg/ ("a1-c2", "mini_cheetah-k4")."""
+        import yaml
+        path = name_or_path
+        if not os.path.isfile(path):
+            path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "cfg", f"{name_or_path}.yaml")
+        if not os.path.isfile(path):
+            raise ValueError(f"no group file '{name_or_path}' (a path, or the stem of a file in cfg/)")
+        with open(path) as f:
+            d = yaml.safe_load(f)
+        # (a robot without some part -- the Solo files have no foot tables -- simply lacks those keys: `table` says so when asked for them)
+        perm = {k: [[int(x) for x in row] for row in d[f"permutation_Q_{k}"]] for k in ("js", "fs", "bs", "ls") if f"permutation_Q_{k}" in d}
+        refl = {k: [[int(x) for x in row] for row in d[f"reflection_Q_{k}"]] for k, pk in cls.PARTS.items() if f"reflection_Q_{k}" in d and pk in perm}
+        for k in refl:
+            pk = cls.PARTS[k]
+            for row_p, row_c in zip(perm[pk], refl[k]):
+                if sorted(row_p) != list(range(len(row_p))) or len(row_c) != len(row_p) or any(x not in (-1, 1) for x in row_c):
+                    raise ValueError(f"group file '{name_or_path}': '{k}' is no permutation with +-1 reflections")
+        return cls(perm, refl, os.path.splitext(os.path.basename(path))[0])
+
+    def table(self, part: str, operator: str, mode: str = "MorphSym") -> Tuple[List[int], List[int]]:
+        """(P, c) with X'[k] = c[k] X[P[k]]: gs -> (P0, c_gs), gt -> (P1, c_gt), gr -> (P0[P1[k]], c_gs c_gt); mode "Euclidean": c is all ones
+        (the reference's create_coefficient_dict)."""
+        if part not in self.PARTS:
+            raise ValueError(f"unknown group part {part!r}: one of {tuple(self.PARTS)}")
+        if operator not in self.OPERATORS:
+            raise ValueError(f"unknown symmetry operator {operator!r}: one of {self.OPERATORS}")
+        if mode not in self.MODES:
+            raise ValueError(f"unknown symmetry mode {mode!r}: one of {self.MODES}")
+        if part not in self.reflection:
+            raise ValueError(f"group '{self.name}' has no '{part}' tables")
+        (P0, P1), (c0, c1) = self.permutation[self.PARTS[part]], self.reflection[part]
+        if operator == "gs":
+            P, c = list(P0), list(c0)
+        elif operator == "gt":
+            P, c = list(P1), list(c1)
+        else:
+            P, c = [P0[P1[k]] for k in range(len(P0))], [c0[k] * c1[k] for k in range(len(c0))]
+        return P, (c if mode == "MorphSym" else [1] * len(c))
 
 
 def quadsdk_a1_c2_recipe(joint_perm: Sequence[int], foot_perm: Sequence[int], history: int = 150, grf_dimension: int = 3,
@@ -71,7 +181,9 @@ def quadsdk_a1_c2_recipe(joint_perm: Sequence[int], foot_perm: Sequence[int], hi
         history=history,
         variables={"base": [("imu_acc", [[0, 1, 2]] * n_base), ("imu_omega", [[0, 1, 2]] * n_base)],
                    "joint": [(s, [[int(j)] for j in joint_perm]) for s in ("q", "qd", "tau")], "foot": []},
-        label_series="F", label_cols=lab, label_rotate=body_frame_labels, quat_series="r_o", normalize=normalize)
+        label_series="F", label_cols=lab, label_rotate=body_frame_labels, quat_series="r_o", normalize=normalize,
+        # (3-D GRFs transform like foot vectors, 1-D ones like labels: apply_symmetry(part='label'), quadSDKDataset_Morph.py:204-211)
+        symmetry_parts={"imu_acc": "bs_lin", "imu_omega": "bs_ang", "q": "js", "qd": "js", "tau": "js", "F": "fs" if grf_dimension == 3 else "ls"})
 
 
 def minicheetah_k4_recipe(joint_perm: Sequence[int], foot_perm: Sequence[int], history: int = 150, normalize: bool = False,
@@ -85,7 +197,8 @@ def minicheetah_k4_recipe(joint_perm: Sequence[int], foot_perm: Sequence[int], h
         variables={"base": [("imu_acc", [[0, 1, 2]] * n_base), ("imu_omega", [[0, 1, 2]] * n_base)],
                    "joint": [(s, [[int(j)] for j in joint_perm]) for s in ("q", "qd")],
                    "foot": [("p", fcols), ("v", fcols)]},
-        label_series="contacts", label_cols=[int(i) for i in foot_perm], normalize=normalize)
+        label_series="contacts", label_cols=[int(i) for i in foot_perm], normalize=normalize,
+        symmetry_parts={"imu_acc": "bs_lin", "imu_omega": "bs_ang", "q": "js", "qd": "js", "p": "fs", "v": "fs", "contacts": "ls"})
 
 
 def solo_com_recipe(kind: str, joint_perm: Sequence[int], history: int = 1) -> WindowRecipe:
@@ -116,13 +229,12 @@ class SequenceStore:
             raise RuntimeError("window assembly runs on a HIP device; there is no CPU fallback")
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.lib = eng.load_library()
-        self.recipe = recipe
         self.dtype = dtype
         self.torch_dtype = torch.bfloat16 if dtype == "bf16" else torch.float32      # the split plan ("x3") takes fp32 inputs
         self.names = recipe.series()
         self.series = []
         n_rows = None
-        self.series16 = []       # bf16 copies for the fused gather of Engine.step_mse_series (made on first use)
+        self._shared16 = {"series": [], "src": None}      # bf16 copies for the fused gather of Engine.step_mse_series (made on first use; shared with `transformed` siblings)
         for s in self.names:
             a = torch.as_tensor(np.asarray(arrays[s])).to(self.device, torch.float32)
             a = a.reshape(a.shape[0], -1).t()                       # column-major: one window of one column is contiguous
@@ -133,48 +245,96 @@ class SequenceStore:
         self.n_rows = int(n_rows)
         if self.n_rows < recipe.history:
             raise ValueError("sequence shorter than one window")
+        self._src = (C.c_void_p * len(self.series))(*[a.data_ptr() for a in self.series])
+        self._pitch = (C.c_int64 * len(self.series))(*[a.shape[1] for a in self.series])     # column stride (rows + slack)
+        self._rows = (C.c_int64 * len(self.series))(*[a.shape[1] - 8 for a in self.series])
+        self._fast = bool(fast)
+        self._describe(recipe)
+
+    SIGN_FLAG = 1 << 30      # MSHGNN_WINDOW_SIGN_FLAG: a run's source word / a label column carries a minus sign
+
+    def _describe(self, recipe: WindowRecipe) -> None:
+        """The device tables, the descriptor and the per-store caches of `recipe` over the series already resident (the constructor; `transformed`)."""
+        self.recipe = recipe
         sidx = {s: i for i, s in enumerate(self.names)}
         runs, rows = [], []
+        signed = False
         for ti, t in enumerate(recipe.node_types):
             vars_ = recipe.variables.get(t, [])
             if not vars_:
                 for n in range(recipe.num_nodes[t]):
                     rows.append([len(runs), len(runs) + 1]); runs.append([ti, n, 0, -1, 1])
                 continue
+            vsig = (recipe.variable_signs or {}).get(t)
             for n in range(recipe.num_nodes[t]):
                 f = 0
                 r_begin = len(runs)
-                for s, cols in vars_:
+                for vi, (s, cols) in enumerate(vars_):
                     ncol = self.series[sidx[s]].shape[0]
-                    for c in cols[n]:
+                    for ai, c in enumerate(cols[n]):
                         if not 0 <= c < min(ncol, 256):
                             raise ValueError(f"column {c} of series '{s}' out of range")
-                        runs.append([ti, n, f, (sidx[s] << 8) | c, recipe.history])
+                        sg = int(vsig[vi][n][ai]) if vsig else 1
+                        if sg not in (-1, 1):
+                            raise ValueError(f"variable_signs of series '{s}': {sg} is not +-1")
+                        signed |= sg < 0
+                        runs.append([ti, n, f, (sidx[s] << 8) | c | (self.SIGN_FLAG if sg < 0 else 0), recipe.history])
                         f += recipe.history
                 rows.append([r_begin, len(runs)])
+        lab = list(recipe.label_cols or [0])
+        if recipe.label_cols:
+            ncol = self.series[sidx[recipe.label_series]].shape[0]
+            for c in lab:
+                if not 0 <= c < min(ncol, 256):
+                    raise ValueError(f"label column {c} of series '{recipe.label_series}' out of range")
+        if recipe.label_signs is not None and recipe.label_cols:
+            if len(recipe.label_signs) != len(recipe.label_cols) or any(int(x) not in (-1, 1) for x in recipe.label_signs):
+                raise ValueError("label_signs: one +-1 per label column")
+            signed |= any(int(x) < 0 for x in recipe.label_signs)
+            lab = [c | (self.SIGN_FLAG if int(x) < 0 else 0) for c, x in zip(lab, recipe.label_signs)]
         self.runs = torch.tensor(runs, dtype=torch.int32, device=self.device)
         self.rows = torch.tensor(rows, dtype=torch.int32, device=self.device)
-        self.label_cols = torch.tensor(recipe.label_cols or [0], dtype=torch.int32, device=self.device)
+        self.label_cols = torch.tensor(lab, dtype=torch.int32, device=self.device)
         d = eng.MshgnnWindowDesc()
-        d.n_types = len(recipe.node_types); d.dtype = {"f32": 0, "bf16": 1, "x3": 2}[dtype]; d.history = recipe.history
+        d.n_types = len(recipe.node_types); d.dtype = {"f32": 0, "bf16": 1, "x3": 2}[self.dtype]; d.history = recipe.history
         d.normalize = int(recipe.normalize)
         for i, t in enumerate(recipe.node_types):
             d.type_nodes[i] = recipe.num_nodes[t]; d.type_width[i] = recipe.width(t)
         d.n_src = len(self.series); d.n_runs = len(runs); d.runs = self.runs.data_ptr()
-        d.fast_layout = int(fast)      # every row's runs are `history` long (or the single constant-1 run) and follow each other from feature 0
+        d.fast_layout = int(self._fast)  # every row's runs are `history` long (or the single constant-1 run) and follow each other from feature 0
                                        # (fast=False: the general run-by-run gather kernel, kept for descriptors that do not promise this)
         d.n_rows = len(rows); d.rows = self.rows.data_ptr()
         d.n_label = len(recipe.label_cols); d.label_src = sidx[recipe.label_series] if recipe.label_series else 0
         d.label_rotate = int(recipe.label_rotate); d.quat_src = sidx[recipe.quat_series] if recipe.quat_series else -1
         d.label_cols = self.label_cols.data_ptr()
+        d.sign_flags = 1 if signed else 0      # the tables carry sign flags (checked by the library on the first call, vouched for afterwards: bit 1)
         self.desc = d
         self._cache = {}
-        self._src = (C.c_void_p * len(self.series))(*[a.data_ptr() for a in self.series])
-        self._pitch = (C.c_int64 * len(self.series))(*[a.shape[1] for a in self.series])     # column stride (rows + slack)
-        self._rows = (C.c_int64 * len(self.series))(*[a.shape[1] - 8 for a in self.series])
-        self._src16 = None; self._run_ptrs = None
+        self._run_ptrs = None
         self._eval_cache = {}
         self._stats_cache = {}
+        if hasattr(self, "_run_ptrs_key"):
+            del self._run_ptrs_key
+
+    @property
+    def series16(self):
+        return self._shared16["series"]
+
+    @property
+    def _src16(self):
+        return self._shared16["src"]
+
+    def transformed(self, operator: str, group: GroupAction, mode: str = "MorphSym") -> "SequenceStore":
+        """A sibling store of g . window (`WindowRecipe.transformed`) over THE SAME resident series: it shares the series tensors, their bf16 copies
+        included, and owns only its runs, label tables, descriptor and caches -- no second copy of the data.  Every route that takes a store takes it."""
+        recipe = self.recipe.transformed(operator, group, mode)
+        # SHARED with the parent (by reference): device, lib, dtype, names, series, _shared16 (the bf16 copies), n_rows, _src / _pitch / _rows, _fast and a
+        # ResidentDataset's seq_* lists.  OWNED by the sibling, all (re)made by _describe: recipe, runs, rows, label_cols, desc, _cache, _run_ptrs,
+        # _run_ptrs_key, _eval_cache, _stats_cache.  A per-store attribute that depends on the recipe or is created lazily belongs in _describe.
+        sib = object.__new__(type(self))
+        sib.__dict__.update(self.__dict__)
+        sib._describe(recipe)
+        return sib
 
     def __len__(self) -> int:
         """Number of windows (the reference's dataset length: rows - history + 1)."""
@@ -231,6 +391,8 @@ class SequenceStore:
         rc = self.lib.mshgnn_assemble_windows(C.byref(self.desc), self._src, self._pitch, self._rows, st.data_ptr(), B, xp, pitch,
                                               y.data_ptr() if y is not None else None, q.data_ptr() if q is not None else None, stream)
         eng._check(self.lib, rc, "mshgnn_assemble_windows")
+        if self.desc.sign_flags == 1:
+            self.desc.sign_flags = 3      # the library has checked these tables: later calls vouch for them (no table read-back per call)
         return xs, y, q
 
     def batch(self, starts, edge_index_dict) -> "WindowBatch":
@@ -260,8 +422,8 @@ class SequenceStore:
         if self._run_ptrs is None:
             self._run_ptrs = torch.zeros(max(1, int(self.desc.n_runs)), dtype=torch.int64, device=self.device)
         if bf16 and self._src16 is None:
-            self.series16 = [a.to(torch.bfloat16) for a in self.series]
-            self._src16 = (C.c_void_p * len(self.series16))(*[a.data_ptr() for a in self.series16])
+            self._shared16["series"] = [a.to(torch.bfloat16) for a in self.series]
+            self._shared16["src"] = (C.c_void_p * len(self.series16))(*[a.data_ptr() for a in self.series16])
         return (self._src16 if bf16 else None), self._run_ptrs
 
 
