@@ -12,13 +12,14 @@
 //     engine on the transposed graph with transposed weight images; weight gradients are one split-K MFMA launch
 //     over all layers with deterministic slab reduction (no float atomics).
 //
-// This file, top to bottom: (1) the kernels of the fp32 / bf16 plans -- prep, encoder, per-layer, 8-wave stack, the slab interpreters (the slab templates
+// This file, top to bottom: (1) the kernels of the fp32 / bf16 plans -- prep, per-layer (the encoder: mshgnn_enc.hpp), 8-wave stack, the slab interpreters (the slab templates
 // themselves: mshgnn_slab.hpp), decoder, weight gradient, finalize; (2) kernel selection; (3) plan lifecycle; (4) forward_impl / backward_impl; (5) the dispatch
 // over plans and chunks; (6) the entry points, the series routes last.  Elsewhere: the split plan (mshgnn_x3.hip), the generic-width engine (mshgnn_gen.hip),
 // the compile-time programs' kernels (mshgnn_spec_shard.hip), the plan-independent entry points (mshgnn_train_ops.hip) and window assembly (mshgnn_windows.hip).
 //
 // No CPU fallback exists: every entry point launches HIP kernels or fails loudly.
 #include "mshgnn_slab.hpp"
+#include "mshgnn_enc.hpp"
 #include "mshgnn_launch.hpp"
 extern "C" const char* mshgnn_last_error(void) { return g_err.c_str(); }
 extern "C" const char* mshgnn_version(void) { return "mshgnn 0.5 (gfx950)"; }
@@ -91,251 +92,7 @@ template <typename T> __device__ __forceinline__ void prep_one(const PrepArgs& a
 }
 template <typename T> __global__ void k_prep(PrepArgs a) { prep_one<T>(a, blockIdx.x * blockDim.x + threadIdx.x, true); }
 
-// ------------------------------------------------------------------------------------------------------
-// k_enc_fwd: X_0[node] = relu((mask . x) W_enc^T + b)      (hgnn_c2.py:143-147)
-// one workgroup = MB row blocks (MB*ROWS windows) of ONE node; K streamed in chunks of 128 through LDS
-// ------------------------------------------------------------------------------------------------------
-
-// ALIGNED: every input row starts 16-byte aligned with a pitch of whole 16-byte chunks (the engine's own input layout): raw
-// 16-byte loads only -- the general element-wise path is compiled out of this instantiation (a third of the kernel's code)
-// SERIES (bf16, ALIGNED): the rows come out of the sequence's raw series (SeriesSrc) and are ALSO written to a.x as materialised windows (the
-// weight-gradient kernel reads them later): window assembly fused into the encoder -- one unaligned 16-byte load per chunk (two where the chunk
-// straddles two runs), no separate gather pass over 118 MB.
-__device__ __forceinline__ u32x4 splice8(u32x4 A, u32x4 B, int n0) {      // bf16 elements A[0 .. n0) ++ B[0 .. 8 - n0), 0 < n0 < 8
-    const unsigned __int128 a = ((unsigned __int128)(((unsigned long long)A[3] << 32) | A[2]) << 64) | (((unsigned long long)A[1] << 32) | A[0]);
-    const unsigned __int128 b = ((unsigned __int128)(((unsigned long long)B[3] << 32) | B[2]) << 64) | (((unsigned long long)B[1] << 32) | B[0]);
-    const int sh = 16 * n0;
-    const unsigned __int128 r = (a & ((((unsigned __int128)1) << sh) - 1)) | (b << sh);
-    return u32x4{(unsigned)r, (unsigned)(r >> 32), (unsigned)(r >> 64), (unsigned)(r >> 96)};
-}
-// SRC (bf16, ALIGNED; 8 / 4): the rows come from the caller's own fp64 / fp32 tensors at their dense pitch (WideSrc), are converted in registers and ALSO
-// written to a.x as plan-dtype rows for the weight-gradient kernel -- the cast + re-pitch pass fused into the encoder (mshgnn_*_src entry points).
-// NORM (with SERIES; mshgnn_forward_series / mshgnn_step_*_series_std on a standardised recipe): the chunk's 8 elements come from the FP32 series (two 4-byte-aligned 16-byte loads per
-// piece, as k_enc_x3<.., SERIES>) and every run with a source column is standardised over its window with the statistics k_series_stats left in ser.stats --
-// fp64 -> fp32 -> bf16, the roundings of mshgnn_assemble_windows(normalize) (standardise_one, mshgnn_device.hpp).  Evaluation materialises nothing (a.x null);
-// the training steps (mshgnn_step_*_series_std) get the standardised bf16 rows written to a.x like the plain SERIES rows, behind the next chunk's loads.
-// SIGN (with SERIES; a descriptor with sign_flags): the run pointers may carry RUN_PTR_SIGN -- the chunk's elements are negated per element (sign_mask8_*: a chunk's
-// two runs may differ) before the standardisation and before the window rows are written out, so a.x receives g . window.  Unsigned descriptors launch the
-// instantiations without it: the code they always ran.
-template <typename T, bool ALIGNED, bool SERIES = false, int SRC = 0, bool NORM = false, bool SIGN = false> __global__ __launch_bounds__(256) void k_enc_fwd(EncArgs a, SeriesSrc ser, WideSrc wsrc) {
-    using P = Prec<T>;
-    static_assert(!NORM || SERIES, "standardisation is part of the series gather");
-    static_assert(!SIGN || SERIES, "signs are part of the series gather");
-    static_assert(!SERIES || (sizeof(T) == 2 && ALIGNED), "the series gather is a bf16 path");
-    static_assert(SRC == 0 || (sizeof(T) == 2 && ALIGNED && !SERIES), "wide source rows: bf16 plan, aligned destination rows");
-    constexpr int MB = P::ENC_MB;                       // row blocks (of 16 windows) per workgroup
-    constexpr int VPB = P::ROWS * P::CPR, NIT = VPB / 256 > 0 ? VPB / 256 : 1, BPP = 256 / VPB > 0 ? 256 / VPB : 1;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // SERIES: the FIRST workgroups of the launch compute the batch's window labels (SeriesSrc.lab) -- chains of dependent round trips that finish
-    // under the encoder's body (as the last workgroups they stretched its tail instead: measured)
-    const int lab_blocks = SERIES ? (int)((ser.lab.B + 255) / 256) : 0;
-    if constexpr (SERIES) {
-        if ((int)blockIdx.x < lab_blocks) {
-            const int64_t b = (int64_t)blockIdx.x * 256 + tid;
-            if (b < ser.lab.B) window_labels_one(ser.lab, b);
-            return;
-        }
-    }
-    const int bid = (int)blockIdx.x - lab_blocks;
-    if (bid >= a.wg_prefix[a.n_types]) {      // a workgroup of the embedded layer-pack prep (bf16 plan; see EncArgs.prep)
-        if constexpr (sizeof(T) == 2 && ALIGNED && !SERIES) prep_one<T>(a.prep, (bid - a.wg_prefix[a.n_types]) * 256 + tid, false);
-        return;
-    }
-    int t = 0;
-    while (t + 1 < a.n_types && bid >= a.wg_prefix[t + 1]) ++t;
-    const int local = bid - a.wg_prefix[t];
-    const int node = a.node_list[a.node_off[t] + (ENC_ORDER ? local % a.nodes[t] : local / a.tiles)], tile = ENC_ORDER ? local / a.nodes[t] : local % a.tiles;
-    const bool skip = SERIES && ((a.skip_mask >> (a.tbase[t] + node)) & 1ull) != 0;      // window rows only: nobody reads this node's X_0 (uniform)
-    const int w0 = tile * MB * P::ROWS;
-    const T* x = reinterpret_cast<const T*>(a.x[t]);
-    const int64_t pitch = a.pitch[t];
-    const int F = a.width[t], nt = a.tbase[t + 1] - a.tbase[t], nkc = a.nkc[t], vb = a.vb[t];      // nt: nodes of the type in the input rows (not the launch's list)
-    const uint8_t* sg = a.signs + a.sign_off[t] + (size_t)node * nkc * H;
-    const T* wpack = reinterpret_cast<const T*>(a.wpack);
-    const float* bias = a.bias + (size_t)max(a.bias_idx[t], 0) * H;      // (a type whose X_0 nobody reads has no packs and no bias row: skip)
-
-    typename P::Acc acc[MB];
-#pragma unroll
-    for (int m = 0; m < MB; ++m) acc_init_bias<T>(acc[m], bias, wv, lane);
-    // staging map: fp32 block = 512 chunks -> 2 per thread; bf16 block = 256 chunks -> 1 per thread
-    const int c = tid % P::CPR, r0 = (tid % VPB) / P::CPR, sub = tid / VPB;   // sub is 0 for fp32
-    typename P::BFrag bf;
-    typename P::AFrag af;
-    const AOff<T> ao(lane);      // fragment offsets once per kernel (the generic load_afrag rebuilds them per call: 14 VALU instructions)
-    u32x4 v[MB / BPP][NIT];
-    u32x4 rawv[(SERIES || SRC) ? MB / BPP : 1][NIT];      // SERIES / SRC: the chunk being multiplied, kept until its window rows have been written
-    u32x2 wv8[SRC ? MB / BPP : 1][SRC ? SRC : 1];          // SRC: the chunk's 8 source elements as 8-byte units, untouched until the staging pass
-    const bool unit_ok = SRC == 8 || (F & 1) == 0;        // every 8-byte unit of a row is wholly valid or wholly past its end (uniform)
-    const int64_t spitch = SRC ? wsrc.pitch[t] : 0;
-    // SERIES: first series row of this thread's window rows, the node row's first run
-    int srow[SERIES ? MB / BPP : 1];
-    // NORM: the chunk's fp32 elements, the statistics of its two runs per window, and how the chunk divides between them (set by fetch, read by the next staging pass)
-    u32x4 vn[NORM ? MB / BPP : 1][2];
-    RunStats rsa[NORM ? MB / BPP : 1], rsb[NORM ? MB / BPP : 1];
-    int n_n0 = 8; bool n_has_a = false, n_has_b = false;
-    int g_n0 = 8; bool g_fa = false, g_fb = false;      // SIGN: how the fetched chunk divides between its two runs and their sign flags (set by fetch, read by the next staging pass)
-    __shared__ unsigned long long rp_s[SERIES ? 16 : 1];      // SERIES: the column pointers of this node row's first 16 runs (a chunk takes its pieces from runs j, j + 1)
-    int rfirst = 0, rend = 0;
-    if constexpr (SERIES) {
-#pragma unroll
-        for (int mi = 0; mi < MB / BPP; ++mi) srow[mi] = (int)ser.starts[min(w0 + (mi * BPP + sub) * P::ROWS + r0, a.B - 1)];
-        // one round trip for the row's run pointers instead of a dependent pointer load in front of every chunk's data loads
-        rfirst = ser.rows[2 * (ser.row0[t] + node)]; rend = ser.rows[2 * (ser.row0[t] + node) + 1];
-        if (tid < 16) rp_s[tid] = rfirst + tid < rend ? ser.run_ptr[rfirst + tid] : 0ull;
-        __syncthreads();
-    }
-    auto fetch = [&](int kc) {
-        const int k0 = kc * H + c * P::EPC;
-        const int nvalid = min(P::EPC, F - k0);
-        if constexpr (SERIES) {
-            // elements [k0, k0 + 8) of the row: n0 of them from run j at time offset off, the rest from run j + 1 at offset 0
-            const int j = k0 / ser.T, off = k0 - j * ser.T, n0 = min(P::EPC, ser.T - off);
-            const bool second = nvalid > n0;
-            // (runs past the 16th -- a node row of more than 16 T-long variables -- come from the global table: a dependent load, rare recipes only)
-            auto run_ptr_of = [&](int jj) -> unsigned long long { return jj < 16 ? rp_s[jj] : (rfirst + jj < rend ? ser.run_ptr[rfirst + jj] : 0ull); };
-            unsigned long long pa = nvalid > 0 ? run_ptr_of(j) : 0ull, pb = second ? run_ptr_of(j + 1) : 0ull;
-            if constexpr (SIGN) {
-                g_n0 = n0; g_fa = (pa & RUN_PTR_SIGN) != 0; g_fb = (pb & RUN_PTR_SIGN) != 0;
-                pa = run_ptr_addr(pa); pb = run_ptr_addr(pb);
-            }
-            if constexpr (NORM) {
-                n_n0 = n0; n_has_a = pa != 0ull; n_has_b = pb != 0ull;
-                const u32x4 ones32 = u32x4{0x3f800000u, 0x3f800000u, 0x3f800000u, 0x3f800000u};      // the constant-1 run
-#pragma unroll
-                for (int mi = 0; mi < MB / BPP; ++mi) {
-                    u32x4 a0 = nvalid > 0 ? ones32 : u32x4{0, 0, 0, 0}, a1 = a0;
-                    // (the window of this thread's row: rows past the batch repeat the last window, as srow does)
-                    const double* sp2 = ser.stats + ((size_t)min(w0 + (mi * BPP + sub) * P::ROWS + r0, a.B - 1) * ser.n_runs + rfirst + j) * 2;
-                    rsa[mi] = RunStats{0.0, 1.0}; rsb[mi] = RunStats{0.0, 1.0};
-                    if (pa) {      // (4-byte aligned; the second load may run up to 7 elements past the window's last step: the columns' slack)
-                        const float* sp = reinterpret_cast<const float*>(pa) + srow[mi] + off;
-                        a0 = *reinterpret_cast<const u32x4*>(sp); a1 = *reinterpret_cast<const u32x4*>(sp + 4);
-                        const f64x2 sv = *reinterpret_cast<const f64x2*>(sp2);
-                        rsa[mi] = RunStats{sv[0], sv[1]};
-                    }
-                    if (second) {
-                        u32x4 b0 = ones32, b1 = ones32;
-                        if (pb) {
-                            const float* sp = reinterpret_cast<const float*>(pb) + srow[mi];
-                            b0 = *reinterpret_cast<const u32x4*>(sp); b1 = *reinterpret_cast<const u32x4*>(sp + 4);
-                            const f64x2 sv = *reinterpret_cast<const f64x2*>(sp2 + 2);
-                            rsb[mi] = RunStats{sv[0], sv[1]};
-                        }
-                        splice8f(a0, a1, b0, b1, n0);
-                    }
-                    vn[mi][0] = a0; vn[mi][1] = a1;
-                }
-                return;
-            }
-            const u32x4 ones = u32x4{0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u};      // the constant-1 run (bf16 1.0)
-#pragma unroll
-            for (int mi = 0; mi < MB / BPP; ++mi) {
-                u32x4 va = nvalid > 0 ? ones : u32x4{0, 0, 0, 0};
-                if (pa) va = *reinterpret_cast<const u32x4*>(reinterpret_cast<const T*>(pa) + srow[mi] + off);       // 2-byte aligned: served at full rate
-                if (second) {
-                    u32x4 vb2 = ones;
-                    if (pb) vb2 = *reinterpret_cast<const u32x4*>(reinterpret_cast<const T*>(pb) + srow[mi]);
-                    va = splice8(va, vb2, n0);
-                }
-                v[mi][0] = va;
-            }
-            return;
-        }
-        if constexpr (SRC > 0) {
-#pragma unroll
-            for (int mi = 0; mi < MB / BPP; ++mi) {
-                const int w = w0 + (mi * BPP + sub) * P::ROWS + r0;
-                const char* row = reinterpret_cast<const char*>(wsrc.p[t]) + ((size_t)min(w, a.B - 1) * nt + node) * spitch * SRC;
-                wide_fetch<SRC>(wv8[mi], row, k0, F, unit_ok, w < a.B);
-            }
-            return;
-        }
-#pragma unroll
-        for (int mi = 0; mi < MB / BPP; ++mi)
-#pragma unroll
-            for (int it = 0; it < NIT; ++it) {
-                const int m = mi * BPP + sub, row = r0 + it * (256 / P::CPR), w = w0 + m * P::ROWS + row;
-                if constexpr (ALIGNED) {
-                    // unconditional raw 16-byte load (nothing uses it here): rows past the batch re-read the last row, chunks past the
-                    // row's end re-read the K chunk's first one -- the staging pass zeroes both
-                    const T* src = x + ((size_t)min(w, a.B - 1) * nt + node) * pitch + (nvalid > 0 ? k0 : kc * H);
-                    v[mi][it] = ld16<ENC_NT>(src);
-                } else {
-                    v[mi][it] = u32x4{0, 0, 0, 0};
-                    if (w < a.B) v[mi][it] = load_chunk<T>(x + ((size_t)w * nt + node) * pitch + k0, nvalid, vb);
-                }
-            }
-    };
-    // (two K chunks in flight per thread were measured: no gain, ENC_DEEP of round 2; the plain loop keeps the kernel at 82 VGPRs = five workgroups per CU)
-    fetch(0);
-    for (int kc = 0; kc < nkc; ++kc) {
-        const u32x4 sx = sign_xor<T>(sg + kc * H + c * P::EPC);   // apply_symmetry: +-1 mask as a sign-bit XOR
-        const int nv = F - (kc * H + c * P::EPC);                  // valid elements of this thread's chunk (pad columns dropped)
-        u32x4 gm = u32x4{0, 0, 0, 0}, gm0 = gm, gm1 = gm;          // SIGN: the chunk's per-element sign masks (bf16 elements; NORM: the fp32 elements it standardises)
-        if constexpr (SIGN && NORM) sign_mask8_f32(g_n0, g_fa, g_fb, gm0, gm1);
-        else if constexpr (SIGN) gm = sign_mask8_bf16(g_n0, g_fa, g_fb);
-        __syncthreads();   // previous chunk's MFMAs are done reading LDS
-#pragma unroll
-        for (int mi = 0; mi < MB / BPP; ++mi)
-#pragma unroll
-            for (int it = 0; it < NIT; ++it) {
-                u32x4 raw;
-                if constexpr (SRC > 0) {      // fp64 / fp32 -> (fp32 ->) bf16, round to nearest even twice as torch's .to(bfloat16) does; elements past the row: zero
-                    f32x4 lo4, hi4;
-                    wide_to_f32<SRC>(wv8[mi], nv, lo4, hi4);
-                    raw = pack_oct(lo4, hi4);
-                } else if constexpr (NORM) {
-                    u32x4 a0 = vn[mi][0], a1 = vn[mi][1];
-                    if constexpr (SIGN) { a0 ^= gm0; a1 ^= gm1; }
-                    standardise_oct(a0, a1, n_n0, n_has_a, n_has_b, rsa[mi], rsb[mi]);
-                    raw = pack_oct(__builtin_bit_cast(f32x4, a0), __builtin_bit_cast(f32x4, a1));
-                    if (kc + 1 == nkc) raw = chunk_keep_first<T>(raw, nv);
-                } else if constexpr (SIGN)
-                raw = kc + 1 == nkc ? chunk_keep_first<T>(v[mi][it] ^ gm, nv) : v[mi][it] ^ gm;
-                else
-                raw = kc + 1 == nkc ? chunk_keep_first<T>(v[mi][it], nv) : v[mi][it];      // only the last K chunk has pad columns
-                *reinterpret_cast<u32x4*>(smem + lds_chunk<T>(mi * BPP + sub, r0 + it * (256 / P::CPR), c)) = raw ^ sx;
-                if constexpr (SERIES || SRC > 0) rawv[mi][it] = raw;
-            }
-        __syncthreads();
-        if (!skip) load_bfrag<T>(bf, wpack, a.pack0[t] + kc, wv, lane);   // before the prefetch: vmcnt retires in order
-        if (kc + 1 < nkc) fetch(kc + 1);   // the next K chunk streams from HBM under this chunk's MFMAs
-        if constexpr (SERIES || SRC > 0) {
-            // the materialised window rows of THIS chunk (raw values: the sign mask is applied by whoever reads them) go out BEHIND the next chunk's
-            // loads: vmcnt retires in issue order, so a load issued after stores can only be waited for together with them -- with the stores
-            // youngest, the next chunk's wait leaves them in flight
-#pragma unroll
-            for (int mi = 0; mi < MB / BPP; ++mi)
-#pragma unroll
-                for (int it = 0; it < NIT; ++it) {
-                    const int w = w0 + (mi * BPP + sub) * P::ROWS + r0 + it * (256 / P::CPR), k0 = kc * H + c * P::EPC;
-                    if (x != nullptr && w < a.B && k0 < (int)pitch) *reinterpret_cast<u32x4*>(const_cast<T*>(x) + ((size_t)w * nt + node) * pitch + k0) = rawv[mi][it];
-                }
-        }
-        if (!skip) {
-#pragma unroll
-            for (int m = 0; m < MB; ++m) {
-                if (w0 + m * P::ROWS < a.B) {   // uniform
-                    load_afrag<T>(af, smem, m, ao);
-                    mac(acc[m], af, bf);
-                }
-            }
-        }
-    }
-    if (skip) return;
-    T* x0 = reinterpret_cast<T*>(a.x0);
-    const int gnode = a.tbase[t] + node;
-#pragma unroll
-    for (int m = 0; m < MB; ++m) {
-        const int w = w0 + m * P::ROWS + c_win(lane);
-        if (w0 + m * P::ROWS < a.B) {     // uniform: the 16-window block exists (rows past the batch land in the mask buffer's padding)
-            const unsigned bits = relu_with_bits<T>(acc[m]);
-            if (a.mask0) a.mask0[relu_tile_base(gnode, a.B, (w0 + m * P::ROWS) >> 4, wv) + lane] = (uint8_t)bits;
-        }
-        if (w < a.B) store_oct(x0 + act_idx(w, gnode, a.B) + wv * 32 + c_oct(lane), acc[m].c[0], acc[m].c[1]);
-    }
-}
+// (k_enc_fwd, the encoder of these plans, and splice8: defined in mshgnn_enc.hpp, beside the split plan's k_enc_x3)
 
 // ------------------------------------------------------------------------------------------------------
 // k_layer_fwd: one HeteroConv layer + activation / base_transform + residual  (hgnn_c2.py:150-166)

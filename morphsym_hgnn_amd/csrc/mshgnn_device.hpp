@@ -177,6 +177,10 @@ template <typename T> __device__ __forceinline__ f32x4 round_as(f32x4 v) {
 // streams of the encoder epilogue and of the weight-gradient kernel (one node, many windows) are contiguous and a layer
 // tile reads one 16 x 128 block per node.
 __device__ __forceinline__ size_t act_idx(int w, int node, int B) { return ((size_t)node * B + w) * H; }
+// the split plan (mshgnn_x3_stack.hpp, k_enc_x3 of mshgnn_enc.hpp): element index of the hi half of (window w, node) in its activation tensors; the lo half follows at + H
+using T16 = __bf16;
+using P16 = Prec<__bf16>;
+__device__ __forceinline__ size_t x3_idx(int w, int node, int B) { return ((size_t)node * B + w) * (2 * H); }
 
 // LDS node-block addressing: block = ROWS rows x 128 elements; 16-byte chunk c of row r lives at chunk slot
 // c ^ swz(r), swz(r) = (r & 15) ^ ((r & 4) << 1).  The plain c ^ (r & 15) of guide T2 is 2-way on the 16x16x32 operand

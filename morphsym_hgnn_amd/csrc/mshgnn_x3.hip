@@ -14,6 +14,7 @@
 //   * the MAC loop of the stack kernels is the bf16 plan's: the plan compiler (split_segs, mshgnn_plan.hpp) turns each
 //     segment into two -- the hi image with the hi and lo block of every source, the lo image with the hi block.
 #include "mshgnn_x3_stack.hpp"
+#include "mshgnn_enc.hpp"
 #include "mshgnn_launch.hpp"
 
 // ------------------------------------------------------------------------------------------------------
@@ -69,215 +70,7 @@ __device__ __forceinline__ void prep_one_x3(const PrepArgs& a, int idx, bool wit
 }
 __global__ void k_prep_x3(PrepArgs a) { prep_one_x3(a, blockIdx.x * blockDim.x + threadIdx.x, true); }
 
-// ------------------------------------------------------------------------------------------------------
-// k_enc_x3: X_0[node] = relu((mask . x) W_enc^T + b) from fp32 inputs (hgnn_c2.py:143-147); one workgroup = 64 windows of ONE
-// node, K streamed in chunks of 128 through LDS (hi blocks [0, 4), lo blocks [4, 8)), the next chunk prefetched in registers
-// ------------------------------------------------------------------------------------------------------
-// SERIES (with ALIGNED): the fp32 inputs are gathered from the sequence's resident series like the bf16 encoder's (k_enc_fwd<.., SERIES>): element k
-// of a node row = element starts[w] + k % T of run k / T -- two 4-byte-aligned 16-byte loads per (window, chunk), four and a splice where the chunk
-// straddles two runs -- and the materialised window rows are written on the side for the weight-gradient pass (a.x: the window buffers).
-// SRC (8 / 4, with ALIGNED): the rows come from the caller's own fp64 / fp32 tensors at their dense pitch (WideSrc, mshgnn_device.hpp) and are also written to
-// a.x as fp32 rows at the engine's pitch for the weight-gradient kernel (mshgnn_*_src entry points)
-// NORM (with SERIES; mshgnn_forward_series / mshgnn_step_*_series_std on a standardised recipe): every run with a source column is standardised over its window with the statistics
-// k_series_stats left in ser.stats (standardise_one, mshgnn_device.hpp: the arithmetic of mshgnn_assemble_windows(normalize)).  Evaluation materialises nothing
-// (a.x null); the training steps (mshgnn_step_*_series_std) get the standardised fp32 rows written to a.x like the plain SERIES rows.
-// SIGN (with SERIES; a descriptor with sign_flags): as k_enc_fwd's -- the chunk's fp32 elements are negated per element before the standardisation and before the
-// window rows are written out; unsigned descriptors launch the instantiations without it.
-template <bool ALIGNED, bool SERIES = false, int SRC = 0, bool NORM = false, bool SIGN = false> __global__ __launch_bounds__(256) void k_enc_x3(EncArgs a, int n_img, SeriesSrc ser, WideSrc wsrc) {
-    static_assert(!NORM || SERIES, "standardisation is part of the series gather");
-    static_assert(!SIGN || SERIES, "signs are part of the series gather");
-    static_assert(!SERIES || ALIGNED, "the series gather writes aligned window buffers");
-    static_assert(SRC == 0 || (ALIGNED && !SERIES), "wide source rows: aligned destination rows, no series gather");
-    using P = P16;
-    constexpr int MB = 4;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int lab_blocks = SERIES ? (int)((ser.lab.B + 255) / 256) : 0;      // SERIES: the first workgroups compute the batch's window labels (as k_enc_fwd)
-    if constexpr (SERIES) {
-        if ((int)blockIdx.x < lab_blocks) {
-            const int64_t b = (int64_t)blockIdx.x * 256 + tid;
-            if (b < ser.lab.B) window_labels_one(ser.lab, b);
-            return;
-        }
-    }
-    const int bid = (int)blockIdx.x - lab_blocks;
-    if (bid >= a.wg_prefix[a.n_types]) {      // a workgroup of the embedded layer-pack prep (EncArgs.prep)
-        if constexpr (ALIGNED && !SERIES) prep_one_x3(a.prep, (bid - a.wg_prefix[a.n_types]) * 256 + tid, false);
-        return;
-    }
-    int t = 0;
-    while (t + 1 < a.n_types && bid >= a.wg_prefix[t + 1]) ++t;
-    const int local = bid - a.wg_prefix[t];
-    const int node = a.node_list[a.node_off[t] + (ENC_ORDER ? local % a.nodes[t] : local / a.tiles)], tile = ENC_ORDER ? local / a.nodes[t] : local % a.tiles;
-    const bool skip = SERIES && ((a.skip_mask >> (a.tbase[t] + node)) & 1ull) != 0;      // window rows only: nobody reads this node's X_0 (uniform; EncArgs)
-    const int w0 = tile * MB * P::ROWS;
-    const float* x = reinterpret_cast<const float*>(a.x[t]);
-    const int64_t pitch = a.pitch[t];
-    const int F = a.width[t], nt = a.tbase[t + 1] - a.tbase[t], nkc = a.nkc[t], vb = a.vb[t];      // nt: nodes of the type in the input rows
-    const uint8_t* sg = a.signs + a.sign_off[t] + (size_t)node * nkc * H;
-    const T16* wpack = reinterpret_cast<const T16*>(a.wpack);
-    const float* bias = a.bias + (size_t)max(a.bias_idx[t], 0) * H;
-
-    P::Acc acc[MB];
-#pragma unroll
-    for (int m = 0; m < MB; ++m) acc_init_bias<T16>(acc[m], bias, wv, lane);
-    const int c = tid & 15, r0 = tid >> 4;      // staging: thread = (row, 8-element chunk) of each of the MB row blocks
-    P::BFrag bfh, bfl;
-    P::AFrag af;
-    const AOff<T16> ao(lane);
-    u32x4 v[MB][2];                             // the 8 fp32 elements of the chunk (two 16-byte loads)
-    u32x2 wv8[SRC ? MB : 1][SRC ? SRC : 1];     // SRC: the chunk's 8 source elements as 8-byte units, untouched until the staging pass
-    const bool unit_ok = SRC == 8 || (F & 1) == 0;
-    const int64_t spitch = SRC ? wsrc.pitch[t] : 0;
-    int srow[SERIES ? MB : 1]; int rfirst = 0;  // SERIES: first series row of this thread's window rows, the node row's first run
-    // NORM: the statistics of the chunk's two runs per window, and how the chunk divides between them (set by fetch, read by the next staging pass)
-    RunStats rsa[NORM ? MB : 1], rsb[NORM ? MB : 1];
-    int n_n0 = 8; bool n_has_a = false, n_has_b = false;
-    int g_n0 = 8; bool g_fa = false, g_fb = false;      // SIGN: how the fetched chunk divides between its two runs and their sign flags
-    if constexpr (SERIES) {
-#pragma unroll
-        for (int m = 0; m < MB; ++m) srow[m] = (int)ser.starts[min(w0 + m * P::ROWS + r0, a.B - 1)];
-        rfirst = ser.rows[2 * (ser.row0[t] + node)];
-    }
-    auto fetch = [&](int kc) {
-        const int k0 = kc * H + c * 8;
-        const int nv = F - k0;
-        if constexpr (SERIES) {
-            // elements [k0, k0 + 8) of the row: n0 of them from run j at time offset off, the rest from run j + 1 at offset 0
-            const int j = k0 / ser.T, off = k0 - j * ser.T, n0 = min(8, ser.T - off);
-            const bool second = min(nv, 8) > n0;
-            unsigned long long pa = nv > 0 ? ser.run_ptr[rfirst + j] : 0ull, pb = second ? ser.run_ptr[rfirst + j + 1] : 0ull;
-            if constexpr (SIGN) {
-                g_n0 = n0; g_fa = (pa & RUN_PTR_SIGN) != 0; g_fb = (pb & RUN_PTR_SIGN) != 0;
-                pa = run_ptr_addr(pa); pb = run_ptr_addr(pb);
-            }
-            const u32x4 ones = u32x4{0x3f800000u, 0x3f800000u, 0x3f800000u, 0x3f800000u};      // the constant-1 run
-            if constexpr (NORM) { n_n0 = n0; n_has_a = pa != 0ull; n_has_b = pb != 0ull; }
-#pragma unroll
-            for (int m = 0; m < MB; ++m) {
-                u32x4 a0 = nv > 0 ? ones : u32x4{0, 0, 0, 0}, a1 = a0;
-                if constexpr (NORM) {      // (rows past the batch repeat the last window, as srow does)
-                    const double* sp2 = ser.stats + ((size_t)min(w0 + m * P::ROWS + r0, a.B - 1) * ser.n_runs + rfirst + j) * 2;
-                    rsa[m] = RunStats{0.0, 1.0}; rsb[m] = RunStats{0.0, 1.0};
-                    if (pa) { const f64x2 sv = *reinterpret_cast<const f64x2*>(sp2); rsa[m] = RunStats{sv[0], sv[1]}; }
-                    if (pb) { const f64x2 sv = *reinterpret_cast<const f64x2*>(sp2 + 2); rsb[m] = RunStats{sv[0], sv[1]}; }
-                }
-                if (pa) {      // (4-byte aligned; the second load may run up to 7 elements past the window's last step: the columns' slack)
-                    const float* sp = reinterpret_cast<const float*>(pa) + srow[m] + off;
-                    a0 = *reinterpret_cast<const u32x4*>(sp); a1 = *reinterpret_cast<const u32x4*>(sp + 4);
-                }
-                if (second) {
-                    u32x4 b0 = ones, b1 = ones;
-                    if (pb) {
-                        const float* sp = reinterpret_cast<const float*>(pb) + srow[m];
-                        b0 = *reinterpret_cast<const u32x4*>(sp); b1 = *reinterpret_cast<const u32x4*>(sp + 4);
-                    }
-                    splice8f(a0, a1, b0, b1, n0);
-                }
-                v[m][0] = a0; v[m][1] = a1;
-            }
-            return;
-        }
-        if constexpr (SRC > 0) {
-#pragma unroll
-            for (int m = 0; m < MB; ++m) {
-                const int w = w0 + m * P::ROWS + r0;
-                const char* row = reinterpret_cast<const char*>(wsrc.p[t]) + ((size_t)min(w, a.B - 1) * nt + node) * spitch * SRC;
-                wide_fetch<SRC>(wv8[m], row, k0, F, unit_ok, w < a.B);
-            }
-            return;
-        }
-#pragma unroll
-        for (int m = 0; m < MB; ++m) {
-            const int w = w0 + m * P::ROWS + r0;
-            if constexpr (ALIGNED) {
-                // unconditional raw loads (nothing uses them here): rows past the batch re-read the last row, halves past the row's end
-                // re-read the K chunk's first elements -- the staging pass zeroes the latter, the former are never stored
-                const float* src = x + ((size_t)min(w, a.B - 1) * nt + node) * pitch;
-                v[m][0] = ld16<ENC_NT>(src + (nv > 0 ? k0 : kc * H));
-                v[m][1] = ld16<ENC_NT>(src + (nv > 4 ? k0 + 4 : kc * H));
-            } else {
-                v[m][0] = u32x4{0, 0, 0, 0}; v[m][1] = u32x4{0, 0, 0, 0};
-                if (w < a.B) {
-                    const float* src = x + ((size_t)w * nt + node) * pitch + k0;
-                    v[m][0] = load_chunk<float>(src, nv, vb);
-                    v[m][1] = load_chunk<float>(src + 4, nv - 4, vb);
-                }
-            }
-        }
-    };
-    fetch(0);
-    for (int kc = 0; kc < nkc; ++kc) {
-        const u32x4 sxa = sign_xor<float>(sg + kc * H + c * 8), sxb = sign_xor<float>(sg + kc * H + c * 8 + 4);   // apply_symmetry: +-1 mask as a sign-bit XOR
-        const int nv = F - (kc * H + c * 8);
-        u32x4 gm0 = u32x4{0, 0, 0, 0}, gm1 = gm0;      // SIGN: the chunk's per-element sign masks
-        if constexpr (SIGN) sign_mask8_f32(g_n0, g_fa, g_fb, gm0, gm1);
-        __syncthreads();   // previous chunk's MFMAs are done reading LDS
-#pragma unroll
-        for (int m = 0; m < MB; ++m) {
-            u32x4 fa = v[m][0], fb = v[m][1];
-            if constexpr (SRC > 0) {      // fp64 -> fp32 (round to nearest even, as torch's .float()), or the fp32 units as they are; elements past the row: zero
-                f32x4 lo4, hi4;
-                wide_to_f32<SRC>(wv8[m], nv, lo4, hi4);
-                fa = __builtin_bit_cast(u32x4, lo4); fb = __builtin_bit_cast(u32x4, hi4);
-            } else
-            {
-                if constexpr (SIGN) { fa ^= gm0; fb ^= gm1; }
-                if constexpr (NORM) standardise_oct(fa, fb, n_n0, n_has_a, n_has_b, rsa[m], rsb[m]);
-                if (kc + 1 == nkc) { fa = chunk_keep_first<float>(fa, nv); fb = chunk_keep_first<float>(fb, nv - 4); }     // only the last K chunk has pad columns
-            }
-            if constexpr (SERIES || SRC > 0) {      // the materialised window row (raw values: the sign mask is applied by whoever reads it)
-                const int w = w0 + m * P::ROWS + r0, k0 = kc * H + c * 8;
-                if (x != nullptr && w < a.B) {
-                    float* dst = const_cast<float*>(x) + ((size_t)w * nt + node) * pitch + k0;
-                    if (k0 < (int)pitch) *reinterpret_cast<u32x4*>(dst) = fa;
-                    if (k0 + 4 < (int)pitch) *reinterpret_cast<u32x4*>(dst + 4) = fb;
-                }
-            }
-            fa ^= sxa; fb ^= sxb;
-            u32x4 hi, lo;
-            split_oct(__builtin_bit_cast(f32x4, fa), __builtin_bit_cast(f32x4, fb), hi, lo);
-            *reinterpret_cast<u32x4*>(smem + lds_chunk<T16>(m, r0, c)) = hi;
-            *reinterpret_cast<u32x4*>(smem + lds_chunk<T16>(MB + m, r0, c)) = lo;
-        }
-        __syncthreads();
-        if (!skip) {
-            load_bfrag<T16>(bfh, wpack, a.pack0[t] + kc, wv, lane);              // before the prefetch: vmcnt retires in order
-            load_bfrag<T16>(bfl, wpack, n_img + a.pack0[t] + kc, wv, lane);
-        }
-        if (kc + 1 < nkc) fetch(kc + 1);   // the next K chunk streams from HBM under this chunk's MFMAs
-        if (!skip) {
-#pragma unroll
-            for (int m = 0; m < MB; ++m) {
-                if (w0 + m * P::ROWS < a.B) {   // uniform
-                    load_afrag<T16>(af, smem, m, ao);
-                    mac(acc[m], af, bfh);
-                    mac(acc[m], af, bfl);
-                    load_afrag<T16>(af, smem, MB + m, ao);
-                    mac(acc[m], af, bfh);
-                }
-            }
-        }
-    }
-    if (skip) return;
-    T16* x0 = reinterpret_cast<T16*>(a.x0);
-    const int gnode = a.tbase[t] + node;
-#pragma unroll
-    for (int m = 0; m < MB; ++m) {
-        const int w = w0 + m * P::ROWS + c_win(lane);
-        if (w0 + m * P::ROWS < a.B) {     // uniform: the 16-window block exists (rows past the batch land in the mask buffer's padding)
-            const unsigned bits = relu_with_bits<T16>(acc[m]);
-            if (a.mask0) a.mask0[relu_tile_base(gnode, a.B, (w0 + m * P::ROWS) >> 4, wv) + lane] = (uint8_t)bits;
-        }
-        if (w < a.B) {
-            u32x4 hi, lo;
-            split_oct(acc[m].c[0], acc[m].c[1], hi, lo);
-            T16* q = x0 + x3_idx(w, gnode, a.B) + wv * 32 + c_oct(lane);
-            *reinterpret_cast<u32x4*>(q) = hi;
-            *reinterpret_cast<u32x4*>(q + H) = lo;
-        }
-    }
-}
+// (k_enc_x3, the encoder of this plan: defined in mshgnn_enc.hpp, beside k_enc_fwd of the fp32 / bf16 plans)
 
 // ------------------------------------------------------------------------------------------------------
 // The stack kernels (mshgnn_x3_stack.hpp) over the plan's run-time tables; those over the compile-time programs are mshgnn_x3_spec_shard.hip's

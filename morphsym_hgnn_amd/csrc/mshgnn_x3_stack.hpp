@@ -4,12 +4,6 @@
 #pragma once
 #include "mshgnn_device.hpp"
 
-using T16 = __bf16;
-using P16 = Prec<__bf16>;
-
-// element index of the hi half of (window w, node) in a split-plan activation tensor; the lo half follows at + H
-__device__ __forceinline__ size_t x3_idx(int w, int node, int B) { return ((size_t)node * B + w) * (2 * H); }
-
 // stage the [hi | lo] rows of every node for which keep(n) into LDS: 512 threads = 16 rows x 32 chunks, one node per load, 10 in flight
 // (an 18-node tile in two round trips to HBM: with one workgroup per CU nothing else hides them)
 template <typename Keep>

@@ -292,6 +292,82 @@ def test_series_step_takes_node_rows_of_more_than_16_runs(materialize):
     assert torch.equal(y, y2) and torch.equal(out_a, out_b) and torch.equal(loss_a, loss_b) and torch.equal(g_a, g_b)
 
 
+def _more_than_16_runs(plan, normalize=False):
+    """the recipe, model and starts of the test above on either plan: (store, engine, flat parameters, starts)"""
+    from morphsym_hgnn_amd import engine as eng, synth, topology
+    from morphsym_hgnn_amd.spec import ModelSpec
+    from morphsym_hgnn_amd.windows import SequenceStore, quadsdk_a1_c2_recipe
+    hist, B = 10, 77
+    recipe = quadsdk_a1_c2_recipe(JP, FP, hist, 3, n_base=1, normalize=normalize)
+    recipe.variables["base"] = recipe.variables["base"] * 3            # 18 runs of 10 steps per base row
+    assert recipe.width("base") == 180 and recipe.width("base") // hist > 16
+    spec = ModelSpec(kind="mi", topology=topology.TOPOLOGIES["quadruped-mi"](), hidden=128, num_layers=2,
+                     widths={t: recipe.width(t) for t in recipe.node_types}, regression=True, grf_dimension=3, group=None, num_timesteps=hist)
+    store = SequenceStore(SEQ, recipe, dtype=plan)
+    e = eng.Engine(spec, plan)
+    assert not e.generic
+    starts = torch.randint(0, N - hist + 1, (B,), generator=torch.Generator().manual_seed(5))
+    starts[0], starts[-1] = 0, N - hist
+    return store, e, eng.flatten_params(spec, synth.make_params(8, spec.param_shapes()), e.device), starts.cuda()
+
+
+def _assemble_then_step(store, e, flat, starts):
+    """the reference of the three tests below: assembly + mshgnn_step_mse, which does not run through the encoders' series gather"""
+    B = int(starts.numel())
+    xs, y, _ = store.assemble(starts)
+    xs = [x.clone() for x in xs]; y = y.clone()
+    out, loss, g = e.step_mse(xs, flat, y.reshape(-1), B)
+    return xs, y, out.clone(), loss.clone(), g.clone()
+
+
+@pytest.mark.gpu
+def test_split_plan_series_step_takes_node_rows_of_more_than_16_runs():
+    """The same on the split plan, whose encoder reads every run pointer from the global table: windows, labels, output, loss and the whole flat gradient."""
+    store, e, flat, starts = _more_than_16_runs("x3")
+    xs, y, out_a, loss_a, g_a = _assemble_then_step(store, e, flat, starts)
+    for x, t in zip(store._buffers(int(starts.numel()))[0], store.recipe.node_types):
+        x.fill_(float("nan"))                          # the fused step must rewrite every feature column ...
+        x[:, store.recipe.width(t):] = 0               # ... and leaves the (zero) pad columns alone
+    xs2, y2, out_b, loss_b, g_b = e.step_mse_series(store, starts, flat)
+    torch.cuda.synchronize()
+    assert len(xs) == len(xs2)
+    for a, b in zip(xs, xs2):
+        assert torch.equal(a, b)
+    assert torch.equal(y, y2) and torch.equal(out_a, out_b) and torch.equal(loss_a, loss_b) and torch.equal(g_a, g_b)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("plan", ["bf16", "x3"])
+def test_standardised_forward_series_takes_node_rows_of_more_than_16_runs(plan):
+    """The standardised recipe (the fp32 gather and the run statistics past the 16th run) through mshgnn_forward_series: the bits of assembly + forward."""
+    store, e, flat, starts = _more_than_16_runs(plan, normalize=True)
+    B = int(starts.numel())
+    xs, y_a, _ = store.assemble(starts)
+    y_a = y_a.clone()
+    out_a = e.forward(xs, flat, B, training=False).clone()
+    y, _, _, out = e.forward_series(store, starts, flat)
+    torch.cuda.synchronize()
+    assert torch.equal(out, out_a) and torch.equal(y, y_a) and torch.isfinite(out).all()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("plan", ["bf16", "x3"])
+def test_standardised_series_step_takes_node_rows_of_more_than_16_runs(plan):
+    """... and through mshgnn_step_mse_series_std: the materialised standardised windows, labels, output, loss and the whole flat gradient of assembly + step."""
+    store, e, flat, starts = _more_than_16_runs(plan, normalize=True)
+    xs, y, out_a, loss_a, g_a = _assemble_then_step(store, e, flat, starts)
+    for x, t in zip(store._buffers(int(starts.numel()))[0], store.recipe.node_types):
+        x.fill_(float("nan"))                          # the fused step must rewrite every feature column ...
+        x[:, store.recipe.width(t):] = 0               # ... and leaves the (zero) pad columns alone
+    xs2, y2, out_b, loss_b, g_b = e.step_mse_series_std(store, starts, flat)
+    torch.cuda.synchronize()
+    assert len(xs) == len(xs2)
+    for a, b in zip(xs, xs2):
+        assert torch.equal(a, b)
+    assert torch.equal(y, y2) and torch.equal(out_a, out_b) and torch.equal(loss_a, loss_b) and torch.equal(g_a, g_b)
+    assert torch.isfinite(out_b).all() and torch.isfinite(g_b).all()
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("B", [3, 130, 1000])
 def test_classification_series_step_is_bit_identical_to_assemble_then_step_ce(B):
