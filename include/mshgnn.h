@@ -344,7 +344,9 @@ typedef struct mshgnn_window_desc {
     int32_t sign_flags;       /* group-transformed windows (the field was reserved: ABI 6 as before, a zero means what it meant).  bit 0: the caller states that
                                * `runs` source words and `label_cols` entries may carry MSHGNN_WINDOW_SIGN_FLAG (see below); with bit 0 clear the tables are read
                                * as they always were.  bit 1: the caller vouches that an earlier call with THIS descriptor (same tables) returned MSHGNN_OK, so
-                               * the tables are not read back and checked again (the check is one small synchronous device-to-host copy: not capturable). */
+                               * the tables are not read back and checked again (the check is one small synchronous device-to-host copy: not capturable).
+                               * bits 8..15: K, the number of group elements whose tables are stacked behind each other (ORBIT BATCHES below); 0 or 1: one table, as
+                               * always.  K in [2, 8]; K > 1 implies bit 0. */
 } mshgnn_window_desc;
 
 /* SIGNED RUNS AND LABELS (sign_flags bit 0): g . window for an element g of a morphological symmetry group is a choice of columns and a +-1 per column, so it
@@ -358,6 +360,24 @@ typedef struct mshgnn_window_desc {
  * (the constant-1 run is the word -1 and cannot carry a sign), a source >= n_src, a label column whose column part is outside [0, 256) -- and a stream that
  * is being captured while the check is still due.                                                                                                        */
 #define MSHGNN_WINDOW_SIGN_FLAG (1 << 30)
+
+/* ORBIT BATCHES (sign_flags bits 8..15 = K > 1): every window of a batch carries its own group element.  The tables are stacked element-major over the same series,
+ *   runs        int32[K][n_runs][5]      label_cols  int32[K][n_label]      run_ptrs scratch  K * n_runs * 8 bytes
+ * and n_runs, rows, n_rows and mshgnn_forward_series_stats_bytes stay those of ONE element (a window has exactly one).  Window b's element rides in starts[b]:
+ * bits 56..63 hold the element index, the low 56 bits the start row.  These bits are read only when the descriptor announces K > 1; with K <= 1 the high bits stay
+ * unread, as always.  Every gather of window b takes its run word, run pointer and label column from block `element` of the tables; the statistics of a standardised
+ * recipe are those of the window's own element's run.  quat_out is not transformed.
+ * The checking call (bit 1 clear) refuses with MSHGNN_EINVAL before any launch, besides what it refuses in every element's sign tables: K > 8; an element table whose
+ * {type, node, first feature, length} differs from element 0's in any run; a constant-1 run (source word -1) that is not constant-1 in every element.
+ * An element index >= K in a device `starts` entry is clamped to K - 1 inside the kernels (one min): it never indexes past the tables.  Device-given starts stay
+ * unchecked otherwise, rows as always.
+ * Routes: mshgnn_assemble_windows, mshgnn_forward_series (standardised recipes included), mshgnn_step_mse_series / _ce_series with x_out given and the two _std steps.
+ * x_out == NULL on the plain steps is refused with MSHGNN_EUNSUPPORTED for K > 1 (the weight-gradient kernel's own series gather has no per-window tables): materialise. */
+#define MSHGNN_WINDOW_MAX_ELEMENTS 8
+#define MSHGNN_WINDOW_ELEMENTS_SHIFT 8                                   /* sign_flags: K = (sign_flags >> 8) & 0xff */
+#define MSHGNN_WINDOW_ELEMENTS_MASK 0xff
+#define MSHGNN_START_ELEMENT_SHIFT 56                                    /* starts[b]: element = (uint64) starts[b] >> 56 */
+#define MSHGNN_START_ROW_MASK ((((int64_t)1) << MSHGNN_START_ELEMENT_SHIFT) - 1)   /* starts[b]: row = starts[b] & MSHGNN_START_ROW_MASK */
 
 int mshgnn_assemble_windows(const mshgnn_window_desc* desc, const float* const* src, const int64_t* src_cstride,
                             const int64_t* src_rows, const int64_t* starts /* device int64[batch] */, int64_t batch,

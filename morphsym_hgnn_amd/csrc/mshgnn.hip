@@ -1619,7 +1619,10 @@ static int forward_impl(const mshgnn_plan* p, StepCall& c) {
         if (route == EncRoute::ALIGNED) enc(k_enc_fwd<T, true>, SeriesSrc{}, WideSrc{});
         else if (route == EncRoute::ELEMENTWISE) enc(k_enc_fwd<T, false>, SeriesSrc{}, WideSrc{});
         else if constexpr (sizeof(T) == 2) {      // (plan_traits<float>.src_routes is false: the fp32 plan takes no other route)
-            if (route == EncRoute::SERIES_STD && c.series->sign) enc(k_enc_fwd<T, true, true, 0, true, true>, *c.series, WideSrc{});
+            const bool orbit = (route == EncRoute::SERIES_STD || route == EncRoute::SERIES) && (c.series->sign >> MSHGNN_WINDOW_ELEMENTS_SHIFT) != 0;      // K > 1: a group element per window
+            if (route == EncRoute::SERIES_STD && orbit) enc(k_enc_fwd<T, true, true, 0, true, true, true>, *c.series, WideSrc{});
+            else if (route == EncRoute::SERIES && orbit) enc(k_enc_fwd<T, true, true, 0, false, true, true>, *c.series, WideSrc{});
+            else if (route == EncRoute::SERIES_STD && c.series->sign) enc(k_enc_fwd<T, true, true, 0, true, true>, *c.series, WideSrc{});
             else if (route == EncRoute::SERIES && c.series->sign) enc(k_enc_fwd<T, true, true, 0, false, true>, *c.series, WideSrc{});
             else if (route == EncRoute::SERIES_STD) enc(k_enc_fwd<T, true, true, 0, true>, *c.series, WideSrc{});
             else if (route == EncRoute::SERIES) enc(k_enc_fwd<T, true, true>, *c.series, WideSrc{});
@@ -1966,6 +1969,19 @@ __global__ void k_series_run_ptrs(const int* runs, int n_runs, WindowArgs wa, in
     run_ptr[r] = p | (neg && p ? RUN_PTR_SIGN : 0ull);      // a negated run: the flag rides in bit 63, masked off by every gather (run_ptr_addr)
 }
 
+// K > 1 group elements (orbit descriptors): all K blocks of `runs`, n_total = K * n_runs <= 8 * 128 pointers, in the same one workgroup
+__global__ void k_series_run_ptrs_orbit(const int* runs, int n_total, WindowArgs wa, int elem_bytes, unsigned long long* run_ptr) {
+    for (int r = threadIdx.x; r < n_total; r += blockDim.x) {
+        bool neg;
+        const int sc = run_source(runs[(size_t)r * 5 + 3], wa.sign, neg);
+        unsigned long long p = 0ull;
+#pragma unroll
+        for (int k = 0; k < WIN_MAX_SRC; ++k)
+            if (sc >= 0 && (sc >> 8) == k) p = (unsigned long long)(reinterpret_cast<const char*>(wa.src[k]) + (size_t)(sc & 0xff) * wa.src_cstride[k] * elem_bytes);
+        run_ptr[r] = p | (neg && p ? RUN_PTR_SIGN : 0ull);
+    }
+}
+
 // ---- what the series routes share: the caller's description of the sequence and the windows, one check of the window descriptor against the plan, one fill of
 // SeriesSrc / LabelArgs.  Training = mshgnn_step_mse_series / mshgnn_step_ce_series and their _std forms, evaluation = mshgnn_forward_series.
 struct SeriesArgs {      // as the entry points receive them
@@ -2024,7 +2040,7 @@ static int check_label_rotation(const SeriesArgs& s, const SeriesChecks& k) {
 }
 // the source arrays the gather reads: the fp32 series (split plan, standardised recipes) or their bf16 copies
 static int check_series_sources(const SeriesArgs& s, bool fp32_gather, WindowArgs& wa) {
-    wa.sign = s.d->sign_flags & 1;
+    wa.sign = desc_sign_word(s.d);
     for (int i = 0; i < s.d->n_src; ++i) {
         // (8 elements of slack behind every column: a chunk's 16-byte loads may run past the window's last step)
         if (!s.src[i] || (!fp32_gather && !s.src_bf16[i]) || s.src_rows[i] < s.d->history || s.src_cstride[i] < s.src_rows[i] + 8 || s.src_rows[i] >= (1ll << 31))
@@ -2038,8 +2054,11 @@ static int check_series_sources(const SeriesArgs& s, bool fp32_gather, WindowArg
 static void fill_series_src(const SeriesArgs& s, const WindowArgs& wa, bool fp32_gather, bool want_q, hipStream_t st, SeriesSrc& ser) {
     const mshgnn_window_desc* d = s.d;
     static_assert(WIN_MAX_RUNS <= 256, "k_series_run_ptrs resolves the runs in one 256-thread workgroup");
-    if (!d->run_ptrs_ready)      // (the caller vouches for the scratch's contents otherwise: same descriptor, same source arrays as the call that filled it)
-        hipLaunchKernelGGL(k_series_run_ptrs, dim3(1), dim3(256), 0, st, d->runs, d->n_runs, wa, fp32_gather ? 4 : 2, reinterpret_cast<unsigned long long*>(s.run_ptrs));
+    const int K = desc_elements(d);
+    if (!d->run_ptrs_ready) {    // (the caller vouches for the scratch's contents otherwise: same descriptor, same source arrays as the call that filled it)
+        if (K > 1) hipLaunchKernelGGL(k_series_run_ptrs_orbit, dim3(1), dim3(256), 0, st, d->runs, K * d->n_runs, wa, fp32_gather ? 4 : 2, reinterpret_cast<unsigned long long*>(s.run_ptrs));
+        else hipLaunchKernelGGL(k_series_run_ptrs, dim3(1), dim3(256), 0, st, d->runs, d->n_runs, wa, fp32_gather ? 4 : 2, reinterpret_cast<unsigned long long*>(s.run_ptrs));
+    }
     const bool want_y = s.y_out != nullptr;
     if (want_y || want_q) {
         LabelArgs& l = ser.lab;
@@ -2048,9 +2067,10 @@ static void fill_series_src(const SeriesArgs& s, const WindowArgs& wa, bool fp32
         const bool q = d->quat_src >= 0 && (want_q || d->label_rotate);
         l.quat_src = q ? s.src[d->quat_src] : nullptr; l.quat_cs = q ? s.src_cstride[d->quat_src] : 0;
         l.starts = s.starts; l.B = s.batch; l.T = d->history; l.label_cols = d->label_cols; l.n_label = want_y ? d->n_label : 0; l.label_rotate = want_y ? d->label_rotate : 0;
-        l.y = s.y_out; l.quat = s.quat_out; l.labels_int = s.labels_out; l.sign = d->sign_flags & 1;
+        l.y = s.y_out; l.quat = s.quat_out; l.labels_int = s.labels_out; l.sign = desc_sign_word(d);
     }
-    ser.sign = d->sign_flags & 1;
+    ser.sign = desc_sign_word(d);
+    if (K > 1) ser.n_runs = d->n_runs;      // (the element blocks of run_ptr are n_runs apart)
     ser.run_ptr = reinterpret_cast<const unsigned long long*>(s.run_ptrs); ser.rows = d->rows; ser.starts = s.starts; ser.T = d->history;
     { int r0 = 0; for (int t = 0; t < d->n_types; ++t) { ser.row0[t] = r0; r0 += d->type_nodes[t]; } }
 }
@@ -2059,6 +2079,14 @@ static bool series_plan_ok(const mshgnn_plan* p) { return !p->gen && (p->hp.d.dt
 
 // the statistics pre-pass of the standardised routes (defined with mshgnn_forward_series below)
 __global__ __launch_bounds__(256) void k_series_stats(const int* runs, int n_runs, const unsigned long long* run_ptr, const int64_t* starts, int64_t B, double* stats);
+__global__ __launch_bounds__(256) void k_series_stats_orbit(const int* runs, int n_runs, int K, const unsigned long long* run_ptr, const int64_t* starts, int64_t B, double* stats);
+static void launch_series_stats(const mshgnn_window_desc* d, const SeriesSrc& ser, const int64_t* starts, int64_t batch, void* stats, hipStream_t st) {
+    const int64_t waves = batch * d->n_runs;
+    const dim3 grid((unsigned)((waves + 3) / 4));
+    const int K = desc_elements(d);
+    if (K > 1) hipLaunchKernelGGL(k_series_stats_orbit, grid, dim3(256), 0, st, d->runs, d->n_runs, K, ser.run_ptr, starts, batch, reinterpret_cast<double*>(stats));
+    else hipLaunchKernelGGL(k_series_stats, grid, dim3(256), 0, st, d->runs, d->n_runs, ser.run_ptr, starts, batch, reinterpret_cast<double*>(stats));
+}
 
 // std_route (mshgnn_step_*_series_std): a standardised recipe -- k_series_stats leaves {mean, sd} of every (window, run) in `stats`, the NORM encoders apply them to the
 // FP32 series on both plans and write the standardised windows to x_out, which the weight-gradient pass then reads like assembled ones.
@@ -2087,6 +2115,8 @@ static int step_series(const mshgnn_plan* p, const SeriesArgs& s, bool std_route
     const bool fp32_gather = x3 || std_route;      // standardisation happens before the bf16 rounding: the bf16 plan's NORM encoder reads the fp32 series too
     if (!fp32_gather && !s.src_bf16) return set_err(MSHGNN_EINVAL, "null argument to mshgnn_step_mse_series / mshgnn_step_ce_series");
     if (x3 && !x_out) return set_err(MSHGNN_EUNSUPPORTED, "the split plan's weight-gradient kernel reads materialised windows: x_out must be given");
+    // (the weight-gradient kernel's own series gather takes one table for the whole batch)
+    if (!x_out && desc_elements(s.d) > 1) return set_err(MSHGNN_EUNSUPPORTED, std::string(who) + ": a descriptor with several group elements needs materialised windows: x_out must be given");
     // (the plain routes leave several_runs_need_history8 open, see SeriesChecks; the standardised ones are new and check it)
     const SeriesChecks k{who, who_ce, /*labels_required*/ true, /*takes_normalize*/ std_route, /*ce_needs_two_logits*/ true, /*several_runs_need_history8*/ std_route};
     WindowArgs wa{};
@@ -2097,9 +2127,7 @@ static int step_series(const mshgnn_plan* p, const SeriesArgs& s, bool std_route
     SeriesSrc ser{};
     fill_series_src(s, wa, fp32_gather, /*want_q: the quaternion travels with the labels wherever the recipe has one*/ true, (hipStream_t)stream, ser);
     if (std_route) {
-        const int64_t waves = s.batch * s.d->n_runs;
-        hipLaunchKernelGGL(k_series_stats, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, (hipStream_t)stream, s.d->runs, s.d->n_runs, ser.run_ptr, s.starts, s.batch,
-                           reinterpret_cast<double*>(stats));
+        launch_series_stats(s.d, ser, s.starts, s.batch, stats, (hipStream_t)stream);
         ser.stats = reinterpret_cast<const double*>(stats); ser.n_runs = s.d->n_runs;
     }
     StepCall c;
@@ -2174,6 +2202,32 @@ __global__ __launch_bounds__(256) void k_series_stats(const int* runs, int n_run
     if (lane == 0) *reinterpret_cast<f64x2*>(stats + (size_t)idx * 2) = f64x2{rs.mean, rs.sd};
 }
 
+// K > 1 group elements: the statistics of window b's run r are those of ITS element's run -- run pointer (and sign) from block `element` of the table; the layout of
+// `stats` stays [B][n_runs][2] (a window has exactly one element) and the lengths are element 0's, which are every element's.
+__global__ __launch_bounds__(256) void k_series_stats_orbit(const int* runs, int n_runs, int K, const unsigned long long* run_ptr, const int64_t* starts, int64_t B, double* stats) {
+    const int lane = threadIdx.x & 63;
+    const int64_t idx = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);      // (window, run): one wave each
+    if (idx >= B * n_runs) return;
+    const int64_t b = idx / n_runs; const int r = (int)(idx - b * n_runs);
+    const int len = runs[(size_t)r * 5 + 4];
+    const int64_t sw = starts[b];
+    const unsigned long long p = run_ptr[(size_t)start_element(sw, K) * n_runs + r];
+    RunStats rs{0.0, 1.0};      // constant-one runs are left alone (never applied)
+    if (p) {
+        const float* sp = reinterpret_cast<const float*>(run_ptr_addr(p)) + start_row(sw);
+        const bool neg = (p & RUN_PTR_SIGN) != 0;      // the statistics of the NEGATED run, as mshgnn_assemble_windows computes them
+        float v[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int k = 2 * lane + 128 * (q >> 1) + (q & 1);
+            v[q] = 1.0f;
+            if (k < len) v[q] = xor_sign(sp[k], neg);
+        }
+        rs = run_stats(v, len, lane);
+    }
+    if (lane == 0) *reinterpret_cast<f64x2*>(stats + (size_t)idx * 2) = f64x2{rs.mean, rs.sd};
+}
+
 extern "C" int64_t mshgnn_forward_series_stats_bytes(const mshgnn_window_desc* d, int64_t batch) {
     if (!d || batch < 1 || d->n_runs < 1 || !d->normalize) return 0;
     return batch * (int64_t)d->n_runs * 2 * (int64_t)sizeof(double);
@@ -2209,8 +2263,7 @@ extern "C" int mshgnn_forward_series(const mshgnn_plan* p, const mshgnn_window_d
     SeriesSrc ser{};
     fill_series_src(s, wa, fp32_gather, quat_out != nullptr && d->quat_src >= 0, st, ser);
     if (norm) {
-        const int64_t waves = batch * d->n_runs;
-        hipLaunchKernelGGL(k_series_stats, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, d->runs, d->n_runs, ser.run_ptr, starts, batch, reinterpret_cast<double*>(stats));
+        launch_series_stats(d, ser, starts, batch, stats, st);
         ser.stats = reinterpret_cast<const double*>(stats); ser.n_runs = d->n_runs;
     }
     StepCall c;      // evaluation, nothing materialised (x = null): only the nodes whose X_0 can reach the output get encoder workgroups

@@ -400,6 +400,14 @@ __device__ __forceinline__ int run_source(int sc, int sign_tables, bool& neg) {
     neg = sign_tables != 0 && sc >= 0 && (sc & WIN_SIGN_FLAG) != 0;
     return neg ? (sc & ~WIN_SIGN_FLAG) : sc;
 }
+// ORBIT BATCHES (sign_flags bits 8..15 = K > 1, include/mshgnn.h): the tables hold K element blocks behind each other and window b's element rides in bits 56..63 of
+// starts[b].  The `sign` words of WindowArgs / LabelArgs / SeriesSrc carry K in bits 8..15 (bit 0 as always: any non-zero word means "the tables carry flags" to the
+// kernels that existed before, which read nothing else of it), so no argument structure changes.  The ORBIT instantiations split every start word with these three:
+// an element index >= K is clamped to K - 1 with one min and never indexes past the tables.
+constexpr int START_ELEMENT_SHIFT = MSHGNN_START_ELEMENT_SHIFT;
+__device__ __forceinline__ int orbit_elements(int sign_word) { return (sign_word >> MSHGNN_WINDOW_ELEMENTS_SHIFT) & MSHGNN_WINDOW_ELEMENTS_MASK; }
+__device__ __forceinline__ int start_element(int64_t start_word, int K) { return min((int)((unsigned long long)start_word >> START_ELEMENT_SHIFT), K - 1); }
+__device__ __forceinline__ int64_t start_row(int64_t start_word) { return start_word & MSHGNN_START_ROW_MASK; }
 // Per-element sign masks of a 16-byte chunk of a node row: its first n0 elements come from a run with flag fa, the rest from the next run with flag fb (two
 // runs of one row may have opposite signs, and the split point is wherever the history length puts it).  8 bf16 / 8 fp32 elements.
 __device__ __forceinline__ u32x4 sign_mask8_bf16(int n0, bool fa, bool fb) {
@@ -422,8 +430,12 @@ struct LabelArgs {
     int sign;                                    // label_cols entries may carry WIN_SIGN_FLAG: the label is negated AFTER the rotation (labels_int stays y != 0)
 };
 
-__device__ __forceinline__ void window_labels_one(const LabelArgs& a, int64_t b) {
-    const int64_t row = a.starts[b] + a.T - 1;
+// ORBIT: the window's label columns (and their signs) are those of its own element's block of label_cols
+template <bool ORBIT = false> __device__ __forceinline__ void window_labels_one(const LabelArgs& a, int64_t b) {
+    const int64_t sw = a.starts[b];
+    const int* label_cols = a.label_cols;
+    if constexpr (ORBIT) label_cols += (size_t)start_element(sw, orbit_elements(a.sign)) * a.n_label;
+    const int64_t row = (ORBIT ? start_row(sw) : sw) + a.T - 1;
     const float* lab = a.lab + row;
     const int64_t lcs = a.lab_cs;
     double R[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
@@ -452,7 +464,7 @@ __device__ __forceinline__ void window_labels_one(const LabelArgs& a, int64_t b)
         for (int j = 0; j < LMAX; ++j) {
             v[j] = 0.f;
             if (k0 + j < a.n_label) {
-                int lc = a.label_cols[k0 + j];
+                int lc = label_cols[k0 + j];
                 if (a.sign) { neg |= (unsigned)((lc >> 30) & 1) << j; lc &= ~WIN_SIGN_FLAG; }
                 v[j] = lab[lc * lcs];
             }
@@ -486,7 +498,8 @@ struct SeriesSrc {
     LabelArgs lab;                       // the batch's labels: computed by extra workgroups of the fused-gather encoder launch (lab.B == 0: none)
     const double* stats;                 // standardised recipes (mshgnn_forward_series): {mean, sd} of every (window, run), [B][n_runs][2] (k_series_stats)
     int n_runs;
-    int sign;                            // the run pointers may carry RUN_PTR_SIGN (a descriptor with sign_flags): the SIGN instantiations of the encoders run
+    int sign;                            // the run pointers may carry RUN_PTR_SIGN (a descriptor with sign_flags): the SIGN instantiations of the encoders run;
+                                         // bits 8..15: K > 1 element blocks in run_ptr (n_runs each: n_runs is then always set) -- the ORBIT instantiations run
 };
 
 // The caller's sequence and windows as mshgnn_assemble_windows (mshgnn_windows.hip) gathers them; the series entry points (mshgnn.hip) fill the same structure
@@ -505,6 +518,9 @@ struct WindowArgs {
 };
 // the sign tables of a descriptor read back and checked on the host (mshgnn_windows.hip): MSHGNN_OK when there is nothing to check or the caller vouches
 int check_sign_tables(const mshgnn_window_desc* d, bool labels, hipStream_t st);
+// K of a descriptor (1: one table) and the `sign` word the kernels get (see ORBIT BATCHES above)
+inline int desc_elements(const mshgnn_window_desc* d) { const int K = (d->sign_flags >> MSHGNN_WINDOW_ELEMENTS_SHIFT) & MSHGNN_WINDOW_ELEMENTS_MASK; return K > 1 ? K : 1; }
+inline int desc_sign_word(const mshgnn_window_desc* d) { const int K = desc_elements(d); return K > 1 ? (1 | (K << MSHGNN_WINDOW_ELEMENTS_SHIFT)) : (d->sign_flags & 1); }
 
 // Per-window standardisation of one run (flexibleDataset.py:390-396): (x - mean) / sd with the unbiased estimator, in fp64, NaN -> 0.  THE arithmetic of
 // mshgnn_assemble_windows(normalize) and of the standardising series encoders (mshgnn_forward_series): both call these two functions, so the bits agree by

@@ -20,6 +20,9 @@
 // SIGN (with SERIES; a descriptor with sign_flags): the run pointers may carry RUN_PTR_SIGN -- the chunk's elements are negated per element (sign_mask8_*: a chunk's
 // two runs may differ) before the standardisation and before the window rows are written out, so a.x receives g . window.  Unsigned descriptors launch the
 // instantiations without it: the code they always ran.
+// ORBIT (with SIGN; a descriptor with K > 1 group elements, include/mshgnn.h): every window row of a tile has its own element, so the run pointers -- address and sign --
+// stop being uniform over the tile: next to srow[] each thread keeps its window rows' elements (erow[]; k_enc_x3: their run-table offsets erun[]) and fetches pa / pb per window row; how a
+// chunk divides between two runs (j, off, n0, whether a run has a source column) is the row structure, which all elements share.  Only the ORBIT instantiations pay for it.
 #pragma once
 #include "mshgnn_device.hpp"
 // the embedded layer-pack prep of each plan (EncArgs.prep): defined beside k_prep in mshgnn.hip / k_prep_x3 in mshgnn_x3.hip
@@ -44,12 +47,12 @@ struct EncRole {
     int F, nt, nkc, vb;      // nt: nodes of the type in the input rows (not the launch's list)
     const uint8_t* sg; const float* bias; int64_t pitch;
 };
-template <bool SERIES> __device__ __forceinline__ EncWg enc_role(const EncArgs& a, const SeriesSrc& ser, int tid, EncRole& r) {
+template <bool SERIES, bool ORBIT = false> __device__ __forceinline__ EncWg enc_role(const EncArgs& a, const SeriesSrc& ser, int tid, EncRole& r) {
     const int lab_blocks = SERIES ? (int)((ser.lab.B + 255) / 256) : 0;
     if constexpr (SERIES) {
         if ((int)blockIdx.x < lab_blocks) {
             const int64_t b = (int64_t)blockIdx.x * 256 + tid;
-            if (b < ser.lab.B) window_labels_one(ser.lab, b);
+            if (b < ser.lab.B) window_labels_one<ORBIT>(ser.lab, b);
             return ENC_WG_LABELS;
         }
     }
@@ -124,8 +127,9 @@ template <typename T> __device__ __forceinline__ void enc_relu_bits(const EncArg
 }
 
 // ---- k_enc_fwd: the fp32 / bf16 plans; MB = Prec<T>::ENC_MB row blocks (of 16 windows) per workgroup ----
-template <typename T, bool ALIGNED, bool SERIES = false, int SRC = 0, bool NORM = false, bool SIGN = false> __global__ __launch_bounds__(256) void k_enc_fwd(EncArgs a, SeriesSrc ser, WideSrc wsrc) {
+template <typename T, bool ALIGNED, bool SERIES = false, int SRC = 0, bool NORM = false, bool SIGN = false, bool ORBIT = false> __global__ __launch_bounds__(256) void k_enc_fwd(EncArgs a, SeriesSrc ser, WideSrc wsrc) {
     using P = Prec<T>;
+    static_assert(!ORBIT || SIGN, "a group element per window: part of the signed series gather");
     static_assert(!NORM || SERIES, "standardisation is part of the series gather");
     static_assert(!SIGN || SERIES, "signs are part of the series gather");
     static_assert(!SERIES || (sizeof(T) == 2 && ALIGNED), "the series gather is a bf16 path");
@@ -135,7 +139,7 @@ template <typename T, bool ALIGNED, bool SERIES = false, int SRC = 0, bool NORM 
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     EncRole r;
-    const EncWg role = enc_role<SERIES>(a, ser, tid, r);
+    const EncWg role = enc_role<SERIES, ORBIT>(a, ser, tid, r);
     if (role != ENC_WG_ENCODE) {
         if constexpr (sizeof(T) == 2 && ALIGNED && !SERIES) if (role == ENC_WG_PREP) prep_one<T>(a.prep, r.prep_wg * 256 + tid, false);      // (bf16 plan; see EncArgs.prep)
         return;
@@ -165,13 +169,22 @@ template <typename T, bool ALIGNED, bool SERIES = false, int SRC = 0, bool NORM 
     u32x4 vn[NORM ? MB / BPP : 1][2];
     RunStats rsa[NORM ? MB / BPP : 1], rsb[NORM ? MB / BPP : 1];
     ChunkState cs;
-    __shared__ unsigned long long rp_s[SERIES ? 16 : 1];      // SERIES: the column pointers of this node row's first 16 runs (a chunk takes its pieces from runs j, j + 1)
+    // SERIES: the column pointers of this node row's first 16 runs (a chunk takes its pieces from runs j, j + 1); ORBIT: of every element, 16 each
+    __shared__ unsigned long long rp_s[SERIES ? (ORBIT ? 16 * MSHGNN_WINDOW_MAX_ELEMENTS : 16) : 1];
     int rfirst = 0, rend = 0;      // SERIES: the node row's runs
+    int erow[ORBIT ? MB / BPP : 1];      // ORBIT: the element of this thread's window rows
+    bool neg_a[ORBIT ? MB / BPP : 1], neg_b[ORBIT ? MB / BPP : 1];      // ORBIT: the signs of the chunk in flight per window row (cs.neg_a / neg_b otherwise)
     if constexpr (SERIES) {
 #pragma unroll
-        for (int mi = 0; mi < MB / BPP; ++mi) srow[mi] = (int)ser.starts[min(w0 + (mi * BPP + sub) * P::ROWS + r0, a.B - 1)];
+        for (int mi = 0; mi < MB / BPP; ++mi) {
+            const int64_t sw = ser.starts[min(w0 + (mi * BPP + sub) * P::ROWS + r0, a.B - 1)];
+            srow[mi] = (int)(ORBIT ? start_row(sw) : sw);
+            if constexpr (ORBIT) erow[mi] = start_element(sw, orbit_elements(ser.sign));
+        }
         rfirst = ser.rows[2 * (ser.row0[t] + node)]; rend = ser.rows[2 * (ser.row0[t] + node) + 1];
-        if (tid < 16) rp_s[tid] = rfirst + tid < rend ? ser.run_ptr[rfirst + tid] : 0ull;
+        if constexpr (ORBIT) {
+            if (tid < 16 * orbit_elements(ser.sign)) rp_s[tid] = rfirst + (tid & 15) < rend ? ser.run_ptr[(size_t)(tid >> 4) * ser.n_runs + rfirst + (tid & 15)] : 0ull;
+        } else if (tid < 16) rp_s[tid] = rfirst + tid < rend ? ser.run_ptr[rfirst + tid] : 0ull;
         __syncthreads();
     }
     auto fetch = [&](int kc) {
@@ -179,11 +192,23 @@ template <typename T, bool ALIGNED, bool SERIES = false, int SRC = 0, bool NORM 
         const int nvalid = min(P::EPC, F - k0);
         if constexpr (SERIES) {
             // (runs past the 16th -- a node row of more than 16 T-long variables -- come from the global table: a dependent load, rare recipes only)
-            const SeriesSplit s = series_split<SIGN>(k0, nvalid, ser.T, [&](int jj) -> unsigned long long { return jj < 16 ? rp_s[jj] : (rfirst + jj < rend ? ser.run_ptr[rfirst + jj] : 0ull); });
+            auto run_ptr_of = [&](int e, int jj) -> unsigned long long {
+                if constexpr (ORBIT) return jj < 16 ? rp_s[16 * e + jj] : (rfirst + jj < rend ? ser.run_ptr[(size_t)e * ser.n_runs + rfirst + jj] : 0ull);
+                else return jj < 16 ? rp_s[jj] : (rfirst + jj < rend ? ser.run_ptr[rfirst + jj] : 0ull);
+            };
+            // (ORBIT: element 0's split gives the chunk's geometry and which runs have a source column -- the row structure every element shares)
+            const SeriesSplit s = series_split<SIGN>(k0, nvalid, ser.T, [&](int jj) -> unsigned long long { return run_ptr_of(0, jj); });
             cs = s.st;
             if constexpr (NORM) {
 #pragma unroll
                 for (int mi = 0; mi < MB / BPP; ++mi) {
+                    if constexpr (ORBIT) {
+                        const SeriesSplit se = series_split<SIGN>(k0, nvalid, ser.T, [&](int jj) -> unsigned long long { return run_ptr_of(erow[mi], jj); });
+                        neg_a[mi] = se.st.neg_a; neg_b[mi] = se.st.neg_b;
+                        const double* sp2 = ser.stats + ((size_t)min(w0 + (mi * BPP + sub) * P::ROWS + r0, a.B - 1) * ser.n_runs + rfirst + se.j) * 2;
+                        series_fetch_f32<true, false>(se, nvalid > 0, srow[mi], sp2, vn[mi][0], vn[mi][1], rsa[mi], rsb[mi]);
+                        continue;
+                    }
                     // (the window of this thread's row: rows past the batch repeat the last window, as srow does)
                     const double* sp2 = ser.stats + ((size_t)min(w0 + (mi * BPP + sub) * P::ROWS + r0, a.B - 1) * ser.n_runs + rfirst + s.j) * 2;
                     series_fetch_f32<true, false>(s, nvalid > 0, srow[mi], sp2, vn[mi][0], vn[mi][1], rsa[mi], rsb[mi]);
@@ -193,11 +218,16 @@ template <typename T, bool ALIGNED, bool SERIES = false, int SRC = 0, bool NORM 
             const u32x4 ones = u32x4{0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u};      // the constant-1 run (bf16 1.0)
 #pragma unroll
             for (int mi = 0; mi < MB / BPP; ++mi) {
+                unsigned long long pa = s.pa, pb = s.pb;
+                if constexpr (ORBIT) {      // this window row's own run pointers and signs
+                    const SeriesSplit se = series_split<SIGN>(k0, nvalid, ser.T, [&](int jj) -> unsigned long long { return run_ptr_of(erow[mi], jj); });
+                    pa = se.pa; pb = se.pb; neg_a[mi] = se.st.neg_a; neg_b[mi] = se.st.neg_b;
+                }
                 u32x4 va = nvalid > 0 ? ones : u32x4{0, 0, 0, 0};
-                if (s.pa) va = *reinterpret_cast<const u32x4*>(reinterpret_cast<const T*>(s.pa) + srow[mi] + s.off);       // 2-byte aligned: served at full rate
+                if (pa) va = *reinterpret_cast<const u32x4*>(reinterpret_cast<const T*>(pa) + srow[mi] + s.off);       // 2-byte aligned: served at full rate
                 if (s.second) {
                     u32x4 vb2 = ones;
-                    if (s.pb) vb2 = *reinterpret_cast<const u32x4*>(reinterpret_cast<const T*>(s.pb) + srow[mi]);
+                    if (pb) vb2 = *reinterpret_cast<const u32x4*>(reinterpret_cast<const T*>(pb) + srow[mi]);
                     va = splice8(va, vb2, s.st.n0);
                 }
                 v[mi][0] = va;
@@ -235,13 +265,15 @@ template <typename T, bool ALIGNED, bool SERIES = false, int SRC = 0, bool NORM 
         const u32x4 sx = sign_xor<T>(r.sg + kc * H + c * P::EPC);   // apply_symmetry: +-1 mask as a sign-bit XOR
         const int nv = F - (kc * H + c * P::EPC);                  // valid elements of this thread's chunk (pad columns dropped)
         u32x4 gm = u32x4{0, 0, 0, 0}, gm0 = gm, gm1 = gm;          // SIGN: the chunk's per-element sign masks (bf16 elements; NORM: the fp32 elements it standardises)
-        if constexpr (SIGN && NORM) sign_mask8_f32(cs.n0, cs.neg_a, cs.neg_b, gm0, gm1);
-        else if constexpr (SIGN) gm = sign_mask8_bf16(cs.n0, cs.neg_a, cs.neg_b);
+        if constexpr (SIGN && NORM && !ORBIT) sign_mask8_f32(cs.n0, cs.neg_a, cs.neg_b, gm0, gm1);
+        else if constexpr (SIGN && !ORBIT) gm = sign_mask8_bf16(cs.n0, cs.neg_a, cs.neg_b);
         __syncthreads();   // previous chunk's MFMAs are done reading LDS
 #pragma unroll
         for (int mi = 0; mi < MB / BPP; ++mi)
 #pragma unroll
             for (int it = 0; it < NIT; ++it) {
+                if constexpr (ORBIT && NORM) sign_mask8_f32(cs.n0, neg_a[mi], neg_b[mi], gm0, gm1);      // (per window row)
+                else if constexpr (ORBIT) gm = sign_mask8_bf16(cs.n0, neg_a[mi], neg_b[mi]);
                 u32x4 raw;
                 if constexpr (SRC > 0) {      // fp64 / fp32 -> (fp32 ->) bf16, round to nearest even twice as torch's .to(bfloat16) does; elements past the row: zero
                     f32x4 lo4, hi4;
@@ -297,7 +329,8 @@ template <typename T, bool ALIGNED, bool SERIES = false, int SRC = 0, bool NORM 
 }
 
 // ---- k_enc_x3: the split plan, from fp32 inputs; one workgroup = 64 windows of ONE node, LDS hi blocks [0, 4), lo blocks [4, 8) ----
-template <bool ALIGNED, bool SERIES = false, int SRC = 0, bool NORM = false, bool SIGN = false> __global__ __launch_bounds__(256) void k_enc_x3(EncArgs a, int n_img, SeriesSrc ser, WideSrc wsrc) {
+template <bool ALIGNED, bool SERIES = false, int SRC = 0, bool NORM = false, bool SIGN = false, bool ORBIT = false> __global__ __launch_bounds__(256) void k_enc_x3(EncArgs a, int n_img, SeriesSrc ser, WideSrc wsrc) {
+    static_assert(!ORBIT || SIGN, "a group element per window: part of the signed series gather");
     static_assert(!NORM || SERIES, "standardisation is part of the series gather");
     static_assert(!SIGN || SERIES, "signs are part of the series gather");
     static_assert(!SERIES || ALIGNED, "the series gather writes aligned window buffers");
@@ -307,7 +340,7 @@ template <bool ALIGNED, bool SERIES = false, int SRC = 0, bool NORM = false, boo
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     EncRole r;
-    const EncWg role = enc_role<SERIES>(a, ser, tid, r);
+    const EncWg role = enc_role<SERIES, ORBIT>(a, ser, tid, r);
     if (role != ENC_WG_ENCODE) {
         if constexpr (ALIGNED && !SERIES) if (role == ENC_WG_PREP) prep_one_x3(a.prep, r.prep_wg * 256 + tid, false);
         return;
@@ -333,21 +366,33 @@ template <bool ALIGNED, bool SERIES = false, int SRC = 0, bool NORM = false, boo
     int srow[SERIES ? MB : 1]; int rfirst = 0;  // SERIES: first series row of this thread's window rows, the node row's first run
     RunStats rsa[NORM ? MB : 1], rsb[NORM ? MB : 1];      // NORM: the statistics of the chunk's two runs per window
     ChunkState cs;
+    int erun[ORBIT ? MB : 1];      // ORBIT: this thread's window rows' offsets into the run-pointer table (element x n_runs)
+    bool neg_a[ORBIT ? MB : 1], neg_b[ORBIT ? MB : 1];      // ORBIT: the signs of the chunk in flight per window row (cs.neg_a / neg_b otherwise)
     if constexpr (SERIES) {
 #pragma unroll
-        for (int m = 0; m < MB; ++m) srow[m] = (int)ser.starts[min(w0 + m * P::ROWS + r0, a.B - 1)];
+        for (int m = 0; m < MB; ++m) {
+            const int64_t sw = ser.starts[min(w0 + m * P::ROWS + r0, a.B - 1)];
+            srow[m] = (int)(ORBIT ? start_row(sw) : sw);
+            if constexpr (ORBIT) erun[m] = start_element(sw, orbit_elements(ser.sign)) * ser.n_runs;
+        }
         rfirst = ser.rows[2 * (ser.row0[t] + node)];
     }
     auto fetch = [&](int kc) {
         const int k0 = kc * H + c * 8;
         const int nv = F - k0;
         if constexpr (SERIES) {
+            // (ORBIT: element 0's split gives the chunk's geometry and which runs have a source column -- the row structure every element shares)
             const SeriesSplit s = series_split<SIGN>(k0, min(nv, 8), ser.T, [&](int jj) -> unsigned long long { return ser.run_ptr[rfirst + jj]; });
             cs = s.st;
 #pragma unroll
             for (int m = 0; m < MB; ++m) {
                 // (rows past the batch repeat the last window, as srow does)
                 const double* sp2 = NORM ? ser.stats + ((size_t)min(w0 + m * P::ROWS + r0, a.B - 1) * ser.n_runs + rfirst + s.j) * 2 : nullptr;
+                if constexpr (ORBIT) {      // this window row's own run pointers and signs
+                    const SeriesSplit se = series_split<SIGN>(k0, min(nv, 8), ser.T, [&](int jj) -> unsigned long long { return ser.run_ptr[erun[m] + rfirst + jj]; });
+                    neg_a[m] = se.st.neg_a; neg_b[m] = se.st.neg_b;
+                    series_fetch_f32<NORM, true>(se, nv > 0, srow[m], sp2, v[m][0], v[m][1], rsa[NORM ? m : 0], rsb[NORM ? m : 0]);
+                } else
                 series_fetch_f32<NORM, true>(s, nv > 0, srow[m], sp2, v[m][0], v[m][1], rsa[NORM ? m : 0], rsb[NORM ? m : 0]);
             }
             return;
@@ -385,10 +430,11 @@ template <bool ALIGNED, bool SERIES = false, int SRC = 0, bool NORM = false, boo
         const u32x4 sxa = sign_xor<float>(r.sg + kc * H + c * 8), sxb = sign_xor<float>(r.sg + kc * H + c * 8 + 4);   // apply_symmetry: +-1 mask as a sign-bit XOR
         const int nv = F - (kc * H + c * 8);
         u32x4 gm0 = u32x4{0, 0, 0, 0}, gm1 = gm0;      // SIGN: the chunk's per-element sign masks
-        if constexpr (SIGN) sign_mask8_f32(cs.n0, cs.neg_a, cs.neg_b, gm0, gm1);
+        if constexpr (SIGN && !ORBIT) sign_mask8_f32(cs.n0, cs.neg_a, cs.neg_b, gm0, gm1);
         __syncthreads();   // previous chunk's MFMAs are done reading LDS
 #pragma unroll
         for (int m = 0; m < MB; ++m) {
+            if constexpr (ORBIT) sign_mask8_f32(cs.n0, neg_a[m], neg_b[m], gm0, gm1);      // (per window row)
             u32x4 fa = v[m][0], fb = v[m][1];
             if constexpr (SRC > 0) {      // fp64 -> fp32 (round to nearest even, as torch's .float()), or the fp32 units as they are; elements past the row: zero
                 f32x4 lo4, hi4;

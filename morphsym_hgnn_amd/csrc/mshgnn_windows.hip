@@ -16,15 +16,18 @@ constexpr int WIN_ROW_RUNS = 8;          // runs per node row handled with all l
 // one WORKGROUP per window, its 4 waves take the node rows round-robin.  Lane r resolves run r ONCE (source pointer, destination
 // offset, length) and the waves fetch those with v_readlane, so there is no dependent descriptor load per run; every run
 // of a row is a contiguous stretch of a column-major series, read coalesced with all of the row's loads in flight.
-template <typename T, int NSET> __global__ __launch_bounds__(256) void k_assemble_windows(WindowArgs a) {
+// ORBIT (with a.sign's K > 1): the window's element picks its block of `runs`; the row structure (a.rows, lengths, destinations) is every element's.
+template <typename T, int NSET, bool ORBIT = false> __global__ __launch_bounds__(256) void k_assemble_windows(WindowArgs a) {
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t b = blockIdx.x;
-    const int64_t start = a.starts[b];
+    const int64_t start = ORBIT ? start_row(a.starts[b]) : a.starts[b];
+    const int* runs = a.runs;
+    if constexpr (ORBIT) runs += (size_t)start_element(a.starts[b], orbit_elements(a.sign)) * a.n_runs * 5;
     // lane r & 63 of register set r >> 6 <- run r (n_runs <= 64 NSET, checked by the host)
     int v_lo[NSET], v_hi[NSET], v_doff[NSET], v_len[NSET], v_t[NSET];
 #pragma unroll
     for (int set = 0; set < NSET; ++set) {
-        const int* run = a.runs + (size_t)min(lane + 64 * set, a.n_runs - 1) * 5;
+        const int* run = (ORBIT ? runs : a.runs) + (size_t)min(lane + 64 * set, a.n_runs - 1) * 5;
         const int t = run[0], node = run[1], f0 = run[2];
         bool neg;
         const int sc = run_source(run[3], a.sign, neg);
@@ -103,17 +106,19 @@ template <typename T, int NSET> __global__ __launch_bounds__(256) void k_assembl
 // window are independent, so every load of the window is in flight at once.  The general kernel above writes 4 bytes per lane and walks a row's
 // runs in turn: 0.12 ms for 8192 A1 windows against 0.03-0.04 ms here.  Pad columns inside a row's last chunk are written as zeros.
 constexpr int WIN_MAX_ROWS = 64;
-template <typename T> __global__ __launch_bounds__(256) void k_assemble_windows_fast(WindowArgs a) {
+template <typename T, bool ORBIT = false> __global__ __launch_bounds__(256) void k_assemble_windows_fast(WindowArgs a) {
     constexpr int EPC = 16 / (int)sizeof(T);
     __shared__ unsigned long long s_src[WIN_MAX_RUNS];                    // source pointer of run r at this window's first step (0: the constant 1)
     __shared__ int s_first[WIN_MAX_ROWS + 1];                             // chunk prefix per node row
     __shared__ int s_run0[WIN_MAX_ROWS], s_len[WIN_MAX_ROWS], s_width[WIN_MAX_ROWS];
     __shared__ unsigned long long s_dst[WIN_MAX_ROWS];                    // destination of the row's first element
     const int tid = threadIdx.x;
-    const int64_t b = blockIdx.x, start = a.starts[b];
+    const int64_t b = blockIdx.x, start = ORBIT ? start_row(a.starts[b]) : a.starts[b];
     if (tid < a.n_runs) {
         bool neg;
-        const int sc = run_source(a.runs[(size_t)tid * 5 + 3], a.sign, neg);
+        // (ORBIT: the source word of the window's element's block; the row structure read below is element 0's, which the host check made every element's)
+        const size_t rblk = ORBIT ? (size_t)start_element(a.starts[b], orbit_elements(a.sign)) * a.n_runs : 0;
+        const int sc = run_source(a.runs[(rblk + tid) * 5 + 3], a.sign, neg);
         const float* sp = nullptr;
 #pragma unroll
         for (int k = 0; k < WIN_MAX_SRC; ++k) if (sc >= 0 && (sc >> 8) == k) sp = a.src[k] + (size_t)(sc & 0xff) * a.src_cstride[k] + start;
@@ -181,29 +186,44 @@ __global__ void k_window_labels(WindowArgs a) {
     const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (b < a.B) window_labels_one(label_args_of(a, nullptr), b);
 }
+__global__ void k_window_labels_orbit(WindowArgs a) {      // K > 1: the label columns of each window's own element
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < a.B) window_labels_one<true>(label_args_of(a, nullptr), b);
+}
 
 // The sign tables of a descriptor (sign_flags bit 0) are the caller's statement about DEVICE memory; before the first launch that reads them they are copied back
 // once and checked, afterwards the caller vouches (bit 1).  What is refused: see MSHGNN_WINDOW_SIGN_FLAG in include/mshgnn.h.
+// Orbit descriptors (sign_flags bits 8..15 = K > 1): all K element blocks are read back; besides every block's sign words, what makes a per-window choice of block safe
+// is checked -- K <= 8, the row structure {type, node, first feature, length} of every run equal to element 0's, constant-1 runs constant-1 in every element.
 int check_sign_tables(const mshgnn_window_desc* d, bool labels, hipStream_t st) {
+    const int K = desc_elements(d);
+    if (K > 1 && !(d->sign_flags & 1)) return set_err(MSHGNN_EINVAL, "window descriptor: K > 1 group elements imply sign_flags bit 0");
+    if (K > MSHGNN_WINDOW_MAX_ELEMENTS) return set_err(MSHGNN_EINVAL, "window descriptor: " + std::to_string(K) + " group elements, at most " + std::to_string(MSHGNN_WINDOW_MAX_ELEMENTS) + " are supported");
     if (!(d->sign_flags & 1) || (d->sign_flags & 2)) return MSHGNN_OK;
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (st && hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
         return set_err(MSHGNN_EINVAL, "sign tables must be checked by a call outside a stream capture first (then vouch with sign_flags bit 1)");
     if (d->n_runs < 1 || d->n_runs > WIN_MAX_RUNS || !d->runs) return set_err(MSHGNN_EINVAL, "bad window descriptor");
-    std::vector<int32_t> runs((size_t)d->n_runs * 5), lab(labels && d->n_label > 0 ? (size_t)d->n_label : 0);
+    std::vector<int32_t> runs((size_t)K * d->n_runs * 5), lab(labels && d->n_label > 0 ? (size_t)K * d->n_label : 0);
     HIPCHK(hipMemcpy(runs.data(), d->runs, runs.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
     if (!lab.empty()) {
         if (!d->label_cols) return set_err(MSHGNN_EINVAL, "bad label description");
         HIPCHK(hipMemcpy(lab.data(), d->label_cols, lab.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
     }
-    for (int r = 0; r < d->n_runs; ++r) {
-        const int32_t w = runs[(size_t)r * 5 + 3];
-        if (w == -1) continue;
-        if (w < 0) return set_err(MSHGNN_EINVAL, "window run " + std::to_string(r) + ": a constant-1 run (source word -1) cannot carry a sign");
-        if (((w & ~MSHGNN_WINDOW_SIGN_FLAG) >> 8) >= d->n_src) return set_err(MSHGNN_EINVAL, "window run " + std::to_string(r) + ": source out of range");
-    }
+    for (int e = 0; e < K; ++e)
+        for (int r = 0; r < d->n_runs; ++r) {
+            const int32_t* run = &runs[((size_t)e * d->n_runs + r) * 5], * run0 = &runs[(size_t)r * 5];
+            const std::string who = (K > 1 ? "element " + std::to_string(e) + ", " : std::string()) + "window run " + std::to_string(r);
+            if (run[0] != run0[0] || run[1] != run0[1] || run[2] != run0[2] || run[4] != run0[4])
+                return set_err(MSHGNN_EINVAL, who + ": {type, node, first feature, length} differs from element 0's");
+            const int32_t w = run[3];
+            if ((w == -1) != (run0[3] == -1)) return set_err(MSHGNN_EINVAL, who + ": a constant-1 run must be constant-1 in every element");
+            if (w == -1) continue;
+            if (w < 0) return set_err(MSHGNN_EINVAL, who + ": a constant-1 run (source word -1) cannot carry a sign");
+            if (((w & ~MSHGNN_WINDOW_SIGN_FLAG) >> 8) >= d->n_src) return set_err(MSHGNN_EINVAL, who + ": source out of range");
+        }
     for (size_t k = 0; k < lab.size(); ++k)
-        if (lab[k] < 0 || (lab[k] & ~MSHGNN_WINDOW_SIGN_FLAG) >= 256) return set_err(MSHGNN_EINVAL, "label column " + std::to_string(k) + ": column part out of range [0, 256)");
+        if (lab[k] < 0 || (lab[k] & ~MSHGNN_WINDOW_SIGN_FLAG) >= 256) return set_err(MSHGNN_EINVAL, "label column " + std::to_string(k % (size_t)d->n_label) + ": column part out of range [0, 256)");
     return MSHGNN_OK;
 }
 
@@ -230,7 +250,8 @@ extern "C" int mshgnn_assemble_windows(const mshgnn_window_desc* d, const float*
     if (d->history > 256) return set_err(MSHGNN_EUNSUPPORTED, "history longer than 256 steps is not supported by this build");
     a.runs = d->runs; a.n_runs = d->n_runs; a.rows = d->rows; a.n_rows = d->n_rows; a.starts = starts; a.B = batch; a.T = d->history; a.normalize = d->normalize;
     a.label_cols = d->label_cols; a.n_label = d->n_label; a.label_src = d->label_src; a.label_rotate = d->label_rotate; a.quat_src = d->quat_src;
-    a.y = y_out; a.quat = quat_out; a.sign = d->sign_flags & 1;
+    a.y = y_out; a.quat = quat_out; a.sign = desc_sign_word(d);
+    const bool orbit = desc_elements(d) > 1;
     hipStream_t st = (hipStream_t)stream;
     if (const int rc = check_sign_tables(d, d->n_label > 0, st)) return rc;
     if (d->n_runs > 128) return set_err(MSHGNN_EUNSUPPORTED, "more than 128 feature runs per window are not supported by this build");
@@ -241,7 +262,18 @@ extern "C" int mshgnn_assemble_windows(const mshgnn_window_desc* d, const float*
         const int epc = f32 ? 4 : 8;
         if (((uintptr_t)x_out[t] & 15) || x_pitch[t] % epc || x_pitch[t] < (d->type_width[t] + epc - 1) / epc * epc) fast = false;
     }
-    if (fast) {
+    if (orbit) {      // a group element per window: the ORBIT instantiations of the same kernels
+        if (fast) {
+            if (f32) hipLaunchKernelGGL((k_assemble_windows_fast<float, true>), dim3((unsigned)batch), dim3(256), 0, st, a);
+            else hipLaunchKernelGGL((k_assemble_windows_fast<__bf16, true>), dim3((unsigned)batch), dim3(256), 0, st, a);
+        } else if (f32) {
+            if (d->n_runs <= 64) hipLaunchKernelGGL((k_assemble_windows<float, 1, true>), dim3((unsigned)batch), dim3(256), 0, st, a);
+            else hipLaunchKernelGGL((k_assemble_windows<float, 2, true>), dim3((unsigned)batch), dim3(256), 0, st, a);
+        } else {
+            if (d->n_runs <= 64) hipLaunchKernelGGL((k_assemble_windows<__bf16, 1, true>), dim3((unsigned)batch), dim3(256), 0, st, a);
+            else hipLaunchKernelGGL((k_assemble_windows<__bf16, 2, true>), dim3((unsigned)batch), dim3(256), 0, st, a);
+        }
+    } else if (fast) {
         if (f32) hipLaunchKernelGGL(k_assemble_windows_fast<float>, dim3((unsigned)batch), dim3(256), 0, st, a);
         else hipLaunchKernelGGL(k_assemble_windows_fast<__bf16>, dim3((unsigned)batch), dim3(256), 0, st, a);
     } else if (f32) {
@@ -251,8 +283,10 @@ extern "C" int mshgnn_assemble_windows(const mshgnn_window_desc* d, const float*
         if (d->n_runs <= 64) hipLaunchKernelGGL((k_assemble_windows<__bf16, 1>), dim3((unsigned)batch), dim3(256), 0, st, a);
         else hipLaunchKernelGGL((k_assemble_windows<__bf16, 2>), dim3((unsigned)batch), dim3(256), 0, st, a);
     }
-    if (d->n_label > 0 || (quat_out && d->quat_src >= 0))
-        hipLaunchKernelGGL(k_window_labels, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, st, a);
+    if (d->n_label > 0 || (quat_out && d->quat_src >= 0)) {
+        if (orbit) hipLaunchKernelGGL(k_window_labels_orbit, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL(k_window_labels, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, st, a);
+    }
     HIPCHK(hipGetLastError());
     return MSHGNN_OK;
 }

@@ -460,7 +460,10 @@ int x3_forward(const mshgnn_plan* p, StepCall& c) {
         if ((rc = pick_enc_route(c, a, tr, enc_grid, route))) return rc;
         unsigned enc_lds = tr.enc_lds;
         auto enc = [&](auto kernel, const SeriesSrc& ser, const WideSrc& wsrc) { hipLaunchKernelGGL(kernel, dim3(enc_grid), dim3(256), enc_lds, st, a, hp.n_img, ser, wsrc); };
-        if (route == EncRoute::SERIES_STD && c.series->sign) enc(k_enc_x3<true, true, 0, true, true>, *c.series, WideSrc{});
+        const bool orbit = (route == EncRoute::SERIES_STD || route == EncRoute::SERIES) && (c.series->sign >> MSHGNN_WINDOW_ELEMENTS_SHIFT) != 0;      // K > 1: a group element per window
+        if (route == EncRoute::SERIES_STD && orbit) enc(k_enc_x3<true, true, 0, true, true, true>, *c.series, WideSrc{});
+        else if (route == EncRoute::SERIES && orbit) enc(k_enc_x3<true, true, 0, false, true, true>, *c.series, WideSrc{});
+        else if (route == EncRoute::SERIES_STD && c.series->sign) enc(k_enc_x3<true, true, 0, true, true>, *c.series, WideSrc{});
         else if (route == EncRoute::SERIES && c.series->sign) enc(k_enc_x3<true, true, 0, false, true>, *c.series, WideSrc{});
         else if (route == EncRoute::SERIES_STD) enc(k_enc_x3<true, true, 0, true>, *c.series, WideSrc{});
         else if (route == EncRoute::SERIES) enc(k_enc_x3<true, true>, *c.series, WideSrc{});

@@ -764,8 +764,8 @@ class Engine:
     def _vouch_sign_tables(store):
         """A descriptor whose tables carry sign flags (a `transformed` store; mshgnn_window_desc.sign_flags bit 0) has them read back and checked by the
         library on its first call; the call succeeded, so later calls vouch for them (bit 1: no read-back, capturable)."""
-        if store.desc.sign_flags == 1:
-            store.desc.sign_flags = 3
+        if store.desc.sign_flags & 3 == 1:
+            store.desc.sign_flags |= 2
 
     def forward_series(self, store, starts: torch.Tensor, params_flat: torch.Tensor, out: Optional[torch.Tensor] = None, labels: bool = True):
         """Evaluation straight from a `windows.SequenceStore` (mshgnn_forward_series): `store.assemble(starts)` + `forward(..., training=False)` in one

@@ -96,6 +96,57 @@ class WindowRecipe:
         w = sum(len(cols[0]) * self.history for _, cols in self.variables.get(t, []))
         return w if w > 0 else 1
 
+    def tables(self, names: Optional[Sequence[str]] = None, n_columns: Optional[Dict[str, int]] = None) -> Tuple[List[List[int]], List[List[int]], List[int], bool]:
+        """The tables of include/mshgnn.h's mshgnn_window_desc for this recipe, on the host: (runs [n_runs][5], rows [n_rows][2], label_cols, signed).
+        names: the order of the source arrays (None: `series()`); n_columns: series name -> its number of columns, checked when given (a store knows them).
+        A negated run / label carries SIGN_FLAG in its source word / column; `signed` says whether any does."""
+        names = list(names) if names is not None else self.series()
+        sidx = {s: i for i, s in enumerate(names)}
+        def ncol_of(s):
+            return min(int(n_columns[s]), 256) if n_columns is not None else 256
+        runs, rows = [], []
+        signed = False
+        for ti, t in enumerate(self.node_types):
+            vars_ = self.variables.get(t, [])
+            if not vars_:
+                for n in range(self.num_nodes[t]):
+                    rows.append([len(runs), len(runs) + 1]); runs.append([ti, n, 0, -1, 1])
+                continue
+            vsig = (self.variable_signs or {}).get(t)
+            for n in range(self.num_nodes[t]):
+                f = 0
+                r_begin = len(runs)
+                for vi, (s, cols) in enumerate(vars_):
+                    for ai, c in enumerate(cols[n]):
+                        if not 0 <= c < ncol_of(s):
+                            raise ValueError(f"column {c} of series '{s}' out of range")
+                        sg = int(vsig[vi][n][ai]) if vsig else 1
+                        if sg not in (-1, 1):
+                            raise ValueError(f"variable_signs of series '{s}': {sg} is not +-1")
+                        signed |= sg < 0
+                        runs.append([ti, n, f, (sidx[s] << 8) | c | (SIGN_FLAG if sg < 0 else 0), self.history])
+                        f += self.history
+                rows.append([r_begin, len(runs)])
+        lab = list(self.label_cols or [0])
+        if self.label_cols:
+            for c in lab:
+                if not 0 <= c < ncol_of(self.label_series):
+                    raise ValueError(f"label column {c} of series '{self.label_series}' out of range")
+        if self.label_signs is not None and self.label_cols:
+            if len(self.label_signs) != len(self.label_cols) or any(int(x) not in (-1, 1) for x in self.label_signs):
+                raise ValueError("label_signs: one +-1 per label column")
+            signed |= any(int(x) < 0 for x in self.label_signs)
+            lab = [c | (SIGN_FLAG if int(x) < 0 else 0) for c, x in zip(lab, self.label_signs)]
+        return runs, rows, lab, signed
+
+    def orbit(self, group: "GroupAction", operators: Sequence[str] = ("gs", "gt", "gr"), mode: str = "MorphSym", identity: bool = True) -> List["WindowRecipe"]:
+        """The recipes of an orbit batch's group elements, in element order: this recipe (identity=True), then `transformed(op)` for every operator --
+        the datasets of the reference's ConcatDataset([ds, ds_gs, ds_gt, ds_gr]).  1 to MAX_ELEMENTS elements."""
+        recipes = ([self] if identity else []) + [self.transformed(op, group, mode) for op in operators]
+        if not 1 <= len(recipes) <= MAX_ELEMENTS:
+            raise ValueError(f"an orbit has 1 to {MAX_ELEMENTS} group elements, not {len(recipes)}")
+        return recipes
+
     def series(self) -> List[str]:
         names = []
         for t in self.node_types:
@@ -106,6 +157,43 @@ class WindowRecipe:
             if s is not None and s not in names:
                 names.append(s)
         return names
+
+
+SIGN_FLAG = 1 << 30          # MSHGNN_WINDOW_SIGN_FLAG: a run's source word / a label column carries a minus sign
+MAX_ELEMENTS = 8             # MSHGNN_WINDOW_MAX_ELEMENTS: group elements of an orbit descriptor
+ELEMENT_SHIFT = 56           # MSHGNN_START_ELEMENT_SHIFT: a packed start = element << 56 | row
+ROW_MASK = (1 << ELEMENT_SHIFT) - 1
+
+
+def stack_orbit_tables(tables: Sequence[Tuple[List[List[int]], List[List[int]], List[int]]]) -> Tuple[List[List[List[int]]], List[List[int]], List[List[int]]]:
+    """The element-major tables of an orbit descriptor from the (runs, rows, label_cols) of its K elements (`WindowRecipe.tables`): (runs [K][n_runs][5],
+    rows, label_cols [K][n_label]).  All elements share their row structure, which is what lets a window pick its element inside the gathers; refused
+    here as the library's checking call refuses it: more than MAX_ELEMENTS elements, an element whose rows or whose {type, node, first feature, length}
+    of any run differ from element 0's, a constant-1 run (source word -1) that is not constant-1 in every element."""
+    K = len(tables)
+    if not 1 <= K <= MAX_ELEMENTS:
+        raise ValueError(f"an orbit has 1 to {MAX_ELEMENTS} group elements, not {K}")
+    runs0, rows0, lab0 = tables[0]
+    for e, (runs, rows, lab) in enumerate(tables):
+        if [list(r) for r in rows] != [list(r) for r in rows0] or len(runs) != len(runs0):
+            raise ValueError(f"orbit element {e}: its node rows differ from element 0's")
+        if len(lab) != len(lab0):
+            raise ValueError(f"orbit element {e}: {len(lab)} label columns, element 0 has {len(lab0)}")
+        for r, (a, b) in enumerate(zip(runs, runs0)):
+            if [a[0], a[1], a[2], a[4]] != [b[0], b[1], b[2], b[4]]:
+                raise ValueError(f"orbit element {e}, run {r}: (type, node, first feature, length) = {[a[0], a[1], a[2], a[4]]} differs from element 0's {[b[0], b[1], b[2], b[4]]}")
+            if (a[3] == -1) != (b[3] == -1) or (a[3] < 0 and a[3] != -1):
+                raise ValueError(f"orbit element {e}, run {r}: a constant-1 run must be the constant-1 run (source word -1) in every element")
+    return [[list(r) for r in t[0]] for t in tables], [list(r) for r in rows0], [list(t[2]) for t in tables]
+
+
+def orbit_index_split(index: int, n_windows: int, n_elements: int) -> Tuple[int, int]:
+    """(element, window) of index `index` of an orbit view over n_windows windows: element index // n, window index % n -- the order of
+    ConcatDataset([view, view_gs, view_gt, view_gr]).  IndexError outside [0, n_elements * n_windows)."""
+    i = int(index)
+    if not 0 <= i < n_elements * n_windows:
+        raise IndexError(f"dataset index {i} out of range [0, {n_elements * n_windows})")
+    return i // n_windows, i % n_windows
 
 
 @dataclass
@@ -251,50 +339,29 @@ class SequenceStore:
         self._fast = bool(fast)
         self._describe(recipe)
 
-    SIGN_FLAG = 1 << 30      # MSHGNN_WINDOW_SIGN_FLAG: a run's source word / a label column carries a minus sign
+    SIGN_FLAG = SIGN_FLAG
 
-    def _describe(self, recipe: WindowRecipe) -> None:
-        """The device tables, the descriptor and the per-store caches of `recipe` over the series already resident (the constructor; `transformed`)."""
+    def _describe(self, recipe: WindowRecipe, elements: Optional[Sequence[WindowRecipe]] = None) -> None:
+        """The device tables, the descriptor and the per-store caches of `recipe` over the series already resident (the constructor; `transformed`).
+        elements (`orbit`): the recipes of the K group elements, `recipe` the first of them -- their tables are stacked element-major."""
         self.recipe = recipe
         sidx = {s: i for i, s in enumerate(self.names)}
-        runs, rows = [], []
-        signed = False
-        for ti, t in enumerate(recipe.node_types):
-            vars_ = recipe.variables.get(t, [])
-            if not vars_:
-                for n in range(recipe.num_nodes[t]):
-                    rows.append([len(runs), len(runs) + 1]); runs.append([ti, n, 0, -1, 1])
-                continue
-            vsig = (recipe.variable_signs or {}).get(t)
-            for n in range(recipe.num_nodes[t]):
-                f = 0
-                r_begin = len(runs)
-                for vi, (s, cols) in enumerate(vars_):
-                    ncol = self.series[sidx[s]].shape[0]
-                    for ai, c in enumerate(cols[n]):
-                        if not 0 <= c < min(ncol, 256):
-                            raise ValueError(f"column {c} of series '{s}' out of range")
-                        sg = int(vsig[vi][n][ai]) if vsig else 1
-                        if sg not in (-1, 1):
-                            raise ValueError(f"variable_signs of series '{s}': {sg} is not +-1")
-                        signed |= sg < 0
-                        runs.append([ti, n, f, (sidx[s] << 8) | c | (self.SIGN_FLAG if sg < 0 else 0), recipe.history])
-                        f += recipe.history
-                rows.append([r_begin, len(runs)])
-        lab = list(recipe.label_cols or [0])
-        if recipe.label_cols:
-            ncol = self.series[sidx[recipe.label_series]].shape[0]
-            for c in lab:
-                if not 0 <= c < min(ncol, 256):
-                    raise ValueError(f"label column {c} of series '{recipe.label_series}' out of range")
-        if recipe.label_signs is not None and recipe.label_cols:
-            if len(recipe.label_signs) != len(recipe.label_cols) or any(int(x) not in (-1, 1) for x in recipe.label_signs):
-                raise ValueError("label_signs: one +-1 per label column")
-            signed |= any(int(x) < 0 for x in recipe.label_signs)
-            lab = [c | (self.SIGN_FLAG if int(x) < 0 else 0) for c, x in zip(lab, recipe.label_signs)]
-        self.runs = torch.tensor(runs, dtype=torch.int32, device=self.device)
+        ncols = {s: int(self.series[sidx[s]].shape[0]) for s in self.names}
+        if elements is not None and len(elements) > 1:
+            tabs = [r.tables(self.names, ncols) for r in elements]
+            runs_k, rows, lab_k = stack_orbit_tables([t[:3] for t in tabs])
+            self.n_elements = len(elements)
+            runs, lab = runs_k[0], lab_k[0]
+            all_runs, all_lab = [r for blk in runs_k for r in blk], [c for blk in lab_k for c in blk]
+            signed = True      # (K > 1 implies sign_flags bit 0)
+        else:
+            runs, rows, lab, signed = recipe.tables(self.names, ncols)
+            self.n_elements = 1
+            all_runs, all_lab = runs, lab
+        self.operators = [None]      # (`orbit` names its elements)
+        self.runs = torch.tensor(all_runs, dtype=torch.int32, device=self.device)
         self.rows = torch.tensor(rows, dtype=torch.int32, device=self.device)
-        self.label_cols = torch.tensor(lab, dtype=torch.int32, device=self.device)
+        self.label_cols = torch.tensor(all_lab, dtype=torch.int32, device=self.device)
         d = eng.MshgnnWindowDesc()
         d.n_types = len(recipe.node_types); d.dtype = {"f32": 0, "bf16": 1, "x3": 2}[self.dtype]; d.history = recipe.history
         d.normalize = int(recipe.normalize)
@@ -308,6 +375,8 @@ class SequenceStore:
         d.label_rotate = int(recipe.label_rotate); d.quat_src = sidx[recipe.quat_series] if recipe.quat_series else -1
         d.label_cols = self.label_cols.data_ptr()
         d.sign_flags = 1 if signed else 0      # the tables carry sign flags (checked by the library on the first call, vouched for afterwards: bit 1)
+        if self.n_elements > 1:
+            d.sign_flags |= self.n_elements << 8      # K stacked element tables: a window's element rides in bits 56..63 of its start
         self.desc = d
         self._cache = {}
         self._run_ptrs = None
@@ -330,11 +399,42 @@ class SequenceStore:
         recipe = self.recipe.transformed(operator, group, mode)
         # SHARED with the parent (by reference): device, lib, dtype, names, series, _shared16 (the bf16 copies), n_rows, _src / _pitch / _rows, _fast and a
         # ResidentDataset's seq_* lists.  OWNED by the sibling, all (re)made by _describe: recipe, runs, rows, label_cols, desc, _cache, _run_ptrs,
-        # _run_ptrs_key, _eval_cache, _stats_cache.  A per-store attribute that depends on the recipe or is created lazily belongs in _describe.
+        # _run_ptrs_key, _eval_cache, _stats_cache, n_elements, operators.  A per-store attribute that depends on the recipe or is created lazily belongs in _describe.
         sib = object.__new__(type(self))
         sib.__dict__.update(self.__dict__)
         sib._describe(recipe)
         return sib
+
+    def orbit(self, group: GroupAction, operators: Sequence[str] = ("gs", "gt", "gr"), mode: str = "MorphSym", identity: bool = True) -> "SequenceStore":
+        """A sibling store whose batches carry a group element PER WINDOW: its tables stack the identity (identity=True) and each operator's
+        `WindowRecipe.transformed`, element-major, over the same resident series (shared / owned exactly as in `transformed`).  `n_elements` is K,
+        `operators` names the elements (None: the identity), `len()` is still the number of windows; `recipe` is element 0's.  `batch` / `assemble`
+        take `elements`; a `DatasetView` of an orbit dataset has K * n indices."""
+        recipes = self.recipe.orbit(group, operators, mode, identity)
+        sib = object.__new__(type(self))
+        sib.__dict__.update(self.__dict__)
+        sib._describe(recipes[0], recipes)
+        sib.operators = ([None] if identity else []) + list(operators)
+        return sib
+
+    def pack_starts(self, rows: torch.Tensor, elements) -> torch.Tensor:
+        """Device start rows + one group element per window -> the packed starts an orbit descriptor's gathers take (element << 56 | row).  elements: a
+        host sequence / tensor (range-checked here) or a device int tensor (trusted: the kernels clamp an index >= K to K - 1); None: element 0."""
+        if elements is None:
+            return rows
+        el = elements if isinstance(elements, torch.Tensor) else torch.as_tensor(np.asarray(elements), dtype=torch.int64)
+        el = el.flatten().to(torch.int64)
+        if el.numel() != rows.numel():
+            raise ValueError(f"{el.numel()} elements for {rows.numel()} windows")
+        if not el.is_cuda:
+            if int(el.min()) < 0 or int(el.max()) >= self.n_elements:
+                raise IndexError(f"group element out of range [0, {self.n_elements})")
+            if self.n_elements <= 1:
+                return rows
+            el = el.to(self.device, non_blocking=True)
+        elif self.n_elements <= 1:
+            raise ValueError("this store has one group element: device `elements` belong to an `orbit` store")
+        return rows | (el << ELEMENT_SHIFT)
 
     def __len__(self) -> int:
         """Number of windows (the reference's dataset length: rows - history + 1)."""
@@ -363,12 +463,13 @@ class SequenceStore:
             self._stats_cache = {B: torch.empty(nbytes // 8, dtype=torch.float64, device=self.device) if nbytes else None}
         return self._stats_cache[B]
 
-    def assemble(self, starts, reuse_buffers: bool = False) -> Tuple[List[torch.Tensor], Optional[torch.Tensor], Optional[torch.Tensor]]:
+    def assemble(self, starts, reuse_buffers: bool = False, elements=None) -> Tuple[List[torch.Tensor], Optional[torch.Tensor], Optional[torch.Tensor]]:
         """starts: window start rows (== the reference's dataset indices), a host sequence / tensor (checked on the host) or
         a device int64 tensor (trusted).  Returns (xs, y, r_o): xs[t] is [B * n_t, padded width] at the store's dtype --
         exactly what `Engine.forward` takes (pad columns are zero) --, y float32 [B, n_label], r_o float32 [B, 4].
         reuse_buffers=True returns the same tensors on every call of one batch size (a training loop that consumes the
-        batch before asking for the next)."""
+        batch before asking for the next).  elements (an `orbit` store): one group element per window, a host sequence (range-checked) or a device
+        int tensor (trusted); None: element 0, or whatever device `starts` already carry packed (`pack_starts`, a view's `starts`)."""
         r = self.recipe
         st = starts if isinstance(starts, torch.Tensor) else torch.as_tensor(np.asarray(starts), dtype=torch.int64)
         st = st.flatten().to(torch.int64)
@@ -378,6 +479,7 @@ class SequenceStore:
             if int(st.min()) < 0 or int(st.max()) + r.history > self.n_rows:
                 raise IndexError("window index out of range")
             st = st.to(self.device, non_blocking=True)
+        st = self.pack_starts(st, elements)
         B = st.numel()
         if reuse_buffers:
             xs, y, q = self._buffers(B)
@@ -391,13 +493,13 @@ class SequenceStore:
         rc = self.lib.mshgnn_assemble_windows(C.byref(self.desc), self._src, self._pitch, self._rows, st.data_ptr(), B, xp, pitch,
                                               y.data_ptr() if y is not None else None, q.data_ptr() if q is not None else None, stream)
         eng._check(self.lib, rc, "mshgnn_assemble_windows")
-        if self.desc.sign_flags == 1:
-            self.desc.sign_flags = 3      # the library has checked these tables: later calls vouch for them (no table read-back per call)
+        if self.desc.sign_flags & 3 == 1:
+            self.desc.sign_flags |= 2     # the library has checked these tables: later calls vouch for them (no table read-back per call)
         return xs, y, q
 
-    def batch(self, starts, edge_index_dict) -> "WindowBatch":
-        """A minibatch of window indices shaped like the PyG batch the wrappers take (see WindowBatch)."""
-        return WindowBatch(self, starts, edge_index_dict)
+    def batch(self, starts, edge_index_dict, elements=None) -> "WindowBatch":
+        """A minibatch of window indices shaped like the PyG batch the wrappers take (see WindowBatch); elements: as in `assemble`."""
+        return WindowBatch(self, starts, edge_index_dict, elements)
 
     def eval_buffers(self, B: int, labels: bool = True, n_flags: int = 0):
         """The by-product buffers and the statistics scratch of `Engine.forward_series` for a batch of B windows, made once per batch size (one batch
@@ -420,7 +522,7 @@ class SequenceStore:
         """What Engine.step_mse_series hands to mshgnn_step_mse_series: bf16 copies of the series (same strides; bf16=False, the split plan:
         none -- it gathers from the fp32 series themselves) and the run-pointer scratch."""
         if self._run_ptrs is None:
-            self._run_ptrs = torch.zeros(max(1, int(self.desc.n_runs)), dtype=torch.int64, device=self.device)
+            self._run_ptrs = torch.zeros(max(1, self.n_elements * int(self.desc.n_runs)), dtype=torch.int64, device=self.device)      # (every element's block)
         if bf16 and self._src16 is None:
             self._shared16["series"] = [a.to(torch.bfloat16) for a in self.series]
             self._shared16["src"] = (C.c_void_p * len(self.series16))(*[a.data_ptr() for a in self.series16])
@@ -439,7 +541,7 @@ class WindowBatch:
     Start rows given as a DEVICE tensor are not checked (see the constructor); indices that a sampler produces on the device go through a
     `ResidentDataset` view (`DatasetView.batch`), whose mapping kernel bounds every one of them -- one sequence is a dataset of one."""
 
-    def __init__(self, store: SequenceStore, starts, edge_index_dict):
+    def __init__(self, store: SequenceStore, starts, edge_index_dict, elements=None):
         st = starts if isinstance(starts, torch.Tensor) else torch.as_tensor(np.asarray(starts), dtype=torch.int64)
         st = st.flatten().to(torch.int64)
         # Contract: every start index i satisfies 0 <= i and i + history <= store.n_rows (the fused-gather kernels read the series at
@@ -447,10 +549,14 @@ class WindowBatch:
         # host synchronisation per batch -- `store.check_starts = True` turns that check on (debugging a sampler).  The CHECKED route for indices made on
         # the device is a `ResidentDataset` view: `view.batch(device_indices, ...)` maps dataset indices to start rows with `mshgnn_dataset_starts`, which
         # sends every index outside the view to row 0 (always a whole window) and raises a flag that `view.check()` reads once per epoch.
+        # An `orbit` store: `elements` gives one group element per window (host values range-checked, device values trusted) and `starts` keeps the packed
+        # words element << 56 | row that every route hands to the library; device starts may arrive packed already (a view's `starts`).
         if not st.is_cuda or getattr(store, "check_starts", False):
-            if st.numel() < 1 or int(st.min()) < 0 or int(st.max()) + store.recipe.history > store.n_rows:
+            rows = st & ROW_MASK if st.is_cuda and store.n_elements > 1 else st
+            if st.numel() < 1 or int(rows.min()) < 0 or int(rows.max()) + store.recipe.history > store.n_rows:
                 raise IndexError("window index out of range")
             st = st.to(store.device)
+        st = store.pack_starts(st, elements)
         self.store, self.starts, self.edge_index_dict = store, st, edge_index_dict
         self.batch_size = int(st.numel())
         self._x = self._y = self._q = None
@@ -466,6 +572,11 @@ class WindowBatch:
         """(the fused training step materialised the windows and the labels as a by-product)"""
         self._x = dict(zip(self.store.recipe.node_types, xs)) if xs is not None else None
         self._y, self._q = y, q
+
+    @property
+    def elements(self) -> Optional[torch.Tensor]:
+        """The group element of every window (device int64 [B]) of an `orbit` store's batch, as the packed starts carry it; None for any other store."""
+        return (self.starts >> ELEMENT_SHIFT) if self.store.n_elements > 1 else None
 
     @property
     def x_dict(self):
@@ -618,15 +729,21 @@ class DatasetView:
         self._cum = torch.from_numpy(self._cum_np).to(dev)
         self._first = torch.from_numpy(self._first_np).to(dev)
         self.bad = torch.zeros(1, dtype=torch.int32, device=dev)      # set by the mapping kernel, zeroed by check(): accumulates over an epoch
+        # an `orbit` dataset: K * n indices over the view's n windows, index i = element i // n of window i % n -- ConcatDataset([view, view_gs, view_gt, view_gr])
+        self.n_elements = int(getattr(dataset, "n_elements", 1))
+        self.n_windows = int(self.cum[-1])
 
     def __len__(self) -> int:
-        return self.cum[-1]
+        return self.n_elements * self.n_windows
 
     def starts(self, indices, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Start rows (device int64, rows of the dataset's concatenated series) of the view's `indices`.  A host sequence / tensor is checked here
         (IndexError) and mapped on the host; a device int64 tensor goes through mshgnn_dataset_starts on the current stream (`out`: a device int64
-        tensor of the same size to write into -- a captured step's static buffer)."""
+        tensor of the same size to write into -- a captured step's static buffer).  An `orbit` dataset: index i is element i // n of window i % n and
+        the result are PACKED starts (element << 56 | row); the split is made with torch integer ops around the mapping kernel, on the device and
+        capturable, and an index outside [0, K n) reaches the kernel as -1: row 0, element 0, and the `bad` word is set."""
         ds = self.dataset
+        K, n = self.n_elements, self.n_windows
         ix = indices if isinstance(indices, torch.Tensor) else torch.as_tensor(np.asarray(indices), dtype=torch.int64)
         if ix.numel() < 1:
             raise ValueError("no window indices")
@@ -634,8 +751,12 @@ class DatasetView:
             ix = ix.flatten().to(torch.int64).numpy()
             if int(ix.min()) < 0 or int(ix.max()) >= len(self):
                 raise IndexError(f"dataset index out of range [0, {len(self)})")
+            el = ix // n if K > 1 else None
+            if K > 1:
+                ix = ix - el * n
             s = np.searchsorted(self._cum_np, ix, side="right") - 1
-            st = torch.from_numpy(self._first_np[s] + (ix - self._cum_np[s])).to(ds.device)
+            rows = self._first_np[s] + (ix - self._cum_np[s])
+            st = torch.from_numpy(rows | (el << ELEMENT_SHIFT) if K > 1 else rows).to(ds.device)
             if out is not None:
                 out.copy_(st)
                 return out
@@ -643,6 +764,11 @@ class DatasetView:
         if ix.dtype != torch.int64 or not ix.is_contiguous():
             ix = ix.to(torch.int64).contiguous()
         ix = ix.view(-1)
+        el = None
+        if K > 1:
+            valid = (ix >= 0) & (ix < K * n)
+            el = torch.where(valid, torch.div(ix, max(n, 1), rounding_mode="floor"), torch.zeros_like(ix))
+            ix = torch.where(valid, ix - el * n, torch.full_like(ix, -1))
         if out is None:
             out = torch.empty_like(ix)
         elif not out.is_cuda or out.dtype != torch.int64 or out.numel() != ix.numel() or not out.is_contiguous():
@@ -653,6 +779,8 @@ class DatasetView:
             rc = ds.lib.mshgnn_dataset_starts(self._cum.data_ptr(), self._first.data_ptr(), len(self.first_row), ix.data_ptr(), ix.numel(), out.data_ptr(),
                                               self.bad.data_ptr(), C.c_void_p(torch.cuda.current_stream(ds.device).cuda_stream))
         eng._check(ds.lib, rc, "mshgnn_dataset_starts")
+        if el is not None:
+            out.bitwise_or_(el << ELEMENT_SHIFT)
         return out
 
     def check(self) -> None:
