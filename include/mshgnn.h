@@ -312,6 +312,30 @@ int mshgnn_metrics_classification_step(const float* logits, const int32_t* y, in
 int mshgnn_metrics_com_step(const float* y_pred, const float* y, int64_t batch, int n_bases, const double* y_mean, const double* y_std,
                             double* batch_state, double* epoch_state, void* scratch, void* stream);
 
+/* The step sums per SEGMENT, for an evaluator's table of one row per symmetry operator and one column group per test sequence
+ * (research/evaluator_regression-grf_c2.py:170-221, evaluator_classification_k4.py:57-89) out of ONE sweep: window b carries an id
+ * segment[b] (DEVICE int32[batch]; an evaluation uses element * n_sequences + sequence) and its sums are added to row segment[b] of the state.
+ * An id outside [0, n_segments), negative ids included, adds its window to the extra row n_segments (the overflow row): nothing is indexed
+ * past the state, and there is no flag word and no host read.
+ *   regression: y_pred / y fp32 [batch][per_window]; state double[n_segments + 1][3], row s: [0] += sum (y_pred - y)^2, [1] += sum |y_pred - y|,
+ *     [2] += per_window * windows, over the windows of segment s (the sums of mshgnn_metrics_regression).
+ *   classification: the layouts of mshgnn_metrics_classification; ce_state double[n_segments + 1][2], counts int64[n_segments + 1][18], row s
+ *     what that call keeps, over the windows of segment s (16-class product rule, first maximum wins).
+ * One launch, asynchronous on `stream`, nothing allocated.  All sums fp64 and bit-reproducible: the result is a function of the arguments alone,
+ * for any arrangement of ids (sorted runs, shuffled, all equal, all distinct) and any arrival order of waves and workgroups.  No
+ * floating-point atomic: a lane adds its window's terms in index order, a wave adds the lanes of one id in a fixed butterfly and leaves one
+ * entry per distinct id in its slot of the scratch, and the workgroup that draws the last ticket adds every id's entries in (slot, entry)
+ * order (csrc/mshgnn_train_ops.hip); the int64 counters are added with integer atomics, exact in any order.
+ * scratch: mshgnn_metrics_segmented_scratch_bytes(batch) = 16 + 1544 * ceil(batch / 64) bytes of device memory (a ticket, then per 64
+ * windows one slot of an entry count and 64 entries of id, windows and two sums), 8-byte aligned, zeroed ONCE by the caller and then owned by
+ * these calls (the ticket is reset by the kernel); a scratch serves every batch up to the one it was sized for; one scratch per stream.
+ * MSHGNN_EINVAL before any launch: a null pointer, batch < 1, per_window < 1, n_segments < 1, a scratch that is not 8-byte aligned.          */
+size_t mshgnn_metrics_segmented_scratch_bytes(int64_t batch);
+int mshgnn_metrics_regression_segmented(const float* y_pred, const float* y, int64_t batch, int32_t per_window, const int32_t* segment,
+                                        int32_t n_segments, double* state, void* scratch, void* stream);
+int mshgnn_metrics_classification_segmented(const float* logits, const int32_t* y, int64_t batch, const int32_t* segment, int32_t n_segments,
+                                            double* ce_state, int64_t* counts, void* scratch, void* stream);
+
 /* body_frame_to_world_frame (gnnLightning.py:663-676) without the per-step CPU/scipy round trip: quat fp32 [batch][4] is
  * the world->body rotation, scalar-last (x, y, z, w) as scipy.Rotation.from_quat takes it; grf fp32 [batch][4][3].       */
 int mshgnn_grf_body_to_world(const float* quat, const float* grf_body, float* grf_world, int64_t batch, void* stream);

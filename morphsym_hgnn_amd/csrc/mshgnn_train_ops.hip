@@ -1,5 +1,5 @@
 // Plan-independent entry points of libmshgnn (include/mshgnn.h): what a training loop runs around the engine's step, kernels and entry points together --
-// Adam on the flat parameter buffer, the stand-alone MSE / cross-entropy losses, the step metrics of the Lightning wrappers and the GRF body -> world rotation.
+// Adam on the flat parameter buffer, the stand-alone MSE / cross-entropy losses, the step metrics of the Lightning wrappers (whole-batch and segmented) and the GRF body -> world rotation.
 // None of it reads a plan; it shares only the error string with the rest of the library.
 #include "mshgnn_device.hpp"
 
@@ -168,14 +168,14 @@ __device__ __forceinline__ double met_load(const double* p) { return __longlong_
 __device__ __forceinline__ void met_store(long long* p, long long v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ long long met_load(const long long* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 // thread 0 of every workgroup, after its partials are stored: true in the workgroup that arrives last (sc == nullptr: a one-block launch)
-__device__ __forceinline__ bool met_last_block(MetScratch* sc) {
-    if (!sc) return true;
+__device__ __forceinline__ bool met_last_ticket(unsigned int* ticket) {
     __atomic_thread_fence(__ATOMIC_RELEASE);        // (agent scope: the partials reach memory every XCD's L2 sees)
-    const unsigned int t = __hip_atomic_fetch_add(&sc->ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned int t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
     if (t != gridDim.x - 1) return false;
     __atomic_thread_fence(__ATOMIC_ACQUIRE);
     return true;
 }
+__device__ __forceinline__ bool met_last_block(MetScratch* sc) { return !sc || met_last_ticket(&sc->ticket); }
 
 // regression (calculate_losses_step, gnnLightning.py:124-130): sums of (pred - y)^2, |pred - y| and n; `batch` (nullable) receives this
 // step's sums (overwritten), `epoch` (nullable) has them added; gout (nullable) = d mean((pred - y)^2) / d pred = 2 (pred - y) / n
@@ -221,6 +221,40 @@ template <int NT> __global__ __launch_bounds__(NT) void k_metrics_reg(const floa
     }
 }
 
+// one window of the classification metrics: its four per-foot cross entropies added to `ce`, its counters to `c` (layout below), its gradient
+// rows to gout (nullable).  Shared by k_metrics_cls and k_metrics_cls_seg.
+__device__ __forceinline__ void met_cls_window(const float* logits, const int32_t* y, int64_t w, int64_t B, float* gout, double& ce, long long (&c)[MET_COUNTS]) {
+    double p1[4];
+    int state = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const double l0 = (double)logits[(w * 4 + k) * 2], l1 = (double)logits[(w * 4 + k) * 2 + 1];
+        const double m = fmax(l0, l1), e0 = exp(l0 - m), e1 = exp(l1 - m), se = e0 + e1;
+        const int lab = y[w * 4 + k] != 0;
+        ce += (m + log(se)) - (lab ? l1 : l0);
+        const double p0 = e0 / se; p1[k] = e1 / se;
+        if (gout) {
+            const double inv = 1.0 / (double)(4 * B);
+            gout[(w * 4 + k) * 2] = (float)((p0 - (lab ? 0.0 : 1.0)) * inv);
+            gout[(w * 4 + k) * 2 + 1] = (float)((p1[k] - (lab ? 1.0 : 0.0)) * inv);
+        }
+        const int pred = p1[k] > p0 ? 1 : 0;             // argmax over (p0, p1): the first maximum wins
+        const int cell = pred ? (lab ? 0 : 1) : (lab ? 2 : 3);      // tp, fp, fn, tn -- added by compare, not by a run-time index (the counters stay in registers)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) c[2 + 4 * k + j] += (cell == j);
+        state = state * 2 + lab;
+    }
+    int best = 0; double bestv = -1.0;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        const double f0 = (j & 8) ? p1[0] : 1.0 - p1[0], f1 = (j & 4) ? p1[1] : 1.0 - p1[1];
+        const double f2 = (j & 2) ? p1[2] : 1.0 - p1[2], f3 = (j & 1) ? p1[3] : 1.0 - p1[3];
+        const double v = (f0 * f1) * (f2 * f3);
+        if (v > bestv) { bestv = v; best = j; }
+    }
+    c[0] += 1; c[1] += (best == state);
+}
+
 // classification (gnnLightning.py:132-151, 285-348): logits [B*4][2], labels [B][4] in {0,1}.
 //   ce_state[0] += sum of per-foot cross entropies, ce_state[1] += 4 B                      (customMetrics.py:17-24)
 //   counts[0] += B, counts[1] += windows whose 16-class argmax equals the label state       (Accuracy, 16 classes)
@@ -238,37 +272,7 @@ template <int NT> __global__ __launch_bounds__(NT) void k_metrics_cls(const floa
     long long c[MET_COUNTS];
 #pragma unroll
     for (int k = 0; k < MET_COUNTS; ++k) c[k] = 0;
-    for (int64_t w = (int64_t)blockIdx.x * NT + threadIdx.x; w < B; w += (int64_t)gridDim.x * NT) {
-        double p1[4];
-        int state = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const double l0 = (double)logits[(w * 4 + k) * 2], l1 = (double)logits[(w * 4 + k) * 2 + 1];
-            const double m = fmax(l0, l1), e0 = exp(l0 - m), e1 = exp(l1 - m), se = e0 + e1;
-            const int lab = y[w * 4 + k] != 0;
-            ce += (m + log(se)) - (lab ? l1 : l0);
-            const double p0 = e0 / se; p1[k] = e1 / se;
-            if (gout) {
-                const double inv = 1.0 / (double)(4 * B);
-                gout[(w * 4 + k) * 2] = (float)((p0 - (lab ? 0.0 : 1.0)) * inv);
-                gout[(w * 4 + k) * 2 + 1] = (float)((p1[k] - (lab ? 1.0 : 0.0)) * inv);
-            }
-            const int pred = p1[k] > p0 ? 1 : 0;             // argmax over (p0, p1): the first maximum wins
-            const int cell = pred ? (lab ? 0 : 1) : (lab ? 2 : 3);      // tp, fp, fn, tn -- added by compare, not by a run-time index (the counters stay in registers)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) c[2 + 4 * k + j] += (cell == j);
-            state = state * 2 + lab;
-        }
-        int best = 0; double bestv = -1.0;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const double f0 = (j & 8) ? p1[0] : 1.0 - p1[0], f1 = (j & 4) ? p1[1] : 1.0 - p1[1];
-            const double f2 = (j & 2) ? p1[2] : 1.0 - p1[2], f3 = (j & 1) ? p1[3] : 1.0 - p1[3];
-            const double v = (f0 * f1) * (f2 * f3);
-            if (v > bestv) { bestv = v; best = j; }
-        }
-        c[0] += 1; c[1] += (best == state);
-    }
+    for (int64_t w = (int64_t)blockIdx.x * NT + threadIdx.x; w < B; w += (int64_t)gridDim.x * NT) met_cls_window(logits, y, w, B, gout, ce, c);
     ce = wave_sum(ce);
 #pragma unroll
     for (int k = 0; k < MET_COUNTS; ++k) c[k] = wave_sum(c[k]);
@@ -428,6 +432,261 @@ __global__ void k_grf_to_world(const float* quat, const float* body, float* worl
     }
 }
 
+// ------------------------------------------------------------------------------------------------------
+// Segmented step metrics (include/mshgnn.h): the same sums per SEGMENT -- window b's sums go to row segment[b] of the state, ids outside
+// [0, n_segments) to the extra row n_segments.  Bit-reproducible for any arrangement of ids and without a floating-point atomic:
+//   * a lane owns a window and adds its terms in index order;
+//   * a wave groups its 64 lanes by id: while lanes remain it takes the first remaining lane's id and sums the lanes that hold it (the xor
+//     butterfly of wave_sum over the masked values: every lane ends with the same bits; a group of one lane is copied, not summed) -- one
+//     entry (id, windows, sums) per distinct id, in order of first appearance, into slot (window index / 64) of the caller's scratch;
+//   * the workgroup that draws the last ticket merges: thread t owns the ids == t (mod SEG_THREADS) and walks ALL entries in (slot, entry)
+//     order -- staged through LDS behind a prefix sum of the slots' entry counts, with a bit mask per thread that marks its entries -- adding the entries of its ids;
+//     consecutive entries of one id are summed in a register and added to the state's row when the id changes.
+// The order of every addition is fixed by the window indices and the ids alone, whichever wave or workgroup arrives first.  An evaluation sweep
+// has one or two ids per wave: one or two entries per slot, a merge of 2 .. 3 entries per 64 windows.
+// ------------------------------------------------------------------------------------------------------
+constexpr int SEG_THREADS = 256, SEG_MAX_BLOCKS = 1024, SEG_STAGE = 1024;
+struct SegSlot { unsigned int n, pad; int id[64]; int cnt[64]; double f[64][2]; };
+struct SegScratch { unsigned int ticket, pad[3]; };      // followed by SegSlot[ceil(batch / 64)]
+static_assert(sizeof(SegSlot) == 1544 && sizeof(SegScratch) == 16, "include/mshgnn.h documents 16 + 1544 * ceil(batch / 64) bytes");
+
+__device__ __forceinline__ void met_store(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ int met_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void met_store(unsigned int* p, unsigned int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ unsigned int met_load(const unsigned int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+__device__ __forceinline__ int seg_row(int32_t id, int32_t n_segments) { return (unsigned)id < (unsigned)n_segments ? id : n_segments; }
+
+// One wave's windows -> its slot.  Every lane of the wave calls this (valid: the lane holds a window); id is a row already (seg_row).
+// extra(mine, cnt, leader, row): per-group work of the caller, wave-uniform control flow (the classification counters).
+template <int NF, class Extra> __device__ __forceinline__ void seg_wave_emit(SegSlot* slot, bool valid, int id, double f0, double f1, Extra&& extra) {
+    const int lane = threadIdx.x & 63;
+    unsigned long long rem = __ballot(valid);
+    int e = 0, e_id = 0, e_cnt = 0;
+    double e0 = 0.0, e1 = 0.0;
+    while (rem) {
+        const int leader = __ffsll((unsigned long long)rem) - 1;
+        const int row = __shfl(id, leader, 64);
+        const bool mine = valid && id == row;
+        const unsigned long long m = __ballot(mine);
+        const int cnt = __popcll(m);
+        double s0, s1 = 0.0;
+        if (cnt == 1) {
+            s0 = __shfl(f0, leader, 64);
+            if (NF > 1) s1 = __shfl(f1, leader, 64);
+        } else {
+            s0 = wave_sum(mine ? f0 : 0.0);
+            if (NF > 1) s1 = wave_sum(mine ? f1 : 0.0);
+        }
+        extra(mine, cnt, leader, row);
+        if (lane == e) { e_id = row; e_cnt = cnt; e0 = s0; e1 = s1; }
+        ++e;
+        rem &= ~m;
+    }
+    // e <= 64: every pass retires at least the leader's lane
+    if (lane < e) {
+        met_store(&slot->id[lane], e_id); met_store(&slot->cnt[lane], e_cnt);
+        met_store(&slot->f[lane][0], e0);
+        if (NF > 1) met_store(&slot->f[lane][1], e1);
+    }
+    if (lane == 0) met_store(&slot->n, (unsigned)e);
+}
+
+// The last workgroup: state[row][0 .. NF - 1] += the entries' sums, state[row][NF] += windows * per_entry, rows 0 .. n_segments.
+// Per SEG_THREADS slots: every thread fetches its slot's entry count AND its first two entries in one round of loads (an evaluation sweep's slots hold
+// one or two), the counts are prefix-summed, and the entries are staged in LDS in (slot, entry) order -- at once where they fit (the rest of a slot's
+// entries in a second round of loads), else SEG_STAGE at a time.  Staging entry j also sets bit j of its owner's row of s_mask (an integer OR: any
+// order, the same bits); thread t then walks the set bits of ITS row in increasing j, so it meets the entries of its ids in (slot, entry) order
+// without reading anyone else's.
+template <int NF> __device__ __forceinline__ void seg_merge(const SegSlot* slots, int64_t n_slots, int32_t n_segments, double* state, int64_t per_entry) {
+    __shared__ int s_off[SEG_THREADS + 1], s_wave[SEG_THREADS / 64], s_id[SEG_STAGE], s_cnt[SEG_STAGE];
+    __shared__ double s_f[SEG_STAGE][NF];
+    __shared__ unsigned int s_mask[SEG_THREADS][SEG_STAGE / 32 + 1];          // (+ 1: the rows start in different banks)
+    const int t = threadIdx.x, lane = t & 63;
+    for (int w = 0; w < SEG_STAGE / 32; ++w) s_mask[t][w] = 0;          // (its own row; the others set bits in it behind the next barrier)
+    int cur = -1;
+    long long ccnt = 0;
+    double a0 = 0.0, a1 = 0.0;
+    auto flush = [&]() {
+        if (cur < 0) return;
+        double* row = state + (int64_t)cur * (NF + 1);
+        const double r0 = row[0], r1 = NF > 1 ? row[1] : 0.0, rn = row[NF];
+        row[0] = r0 + a0;
+        if (NF > 1) row[1] = r1 + a1;
+        row[NF] = rn + (double)(ccnt * per_entry);
+    };
+    auto stage = [&](int j, int id, int cnt, double f0, double f1) {
+        id = seg_row(id, n_segments);
+        s_id[j] = id; s_cnt[j] = cnt; s_f[j][0] = f0;
+        if (NF > 1) s_f[j][NF - 1] = f1;
+        atomicOr(&s_mask[id & (SEG_THREADS - 1)][j >> 5], 1u << (j & 31));
+    };
+    auto stage_from = [&](int j, const SegSlot* sl, int k) {
+        stage(j, met_load(&sl->id[k]), met_load(&sl->cnt[k]), met_load(&sl->f[k][0]), NF > 1 ? met_load(&sl->f[k][1]) : 0.0);
+    };
+    auto slot_of = [&](int e) {          // s_off[lo] <= e < s_off[lo + 1]: the last slot that starts at or before e holds it
+        int lo = 0, hi = SEG_THREADS;
+        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (s_off[mid] <= e) lo = mid; else hi = mid; }
+        return lo;
+    };
+    auto consume = [&](int te) {
+        for (int w = 0; w < (te + 31) >> 5; ++w) {
+            unsigned int m = s_mask[t][w];
+            if (!m) continue;
+            s_mask[t][w] = 0;
+            while (m) {
+                const int j = (w << 5) + __ffs(m) - 1;
+                m &= m - 1;
+                const int id = s_id[j];
+                if (id != cur) { flush(); cur = id; ccnt = 0; a0 = a1 = 0.0; }
+                a0 += s_f[j][0];
+                if (NF > 1) a1 += s_f[j][NF - 1];
+                ccnt += s_cnt[j];
+            }
+        }
+    };
+    for (int64_t c0 = 0; c0 < n_slots; c0 += SEG_THREADS) {
+        const bool have = c0 + t < n_slots;
+        const SegSlot* mine = slots + (have ? c0 + t : 0);
+        int n = 0, pid[2] = {0, 0}, pcnt[2] = {0, 0};
+        double pf[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
+        if (have) {
+            n = (int)min(met_load(&mine->n), 64u);
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {          // (entry k of a slot with fewer entries: whatever an earlier call left, never used)
+                pid[k] = met_load(&mine->id[k]); pcnt[k] = met_load(&mine->cnt[k]);
+                pf[k][0] = met_load(&mine->f[k][0]);
+                if (NF > 1) pf[k][1] = met_load(&mine->f[k][1]);
+            }
+        }
+        int incl = n;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) { const int v = __shfl_up(incl, d, 64); if (lane >= d) incl += v; }
+        if (lane == 63) s_wave[t >> 6] = incl;
+        __syncthreads();
+        for (int w = 0; w < (t >> 6); ++w) incl += s_wave[w];
+        s_off[t + 1] = incl;
+        if (t == 0) s_off[0] = 0;
+        const int more = __syncthreads_or(n > 2);
+        const int total = s_off[SEG_THREADS];
+        if (total <= SEG_STAGE) {
+#pragma unroll
+            for (int k = 0; k < 2; ++k) if (k < n) stage(incl - n + k, pid[k], pcnt[k], pf[k][0], pf[k][1]);
+            if (more) {
+                for (int j = t; j < total; j += SEG_THREADS) {
+                    const int lo = slot_of(j), k = j - s_off[lo];
+                    if (k >= 2) stage_from(j, slots + c0 + lo, k);
+                }
+            }
+            __syncthreads();
+            consume(total);
+            __syncthreads();
+        } else {
+            for (int e0 = 0; e0 < total; e0 += SEG_STAGE) {
+                const int te = min(SEG_STAGE, total - e0);
+                for (int j = t; j < te; j += SEG_THREADS) {
+                    const int lo = slot_of(e0 + j);
+                    stage_from(j, slots + c0 + lo, e0 + j - s_off[lo]);
+                }
+                __syncthreads();
+                consume(te);
+                __syncthreads();
+            }
+        }
+    }
+    flush();
+}
+
+// every wave's entries are stored and drained, then one ticket per workgroup; true in all threads of the workgroup that arrives last
+__device__ __forceinline__ bool seg_last_block(SegScratch* sc) {
+    __shared__ int s_last;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) s_last = met_last_ticket(&sc->ticket) ? 1 : 0;
+    __syncthreads();
+    if (!s_last) return false;
+    __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    return true;
+}
+
+__global__ __launch_bounds__(SEG_THREADS) void k_metrics_reg_seg(const float* pred, const float* y, int64_t batch, int per_window, int vec4, const int32_t* segment,
+                                                                 int32_t n_segments, double* state, SegScratch* sc) {
+    SegSlot* slots = reinterpret_cast<SegSlot*>(sc + 1);
+    const int64_t n_slots = (batch + 63) / 64;
+    for (int64_t base = (int64_t)blockIdx.x * SEG_THREADS; base < batch; base += (int64_t)gridDim.x * SEG_THREADS) {
+        const int64_t w = base + threadIdx.x, wave0 = base + (threadIdx.x & ~63);
+        if (wave0 >= batch) continue;          // (wave-uniform: this wave has no window, and no slot)
+        const bool valid = w < batch;
+        double s = 0.0, a = 0.0;
+        int id = 0;
+        if (valid) {          // the window's terms in index order, four loads of each operand in flight (vec4: 16-byte loads, the same additions in the same order)
+            id = seg_row(segment[w], n_segments);
+            const float* p = pred + w * per_window; const float* q = y + w * per_window;
+            if (vec4) {
+                const f32x4* p4 = reinterpret_cast<const f32x4*>(p); const f32x4* q4 = reinterpret_cast<const f32x4*>(q);
+                const int n4 = per_window >> 2;
+                for (int i = 0; i < n4; i += 4) {
+                    f32x4 pv[4], qv[4];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) if (i + u < n4) { pv[u] = p4[i + u]; qv[u] = q4[i + u]; }
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) if (i + u < n4) {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) { const double dlt = (double)pv[u][e] - (double)qv[u][e]; s += dlt * dlt; a += fabs(dlt); }
+                    }
+                }
+            } else {
+                for (int i = 0; i < per_window; i += 4) {
+                    float pv[4], qv[4];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) if (i + u < per_window) { pv[u] = p[i + u]; qv[u] = q[i + u]; }
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) if (i + u < per_window) { const double dlt = (double)pv[u] - (double)qv[u]; s += dlt * dlt; a += fabs(dlt); }
+                }
+            }
+        }
+        seg_wave_emit<2>(slots + (wave0 >> 6), valid, id, s, a, [](bool, int, int, int) {});
+    }
+    if (!seg_last_block(sc)) return;
+    seg_merge<2>(slots, n_slots, n_segments, state, per_window);
+    if (threadIdx.x == 0) __hip_atomic_store(&sc->ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// classification: the cross entropies go through the entries like the regression sums; the 18 int64 counters of a group are added to its row
+// with integer atomics (exact in any order), lane k the counter k
+__global__ __launch_bounds__(SEG_THREADS) void k_metrics_cls_seg(const float* logits, const int32_t* y, int64_t batch, const int32_t* segment, int32_t n_segments,
+                                                                 double* ce_state, long long* counts, SegScratch* sc) {
+    SegSlot* slots = reinterpret_cast<SegSlot*>(sc + 1);
+    const int64_t n_slots = (batch + 63) / 64;
+    const int lane = threadIdx.x & 63;
+    for (int64_t base = (int64_t)blockIdx.x * SEG_THREADS; base < batch; base += (int64_t)gridDim.x * SEG_THREADS) {
+        const int64_t w = base + threadIdx.x, wave0 = base + (threadIdx.x & ~63);
+        if (wave0 >= batch) continue;
+        const bool valid = w < batch;
+        double ce = 0.0;
+        long long c[MET_COUNTS];
+#pragma unroll
+        for (int k = 0; k < MET_COUNTS; ++k) c[k] = 0;
+        int id = 0;
+        if (valid) {
+            id = seg_row(segment[w], n_segments);
+            met_cls_window(logits, y, w, batch, nullptr, ce, c);
+        }
+        seg_wave_emit<1>(slots + (wave0 >> 6), valid, id, ce, 0.0, [&](bool mine, int cnt, int leader, int row) {
+            long long v = 0;
+#pragma unroll
+            for (int k = 0; k < MET_COUNTS; ++k) {
+                const long long sum = cnt == 1 ? __shfl(c[k], leader, 64) : wave_sum(mine ? c[k] : 0ll);
+                if (lane == k) v = sum;
+            }
+            if (lane < MET_COUNTS && v) __hip_atomic_fetch_add(counts + (int64_t)row * MET_COUNTS + lane, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        });
+    }
+    if (!seg_last_block(sc)) return;
+    seg_merge<1>(slots, n_slots, n_segments, ce_state, 4);
+    if (threadIdx.x == 0) __hip_atomic_store(&sc->ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 static int met_blocks(int64_t items, int per_thread) {
     return (int)std::max<int64_t>(1, std::min<int64_t>(MET_BLOCKS, (items + per_thread * MET_THREADS - 1) / (per_thread * MET_THREADS)));
 }
@@ -475,6 +734,34 @@ extern "C" int mshgnn_metrics_com_step(const float* y_pred, const float* y, int6
     for (int k = 0; k < 6; ++k) { st.mean[k] = y_mean[k]; st.std[k] = y_std[k]; }
     hipLaunchKernelGGL(k_metrics_com, dim3(met_blocks(batch, 1)), dim3(MET_THREADS), 0, (hipStream_t)stream, y_pred, y, batch, n_bases, st, batch_state,
                        epoch_state, reinterpret_cast<MetScratchCom*>(scratch));
+    HIPCHK(hipGetLastError());
+    return MSHGNN_OK;
+}
+
+extern "C" size_t mshgnn_metrics_segmented_scratch_bytes(int64_t batch) {
+    return batch < 1 ? 0 : sizeof(SegScratch) + sizeof(SegSlot) * (size_t)((batch + 63) / 64);
+}
+
+static int seg_blocks(int64_t batch) { return (int)std::min<int64_t>(SEG_MAX_BLOCKS, (batch + SEG_THREADS - 1) / SEG_THREADS); }
+
+extern "C" int mshgnn_metrics_regression_segmented(const float* y_pred, const float* y, int64_t batch, int32_t per_window, const int32_t* segment,
+                                                   int32_t n_segments, double* state, void* scratch, void* stream) {
+    if (!y_pred || !y || !segment || !state || !scratch) return set_err(MSHGNN_EINVAL, "null argument to mshgnn_metrics_regression_segmented");
+    if (batch < 1 || per_window < 1 || n_segments < 1) return set_err(MSHGNN_EINVAL, "mshgnn_metrics_regression_segmented: batch, per_window and n_segments must be >= 1");
+    if ((uintptr_t)scratch & 7) return set_err(MSHGNN_EINVAL, "mshgnn_metrics_regression_segmented: the scratch must be 8-byte aligned");
+    hipLaunchKernelGGL(k_metrics_reg_seg, dim3(seg_blocks(batch)), dim3(SEG_THREADS), 0, (hipStream_t)stream, y_pred, y, batch, (int)per_window,
+                       (int)(per_window % 4 == 0 && (((uintptr_t)y_pred | (uintptr_t)y) & 15) == 0), segment, n_segments, state, reinterpret_cast<SegScratch*>(scratch));
+    HIPCHK(hipGetLastError());
+    return MSHGNN_OK;
+}
+
+extern "C" int mshgnn_metrics_classification_segmented(const float* logits, const int32_t* y, int64_t batch, const int32_t* segment, int32_t n_segments,
+                                                       double* ce_state, int64_t* counts, void* scratch, void* stream) {
+    if (!logits || !y || !segment || !ce_state || !counts || !scratch) return set_err(MSHGNN_EINVAL, "null argument to mshgnn_metrics_classification_segmented");
+    if (batch < 1 || n_segments < 1) return set_err(MSHGNN_EINVAL, "mshgnn_metrics_classification_segmented: batch and n_segments must be >= 1");
+    if ((uintptr_t)scratch & 7) return set_err(MSHGNN_EINVAL, "mshgnn_metrics_classification_segmented: the scratch must be 8-byte aligned");
+    hipLaunchKernelGGL(k_metrics_cls_seg, dim3(seg_blocks(batch)), dim3(SEG_THREADS), 0, (hipStream_t)stream, logits, y, batch, segment, n_segments, ce_state,
+                       reinterpret_cast<long long*>(counts), reinterpret_cast<SegScratch*>(scratch));
     HIPCHK(hipGetLastError());
     return MSHGNN_OK;
 }

@@ -85,6 +85,7 @@ EXPORTS = [
     "mshgnn_comm_unique_id", "mshgnn_comm_create", "mshgnn_comm_destroy", "mshgnn_comm_allreduce_mean", "mshgnn_comm_allreduce_sum",
     "mshgnn_input_grad", "mshgnn_forward_series", "mshgnn_forward_series_stats_bytes", "mshgnn_step_mse_series_std", "mshgnn_step_ce_series_std",
     "mshgnn_dataset_starts",
+    "mshgnn_metrics_segmented_scratch_bytes", "mshgnn_metrics_regression_segmented", "mshgnn_metrics_classification_segmented",
 ]
 ABI_VERSION = 6      # include/mshgnn.h MSHGNN_ABI_VERSION: the ctypes structures above mirror THAT header
 
@@ -187,6 +188,12 @@ def load_library():
         lib.mshgnn_step_ce_series_std.argtypes = list(lib.mshgnn_step_mse_series_std.argtypes)
     if hasattr(lib, "mshgnn_dataset_starts"):      # (absent from older builds of the library handed over through MSHGNN_LIB for A/B runs)
         lib.mshgnn_dataset_starts.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "mshgnn_metrics_regression_segmented"):      # (absent from older builds of the library handed over through MSHGNN_LIB for A/B runs)
+        lib.mshgnn_metrics_segmented_scratch_bytes.restype = C.c_size_t
+        lib.mshgnn_metrics_segmented_scratch_bytes.argtypes = [C.c_int64]
+        lib.mshgnn_metrics_regression_segmented.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.mshgnn_metrics_classification_segmented.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                                C.c_void_p]
     lib.mshgnn_struct_size.restype = C.c_size_t
     lib.mshgnn_struct_size.argtypes = [C.c_int]
     lib.mshgnn_comm_unique_id.argtypes = [C.c_char_p, C.c_void_p]

@@ -11,7 +11,7 @@ loss a `training_step` returns (`mse_loss` / `ce_loss`, gnnLightning.py:709-722)
 launch of `mshgnn_mse_loss` / `mshgnn_ce_loss` (dL/dy_pred on the device), so a wrapper built on this class trains without torch's
 elementwise loss kernels.
 
-There is no CPU implementation: without a HIP device every method raises.
+There is no CPU implementation: without a HIP device every method raises (`segmented_reference`, the numpy mirror the tests use as their yardstick, aside).
 """
 from __future__ import annotations
 
@@ -254,3 +254,172 @@ class ComStepMetrics(StepMetrics):
     cos_sim_ang = property(lambda self: self._com(5, 6))
     avg_cos_sim = property(lambda self: None if self._com_cur is None else (self.cos_sim_lin + self.cos_sim_ang) / 2)
     loss = property(lambda self: self.mse_loss)
+
+
+# ---- per-segment sums: one row per (group element, sequence) out of one evaluation sweep ----------------------------------------------------------
+# The reference's evaluators write one CSV row per symmetry operator with MSE / RMSE / L1 per test sequence (research/evaluator_regression-grf_c2.py:
+# 170-221) or accuracy / per-leg F1 per operator (evaluator_classification_k4.py:57-89).  `SegmentedMetrics` keeps the sums of `StepMetrics` per segment
+# id (mshgnn_metrics_regression_segmented / _classification_segmented, include/mshgnn.h): one launch per batch, deterministic, no host read until asked.
+
+def _cls_terms(logits, labels):
+    """Per-window classification terms in float64, operation by operation as the kernel's `met_cls_window`: (ce [B][4], counters int64 [B][18])."""
+    import numpy as np
+    lg = np.asarray(logits, dtype=np.float32).reshape(-1, 4, 2).astype(np.float64)
+    lab = np.asarray(labels).reshape(-1, 4) != 0
+    B = lg.shape[0]
+    l0, l1 = lg[..., 0], lg[..., 1]
+    m = np.maximum(l0, l1)
+    e0, e1 = np.exp(l0 - m), np.exp(l1 - m)
+    se = e0 + e1
+    ce = (m + np.log(se)) - np.where(lab, l1, l0)
+    p0, p1 = e0 / se, e1 / se
+    pred = p1 > p0                                          # the first maximum wins
+    c = np.zeros((B, 18), dtype=np.int64)
+    for k in range(4):
+        c[:, 2 + 4 * k] = pred[:, k] & lab[:, k]             # tp, fp, fn, tn
+        c[:, 3 + 4 * k] = pred[:, k] & ~lab[:, k]
+        c[:, 4 + 4 * k] = ~pred[:, k] & lab[:, k]
+        c[:, 5 + 4 * k] = ~pred[:, k] & ~lab[:, k]
+    v = np.empty((B, 16), dtype=np.float64)
+    for j in range(16):
+        f = [p1[:, k] if (j >> (3 - k)) & 1 else 1.0 - p1[:, k] for k in range(4)]
+        v[:, j] = (f[0] * f[1]) * (f[2] * f[3])
+    state = (lab.astype(np.int64) * np.array([8, 4, 2, 1])).sum(1)
+    c[:, 0] = 1
+    c[:, 1] = np.argmax(v, axis=1) == state                 # (np.argmax: the first maximum)
+    return ce, c
+
+
+def segmented_reference(y, y_pred, segment, n_segments: int, regression: bool = True):
+    """Host mirror of one `SegmentedMetrics.update` (numpy; no GPU): the raw state the kernels would ADD, overflow row (index n_segments) included.
+    The terms are formed in float64 with the kernels' operations, every sum is `math.fsum` (the correctly rounded sum of those terms), the
+    integer counts are exact.  regression: float64 [n_segments + 1][3] (sq, abs, elements); classification: (float64 [n_segments + 1][2] (ce, rows),
+    int64 [n_segments + 1][18])."""
+    import math
+
+    import numpy as np
+    n_segments = int(n_segments)
+    if n_segments < 1:
+        raise ValueError("n_segments must be >= 1")
+    seg = np.asarray(segment.cpu() if isinstance(segment, torch.Tensor) else segment).astype(np.int64).reshape(-1)
+    B = seg.shape[0]
+    row = np.where((seg >= 0) & (seg < n_segments), seg, n_segments)
+    order = np.argsort(row, kind="stable")
+    bounds = np.searchsorted(row[order], np.arange(n_segments + 2))
+    groups = [order[bounds[s]:bounds[s + 1]] for s in range(n_segments + 1)]
+    to_np = lambda a: np.asarray(a.detach().cpu() if isinstance(a, torch.Tensor) else a)
+    if regression:
+        yp = to_np(y_pred).astype(np.float32).reshape(B, -1).astype(np.float64)
+        yy = to_np(y).astype(np.float32).reshape(B, -1).astype(np.float64)
+        if yp.shape != yy.shape:
+            raise ValueError("y and y_pred must have the same number of elements")
+        d = yp - yy
+        sq, ab = d * d, np.abs(d)
+        state = np.zeros((n_segments + 1, 3), dtype=np.float64)
+        for s, g in enumerate(groups):
+            if g.size:
+                state[s] = (math.fsum(sq[g].ravel()), math.fsum(ab[g].ravel()), float(g.size * yp.shape[1]))
+        return state
+    ce, c = _cls_terms(to_np(y_pred), to_np(y))
+    ce_state = np.zeros((n_segments + 1, 2), dtype=np.float64)
+    counts = np.zeros((n_segments + 1, 18), dtype=np.int64)
+    for s, g in enumerate(groups):
+        if g.size:
+            ce_state[s] = (math.fsum(ce[g].ravel()), float(4 * g.size))
+            counts[s] = c[g].sum(0)
+    return ce_state, counts
+
+
+_SEG_REG_COLUMNS = ("MSE", "RMSE", "L1", "n")
+_SEG_CLS_COLUMNS = ("CE", "accuracy", "f1_leg_0", "f1_leg_1", "f1_leg_2", "f1_leg_3", "f1_avg_legs", "n")
+
+
+def table_from_state(state, counts=None, per_window: int = 1):
+    """The published values per segment from raw sums (torch float64 / int64 tensors, any device; the overflow row already cut off):
+    regression (counts None) `MSE`, `RMSE`, `L1`, `n`; classification `CE`, `accuracy`, `f1_leg_0..3`, `f1_avg_legs`, `n`.  `n` is the number
+    of WINDOWS of the segment.  An empty segment's means are NaN (0 / 0); F1 follows the reference's 0 / 0 -> 0 (customMetrics.py:51-54)."""
+    if counts is None:
+        mse = state[:, 0] / state[:, 2]
+        return {"MSE": mse, "RMSE": torch.sqrt(mse), "L1": state[:, 1] / state[:, 2], "n": state[:, 2] / float(per_window)}
+    out = {"CE": state[:, 0].float().double() / state[:, 1],            # `summed_loss.float() / total_num`, customMetrics.py:24
+           "accuracy": counts[:, 1].double() / counts[:, 0].double()}
+    legs = [_f1(counts[:, 2 + 4 * k], counts[:, 3 + 4 * k], counts[:, 4 + 4 * k]) for k in range(4)]
+    for k in range(4):
+        out[f"f1_leg_{k}"] = legs[k]
+    out["f1_avg_legs"] = (legs[0] + legs[1] + legs[2] + legs[3]) / 4.0
+    out["n"] = counts[:, 0].double()
+    return out
+
+
+class SegmentedMetrics:
+    """The sums of `StepMetrics` per segment: `update(y, y_pred, segment)` adds every window's sums to the row its id names, in ONE launch, bit-reproducibly
+    (no floating-point atomic; include/mshgnn.h).  An id outside [0, n_segments) lands in an extra overflow row that `overflow()` / `check()` read."""
+
+    def __init__(self, n_segments: int, regression: bool = True, device=None):
+        if int(n_segments) < 1:
+            raise ValueError("n_segments must be >= 1")
+        self.n_segments, self.regression = int(n_segments), bool(regression)
+        self.device = _device(device)
+        self.lib = eng.load_library()
+        if not hasattr(self.lib, "mshgnn_metrics_regression_segmented"):
+            raise eng.MshgnnError("this build of the library has no mshgnn_metrics_regression_segmented / _classification_segmented")
+        self.state = torch.zeros(self.n_segments + 1, 3 if regression else 2, dtype=torch.float64, device=self.device)
+        self.counts = None if regression else torch.zeros(self.n_segments + 1, 18, dtype=torch.int64, device=self.device)
+        self.per_window = 1 if regression else 4
+        self._scratch, self._scratch_batch = None, 0
+
+    def reserve(self, batch: int) -> None:
+        """The scratch for batches of up to `batch` windows (`update` grows it when needed; reserve before capturing `update` in a graph)."""
+        if batch > self._scratch_batch:
+            nbytes = int(self.lib.mshgnn_metrics_segmented_scratch_bytes(int(batch)))
+            self._scratch = torch.zeros((nbytes + 7) // 8, dtype=torch.int64, device=self.device)      # zeroed once; the calls own it from here
+            self._scratch_batch = int(batch)
+
+    def update(self, y: torch.Tensor, y_pred: torch.Tensor, segment: torch.Tensor) -> None:
+        """y / y_pred as `calculate_losses_step` takes them, segment: int32 [batch] on the device (one id per window)."""
+        dev = self.device
+        seg = segment.detach().to(dev, torch.int32).reshape(-1).contiguous()
+        batch = int(seg.numel())
+        if batch < 1:
+            raise ValueError("no windows")
+        self.reserve(batch)
+        with torch.cuda.device(dev):
+            if self.regression:
+                yp = y_pred.detach().to(dev, torch.float32).reshape(-1).contiguous()
+                yy = y.detach().to(dev, torch.float32).reshape(-1).contiguous()
+                if yp.numel() != yy.numel() or yp.numel() % batch:
+                    raise ValueError("y and y_pred must hold the same number of elements, a multiple of the number of segment ids")
+                self.per_window = yp.numel() // batch
+                eng._check(self.lib, self.lib.mshgnn_metrics_regression_segmented(yp.data_ptr(), yy.data_ptr(), batch, self.per_window, seg.data_ptr(), self.n_segments,
+                                                                                  self.state.data_ptr(), self._scratch.data_ptr(), _stream(dev)),
+                           "mshgnn_metrics_regression_segmented")
+            else:
+                if y_pred.numel() != batch * 8 or y.numel() != batch * 4:
+                    raise ValueError("expected logits [batch * 4, 2] and labels [batch, 4] for the segment ids given")
+                yp = y_pred.detach().to(dev, torch.float32).reshape(batch * 4, 2).contiguous()
+                yy = y.detach().to(dev, torch.int32).reshape(batch * 4).contiguous()
+                eng._check(self.lib, self.lib.mshgnn_metrics_classification_segmented(yp.data_ptr(), yy.data_ptr(), batch, seg.data_ptr(), self.n_segments,
+                                                                                      self.state.data_ptr(), self.counts.data_ptr(), self._scratch.data_ptr(),
+                                                                                      _stream(dev)),
+                           "mshgnn_metrics_classification_segmented")
+
+    def table(self) -> dict:
+        """fp64 device tensors [n_segments] (`table_from_state`); no synchronisation."""
+        n = self.n_segments
+        return table_from_state(self.state[:n], None if self.regression else self.counts[:n], self.per_window)
+
+    def overflow(self) -> int:
+        """Windows whose id was outside [0, n_segments) since the last reset (one host synchronisation)."""
+        if self.regression:
+            return int(round(float(self.state[self.n_segments, 2].item()) / self.per_window))
+        return int(self.counts[self.n_segments, 0].item())
+
+    def check(self) -> None:
+        n = self.overflow()
+        if n:
+            raise IndexError(f"{n} windows carried a segment id outside [0, {self.n_segments})")
+
+    def reset(self) -> None:
+        self.state.zero_()
+        if self.counts is not None:
+            self.counts.zero_()

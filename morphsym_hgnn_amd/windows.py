@@ -670,9 +670,13 @@ class ResidentDataset(SequenceStore):
     no window straddles two sequences, `len(dataset)` is the sum.  `view()`, `subset(ranges)` and `split()` give `DatasetView`s that map indices to start
     rows, on the host for host indices and with `mshgnn_dataset_starts` for device indices."""
 
-    def __init__(self, sequences: List[Dict[str, np.ndarray]], recipe: WindowRecipe, dtype: str = "bf16", device=None, fast: bool = True):
+    def __init__(self, sequences: List[Dict[str, np.ndarray]], recipe: WindowRecipe, dtype: str = "bf16", device=None, fast: bool = True,
+                 names: Optional[Sequence[str]] = None):
         if len(sequences) < 1:
             raise ValueError("a dataset needs at least one sequence")
+        if names is not None and len(names) != len(sequences):
+            raise ValueError(f"{len(names)} names for {len(sequences)} sequences")
+        seq_names = [str(x) for x in names] if names is not None else [f"seq{k}" for k in range(len(sequences))]
         names = recipe.series()
         lengths, cols, parts = [], None, {s: [] for s in names}
         for k, seq in enumerate(sequences):
@@ -696,6 +700,7 @@ class ResidentDataset(SequenceStore):
         self.seq_rows = lengths
         self.seq_windows = dataset_window_counts(lengths, recipe.history)
         self.seq_first_row = [int(x) for x in np.concatenate([[0], np.cumsum(lengths)[:-1]])]
+        self.seq_names = seq_names      # (`names`: the sequences' names, default "seq0", ...; a view carries them -- an evaluation table's column groups)
 
     def __len__(self) -> int:
         """Number of windows: the sum over the sequences (fewer than rows - history + 1 of the concatenated series: nothing straddles)."""
@@ -735,6 +740,52 @@ class DatasetView:
 
     def __len__(self) -> int:
         return self.n_elements * self.n_windows
+
+    # segment ids of an evaluation table (metrics.SegmentedMetrics): one row per group element, one column per sequence
+    @property
+    def n_sequences(self) -> int:
+        return len(self.first_row)
+
+    @property
+    def names(self) -> List[str]:
+        return list(self.dataset.seq_names)
+
+    @property
+    def segment_shape(self) -> Tuple[int, int]:
+        return self.n_elements, self.n_sequences
+
+    @property
+    def n_segments(self) -> int:
+        return self.n_elements * self.n_sequences
+
+    def segments(self, indices, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Segment ids (device int32) element * n_sequences + sequence of the view's `indices`.  A host sequence / tensor is checked here (IndexError) and
+        mapped on the host; a device integer tensor is mapped with torch.searchsorted over the view's device `cum` and the integer ops `starts` uses for
+        the element split -- on the device, capturable, no synchronisation --, an index outside [0, K n) to -1 (`SegmentedMetrics` counts it in its
+        overflow row).  A sequence whose range is empty owns no index and so no id.  out: an int32 tensor on the dataset's device, of the same size, to write into."""
+        K, n, S = self.n_elements, self.n_windows, self.n_sequences
+        dev = self.dataset.device
+        ix = indices if isinstance(indices, torch.Tensor) else torch.as_tensor(np.asarray(indices), dtype=torch.int64)
+        if ix.numel() < 1:
+            raise ValueError("no window indices")
+        if not ix.is_cuda:
+            ix = ix.flatten().to(torch.int64).numpy()
+            if int(ix.min()) < 0 or int(ix.max()) >= len(self):
+                raise IndexError(f"dataset index out of range [0, {len(self)})")
+            el = ix // n
+            seg = torch.from_numpy((el * S + (np.searchsorted(self._cum_np, ix - el * n, side="right") - 1)).astype(np.int32)).to(dev)
+        else:
+            ix = ix.reshape(-1).to(torch.int64)
+            valid = (ix >= 0) & (ix < K * n)
+            el = torch.div(ix, max(n, 1), rounding_mode="floor")
+            seq = torch.searchsorted(self._cum, (ix - el * n).contiguous(), right=True) - 1
+            seg = torch.where(valid, el * S + seq, torch.full_like(ix, -1))
+        if out is None:
+            return seg.to(torch.int32)
+        if out.device != seg.device or out.dtype != torch.int32 or out.numel() != seg.numel() or not out.is_contiguous():
+            raise ValueError("out must be a contiguous int32 tensor on the dataset's device with one element per index")
+        out.view(-1).copy_(seg)
+        return out
 
     def starts(self, indices, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Start rows (device int64, rows of the dataset's concatenated series) of the view's `indices`.  A host sequence / tensor is checked here

@@ -643,15 +643,9 @@ class GraphedTrainingStep:
         return self.loss
 
 
-def evaluate_sequence(wrapper, store, edge_index_dict, batch_size: int, stride: int = 1) -> torch.Tensor:
-    """A test epoch over every window of one sequence, in order (the loop of the reference's `evaluate_model` without its dataset plumbing): windows
-    0, stride, 2 stride, ... of `store` in batches of `batch_size` (the last one ragged) through the wrapper's `test_step` under torch.no_grad() --
-    with `fused_evaluation_step` straight from the resident series.  `edge_index_dict`: the edges of ONE window (tiled per batch here) or a
-    callable batch size -> edge_index_dict.  Returns the predictions [n_windows, ...] in window order; the epoch's metrics are left in the
-    wrapper's state (`on_test_epoch_end` has run: `wrapper.logged`, the metric attributes).
-
-    `store` may be a `windows.DatasetView` (or a `ResidentDataset`: all of it): the view's indices 0, stride, 2 stride, ... are swept through `view.batch`,
-    the predictions come back in dataset-index order."""
+def _evaluation_sweep(wrapper, store, edge_index_dict, batch_size: int, stride: int, per_batch=None, test_only_on_z: bool = False):
+    """The loop `evaluate_sequence` and `evaluate_table` share: (predictions in index order, the view swept or None).  per_batch(lo, batch, y, y_pred) runs
+    after the wrapper's own metrics of every batch; lo: the batch's position in the swept indices 0, stride, 2 stride, ..."""
     if batch_size < 1 or stride < 1:
         raise ValueError("batch_size and stride must be >= 1")
     from .windows import DatasetView, ResidentDataset
@@ -682,11 +676,114 @@ def evaluate_sequence(wrapper, store, edge_index_dict, batch_size: int, stride: 
             batch = (view if view is not None else store).batch(st, edges_for(int(st.numel())))
             y, y_pred = wrapper.step_helper_function(batch)
             if getattr(wrapper, "body_to_world_frame", False):
-                wrapper.calculate_losses_step_worldframe(y, y_pred, batch.r_o.view(batch.batch_size, 4))
+                wrapper.calculate_losses_step_worldframe(y, y_pred, batch.r_o.view(batch.batch_size, 4), test_only_on_z)
             else:
                 wrapper.calculate_losses_step(y, y_pred)
+            if per_batch is not None:
+                per_batch(lo, batch, y, y_pred)
             preds.append(y_pred.clone())
         wrapper.on_test_epoch_end()
     if view is not None:
         view.check()
-    return torch.cat(preds, 0)
+    return torch.cat(preds, 0), view
+
+
+def evaluate_sequence(wrapper, store, edge_index_dict, batch_size: int, stride: int = 1) -> torch.Tensor:
+    """A test epoch over every window of one sequence, in order (the loop of the reference's `evaluate_model` without its dataset plumbing): windows
+    0, stride, 2 stride, ... of `store` in batches of `batch_size` (the last one ragged) through the wrapper's `test_step` under torch.no_grad() --
+    with `fused_evaluation_step` straight from the resident series.  `edge_index_dict`: the edges of ONE window (tiled per batch here) or a
+    callable batch size -> edge_index_dict.  Returns the predictions [n_windows, ...] in window order; the epoch's metrics are left in the
+    wrapper's state (`on_test_epoch_end` has run: `wrapper.logged`, the metric attributes).
+
+    `store` may be a `windows.DatasetView` (or a `ResidentDataset`: all of it): the view's indices 0, stride, 2 stride, ... are swept through `view.batch`,
+    the predictions come back in dataset-index order."""
+    return _evaluation_sweep(wrapper, store, edge_index_dict, batch_size, stride)[0]
+
+
+class EvaluationTable:
+    """What `evaluate_table` returns: `predictions` (exactly `evaluate_sequence`'s), `table` -- a dict of fp64 tensors [K][n_sequences], one row per
+    operator and one column per sequence (`metrics.table_from_state`: regression MSE / RMSE / L1 / n, classification CE / accuracy / f1_leg_0..3 /
+    f1_avg_legs / n) --, `operators` ("None", then the orbit's), `names` (the sequences') and, for classification, `totals`: the same values per
+    operator over ALL sequences, [K].  With `grf_body_to_world_frame` wrappers `table_world` holds the world-frame values."""
+
+    def __init__(self, predictions, table, operators, names, regression: bool = True, totals=None, table_world=None):
+        self.predictions, self.table, self.operators, self.names = predictions, table, list(operators), list(names)
+        self.regression, self.totals, self.table_world = bool(regression), totals, table_world
+
+    def header(self):
+        if self.regression:      # evaluator_regression-grf_c2.py:170-179
+            return ["Swap"] + [f"{name}-{m}" for name in self.names for m in ("MSE", "RMSE", "L1")]
+        return ["Symmetry Operator", "Model Accuracy", "Rear-Left", "Front-Left", "Rear-Right", "Front-Right", "F1 Avg"]      # evaluator_classification_k4.py:52
+
+    def rows(self):
+        """One list per operator: its name, then the header's values as Python floats (one device -> host copy per column)."""
+        if self.regression:
+            cols = {m: self.table[m].detach().cpu().tolist() for m in ("MSE", "RMSE", "L1")}
+            return [[op] + [cols[m][k][s] for s in range(len(self.names)) for m in ("MSE", "RMSE", "L1")] for k, op in enumerate(self.operators)]
+        if self.totals is None:
+            raise ValueError("a classification table is written from `totals` (per operator over all sequences)")
+        cols = [self.totals[m].detach().cpu().tolist() for m in ("accuracy", "f1_leg_0", "f1_leg_1", "f1_leg_2", "f1_leg_3", "f1_avg_legs")]
+        return [[op] + [c[k] for c in cols] for k, op in enumerate(self.operators)]
+
+    def to_csv(self, path) -> None:
+        """One row per operator, the evaluators' columns (regression: per sequence `<name>-MSE`, `<name>-RMSE`, `<name>-L1`; classification: accuracy, the
+        four per-leg F1 scores and their average over all sequences).  path: a file name or an open text stream."""
+        import csv
+        if hasattr(path, "write"):
+            w = csv.writer(path, lineterminator="\n")
+            w.writerow(self.header()); w.writerows(self.rows())
+            return
+        with open(path, "w", newline="") as f:
+            w = csv.writer(f, lineterminator="\n")
+            w.writerow(self.header()); w.writerows(self.rows())
+
+
+def evaluate_table(wrapper, view_or_dataset, edge_index_dict, batch_size: int, stride: int = 1, test_only_on_z: bool = False) -> EvaluationTable:
+    """The sweep of `evaluate_sequence` over a `windows.DatasetView` (or a `ResidentDataset`: all of it) that ALSO keeps the metrics per (operator, sequence):
+    every window carries the segment id element * n_sequences + sequence (`DatasetView.segments`) and one `metrics.SegmentedMetrics.update` per batch adds
+    its sums to that row -- the evaluators' whole table (one CSV row per symmetry operator, research/evaluator_regression-grf_c2.py:170-221,
+    evaluator_classification_k4.py:57-89) out of one pass over an `orbit` view, with no host read until the sweep is over.  The wrapper's own epoch metrics
+    are left in its state as `evaluate_sequence` leaves them.  With `grf_body_to_world_frame` a second table is kept on the rotated pairs (`test_only_on_z`
+    as in `calculate_losses_step_worldframe`)."""
+    from .metrics import SegmentedMetrics, table_from_state
+    from .windows import DatasetView, ResidentDataset
+    if isinstance(wrapper, COM_Base_Lightning):
+        raise ValueError("evaluate_table does not take the centroidal-momentum (COM) wrappers: their recipes have no orbit and segmented cosine sums are not kept")
+    if isinstance(view_or_dataset, ResidentDataset):
+        view_or_dataset = view_or_dataset.view()
+    if not isinstance(view_or_dataset, DatasetView):
+        raise TypeError("evaluate_table takes a windows.DatasetView or a windows.ResidentDataset")
+    view = view_or_dataset
+    K, S = view.segment_shape
+    regression = bool(wrapper.regression)
+    world = bool(getattr(wrapper, "body_to_world_frame", False))
+    seg_m = SegmentedMetrics(K * S, regression, device=view.dataset.device)
+    seg_w = SegmentedMetrics(K * S, True, device=view.dataset.device) if world else None
+    seg_m.reserve(batch_size)
+    if world:
+        seg_w.reserve(batch_size)
+
+    # the ids of the whole sweep in one go (a handful of torch integer ops on the device), a slice of them per batch
+    seg_all = view.segments(torch.arange(0, len(view), stride, dtype=torch.int64, device=view.dataset.device))
+
+    def per_batch(lo, batch, y, y_pred):
+        seg = seg_all[lo:lo + batch.batch_size]
+        seg_m.update(y, y_pred, seg)
+        if world:
+            q = batch.r_o.view(batch.batch_size, 4)
+            y_w, p_w = wrapper.body_frame_to_world_frame(q, y.detach()), wrapper.body_frame_to_world_frame(q, y_pred.detach())
+            if test_only_on_z:
+                y_w, p_w = y_w[:, [2, 5, 8, 11]], p_w[:, [2, 5, 8, 11]]
+            seg_w.update(y_w, p_w, seg)
+
+    preds, _ = _evaluation_sweep(wrapper, view, edge_index_dict, batch_size, stride, per_batch, test_only_on_z)
+    seg_m.check()
+    shape = lambda t: {k: v.view(K, S) for k, v in t.items()}
+    totals = None
+    if not regression:
+        n = K * S
+        totals = table_from_state(seg_m.state[:n].view(K, S, 2).sum(1), seg_m.counts[:n].view(K, S, 18).sum(1))
+    ops = ["None" if op is None else str(op) for op in getattr(view.dataset, "operators", [None])]
+    res = EvaluationTable(preds, shape(seg_m.table()), ops, view.names, regression, totals, shape(seg_w.table()) if world else None)
+    res.metrics, res.metrics_world = seg_m, seg_w
+    return res
