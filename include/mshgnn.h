@@ -254,18 +254,19 @@ int mshgnn_input_grad(const mshgnn_plan* plan, const float* params, void* const*
 
 /* Adam on the flat fp32 buffers (configure_optimizers, gnnLightning.py:258-265; torch.optim.Adam defaults, no weight
  * decay / amsgrad).  step is 1-based; grads are multiplied by grad_scale first (1/world_size after a sum all-reduce).
- * All four buffers: device fp32, n elements, 16-byte aligned; updated in place.                                     */
+ * All four buffers: device fp32, n elements, 16-byte aligned; params and both moments are updated in place, grads is
+ * only read.  The bias corrections 1 - beta^step are formed in double from the fp32 betas and rounded to fp32 once. */
 int mshgnn_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, int64_t step,
                      float lr, float beta1, float beta2, float eps, float grad_scale, void* stream);
 /* The same update with the step count kept on the DEVICE: *step_count = steps taken so far (int64, device memory); the launch uses t = *step_count + 1 for
- * the bias corrections and stores t behind the update.  Nothing that changes from step to step is a launch argument, so a training step (forward, loss,
+ * the bias corrections (formed in fp64 on the device) and stores t behind the update.  Nothing that changes from step to step is a launch argument, so a training step (forward, loss,
  * backward, this) can be captured once in a HIP graph and replayed -- what torch.optim.Adam(capturable=True) does for the reference's optimizer
  * (gnnLightning.py:258-265).  morphsym_hgnn_amd.optim.FlatAdam(graph_safe=True), wrappers.GraphedTrainingStep.                                          */
 int mshgnn_adam_step_counted(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, int64_t* step_count,
                              float lr, float beta1, float beta2, float eps, float grad_scale, void* stream);
 
 /* Loss of the Lightning wrapper (gnnLightning.py:633-639): loss = mean((out - y)^2) over n elements and
- * grad_out = 2 (out - y) / n.  loss_out: device float[1].                                               */
+ * grad_out = 2 (out - y) / n (NULL: loss only).  loss_out: device float[1], cleared by the call.        */
 int mshgnn_mse_loss(const float* out, const float* y, int64_t n, float* loss_out, float* grad_out, void* stream);
 
 /* Loss of the classification wrappers (gnnLightning.py:640-648, customMetrics.py:6-25): mean cross entropy over `rows` per-foot logit

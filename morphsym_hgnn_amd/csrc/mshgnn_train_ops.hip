@@ -7,8 +7,10 @@
 // Adam on the flat fp32 buffers (configure_optimizers: optim.Adam(self.parameters(), lr), gnnLightning.py:258-265;
 // torch defaults beta=(0.9, 0.999), eps=1e-8, no weight decay, no amsgrad).  SURVEY.md section 8(f) row 2.
 // ------------------------------------------------------------------------------------------------------
-__global__ void k_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps,
-                       float bc1, float bc2_sqrt, float gscale) {
+// One element-wise sweep of the update, shared by both kernels: 16-byte accesses on whole quads, a scalar tail for the last n % 4 elements (the thread that
+// owns the quad that straddles n).  bc1 = fl32(1 - beta1^t), bc2_sqrt = fl32(sqrt(1 - beta2^t)), both formed in fp64 and rounded once by the caller.
+__device__ __forceinline__ void adam_sweep(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps,
+                                           float bc1, float bc2_sqrt, float gscale) {
     for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += (int64_t)gridDim.x * blockDim.x * 4) {
         if (i + 4 <= n) {
             f32x4 pp = *reinterpret_cast<f32x4*>(p + i), gg = *reinterpret_cast<const f32x4*>(g + i) * gscale;
@@ -28,40 +30,42 @@ __global__ void k_adam(float* p, const float* g, float* m, float* v, int64_t n, 
     }
 }
 
+__global__ void k_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps,
+                       float bc1, float bc2_sqrt, float gscale) {
+    adam_sweep(p, g, m, v, n, lr, b1, b2, eps, bc1, bc2_sqrt, gscale);
+}
+
+// The bias corrections are formed in DOUBLE from the fp32 betas and rounded to fp32 once (as torch.optim.Adam forms them in Python floats): in fp32,
+// 1 - powf(0.999f, t) cancels -- at t = 2 the difference keeps 17 of its 24 bits and the update is off by 58 units of 2^-24 of its own size.
 extern "C" int mshgnn_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, int64_t step,
                                 float lr, float beta1, float beta2, float eps, float grad_scale, void* stream) {
     if (!params || !grads || !exp_avg || !exp_avg_sq || n < 1 || step < 1) return set_err(MSHGNN_EINVAL, "bad argument to mshgnn_adam_step");
     if (((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) return set_err(MSHGNN_EINVAL, "adam buffers must be 16-byte aligned");
-    const float bc1 = 1.0f - powf(beta1, (float)step), bc2 = 1.0f - powf(beta2, (float)step);
+    const double bc1 = 1.0 - std::pow((double)beta1, (double)step), bc2 = 1.0 - std::pow((double)beta2, (double)step);
     const int blocks = (int)std::min<int64_t>((n / 4 + 255) / 256 + 1, 2048);
     hipLaunchKernelGGL(k_adam, dim3(blocks), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps,
-                       bc1, sqrtf(bc2), grad_scale);
+                       (float)bc1, (float)std::sqrt(bc2), grad_scale);
     HIPCHK(hipGetLastError());
     return MSHGNN_OK;
 }
 
 // The same update with the step count on the DEVICE (capturable in a HIP graph: nothing of the bias corrections is baked into the launch arguments).  The kernel
-// reads t = *step_count + 1 and derives 1 - beta^t itself; a one-thread launch behind it stores t.  FlatAdam(graph_safe=True), wrappers.GraphedTrainingStep.
+// reads t = *step_count + 1 and derives 1 - beta^t itself, in fp64; a one-thread launch behind it stores t.  FlatAdam(graph_safe=True), wrappers.GraphedTrainingStep.
+// beta1^t and beta2^t by binary powering in one loop (at most 63 rounds of four fp64 products; relative error <= 2 t 2^-53, nothing against the one fp32
+// rounding behind it).  One thread of the workgroup forms the two factors and hands them over through LDS: every wave doing it for itself costs the launch
+// ~0.7 us of fp64 issue at 2048 workgroups.
 __global__ void k_adam_counted(float* p, const float* g, float* m, float* v, int64_t n, const int64_t* step_count, float lr, float b1, float b2, float eps, float gscale) {
-    const float t = (float)(*step_count + 1);
-    const float bc1 = 1.0f - powf(b1, t), bc2_sqrt = sqrtf(1.0f - powf(b2, t));
-    for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += (int64_t)gridDim.x * blockDim.x * 4) {
-        if (i + 4 <= n) {
-            f32x4 pp = *reinterpret_cast<f32x4*>(p + i), gg = *reinterpret_cast<const f32x4*>(g + i) * gscale;
-            f32x4 mm = *reinterpret_cast<f32x4*>(m + i), vv = *reinterpret_cast<f32x4*>(v + i);
-            mm = b1 * mm + (1.f - b1) * gg;
-            vv = b2 * vv + (1.f - b2) * gg * gg;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) pp[e] -= lr / bc1 * mm[e] / (sqrtf(vv[e]) / bc2_sqrt + eps);
-            *reinterpret_cast<f32x4*>(p + i) = pp; *reinterpret_cast<f32x4*>(m + i) = mm; *reinterpret_cast<f32x4*>(v + i) = vv;
-        } else {
-            for (int64_t k = i; k < n; ++k) {
-                const float gg = g[k] * gscale;
-                m[k] = b1 * m[k] + (1.f - b1) * gg; v[k] = b2 * v[k] + (1.f - b2) * gg * gg;
-                p[k] -= lr / bc1 * m[k] / (sqrtf(v[k]) / bc2_sqrt + eps);
-            }
+    __shared__ float s_bc[2];
+    if (threadIdx.x == 0) {
+        double a1 = (double)b1, a2 = (double)b2, r1 = 1.0, r2 = 1.0;
+        for (int64_t t = *step_count + 1; t > 0; t >>= 1) {
+            if (t & 1) { r1 *= a1; r2 *= a2; }
+            a1 *= a1; a2 *= a2;
         }
+        s_bc[0] = (float)(1.0 - r1); s_bc[1] = (float)sqrt(1.0 - r2);
     }
+    __syncthreads();
+    adam_sweep(p, g, m, v, n, lr, b1, b2, eps, s_bc[0], s_bc[1], gscale);
 }
 __global__ void k_step_count_inc(int64_t* step_count) { *step_count += 1; }
 

@@ -3,7 +3,9 @@
 `configure_optimizers` of the reference's wrappers returns `optim.Adam(self.parameters(), lr)` (gnnLightning.py:258-265).  With this
 package's models the parameters are views of one flat fp32 buffer and their `.grad`s are views of one flat gradient buffer
 (`models._MSHGNNBase._flat_params`, `_deliver_gradients`), so the ~50 per-tensor (or multi-tensor) kernels of torch's Adam collapse into
-`mshgnn_adam_step` on the two flat buffers -- same arithmetic (torch defaults: no weight decay, no amsgrad; pinned against
+`mshgnn_adam_step` on the two flat buffers -- torch's update (defaults: no weight decay, no amsgrad) with the bias corrections 1 - beta^t formed in
+double, as torch forms them, and rounded to fp32 once; the moments and the update itself are fp32 arithmetic, every element within a few units of 2^-24 of the
+fp64 value of one step (the bounds of tests/train_ops_reference.py, held per element in tests/test_train_ops_exact_gpu.py; whole runs are compared with
 `torch.optim.Adam` in tests/test_engine_gpu.py and tests/test_wrappers.py).
 
 `FlatAdam` IS a `torch.optim.Adam` (same constructor defaults, `param_groups`, `state_dict()` / `load_state_dict()` with torch's own
@@ -21,7 +23,8 @@ from . import engine as eng
 class FlatAdam(torch.optim.Adam):
     def __init__(self, model, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, graph_safe: bool = False, **kw):
         """graph_safe: the step count lives on the device (`mshgnn_adam_step_counted`), so `step()` can be captured in a HIP graph and replayed
-        (wrappers.GraphedTrainingStep) -- the flat route's counterpart of torch.optim.Adam(capturable=True)."""
+        (wrappers.GraphedTrainingStep) -- the flat route's counterpart of torch.optim.Adam(capturable=True).  Its flat state buffers (`_m`, `_v`, `_t_dev`) are
+        allocated once and then only written in place: `load_state_dict` and a re-adoption copy into them."""
         super().__init__(model.parameters(), lr=lr, betas=betas, eps=eps, **kw)
         self._model = model
         self._graph_safe = bool(graph_safe)
@@ -53,21 +56,30 @@ class FlatAdam(torch.optim.Adam):
         return list(self._model._spec.param_offsets().values())
 
     def _adopt(self, flat, params):
-        """Start (or re-start, after the model re-created its flat buffer) the flat state from whatever torch-layout state exists."""
-        self._m, self._v = torch.zeros_like(flat), torch.zeros_like(flat)
-        self._t, self._owner = 0, flat
+        """Start (or re-start, after the model re-created its flat buffer or a state was loaded) the flat state from whatever torch-layout state exists.
+        graph_safe: once `_m`, `_v`, `_t_dev` exist (and fit the flat buffer) they are FILLED IN PLACE, never re-allocated -- a captured step
+        (wrappers.GraphedTrainingStep) addresses them."""
+        m, v = torch.zeros_like(flat), torch.zeros_like(flat)      # (filled first: the entries read below may be views of the buffers that are kept)
         steps = set()
         for (o, n), p in zip(self._offsets(), params):
             st = self.state.get(p)
             if st:
-                self._m[o:o + n].copy_(st["exp_avg"].reshape(-1))
-                self._v[o:o + n].copy_(st["exp_avg_sq"].reshape(-1))
+                m[o:o + n].copy_(st["exp_avg"].reshape(-1))
+                v[o:o + n].copy_(st["exp_avg_sq"].reshape(-1))
                 steps.add(int(st["step"]))
         if len(steps) > 1:
             raise RuntimeError("FlatAdam: the parameters' step counts differ; use torch.optim.Adam for this state")
-        self._t = steps.pop() if steps else 0
+        keep = self._graph_safe and self._m is not None and self._t_dev is not None and self._m.shape == flat.shape and self._m.device == flat.device
+        if keep:
+            self._m.copy_(m); self._v.copy_(v)
+        else:
+            self._m, self._v = m, v
+        self._t, self._owner = (steps.pop() if steps else 0), flat
         if self._graph_safe:
-            self._t_dev = torch.tensor([self._t], dtype=torch.int64, device=flat.device)
+            if keep:
+                self._t_dev.fill_(self._t)
+            else:
+                self._t_dev = torch.tensor([self._t], dtype=torch.int64, device=flat.device)
         self._publish(params)
 
     def _publish(self, params):
@@ -88,8 +100,17 @@ class FlatAdam(torch.optim.Adam):
         return super().state_dict()
 
     def load_state_dict(self, state_dict):
+        """graph_safe, with the flat state in place: the loaded moments and step count are copied INTO the existing flat buffers at once (a captured step keeps
+        addressing them, so a checkpoint loaded after the graph was built takes effect at the next replay).  lr / betas / eps are launch arguments of a captured
+        step: GraphedTrainingStep refuses to replay when the loaded group's differ from the captured ones."""
+        owner = self._owner
         super().load_state_dict(state_dict)
         self._owner = None                # re-adopt from the loaded per-parameter state at the next step
+        params = getattr(self._model, "_param_list", None)
+        if self._graph_safe and owner is not None and self._m is not None and params is not None and len(self.param_groups) == 1 \
+                and len(params) == len(self.param_groups[0]["params"]) and all(a is b for a, b in zip(params, self.param_groups[0]["params"])):
+            with torch.no_grad():
+                self._adopt(owner, params)
 
     # ---- step ---------------------------------------------------------------------------------------------------------
     @torch.no_grad()

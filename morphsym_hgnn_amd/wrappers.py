@@ -540,6 +540,11 @@ class GraphedTrainingStep:
 
     Returns the step's loss as a device tensor (a static buffer: read it before the next call).
 
+    Resuming: `optimizer.load_state_dict()` may be called after the graph was built -- FlatAdam(graph_safe=True) copies the loaded moments and step count into
+    the flat buffers the captured launches address, so the next replay continues from the loaded state (restore the parameters in place as well).  lr, betas
+    and eps are plain launch arguments of the captured Adam: a replay RAISES when the param group's differ from the captured values (a scheduler, a loaded
+    group with another lr); build a new GraphedTrainingStep for them.
+
     `index_source` (a `windows.DatasetView`): the batch is a set of DATASET INDICES of that view.  `example_batch` is then `view.batch(indices, edge_index_dict)`
     (or anything with `indices` and `edge_index_dict`); the static input is one device int64 tensor of indices, and the captured region runs the index
     mapping (`mshgnn_dataset_starts`, which bounds every index) + the step straight from the resident series + the optimizer.  `load(indices)` /
@@ -595,6 +600,16 @@ class GraphedTrainingStep:
                 optimizer.load_state_dict(snap_o)
         if hasattr(wrapper, "reset_all_metrics"):
             wrapper.reset_all_metrics()
+        self._captured = self._optimizer_arguments()
+
+    def _optimizer_arguments(self):
+        """What the captured FlatAdam launch holds as plain arguments: (lr, betas, eps) of the one param group and the addresses of the flat state."""
+        from .optim import FlatAdam
+        o = self.optimizer
+        if not isinstance(o, FlatAdam):
+            return None
+        g = o.param_groups[0]
+        return (float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), o._m.data_ptr(), o._v.data_ptr(), o._t_dev.data_ptr())
 
     @staticmethod
     def _static_copy(batch):
@@ -637,6 +652,9 @@ class GraphedTrainingStep:
                     dst[kk].copy_(vv, non_blocking=True)
 
     def __call__(self, batch=None):
+        if self._captured is not None and self._optimizer_arguments() != self._captured:
+            raise RuntimeError("GraphedTrainingStep: lr, betas or eps of the optimizer's param group (or its flat state buffers) differ from what the graph "
+                               f"captured: {self._optimizer_arguments()[:4]} now, {self._captured[:4]} captured; build a new GraphedTrainingStep")
         if batch is not None:
             self.load(batch)
         self.graph.replay()

@@ -331,7 +331,7 @@ def test_graphed_training_step_replays_the_eager_step_bit_for_bit():
     for p, q in zip(a.model.parameters(), b.model.parameters()):
         assert torch.equal(p.detach(), q.detach())
     assert int(oa._t_dev.item()) == 3 and oa.state_dict()["state"][0]["step"] == 3
-    # the device-counted Adam tracks torch.optim.Adam like the host-counted one (bias corrections from the device's powf)
+    # the device-counted Adam tracks torch.optim.Adam like the host-counted one (bias corrections formed in fp64 from the device's count)
     c = _wrapper(case, spec, batches[0]).to(dev)
     c.model.load_state_dict(params)
     oc = torch.optim.Adam(c.parameters(), lr=1e-3)
@@ -342,6 +342,64 @@ def test_graphed_training_step_replays_the_eager_step_bit_for_bit():
     assert worst < 5e-5, worst
     with pytest.raises(ValueError, match="graph_safe"):
         wrappers.GraphedTrainingStep(c, FlatAdam(c.model, lr=1e-3), batches[0])
+
+
+@pytest.mark.gpu
+def test_graphed_training_step_resumes_from_an_optimizer_state_loaded_after_capture():
+    """a captured step addresses FlatAdam's flat state buffers and holds lr / betas / eps as launch arguments.  load_state_dict after the graph
+    was built must therefore fill the SAME buffers (not re-allocate them at the next eager step): replay twice, snapshot parameters and state_dict(), replay
+    twice more (A); restore the parameters in place, load the snapshot, replay the same two batches -> A's bits, the same losses, `_m` at the same address,
+    the step count the loaded count plus two.  A param group whose lr differs from the captured one makes the replay raise."""
+    import copy
+    from morphsym_hgnn_amd import wrappers
+    torch.set_default_dtype(torch.float64)
+    case, spec, fx, x_dict, y, params, ei = helpers.load_case("a1c2_h128_L3_d3_B3")
+    dev = torch.device("cuda")
+    B = case["B"]
+    batches = []
+    for s in range(4):
+        g = torch.Generator().manual_seed(200 + s)
+        xb = {k: torch.randn(v.shape, generator=g, dtype=torch.float64) * (0.0 if k == "foot" else 1.0) + (1.0 if k == "foot" else 0.0) for k, v in x_dict.items()}
+        batches.append(_batch(xb, ei, torch.randn(y.shape, generator=g, dtype=torch.float64), B, dev))
+    w = _wrapper(case, spec, batches[0]).to(dev)
+    w.model.load_state_dict(params)
+    w.lr = 1e-3
+    w.graph_safe_optimizer = True
+    opt = w.configure_optimizers()
+    gs = wrappers.GraphedTrainingStep(w, opt, batches[0])
+    for bt in batches[:2]:
+        gs(bt)
+    torch.cuda.synchronize()
+    snap_p = [p.detach().clone() for p in w.model.parameters()]
+    snap_o = copy.deepcopy(opt.state_dict())
+    assert snap_o["state"][0]["step"] == 2
+    addr = (opt._m.data_ptr(), opt._v.data_ptr(), opt._t_dev.data_ptr())
+    losses_a = [float(gs(bt)) for bt in batches[2:]]
+    a = [p.detach().clone() for p in w.model.parameters()]
+    m_a = opt._m.clone()
+    assert any(not torch.equal(p, q) for p, q in zip(a, snap_p))
+    with torch.no_grad():
+        for p, q in zip(w.model.parameters(), snap_p):
+            p.copy_(q)
+    opt.load_state_dict(snap_o)
+    assert (opt._m.data_ptr(), opt._v.data_ptr(), opt._t_dev.data_ptr()) == addr, "load_state_dict re-allocated the flat state a captured step addresses"
+    assert int(opt._t_dev.item()) == 2
+    losses_b = [float(gs(bt)) for bt in batches[2:]]
+    torch.cuda.synchronize()
+    assert losses_b == losses_a, (losses_a, losses_b)
+    for p, q in zip(w.model.parameters(), a):
+        assert torch.equal(p.detach(), q), "the replays after load_state_dict did not continue from the loaded state"
+    assert torch.equal(opt._m, m_a) and opt._m.data_ptr() == addr[0]
+    assert int(opt._t_dev.item()) == 4 and opt.state_dict()["state"][0]["step"] == 4
+    opt.param_groups[0]["lr"] = 5e-4
+    before = [p.detach().clone() for p in w.model.parameters()]
+    with pytest.raises(RuntimeError, match="lr"):
+        gs(batches[0])
+    torch.cuda.synchronize()
+    assert all(torch.equal(p.detach(), q) for p, q in zip(w.model.parameters(), before)) and int(opt._t_dev.item()) == 4
+    opt.param_groups[0]["lr"] = 1e-3
+    gs(batches[0])
+    assert int(opt._t_dev.item()) == 5
 
 
 @pytest.mark.gpu
