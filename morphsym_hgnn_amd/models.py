@@ -26,6 +26,13 @@ from .engine import accepted_pitches
 from .topology import NODE_TYPES, RobotTopology, infer_window_edges
 
 
+def _fill_flat(flat, offsets, params):
+    """Copy the parameters into their slices of a flat fp32 buffer (state_dict order, the C-ABI's layout); returns the slices as views of the parameters' shapes."""
+    views = [flat[o:o + n].view(p.shape) for (o, n), p in zip(offsets, params)]
+    torch._foreach_copy_(views, [p.detach() for p in params])
+    return views
+
+
 class _Flatten(torch.autograd.Function):
     """named parameters -> the C-ABI's flat fp32 buffer; backward hands each parameter a view of the flat
     gradient (cast back to the parameter's dtype)."""
@@ -35,8 +42,7 @@ class _Flatten(torch.autograd.Function):
         ctx.offsets = offsets
         ctx.meta = [(p.shape, p.dtype, p.device) for p in params]
         flat = torch.zeros(size, dtype=torch.float32, device=device)
-        views = [flat[o:o + n].view(p.shape) for (o, n), p in zip(offsets, params)]
-        torch._foreach_copy_(views, [p.detach() for p in params])
+        _fill_flat(flat, offsets, params)
         return flat
 
     @staticmethod
@@ -47,95 +53,30 @@ class _Flatten(torch.autograd.Function):
         return (None, None, None, *grads)
 
 
+def _check_stash(engine, B, ticket):
+    if engine.stash_ticket(B) != ticket:
+        raise RuntimeError("the activation stash of this forward was overwritten by a later forward of the same "
+                           "batch size on the same engine; call backward before the next forward")
+
+
 class _EngineFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, flat, engine, B, training, *xs):
-        out = engine.forward(xs, flat, B, training=training)
-        ctx.engine, ctx.B, ctx.xs, ctx.flat = engine, B, xs, flat
-        ctx.ticket = engine.stash_ticket(B)
-        return out
-
-    @staticmethod
-    def backward(ctx, gout):
-        e = ctx.engine
-        if e.stash_ticket(ctx.B) != ctx.ticket:
-            raise RuntimeError("the activation stash of this forward was overwritten by a later forward of the same "
-                               "batch size on the same engine; call backward before the next forward")
-        gflat = e.backward(ctx.xs, ctx.flat, gout.contiguous().to(torch.float32), ctx.B)
-        return (gflat, None, None, None, *([None] * len(ctx.xs)))
-
-
-class _EngineFnP(torch.autograd.Function):
-    """The hot path for parameters that already live as views of the engine's flat fp32 buffer (`_MSHGNNBase._flat_params`): nothing
-    is copied on the way in, and backward hands every parameter a VIEW of the fresh flat gradient buffer the C-ABI fills -- no
-    per-parameter cast or copy kernels (the parameters are autograd inputs only so that their .grad gets populated)."""
-
-    @staticmethod
-    def forward(ctx, engine, B, flat, offsets, ddp, n_x, *args):
-        """ddp: None, or the process group (True: the default one) of ddp.flat_data_parallel -- the flat gradient is then all-reduced here, since
-        no DistributedDataParallel wrapper hooks the parameters on that route."""
-        xs = args[:n_x]
-        out = engine.forward(xs, flat, B, training=True)
-        ctx.engine, ctx.B, ctx.xs, ctx.flat, ctx.offsets, ctx.n_x, ctx.ddp = engine, B, xs, flat, offsets, n_x, ddp
-        ctx.shapes = [p.shape for p in args[n_x:]]
-        ctx.ticket = engine.stash_ticket(B)
-        return out
-
-    @staticmethod
-    def backward(ctx, gout):
-        e = ctx.engine
-        if e.stash_ticket(ctx.B) != ctx.ticket:
-            raise RuntimeError("the activation stash of this forward was overwritten by a later forward of the same "
-                               "batch size on the same engine; call backward before the next forward")
-        n_flat = ctx.flat.numel()
-        full = torch.empty(n_flat + 16, dtype=torch.float32, device=ctx.flat.device)      # a fresh buffer per backward: .grad views never alias
-        gflat = e.backward(ctx.xs, ctx.flat, gout.contiguous().to(torch.float32), ctx.B, grad_flat=full[:n_flat])
-        if ctx.ddp is not None:      # ddp.flat_data_parallel on the two-call route: the same single exchange the fused training step makes
-            from .ddp import exchange_flat_gradient_
-            group, weighted, live = (*ctx.ddp, None)[:3]
-            gflat.div_(exchange_flat_gradient_(full, n_flat, ctx.B, None if group is True else group, weighted, live))
-        grads = [gflat[o:o + n].view(shape) for (o, n), shape in zip(ctx.offsets, ctx.shapes)]
-        return (None, None, None, None, None, None, *([None] * ctx.n_x), *grads)
-
-
-class _EngineFnFast(torch.autograd.Function):
-    """Single-process fast path: like _EngineFnP, but the parameter gradients do not travel through autograd at all -- 50 AccumulateGrad
-    nodes and 50 freshly sliced views per step cost more host time than the whole step takes on the GPU.  The C-ABI writes the flat
-    gradient into a persistent buffer whose per-parameter views are cached; backward assigns them to .grad when the gradients were
-    cleared (zero_grad(set_to_none=True), the first step) and ADDS a fresh gradient in place otherwise (accumulation, or gradients
-    zeroed in place), which is what autograd's accumulation would have produced.  Not used under torch.distributed (DDP needs the
-    per-parameter autograd hooks: _EngineFnP)."""
-
-    @staticmethod
-    def forward(ctx, anchor, model, engine, B, *xs):
-        out = engine.forward(xs, model._flat, B, training=True)
-        ctx.model, ctx.engine, ctx.B, ctx.xs, ctx.flat = model, engine, B, xs, model._flat
-        ctx.ticket = engine.stash_ticket(B)
-        return out
-
-    @staticmethod
-    def backward(ctx, gout):
-        e, m = ctx.engine, ctx.model
-        if e.stash_ticket(ctx.B) != ctx.ticket:
-            raise RuntimeError("the activation stash of this forward was overwritten by a later forward of the same "
-                               "batch size on the same engine; call backward before the next forward")
-        g32 = gout.contiguous().to(torch.float32)
-        _deliver_gradients(m, ctx.flat, lambda target: e.backward(ctx.xs, ctx.flat, g32, ctx.B, grad_flat=target))
-        return (None, None, None, None, *([None] * len(ctx.xs)))
-
-
-class _EngineFnIn(torch.autograd.Function):
-    """Any route of forward() when some x_dict tensor requires grad: the autograd inputs are the CALLER's tensors (the engine's cast / re-pitched copies stay
-    out of the graph), and backward returns each one its gradient -- same shape, dtype and device -- from mshgnn_input_grad (models the reference's
-    autograd through apply_symmetry and the encoder, hgnn_c2.py:150-151).  The parameters travel as on the route without input gradients:
-      "fast": device views of the flat buffer, gradients delivered outside autograd (_EngineFnFast);  "p": the parameters as autograd inputs (_EngineFnP,
-      torch.distributed);  "flat": the _Flatten output of host parameters (_EngineFn);  None: every parameter frozen -- the backward passes no gradient
-      buffer (activation backward only) and no .grad is touched.
-    cfg: (model, engine, B, flat, cast inputs, route, offsets, ddp, number of parameter tensors); tensors: (*parameter tensors, *caller's inputs)."""
+    """The two-call route of forward(): engine.forward here, engine.backward (and mshgnn_input_grad) in backward.  Double backward is not supported on any route.
+    cfg: (model, engine, B, flat, cast inputs, route, number of parameter tensors); tensors: (*parameter tensors, *caller's inputs).  The parameters travel by `route`:
+      "fast": single process, parameters are device views of the flat buffer.  Their gradients do not travel through autograd at all -- 50 AccumulateGrad nodes and
+              50 freshly sliced views per step cost more host time than the whole step takes on the GPU: the C-ABI writes the flat gradient into a persistent buffer
+              whose per-parameter views are cached (_deliver_gradients).  The one parameter tensor is the model's `_anchor`, there only so that the output requires grad.
+      "p":    the same device views under torch.distributed, as autograd inputs: DistributedDataParallel needs the per-parameter autograd hooks.  Backward hands every
+              parameter a VIEW of the flat gradient (no per-parameter cast or copy kernels), in a fresh buffer per backward so that .grad views never alias; under
+              ddp.flat_data_parallel no DDP wrapper hooks the parameters and the flat gradient is exchanged here (_MSHGNNBase._flat_exchange).
+      "flat": host parameters; the one parameter tensor is their _Flatten output, which stands in for cfg's flat buffer.
+      None:   every parameter frozen -- the backward passes no gradient buffer (activation backward only) and no .grad is touched.
+    The caller's x_dict tensors are autograd inputs iff one of them requires grad (the engine's cast / re-pitched copies stay out of the graph); backward then returns
+    each one its gradient -- same shape, dtype and device -- from mshgnn_input_grad (models the reference's autograd through apply_symmetry and the encoder,
+    hgnn_c2.py:150-151).  Otherwise none is passed and mshgnn_input_grad is not called."""
 
     @staticmethod
     def forward(ctx, cfg, *tensors):
-        model, engine, B, flat, xs, route, offsets, ddp, n_p = cfg
+        model, engine, B, flat, xs, route, n_p = cfg
         if route == "flat":
             flat = tensors[0]
         out = engine.forward(xs, flat, B, training=True)
@@ -147,11 +88,9 @@ class _EngineFnIn(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, gout):
-        model, e, B, _, xs, route, offsets, ddp, n_p = ctx.cfg
+        model, e, B, _, xs, route, n_p = ctx.cfg
         flat = ctx.flat
-        if e.stash_ticket(B) != ctx.ticket:
-            raise RuntimeError("the activation stash of this forward was overwritten by a later forward of the same "
-                               "batch size on the same engine; call backward before the next forward")
+        _check_stash(e, B, ctx.ticket)
         g32 = gout.contiguous().to(torch.float32)
         pgrads = [None] * n_p
         if route is None:
@@ -162,13 +101,14 @@ class _EngineFnIn(torch.autograd.Function):
             pgrads = [e.backward(xs, flat, g32, B)]
         else:
             n_flat = flat.numel()
-            full = torch.empty(n_flat + 16, dtype=torch.float32, device=flat.device)
+            full = torch.empty(n_flat + 16, dtype=torch.float32, device=flat.device)      # a fresh buffer per backward: .grad views never alias
             gflat = e.backward(xs, flat, g32, B, grad_flat=full[:n_flat])
-            if ddp is not None:
-                from .ddp import exchange_flat_gradient_
-                group, weighted, live = (*ddp, None)[:3]
-                gflat.div_(exchange_flat_gradient_(full, n_flat, B, None if group is True else group, weighted, live))
-            pgrads = [gflat[o:o + n].view(shape) for (o, n), shape in zip(offsets, ctx.shapes)]
+            div = model._flat_exchange(full, n_flat, B)
+            if div is not None:
+                gflat.div_(div)
+            pgrads = [gflat[o:o + n].view(shape) for (o, n), shape in zip(model._spec.param_offsets().values(), ctx.shapes)]
+        if not ctx.xin:
+            return (None, *pgrads)
         want = [t for t, (_, _, _, rg) in zip(e.types, ctx.xin) if rg]
         direct = {t: dt for t, (shape, dt, dev, _) in zip(e.types, ctx.xin) if dt in (torch.float32, torch.float64)}
         pitches = {t: shape[1] for t, (shape, _, _, _) in zip(e.types, ctx.xin)}
@@ -180,6 +120,31 @@ class _EngineFnIn(torch.autograd.Function):
             g.update(e.input_grad(B, flat, ts, dt, pitches))
         xgrads = [g[t].to(device=dev, dtype=dt) if t in g else None for t, (_, dt, dev, _) in zip(e.types, ctx.xin)]
         return (None, *pgrads, *xgrads)
+
+
+def _several_processes():
+    import torch.distributed as dist
+    return dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+
+
+def _window_recipe_ok(spec, r, desc, dtype, training):
+    """The device-free part of `_MSHGNNBase._window_route`: can a store of this recipe, descriptor and dtype feed the series entry points of a model with `spec`
+    (training: mshgnn_step_*_series[_std]; evaluation: mshgnn_forward_series)?  Mirrors what the library's check_window_desc refuses, so that such a batch is
+    assembled instead of raising."""
+    if spec is None or dtype not in ("bf16", "x3", "f32") or not desc.fast_layout:      # (spec None: the model has not seen its lazy-initialising forward yet)
+        return False
+    if r.normalize and not 2 <= r.history <= 256:      # (what the standardising encoders refuse)
+        return False
+    if list(r.node_types) != list(spec.node_types) or any(r.num_nodes[t] != spec.num_nodes[t] or r.width(t) != spec.widths[t] for t in r.node_types):
+        return False
+    if training and not r.label_cols:      # the training steps compute the loss from the recipe's labels; evaluation runs without
+        return False
+    # Node rows of several runs need history >= 8 (the encoders take a chunk's 8 elements from at most two runs): the Solo recipes.  Evaluation and the standardised
+    # training steps check it.  The plain training steps lack the check, in the library (several_runs_need_history8 = false there) and therefore here: closing that
+    # changes what the wrappers must fall back on and belongs in a change of its own.
+    if r.history < 8 and desc.n_runs > desc.n_rows and (r.normalize or not training):
+        return False
+    return True
 
 
 def _deliver_gradients(m, flat, fresh, scale=None):
@@ -249,10 +214,9 @@ class _FusedStepFn(torch.autograd.Function):
             raise RuntimeError("the pending gradient of this training step was overwritten by a later fused training step of the same "
                                "model; call backward before the next step")
         pend, scale = m._gpend, gl.to(device=m._gpend.device, dtype=torch.float32)
-        if m._flat_ddp is not None:      # data parallel: ONE sum-all-reduce of the flat gradient (weighted by the ranks' window counts: ddp.py)
-            from .ddp import exchange_flat_gradient_
-            group = None if m._flat_ddp is True else m._flat_ddp
-            scale = scale / exchange_flat_gradient_(m._gpend_full, pend.numel(), ctx.windows, group, m._flat_ddp_weighted, getattr(m, "_flat_ddp_live", None))
+        div = m._flat_exchange(m._gpend_full, pend.numel(), ctx.windows)
+        if div is not None:
+            scale = scale / div
         _deliver_gradients(m, ctx.flat, lambda target: torch.mul(pend, scale, out=target) if target is not None else pend * scale)
         return (None,) * n_in
 
@@ -278,7 +242,7 @@ class _MSHGNNBase(nn.Module):
         self._flat: Optional[torch.Tensor] = None
         self._flat_ok = False            # parameters are fp32 views into self._flat (device-resident fast path)
         self._param_list = None
-        self._gflat = None               # persistent flat gradient + its cached per-parameter views (_EngineFnFast)
+        self._gflat = None               # persistent flat gradient + its cached per-parameter views (_EngineFn's "fast" route)
         self._gpend = None               # the flat gradient a fused training step computed, until its backward() delivers it
         self._gpend_id = 0
         self._flat_ddp = None            # ddp.flat_data_parallel: the process group the fused training step all-reduces its flat gradient over
@@ -333,9 +297,7 @@ class _MSHGNNBase(nn.Module):
         params = self._params_in_flat_order()
         flat = torch.zeros(self._spec.flat_size(), dtype=torch.float32, device=pdev)
         with torch.no_grad():
-            for (o, n), p in zip(self._spec.param_offsets().values(), params):
-                v = flat[o:o + n].view(p.shape)
-                v.copy_(p.detach())
+            for p, v in zip(params, _fill_flat(flat, self._spec.param_offsets().values(), params)):
                 p.data = v
         self._flat, self._flat_ok = flat, True
         self._gflat = self._gviews = self._gpend = None
@@ -347,6 +309,42 @@ class _MSHGNNBase(nn.Module):
             sd = dict(self.named_parameters())
             self._param_list = [sd[k] for k in self._spec.param_offsets().keys()]
         return self._param_list
+
+    def _host_flat(self, pdev, fill):
+        """Parameters on the host: their device staging buffer (self._flat, which is NOT their storage: _flat_ok stays False), holding a copy of them when `fill`."""
+        if self._flat is None or self._flat.device != pdev or self._flat_ok:
+            self._flat, self._flat_ok = torch.zeros(self._spec.flat_size(), dtype=torch.float32, device=pdev), False
+        if fill:
+            with torch.no_grad():
+                _fill_flat(self._flat, self._spec.param_offsets().values(), self._params_in_flat_order())
+        return self._flat
+
+    def _param_route(self, pdev, need_grad):
+        """How the parameters reach the engine on the two-call route: (flat buffer, _EngineFn route, the parameter tensors autograd sees)."""
+        params = self._params_in_flat_order()
+        if params[0].device.type == "cuda":
+            # parameters on the device: they are (made) views of the flat fp32 buffer -- no copy in, no copy out
+            flat = self._flat_params(pdev)
+            if not need_grad:
+                return flat, None, []
+            if _several_processes():      # gradients through autograd: DDP's hooks see them
+                return flat, "p", list(params)
+            return flat, "fast", [self._anchor]
+        # parameters on the host: a device copy per forward (the slow path: lazy-init call, CPU-pinned evaluation)
+        flat = self._host_flat(pdev, fill=not need_grad)
+        if not need_grad:
+            return flat, None, []
+        spec = self._spec
+        return None, "flat", [_Flatten.apply(spec.flat_size(), pdev, list(spec.param_offsets().values()), *params)]
+
+    def _flat_exchange(self, full, n_flat, windows):
+        """ddp.flat_data_parallel: ONE sum-all-reduce of the flat gradient in full[:n_flat] (the spare elements behind it carry this rank's window count: ddp.py).
+        Returns what to divide the summed gradient by, or None when no group is set.  The settings are read when a backward runs, not when its forward did:
+        ddp.flat_data_parallel set or cleared between the two takes effect in that backward."""
+        if self._flat_ddp is None:
+            return None
+        from .ddp import exchange_flat_gradient_
+        return exchange_flat_gradient_(full, n_flat, windows, None if self._flat_ddp is True else self._flat_ddp, self._flat_ddp_weighted, getattr(self, "_flat_ddp_live", None))
 
     # ---- construction helpers ---------------------------------------------------------------------
     def _build_convs(self, mean_rels):
@@ -436,12 +434,7 @@ class _MSHGNNBase(nn.Module):
             if nn_[t] != spec.num_nodes[t] or not _pitch_ok(x_dict[t], spec.widths[t]):
                 raise ValueError(f"x_dict['{t}'] does not match the compiled topology "
                                  f"({nn_[t]} nodes x {x_dict[t].shape[1]} vs {spec.num_nodes[t]} x {spec.widths[t]})")
-        if B not in self._checked_batches:   # one host-side check per batch size: B copies of the compiled graph
-            for et in self._edge_types:
-                s, _, d = et
-                if infer_window_edges(edge_index_dict[et], nn_[s], nn_[d], B) != spec.topology.edges(et):
-                    raise ValueError(f"edge_index_dict[{et}] differs from the topology this model was compiled for")
-            self._checked_batches.add(B)
+        self._check_edges(edge_index_dict, B)
         if not self._fused_activation:
             return spec, B, None, None
         pdev = self.decoder.weight.device
@@ -454,8 +447,23 @@ class _MSHGNNBase(nn.Module):
             pdev = torch.device("cuda", torch.cuda.current_device())
         return spec, B, self._engine(pdev), pdev
 
+    def _check_edges(self, edge_index_dict, B):
+        """One host-side check per batch size: the batch is B copies of the compiled graph."""
+        if B in self._checked_batches:
+            return
+        spec = self._spec
+        for et in self._edge_types:
+            s, _, d = et
+            if infer_window_edges(edge_index_dict[et], spec.num_nodes[s], spec.num_nodes[d], B) != spec.topology.edges(et):
+                raise ValueError(f"edge_index_dict[{et}] differs from the topology this model was compiled for")
+        self._checked_batches.add(B)
+
     def _shape_output(self, out, spec, B, in_dev, in_dtype):
         out = out.to(device=in_dev, dtype=in_dtype if in_dtype in (torch.float64, torch.float32) else torch.float32)
+        return self._view_output(out, spec, B)
+
+    @staticmethod
+    def _view_output(out, spec, B):
         if spec.output_is_window_major:
             return out.view(B, -1)      # ms_foot_decoder: [B, 4*3]   (hgnn_c2.py:184-189)
         if spec.kind in ("k4_com", "c2_com"):
@@ -476,8 +484,7 @@ class _MSHGNNBase(nn.Module):
             return None
         if any(x_dict[t].requires_grad for t in self._node_types):      # the caller wants x.grad too: the two-call route (forward() + backward) delivers it
             return None
-        import torch.distributed as dist
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1 and self._flat_ddp is None:
+        if self._flat_ddp is None and _several_processes():
             return None
         in_dev, in_dtype = x_dict[self._node_types[0]].device, x_dict[self._node_types[0]].dtype
         xs = e.cast_inputs(x_dict)
@@ -493,35 +500,12 @@ class _MSHGNNBase(nn.Module):
     def fused_training_step_windows(self, batch):
         """`fused_training_step` for a `windows.WindowBatch`: the encoder gathers the batch's inputs straight from the sequence's resident
         series (mshgnn_step_mse_series / mshgnn_step_ce_series, standardised recipes: mshgnn_step_mse_series_std / mshgnn_step_ce_series_std -- no
-        separate assembly pass over the windows); the labels (and the materialised windows) are left on the batch.  Returns (out, loss) or None when
-        this route does not apply: the model has not seen its lazy-initialising forward yet, a plan other than bf16 / split-bf16 on the LDS-resident
-        kernels, a store whose dtype is not the plan's input dtype or that is not fast-layout, a standardised recipe whose history is outside [2, 256]
-        or shorter than 8 with node rows of several runs, or a recipe that differs from the model's node types and widths, plus fused_training_step's
-        own conditions."""
-        spec = self._spec
-        store, B = batch.store, batch.batch_size
-        r = store.recipe
-        if spec is None or not self._fused_activation or store.dtype not in ("bf16", "x3", "f32") or not store.desc.fast_layout or not r.label_cols:
+        separate assembly pass over the windows); the labels (and the materialised windows) are left on the batch.  Returns (out, loss), or None when
+        this route does not apply (`_window_route` with training=True is the rule); the caller then assembles the windows and takes `fused_training_step`."""
+        e = self._window_route(batch, training=True)
+        if e is None:
             return None
-        if r.normalize and (not 2 <= r.history <= 256 or (r.history < 8 and store.desc.n_runs > store.desc.n_rows)):      # (what the standardising encoders refuse: assembled)
-            return None
-        if list(r.node_types) != list(spec.node_types) or any(r.num_nodes[t] != spec.num_nodes[t] or r.width(t) != spec.widths[t] for t in r.node_types):
-            return None
-        params = self._params_in_flat_order()
-        if not torch.is_grad_enabled() or params[0].device.type != "cuda" or params[0].device != store.device or not all(p.requires_grad for p in params):
-            return None
-        import torch.distributed as dist
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1 and self._flat_ddp is None:
-            return None
-        e = self._engine(store.device)
-        if e.generic or getattr(e, "padded", False) or e.storage not in ("bf16", "x3") or (e.storage == "bf16") != (store.dtype == "bf16"):      # (the split plan gathers fp32 series)
-            return None
-        if B not in self._checked_batches:   # one host-side check per batch size: B copies of the compiled graph
-            for et in self._edge_types:
-                s_, _, d_ = et
-                if infer_window_edges(batch.edge_index_dict[et], spec.num_nodes[s_], spec.num_nodes[d_], B) != spec.topology.edges(et):
-                    raise ValueError(f"edge_index_dict[{et}] differs from the topology this model was compiled for")
-            self._checked_batches.add(B)
+        spec, store, B, r = self._spec, batch.store, batch.batch_size, batch.store.recipe
         self._flat_params(store.device)
         if r.normalize:
             step = e.step_mse_series_std if spec.regression else e.step_ce_series_std
@@ -540,38 +524,42 @@ class _MSHGNNBase(nn.Module):
         """The evaluation forward for a `windows.WindowBatch` without autograd: the encoder gathers the batch's inputs straight from the sequence's
         resident series (mshgnn_forward_series -- no assembly pass, no materialised windows; standardised recipes included) and the labels are left
         on the batch.  Returns the output as forward() does -- bit-identical to forward(batch.x_dict, ...) -- or None when this route does not
-        apply: gradients enabled, the model has not seen its lazy-initialising forward yet, a plan other than bf16 / split-bf16 on the LDS-resident
-        kernels, parameters on the host or another device, a store whose dtype is not the plan's input dtype or that is not fast-layout, or whose
-        recipe differs from the model's node types and widths."""
-        spec = self._spec
-        store, B = batch.store, batch.batch_size
-        r = store.recipe
-        if torch.is_grad_enabled() or spec is None or not self._fused_activation or store.dtype not in ("bf16", "x3", "f32") or not store.desc.fast_layout:
+        apply (`_window_route` with training=False is the rule); the caller then assembles the windows and calls forward()."""
+        e = self._window_route(batch, training=False)
+        if e is None:
             return None
-        if r.normalize and not 2 <= r.history <= 256:
-            return None
-        if list(r.node_types) != list(spec.node_types) or any(r.num_nodes[t] != spec.num_nodes[t] or r.width(t) != spec.widths[t] for t in r.node_types):
-            return None
-        params = self._params_in_flat_order()
-        if params[0].device.type != "cuda" or params[0].device != store.device:
-            return None
-        e = self._engine(store.device)
-        if e.generic or e.storage not in ("bf16", "x3") or (e.storage == "bf16") != (store.dtype == "bf16") or not hasattr(e.lib, "mshgnn_forward_series"):
-            return None
-        if r.label_cols and len(r.label_cols) != e.n_out * (spec.out_channels if spec.regression else 1):
-            return None
-        if r.history < 8 and store.desc.n_runs > store.desc.n_rows:      # (node rows of several runs shorter than a chunk: the Solo recipes -- assembled)
-            return None
-        if B not in self._checked_batches:   # one host-side check per batch size: B copies of the compiled graph
-            for et in self._edge_types:
-                s_, _, d_ = et
-                if infer_window_edges(batch.edge_index_dict[et], spec.num_nodes[s_], spec.num_nodes[d_], B) != spec.topology.edges(et):
-                    raise ValueError(f"edge_index_dict[{et}] differs from the topology this model was compiled for")
-            self._checked_batches.add(B)
+        spec, store, B = self._spec, batch.store, batch.batch_size
         y, q, _, out = e.forward_series(store, batch.starts, self._flat_params(store.device))
         if y is not None:
             batch._labels_from_step(None, y, q)
         return self._shape_output(out, spec, B, store.device, torch.float32)
+
+    def _window_route(self, batch, training):
+        """The engine for `fused_training_step_windows` (training) or `forward_windows` (evaluation) on this batch, or None when the batch takes the assembled
+        route instead.  Cheap checks first (_window_recipe_ok), then the parameters' device and the grad mode; the engine is looked up only after those pass."""
+        store, r = batch.store, batch.store.recipe
+        if not self._fused_activation or not _window_recipe_ok(self._spec, r, store.desc, store.dtype, training):
+            return None
+        params = self._params_in_flat_order()
+        if params[0].device.type != "cuda" or params[0].device != store.device or torch.is_grad_enabled() != training:
+            return None
+        if training:
+            # fused_training_step's own conditions: torch's DDP needs the per-parameter autograd hooks, and a frozen parameter needs the two-call route
+            if not all(p.requires_grad for p in params) or (self._flat_ddp is None and _several_processes()):
+                return None
+        e = self._engine(store.device)
+        if e.generic or e.storage not in ("bf16", "x3") or (e.storage == "bf16") != (store.dtype == "bf16"):      # (the split plan gathers fp32 series)
+            return None
+        if training and getattr(e, "padded", False):      # engine.PaddedEngine has no series steps (its forward_series pads the parameters itself)
+            return None
+        if not training:
+            if not hasattr(e.lib, "mshgnn_forward_series"):
+                return None
+            # evaluation leaves labels on the batch only when the recipe has some, and then they must be the model's targets (training: the library's step checks them)
+            if r.label_cols and len(r.label_cols) != e.n_out * (self._spec.out_channels if self._spec.regression else 1):
+                return None
+        self._check_edges(batch.edge_index_dict, batch.batch_size)
+        return e
 
     def forward(self, x_dict, edge_index_dict):
         spec, B, e, pdev = self._prepare(x_dict, edge_index_dict)
@@ -579,64 +567,17 @@ class _MSHGNNBase(nn.Module):
             return self._forward_operators(x_dict, edge_index_dict, B)
         in_dev, in_dtype = x_dict[self._node_types[0]].device, x_dict[self._node_types[0]].dtype
         xs = e.cast_inputs(x_dict)
-        params = self._params_in_flat_order()
-        offsets = list(spec.param_offsets().values())
-        need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in params)
-        if torch.is_grad_enabled() and any(x_dict[t].requires_grad for t in self._node_types):
-            out = self._forward_input_grad(x_dict, xs, e, B, pdev, params, offsets, need_grad)
-            return self._shape_output(out, spec, B, in_dev, in_dtype)
-        if params[0].device.type == "cuda":
-            # parameters on the device: they are (made) views of the flat fp32 buffer -- no copy in, no copy out
-            flat = self._flat_params(pdev)
-            if need_grad:
-                import torch.distributed as dist
-                if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-                    out = _EngineFnP.apply(e, B, flat, offsets, None if self._flat_ddp is None else (self._flat_ddp, self._flat_ddp_weighted, getattr(self, "_flat_ddp_live", None)), len(xs), *xs, *params)      # gradients through autograd: DDP's hooks see them
-                else:
-                    out = _EngineFnFast.apply(self._anchor, self, e, B, *xs)
-            else:
-                with torch.no_grad():
-                    out = e.forward(xs, flat, B, training=False)
+        grad_on = torch.is_grad_enabled()
+        need_grad = grad_on and any(p.requires_grad for p in self._params_in_flat_order())
+        # the caller's tensors enter autograd only when one of them wants its gradient (_EngineFn)
+        xin = [x_dict[t] for t in self._node_types] if grad_on and any(x_dict[t].requires_grad for t in self._node_types) else []
+        flat, route, ptens = self._param_route(pdev, need_grad)
+        if route is None and not xin:
+            with torch.no_grad():
+                out = e.forward(xs, flat, B, training=False)
         else:
-            # parameters on the host: a device copy per forward (the slow path: lazy-init call, CPU-pinned evaluation)
-            if self._flat is None or self._flat.device != pdev or self._flat_ok:
-                self._flat, self._flat_ok = torch.zeros(spec.flat_size(), dtype=torch.float32, device=pdev), False
-            if need_grad:
-                flat = _Flatten.apply(spec.flat_size(), pdev, offsets, *params)
-                out = _EngineFn.apply(flat, e, B, True, *xs)
-            else:
-                with torch.no_grad():
-                    views = [self._flat[o:o + n].view(p.shape) for (o, n), p in zip(offsets, params)]
-                    torch._foreach_copy_(views, [p.detach() for p in params])
-                    out = e.forward(xs, self._flat, B, training=False)
+            out = _EngineFn.apply((self, e, B, flat, xs, route, len(ptens)), *ptens, *xin)
         return self._shape_output(out, spec, B, in_dev, in_dtype)
-
-    def _forward_input_grad(self, x_dict, xs, e, B, pdev, params, offsets, need_grad):
-        """forward() when some input requires grad (_EngineFnIn): the parameters take the route they take without input gradients, frozen ones none."""
-        spec = self._spec
-        xin = [x_dict[t] for t in self._node_types]
-        if params[0].device.type == "cuda":
-            flat = self._flat_params(pdev)
-            route, ptens, ddp = None, [], None
-            if need_grad:
-                import torch.distributed as dist
-                if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-                    route, ptens = "p", list(params)
-                    ddp = None if self._flat_ddp is None else (self._flat_ddp, self._flat_ddp_weighted, getattr(self, "_flat_ddp_live", None))
-                else:
-                    route = "fast"
-        else:
-            if self._flat is None or self._flat.device != pdev or self._flat_ok:
-                self._flat, self._flat_ok = torch.zeros(spec.flat_size(), dtype=torch.float32, device=pdev), False
-            if need_grad:
-                flat, route, ptens, ddp = None, "flat", [_Flatten.apply(spec.flat_size(), pdev, offsets, *params)], None
-            else:
-                with torch.no_grad():
-                    views = [self._flat[o:o + n].view(p.shape) for (o, n), p in zip(offsets, params)]
-                    torch._foreach_copy_(views, [p.detach() for p in params])
-                flat, route, ptens, ddp = self._flat, None, [], None
-        cfg = (self, e, B, flat, xs, route, offsets, ddp, len(ptens))
-        return _EngineFnIn.apply(cfg, *ptens, *xin)
 
     def _forward_operators(self, x_dict, edge_index_dict, B):
         """The reference's forward (hgnn_c2.py:133-182, hgnn_k4.py:146-196, hgnn.py:57-62, hgnn_*_com.py) operator by operator, for models built with
@@ -673,11 +614,7 @@ class _MSHGNNBase(nn.Module):
         out = self.decoder(x[spec.out_type])
         n_out = spec.num_nodes[spec.out_type]
         out = (out.view(B, n_out, -1) * spec.output_mask().to(out.device, out.dtype).unsqueeze(0)).reshape(B * n_out, -1)
-        if spec.output_is_window_major:
-            return out.view(B, -1)
-        if spec.kind in ("k4_com", "c2_com"):
-            return out.view(B, spec.num_nodes["base"], spec.out_channels)
-        return out
+        return self._view_output(out, spec, B)
 
     # ---- reference helper kept for API compatibility ------------------------------------------------------
     def apply_symmetry(self, x_dict):

@@ -1,4 +1,4 @@
-"""Gradients with respect to the inputs (mshgnn_input_grad, Engine.input_grad, models._EngineFnIn) against the fp64 oracle BIT FOR BIT, on rounding-free
+"""Gradients with respect to the inputs (mshgnn_input_grad, Engine.input_grad, models._EngineFn) against the fp64 oracle BIT FOR BIT, on rounding-free
 data (tests/exact_data.py with enc_cover=True: on it dx = m . (dY_enc @ W_enc) is a short sum of exact products in every plan's operand form, and every
 input type's dx is non-zero in every 16-column tile -- tests/test_exact_data.py proves that, (a)-(d), on the host for every (model, batch) used here).
 A wrong column chunk, a dropped K block, a mis-indexed node row or a missing sign flip is then a failure, where a tolerance could miss it.  The split
@@ -13,7 +13,7 @@ Matrix:
     hidden 200 and 1000 (served at 256 and 1024).
   * MiniCheetah-K4 classification at 3 layers through backward(gout) (live joint F = 300 and foot F = 900: 5- and 15-chunk types); after backward_ce
     (softmax: not exact) the same launch against its own operands (helpers.check_input_grad_against_own_operands).
-  * One module through _EngineFnIn, with fp32 and fp64 leaves mixed across types.
+  * One module through _EngineFn, with fp32 and fp64 leaves mixed across types.
 The references are the oracle alone: the host proofs live in tests/test_exact_data.py, which runs check_exact on exactly these cases.
 """
 from functools import lru_cache
@@ -148,7 +148,7 @@ def test_classification_input_grad_is_the_oracle_bit_for_bit(monkeypatch, model,
 
 
 def test_module_input_grad_with_mixed_leaf_dtypes_is_the_oracle_bit_for_bit(monkeypatch):
-    """models._EngineFnIn: fp64 base and foot leaves, an fp32 joint leaf (one launch per dtype), each given its gradient in its own dtype."""
+    """models._EngineFn: fp64 base and foot leaves, an fp32 joint leaf (one launch per dtype), each given its gradient in its own dtype."""
     from tests.test_models import _build
     model, B = MODULE_CASE
     spec, case, ref = _reference(model, B)

@@ -1,4 +1,4 @@
-"""Gradients with respect to the model's inputs on the fused engines (mshgnn_input_grad, Engine.input_grad, models._EngineFnIn): x_dict leaves that
+"""Gradients with respect to the model's inputs on the fused engines (mshgnn_input_grad, Engine.input_grad, models._EngineFn): x_dict leaves that
 require grad get the fp64 oracle's gradient (the reference's autograd through apply_symmetry and the encoder), in their own dtype / shape / device,
 whatever the parameters do -- and the parameter gradients stay bit-identical to the same step without input gradients."""
 import pytest
