@@ -1190,24 +1190,70 @@ __device__ __forceinline__ void fs_run(const FP& wp, typename Prec<T>::Acc (&acc
 // the tail's global operands of one pass (decoder weights / bias, output mask, labels of this thread's rows): requested in one go -- by the tail itself, or
 // (compile-time programs) before the last layer's store phase, so that the tail starts with its operands in registers instead of behind that phase's drain
 template <int DMAX, int NPP> struct DecOps { float Wv[DMAX][8], bv[DMAX], mk[NPP][DMAX], yv[NPP][DMAX]; int labv[NPP]; };
-template <int DMAX, int NPP>
+// What a kernel knows about its tail at compile time.  DecDyn: nothing (the interpreting kernels: dout / n_out from the arguments, any batch).  DecFacts (a
+// compile-time program): the program's output channels and output nodes, and FULL = every tile of the launch is whole -- the clamps and the `live` / `ok`
+// selects go, a window's n_out x dout labels / outputs move as vectors, and every global address is a uniform base + one 32-bit lane offset.  Same arithmetic.
+struct DecDyn { static constexpr int DOUT = 0, NOUT = 0; static constexpr bool FULL = false; };
+template <int DOUT_, int NOUT_, bool FULL_> struct DecFacts { static constexpr int DOUT = DOUT_, NOUT = NOUT_; static constexpr bool FULL = FULL_; };
+typedef const float __attribute__((address_space(1))) gfloat;
+typedef float __attribute__((address_space(1))) gwfloat;
+// x + (x of the lane 16 / 32 away): what `x += __shfl_xor(x, 16 / 32, 64)` adds, as one row / half swap instead of a round trip through the LDS crossbar
+__device__ __forceinline__ float xor16_sum(float x) {
+    const auto r = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, x), __builtin_bit_cast(unsigned, x), false, false);      // rows [0 0 2 2] and [1 1 3 3]
+    return __builtin_bit_cast(float, (unsigned)r[0]) + __builtin_bit_cast(float, (unsigned)r[1]);      // (own + other or other + own: fp32 addition commutes, same bits)
+}
+__device__ __forceinline__ float xor32_sum(float x) {
+    const auto r = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, x), __builtin_bit_cast(unsigned, x), false, false);      // halves [0 0] and [1 1]
+    return __builtin_bit_cast(float, (unsigned)r[0]) + __builtin_bit_cast(float, (unsigned)r[1]);
+}
+template <int DMAX, int NPP, class K = DecDyn>
 __device__ __forceinline__ void decoder_ops_load_w(const StackArgs& a, int tid, DecOps<DMAX, NPP>& o) {      // decoder weights / bias: once per tile
     const int c = tid & 15;
     const float* W = a.params + a.off_dec_w;
+    const int dout = K::DOUT ? K::DOUT : a.dout;
 #pragma unroll
     for (int dd = 0; dd < DMAX; ++dd) {
-        const int dc = min(dd, a.dout - 1);
+        const int dc = min(dd, dout - 1);
         const f32x4 wa = *reinterpret_cast<const f32x4*>(W + dc * H + c * 8), wb = *reinterpret_cast<const f32x4*>(W + dc * H + c * 8 + 4);
         o.Wv[dd][0] = wa[0]; o.Wv[dd][1] = wa[1]; o.Wv[dd][2] = wa[2]; o.Wv[dd][3] = wa[3];
         o.Wv[dd][4] = wb[0]; o.Wv[dd][5] = wb[1]; o.Wv[dd][6] = wb[2]; o.Wv[dd][7] = wb[3];
         o.bv[dd] = a.params[a.off_dec_b + dc];
     }
 }
-template <int THREADS, int DMAX, int NPP>
+// (compile-time facts) whether any lane's pass slot i holds a node at all
+template <int THREADS, class K> __device__ __forceinline__ constexpr bool dec_slot_used(int i) { return i * (THREADS / 256) < K::NOUT; }
+template <int THREADS, int DMAX, int NPP, class K = DecDyn>
 __device__ __forceinline__ void decoder_ops_load(const StackArgs& a, int tid, int w0, int B, int f0, bool with_w, DecOps<DMAX, NPP>& o) {      // one pass's output mask and labels (+ the weights)
-    const int c = tid & 15, row = (tid >> 4) & 15;
+    const int row = (tid >> 4) & 15;
     const bool ce = a.labels != nullptr;
-    if (with_w) decoder_ops_load_w<DMAX, NPP>(a, tid, o);
+    if (with_w) decoder_ops_load_w<DMAX, NPP, K>(a, tid, o);
+    if constexpr (K::DOUT != 0) {
+        // a window's labels are NOUT * DOUT contiguous floats, a node's DOUT of them: one vector request per node off a uniform base
+        static_assert(K::NOUT <= NPP * (THREADS / 256), "one pass covers the program's output nodes");
+        const int wr = K::FULL ? w0 + row : min(w0 + row, B - 1);
+        const unsigned roff = (unsigned)((wr * K::NOUT + min(f0, K::NOUT - 1)) * (int)sizeof(float));      // (f0 = the pass's first node of this lane: 0 .. THREADS / 256 - 1)
+        gfloat* yb = reinterpret_cast<gfloat*>(uniform_ptr(reinterpret_cast<const char*>(a.y)) + roff * K::DOUT);
+        gfloat* mb = reinterpret_cast<gfloat*>(uniform_ptr(reinterpret_cast<const char*>(a.out_mask)) + (unsigned)(min(f0, K::NOUT - 1) * K::DOUT * (int)sizeof(float)));
+        const int32_t __attribute__((address_space(1)))* lb = reinterpret_cast<const int32_t __attribute__((address_space(1)))*>(uniform_ptr(reinterpret_cast<const char*>(a.labels)) + roff);
+#pragma unroll
+        for (int i = 0; i < NPP; ++i) {
+            o.labv[i] = 0;
+#pragma unroll
+            for (int dd = 0; dd < DMAX; ++dd) { o.mk[i][dd] = 0.f; o.yv[i][dd] = 0.f; }
+            if (dec_slot_used<THREADS, K>(i)) {
+                // (NOUT a multiple of the node stride: slot i is live in every lane; else the last slot's node index is clamped, as in the run-time form)
+                const int df = (K::NOUT % (THREADS / 256) == 0) ? i * (THREADS / 256) : min(f0 + i * (THREADS / 256), K::NOUT - 1) - min(f0, K::NOUT - 1);
+                if (ce) o.labv[i] = lb[df] != 0;
+#pragma unroll
+                for (int dd = 0; dd < DMAX; ++dd) {
+                    const int dc = min(dd, K::DOUT - 1);
+                    o.mk[i][dd] = mb[df * K::DOUT + dc];
+                    o.yv[i][dd] = a.y ? yb[df * K::DOUT + dc] : 0.f;
+                }
+            }
+        }
+        return;
+    }
 #pragma unroll
     for (int i = 0; i < NPP; ++i) {
         const int f = min(f0 + i * (THREADS / 256), a.n_out - 1);
@@ -1222,7 +1268,7 @@ __device__ __forceinline__ void decoder_ops_load(const StackArgs& a, int tid, in
         }
     }
 }
-template <typename T, int THREADS, int DMAX, bool SPLIT = false, bool TOLDS = false, int NPP = 2, bool PRE = false>      // DMAX: compile-time bound on the output channels (4 or 8): loops, loads and registers scale with it; NPP: nodes per pass; PRE: *pre holds pass 0's operands
+template <typename T, int THREADS, int DMAX, bool SPLIT = false, bool TOLDS = false, int NPP = 2, bool PRE = false, class K = DecDyn>      // DMAX: compile-time bound on the output channels (4 or 8): loops, loads and registers scale with it; NPP: nodes per pass; PRE: *pre holds pass 0's operands; K: DecDyn / DecFacts
 __device__ __forceinline__ void decoder_tail_impl(const StackArgs& a, char* smem, int tid, int lane, int wv, int w0, int B, DecOps<DMAX, NPP>* pre = nullptr) {
     // decoder on the out-type rows of X_L (hgnn_c2.py:176-189): thread = (node, row, 8-column chunk).  With y (mshgnn_step_mse) the
     // same threads also take the wrapper MSE (gnnLightning.py:633-639) and the decoder backward: dX_L rows to global for
@@ -1231,6 +1277,9 @@ __device__ __forceinline__ void decoder_tail_impl(const StackArgs& a, char* smem
         const int c = tid & 15, row = (tid >> 4) & 15;
         const float* W = a.params + a.off_dec_w;
         const bool ce = a.labels != nullptr, fuse = a.y != nullptr || ce;      // ce: cross entropy over the two logits of a foot (gnnLightning.py:640-648)
+        constexpr bool KS = K::DOUT != 0;      // compile-time facts (see DecFacts)
+        static_assert(!KS || (!SPLIT && sizeof(T) == 2 && K::DOUT <= DMAX), "the compile-time tail: bf16 plan");
+        const int dout = KS ? K::DOUT : a.dout, n_out = KS ? K::NOUT : a.n_out;
         T* dxl = reinterpret_cast<T*>(a.ws + a.dx_off[a.L]);
         float accw[DMAX][8], accb[DMAX], lsum = 0.f;
         if (fuse) {
@@ -1243,16 +1292,17 @@ __device__ __forceinline__ void decoder_tail_impl(const StackArgs& a, char* smem
         // costs a full vmcnt(0) drain (loads and stores retire out of order with respect to each other)
         // (unconditional loads with clamped indices, so that they are issued back to back and waited for once)
         DecOps<DMAX, NPP> ops;
-        if constexpr (PRE) ops = *pre; else decoder_ops_load_w<DMAX, NPP>(a, tid, ops);
+        if constexpr (PRE) ops = *pre; else decoder_ops_load_w<DMAX, NPP, K>(a, tid, ops);
         auto& Wv = ops.Wv; auto& bv = ops.bv; auto& mk = ops.mk; auto& yv = ops.yv; auto& labv = ops.labv;
         FS_STAMP(24);
-        for (int f0 = tid >> 8; f0 < a.n_out; f0 += NPP * (THREADS / 256)) {
+        for (int f0 = tid >> 8; f0 < n_out; f0 += NPP * (THREADS / 256)) {
             float ov[NPP][DMAX], dxv[NPP][8];
-            if (!(PRE && f0 == (tid >> 8))) decoder_ops_load<THREADS, DMAX, NPP>(a, tid, w0, B, f0, false, ops);
+            if (!(PRE && f0 == (tid >> 8))) decoder_ops_load<THREADS, DMAX, NPP, K>(a, tid, w0, B, f0, false, ops);
 #pragma unroll
             for (int i = 0; i < NPP; ++i) {
                 const int f = f0 + i * (THREADS / 256);
-                const bool live = f < a.n_out;
+                if constexpr (KS) { if (!dec_slot_used<THREADS, K>(i)) continue; }      // (no lane's slot i holds a node: nothing of it is read below)
+                const bool live = (KS && K::NOUT % (THREADS / 256) == 0) || f < n_out;
                 f32x4 x0, x1;
                 lds_load_oct<T>(smem, a.node0 + (live ? f : f0), row, c * 8, x0, x1);
                 if constexpr (SPLIT) {      // X_L = hi + lo
@@ -1263,11 +1313,11 @@ __device__ __forceinline__ void decoder_tail_impl(const StackArgs& a, char* smem
                 const float x[8] = {x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]};
 #pragma unroll
                 for (int e = 0; e < 8; ++e) dxv[i][e] = 0.f;
-                const bool ok = live && w0 + row < B;
+                const bool ok = live && (K::FULL || w0 + row < B);
 #pragma unroll
                 for (int dd = 0; dd < DMAX; ++dd) {
                     ov[i][dd] = 0.f;
-                    if (dd < a.dout && live) {
+                    if (dd < dout && live) {
                         float sum = 0.f;
 #pragma unroll
                         for (int e = 0; e < 8; ++e) sum = __builtin_fmaf(x[e], Wv[dd][e], sum);      // (explicit fused multiply-adds in this tail: every instantiation -- one-launch
@@ -1285,7 +1335,7 @@ __device__ __forceinline__ void decoder_tail_impl(const StackArgs& a, char* smem
                     }
 #pragma unroll
                     for (int dd = 0; dd < DMAX; ++dd) {
-                        if (dd < a.dout) {
+                        if (dd < dout) {
                             float g;
                             if (ce) g = ce_g[dd & 1] * mk[i][dd];
                             else {
@@ -1303,6 +1353,27 @@ __device__ __forceinline__ void decoder_tail_impl(const StackArgs& a, char* smem
 #pragma unroll
             for (int i = 0; i < NPP; ++i) {
                 const int f = f0 + i * (THREADS / 256);
+                if constexpr (KS) {      // the same rows to the same places: a node's DOUT outputs as one vector, the dX_L row off the node's uniform base
+                    if (!dec_slot_used<THREADS, K>(i)) continue;
+                    const bool live = K::NOUT % (THREADS / 256) == 0 || f < n_out, ok = live && (K::FULL || w0 + row < B);
+                    const int fu = __builtin_amdgcn_readfirstlane(f);      // (f0 = tid >> 8: the same in every lane of a wave)
+                    if (c == 0 && ok) {
+                        gwfloat* ob = reinterpret_cast<gwfloat*>(uniform_wptr(reinterpret_cast<char*>(a.out + fu * K::DOUT)) + (unsigned)((w0 + row) * (K::NOUT * K::DOUT * (int)sizeof(float))));
+#pragma unroll
+                        for (int dd = 0; dd < K::DOUT; ++dd) ob[dd] = ov[i][dd];
+                    }
+                    if (live) {
+                        union { u32x4 r; __bf16 e[8]; } u;
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) u.e[e] = (__bf16)dxv[i][e];
+                        if (fuse && ok) gstore16(uniform_wptr(reinterpret_cast<char*>(dxl + act_idx(0, a.node0 + fu, B))), (unsigned)(((w0 + row) * H + c * 8) * (int)sizeof(T)), u.r);
+                        if constexpr (TOLDS) {
+                            if (!ok) u.r = u32x4{0, 0, 0, 0};      // (bf16(0.f) is the zero pattern)
+                            *reinterpret_cast<u32x4*>(smem + lds_chunk<T>(a.node0 + f, row, c)) = u.r;
+                        }
+                    }
+                    continue;
+                }
                 const bool ok = f < a.n_out && w0 + row < B;
                 const size_t r = (size_t)(w0 + row) * a.n_out + f;
                 if (c == 0 && ok) {
@@ -1338,13 +1409,20 @@ __device__ __forceinline__ void decoder_tail_impl(const StackArgs& a, char* smem
             // reduce over the 4 rows of the wave (lanes 16 apart), then over the 8 waves through LDS (the X tile is dead after the barrier)
 #pragma unroll
             for (int dd = 0; dd < DMAX; ++dd) {
-                if (dd < a.dout) {
+                if constexpr (KS) {      // the same two additions per value, in the same order
+                    if (dd < K::DOUT) {
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) accw[dd][e] = xor32_sum(xor16_sum(accw[dd][e]));
+                        accb[dd] = xor32_sum(xor16_sum(accb[dd]));
+                    }
+                } else if (dd < a.dout) {
 #pragma unroll
                     for (int e = 0; e < 8; ++e) { accw[dd][e] += __shfl_xor(accw[dd][e], 16, 64); accw[dd][e] += __shfl_xor(accw[dd][e], 32, 64); }
                     accb[dd] += __shfl_xor(accb[dd], 16, 64); accb[dd] += __shfl_xor(accb[dd], 32, 64);
                 }
             }
-            lsum += __shfl_xor(lsum, 16, 64); lsum += __shfl_xor(lsum, 32, 64);
+            if constexpr (KS) lsum = xor32_sum(xor16_sum(lsum));
+            else { lsum += __shfl_xor(lsum, 16, 64); lsum += __shfl_xor(lsum, 32, 64); }
             FS_STAMP(26);
             __syncthreads();
             float* red = reinterpret_cast<float*>(smem + a.red_off);          // [waves][8 H + 16]
@@ -1360,12 +1438,20 @@ __device__ __forceinline__ void decoder_tail_impl(const StackArgs& a, char* smem
             __syncthreads();
             FS_STAMP(27);
             float* slab = a.dec_slabs + (size_t)blockIdx.x * DEC_SLAB_FLOATS;
-            for (int i = tid; i < 8 * H + 9; i += THREADS) {
-                if (i >= a.dout * H && i < 8 * H) continue;       // rows of unused output channels (k_finalize reads dout rows only)
+            auto slab_sum = [&](int i) {
                 float s2 = 0.f;
 #pragma unroll
                 for (int k = 0; k < THREADS / 64; ++k) s2 += red[k * DEC_SLAB_FLOATS + i];
                 slab[i] = s2;
+            };
+            if constexpr (KS) {      // the DOUT weight rows, then the bias / loss entries: no trip over the rows of unused channels
+                for (int i = tid; i < K::DOUT * H; i += THREADS) slab_sum(i);
+                if (tid < 9) slab_sum(8 * H + tid);
+            } else {
+                for (int i = tid; i < 8 * H + 9; i += THREADS) {
+                    if (i >= a.dout * H && i < 8 * H) continue;       // rows of unused output channels (k_finalize reads dout rows only)
+                    slab_sum(i);
+                }
             }
         }
     }

@@ -207,6 +207,10 @@ __device__ __forceinline__ void slab_fwd_layer(const A& a, char* smem, const T* 
     FS_STAMP(5 + 4 * l);
 }
 // the layers of a compile-time program SP, unrolled
+// what the program tells the decoder tail at compile time (DecFacts: its output channels and nodes; FULL: whole tiles): the generated tables carry DOUT / NOUT,
+// a program rendered without them (one compiled for a single plan after the build) keeps the run-time form
+template <class SP, bool FULL, class = void> struct SlabDecFacts { using type = DecDyn; };
+template <class SP, bool FULL> struct SlabDecFacts<SP, FULL, std::void_t<decltype(SP::DOUT), decltype(SP::NOUT)>> { using type = DecFacts<SP::DOUT, SP::NOUT, FULL>; };
 // the first pass with work of forward (DIR 0) / backward (DIR 1) layer l of a compile-time program: request its first two weight fragments
 template <typename T, class SP, int DIR, int l> __device__ __forceinline__ void slab_prefetch_static(typename Prec<T>::BFrag (&pre)[2], const T* wpack, int wn, int lane) {
     if constexpr (!(SHdr<SP, DIR, l>{}[FH_FLAGS] & FF_A_EMPTY)) fs_prefetch_static<T, SProg<SP, DIR, l, 0>>(pre, wpack, wn, lane);
@@ -220,7 +224,7 @@ __device__ __forceinline__ void slab_fwd_layers_static(const A& a, char* smem, c
     if constexpr (l < SP::L) {
         auto mid = [&] {
             if constexpr (l + 1 < SP::L) { if constexpr ((SP::PRE & 1) != 0) slab_prefetch_static<T, SP, 0, l + 1>(pre, wpack, wn, lane); }
-            else if constexpr ((SP::PRE & 4) != 0) decoder_ops_load<SL_THREADS, SP::DMAX, DEC_NPP_STATIC>(args_of(a), threadIdx.x, blockIdx.x * Prec<T>::ROWS, a.B, threadIdx.x >> 8, true, dops);
+            else if constexpr ((SP::PRE & 4) != 0) decoder_ops_load<SL_THREADS, SP::DMAX, DEC_NPP_STATIC, typename SlabDecFacts<SP, A::full>::type>(args_of(a), threadIdx.x, blockIdx.x * Prec<T>::ROWS, a.B, threadIdx.x >> 8, true, dops);
         };
         slab_fwd_layer<T, NM, HB, STEP, (SP::PRE & 1) != 0>(a, smem, wpack, wn, lane, l, SP::L, SHdr<SP, 0, l>{}, SProg<SP, 0, l, 0>{}, SProg<SP, 0, l, 1>{}, mid, &pre,
                                                             l + 1 == SP::L ? lastbits : nullptr);
@@ -282,7 +286,7 @@ template <typename T, int NM, int HB, bool STEP, class SP = void, class A = Stac
     } else {
         DecOps<SP::DMAX, DEC_NPP_STATIC> dops;
         slab_fwd_layers_static<T, NM, HB, STEP, SP>(a, smem, wpack, wn, lane, pre, lastbits, dops);
-        decoder_tail_impl<T, SL_THREADS, SP::DMAX, false, STEP, DEC_NPP_STATIC, (SP::PRE & 4) != 0>(args_of(a), smem, tid, lane, wn, w0, B, &dops);
+        decoder_tail_impl<T, SL_THREADS, SP::DMAX, false, STEP, DEC_NPP_STATIC, (SP::PRE & 4) != 0, typename SlabDecFacts<SP, A::full>::type>(args_of(a), smem, tid, lane, wn, w0, B, &dops);
     }
     FS_STAMP(30);
 }
@@ -673,6 +677,9 @@ using StackKernel = void (*)(StackArgs);
 #include "mshgnn_spec_tables.inc"
 template <class SP> static bool spec_matches(const HostPlan& hp) {
     if (!hp.slab || hp.L != SP::L || hp.NN != SP::NN || hp.sl_hb != SP::HB || (hp.n_mlp <= 2 ? 2 : 4) != SP::NM || (hp.d.out_channels <= 4 ? 4 : 8) != SP::DMAX) return false;
+    if constexpr (!std::is_same<typename SlabDecFacts<SP, true>::type, DecDyn>::value) {      // the tail is compiled for the program's output channels and nodes
+        if (hp.d.out_channels != SP::DOUT || hp.d.type_nodes[hp.d.out_type] != SP::NOUT) return false;
+    }
     for (int l = 0; l < SP::L; ++l) {
         if (hp.sl_fwd_off[l] + SP::ROW > (int)hp.tables.size() || hp.sl_bwd_off[l] + SP::ROW > (int)hp.tables.size()) return false;
         if (memcmp(hp.tables.data() + hp.sl_fwd_off[l], SP::fwd[l], sizeof(int32_t) * SP::ROW) != 0) return false;
