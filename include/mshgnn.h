@@ -265,6 +265,39 @@ int mshgnn_adam_step(float* params, const float* grads, float* exp_avg, float* e
 int mshgnn_adam_step_counted(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, int64_t* step_count,
                              float lr, float beta1, float beta2, float eps, float grad_scale, void* stream);
 
+/* SGD on the flat fp32 buffers (configure_optimizers with optimizer = "sgd", gnnLightning.py:258-265): torch.optim.SGD, maximize = False.
+ *   d = g grad_scale (+ weight_decay p when weight_decay != 0);
+ *   momentum != 0:  buf = d on the first step, momentum buf + (1 - dampening) d on later ones;  d = nesterov ? d + momentum buf : buf;
+ *   p -= lr d.
+ * The first step is step == 1, or *step_count == 0 when step_count (device int64[1], 8-byte aligned) is given: then `step` is not read, the sweep reads the
+ * count and a one-thread launch behind it adds 1.  lr_dev (device float[1]) given: it is read INSTEAD of lr, once at the head of the sweep -- with both on
+ * the device nothing that changes from step to step is a launch argument, and a captured step follows a learning-rate schedule.  momentum_buf: NULL exactly
+ * when momentum == 0; on the first step it is only written.  params, grads, momentum_buf: device fp32, n elements, 16-byte aligned; grads is only read.
+ * MSHGNN_EINVAL (nothing launched): a null / misaligned buffer, n < 1, step < 1 without step_count, negative or NaN lr / momentum / weight_decay, nesterov
+ * with momentum <= 0 or dampening != 0 (torch's constructor refuses the same).  morphsym_hgnn_amd.optim.FlatSGD.                                           */
+int mshgnn_sgd_step(float* params, const float* grads, float* momentum_buf, int64_t n, int64_t step, int64_t* step_count, float lr, const float* lr_dev,
+                    float momentum, float dampening, float weight_decay, int nesterov, float grad_scale, void* stream);
+/* Adam with weight decay on the flat buffers, step count and learning rate on the host or on the device as for mshgnn_sgd_step.
+ *   decoupled == 0: torch.optim.Adam(weight_decay): g' = g grad_scale + weight_decay p enters both moments;
+ *   decoupled != 0: torch.optim.AdamW: p *= 1 - lr weight_decay first, then the Adam update from g grad_scale.
+ * Bias corrections as the two entry points above form them (fp64, rounded to fp32 once; on the host from `step`, on the device from *step_count).  With
+ * weight_decay == 0 the result is bit for bit mshgnn_adam_step's (host step) / mshgnn_adam_step_counted's (device step), with lr_dev or without.
+ * morphsym_hgnn_amd.optim.FlatAdam(weight_decay) / FlatAdamW.                                                                                                */
+int mshgnn_adamw_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, int64_t step, int64_t* step_count, float lr,
+                      const float* lr_dev, float beta1, float beta2, float eps, float weight_decay, int decoupled, float grad_scale, void* stream);
+
+/* Gradient clipping on the flat gradient buffer (torch.nn.utils.clip_grad_norm_, norm_type = 2), two launches, both capturable.
+ * mshgnn_grad_norm: *norm_out (device double[1]) = sqrt(sum g_i^2), accumulated in fp64 (an fp32 square is exact there).  Bit-reproducible, no floating-point
+ * atomic: the grid is min(ceil(ceil(n / 4) / 256), 256) workgroups of 256 threads -- a function of n alone -- every lane adds its grid-stride quads in
+ * ascending order, waves reduce in a fixed butterfly, the workgroup that finishes last adds the workgroups' partial sums in index order.  scratch:
+ * mshgnn_grad_norm_scratch_bytes(n) bytes (<= 2064) of device memory, 16-byte aligned, zeroed ONCE by the caller (every call leaves it ready for the next
+ * one on the same stream).  grads: 16-byte aligned, only read; n >= 1.
+ * mshgnn_grad_clip: g *= c for every element, c = min(1, max_norm / (*norm + 1e-6)) formed in fp64 and rounded to fp32 once; c == 1 leaves every bit as it
+ * was (the sign of a zero included).  max_norm >= 0.                                                                                                             */
+size_t mshgnn_grad_norm_scratch_bytes(int64_t n);
+int mshgnn_grad_norm(const float* grads, int64_t n, double* norm_out, void* scratch, void* stream);
+int mshgnn_grad_clip(float* grads, int64_t n, const double* norm, float max_norm, void* stream);
+
 /* Loss of the Lightning wrapper (gnnLightning.py:633-639): loss = mean((out - y)^2) over n elements and
  * grad_out = 2 (out - y) / n (NULL: loss only).  loss_out: device float[1], cleared by the call.        */
 int mshgnn_mse_loss(const float* out, const float* y, int64_t n, float* loss_out, float* grad_out, void* stream);

@@ -80,6 +80,149 @@ extern "C" int mshgnn_adam_step_counted(float* params, const float* grads, float
     return MSHGNN_OK;
 }
 
+// ------------------------------------------------------------------------------------------------------
+// SGD (torch.optim.SGD: momentum / dampening / nesterov / weight decay) and Adam with weight decay, coupled (torch.optim.Adam(weight_decay)) or decoupled
+// (torch.optim.AdamW), on the same flat buffers with the same sweep: the reference's wrappers take optimizer = "adam" | "sgd" (gnnLightning.py:258-265).
+// The step count and the learning rate may live on the device (step_count, lr_dev: both read at the head of the sweep, before any store), so that a
+// captured step follows a scheduler and a loaded state.
+// ------------------------------------------------------------------------------------------------------
+constexpr int ADAM_PLAIN = 0, ADAM_COUPLED = 1, ADAM_DECOUPLED = 2;
+constexpr int SGD_PLAIN = 0, SGD_MOMENTUM = 1, SGD_NESTEROV = 2;
+
+// one element or one quad of torch.optim.SGD's update (T = float | f32x4); bb is read only on a later step (first: the buffer may hold anything)
+template <bool WD, int MOM, class T> __device__ __forceinline__ void sgd_update(T& pp, T gg, T& bb, bool first, float lr, float mom, float keep, float wd, float gscale) {
+    T d = gg * gscale;
+    if (WD) d += wd * pp;
+    if (MOM != SGD_PLAIN) {
+        if (first) bb = d;
+        else bb = mom * bb + keep * d;
+        if (MOM == SGD_NESTEROV) d += mom * bb;
+        else d = bb;
+    }
+    pp -= lr * d;
+}
+
+template <bool WD, int MOM> __global__ void k_sgd(float* p, const float* g, float* buf, int64_t n, const int64_t* step_count, int first, float lr,
+                                                  const float* lr_dev, float mom, float damp, float wd, float gscale) {
+    if (step_count) first = *step_count == 0;
+    if (lr_dev) lr = *lr_dev;
+    const float keep = 1.f - damp;
+    for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += (int64_t)gridDim.x * blockDim.x * 4) {
+        if (i + 4 <= n) {
+            f32x4 pp = *reinterpret_cast<f32x4*>(p + i), bb = {0.f, 0.f, 0.f, 0.f};
+            if (MOM != SGD_PLAIN && !first) bb = *reinterpret_cast<f32x4*>(buf + i);
+            sgd_update<WD, MOM>(pp, *reinterpret_cast<const f32x4*>(g + i), bb, first, lr, mom, keep, wd, gscale);
+            *reinterpret_cast<f32x4*>(p + i) = pp;
+            if (MOM != SGD_PLAIN) *reinterpret_cast<f32x4*>(buf + i) = bb;
+        } else {
+            for (int64_t k = i; k < n; ++k) {
+                float pp = p[k], bb = 0.f;
+                if (MOM != SGD_PLAIN && !first) bb = buf[k];
+                sgd_update<WD, MOM>(pp, g[k], bb, first, lr, mom, keep, wd, gscale);
+                p[k] = pp;
+                if (MOM != SGD_PLAIN) buf[k] = bb;
+            }
+        }
+    }
+}
+
+static int sweep_blocks(int64_t n) { return (int)std::min<int64_t>((n / 4 + 255) / 256 + 1, 2048); }      // (Adam's grid)
+
+// what the two entry points below check about the device-resident step count and learning rate
+static const char* bad_step_or_lr(int64_t step, const int64_t* step_count, float lr, const float* lr_dev) {
+    if (!step_count && step < 1) return "step must be >= 1 (or step_count given)";
+    if ((uintptr_t)step_count & 7) return "step_count must be 8-byte aligned";
+    if ((uintptr_t)lr_dev & 3) return "lr_dev must be 4-byte aligned";
+    if (!lr_dev && !(lr >= 0.f)) return "lr must be >= 0";
+    return nullptr;
+}
+
+extern "C" int mshgnn_sgd_step(float* params, const float* grads, float* momentum_buf, int64_t n, int64_t step, int64_t* step_count, float lr,
+                               const float* lr_dev, float momentum, float dampening, float weight_decay, int nesterov, float grad_scale, void* stream) {
+    if (!params || !grads || n < 1) return set_err(MSHGNN_EINVAL, "bad argument to mshgnn_sgd_step");
+    if (!(momentum >= 0.f) || !(weight_decay >= 0.f) || dampening != dampening) return set_err(MSHGNN_EINVAL, "mshgnn_sgd_step: momentum and weight_decay must be >= 0");
+    if ((momentum != 0.f) != (momentum_buf != nullptr)) return set_err(MSHGNN_EINVAL, "mshgnn_sgd_step: momentum_buf must be given exactly when momentum != 0");
+    if (nesterov && (momentum <= 0.f || dampening != 0.f)) return set_err(MSHGNN_EINVAL, "mshgnn_sgd_step: nesterov needs momentum > 0 and dampening == 0");
+    if (((uintptr_t)params | (uintptr_t)grads | (uintptr_t)momentum_buf) & 15) return set_err(MSHGNN_EINVAL, "sgd buffers must be 16-byte aligned");
+    if (const char* why = bad_step_or_lr(step, step_count, lr, lr_dev)) return set_err(MSHGNN_EINVAL, std::string("mshgnn_sgd_step: ") + why);
+    const int mom = momentum == 0.f ? SGD_PLAIN : nesterov ? SGD_NESTEROV : SGD_MOMENTUM;
+    const bool wd = weight_decay != 0.f;
+    auto kernel = mom == SGD_PLAIN ? (wd ? k_sgd<true, SGD_PLAIN> : k_sgd<false, SGD_PLAIN>)
+                : mom == SGD_MOMENTUM ? (wd ? k_sgd<true, SGD_MOMENTUM> : k_sgd<false, SGD_MOMENTUM>)
+                                      : (wd ? k_sgd<true, SGD_NESTEROV> : k_sgd<false, SGD_NESTEROV>);
+    hipLaunchKernelGGL(kernel, dim3(sweep_blocks(n)), dim3(256), 0, (hipStream_t)stream, params, grads, momentum_buf, n, (const int64_t*)step_count,
+                       step == 1 ? 1 : 0, lr, lr_dev, momentum, dampening, weight_decay, grad_scale);
+    if (step_count) hipLaunchKernelGGL(k_step_count_inc, dim3(1), dim3(1), 0, (hipStream_t)stream, step_count);
+    HIPCHK(hipGetLastError());
+    return MSHGNN_OK;
+}
+
+// Adam with weight decay.  MODE == ADAM_PLAIN runs adam_sweep itself (the bits of k_adam / k_adam_counted); the other two restate it, in its order of
+// operations, with g' = g s + wd p entering both moments (coupled) or p scaled by 1 - lr wd first (decoupled).  The bias corrections arrive as arguments
+// (formed on the host from `step`) or are formed as k_adam_counted forms them when step_count is given.
+template <int MODE> __global__ void k_adamw(float* p, const float* g, float* m, float* v, int64_t n, const int64_t* step_count, float lr, const float* lr_dev,
+                                            float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt, float gscale) {
+    __shared__ float s_bc[2];
+    if (step_count) {
+        if (threadIdx.x == 0) {
+            double a1 = (double)b1, a2 = (double)b2, r1 = 1.0, r2 = 1.0;
+            for (int64_t t = *step_count + 1; t > 0; t >>= 1) {
+                if (t & 1) { r1 *= a1; r2 *= a2; }
+                a1 *= a1; a2 *= a2;
+            }
+            s_bc[0] = (float)(1.0 - r1); s_bc[1] = (float)sqrt(1.0 - r2);
+        }
+        __syncthreads();
+        bc1 = s_bc[0]; bc2_sqrt = s_bc[1];
+    }
+    if (lr_dev) lr = *lr_dev;
+    if (MODE == ADAM_PLAIN) {
+        adam_sweep(p, g, m, v, n, lr, b1, b2, eps, bc1, bc2_sqrt, gscale);
+        return;
+    }
+    for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += (int64_t)gridDim.x * blockDim.x * 4) {
+        if (i + 4 <= n) {
+            f32x4 pp = *reinterpret_cast<f32x4*>(p + i), gg = *reinterpret_cast<const f32x4*>(g + i) * gscale;
+            f32x4 mm = *reinterpret_cast<f32x4*>(m + i), vv = *reinterpret_cast<f32x4*>(v + i);
+            if (MODE == ADAM_COUPLED) gg += wd * pp;
+            else pp *= 1.f - lr * wd;
+            mm = b1 * mm + (1.f - b1) * gg;
+            vv = b2 * vv + (1.f - b2) * gg * gg;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) pp[e] -= lr / bc1 * mm[e] / (sqrtf(vv[e]) / bc2_sqrt + eps);
+            *reinterpret_cast<f32x4*>(p + i) = pp; *reinterpret_cast<f32x4*>(m + i) = mm; *reinterpret_cast<f32x4*>(v + i) = vv;
+        } else {
+            for (int64_t k = i; k < n; ++k) {
+                float pp = p[k], gg = g[k] * gscale;
+                if (MODE == ADAM_COUPLED) gg += wd * pp;
+                else pp *= 1.f - lr * wd;
+                m[k] = b1 * m[k] + (1.f - b1) * gg; v[k] = b2 * v[k] + (1.f - b2) * gg * gg;
+                p[k] = pp - lr / bc1 * m[k] / (sqrtf(v[k]) / bc2_sqrt + eps);
+            }
+        }
+    }
+}
+
+extern "C" int mshgnn_adamw_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, int64_t step, int64_t* step_count,
+                                 float lr, const float* lr_dev, float beta1, float beta2, float eps, float weight_decay, int decoupled, float grad_scale,
+                                 void* stream) {
+    if (!params || !grads || !exp_avg || !exp_avg_sq || n < 1) return set_err(MSHGNN_EINVAL, "bad argument to mshgnn_adamw_step");
+    if (!(weight_decay >= 0.f)) return set_err(MSHGNN_EINVAL, "mshgnn_adamw_step: weight_decay must be >= 0");
+    if (((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) return set_err(MSHGNN_EINVAL, "adam buffers must be 16-byte aligned");
+    if (const char* why = bad_step_or_lr(step, step_count, lr, lr_dev)) return set_err(MSHGNN_EINVAL, std::string("mshgnn_adamw_step: ") + why);
+    float bc1 = 1.f, bc2_sqrt = 1.f;
+    if (!step_count) {      // (as mshgnn_adam_step forms them)
+        bc1 = (float)(1.0 - std::pow((double)beta1, (double)step));
+        bc2_sqrt = (float)std::sqrt(1.0 - std::pow((double)beta2, (double)step));
+    }
+    auto kernel = weight_decay == 0.f ? k_adamw<ADAM_PLAIN> : decoupled ? k_adamw<ADAM_DECOUPLED> : k_adamw<ADAM_COUPLED>;
+    hipLaunchKernelGGL(kernel, dim3(sweep_blocks(n)), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg, exp_avg_sq, n, (const int64_t*)step_count, lr,
+                       lr_dev, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, grad_scale);
+    if (step_count) hipLaunchKernelGGL(k_step_count_inc, dim3(1), dim3(1), 0, (hipStream_t)stream, step_count);
+    HIPCHK(hipGetLastError());
+    return MSHGNN_OK;
+}
+
 __global__ void k_mse(const float* out, const float* y, int64_t n, float* loss, float* gout) {
     __shared__ float red[4];
     float s = 0.f;
@@ -180,6 +323,101 @@ __device__ __forceinline__ bool met_last_ticket(unsigned int* ticket) {
     return true;
 }
 __device__ __forceinline__ bool met_last_block(MetScratch* sc) { return !sc || met_last_ticket(&sc->ticket); }
+
+// ------------------------------------------------------------------------------------------------------
+// L2 norm of the flat gradient and the clipping sweep (torch.nn.utils.clip_grad_norm_, norm_type 2), with the ticket pattern above: no floating-point atomic,
+// the same bits for the same n whatever the arrival order.  Grid = norm_blocks(n) workgroups of 256 threads, a function of n alone (include/mshgnn.h).
+// A lane adds the squares of its grid-stride quads in ascending order (fp64: an fp32 square is exact), a wave reduces in the fixed butterfly of wave_sum,
+// thread 0 adds the four waves in order and leaves the workgroup's partial in the scratch; the last workgroup adds the partials in index order.
+// ------------------------------------------------------------------------------------------------------
+constexpr int NORM_THREADS = 256, NORM_BLOCKS = 256;
+struct NormScratch {
+    unsigned int ticket, pad[3];
+    double part[NORM_BLOCKS];
+};
+static int norm_blocks(int64_t n) { return (int)std::min<int64_t>(((n + 3) / 4 + NORM_THREADS - 1) / NORM_THREADS, NORM_BLOCKS); }
+
+__global__ __launch_bounds__(NORM_THREADS) void k_grad_norm(const float* g, int64_t n, double* norm_out, NormScratch* sc) {
+    __shared__ double r[NORM_THREADS / 64], pf[NORM_BLOCKS];
+    __shared__ int s_last;
+    double s = 0.0;
+    for (int64_t i = ((int64_t)blockIdx.x * NORM_THREADS + threadIdx.x) * 4; i < n; i += (int64_t)gridDim.x * NORM_THREADS * 4) {
+        if (i + 4 <= n) {
+            const f32x4 q = *reinterpret_cast<const f32x4*>(g + i);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { const double x = (double)q[e]; s += x * x; }
+        } else {
+            for (int64_t k = i; k < n; ++k) { const double x = (double)g[k]; s += x * x; }
+        }
+    }
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) r[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = 0.0;
+        for (int k = 0; k < NORM_THREADS / 64; ++k) t += r[k];
+        met_store(&sc->part[blockIdx.x], t);
+        s_last = met_last_ticket(&sc->ticket) ? 1 : 0;
+    }
+    __syncthreads();
+    if (!s_last) return;
+    __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    if (threadIdx.x < gridDim.x) pf[threadIdx.x] = met_load(&sc->part[threadIdx.x]);      // (gridDim.x <= NORM_BLOCKS == NORM_THREADS: one partial per thread)
+    __syncthreads();
+    if (threadIdx.x == 0) {      // index order; eight LDS reads in flight ahead of their (dependent) additions
+        double t = 0.0;
+        unsigned b = 0;
+        for (; b + 8 <= gridDim.x; b += 8) {
+            double x[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) x[k] = pf[b + k];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) t += x[k];
+        }
+        for (; b < gridDim.x; ++b) t += pf[b];
+        __hip_atomic_store(&sc->ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        *norm_out = sqrt(t);
+    }
+}
+static_assert(NORM_BLOCKS <= NORM_THREADS, "the last workgroup loads one partial per thread");
+
+// g *= c, c = fl32(min(1, max_norm / (norm + 1e-6))) formed in fp64 by one thread of the workgroup (a NaN norm gives a NaN coefficient, as torch's clamp does)
+__global__ void k_grad_clip(float* g, int64_t n, const double* norm, float max_norm) {
+    __shared__ float s_c;
+    if (threadIdx.x == 0) {
+        const double q = (double)max_norm / (*norm + 1e-6);
+        s_c = (float)(q > 1.0 ? 1.0 : q);
+    }
+    __syncthreads();
+    const float c = s_c;
+    for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += (int64_t)gridDim.x * blockDim.x * 4) {
+        if (i + 4 <= n) *reinterpret_cast<f32x4*>(g + i) = *reinterpret_cast<f32x4*>(g + i) * c;
+        else for (int64_t k = i; k < n; ++k) g[k] *= c;
+    }
+}
+
+extern "C" size_t mshgnn_grad_norm_scratch_bytes(int64_t n) {
+    return n < 1 ? 0 : offsetof(NormScratch, part) + (((size_t)norm_blocks(n) * sizeof(double) + 15) & ~(size_t)15);
+}
+
+extern "C" int mshgnn_grad_norm(const float* grads, int64_t n, double* norm_out, void* scratch, void* stream) {
+    if (!grads || !norm_out || !scratch || n < 1) return set_err(MSHGNN_EINVAL, "bad argument to mshgnn_grad_norm");
+    if (((uintptr_t)grads | (uintptr_t)scratch) & 15) return set_err(MSHGNN_EINVAL, "mshgnn_grad_norm: grads and scratch must be 16-byte aligned");
+    if ((uintptr_t)norm_out & 7) return set_err(MSHGNN_EINVAL, "mshgnn_grad_norm: norm_out must be 8-byte aligned");
+    hipLaunchKernelGGL(k_grad_norm, dim3(norm_blocks(n)), dim3(NORM_THREADS), 0, (hipStream_t)stream, grads, n, norm_out, (NormScratch*)scratch);
+    HIPCHK(hipGetLastError());
+    return MSHGNN_OK;
+}
+
+extern "C" int mshgnn_grad_clip(float* grads, int64_t n, const double* norm, float max_norm, void* stream) {
+    if (!grads || !norm || n < 1) return set_err(MSHGNN_EINVAL, "bad argument to mshgnn_grad_clip");
+    if (!(max_norm >= 0.f)) return set_err(MSHGNN_EINVAL, "mshgnn_grad_clip: max_norm must be >= 0");
+    if ((uintptr_t)grads & 15) return set_err(MSHGNN_EINVAL, "mshgnn_grad_clip: grads must be 16-byte aligned");
+    if ((uintptr_t)norm & 7) return set_err(MSHGNN_EINVAL, "mshgnn_grad_clip: norm must be 8-byte aligned");
+    hipLaunchKernelGGL(k_grad_clip, dim3(sweep_blocks(n)), dim3(256), 0, (hipStream_t)stream, grads, n, norm, max_norm);
+    HIPCHK(hipGetLastError());
+    return MSHGNN_OK;
+}
 
 // regression (calculate_losses_step, gnnLightning.py:124-130): sums of (pred - y)^2, |pred - y| and n; `batch` (nullable) receives this
 // step's sums (overwritten), `epoch` (nullable) has them added; gout (nullable) = d mean((pred - y)^2) / d pred = 2 (pred - y) / n

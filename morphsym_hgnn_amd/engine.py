@@ -86,6 +86,7 @@ EXPORTS = [
     "mshgnn_input_grad", "mshgnn_forward_series", "mshgnn_forward_series_stats_bytes", "mshgnn_step_mse_series_std", "mshgnn_step_ce_series_std",
     "mshgnn_dataset_starts",
     "mshgnn_metrics_segmented_scratch_bytes", "mshgnn_metrics_regression_segmented", "mshgnn_metrics_classification_segmented",
+    "mshgnn_sgd_step", "mshgnn_adamw_step", "mshgnn_grad_norm_scratch_bytes", "mshgnn_grad_norm", "mshgnn_grad_clip",
 ]
 ABI_VERSION = 6      # include/mshgnn.h MSHGNN_ABI_VERSION: the ctypes structures above mirror THAT header
 
@@ -143,6 +144,15 @@ def load_library():
     if hasattr(lib, "mshgnn_adam_step_counted"):
         lib.mshgnn_adam_step_counted.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_float, C.c_float,
                                                  C.c_float, C.c_float, C.c_float, C.c_void_p]
+    if hasattr(lib, "mshgnn_sgd_step"):      # (absent from older builds of the library handed over through MSHGNN_LIB for A/B runs)
+        lib.mshgnn_sgd_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_float, C.c_void_p, C.c_float, C.c_float,
+                                        C.c_float, C.c_int, C.c_float, C.c_void_p]
+        lib.mshgnn_adamw_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_float, C.c_void_p, C.c_float,
+                                          C.c_float, C.c_float, C.c_float, C.c_int, C.c_float, C.c_void_p]
+        lib.mshgnn_grad_norm_scratch_bytes.restype = C.c_size_t
+        lib.mshgnn_grad_norm_scratch_bytes.argtypes = [C.c_int64]
+        lib.mshgnn_grad_norm.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.mshgnn_grad_clip.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_float, C.c_void_p]
     lib.mshgnn_profile_enable.argtypes = [C.c_void_p, C.c_int]
     lib.mshgnn_profile_read.argtypes = [C.c_void_p, C.POINTER(MshgnnKernelStat), C.POINTER(C.c_int32)]
     lib.mshgnn_mse_loss.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -220,6 +230,15 @@ class MshgnnError(RuntimeError):
 def _check(lib, rc: int, what: str):
     if rc != 0:
         raise MshgnnError(f"{what} failed ({rc}): {lib.mshgnn_last_error().decode()}")
+
+
+def _scalar_ptr(t, dtype):
+    """Address of a one-element device tensor of `dtype` (None: NULL)."""
+    if t is None:
+        return None
+    if t.dtype != dtype or not t.is_cuda or t.numel() != 1:
+        raise ValueError(f"expected a device tensor of one {dtype} element")
+    return t.data_ptr()
 
 
 class _DescHolder:
@@ -836,6 +855,48 @@ class Engine:
             _check(self.lib, self.lib.mshgnn_adam_step(params_flat.data_ptr(), grad_flat.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
                                                    params_flat.numel(), step, lr, betas[0], betas[1], eps, grad_scale, stream), "mshgnn_adam_step")
 
+    def _flat_call(self, name, tensors, n, *args):
+        """A plan-independent launch on flat fp32 buffers of n elements (None entries pass as NULL), on the current stream."""
+        for t, what in tensors:
+            if t is not None and (t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.numel() != n):
+                raise ValueError(f"{what} must be a contiguous fp32 device tensor of {n} elements")
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        with torch.cuda.device(self.device):
+            _check(self.lib, getattr(self.lib, name)(*[t.data_ptr() if t is not None else None for t, _ in tensors], n, *args, stream), name)
+
+    def sgd_step(self, params_flat, grad_flat, momentum_buf, step, lr, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, grad_scale=1.0,
+                 step_count=None, lr_dev=None):
+        """torch.optim.SGD semantics on the flat buffers, in place (mshgnn_sgd_step).  momentum_buf: None exactly when momentum == 0.  step_count (device
+        int64[1]) / lr_dev (device fp32[1]): the first-step decision / the learning rate are read on the device instead of `step` / `lr`."""
+        self._flat_call("mshgnn_sgd_step", ((params_flat, "params"), (grad_flat, "grads"), (momentum_buf, "momentum_buf")), self._flat_n(params_flat), int(step),
+                        _scalar_ptr(step_count, torch.int64), float(lr), _scalar_ptr(lr_dev, torch.float32), float(momentum), float(dampening),
+                        float(weight_decay), int(bool(nesterov)), float(grad_scale))
+
+    def adamw_step(self, params_flat, grad_flat, exp_avg, exp_avg_sq, step, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=True,
+                   grad_scale=1.0, step_count=None, lr_dev=None):
+        """torch.optim.AdamW (decoupled) / torch.optim.Adam(weight_decay) (not decoupled) on the flat buffers, in place (mshgnn_adamw_step)."""
+        self._flat_call("mshgnn_adamw_step", ((params_flat, "params"), (grad_flat, "grads"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")),
+                        self._flat_n(params_flat), int(step), _scalar_ptr(step_count, torch.int64), float(lr), _scalar_ptr(lr_dev, torch.float32),
+                        float(betas[0]), float(betas[1]), float(eps), float(weight_decay), int(bool(decoupled)), float(grad_scale))
+
+    def grad_norm(self, grad_flat, out=None, scratch=None):
+        """(L2 norm of the flat gradient as a device fp64[1], the scratch): mshgnn_grad_norm.  Pass the returned scratch (zeroed once, here) to later calls."""
+        n = self._flat_n(grad_flat)
+        if scratch is None:
+            scratch = torch.zeros((self.lib.mshgnn_grad_norm_scratch_bytes(n) + 7) // 8, dtype=torch.int64, device=grad_flat.device)
+        if out is None:
+            out = torch.empty(1, dtype=torch.float64, device=grad_flat.device)
+        self._flat_call("mshgnn_grad_norm", ((grad_flat, "grads"),), n, _scalar_ptr(out, torch.float64), scratch.data_ptr())
+        return out, scratch
+
+    def grad_clip(self, grad_flat, norm, max_norm):
+        """grad_flat *= min(1, max_norm / (norm + 1e-6)) in place (mshgnn_grad_clip); norm: the device fp64[1] of `grad_norm`."""
+        self._flat_call("mshgnn_grad_clip", ((grad_flat, "grads"),), self._flat_n(grad_flat), _scalar_ptr(norm, torch.float64), float(max_norm))
+
+    def _flat_n(self, t):
+        self._check_flat(t, "the flat buffer")
+        return t.numel()
+
     def mse_loss(self, out: torch.Tensor, y: torch.Tensor, want_grad: bool = True):
         """Wrapper loss (gnnLightning.py:633-639): returns (loss[1], dL/d out or None)."""
         n = out.numel()
@@ -1026,6 +1087,15 @@ class PaddedEngine:
         with torch.cuda.device(self.device):
             _check(self.inner.lib, self.inner.lib.mshgnn_adam_step(params_flat.data_ptr(), grad_flat.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
                                                                    n, step, lr, betas[0], betas[1], eps, grad_scale, stream), "mshgnn_adam_step")
+
+    # SGD / AdamW / the gradient norm and clipping are elementwise or a plain sum: on the caller's TRUE-size flat buffers, as adam_step above
+    sgd_step, adamw_step, grad_norm, grad_clip, _flat_call = Engine.sgd_step, Engine.adamw_step, Engine.grad_norm, Engine.grad_clip, Engine._flat_call
+
+    def _flat_n(self, t):
+        n = self.spec.flat_size()
+        if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.numel() != n:
+            raise ValueError(f"the flat buffer must be a contiguous fp32 device tensor of {n} elements")
+        return n
 
     def padded_width(self, t):
         return self.inner.padded_width(t)

@@ -78,6 +78,10 @@ class Base_Lightning(_Base):
     # validation_step / test_step / predict_step on a windows.WindowBatch under torch.no_grad(): the engine's encoder gathers the windows from the resident
     # series (models.forward_windows, mshgnn_forward_series) instead of reading assembled ones; False: always assemble, then forward.  Same bits.
     fused_evaluation_step = True
+    # configure_optimizers hands these to the flat optimizers (optim.py): the step count / the learning rate live on the device, so that the step can be
+    # captured in a HIP graph (GraphedTrainingStep) and a captured step follows a learning-rate scheduler.
+    graph_safe_optimizer = False
+    device_lr_optimizer = False
 
     def __init__(self, optimizer: str, lr: float, regression: bool):
         super().__init__()
@@ -171,13 +175,19 @@ class Base_Lightning(_Base):
 
     # ---- optimizer (gnnLightning.py:258-265) -------------------------------------------------------------------------
     def configure_optimizers(self):
+        model = getattr(self, "model", None)
+        flat = isinstance(model, models._MSHGNNBase) and len(list(self.parameters())) == len(list(model.parameters()))
+        on_device = dict(graph_safe=bool(getattr(self, "graph_safe_optimizer", False)),      # (graph_safe: GraphedTrainingStep)
+                         device_lr=bool(getattr(self, "device_lr_optimizer", False)))      # (device_lr: a captured step follows a scheduler)
         if self.optimizer == "adam":
-            model = getattr(self, "model", None)
-            if isinstance(model, models._MSHGNNBase) and len(list(self.parameters())) == len(list(model.parameters())):
+            if flat:
                 from .optim import FlatAdam      # a torch.optim.Adam whose step is one launch on the flat buffers (torch's own step otherwise)
-                return FlatAdam(model, lr=self.lr, graph_safe=bool(getattr(self, "graph_safe_optimizer", False)))      # (graph_safe: GraphedTrainingStep)
+                return FlatAdam(model, lr=self.lr, **on_device)
             return optim.Adam(self.parameters(), lr=self.lr)
         if self.optimizer == "sgd":
+            if flat:
+                from .optim import FlatSGD      # the same for torch.optim.SGD
+                return FlatSGD(model, lr=self.lr, **on_device)
             return optim.SGD(self.parameters(), lr=self.lr)
         raise ValueError("Invalid optimizer setting")
 
@@ -534,8 +544,8 @@ class GraphedTrainingStep:
 
     The graph reads its inputs from STATIC device tensors (copies of `example_batch`'s tensors, made here); `__call__(batch)` copies the new batch's tensors
     into them (same shapes and dtypes) and replays.  Everything the step touches lives on the device: the loss / metric sums (metrics.py), the flat gradient
-    buffer, and the optimizer's step count -- which is why the optimizer must be `FlatAdam(graph_safe=True)` (set `wrapper.graph_safe_optimizer = True`
-    before `configure_optimizers()`) or a `torch.optim` optimizer created with `capturable=True`.  The model's parameters, the optimizer state and the metric
+    buffer, and the optimizer's step count -- which is why the optimizer must be `FlatAdam` / `FlatAdamW` / `FlatSGD(graph_safe=True)` (set
+    `wrapper.graph_safe_optimizer = True` before `configure_optimizers()`) or a `torch.optim` optimizer created with `capturable=True`.  The model's parameters, the optimizer state and the metric
     state are restored after the warm-up steps the capture needs, so constructing this object does not train.
 
     Returns the step's loss as a device tensor (a static buffer: read it before the next call).
@@ -543,7 +553,11 @@ class GraphedTrainingStep:
     Resuming: `optimizer.load_state_dict()` may be called after the graph was built -- FlatAdam(graph_safe=True) copies the loaded moments and step count into
     the flat buffers the captured launches address, so the next replay continues from the loaded state (restore the parameters in place as well).  lr, betas
     and eps are plain launch arguments of the captured Adam: a replay RAISES when the param group's differ from the captured values (a scheduler, a loaded
-    group with another lr); build a new GraphedTrainingStep for them.
+    group with another lr); build a new GraphedTrainingStep for them.  With `device_lr=True` (`wrapper.device_lr_optimizer = True`) the learning rate is
+    not among them: the captured launch reads a device scalar that `__call__` refreshes from the param group before the replay, so a scheduler just works.
+
+    `max_grad_norm`: `optim.clip_grad_norm_(wrapper.model, max_grad_norm)` is captured between `backward()` and `optimizer.step()`; `self.grad_norm` is the
+    device fp64 norm (before clipping) of the last replay, a static tensor.
 
     `index_source` (a `windows.DatasetView`): the batch is a set of DATASET INDICES of that view.  `example_batch` is then `view.batch(indices, edge_index_dict)`
     (or anything with `indices` and `edge_index_dict`); the static input is one device int64 tensor of indices, and the captured region runs the index
@@ -551,14 +565,17 @@ class GraphedTrainingStep:
     `__call__(indices)` copy the next batch's indices (host or device, same count) into it; `index_source.check()` tells afterwards whether any was out
     of range."""
 
-    def __init__(self, wrapper, optimizer, example_batch, warmup: int = 3, index_source=None):
+    def __init__(self, wrapper, optimizer, example_batch, warmup: int = 3, index_source=None, max_grad_norm=None):
         import copy
-        from .optim import FlatAdam
-        if isinstance(optimizer, FlatAdam) and not optimizer._graph_safe:
-            raise ValueError("GraphedTrainingStep needs FlatAdam(graph_safe=True): set wrapper.graph_safe_optimizer = True before configure_optimizers()")
-        if not isinstance(optimizer, FlatAdam) and not all(g.get("capturable", False) for g in optimizer.param_groups):
+        from .optim import _FlatMixin
+        flat_opt = isinstance(optimizer, _FlatMixin)      # FlatAdam, FlatAdamW, FlatSGD
+        if flat_opt and not optimizer._graph_safe:
+            raise ValueError(f"GraphedTrainingStep needs {type(optimizer).__name__}(graph_safe=True): set wrapper.graph_safe_optimizer = True before "
+                             "configure_optimizers()")
+        if not flat_opt and not all(g.get("capturable", False) for g in optimizer.param_groups):
             raise ValueError("GraphedTrainingStep needs an optimizer whose step count lives on the device (capturable=True)")
         self.wrapper, self.optimizer = wrapper, optimizer
+        self.max_grad_norm, self.grad_norm = (None if max_grad_norm is None else float(max_grad_norm)), None
         self.index_source = index_source
         if index_source is not None:
             from .windows import WindowBatch
@@ -569,10 +586,8 @@ class GraphedTrainingStep:
             self.batch = self._static_copy(example_batch)
         dev = next(wrapper.parameters()).device
         snap_p = [p.detach().clone() for p in wrapper.parameters()]
-        flat_opt = isinstance(optimizer, FlatAdam)
-        if flat_opt:      # FlatAdam's state lives in flat device buffers the captured launches will address: snapshot / restore them IN PLACE
-            optimizer._sync_steps()
-            snap_o = None if optimizer._m is None or optimizer._owner is None else (optimizer._m.clone(), optimizer._v.clone(), int(optimizer._t))
+        if flat_opt:      # a flat optimizer's state lives in flat device buffers the captured launches will address: snapshot / restore them IN PLACE
+            snap_o = optimizer._snapshot()
         else:
             snap_o = copy.deepcopy(optimizer.state_dict())
         side = torch.cuda.Stream(device=dev)
@@ -588,14 +603,9 @@ class GraphedTrainingStep:
             for p, q in zip(wrapper.parameters(), snap_p):
                 p.copy_(q)
             if flat_opt:
-                if optimizer._m is None or optimizer._t_dev is None:
+                if optimizer._owner is None or optimizer._t_dev is None:
                     raise RuntimeError("GraphedTrainingStep: the optimizer did not take the flat route during capture (parameters or gradients are not the flat views)")
-                if snap_o is None:
-                    optimizer._m.zero_(); optimizer._v.zero_(); optimizer._t = 0
-                else:
-                    optimizer._m.copy_(snap_o[0]); optimizer._v.copy_(snap_o[1]); optimizer._t = snap_o[2]
-                optimizer._t_dev.fill_(optimizer._t)
-                optimizer._sync_steps()
+                optimizer._restore(snap_o)
             else:
                 optimizer.load_state_dict(snap_o)
         if hasattr(wrapper, "reset_all_metrics"):
@@ -603,13 +613,11 @@ class GraphedTrainingStep:
         self._captured = self._optimizer_arguments()
 
     def _optimizer_arguments(self):
-        """What the captured FlatAdam launch holds as plain arguments: (lr, betas, eps) of the one param group and the addresses of the flat state."""
-        from .optim import FlatAdam
+        """What the captured flat optimizer launch holds as plain arguments: lr (None with device_lr: the launch reads the device scalar) and the other
+        hyperparameters of the one param group ((betas, eps, ...) of FlatAdam), then the addresses of the flat state."""
+        from .optim import _FlatMixin
         o = self.optimizer
-        if not isinstance(o, FlatAdam):
-            return None
-        g = o.param_groups[0]
-        return (float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), o._m.data_ptr(), o._v.data_ptr(), o._t_dev.data_ptr())
+        return o._captured_arguments() if isinstance(o, _FlatMixin) else None
 
     @staticmethod
     def _static_copy(batch):
@@ -631,6 +639,9 @@ class GraphedTrainingStep:
         self.optimizer.zero_grad(set_to_none=True)
         loss = self.wrapper.training_step(self.batch, 0)
         loss.backward()
+        if self.max_grad_norm is not None:
+            from .optim import clip_grad_norm_
+            self.grad_norm = clip_grad_norm_(self.wrapper.model, self.max_grad_norm)      # (the flat route returns one static device tensor)
         self.optimizer.step()
         return loss.detach()
 
@@ -657,7 +668,10 @@ class GraphedTrainingStep:
                                f"captured: {self._optimizer_arguments()[:4]} now, {self._captured[:4]} captured; build a new GraphedTrainingStep")
         if batch is not None:
             self.load(batch)
+        if self._captured is not None:
+            self.optimizer._refresh_lr()      # device_lr: the scalar the captured launch reads follows param_groups[0]["lr"]
         self.graph.replay()
+        self.optimizer._opt_called = True      # (the replay ran optimizer.step(): torch's lr schedulers look at this flag to warn about the call order)
         return self.loss
 
 
