@@ -569,6 +569,71 @@ void mshgnn_comm_destroy(mshgnn_comm* comm);
 int mshgnn_comm_allreduce_mean(mshgnn_comm* comm, float* buf, int64_t n, void* stream);
 int mshgnn_comm_allreduce_sum(mshgnn_comm* comm, float* buf, int64_t n, void* stream);
 
+/* ---- MLP baselines (csrc/mshgnn_mlp.hip) -------------------------------------------------------------------------------------------------------------
+ * The reference's MLP (gnnLightning.py:391-405: nn.Sequential of num_layers Linear layers with ReLU between them, in -> hidden -> ... -> hidden -> out) on the
+ * bf16 arithmetic class of the HGNN engine's bf16 plan: inputs and weights are bf16 MFMA operands (weights rounded from the flat fp32 buffer), fp32 accumulation
+ * and bias add, activations and activation gradients pass between layers as bf16, output / loss / parameter gradients fp32.  No floating-point atomic: every
+ * sum has a fixed order, two runs give identical bits.  The flat parameter buffer is torch's state_dict order of that nn.Sequential: 0.weight, 0.bias,
+ * 2.weight, 2.bias, ..., each weight [out_f, in_f] row-major (mshgnn_mlp_info.off_w / off_b, Linear layer i = 0 .. num_layers - 1).
+ * Supported: hidden 128 / 256 / 384 / 512, in_channels 1 .. 16384 (no alignment condition), out_channels 1 .. 16, num_layers 2 .. 16, dtype MSHGNN_BF16;
+ * anything else is MSHGNN_EUNSUPPORTED with the limit named in mshgnn_last_error().
+ * A step is five launches at any depth: weight pack, input layer, stack (layers 2 .. L, the loss tail and the backward sweep down to dZ_1 in one workgroup
+ * per 32-row tile, activations LDS-resident), weight gradients (partial sums over row slabs), fixed-order slab sum (+ the loss).  The series form adds the
+ * one-workgroup run-pointer launch unless the caller vouches (run_ptrs_ready).  Every launch goes on `stream`; nothing is allocated, nothing read back.        */
+#define MSHGNN_MLP_MAX_LAYERS 16
+typedef struct mshgnn_mlp_plan mshgnn_mlp_plan;
+typedef struct mshgnn_mlp_desc {
+    int32_t in_channels, hidden, out_channels, num_layers, dtype;
+} mshgnn_mlp_desc;
+typedef struct mshgnn_mlp_info {
+    int64_t n_flat;                               /* length of the flat parameter buffer                                           */
+    int64_t off_w[MSHGNN_MLP_MAX_LAYERS];         /* Linear layer i: weight [out_f, in_f] at off_w[i], bias [out_f] at off_b[i]    */
+    int64_t off_b[MSHGNN_MLP_MAX_LAYERS];
+    int32_t rows_per_tile;                        /* windows per workgroup tile of the input-layer and stack launches             */
+    int32_t n_launches_step;                      /* launches of one mshgnn_mlp_step on dense rows                                 */
+    int64_t lds_bytes;                            /* dynamic LDS of the stack launch                                               */
+    double flops_fwd, flops_bwd;                  /* algorithmic FLOPs / window (2 per MAC): forward; backward (dA chain + all dW)  */
+} mshgnn_mlp_info;
+/* Where a batch's rows come from.  Dense form: x != NULL, bf16 rows [batch][pitch], 16-byte aligned, pitch a multiple of 8 and >= in_channels rounded up to 8;
+ * everything below `pitch` is ignored.  Series form: x == NULL and desc / src / src_bf16 / src_cstride / src_rows / starts / run_ptrs exactly as
+ * mshgnn_step_mse_series takes them (desc->run_ptrs_ready vouches the same way); row b is the window of the one node row of the recipe at starts[b], gathered
+ * per K chunk from the bf16 series -- no window row is written to memory, the weight-gradient launch gathers the same operand again.  The series form takes a
+ * bf16, fast_layout, unstandardised, unsigned descriptor with n_types == 1, type_nodes[0] == 1, type_width[0] == in_channels and one group element; any other
+ * descriptor is MSHGNN_EUNSUPPORTED (assemble, then use the dense form: same bits).  y_out / quat_out / labels_out (each nullable): the window labels
+ * (fp32 [batch][n_label]), quaternions and contact flags (int32, y != 0) as mshgnn_step_*_series produce them.                                              */
+typedef struct mshgnn_mlp_input {
+    const void* x; int64_t pitch;
+    const mshgnn_window_desc* desc;
+    const float* const* src; const void* const* src_bf16; const int64_t* src_cstride; const int64_t* src_rows;
+    const int64_t* starts;
+    float* y_out; float* quat_out; int32_t* labels_out;
+    void* run_ptrs;
+} mshgnn_mlp_input;
+/* mshgnn_struct_size: 5 = mshgnn_mlp_desc, 6 = mshgnn_mlp_info, 7 = mshgnn_mlp_input */
+
+/* The descriptor check and the info alone, on the host: no device is touched.  loss_kind: -1 (none), 0 (MSE) or 1 (cross entropy: out_channels must be even). */
+int mshgnn_mlp_compile_host(const mshgnn_mlp_desc* desc, int loss_kind, mshgnn_mlp_info* info);
+int mshgnn_mlp_create(const mshgnn_mlp_desc* desc, mshgnn_mlp_plan** plan_out);
+void mshgnn_mlp_destroy(mshgnn_mlp_plan* plan);
+int mshgnn_mlp_info_get(const mshgnn_mlp_plan* plan, mshgnn_mlp_info* info);
+/* Bytes of the caller-owned workspace for `batch` rows (16-byte aligned base).  training = 0: forward only.  0: bad arguments. */
+size_t mshgnn_mlp_workspace_bytes(const mshgnn_mlp_plan* plan, int64_t batch, int training);
+/* Byte offset inside a training workspace of the bf16 stash of relu(Z_layer) (layer = 1 .. num_layers - 1, [rows][hidden], rows = batch rounded up to the tile;
+ * rows past the batch are zeros) -- for tests / debugging; 0: no such stash.                                                                                  */
+size_t mshgnn_mlp_stash_offset(const mshgnn_mlp_plan* plan, int64_t batch, int layer);
+/* out: fp32 [batch][out_channels].  training != 0 leaves the bf16 stashes mshgnn_mlp_backward reads. */
+int mshgnn_mlp_forward(const mshgnn_mlp_plan* plan, const mshgnn_mlp_input* input, const float* params, float* out, void* workspace, int64_t batch,
+                       int training, void* stream);
+/* After a training forward on the same workspace, input and params: gout fp32 [batch][out_channels] = dL / d out; grad_params (flat fp32) is fully overwritten. */
+int mshgnn_mlp_backward(const mshgnn_mlp_plan* plan, const mshgnn_mlp_input* input, const float* params, const float* gout, float* grad_params,
+                        void* workspace, int64_t batch, void* stream);
+/* forward + loss + backward in one call, bit for bit the three calls (the same kernels; the loss tail runs inside the stack launch).
+ * loss_kind 0: loss = mean((out - y)^2), targets fp32 [batch][out_channels]; loss_kind 1: mean cross entropy over the batch * out_channels / 2 logit pairs,
+ * targets int32 [batch][out_channels / 2] in {0, 1}.  Series input with targets == NULL: the targets are the window labels the call gathers (input->y_out,
+ * and input->labels_out for loss_kind 1).  loss_out: device float[1].                                                                                      */
+int mshgnn_mlp_step(const mshgnn_mlp_plan* plan, const mshgnn_mlp_input* input, int loss_kind, const void* targets, const float* params, float* out,
+                    float* loss_out, float* grad_params, void* workspace, int64_t batch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

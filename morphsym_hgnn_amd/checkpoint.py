@@ -168,3 +168,40 @@ def to_lightning_checkpoint(model: nn.Module, hyper_parameters: Optional[dict] =
     as a keyword argument next to the path, as `evaluate_model` passes its other overrides."""
     return {"state_dict": {prefix + k: v.detach().cpu() for k, v in model.state_dict().items()},
             "hyper_parameters": dict(hyper_parameters or {}), "pytorch-lightning_version": "2.1.0", "epoch": 0, "global_step": 0}
+
+
+# ---- the MLP baselines: `mlp_model.*` (MLP_Lightning, gnnLightning.py:407) / `model.*` (COM_MLP_Lightning, gnnLightning_com.py:279) -----------------------
+MLP_PREFIXES = {"mlp": "mlp_model.", "mlp_com": "model."}
+
+
+def mlp_to_lightning_checkpoint(model: nn.Module, model_type: str = "mlp", hyper_parameters: Optional[dict] = None) -> dict:
+    """A `models.MLP` in the Lightning layout of the reference's wrapper for `model_type` ("mlp": keys `mlp_model.0.weight`, ...; "mlp_com": `model.0.weight`,
+    ...), with the wrapper's constructor arguments as `hyper_parameters` unless given."""
+    if model_type not in MLP_PREFIXES:
+        raise ValueError(f"unknown MLP model_type {model_type!r}")
+    hp = dict(hyper_parameters) if hyper_parameters is not None else dict(
+        in_channels=model.in_channels, hidden_channels=model.hidden_channels, out_channels=model.out_channels, num_layers=model.num_layers,
+        regression=model.regression)
+    return to_lightning_checkpoint(model, hp, prefix=MLP_PREFIXES[model_type])
+
+
+def mlp_from_checkpoint(ckpt, model_type: str = "mlp", **overrides) -> nn.Module:
+    """Rebuild a `models.MLP` from a Lightning checkpoint of `MLP_Lightning` / `COM_MLP_Lightning` (path or dict): the dimensions come from
+    `hyper_parameters` (overrides first) or, where those are absent, from the weight shapes themselves."""
+    if not isinstance(ckpt, dict):
+        ckpt = read_checkpoint(ckpt)
+    if model_type not in MLP_PREFIXES:
+        raise ValueError(f"unknown MLP model_type {model_type!r}")
+    sd = model_state_dict(ckpt, MLP_PREFIXES[model_type])
+    hp = dict(ckpt.get("hyper_parameters", {}))
+    hp.update(overrides)
+    ws = sorted((int(k.split(".")[0]), v) for k, v in sd.items() if k.endswith(".weight"))
+    if not ws:
+        raise ValueError("the checkpoint holds no MLP weights under " + MLP_PREFIXES[model_type])
+    dims = dict(in_channels=int(ws[0][1].shape[1]), hidden_channels=int(ws[0][1].shape[0]), out_channels=int(ws[-1][1].shape[0]), num_layers=len(ws))
+    for k, v in dims.items():
+        if k in hp and int(hp[k]) != v:
+            raise ValueError(f"hyper_parameters[{k!r}] = {hp[k]} but the weights say {v}")
+    model = models.MLP(regression=bool(hp.get("regression", True)), **dims)
+    model.load_state_dict(sd, strict=True)
+    return model

@@ -31,6 +31,9 @@ extern "C" size_t mshgnn_struct_size(int which) {
         case 2: return sizeof(mshgnn_ws_layout);
         case 3: return sizeof(mshgnn_window_desc);
         case 4: return sizeof(mshgnn_kernel_stat);
+        case 5: return sizeof(mshgnn_mlp_desc);
+        case 6: return sizeof(mshgnn_mlp_info);
+        case 7: return sizeof(mshgnn_mlp_input);
         default: return 0;
     }
 }

@@ -74,6 +74,28 @@ class MshgnnKernelStat(C.Structure):
     ]
 
 
+MLP_MAX_LAYERS = 16
+
+
+class MshgnnMlpDesc(C.Structure):
+    _fields_ = [("in_channels", C.c_int32), ("hidden", C.c_int32), ("out_channels", C.c_int32), ("num_layers", C.c_int32), ("dtype", C.c_int32)]
+
+
+class MshgnnMlpInfo(C.Structure):
+    _fields_ = [
+        ("n_flat", C.c_int64), ("off_w", C.c_int64 * MLP_MAX_LAYERS), ("off_b", C.c_int64 * MLP_MAX_LAYERS),
+        ("rows_per_tile", C.c_int32), ("n_launches_step", C.c_int32), ("lds_bytes", C.c_int64), ("flops_fwd", C.c_double), ("flops_bwd", C.c_double),
+    ]
+
+
+class MshgnnMlpInput(C.Structure):
+    _fields_ = [
+        ("x", C.c_void_p), ("pitch", C.c_int64), ("desc", C.POINTER(MshgnnWindowDesc)),
+        ("src", C.POINTER(C.c_void_p)), ("src_bf16", C.POINTER(C.c_void_p)), ("src_cstride", C.POINTER(C.c_int64)), ("src_rows", C.POINTER(C.c_int64)),
+        ("starts", C.c_void_p), ("y_out", C.c_void_p), ("quat_out", C.c_void_p), ("labels_out", C.c_void_p), ("run_ptrs", C.c_void_p),
+    ]
+
+
 EXPORTS = [
     "mshgnn_last_error", "mshgnn_version", "mshgnn_plan_create", "mshgnn_plan_destroy", "mshgnn_plan_info", "mshgnn_plan_specialised", "mshgnn_plan_attach_program",
     "mshgnn_plan_compile_host", "mshgnn_workspace_layout", "mshgnn_forward", "mshgnn_backward", "mshgnn_mse_loss", "mshgnn_ce_loss", "mshgnn_metrics_regression_step", "mshgnn_metrics_classification_step", "mshgnn_metrics_com_step",
@@ -87,6 +109,8 @@ EXPORTS = [
     "mshgnn_dataset_starts",
     "mshgnn_metrics_segmented_scratch_bytes", "mshgnn_metrics_regression_segmented", "mshgnn_metrics_classification_segmented",
     "mshgnn_sgd_step", "mshgnn_adamw_step", "mshgnn_grad_norm_scratch_bytes", "mshgnn_grad_norm", "mshgnn_grad_clip",
+    "mshgnn_mlp_compile_host", "mshgnn_mlp_create", "mshgnn_mlp_destroy", "mshgnn_mlp_info_get", "mshgnn_mlp_workspace_bytes", "mshgnn_mlp_stash_offset",
+    "mshgnn_mlp_forward", "mshgnn_mlp_backward", "mshgnn_mlp_step",
 ]
 ABI_VERSION = 6      # include/mshgnn.h MSHGNN_ABI_VERSION: the ctypes structures above mirror THAT header
 
@@ -204,6 +228,20 @@ def load_library():
         lib.mshgnn_metrics_regression_segmented.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.mshgnn_metrics_classification_segmented.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                                                 C.c_void_p]
+    # the MLP baselines (csrc/mshgnn_mlp.hip)
+    lib.mshgnn_mlp_compile_host.argtypes = [C.POINTER(MshgnnMlpDesc), C.c_int, C.POINTER(MshgnnMlpInfo)]
+    lib.mshgnn_mlp_create.argtypes = [C.POINTER(MshgnnMlpDesc), C.POINTER(C.c_void_p)]
+    lib.mshgnn_mlp_destroy.argtypes = [C.c_void_p]
+    lib.mshgnn_mlp_destroy.restype = None
+    lib.mshgnn_mlp_info_get.argtypes = [C.c_void_p, C.POINTER(MshgnnMlpInfo)]
+    lib.mshgnn_mlp_workspace_bytes.restype = C.c_size_t
+    lib.mshgnn_mlp_workspace_bytes.argtypes = [C.c_void_p, C.c_int64, C.c_int]
+    lib.mshgnn_mlp_stash_offset.restype = C.c_size_t
+    lib.mshgnn_mlp_stash_offset.argtypes = [C.c_void_p, C.c_int64, C.c_int]
+    lib.mshgnn_mlp_forward.argtypes = [C.c_void_p, C.POINTER(MshgnnMlpInput), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
+    lib.mshgnn_mlp_backward.argtypes = [C.c_void_p, C.POINTER(MshgnnMlpInput), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    lib.mshgnn_mlp_step.argtypes = [C.c_void_p, C.POINTER(MshgnnMlpInput), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_int64, C.c_void_p]
     lib.mshgnn_struct_size.restype = C.c_size_t
     lib.mshgnn_struct_size.argtypes = [C.c_int]
     lib.mshgnn_comm_unique_id.argtypes = [C.c_char_p, C.c_void_p]
@@ -217,6 +255,9 @@ def load_library():
     if lib.mshgnn_abi_version() != ABI_VERSION:
         raise RuntimeError(f"{LIB_PATH}: ABI version {lib.mshgnn_abi_version()} != {ABI_VERSION} of this binding -- rebuild (make -C morphsym_hgnn_amd/csrc)")
     for which, st in enumerate((MshgnnDesc, MshgnnInfo, MshgnnWsLayout, MshgnnWindowDesc, MshgnnKernelStat)):
+        if lib.mshgnn_struct_size(which) != C.sizeof(st):
+            raise RuntimeError(f"{LIB_PATH}: sizeof({st.__name__}) is {lib.mshgnn_struct_size(which)} in the library, {C.sizeof(st)} in engine.py")
+    for which, st in ((5, MshgnnMlpDesc), (6, MshgnnMlpInfo), (7, MshgnnMlpInput)):
         if lib.mshgnn_struct_size(which) != C.sizeof(st):
             raise RuntimeError(f"{LIB_PATH}: sizeof({st.__name__}) is {lib.mshgnn_struct_size(which)} in the library, {C.sizeof(st)} in engine.py")
     _lib = lib
@@ -1126,3 +1167,270 @@ class PaddedEngine:
 def make_engine(spec: ModelSpec, dtype: str = "f32", device: Optional[torch.device] = None):
     """Engine for any hidden width: multiples of 128 as they are, other widths zero-padded to the next one (PaddedEngine)."""
     return Engine(spec, dtype=dtype, device=device) if spec.hidden % 128 == 0 else PaddedEngine(spec, dtype=dtype, device=device)
+
+
+# ---- MLP baselines (include/mshgnn.h "MLP baselines", csrc/mshgnn_mlp.hip) ---------------------------------------------------------------------------
+MLP_HIDDEN = (128, 256, 384, 512)      # what the fused path takes; models.MLP routes everything else operator by operator
+MLP_MAX_IN, MLP_MAX_OUT = 16384, 16
+
+
+def mlp_supported(in_channels: int, hidden: int, out_channels: int, num_layers: int) -> bool:
+    return hidden in MLP_HIDDEN and 1 <= in_channels <= MLP_MAX_IN and 1 <= out_channels <= MLP_MAX_OUT and 2 <= num_layers <= MLP_MAX_LAYERS
+
+
+def mlp_compile_host(in_channels: int, hidden: int, out_channels: int, num_layers: int, dtype: str = "bf16", loss: Optional[str] = None) -> MshgnnMlpInfo:
+    """The descriptor check and the flat layout alone (no GPU needed): mshgnn_mlp_compile_host.  loss: None, "mse" or "ce"."""
+    lib = load_library()
+    d = MshgnnMlpDesc(in_channels, hidden, out_channels, num_layers, DTYPE_CODES[dtype])
+    info = MshgnnMlpInfo()
+    _check(lib, lib.mshgnn_mlp_compile_host(C.byref(d), {None: -1, "mse": 0, "ce": 1}[loss], C.byref(info)), "mshgnn_mlp_compile_host")
+    return info
+
+
+class MLPEngine:
+    """The reference's MLP baseline (gnnLightning.py:391-405) on one GPU: a ctypes mirror of the mshgnn_mlp_* entry points.  Parameters and gradients are one
+    flat fp32 buffer in torch's state_dict order of the nn.Sequential (`offsets()`).  Dense rows: bf16 [B, pitch] (`cast_input`); the series methods take a
+    `windows.SequenceStore` / `ResidentDataset` of an `mlp_recipe` and device `starts`, and gather the rows inside the kernels -- where the library's series
+    form refuses (standardised recipes, `transformed` / `orbit` stores, fp32 stores) they assemble the windows and run the dense form: same bits."""
+
+    def __init__(self, in_channels: int, hidden: int, out_channels: int, num_layers: int, dtype: str = "bf16", device: Optional[torch.device] = None):
+        if dtype != "bf16":
+            raise ValueError("the fused MLP runs the bf16 arithmetic (dtype='bf16'); models.MLP serves 'f32' / 'x3' operator by operator")
+        if not torch.cuda.is_available():
+            raise RuntimeError("the MLP engine needs a HIP device; there is no CPU fallback")
+        self.lib = load_library()
+        self.in_channels, self.hidden, self.out_channels, self.num_layers, self.dtype = int(in_channels), int(hidden), int(out_channels), int(num_layers), dtype
+        self.device = torch.device(device if device is not None else "cuda:0")
+        self._desc = MshgnnMlpDesc(self.in_channels, self.hidden, self.out_channels, self.num_layers, DTYPE_CODES[dtype])
+        self._plan = C.c_void_p()
+        with torch.cuda.device(self.device):
+            _check(self.lib, self.lib.mshgnn_mlp_create(C.byref(self._desc), C.byref(self._plan)), "mshgnn_mlp_create")
+        self.info = MshgnnMlpInfo()
+        _check(self.lib, self.lib.mshgnn_mlp_info_get(self._plan, C.byref(self.info)), "mshgnn_mlp_info_get")
+        self.n_flat = int(self.info.n_flat)
+        self._ws: Dict[Tuple[int, int], torch.Tensor] = {}
+
+    def __del__(self):
+        try:
+            if getattr(self, "_plan", None) is not None and self._plan.value:
+                self.lib.mshgnn_mlp_destroy(self._plan)
+                self._plan = C.c_void_p()
+        except Exception:
+            pass
+
+    MAX_WORKSPACES = 4
+
+    def offsets(self) -> List[Tuple[int, int, int, int]]:
+        """Per Linear layer (off_w, off_b, out_f, in_f) into the flat buffer."""
+        L = self.num_layers
+        return [(int(self.info.off_w[i]), int(self.info.off_b[i]), self.out_channels if i == L - 1 else self.hidden, self.in_channels if i == 0 else self.hidden)
+                for i in range(L)]
+
+    def workspace_bytes(self, B: int, training: bool = True) -> int:
+        n = int(self.lib.mshgnn_mlp_workspace_bytes(self._plan, B, int(training)))
+        if n == 0:
+            raise ValueError("batch must be in [1, 2^24]")
+        return n
+
+    def workspace(self, B: int, training: bool = True) -> torch.Tensor:
+        """The caller-owned workspace of the C-ABI for batch size B, one per (B, training), at most MAX_WORKSPACES of them."""
+        key = (B, int(training))
+        ws = self._ws.pop(key, None)
+        if ws is None:
+            ws = torch.empty(self.workspace_bytes(B, training), dtype=torch.uint8, device=self.device)
+            if os.environ.get("MSHGNN_POISON_WS") == "1":      # tests: what no launch wrote reads as NaNs
+                ws.fill_(0xFF)
+            while len(self._ws) >= self.MAX_WORKSPACES:
+                del self._ws[next(iter(self._ws))]
+        self._ws[key] = ws
+        return ws
+
+    def stash(self, B: int, layer: int = 1, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """relu(Z_layer) of the last training forward / step of batch size B as the kernels stashed it: bf16 [B, hidden] (layer 1: the input layer)."""
+        off = int(self.lib.mshgnn_mlp_stash_offset(self._plan, B, layer))
+        ws = workspace if workspace is not None else self.workspace(B, True)
+        return ws[off:off + B * self.hidden * 2].view(torch.bfloat16).view(B, self.hidden)
+
+    def pitch(self) -> int:
+        return row_pitch(self.in_channels, 2)
+
+    def cast_input(self, x: torch.Tensor) -> torch.Tensor:
+        """[B, in_channels] of any float dtype -> bf16 device rows at the engine's pitch (pad columns zero); rows already in that form pass through."""
+        if x.dim() != 2:
+            raise ValueError("x must be [B, in_channels]")
+        if x.is_cuda and x.device == self.device and x.dtype == torch.bfloat16 and x.is_contiguous() and x.shape[1] % 8 == 0 and x.shape[1] >= self.in_channels \
+                and x.shape[1] in accepted_pitches(self.in_channels, 2) and x.data_ptr() % 16 == 0:
+            return x
+        if x.shape[1] != self.in_channels:
+            raise ValueError(f"x has {x.shape[1]} columns, the model {self.in_channels}")
+        rows = torch.zeros(x.shape[0], self.pitch(), dtype=torch.bfloat16, device=self.device)
+        rows[:, :self.in_channels] = x.to(self.device).to(torch.float32)      # (fp64 -> fp32 -> bf16: torch's two roundings)
+        return rows
+
+    # ---- plumbing ----
+    def _check_flat(self, flat: torch.Tensor, name: str):
+        if flat.dtype != torch.float32 or not flat.is_cuda or flat.device != self.device or flat.numel() != self.n_flat or not flat.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous fp32 device tensor of {self.n_flat} elements")
+
+    def _dense(self, x: torch.Tensor) -> Tuple[MshgnnMlpInput, int]:
+        if not (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 2 and x.is_contiguous()):
+            raise ValueError("x must be contiguous bf16 device rows [B, pitch] (cast_input)")
+        inp = MshgnnMlpInput()
+        inp.x = x.data_ptr(); inp.pitch = x.shape[1]
+        return inp, int(x.shape[0])
+
+    def _series(self, store, starts: torch.Tensor, y, q, li) -> Tuple[MshgnnMlpInput, int]:
+        if not starts.is_cuda or starts.dtype != torch.int64:
+            raise ValueError("starts must be a device int64 tensor")
+        src16, run_ptrs = store.series_step_args(bf16=True)
+        inp = MshgnnMlpInput()
+        inp.x = None; inp.pitch = 0
+        inp.desc = C.pointer(store.desc)
+        inp.src = C.cast(store._src, C.POINTER(C.c_void_p)); inp.src_bf16 = C.cast(src16, C.POINTER(C.c_void_p))
+        inp.src_cstride = C.cast(store._pitch, C.POINTER(C.c_int64)); inp.src_rows = C.cast(store._rows, C.POINTER(C.c_int64))
+        inp.starts = starts.data_ptr()
+        inp.y_out = y.data_ptr() if y is not None else None
+        inp.quat_out = q.data_ptr() if q is not None else None
+        inp.labels_out = li.data_ptr() if li is not None else None
+        inp.run_ptrs = run_ptrs.data_ptr()
+        return inp, int(starts.numel())
+
+    def _series_ok(self, store) -> bool:
+        """What the library's series form takes (it refuses the rest with MSHGNN_EUNSUPPORTED; decided here so that no by-product buffer is made in vain)."""
+        r = store.recipe
+        return (store.dtype == "bf16" and bool(store._fast) and not r.normalize and not (store.desc.sign_flags & 1) and store.n_elements == 1
+                and len(r.node_types) == 1 and r.num_nodes[r.node_types[0]] == 1)
+
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _results(self, B, out, grad_flat, loss):
+        if out is None:
+            out = torch.empty(B, self.out_channels, dtype=torch.float32, device=self.device)
+        if grad_flat is None:
+            grad_flat = torch.empty(self.n_flat, dtype=torch.float32, device=self.device)
+        if loss is None:
+            loss = torch.empty(1, dtype=torch.float32, device=self.device)
+        if out.dtype != torch.float32 or out.numel() != B * self.out_channels or not out.is_contiguous() or not out.is_cuda:
+            raise ValueError("out must be a contiguous fp32 device tensor of B * out_channels elements")
+        self._check_flat(grad_flat, "grad_flat")
+        return out, grad_flat, loss
+
+    def _forward(self, inp, B, params_flat, training, out, workspace):
+        self._check_flat(params_flat, "params_flat")
+        out, _, _ = self._results(B, out, params_flat, None)
+        ws = workspace if workspace is not None else self.workspace(B, training)
+        with torch.cuda.device(self.device):
+            _check(self.lib, self.lib.mshgnn_mlp_forward(self._plan, C.byref(inp), params_flat.data_ptr(), out.data_ptr(), ws.data_ptr(), B, int(training),
+                                                         self._stream()), "mshgnn_mlp_forward")
+        return out
+
+    def _backward(self, inp, B, params_flat, gout, grad_flat, workspace):
+        self._check_flat(params_flat, "params_flat")
+        if gout.dtype != torch.float32 or gout.numel() != B * self.out_channels or not gout.is_contiguous() or not gout.is_cuda:
+            raise ValueError("gout must be a contiguous fp32 device tensor of B * out_channels elements")
+        _, grad_flat, _ = self._results(B, None, grad_flat, None)
+        ws = workspace if workspace is not None else self.workspace(B, True)
+        with torch.cuda.device(self.device):
+            _check(self.lib, self.lib.mshgnn_mlp_backward(self._plan, C.byref(inp), params_flat.data_ptr(), gout.data_ptr(), grad_flat.data_ptr(), ws.data_ptr(), B,
+                                                          self._stream()), "mshgnn_mlp_backward")
+        return grad_flat
+
+    def _step(self, inp, B, kind, target, params_flat, out, grad_flat, loss, workspace):
+        self._check_flat(params_flat, "params_flat")
+        if kind == 1 and self.out_channels % 2:
+            raise ValueError("cross entropy needs an even out_channels (logit pairs)")
+        if target is not None:
+            want = (torch.int32, B * self.out_channels // 2) if kind == 1 else (torch.float32, B * self.out_channels)
+            if target.dtype != want[0] or target.numel() != want[1] or not target.is_contiguous() or not target.is_cuda:
+                raise ValueError("targets: contiguous device fp32 [B, out] (MSE) or int32 [B, out / 2] (cross entropy)")
+        out, grad_flat, loss = self._results(B, out, grad_flat, loss)
+        ws = workspace if workspace is not None else self.workspace(B, True)
+        with torch.cuda.device(self.device):
+            _check(self.lib, self.lib.mshgnn_mlp_step(self._plan, C.byref(inp), kind, target.data_ptr() if target is not None else None, params_flat.data_ptr(),
+                                                      out.data_ptr(), loss.data_ptr(), grad_flat.data_ptr(), ws.data_ptr(), B, self._stream()), "mshgnn_mlp_step")
+        return out, loss, grad_flat
+
+    # ---- dense rows ----
+    def forward(self, x: torch.Tensor, params_flat: torch.Tensor, training: bool = True, out: Optional[torch.Tensor] = None, workspace=None) -> torch.Tensor:
+        inp, B = self._dense(x)
+        return self._forward(inp, B, params_flat, training, out, workspace)
+
+    def backward(self, x: torch.Tensor, params_flat: torch.Tensor, gout: torch.Tensor, grad_flat: Optional[torch.Tensor] = None, workspace=None) -> torch.Tensor:
+        """After `forward(training=True)` on the same rows, parameters and workspace: the flat gradient for dL/d out = gout."""
+        inp, B = self._dense(x)
+        return self._backward(inp, B, params_flat, gout, grad_flat, workspace)
+
+    def step_mse(self, x, params_flat, y, out=None, grad_flat=None, loss=None, workspace=None):
+        """forward + mean((out - y)^2) + backward in one call: (out, loss[1], grad_flat)."""
+        inp, B = self._dense(x)
+        return self._step(inp, B, 0, y, params_flat, out, grad_flat, loss, workspace)
+
+    def step_ce(self, x, params_flat, labels, out=None, grad_flat=None, loss=None, workspace=None):
+        """forward + mean cross entropy over the B * out / 2 logit pairs (labels int32 [B, out / 2] in {0, 1}) + backward: (out, loss[1], grad_flat)."""
+        inp, B = self._dense(x)
+        return self._step(inp, B, 1, labels, params_flat, out, grad_flat, loss, workspace)
+
+    # ---- rows gathered from a resident sequence ----
+    def _assembled(self, store, starts):
+        xs, y, q = store.assemble(starts, reuse_buffers=True)
+        x = xs[0] if xs[0].dtype == torch.bfloat16 else xs[0].to(torch.bfloat16)
+        return x, y, q
+
+    def _after_series(self, store):
+        Engine._vouch_sign_tables(store)
+
+    def forward_series(self, store, starts: torch.Tensor, params_flat: torch.Tensor, out: Optional[torch.Tensor] = None, labels: bool = True,
+                       training: bool = False, workspace=None):
+        """`store.assemble(starts)` + `forward` in one call with no window materialised: (y | None, quat | None, labels_int | None, out).  The by-products are
+        the store's reusable buffers of this batch size.  labels_int (int32 [B, out / 2], y != 0) when the recipe has out / 2 unrotated labels."""
+        B = int(starts.numel())
+        n_flags = self.out_channels // 2 if self.out_channels % 2 == 0 else 0
+        if not self._series_ok(store):
+            x, y, q = self._assembled(store, starts)
+            li = (y != 0).to(torch.int32) if labels and y is not None and n_flags and y.shape[1] == n_flags and not store.recipe.label_rotate else None
+            return (y if labels else None), (q if labels else None), li, self.forward(x, params_flat, training, out, workspace)
+        y, q, li, _ = store.eval_buffers(B, labels, n_flags)
+        inp, B = self._series(store, starts, y, q, li)
+        Engine._vouch_run_ptrs(store, False, self._stream())
+        out = self._forward(inp, B, params_flat, training, out, workspace)
+        return y, q, li, out
+
+    def backward_series(self, store, starts, params_flat, gout, grad_flat=None, workspace=None):
+        """`backward` after `forward_series(training=True)`: the input-layer weight gradient gathers its rows from the series again."""
+        if not self._series_ok(store):
+            x, _, _ = self._assembled(store, starts)
+            return self.backward(x, params_flat, gout, grad_flat, workspace)
+        inp, B = self._series(store, starts, None, None, None)
+        Engine._vouch_run_ptrs(store, False, self._stream())
+        return self._backward(inp, B, params_flat, gout, grad_flat, workspace)
+
+    def _step_series(self, kind, store, starts, params_flat, out, grad_flat, loss, workspace, targets=None):
+        B = int(starts.numel())
+        if targets is None and not store.recipe.label_cols:
+            raise ValueError("the recipe has no labels")
+        if not self._series_ok(store):
+            x, y, q = self._assembled(store, starts)
+            target = targets if targets is not None else ((y != 0).to(torch.int32) if kind == 1 else y)
+            return (target,) + self._step(self._dense(x)[0], B, kind, target.contiguous(), params_flat, out, grad_flat, loss, workspace)
+        if targets is not None:      # the caller's own targets: no label by-products
+            inp, B = self._series(store, starts, None, None, None)
+            Engine._vouch_run_ptrs(store, False, self._stream())
+            return (targets,) + self._step(inp, B, kind, targets, params_flat, out, grad_flat, loss, workspace)
+        y, q, li, _ = store.eval_buffers(B, True, self.out_channels // 2 if kind == 1 else 0)
+        if kind == 1 and li is None:
+            raise ValueError("the recipe's labels are not the model's out / 2 contact flags")
+        inp, B = self._series(store, starts, y, q, li)
+        Engine._vouch_run_ptrs(store, False, self._stream())
+        res = self._step(inp, B, kind, None, params_flat, out, grad_flat, loss, workspace)
+        return ((li if kind == 1 else y),) + res
+
+    def step_mse_series(self, store, starts, params_flat, out=None, grad_flat=None, loss=None, workspace=None, targets=None):
+        """One training step straight from a resident sequence, the targets being the window labels (or `targets`, fp32 [B, out]): (y, out, loss[1],
+        grad_flat) -- bit-identical to `store.assemble(starts)` followed by `step_mse`."""
+        return self._step_series(0, store, starts, params_flat, out, grad_flat, loss, workspace, targets)
+
+    def step_ce_series(self, store, starts, params_flat, out=None, grad_flat=None, loss=None, workspace=None, targets=None):
+        """`step_mse_series` with the cross entropy over the contact flags of each window's last step (or `targets`, int32 [B, out / 2]): (labels, out,
+        loss[1], grad_flat)."""
+        return self._step_series(1, store, starts, params_flat, out, grad_flat, loss, workspace, targets)

@@ -813,3 +813,215 @@ class COM_HGNN(_MSHGNNBase):
         self.num_dimensions_per_base = com_dimension
         self._build_convs(mean_rels=())
         self.decoder = pnn.Linear(hidden_channels, self.num_dimensions_per_base)
+
+
+# ---- the MLP baseline (gnnLightning.py:363-413, gnnLightning_com.py:234-287) ---------------------------------------------------------------------------
+class _MLPSpec:
+    """What the module surface (the flat-parameter views, _FusedStepFn, _deliver_gradients, the flat optimizers) reads of a model's spec, for the MLP: the
+    flat layout in torch's state_dict order of the reference's nn.Sequential, one window = one row."""
+
+    def __init__(self, in_channels, hidden, out_channels, num_layers, regression):
+        self.in_channels, self.hidden, self.out_channels, self.num_layers, self.regression = in_channels, hidden, out_channels, num_layers, regression
+        self.node_types, self.num_nodes, self.out_type = ["mlp"], {"mlp": 1}, "mlp"
+        self._offsets, self._shapes, o = {}, {}, 0
+        for i in range(num_layers):
+            of, kf = (hidden if i < num_layers - 1 else out_channels), (in_channels if i == 0 else hidden)
+            self._offsets[f"{2 * i}.weight"], self._shapes[f"{2 * i}.weight"] = (o, of * kf), (of, kf); o += of * kf
+            self._offsets[f"{2 * i}.bias"], self._shapes[f"{2 * i}.bias"] = (o, of), (of,); o += of
+        self._n = o
+
+    def param_offsets(self):
+        return self._offsets
+
+    def param_shapes(self):
+        return self._shapes
+
+    def flat_size(self):
+        return self._n
+
+
+class _MLPFn(torch.autograd.Function):
+    """The two-call route of MLP.forward on the fused engine: engine.forward(training) here, mshgnn_mlp_backward in backward.  cfg: (model, engine, flat, rows,
+    route, number of parameter tensors); the parameters travel by `route` exactly as in _EngineFn.  No gradient with respect to the inputs."""
+
+    @staticmethod
+    def forward(ctx, cfg, *tensors):
+        model, e, flat, xs, route, n_p = cfg
+        if route == "flat":
+            flat = tensors[0]
+        out = e.forward(xs, flat, training=True)
+        model._fwd_id += 1
+        ctx.cfg, ctx.flat, ctx.ticket = cfg, flat, model._fwd_id
+        ctx.shapes = [p.shape for p in tensors[:n_p]]
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        model, e, _, xs, route, n_p = ctx.cfg
+        flat = ctx.flat
+        if model._fwd_id != ctx.ticket:
+            raise RuntimeError("the activation stash of this forward was overwritten by a later forward of the same model; call backward before the next forward")
+        g32 = gout.contiguous().to(torch.float32)
+        if route == "fast":
+            _deliver_gradients(model, flat, lambda target: e.backward(xs, flat, g32, grad_flat=target))
+            return (None, None)
+        if route == "flat":
+            return (None, e.backward(xs, flat, g32))
+        gflat = e.backward(xs, flat, g32)
+        return (None, *[gflat[o:o + n].view(shape) for (o, n), shape in zip(model._spec.param_offsets().values(), ctx.shapes)])
+
+
+class MLP(_MSHGNNBase):
+    """The reference's MLP baseline as a module: `num_layers` nn.Linear layers with the activation between them, created by torch's own nn.Linear in the
+    reference's order under the reference's names (state_dict keys 0.weight, 0.bias, 2.weight, ...: the same seed gives the same initial weights as
+    nn.Sequential(*modules), gnnLightning.py:391-407).  forward(x [B, in_channels]) -> [B, out_channels] routes by the module surface's one rule:
+      precision "bf16", nn.ReLU(), a shape the fused engine takes, parameters on the device -> engine.MLPEngine through one autograd.Function;
+      anything else on a HIP device (set_precision("f32" | "x3"), another activation, another width) -> operator by operator on ops.linear (fp32 MFMA).
+    There is no CPU path."""
+    kind = "mlp"
+    num_bases = 1
+    num_dimensions_per_base = 6
+
+    def __init__(self, in_channels: int, hidden_channels: int, out_channels: int, num_layers: int, activation_fn=nn.ReLU(), regression: bool = True):
+        super().__init__()
+        if num_layers < 2:
+            raise ValueError("num_layers must be 2 or greater")
+        self._init_common(hidden_channels, num_layers, (["mlp"], []), regression, activation_fn)
+        self.in_channels, self.out_channels = in_channels, out_channels
+        dims = [in_channels] + [hidden_channels] * (num_layers - 1) + [out_channels]
+        for i in range(num_layers):
+            self.add_module(str(2 * i), nn.Linear(dims[i], dims[i + 1]))
+            if i < num_layers - 1:
+                self.add_module(str(2 * i + 1), activation_fn)
+        self._spec = _MLPSpec(in_channels, hidden_channels, out_channels, num_layers, regression)
+        self._fwd_id = 0
+
+    def linears(self):
+        return [getattr(self, str(2 * i)) for i in range(self.num_layers)]
+
+    def __len__(self):
+        return 2 * self.num_layers - 1
+
+    def __getitem__(self, i):
+        return getattr(self, str(range(len(self))[i]))
+
+    def _fused(self) -> bool:
+        from . import engine as eng
+        return (self._fused_activation and self._precision == "bf16"
+                and eng.mlp_supported(self.in_channels, self.hidden_channels, self.out_channels, self.num_layers))
+
+    def _engine(self, device):
+        from . import engine as eng
+        key = ("mlp", str(device))
+        if key not in self._engines:
+            self._engines[key] = eng.MLPEngine(self.in_channels, self.hidden_channels, self.out_channels, self.num_layers, "bf16", device)
+        return self._engines[key]
+
+    def _device_of(self, x):
+        p = self._params_in_flat_order()[0]
+        dev = p.device if p.device.type == "cuda" else x.device
+        if dev.type != "cuda":
+            raise RuntimeError("the MLP runs on a HIP device (parameters and inputs are on the host); there is no CPU fallback")
+        return dev
+
+    def forward(self, x):
+        x2 = x.reshape(-1, self.in_channels) if x.dim() != 2 else x
+        dev = self._device_of(x2)
+        if not self._fused():
+            return self._forward_operators_mlp(x2, dev)
+        e = self._engine(dev)
+        xs = e.cast_input(x2.detach())
+        need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self._params_in_flat_order())
+        flat, route, ptens = self._param_route(dev, need_grad)
+        if route is None:
+            with torch.no_grad():
+                out = e.forward(xs, flat, training=False)
+        else:
+            out = _MLPFn.apply((self, e, flat, xs, route, len(ptens)), *ptens)
+        return out.to(x.dtype) if x.dtype in (torch.float64, torch.float32) and out.dtype != x.dtype else out
+
+    def _forward_operators_mlp(self, x, dev):
+        """Operator by operator on ops.linear (fp32 MFMA, autograd through ops._Linear): the parity route."""
+        from . import ops
+        lin = self.linears()
+        if lin[0].weight.device != dev:
+            raise RuntimeError("move the model to the inputs' device first (model.to(device))")
+        a = x.to(dev, torch.float32)
+        for i, m in enumerate(lin):
+            a = ops.linear(a, m.weight.to(torch.float32), m.bias.to(torch.float32))
+            if i < len(lin) - 1:
+                a = self.activation(a)
+        return a
+
+    # ---- the one-call routes of the wrappers on a windows.WindowBatch ----
+    def _window_route(self, batch, training):
+        store, r = batch.store, batch.store.recipe
+        if not self._fused() or len(r.node_types) != 1 or r.num_nodes[r.node_types[0]] != 1 or r.width(r.node_types[0]) != self.in_channels:
+            return None
+        params = self._params_in_flat_order()
+        if params[0].device.type != "cuda" or params[0].device != store.device or torch.is_grad_enabled() != training:
+            return None
+        n_target = self.out_channels if self.regression else self.out_channels // 2
+        if training:
+            if not all(p.requires_grad for p in params) or _several_processes() or len(r.label_cols) != n_target or (not self.regression and self.out_channels % 2):
+                return None
+        elif r.label_cols and len(r.label_cols) != n_target:
+            return None
+        return self._engine(store.device)
+
+    def _leave_labels(self, e, batch):
+        store, B = batch.store, batch.batch_size
+        if e._series_ok(store):
+            y, q, _, _ = store.eval_buffers(B, True, self.out_channels // 2 if (not self.regression and self.out_channels % 2 == 0) else 0)
+        else:
+            _, y, q = store._buffers(B)
+        batch._labels_from_step(None, y, q)
+
+    def fused_training_step_windows(self, batch):
+        """forward + the wrapper's loss + backward for a `windows.WindowBatch` as ONE MLPEngine.step_*_series call (the rows gathered from the resident series);
+        the labels are left on the batch.  Returns (out, loss) as _MSHGNNBase.fused_training_step_windows does, or None when the route does not apply."""
+        e = self._window_route(batch, training=True)
+        if e is None:
+            return None
+        store = batch.store
+        self._flat_params(store.device)
+        step = e.step_mse_series if self.regression else e.step_ce_series
+
+        def run(g):
+            _, out, loss, _ = step(store, batch.starts, self._flat, grad_flat=g)
+            self._leave_labels(e, batch)
+            return out, loss
+        loss, out = _FusedStepFn.apply(self._anchor, self, run)
+        return out, loss
+
+    def forward_windows(self, batch):
+        """The evaluation forward for a `windows.WindowBatch` without autograd (MLPEngine.forward_series); None when the route does not apply."""
+        e = self._window_route(batch, training=False)
+        if e is None:
+            return None
+        y, q, _, out = e.forward_series(batch.store, batch.starts, self._flat_params(batch.store.device), labels=bool(batch.store.recipe.label_cols))
+        if y is not None:
+            batch._labels_from_step(None, y, q)
+        return out
+
+    def fused_training_step(self, x, y):
+        """The one-call step on the caller's own rows ((x, y) tuple batches): (out, loss) or None."""
+        params = self._params_in_flat_order()
+        if not self._fused() or not torch.is_grad_enabled() or params[0].device.type != "cuda" or not all(p.requires_grad for p in params) or _several_processes():
+            return None
+        dev = params[0].device
+        e = self._engine(dev)
+        xs = e.cast_input(x.reshape(-1, self.in_channels).detach())
+        B = xs.shape[0]
+        self._flat_params(dev)
+        if self.regression:
+            target, step = y.detach().to(dev, torch.float32).reshape(B, self.out_channels).contiguous(), e.step_mse
+        else:
+            target, step = (y.detach().to(dev) != 0).to(torch.int32).reshape(B, self.out_channels // 2).contiguous(), e.step_ce
+        loss, out = _FusedStepFn.apply(self._anchor, self, lambda g: step(xs, self._flat, target, grad_flat=g)[:2])
+        return out, loss
+
+    def reset_parameters(self):
+        for m in self.linears():
+            m.reset_parameters()

@@ -50,10 +50,14 @@ class WindowRecipe:
         (`variable_signs`, `label_signs`), so the transformed windows come out of the same resident series.  Composes: the result can be
         transformed again."""
         perm_of = {}
-        def table(part, n, what):
+        def table(part, n, what, one_node=False):
             if part not in perm_of:
                 perm_of[part] = group.table(part, operator, mode)
             P, c = perm_of[part]
+            if one_node and len(P) != n and n > 0 and len(P) % n == 0 and all(P[k] % n == k % n and c[k] == c[k % n] for k in range(len(P))):
+                # the part's tables are tiled over copies of ONE n-vector (the base series, tiled to the graph models' base nodes) and this variable is a
+                # single node holding one copy (`mlp_recipe`: lin_acc / ang_vel are [T, 3]): the action on one copy -- no permutation, the copy's reflection
+                P, c = list(range(n)), list(c[:n])
             if len(P) != n:
                 raise ValueError(f"{what}: {n} columns, but the group's '{part}' tables have {len(P)}")
             return P, c
@@ -74,7 +78,7 @@ class WindowRecipe:
                 na = len(cols[0])
                 flat = [c for node in cols for c in node]
                 fsig = [x for node in old_signs[vi] for x in node] if old_signs else [1] * len(flat)
-                P, c = table(self.symmetry_parts[s], len(flat), f"variable '{s}' of type '{t}'")
+                P, c = table(self.symmetry_parts[s], len(flat), f"variable '{s}' of type '{t}'", one_node=len(cols) == 1)
                 nflat = [flat[P[k]] for k in range(len(flat))]
                 nsig = [int(c[k]) * int(fsig[P[k]]) for k in range(len(flat))]
                 variables[t].append((s, [nflat[i:i + na] for i in range(0, len(nflat), na)]))
@@ -299,6 +303,51 @@ def solo_com_recipe(kind: str, joint_perm: Sequence[int], history: int = 1) -> W
         variables={"base": [("base_lin", [[0, 1, 2]] * nb), ("base_ang", [[0, 1, 2]] * nb)],
                    "joint": [(s, [[int(j)] for j in joint_perm]) for s in ("q", "qd")]},
         label_series="Y", label_cols=[0, 1, 2, 3, 4, 5] * nb)
+
+
+MLP_NODE_TYPE = "mlp"
+
+
+def mlp_recipe(variables: Sequence[Tuple[str, Sequence[int]]], history: int, label_series: Optional[str] = None, label_cols: Sequence[int] = (),
+               label_rotate: bool = False, quat_series: Optional[str] = None, normalize: bool = False,
+               symmetry_parts: Optional[Dict[str, str]] = None) -> WindowRecipe:
+    """The input of the reference's MLP baseline (flexibleDataset.get_helper_mlp, flexibleDataset.py:510-535): the concatenation, variable by variable, of
+    X.flatten('F') of the sorted [T, n] arrays -- every column's T steps contiguous.  That is ONE node type holding ONE node whose variables list all
+    columns: each (variable, column) becomes one run of `history` elements at consecutive feature offsets, so every window route serves it unchanged.
+    variables: (series name, columns) in the reference's order [lin_acc, ang_vel, j_p, j_v, j_T, f_p, f_v]; absent (None / empty) variables are skipped."""
+    vars_ = [(s, [[int(c) for c in cols]]) for s, cols in variables if s is not None and cols is not None and len(cols) > 0]
+    if not vars_:
+        raise ValueError("an MLP recipe needs at least one variable")
+    return WindowRecipe(node_types=[MLP_NODE_TYPE], num_nodes={MLP_NODE_TYPE: 1}, history=history, variables={MLP_NODE_TYPE: vars_},
+                        label_series=label_series, label_cols=[int(c) for c in label_cols], label_rotate=label_rotate, quat_series=quat_series,
+                        normalize=normalize, symmetry_parts=symmetry_parts)
+
+
+def quadsdk_a1_mlp_recipe(joint_perm: Sequence[int], foot_perm: Sequence[int], history: int = 150, grf_dimension: int = 3,
+                          body_frame_labels: bool = False, normalize: bool = False) -> WindowRecipe:
+    """The A1 / Quad-SDK dataset as the MLP baseline reads it: in = history x 42 (lin acc 3, ang vel 3, q / qd / tau 12 each in sorted joint order); series
+    names, labels and symmetry parts of `quadsdk_a1_c2_recipe`."""
+    g = quadsdk_a1_c2_recipe(joint_perm, foot_perm, history, grf_dimension, body_frame_labels, normalize)
+    jp = [int(j) for j in joint_perm]
+    return mlp_recipe([("imu_acc", [0, 1, 2]), ("imu_omega", [0, 1, 2]), ("q", jp), ("qd", jp), ("tau", jp)], history, g.label_series, g.label_cols,
+                      g.label_rotate, g.quat_series, normalize, g.symmetry_parts)
+
+
+def minicheetah_mlp_recipe(joint_perm: Sequence[int], foot_perm: Sequence[int], history: int = 150, normalize: bool = False) -> WindowRecipe:
+    """The MiniCheetah contact dataset as the MLP baseline reads it: in = history x 54 (lin acc, ang vel, q, qd, foot p, foot v); series names, labels and
+    symmetry parts of `minicheetah_k4_recipe`."""
+    g = minicheetah_k4_recipe(joint_perm, foot_perm, history, normalize)
+    jp = [int(j) for j in joint_perm]
+    fc = [int(3 * i + k) for i in foot_perm for k in range(3)]
+    return mlp_recipe([("imu_acc", [0, 1, 2]), ("imu_omega", [0, 1, 2]), ("q", jp), ("qd", jp), ("p", fc), ("v", fc)], history, g.label_series, g.label_cols,
+                      False, None, normalize, g.symmetry_parts)
+
+
+def solo_com_mlp_recipe(joint_perm: Sequence[int], history: int = 1) -> WindowRecipe:
+    """The Solo-12 centroidal-momentum dataset as the MLP baseline reads it (gnnLightning_com.py:234-287): in = history x 24 (q | qd), labels = the 6-D base
+    velocity of the window's last row; series names of `solo_com_recipe` / `solo_com_arrays`."""
+    jp = [int(j) for j in joint_perm]
+    return mlp_recipe([("q", jp), ("qd", jp)], history, "Y", [0, 1, 2, 3, 4, 5])
 
 
 def solo_com_arrays(X: np.ndarray, Y: np.ndarray) -> Dict[str, np.ndarray]:

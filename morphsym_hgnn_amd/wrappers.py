@@ -534,6 +534,96 @@ class COM_HGNN_SYM_Lightning(COM_Base_Lightning):
         self._finish_init(dummy_batch)
 
 
+class _MLPSteps:
+    """What the two MLP wrappers share: `step_helper_function` for a `windows.WindowBatch` of an `windows.mlp_recipe` store (under no_grad: straight from the
+    resident series, MLPEngine.forward_series) or the reference's `(x, y)` tuple batch, and the one-call training step (MLPEngine.step_*_series / step_*)."""
+
+    def _rows(self, batch):
+        from .windows import WindowBatch
+        if isinstance(batch, WindowBatch):
+            t = batch.store.recipe.node_types[0]
+            return batch.x_dict[t][:, :self.model.in_channels], batch.y
+        x, y = batch
+        return x, y
+
+    def step_helper_function(self, batch):
+        from .windows import WindowBatch
+        m = self.model
+        if isinstance(batch, WindowBatch) and self.fused_evaluation_step and not torch.is_grad_enabled():
+            out = m.forward_windows(batch)
+            if out is not None:
+                return batch.y, out
+        x, y = self._rows(batch)
+        return y, m(x)
+
+    def _fused_mlp_step(self, batch):
+        """(y, y_pred, loss) from the one-call step, or None when the two-call route has to be taken."""
+        if not self.fused_training_step:
+            return None
+        from .windows import WindowBatch
+        m = self.model
+        if isinstance(batch, WindowBatch):
+            r = m.fused_training_step_windows(batch)
+            if r is not None:
+                return batch.y, r[0], r[1]
+        x, y = self._rows(batch)
+        r = m.fused_training_step(x, y)
+        return None if r is None else (y, r[0], r[1])
+
+
+class MLP_Lightning(_MLPSteps, Base_Lightning):
+    """`MLP_Lightning` (gnnLightning.py:363-413): the MLP baseline every table of the paper compares against.  `mlp_model` is a `models.MLP` with the
+    reference's parameter names (`mlp_model.0.weight`, ...); `model` is the same module."""
+
+    def __init__(self, in_channels: int, hidden_channels: int, out_channels: int, num_layers: int, batch_size: int, optimizer: str = "adam",
+                 lr: float = 0.003, regression: bool = True, activation_fn=nn.ReLU()):
+        super().__init__(optimizer, lr, regression)
+        self.batch_size = batch_size
+        self.regression = regression
+        self.mlp_model = models.MLP(in_channels, hidden_channels, out_channels, num_layers, activation_fn, regression=regression)
+        if _L is not None:  # pragma: no cover
+            self.save_hyperparameters(ignore=["activation_fn"])
+
+    model = property(lambda self: self.mlp_model)
+
+    def training_step(self, batch, batch_idx):
+        r = self._fused_mlp_step(batch)
+        if r is None:
+            return Base_Lightning.training_step(self, batch, batch_idx)
+        y, y_pred, loss = r
+        self.calculate_losses_step(y, y_pred)
+        self._m().set_step_loss(loss)
+        self.log_losses("train", on_step=True)
+        return loss
+
+
+class COM_MLP_Lightning(_MLPSteps, COM_Base_Lightning):
+    """`COM_MLP_Lightning` (gnnLightning_com.py:234-287): the MLP baseline of the centroidal-momentum task; `model.num_bases = 1`,
+    `model.num_dimensions_per_base = 6`."""
+
+    def __init__(self, in_channels: int, hidden_channels: int, out_channels: int, num_layers: int, batch_size: int, optimizer: str = "adam",
+                 lr: float = 0.003, regression: bool = True, activation_fn=nn.ReLU(), data_path=None, stats=None):
+        super().__init__(optimizer, lr, data_path, stats)
+        self.batch_size = batch_size
+        self.regression = regression
+        self.model = models.MLP(in_channels, hidden_channels, out_channels, num_layers, activation_fn, regression=True)
+        self.model.num_bases = 1
+        self.model.num_dimensions_per_base = 6
+        if _L is not None:  # pragma: no cover
+            self.save_hyperparameters(ignore=["activation_fn"])
+
+    def training_step(self, batch, batch_idx):
+        r = self._fused_mlp_step(batch)
+        if r is None:
+            y, y_pred = self.step_helper_function(batch)
+            self.calculate_losses_step(y, y_pred)
+        else:
+            self.calculate_losses_step(r[0], r[1])
+            self._m().set_step_loss(r[2])
+        self.log_losses("train", on_step=True)
+        return self.loss
+
+
 class GraphedTrainingStep:
     """One training step of a wrapper -- `optimizer.zero_grad(); loss = wrapper.training_step(batch, i); loss.backward(); optimizer.step()` -- captured ONCE in a
     HIP graph and replayed per batch.
