@@ -2,7 +2,7 @@
 """The MLP baseline (the reference's `--model_type mlp`, gnnLightning.py:363-413) trained straight from a resident dataset:
 
     ResidentDataset(sequences, quadsdk_a1_mlp_recipe(...))   one node type holding one node: a window row is get_helper_mlp's input
-    MLP_Lightning(in = history x 42, hidden, out = 4, ...)   models.MLP at precision "bf16": the fused engine (engine.MLPEngine)
+    MLP_Lightning(in = history x 42, hidden, out = 4, ...)   models.MLP at the default precision ("x3", the split-bf16 parity plan): the fused engine (engine.MLPEngine)
     GraphedTrainingStep(model, opt, batch, index_source=train)   index mapping + the fused series step + FlatAdam captured once, replayed per batch
     evaluate_table(model, val.orbit view, {})                the evaluators' table (one row per symmetry operator, one column per sequence)
 
@@ -29,7 +29,7 @@ def train(epochs=3, batch=64, rows=(700, 1300), history=150, hidden=128, layers=
     train_view, val_view = dataset.split(0.85)
     torch.manual_seed(0)
     model = wrappers.MLP_Lightning(recipe.width("mlp"), hidden, 4, layers, batch, optimizer="adam", lr=lr, regression=True).to(dev)
-    model.model.set_precision("bf16")      # the fused engine; "f32" / "x3" run operator by operator
+    # (the default precision "x3" runs the fused split-bf16 step at 1e-4 of fp64; model.model.set_precision("bf16") trades that for the bf16 step's speed)
     model.graph_safe_optimizer = graphed
     opt = model.configure_optimizers()
     gen = torch.Generator(device=dev).manual_seed(1234)

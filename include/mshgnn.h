@@ -573,9 +573,15 @@ int mshgnn_comm_allreduce_sum(mshgnn_comm* comm, float* buf, int64_t n, void* st
  * The reference's MLP (gnnLightning.py:391-405: nn.Sequential of num_layers Linear layers with ReLU between them, in -> hidden -> ... -> hidden -> out) on the
  * bf16 arithmetic class of the HGNN engine's bf16 plan: inputs and weights are bf16 MFMA operands (weights rounded from the flat fp32 buffer), fp32 accumulation
  * and bias add, activations and activation gradients pass between layers as bf16, output / loss / parameter gradients fp32.  No floating-point atomic: every
- * sum has a fixed order, two runs give identical bits.  The flat parameter buffer is torch's state_dict order of that nn.Sequential: 0.weight, 0.bias,
+ * sum has a fixed order, two runs give identical bits.
+ * dtype MSHGNN_BF16X3 runs the same launches on the split-bf16 arithmetic class of the HGNN engine's parity plan (1e-4 of fp64): every operand of a product
+ * travels as hi = bf16(v), lo = bf16(v - hi) (both roundings to nearest even) and a product is hi hi + lo hi + hi lo with fp32 accumulation.  The dense rows are
+ * fp32 and are split while they are staged; every packed weight region of the workspace is a hi image followed by a lo image; every stash and activation
+ * gradient is rows of [hi hidden | lo hidden] bf16 (dZ of the output layer: [hi 16 | lo 16]); the ReLU mask of the backward sweep is [hi > 0].  There is no
+ * series form on this dtype.  The flat parameter buffer is torch's state_dict order of that nn.Sequential: 0.weight, 0.bias,
  * 2.weight, 2.bias, ..., each weight [out_f, in_f] row-major (mshgnn_mlp_info.off_w / off_b, Linear layer i = 0 .. num_layers - 1).
- * Supported: hidden 128 / 256 / 384 / 512, in_channels 1 .. 16384 (no alignment condition), out_channels 1 .. 16, num_layers 2 .. 16, dtype MSHGNN_BF16;
+ * Supported: hidden 128 / 256 / 384 / 512, in_channels 1 .. 16384 (no alignment condition), out_channels 1 .. 16, num_layers 2 .. 16, dtype MSHGNN_BF16 or
+ * MSHGNN_BF16X3 (not MSHGNN_F32);
  * anything else is MSHGNN_EUNSUPPORTED with the limit named in mshgnn_last_error().
  * A step is five launches at any depth: weight pack, input layer, stack (layers 2 .. L, the loss tail and the backward sweep down to dZ_1 in one workgroup
  * per 32-row tile, activations LDS-resident), weight gradients (partial sums over row slabs), fixed-order slab sum (+ the loss).  The series form adds the
@@ -594,8 +600,8 @@ typedef struct mshgnn_mlp_info {
     int64_t lds_bytes;                            /* dynamic LDS of the stack launch                                               */
     double flops_fwd, flops_bwd;                  /* algorithmic FLOPs / window (2 per MAC): forward; backward (dA chain + all dW)  */
 } mshgnn_mlp_info;
-/* Where a batch's rows come from.  Dense form: x != NULL, bf16 rows [batch][pitch], 16-byte aligned, pitch a multiple of 8 and >= in_channels rounded up to 8;
- * everything below `pitch` is ignored.  Series form: x == NULL and desc / src / src_bf16 / src_cstride / src_rows / starts / run_ptrs exactly as
+/* Where a batch's rows come from.  Dense form: x != NULL, bf16 rows (MSHGNN_BF16X3: fp32 rows) [batch][pitch], 16-byte aligned, pitch a multiple of 8 and >= in_channels rounded up to 8;
+ * columns at or beyond in_channels are ignored.  Series form (MSHGNN_BF16 only; MSHGNN_BF16X3: MSHGNN_EUNSUPPORTED, assemble and use the dense form): x == NULL and desc / src / src_bf16 / src_cstride / src_rows / starts / run_ptrs exactly as
  * mshgnn_step_mse_series takes them (desc->run_ptrs_ready vouches the same way); row b is the window of the one node row of the recipe at starts[b], gathered
  * per K chunk from the bf16 series -- no window row is written to memory, the weight-gradient launch gathers the same operand again.  The series form takes a
  * bf16, fast_layout, unstandardised, unsigned descriptor with n_types == 1, type_nodes[0] == 1, type_width[0] == in_channels and one group element; any other
@@ -618,8 +624,8 @@ void mshgnn_mlp_destroy(mshgnn_mlp_plan* plan);
 int mshgnn_mlp_info_get(const mshgnn_mlp_plan* plan, mshgnn_mlp_info* info);
 /* Bytes of the caller-owned workspace for `batch` rows (16-byte aligned base).  training = 0: forward only.  0: bad arguments. */
 size_t mshgnn_mlp_workspace_bytes(const mshgnn_mlp_plan* plan, int64_t batch, int training);
-/* Byte offset inside a training workspace of the bf16 stash of relu(Z_layer) (layer = 1 .. num_layers - 1, [rows][hidden], rows = batch rounded up to the tile;
- * rows past the batch are zeros) -- for tests / debugging; 0: no such stash.                                                                                  */
+/* Byte offset inside a training workspace of the bf16 stash of relu(Z_layer) (layer = 1 .. num_layers - 1, [rows][hidden], MSHGNN_BF16X3: [rows][hi hidden |
+ * lo hidden]; rows = batch rounded up to the tile; rows past the batch are zeros) -- for tests / debugging; 0: no such stash.                                                                                  */
 size_t mshgnn_mlp_stash_offset(const mshgnn_mlp_plan* plan, int64_t batch, int layer);
 /* out: fp32 [batch][out_channels].  training != 0 leaves the bf16 stashes mshgnn_mlp_backward reads. */
 int mshgnn_mlp_forward(const mshgnn_mlp_plan* plan, const mshgnn_mlp_input* input, const float* params, float* out, void* workspace, int64_t batch,

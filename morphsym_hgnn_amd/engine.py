@@ -1189,19 +1189,22 @@ def mlp_compile_host(in_channels: int, hidden: int, out_channels: int, num_layer
 
 class MLPEngine:
     """The reference's MLP baseline (gnnLightning.py:391-405) on one GPU: a ctypes mirror of the mshgnn_mlp_* entry points.  Parameters and gradients are one
-    flat fp32 buffer in torch's state_dict order of the nn.Sequential (`offsets()`).  Dense rows: bf16 [B, pitch] (`cast_input`); the series methods take a
+    flat fp32 buffer in torch's state_dict order of the nn.Sequential (`offsets()`).  dtype "bf16": the bf16 arithmetic; "x3": the split-bf16 parity plan (every
+    operand a hi / lo pair of bf16, 1e-4 of fp64).  Dense rows: bf16 [B, pitch] ("x3": fp32) from `cast_input`; the series methods take a
     `windows.SequenceStore` / `ResidentDataset` of an `mlp_recipe` and device `starts`, and gather the rows inside the kernels -- where the library's series
-    form refuses (standardised recipes, `transformed` / `orbit` stores, fp32 stores) they assemble the windows and run the dense form: same bits."""
+    form refuses (standardised recipes, `transformed` / `orbit` stores, fp32 stores, and every store on an "x3" engine, which has no series form) they assemble
+    the windows and run the dense form: same bits."""
 
     def __init__(self, in_channels: int, hidden: int, out_channels: int, num_layers: int, dtype: str = "bf16", device: Optional[torch.device] = None):
-        if dtype != "bf16":
-            raise ValueError("the fused MLP runs the bf16 arithmetic (dtype='bf16'); models.MLP serves 'f32' / 'x3' operator by operator")
+        if dtype not in ("bf16", "x3"):
+            raise ValueError("the fused MLP runs the bf16 and the split-bf16 arithmetic (dtype='bf16' / 'x3'); models.MLP serves 'f32' operator by operator")
         if not torch.cuda.is_available():
             raise RuntimeError("the MLP engine needs a HIP device; there is no CPU fallback")
         self.lib = load_library()
         self.in_channels, self.hidden, self.out_channels, self.num_layers, self.dtype = int(in_channels), int(hidden), int(out_channels), int(num_layers), dtype
         self.device = torch.device(device if device is not None else "cuda:0")
         self._desc = MshgnnMlpDesc(self.in_channels, self.hidden, self.out_channels, self.num_layers, DTYPE_CODES[dtype])
+        self._row_dtype, self._row_bytes = (torch.float32, 4) if dtype == "x3" else (torch.bfloat16, 2)
         self._plan = C.c_void_p()
         with torch.cuda.device(self.device):
             _check(self.lib, self.lib.mshgnn_mlp_create(C.byref(self._desc), C.byref(self._plan)), "mshgnn_mlp_create")
@@ -1246,24 +1249,29 @@ class MLPEngine:
         return ws
 
     def stash(self, B: int, layer: int = 1, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """relu(Z_layer) of the last training forward / step of batch size B as the kernels stashed it: bf16 [B, hidden] (layer 1: the input layer)."""
+        """relu(Z_layer) of the last training forward / step of batch size B as the kernels stashed it: bf16 [B, hidden] (layer 1: the input layer); on an "x3"
+        engine fp32 [B, hidden] = hi + lo of the stashed pairs (exact in fp32)."""
         off = int(self.lib.mshgnn_mlp_stash_offset(self._plan, B, layer))
         ws = workspace if workspace is not None else self.workspace(B, True)
+        if self.dtype == "x3":
+            pair = ws[off:off + B * self.hidden * 4].view(torch.bfloat16).view(B, 2, self.hidden)
+            return pair[:, 0].float() + pair[:, 1].float()
         return ws[off:off + B * self.hidden * 2].view(torch.bfloat16).view(B, self.hidden)
 
     def pitch(self) -> int:
-        return row_pitch(self.in_channels, 2)
+        return (row_pitch(self.in_channels, self._row_bytes) + 7) // 8 * 8      # (the kernels stage 8 columns at a time; fp32 rows of <= 32 columns round up to it)
 
     def cast_input(self, x: torch.Tensor) -> torch.Tensor:
-        """[B, in_channels] of any float dtype -> bf16 device rows at the engine's pitch (pad columns zero); rows already in that form pass through."""
+        """[B, in_channels] of any float dtype -> device rows of the engine's row dtype (bf16; "x3": fp32) at the engine's pitch (pad columns zero); rows already
+        in that form pass through."""
         if x.dim() != 2:
             raise ValueError("x must be [B, in_channels]")
-        if x.is_cuda and x.device == self.device and x.dtype == torch.bfloat16 and x.is_contiguous() and x.shape[1] % 8 == 0 and x.shape[1] >= self.in_channels \
-                and x.shape[1] in accepted_pitches(self.in_channels, 2) and x.data_ptr() % 16 == 0:
+        if x.is_cuda and x.device == self.device and x.dtype == self._row_dtype and x.is_contiguous() and x.shape[1] % 8 == 0 and x.shape[1] >= self.in_channels \
+                and x.shape[1] in accepted_pitches(self.in_channels, self._row_bytes) | {self.pitch()} and x.data_ptr() % 16 == 0:
             return x
         if x.shape[1] != self.in_channels:
             raise ValueError(f"x has {x.shape[1]} columns, the model {self.in_channels}")
-        rows = torch.zeros(x.shape[0], self.pitch(), dtype=torch.bfloat16, device=self.device)
+        rows = torch.zeros(x.shape[0], self.pitch(), dtype=self._row_dtype, device=self.device)
         rows[:, :self.in_channels] = x.to(self.device).to(torch.float32)      # (fp64 -> fp32 -> bf16: torch's two roundings)
         return rows
 
@@ -1273,8 +1281,8 @@ class MLPEngine:
             raise ValueError(f"{name} must be a contiguous fp32 device tensor of {self.n_flat} elements")
 
     def _dense(self, x: torch.Tensor) -> Tuple[MshgnnMlpInput, int]:
-        if not (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 2 and x.is_contiguous()):
-            raise ValueError("x must be contiguous bf16 device rows [B, pitch] (cast_input)")
+        if not (x.is_cuda and x.dtype == self._row_dtype and x.dim() == 2 and x.is_contiguous()):
+            raise ValueError(f"x must be contiguous {'fp32' if self.dtype == 'x3' else 'bf16'} device rows [B, pitch] (cast_input)")
         inp = MshgnnMlpInput()
         inp.x = x.data_ptr(); inp.pitch = x.shape[1]
         return inp, int(x.shape[0])
@@ -1298,7 +1306,7 @@ class MLPEngine:
     def _series_ok(self, store) -> bool:
         """What the library's series form takes (it refuses the rest with MSHGNN_EUNSUPPORTED; decided here so that no by-product buffer is made in vain)."""
         r = store.recipe
-        return (store.dtype == "bf16" and bool(store._fast) and not r.normalize and not (store.desc.sign_flags & 1) and store.n_elements == 1
+        return (self.dtype == "bf16" and store.dtype == "bf16" and bool(store._fast) and not r.normalize and not (store.desc.sign_flags & 1) and store.n_elements == 1
                 and len(r.node_types) == 1 and r.num_nodes[r.node_types[0]] == 1)
 
     def _stream(self):
@@ -1374,6 +1382,9 @@ class MLPEngine:
     # ---- rows gathered from a resident sequence ----
     def _assembled(self, store, starts):
         xs, y, q = store.assemble(starts, reuse_buffers=True)
+        if self.dtype == "x3":      # an fp32 store's rows as they are; a bf16 store's widened (exact: lo = 0)
+            x = xs[0]
+            return self.cast_input(x if x.dtype == torch.float32 and x.shape[1] % 8 == 0 else x[:, :self.in_channels]), y, q
         x = xs[0] if xs[0].dtype == torch.bfloat16 else xs[0].to(torch.bfloat16)
         return x, y, q
 

@@ -876,8 +876,9 @@ class MLP(_MSHGNNBase):
     """The reference's MLP baseline as a module: `num_layers` nn.Linear layers with the activation between them, created by torch's own nn.Linear in the
     reference's order under the reference's names (state_dict keys 0.weight, 0.bias, 2.weight, ...: the same seed gives the same initial weights as
     nn.Sequential(*modules), gnnLightning.py:391-407).  forward(x [B, in_channels]) -> [B, out_channels] routes by the module surface's one rule:
-      precision "bf16", nn.ReLU(), a shape the fused engine takes, parameters on the device -> engine.MLPEngine through one autograd.Function;
-      anything else on a HIP device (set_precision("f32" | "x3"), another activation, another width) -> operator by operator on ops.linear (fp32 MFMA).
+      precision "x3" (the default: the split-bf16 parity plan, 1e-4 of fp64) or "bf16", nn.ReLU(), a shape the fused engine takes, parameters on the device
+        -> the engine.MLPEngine of that precision through one autograd.Function;
+      anything else on a HIP device (set_precision("f32"), another activation, another width) -> operator by operator on ops.linear (fp32 MFMA).
     There is no CPU path."""
     kind = "mlp"
     num_bases = 1
@@ -908,14 +909,14 @@ class MLP(_MSHGNNBase):
 
     def _fused(self) -> bool:
         from . import engine as eng
-        return (self._fused_activation and self._precision == "bf16"
+        return (self._fused_activation and self._precision in ("bf16", "x3")
                 and eng.mlp_supported(self.in_channels, self.hidden_channels, self.out_channels, self.num_layers))
 
     def _engine(self, device):
         from . import engine as eng
-        key = ("mlp", str(device))
+        key = (self._precision, str(device))
         if key not in self._engines:
-            self._engines[key] = eng.MLPEngine(self.in_channels, self.hidden_channels, self.out_channels, self.num_layers, "bf16", device)
+            self._engines[key] = eng.MLPEngine(self.in_channels, self.hidden_channels, self.out_channels, self.num_layers, self._precision, device)
         return self._engines[key]
 
     def _device_of(self, x):

@@ -6,6 +6,8 @@ at 64 and 8192 windows.  Routes:
   (b) dense    SequenceStore.assemble + MLPEngine.step_*: the fused step on materialised windows
   (c) ops      models.MLP at precision "f32": operator by operator on ops.linear (fp32 MFMA) with torch's loss and autograd -- what the package could already run
   (d) torch    nn.Sequential under bf16 autocast on assembled windows with torch's loss and backward
+  (e) x3       SequenceStore.assemble (fp32 store) + MLPEngine("x3").step_*: the fused split-bf16 step on dense fp32 rows -- what models.MLP runs at the
+               default precision, to be compared with (c), the route the same request took before
 Every step is bracketed by HIP events on the stream; the `starts` rotate over resident index tensors, so no step re-reads the previous step's windows;
 warm-up steps come first.  Prints one JSON line per (shape, batch)."""
 import argparse
@@ -55,7 +57,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--rows", type=int, default=60000)
     ap.add_argument("--batches", type=int, nargs="+", default=[64, 8192])
-    ap.add_argument("--routes", default="abcd")
+    ap.add_argument("--routes", default="abcde")
     ap.add_argument("--shapes", nargs="+", default=["minicheetah", "a1"])
     args = ap.parse_args()
     for kind in args.shapes:
@@ -63,7 +65,9 @@ def main():
         recipe = windows.minicheetah_mlp_recipe(JP, FP, 150) if ce else windows.quadsdk_a1_mlp_recipe(JP, FP, 150, 1)
         store = windows.SequenceStore(sequence(kind, args.rows), recipe, dtype="bf16", device=DEV)
         in_channels, out = recipe.width("mlp"), (8 if ce else 4)
+        store32 = windows.SequenceStore(sequence(kind, args.rows), recipe, dtype="f32", device=DEV)
         e = engine.MLPEngine(in_channels, 128, out, 8, "bf16", DEV)
+        e3 = engine.MLPEngine(in_channels, 128, out, 8, "x3", DEV)
         torch.manual_seed(0)
         m_ops = models.MLP(in_channels, 128, out, 8).to(DEV).set_precision("f32")
         m_torch = nn.Sequential(*[type(mod)(mod.in_features, mod.out_features) if isinstance(mod, nn.Linear) else nn.ReLU() for mod in m_ops]).to(DEV)
@@ -97,8 +101,15 @@ def main():
                     o = m_torch(xs[0][:, :in_channels])
                 lossf(o, y).backward()
 
+            def x3(st):
+                xs, y, _ = store32.assemble(st, reuse_buffers=True)
+                if ce:
+                    e3.step_ce(xs[0], flat, (y != 0).to(torch.int32), out=out_t, grad_flat=grad, loss=loss)
+                else:
+                    e3.step_mse(xs[0], flat, y, out=out_t, grad_flat=grad, loss=loss)
+
             res = {"shape": kind, "in": in_channels, "hidden": 128, "layers": 8, "out": out, "loss": "ce" if ce else "mse", "windows": B}
-            for key, fn, name in (("a", a, "series"), ("b", b, "dense"), ("c", c, "ops"), ("d", d, "torch")):
+            for key, fn, name in (("a", a, "series"), ("b", b, "dense"), ("c", c, "ops"), ("d", d, "torch"), ("e", x3, "x3")):
                 if key in args.routes:
                     med, best = timed(fn, starts_list, args.steps, args.warmup)
                     res[name + "_ms"], res[name + "_min_ms"], res[name + "_windows_per_s"] = round(med, 4), round(best, 4), round(B / med * 1e3)
