@@ -1,5 +1,7 @@
 // MLP baselines (include/mshgnn.h, "MLP baselines"): y = W_L relu(... relu(W_1 x + b_1) ...) + b_L, the reference's nn.Sequential (gnnLightning.py:391-405),
-// on bf16 MFMA operands with fp32 accumulation.  Launches of one step, all on the caller's stream:
+// on bf16 MFMA operands with fp32 accumulation.  Launches of one step, all on the caller's stream; every kernel that touches an operand is one template over the
+// plan (<X3>: false the bf16 plan, true the split plan below; <X3, SERIES> where the batch's rows are read), so a kernel trace shows k_mlp_stack<true> next to
+// k_mlp_stack<false>:
 //   k_mlp_pack    the fp32 weights rounded to bf16: W_1 [H][K1p] (K zero-padded to 128), W_l and W_l^T for l = 2 .. L (the output layer padded to 16 rows / 32 columns)
 //   k_mlp_in      A_1 = relu(X W_1^T + b_1) -> bf16 stash.  X: dense bf16 rows, or gathered per 8-element K chunk from the resident bf16 series (mlp_fetch8: one
 //                 unaligned 16-byte load, two and a splice where the chunk straddles two runs; element-wise for history < 8).  Series form: the first workgroups
@@ -11,12 +13,17 @@
 //   k_mlp_reduce  grad = the slabs added in slab order; one more workgroup adds the tiles' loss terms in tile order.
 // Rounding points (bf16, round to nearest even): X (given as bf16), every weight, A_l = relu(Z_l + b_l) for l < L, dZ_L = the loss gradient (or gout), dZ_l for l < L.
 // Z_l, the bias add, out, the loss and every dW / db are fp32.
-// Split plan (dtype MSHGNN_BF16X3, the arithmetic of mshgnn_x3.hip): the same five launches (k_mlp_pack_x3, k_mlp_in_x3, k_mlp_stack_x3, k_mlp_wgrad_x3, k_mlp_reduce) with
-// every operand of a product as hi = bf16(v), lo = bf16(v - hi) and every product as hi hi + lo hi + hi lo, fp32 accumulation.  X: dense fp32 rows, split in registers
-// while they are staged (no series form).  Every packed weight region is a hi image followed by a lo image; every stash and dZ row is [hi | lo] (A_l, dZ_l: 2 H bf16,
-// dZ_L: 2 x 16).  Rounding points: the second rounding (lo) of X, every weight, A_l and dZ_l; the ReLU mask of the backward sweep is [hi > 0].
+// Split plan (dtype MSHGNN_BF16X3, the arithmetic of mshgnn_x3.hip): the same kernels at X3 = true, with every operand of a product as hi = bf16(v),
+// lo = bf16(v - hi) and every product as hi hi + lo hi + hi lo (the lo half of the weight, or of dZ in the weight gradient, first), fp32 accumulation.  X: dense
+// fp32 rows, split in registers while they are staged (no series form: <true, true> is never instantiated).  Every packed weight region is a hi image followed
+// by a lo image; every stash and dZ row is [hi | lo] (A_l, dZ_l: 2 H bf16, dZ_L: 2 x 16).  Rounding points: the second rounding (lo) of X, every weight, A_l and
+// dZ_l; the ReLU mask of the backward sweep is [hi > 0].
+// What differs between the plans lives in four primitives: mlp_fetch8 (8 K elements of a row as NP octs), mlp_store4 / mlp_store2 (values rounded to one quad or
+// pair, or to the hi and the lo one), mlp_mma (one MFMA, or the three); the kernel bodies name the plan only in strides written NP * ... and, in k_mlp_in, in the
+// spelling of one statement (see there).
 #include <algorithm>
 #include <new>
+#include <type_traits>
 
 #include "mshgnn_enc.hpp"
 
@@ -103,64 +110,9 @@ MlpWs mlp_layout(const mshgnn_mlp_desc& d, int64_t n_flat, int64_t B, bool train
     return w;
 }
 
-// ---- the batch's rows: dense bf16 rows, or windows of the resident bf16 series ----
-struct MlpIn {
-    const __bf16* x; int64_t pitch;                                   // dense (split plan: fp32 rows behind the same pointer, pitch in floats)
-    const unsigned long long* run_ptr; const int64_t* starts; int T;  // series
-    int in; int64_t B;
-};
-struct RowRef { const __bf16* p; int64_t s; };
-template <bool SERIES> __device__ __forceinline__ RowRef mlp_row(const MlpIn& a, int64_t b) {      // b < B
-    RowRef r; r.p = nullptr; r.s = 0;
-    if constexpr (SERIES) r.s = a.starts[b]; else r.p = a.x + b * a.pitch;
-    return r;
-}
-// elements [k0, k0 + 8) of a row as 8 bf16 (k0 a multiple of 8); elements at or beyond `in` are zeros
-template <bool SERIES> __device__ __forceinline__ u32x4 mlp_fetch8(const MlpIn& a, const RowRef& r, int k0) {
-    u32x4 v = u32x4{0, 0, 0, 0};
-    const int nvalid = a.in - k0;
-    if (nvalid <= 0) return v;
-    if constexpr (!SERIES) {
-        v = *reinterpret_cast<const u32x4*>(r.p + k0);
-    } else {
-        const int T = a.T;
-        if (T >= 8) {
-            const u32x4 ones = u32x4{0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u};      // a constant-1 run (run pointer 0)
-            const int j = k0 / T, off = k0 - j * T, n0 = min(8, T - off);
-            const unsigned long long pa = a.run_ptr[j];
-            v = ones;
-            if (pa) v = *reinterpret_cast<const u32x4*>(reinterpret_cast<const __bf16*>(pa) + r.s + off);      // 2-byte aligned; may run into the column's slack
-            if (min(nvalid, 8) > n0) {      // the chunk's tail belongs to run j + 1 (then n0 < 8, and (j + 1) T = k0 + n0 < in: the run exists)
-                const unsigned long long pb = a.run_ptr[j + 1];
-                u32x4 vb = ones;
-                if (pb) vb = *reinterpret_cast<const u32x4*>(reinterpret_cast<const __bf16*>(pb) + r.s);
-                v = splice8(v, vb, n0);
-            }
-        } else {      // runs shorter than a chunk: element by element
-            unsigned e16[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                e16[e] = 0u;
-                const int k = k0 + e;
-                if (k < a.in) {
-                    const int j = k / T, off = k - j * T;
-                    const unsigned long long p = a.run_ptr[j];
-                    e16[e] = p ? (unsigned)reinterpret_cast<const unsigned short*>(p)[r.s + off] : 0x3f80u;
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) v[q] = e16[2 * q] | (e16[2 * q + 1] << 16);
-        }
-    }
-    if (nvalid < 8) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const unsigned lo = 2 * q < nvalid ? 0xffffu : 0u, hi = 2 * q + 1 < nvalid ? 0xffff0000u : 0u;
-            v[q] &= lo | hi;
-        }
-    }
-    return v;
-}
+// ---- the plan's primitives: every kernel below is one template over the plan (X3: the split plan) and reads the same for both; NP operands per product ----
+template <bool X3> constexpr int mlp_np = X3 ? 2 : 1;      // planes per operand: hi alone, or hi and lo
+template <int NP> struct Octs { u32x4 v[NP]; };             // 8 K elements of one operand, per plane
 
 __device__ __forceinline__ u32x2 pack4_bf16(f32x4 v) {
     union { u32x2 r; __bf16 e[4]; } u;
@@ -168,8 +120,108 @@ __device__ __forceinline__ u32x2 pack4_bf16(f32x4 v) {
     for (int i = 0; i < 4; ++i) u.e[i] = (__bf16)v[i];
     return u.r;
 }
+__device__ __forceinline__ f32x4 widen4_bf16(u32x2 r) {
+    return f32x4{__builtin_bit_cast(float, r[0] << 16), __builtin_bit_cast(float, r[0] & 0xffff0000u), __builtin_bit_cast(float, r[1] << 16), __builtin_bit_cast(float, r[1] & 0xffff0000u)};
+}
+// four consecutive values rounded to bf16 at dst; split plan: the hi quad there and the lo quad (split_oct of mshgnn_device.hpp on four values) `lo_off` elements
+// further -- H in the rows of a stash, the plane stride in LDS
+template <int NP> __device__ __forceinline__ void mlp_store4(__bf16* dst, size_t lo_off, f32x4 v) {
+    const u32x2 hi = pack4_bf16(v);
+    *reinterpret_cast<u32x2*>(dst) = hi;
+    if constexpr (NP == 2) *reinterpret_cast<u32x2*>(dst + lo_off) = pack4_bf16(v - widen4_bf16(hi));
+}
+template <int NP> __device__ __forceinline__ void mlp_store2(__bf16* dst, size_t lo_off, float v0, float v1) {      // the same for a pair
+    union { unsigned u; __bf16 e[2]; } hi;
+    hi.e[0] = (__bf16)v0; hi.e[1] = (__bf16)v1;
+    *reinterpret_cast<unsigned*>(dst) = hi.u;
+    if constexpr (NP == 2) {
+        union { unsigned u; __bf16 e[2]; } lo;
+        lo.e[0] = (__bf16)(v0 - (float)hi.e[0]); lo.e[1] = (__bf16)(v1 - (float)hi.e[1]);
+        *reinterpret_cast<unsigned*>(dst + lo_off) = lo.u;
+    }
+}
 __device__ __forceinline__ f32x4 mfma_bf16(u32x4 a, u32x4 b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+}
+// c += w x over one K step (w: the weight, or dZ in the weight gradient); split plan: w_hi x_hi, then w_lo x_hi, then w_hi x_lo
+template <int NP> __device__ __forceinline__ f32x4 mlp_mma(const u32x4 (&w)[NP], const u32x4 (&x)[NP], f32x4 c) {
+    c = mfma_bf16(w[0], x[0], c);
+    if constexpr (NP == 2) { c = mfma_bf16(w[1], x[0], c); c = mfma_bf16(w[0], x[1], c); }
+    return c;
+}
+
+// ---- the batch's rows: dense rows (bf16; split plan: fp32, split in registers while they are staged), or windows of the resident bf16 series ----
+struct MlpIn {
+    const void* x; int64_t pitch;                                     // dense: bf16 rows, or fp32 rows on the split plan (pitch in elements of either)
+    const unsigned long long* run_ptr; const int64_t* starts; int T;  // series
+    int in; int64_t B;
+};
+template <bool X3> struct RowRef { const std::conditional_t<X3, float, __bf16>* p; int64_t s; };
+template <bool X3, bool SERIES> __device__ __forceinline__ RowRef<X3> mlp_row(const MlpIn& a, int64_t b) {      // b < B
+    static_assert(!(X3 && SERIES), "the split plan has no series form (the host refuses it): X3 && SERIES is never instantiated");
+    RowRef<X3> r; r.p = nullptr; r.s = 0;
+    if constexpr (SERIES) r.s = a.starts[b]; else r.p = static_cast<decltype(r.p)>(a.x) + b * a.pitch;
+    return r;
+}
+// elements [k0, k0 + 8) of a row as 8 bf16 per plane (k0 a multiple of 8); elements at or beyond `in` are zeros, whatever the pad columns hold
+template <bool X3, bool SERIES> __device__ __forceinline__ Octs<mlp_np<X3>> mlp_fetch8(const MlpIn& a, const RowRef<X3>& r, int k0) {
+    const int nvalid = a.in - k0;
+    if constexpr (X3) {
+        Octs<2> o;
+        f32x4 q0 = f32x4{0.f, 0.f, 0.f, 0.f}, q1 = q0;
+        if (nvalid > 0) {      // (the pitch covers `in` rounded up to 8: both loads stay inside the row)
+            q0 = load_quad(r.p + k0); q1 = load_quad(r.p + k0 + 4);
+            if (nvalid < 8) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) { if (i >= nvalid) q0[i] = 0.f; if (4 + i >= nvalid) q1[i] = 0.f; }
+            }
+        }
+        split_oct(q0, q1, o.v[0], o.v[1]);
+        return o;
+    } else {
+        u32x4 v = u32x4{0, 0, 0, 0};
+        if (nvalid <= 0) return Octs<1>{{v}};
+        if constexpr (!SERIES) {
+            v = *reinterpret_cast<const u32x4*>(r.p + k0);
+        } else {
+            const int T = a.T;
+            if (T >= 8) {
+                const u32x4 ones = u32x4{0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u};      // a constant-1 run (run pointer 0)
+                const int j = k0 / T, off = k0 - j * T, n0 = min(8, T - off);
+                const unsigned long long pa = a.run_ptr[j];
+                v = ones;
+                if (pa) v = *reinterpret_cast<const u32x4*>(reinterpret_cast<const __bf16*>(pa) + r.s + off);      // 2-byte aligned; may run into the column's slack
+                if (min(nvalid, 8) > n0) {      // the chunk's tail belongs to run j + 1 (then n0 < 8, and (j + 1) T = k0 + n0 < in: the run exists)
+                    const unsigned long long pb = a.run_ptr[j + 1];
+                    u32x4 vb = ones;
+                    if (pb) vb = *reinterpret_cast<const u32x4*>(reinterpret_cast<const __bf16*>(pb) + r.s);
+                    v = splice8(v, vb, n0);
+                }
+            } else {      // runs shorter than a chunk: element by element
+                unsigned e16[8];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    e16[e] = 0u;
+                    const int k = k0 + e;
+                    if (k < a.in) {
+                        const int j = k / T, off = k - j * T;
+                        const unsigned long long p = a.run_ptr[j];
+                        e16[e] = p ? (unsigned)reinterpret_cast<const unsigned short*>(p)[r.s + off] : 0x3f80u;
+                    }
+                }
+#pragma unroll
+                for (int q = 0; q < 4; ++q) v[q] = e16[2 * q] | (e16[2 * q + 1] << 16);
+            }
+        }
+        if (nvalid < 8) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const unsigned lo = 2 * q < nvalid ? 0xffffu : 0u, hi = 2 * q + 1 < nvalid ? 0xffff0000u : 0u;
+                v[q] &= lo | hi;
+            }
+        }
+        return Octs<1>{{v}};
+    }
 }
 
 // ---- run pointers of the series form (what k_series_run_ptrs of mshgnn.hip resolves, for unsigned tables and any number of runs) ----
@@ -188,7 +240,7 @@ __global__ void k_mlp_run_ptrs(const int* runs, int n_runs, MlpSrc s, unsigned l
 // ---- weight pack ----
 struct PackRegion { __bf16* dst; int64_t src; int rows, cols, srows, scols, transposed; };      // dst [rows][cols] <- W [srows][scols] at params + src (or its transpose), zero-padded
 struct PackArgs { PackRegion r[2 * MLP_MAXL]; int64_t prefix[2 * MLP_MAXL + 1]; int n; };
-__global__ __launch_bounds__(256) void k_mlp_pack(PackArgs a, const float* params) {
+template <bool X3> __global__ __launch_bounds__(256) void k_mlp_pack(PackArgs a, const float* params) {
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (idx >= a.prefix[a.n]) return;
     int i = 0;
@@ -199,14 +251,21 @@ __global__ __launch_bounds__(256) void k_mlp_pack(PackArgs a, const float* param
     const int sr = g.transposed ? col : row, sc = g.transposed ? row : col;
     float v = 0.f;
     if (sr < g.srows && sc < g.scols) v = params[g.src + (int64_t)sr * g.scols + sc];
-    g.dst[local] = (__bf16)v;
+    const __bf16 hi = (__bf16)v;
+    g.dst[local] = hi;
+    if constexpr (X3) g.dst[(int64_t)g.rows * g.cols + local] = (__bf16)(v - (float)hi);      // the lo image, behind the hi image [rows][cols]
 }
 
 // ---- input layer ----
 struct InArgs {
     MlpIn in; const __bf16* w1p; int K1p; const float* bias; __bf16* act1; int H; int lab_blocks; LabelArgs lab;
 };
-template <bool SERIES> __global__ __launch_bounds__(256) void k_mlp_in(InArgs a) {
+// K steps per trip of the input layer's K loop, their loads issued together.  bf16, four: a step's gather is two dependent round trips (run pointer, then the
+// series), and one step per trip left the launch waiting on 254 of them in a row at K = 8100.  Split plan, two: the fp32 rows and both weight images of four
+// steps would not fit the registers of two waves per SIMD.  (K1p is a multiple of 128: the pack's zero columns and mlp_fetch8's zeros fill the last trip)
+template <bool X3> constexpr int mlp_in_steps = X3 ? 2 : 4;
+template <bool X3, bool SERIES> __global__ __launch_bounds__(256) void k_mlp_in(InArgs a) {
+    constexpr int NP = mlp_np<X3>, NU = mlp_in_steps<X3>;
     const int tid = threadIdx.x;
     if constexpr (SERIES) {
         if ((int)blockIdx.x < a.lab_blocks) {
@@ -215,37 +274,45 @@ template <bool SERIES> __global__ __launch_bounds__(256) void k_mlp_in(InArgs a)
             return;
         }
     }
-    const int64_t bid = (int64_t)blockIdx.x - (SERIES ? a.lab_blocks : 0);
+    const unsigned bid = blockIdx.x - (SERIES ? a.lab_blocks : 0);
     const int nh = a.H / 128;
-    const int64_t tile = bid / nh; const int hc = (int)(bid - tile * nh);
+    const int64_t tile = bid / nh; const int hc = (int)(bid - (unsigned)tile * nh);
     const int wave = tid >> 6, lane = tid & 63, g = lane >> 4, c = lane & 15;
     const int n0 = hc * 128 + wave * 32;
     const int64_t b0 = tile * MLP_TILE;
-    RowRef rr[2];
+    RowRef<X3> rr[2];
 #pragma unroll
-    for (int rb = 0; rb < 2; ++rb) rr[rb] = mlp_row<SERIES>(a.in, min(b0 + rb * 16 + c, a.in.B - 1));
+    for (int rb = 0; rb < 2; ++rb) rr[rb] = mlp_row<X3, SERIES>(a.in, min(b0 + rb * 16 + c, a.in.B - 1));
     f32x4 acc[2][2];
 #pragma unroll
     for (int fb = 0; fb < 2; ++fb)
 #pragma unroll
         for (int rb = 0; rb < 2; ++rb) acc[fb][rb] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const __bf16* w0 = a.w1p + (size_t)(n0 + c) * a.K1p + 8 * g;
-    const __bf16* w1 = w0 + (size_t)16 * a.K1p;
-    // four K steps per trip, their loads issued together: a step's gather is two dependent round trips (run pointer, then the series), and one step per trip left
-    // the launch waiting on 254 of them in a row at K = 8100 (K1p is a multiple of 128: the pack's zero columns and mlp_fetch8's zeros fill the last trip)
-    for (int ks = 0; ks < a.K1p; ks += 128) {
-        u32x4 x0[4], x1[4], wa[4], wb[4];
+    const size_t wimg = (size_t)a.H * a.K1p;      // one image of W_1
+    const __bf16* wr[2];
+    wr[0] = a.w1p + (size_t)(n0 + c) * a.K1p + 8 * g; wr[1] = wr[0] + (size_t)16 * a.K1p;
+    for (int ks = 0; ks < a.K1p; ks += 32 * NU) {
+        Octs<NP> x[NU][2], w[NU][2];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
+        for (int u = 0; u < NU; ++u) {
             const int k0 = ks + 32 * u + 8 * g;
-            x0[u] = mlp_fetch8<SERIES>(a.in, rr[0], k0); x1[u] = mlp_fetch8<SERIES>(a.in, rr[1], k0);
-            wa[u] = *reinterpret_cast<const u32x4*>(w0 + ks + 32 * u); wb[u] = *reinterpret_cast<const u32x4*>(w1 + ks + 32 * u);
+            // The one statement spelled per plan, for the compiler alone: the two row blocks' fetches written out (bf16) or as a loop (split plan).  Either
+            // spelling costs the other plan about twenty instructions per trip in this latency-bound loop, 1 - 2 % of the launch ("One template").
+            if constexpr (X3) {
+#pragma unroll
+                for (int rb = 0; rb < 2; ++rb) x[u][rb] = mlp_fetch8<X3, SERIES>(a.in, rr[rb], k0);
+            } else { x[u][0] = mlp_fetch8<X3, SERIES>(a.in, rr[0], k0); x[u][1] = mlp_fetch8<X3, SERIES>(a.in, rr[1], k0); }
+#pragma unroll
+            for (int fb = 0; fb < 2; ++fb)
+#pragma unroll
+                for (int h = 0; h < NP; ++h) w[u][fb].v[h] = *reinterpret_cast<const u32x4*>(wr[fb] + h * wimg + ks + 32 * u);
         }
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            acc[0][0] = mfma_bf16(wa[u], x0[u], acc[0][0]); acc[0][1] = mfma_bf16(wa[u], x1[u], acc[0][1]);
-            acc[1][0] = mfma_bf16(wb[u], x0[u], acc[1][0]); acc[1][1] = mfma_bf16(wb[u], x1[u], acc[1][1]);
-        }
+        for (int u = 0; u < NU; ++u)
+#pragma unroll
+            for (int fb = 0; fb < 2; ++fb)
+#pragma unroll
+                for (int rb = 0; rb < 2; ++rb) acc[fb][rb] = mlp_mma<NP>(w[u][fb].v, x[u][rb].v, acc[fb][rb]);
     }
 #pragma unroll
     for (int fb = 0; fb < 2; ++fb) {
@@ -257,7 +324,7 @@ template <bool SERIES> __global__ __launch_bounds__(256) void k_mlp_in(InArgs a)
             f32x4 v;
 #pragma unroll
             for (int i = 0; i < 4; ++i) v[i] = b < a.in.B ? fmaxf(acc[fb][rb][i] + bv[i], 0.f) : 0.f;
-            *reinterpret_cast<u32x2*>(a.act1 + (size_t)b * a.H + f) = pack4_bf16(v);
+            mlp_store4<NP>(a.act1 + (size_t)b * (NP * a.H) + f, a.H, v);
         }
     }
 }
@@ -269,30 +336,39 @@ struct StackArgs {
     const __bf16* wp[MLP_MAXL + 1]; const __bf16* wtp[MLP_MAXL + 1]; __bf16* act[MLP_MAXL + 1]; __bf16* dz[MLP_MAXL + 1];
     float* out_p; const float* y; const int32_t* labels; const float* gout; float* loss_part;
 };
-// D[n][row] = sum_k W[n][k] X[row][k] over the tile's 32 rows: W global bf16 [N][Kw] (N a multiple of 16, Kw of 32), X in LDS at stride xs.
+// D[n][row] = sum_k W[n][k] X[row][k] over the tile's 32 rows: W global bf16 [N][Kw] (N a multiple of 16, Kw of 32), X in LDS at stride xs; split plan: the lo
+// image of W behind its hi image, the lo plane of X `plane` elements behind its hi plane.
 // epi(first of 4 consecutive features, row in the tile, the 4 sums); the (feature, row) -> thread map depends on N alone.
-template <typename Epi> __device__ __forceinline__ void mlp_layer(const __bf16* W, int N, int Kw, const __bf16* X, int xs, int wave, int lane, Epi epi) {
+template <int NP, typename Epi> __device__ __forceinline__ void mlp_layer(const __bf16* W, int N, int Kw, const __bf16* X, int xs, int plane, int wave, int lane, Epi epi) {
     const int g = lane >> 4, c = lane & 15;
+    const size_t wimg = (size_t)N * Kw;
     for (int fb = wave; fb < N / 16; fb += 4) {
         f32x4 a0 = f32x4{0.f, 0.f, 0.f, 0.f}, a1 = a0;
         const __bf16* wr = W + (size_t)(fb * 16 + c) * Kw + 8 * g;
         const __bf16* x0 = X + c * xs + 8 * g;
         const __bf16* x1 = x0 + 16 * xs;
         for (int k = 0; k < Kw; k += 32) {
-            const u32x4 wf = *reinterpret_cast<const u32x4*>(wr + k);
-            const u32x4 f0 = *reinterpret_cast<const u32x4*>(x0 + k), f1 = *reinterpret_cast<const u32x4*>(x1 + k);
-            a0 = mfma_bf16(wf, f0, a0); a1 = mfma_bf16(wf, f1, a1);
+            u32x4 wf[NP], f0[NP], f1[NP];
+#pragma unroll
+            for (int h = 0; h < NP; ++h) {
+                wf[h] = *reinterpret_cast<const u32x4*>(wr + h * wimg + k);
+                f0[h] = *reinterpret_cast<const u32x4*>(x0 + h * plane + k); f1[h] = *reinterpret_cast<const u32x4*>(x1 + h * plane + k);
+            }
+            a0 = mlp_mma<NP>(wf, f0, a0); a1 = mlp_mma<NP>(wf, f1, a1);
         }
         epi(fb * 16 + 4 * g, c, a0); epi(fb * 16 + 4 * g, 16 + c, a1);
     }
 }
 
-__global__ __launch_bounds__(256) void k_mlp_stack(StackArgs a) {
+// LDS: two activation buffers of NP planes [32][H + 8] each (a row shifts the 16-byte reads of a lane group by four banks; the planes are read by separate
+// instructions, so the plane stride adds no conflict), then the output and reduction buffers.  Rows of the stashes and of dZ: NP halves, [hi | lo].
+template <bool X3> __global__ __launch_bounds__(256) void k_mlp_stack(StackArgs a) {
+    constexpr int NP = mlp_np<X3>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int H = a.H, xs = H + 8, L = a.L;
+    const int H = a.H, xs = H + 8, L = a.L, plane = MLP_TILE * xs;
     __bf16* buf0 = reinterpret_cast<__bf16*>(smem);
-    __bf16* buf1 = buf0 + MLP_TILE * xs;
-    float* obuf = reinterpret_cast<float*>(buf1 + MLP_TILE * xs);
+    __bf16* buf1 = buf0 + NP * plane;
+    float* obuf = reinterpret_cast<float*>(buf1 + NP * plane);
     float* red = obuf + MLP_TILE * MLP_OPAD;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int64_t b0 = (int64_t)blockIdx.x * MLP_TILE;
@@ -303,27 +379,28 @@ __global__ __launch_bounds__(256) void k_mlp_stack(StackArgs a) {
         const int cpr = H / 8;
         for (int i = tid; i < MLP_TILE * cpr; i += 256) {
             const int row = i / cpr, ch = i - row * cpr;
-            *reinterpret_cast<u32x4*>(cur + row * xs + ch * 8) = *reinterpret_cast<const u32x4*>(a.act[1] + (size_t)(b0 + row) * H + ch * 8);
+#pragma unroll
+            for (int h = 0; h < NP; ++h)
+                *reinterpret_cast<u32x4*>(cur + h * plane + row * xs + ch * 8) = *reinterpret_cast<const u32x4*>(a.act[1] + (size_t)(b0 + row) * (NP * H) + h * H + ch * 8);
         }
         __syncthreads();
         for (int l = 2; l < L; ++l) {
             const float* bias = a.params + a.off_b[l];
             __bf16* st = a.act[l];
-            mlp_layer(a.wp[l], H, H, cur, xs, wave, lane, [&](int f, int row, f32x4 s) {
+            mlp_layer<NP>(a.wp[l], H, H, cur, xs, plane, wave, lane, [&](int f, int row, f32x4 s) {
                 const bool live = b0 + row < a.B;
                 f32x4 v;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) v[i] = live ? fmaxf(s[i] + bias[f + i], 0.f) : 0.f;
-                const u32x2 pk = pack4_bf16(v);
-                *reinterpret_cast<u32x2*>(nxt + row * xs + f) = pk;
-                if (stash) *reinterpret_cast<u32x2*>(st + (size_t)(b0 + row) * H + f) = pk;
+                mlp_store4<NP>(nxt + row * xs + f, plane, v);
+                if (stash) mlp_store4<NP>(st + (size_t)(b0 + row) * (NP * H) + f, H, v);
             });
             __syncthreads();
             __bf16* t = cur; cur = nxt; nxt = t;
         }
         {
             const float* bias = a.params + a.off_b[L];
-            mlp_layer(a.wp[L], MLP_OPAD, H, cur, xs, wave, lane, [&](int f, int row, f32x4 s) {
+            mlp_layer<NP>(a.wp[L], MLP_OPAD, H, cur, xs, plane, wave, lane, [&](int f, int row, f32x4 s) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const float v = f + i < a.out ? s[i] + bias[f + i] : 0.f;
@@ -357,327 +434,9 @@ __global__ __launch_bounds__(256) void k_mlp_stack(StackArgs a) {
                 if (f0 + 1 < a.out) g1 = a.gout[(size_t)b * a.out + f0 + 1];
             }
         }
-        union { unsigned u; __bf16 e[2]; } pk;
-        pk.e[0] = (__bf16)g0; pk.e[1] = (__bf16)g1;
-        *reinterpret_cast<unsigned*>(nxt + row * xs + f0) = pk.u;
-        *reinterpret_cast<unsigned*>(nxt + row * xs + MLP_OPAD + f0) = 0u;      // K columns 16 .. 31 of the first backward product
-        *reinterpret_cast<unsigned*>(a.dz[L] + (size_t)b * MLP_OPAD + f0) = pk.u;
-        if (a.mode == MODE_STEP) {
-            red[tid] = term;
-            __syncthreads();
-            for (int s = 128; s > 0; s >>= 1) {
-                if (tid < s) red[tid] += red[tid + s];
-                __syncthreads();
-            }
-            if (tid == 0) a.loss_part[blockIdx.x] = red[0];
-        }
-    }
-    __syncthreads();
-    { __bf16* t = cur; cur = nxt; nxt = t; }
-    // backward sweep: dZ_{l-1} = (dZ_l W_l) . [A_{l-1} > 0]
-    int Kw = MLP_GK;
-    for (int l = L; l >= 2; --l) {
-        const __bf16* am = a.act[l - 1];
-        __bf16* dzo = a.dz[l - 1];
-        mlp_layer(a.wtp[l], H, Kw, cur, xs, wave, lane, [&](int f, int row, f32x4 s) {
-            const f32x4 av = load_quad(am + (size_t)(b0 + row) * H + f);
-            f32x4 v;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) v[i] = av[i] > 0.f ? s[i] : 0.f;
-            const u32x2 pk = pack4_bf16(v);
-            *reinterpret_cast<u32x2*>(nxt + row * xs + f) = pk;
-            *reinterpret_cast<u32x2*>(dzo + (size_t)(b0 + row) * H + f) = pk;
-        });
-        __syncthreads();
-        __bf16* t = cur; cur = nxt; nxt = t;
-        Kw = H;
-    }
-}
-
-// ---- weight gradients ----
-struct WgArgs {
-    int L, H, in, out, nslab; int64_t B, slab_rows, n_flat;
-    int prefix[MLP_MAXL + 2];      // workgroups (dW tiles) of layer l = 1 .. L start at prefix[l]; prefix[L + 1] = all
-    int itiles[MLP_MAXL + 1];
-    const __bf16* dz[MLP_MAXL + 1]; const __bf16* act[MLP_MAXL + 1];
-    int64_t off_w[MLP_MAXL + 1], off_b[MLP_MAXL + 1];
-    float* slabs; MlpIn xin;
-};
-template <bool SERIES> __global__ __launch_bounds__(256) void k_mlp_wgrad(WgArgs a) {
-    __shared__ __attribute__((aligned(16))) __bf16 sdz[MLP_TILE * WG_LD];
-    __shared__ __attribute__((aligned(16))) __bf16 sx[MLP_TILE * WG_LD];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, g = lane >> 4, c = lane & 15;
-    const int per_slab = a.prefix[a.L + 1];
-    const int slab = (int)(blockIdx.x / per_slab), r = (int)(blockIdx.x - (unsigned)slab * per_slab);
-    int l = 1;
-    while (l < a.L && r >= a.prefix[l + 1]) ++l;
-    const int local = r - a.prefix[l];
-    const int jt = local / a.itiles[l], it = local - jt * a.itiles[l];
-    const int Jd = l == a.L ? a.out : a.H, zs = l == a.L ? MLP_OPAD : a.H, Id = l == 1 ? a.in : a.H;
-    const __bf16* dz = a.dz[l];
-    const __bf16* ap = a.act[l - 1];      // (l == 1: null, the rows come from xin)
-    const int64_t r0 = (int64_t)slab * a.slab_rows, r1 = min(r0 + a.slab_rows, a.B);
-    const int srow = tid >> 3, ch = tid & 7;
-    const int jcol = jt * WG_T + ch * 8, icol = it * WG_T + ch * 8;
-    f32x4 acc[4];
-#pragma unroll
-    for (int ib = 0; ib < 4; ++ib) acc[ib] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float bsum = 0.f;
-    for (int64_t rb = r0; rb < r1; rb += MLP_TILE) {
-        const int64_t b = rb + srow;
-        u32x4 vz = u32x4{0, 0, 0, 0}, vx = u32x4{0, 0, 0, 0};
-        if (b < r1) {
-            if (jcol < zs) vz = *reinterpret_cast<const u32x4*>(dz + (size_t)b * zs + jcol);
-            if (l == 1) vx = mlp_fetch8<SERIES>(a.xin, mlp_row<SERIES>(a.xin, b), icol);
-            else if (icol < a.H) vx = *reinterpret_cast<const u32x4*>(ap + (size_t)b * a.H + icol);
-        }
-        __syncthreads();      // the previous step's reads are done
-        *reinterpret_cast<u32x2*>(sdz + srow * WG_LD + ch * 8) = u32x2{vz[0], vz[1]};
-        *reinterpret_cast<u32x2*>(sdz + srow * WG_LD + ch * 8 + 4) = u32x2{vz[2], vz[3]};
-        *reinterpret_cast<u32x2*>(sx + srow * WG_LD + ch * 8) = u32x2{vx[0], vx[1]};
-        *reinterpret_cast<u32x2*>(sx + srow * WG_LD + ch * 8 + 4) = u32x2{vx[2], vx[3]};
-        __syncthreads();
-        // operands of the row-reduction: element e of lane group g is row 8 g + e of the step
-        const unsigned short* zz = reinterpret_cast<const unsigned short*>(sdz) + (8 * g) * WG_LD + wave * 16 + c;
-        u32x4 zf;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) zf[q] = (unsigned)zz[(2 * q) * WG_LD] | ((unsigned)zz[(2 * q + 1) * WG_LD] << 16);
-#pragma unroll
-        for (int ib = 0; ib < 4; ++ib) {
-            const unsigned short* xx = reinterpret_cast<const unsigned short*>(sx) + (8 * g) * WG_LD + ib * 16 + c;
-            u32x4 xf;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) xf[q] = (unsigned)xx[(2 * q) * WG_LD] | ((unsigned)xx[(2 * q + 1) * WG_LD] << 16);
-            acc[ib] = mfma_bf16(zf, xf, acc[ib]);
-        }
-        if (it == 0 && tid < WG_T) {
-#pragma unroll 8
-            for (int rw = 0; rw < MLP_TILE; ++rw) bsum += (float)sdz[rw * WG_LD + tid];
-        }
-    }
-    float* sl = a.slabs + (size_t)slab * a.n_flat;
-#pragma unroll
-    for (int ib = 0; ib < 4; ++ib) {
-        const int i = it * WG_T + ib * 16 + c;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int j = jt * WG_T + wave * 16 + 4 * g + q;
-            if (j < Jd && i < Id) sl[a.off_w[l] + (int64_t)j * Id + i] = acc[ib][q];
-        }
-    }
-    if (it == 0 && tid < WG_T && jt * WG_T + tid < Jd) sl[a.off_b[l] + jt * WG_T + tid] = bsum;
-}
-
-// ---- the split plan: the four launches above on hi / lo pairs (k_mlp_reduce is shared) ----
-__device__ __forceinline__ f32x4 widen4_bf16(u32x2 r) {
-    return f32x4{__builtin_bit_cast(float, r[0] << 16), __builtin_bit_cast(float, r[0] & 0xffff0000u), __builtin_bit_cast(float, r[1] << 16), __builtin_bit_cast(float, r[1] & 0xffff0000u)};
-}
-__device__ __forceinline__ void split_quad(f32x4 v, u32x2& hi, u32x2& lo) {      // split_oct (mshgnn_device.hpp) on four values
-    hi = pack4_bf16(v);
-    lo = pack4_bf16(v - widen4_bf16(hi));
-}
-// elements [k0, k0 + 8) of a dense fp32 row as a hi and a lo oct (k0 a multiple of 8); elements at or beyond `in` are zeros, whatever the pad columns hold
-__device__ __forceinline__ void mlp_fetch8_x3(const float* row, int in, int k0, u32x4& hi, u32x4& lo) {
-    f32x4 a = f32x4{0.f, 0.f, 0.f, 0.f}, b = a;
-    const int nvalid = in - k0;
-    if (nvalid > 0) {      // (the pitch covers `in` rounded up to 8: both loads stay inside the row)
-        a = load_quad(row + k0); b = load_quad(row + k0 + 4);
-        if (nvalid < 8) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) { if (i >= nvalid) a[i] = 0.f; if (4 + i >= nvalid) b[i] = 0.f; }
-        }
-    }
-    split_oct(a, b, hi, lo);
-}
-
-__global__ __launch_bounds__(256) void k_mlp_pack_x3(PackArgs a, const float* params) {      // k_mlp_pack; region i: the hi image [rows][cols], the lo image behind it
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= a.prefix[a.n]) return;
-    int i = 0;
-    while (i + 1 < a.n && idx >= a.prefix[i + 1]) ++i;
-    const PackRegion& g = a.r[i];
-    const int64_t local = idx - a.prefix[i];
-    const int row = (int)(local / g.cols), col = (int)(local - (int64_t)row * g.cols);
-    const int sr = g.transposed ? col : row, sc = g.transposed ? row : col;
-    float v = 0.f;
-    if (sr < g.srows && sc < g.scols) v = params[g.src + (int64_t)sr * g.scols + sc];
-    const __bf16 hi = (__bf16)v;
-    g.dst[local] = hi;
-    g.dst[(int64_t)g.rows * g.cols + local] = (__bf16)(v - (float)hi);
-}
-
-// k_mlp_in's tile and thread map; two K steps per trip (the fp32 rows and both weight images of four steps would not fit the registers of two waves per SIMD)
-__global__ __launch_bounds__(256) void k_mlp_in_x3(InArgs a) {
-    const int tid = threadIdx.x;
-    const int nh = a.H / 128;
-    const int64_t tile = blockIdx.x / nh; const int hc = (int)(blockIdx.x - tile * nh);
-    const int wave = tid >> 6, lane = tid & 63, g = lane >> 4, c = lane & 15;
-    const int n0 = hc * 128 + wave * 32;
-    const int64_t b0 = tile * MLP_TILE;
-    const float* xr[2];
-#pragma unroll
-    for (int rb = 0; rb < 2; ++rb) xr[rb] = reinterpret_cast<const float*>(a.in.x) + min(b0 + rb * 16 + c, a.in.B - 1) * a.in.pitch;
-    f32x4 acc[2][2];
-#pragma unroll
-    for (int fb = 0; fb < 2; ++fb)
-#pragma unroll
-        for (int rb = 0; rb < 2; ++rb) acc[fb][rb] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const size_t wlo = (size_t)a.H * a.K1p;      // the lo image
-    const __bf16* wr[2];
-    wr[0] = a.w1p + (size_t)(n0 + c) * a.K1p + 8 * g; wr[1] = wr[0] + (size_t)16 * a.K1p;
-    for (int ks = 0; ks < a.K1p; ks += 64) {
-        u32x4 xh[2][2], xl[2][2], wh[2][2], wl[2][2];
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int k0 = ks + 32 * u + 8 * g;
-#pragma unroll
-            for (int rb = 0; rb < 2; ++rb) mlp_fetch8_x3(xr[rb], a.in.in, k0, xh[u][rb], xl[u][rb]);
-#pragma unroll
-            for (int fb = 0; fb < 2; ++fb) {
-                wh[u][fb] = *reinterpret_cast<const u32x4*>(wr[fb] + ks + 32 * u); wl[u][fb] = *reinterpret_cast<const u32x4*>(wr[fb] + wlo + ks + 32 * u);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-#pragma unroll
-            for (int fb = 0; fb < 2; ++fb)
-#pragma unroll
-                for (int rb = 0; rb < 2; ++rb) acc[fb][rb] = mfma_bf16(wh[u][fb], xh[u][rb], acc[fb][rb]);
-#pragma unroll
-            for (int fb = 0; fb < 2; ++fb)
-#pragma unroll
-                for (int rb = 0; rb < 2; ++rb) acc[fb][rb] = mfma_bf16(wl[u][fb], xh[u][rb], acc[fb][rb]);
-#pragma unroll
-            for (int fb = 0; fb < 2; ++fb)
-#pragma unroll
-                for (int rb = 0; rb < 2; ++rb) acc[fb][rb] = mfma_bf16(wh[u][fb], xl[u][rb], acc[fb][rb]);
-        }
-    }
-#pragma unroll
-    for (int fb = 0; fb < 2; ++fb) {
-        const int f = n0 + fb * 16 + 4 * g;
-        const f32x4 bv = f32x4{a.bias[f], a.bias[f + 1], a.bias[f + 2], a.bias[f + 3]};
-#pragma unroll
-        for (int rb = 0; rb < 2; ++rb) {
-            const int64_t b = b0 + rb * 16 + c;
-            f32x4 v;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) v[i] = b < a.in.B ? fmaxf(acc[fb][rb][i] + bv[i], 0.f) : 0.f;
-            u32x2 hi, lo;
-            split_quad(v, hi, lo);
-            __bf16* dst = a.act1 + (size_t)b * (2 * a.H) + f;
-            *reinterpret_cast<u32x2*>(dst) = hi; *reinterpret_cast<u32x2*>(dst + a.H) = lo;
-        }
-    }
-}
-
-// mlp_layer on pairs: W = the hi image [N][Kw] with the lo image behind it, X = the hi plane in LDS with the lo plane `plane` elements further; per K step
-// W_hi X_hi + W_lo X_hi + W_hi X_lo, the two row blocks alternating
-template <typename Epi> __device__ __forceinline__ void mlp_layer_x3(const __bf16* W, int N, int Kw, const __bf16* X, int xs, int plane, int wave, int lane, Epi epi) {
-    const int g = lane >> 4, c = lane & 15;
-    const size_t wlo = (size_t)N * Kw;
-    for (int fb = wave; fb < N / 16; fb += 4) {
-        f32x4 a0 = f32x4{0.f, 0.f, 0.f, 0.f}, a1 = a0;
-        const __bf16* wr = W + (size_t)(fb * 16 + c) * Kw + 8 * g;
-        const __bf16* x0 = X + c * xs + 8 * g;
-        const __bf16* x1 = x0 + 16 * xs;
-        for (int k = 0; k < Kw; k += 32) {
-            const u32x4 wh = *reinterpret_cast<const u32x4*>(wr + k), wl = *reinterpret_cast<const u32x4*>(wr + wlo + k);
-            const u32x4 h0 = *reinterpret_cast<const u32x4*>(x0 + k), h1 = *reinterpret_cast<const u32x4*>(x1 + k);
-            const u32x4 l0 = *reinterpret_cast<const u32x4*>(x0 + plane + k), l1 = *reinterpret_cast<const u32x4*>(x1 + plane + k);
-            a0 = mfma_bf16(wh, h0, a0); a1 = mfma_bf16(wh, h1, a1);
-            a0 = mfma_bf16(wl, h0, a0); a1 = mfma_bf16(wl, h1, a1);
-            a0 = mfma_bf16(wh, l0, a0); a1 = mfma_bf16(wh, l1, a1);
-        }
-        epi(fb * 16 + 4 * g, c, a0); epi(fb * 16 + 4 * g, 16 + c, a1);
-    }
-}
-
-// k_mlp_stack on pairs.  LDS: two activation buffers, each a hi plane [32][H + 8] and a lo plane behind it (a row shifts the 16-byte reads of a lane group by
-// four banks, as in k_mlp_stack; the planes are read by separate instructions, so the plane stride adds no conflict), then the output and reduction buffers.
-__global__ __launch_bounds__(256) void k_mlp_stack_x3(StackArgs a) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int H = a.H, xs = H + 8, L = a.L, plane = MLP_TILE * xs, H2 = 2 * H;
-    __bf16* buf0 = reinterpret_cast<__bf16*>(smem);
-    __bf16* buf1 = buf0 + 2 * plane;
-    float* obuf = reinterpret_cast<float*>(buf1 + 2 * plane);
-    float* red = obuf + MLP_TILE * MLP_OPAD;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int64_t b0 = (int64_t)blockIdx.x * MLP_TILE;
-    __bf16* cur = buf0; __bf16* nxt = buf1;
-    const bool stash = a.mode != MODE_INFER;
-    if (a.mode != MODE_BWD) {
-        // A_1 of the tile, both halves (rows past the batch: the zeros k_mlp_in_x3 wrote)
-        const int cpr = H2 / 8;
-        for (int i = tid; i < MLP_TILE * cpr; i += 256) {
-            const int row = i / cpr, ch = i - row * cpr;
-            const int col = ch * 8 < H ? ch * 8 : plane + ch * 8 - H;
-            *reinterpret_cast<u32x4*>(cur + row * xs + col) = *reinterpret_cast<const u32x4*>(a.act[1] + (size_t)(b0 + row) * H2 + ch * 8);
-        }
-        __syncthreads();
-        for (int l = 2; l < L; ++l) {
-            const float* bias = a.params + a.off_b[l];
-            __bf16* st = a.act[l];
-            mlp_layer_x3(a.wp[l], H, H, cur, xs, plane, wave, lane, [&](int f, int row, f32x4 s) {
-                const bool live = b0 + row < a.B;
-                f32x4 v;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) v[i] = live ? fmaxf(s[i] + bias[f + i], 0.f) : 0.f;
-                u32x2 hi, lo;
-                split_quad(v, hi, lo);
-                *reinterpret_cast<u32x2*>(nxt + row * xs + f) = hi; *reinterpret_cast<u32x2*>(nxt + plane + row * xs + f) = lo;
-                if (stash) {
-                    __bf16* dst = st + (size_t)(b0 + row) * H2 + f;
-                    *reinterpret_cast<u32x2*>(dst) = hi; *reinterpret_cast<u32x2*>(dst + H) = lo;
-                }
-            });
-            __syncthreads();
-            __bf16* t = cur; cur = nxt; nxt = t;
-        }
-        {
-            const float* bias = a.params + a.off_b[L];
-            mlp_layer_x3(a.wp[L], MLP_OPAD, H, cur, xs, plane, wave, lane, [&](int f, int row, f32x4 s) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const float v = f + i < a.out ? s[i] + bias[f + i] : 0.f;
-                    obuf[row * MLP_OPAD + f + i] = v;
-                    if (f + i < a.out && b0 + row < a.B) a.out_p[(size_t)(b0 + row) * a.out + f + i] = v;
-                }
-            });
-        }
-        __syncthreads();
-        if (a.mode != MODE_STEP) return;
-    }
-    // dZ_L: the loss tail (step) or the caller's gout (backward), k_mlp_stack's arithmetic; thread = (row, logit pair)
-    {
-        const int row = tid >> 3, p = tid & 7, f0 = 2 * p;
-        const int64_t b = b0 + row;
-        float g0 = 0.f, g1 = 0.f, term = 0.f;
-        if (b < a.B) {
-            if (a.mode == MODE_STEP) {
-                const float o0 = obuf[row * MLP_OPAD + f0], o1 = obuf[row * MLP_OPAD + f0 + 1];
-                if (a.loss_kind == 0) {
-                    if (f0 < a.out) { const float d = o0 - a.y[(size_t)b * a.out + f0]; g0 = 2.0f * d * a.inv; term = d * d; }
-                    if (f0 + 1 < a.out) { const float d = o1 - a.y[(size_t)b * a.out + f0 + 1]; g1 = 2.0f * d * a.inv; term += d * d; }
-                } else if (f0 + 1 < a.out) {
-                    const int cls = a.labels[(size_t)b * (a.out / 2) + p] != 0;
-                    const float m = fmaxf(o0, o1), e0 = expf(o0 - m), e1 = expf(o1 - m), s = e0 + e1;
-                    term = logf(s) + m - (cls ? o1 : o0);
-                    g0 = (e0 / s - (cls ? 0.f : 1.f)) * a.inv; g1 = (e1 / s - (cls ? 1.f : 0.f)) * a.inv;
-                }
-            } else {
-                if (f0 < a.out) g0 = a.gout[(size_t)b * a.out + f0];
-                if (f0 + 1 < a.out) g1 = a.gout[(size_t)b * a.out + f0 + 1];
-            }
-        }
-        union { unsigned u; __bf16 e[2]; } ph, pl;
-        ph.e[0] = (__bf16)g0; ph.e[1] = (__bf16)g1;
-        pl.e[0] = (__bf16)(g0 - (float)ph.e[0]); pl.e[1] = (__bf16)(g1 - (float)ph.e[1]);
-        *reinterpret_cast<unsigned*>(nxt + row * xs + f0) = ph.u; *reinterpret_cast<unsigned*>(nxt + plane + row * xs + f0) = pl.u;
-        *reinterpret_cast<unsigned*>(nxt + row * xs + MLP_OPAD + f0) = 0u;      // K columns 16 .. 31 of the first backward product
-        *reinterpret_cast<unsigned*>(nxt + plane + row * xs + MLP_OPAD + f0) = 0u;
-        *reinterpret_cast<unsigned*>(a.dz[L] + (size_t)b * (2 * MLP_OPAD) + f0) = ph.u;
-        *reinterpret_cast<unsigned*>(a.dz[L] + (size_t)b * (2 * MLP_OPAD) + MLP_OPAD + f0) = pl.u;
+        mlp_store2<NP>(nxt + row * xs + f0, plane, g0, g1);
+        mlp_store2<NP>(nxt + row * xs + MLP_OPAD + f0, plane, 0.f, 0.f);      // K columns 16 .. 31 of the first backward product
+        mlp_store2<NP>(a.dz[L] + (size_t)b * (NP * MLP_OPAD) + f0, MLP_OPAD, g0, g1);
         if (a.mode == MODE_STEP) {
             red[tid] = term;
             __syncthreads();
@@ -695,16 +454,13 @@ __global__ __launch_bounds__(256) void k_mlp_stack_x3(StackArgs a) {
     for (int l = L; l >= 2; --l) {
         const __bf16* am = a.act[l - 1];
         __bf16* dzo = a.dz[l - 1];
-        mlp_layer_x3(a.wtp[l], H, Kw, cur, xs, plane, wave, lane, [&](int f, int row, f32x4 s) {
-            const f32x4 av = load_quad(am + (size_t)(b0 + row) * H2 + f);
+        mlp_layer<NP>(a.wtp[l], H, Kw, cur, xs, plane, wave, lane, [&](int f, int row, f32x4 s) {
+            const f32x4 av = load_quad(am + (size_t)(b0 + row) * (NP * H) + f);
             f32x4 v;
 #pragma unroll
             for (int i = 0; i < 4; ++i) v[i] = av[i] > 0.f ? s[i] : 0.f;
-            u32x2 hi, lo;
-            split_quad(v, hi, lo);
-            *reinterpret_cast<u32x2*>(nxt + row * xs + f) = hi; *reinterpret_cast<u32x2*>(nxt + plane + row * xs + f) = lo;
-            __bf16* dst = dzo + (size_t)(b0 + row) * H2 + f;
-            *reinterpret_cast<u32x2*>(dst) = hi; *reinterpret_cast<u32x2*>(dst + H) = lo;
+            mlp_store4<NP>(nxt + row * xs + f, plane, v);
+            mlp_store4<NP>(dzo + (size_t)(b0 + row) * (NP * H) + f, H, v);
         });
         __syncthreads();
         __bf16* t = cur; cur = nxt; nxt = t;
@@ -712,11 +468,21 @@ __global__ __launch_bounds__(256) void k_mlp_stack_x3(StackArgs a) {
     }
 }
 
-// k_mlp_wgrad on pairs: the hi and lo planes of both operands in LDS (4 x 4352 B), dZ_hi A_hi + dZ_lo A_hi + dZ_hi A_lo per block; db = the column sums of hi + lo
-// (exact in fp32) in row order; layer 1's A operand is the fp32 rows, split as k_mlp_in_x3 split them
-__global__ __launch_bounds__(256) void k_mlp_wgrad_x3(WgArgs a) {
-    __shared__ __attribute__((aligned(16))) __bf16 sdz[2][MLP_TILE * WG_LD];      // [hi, lo]
-    __shared__ __attribute__((aligned(16))) __bf16 sx[2][MLP_TILE * WG_LD];
+// ---- weight gradients ----
+struct WgArgs {
+    int L, H, in, out, nslab; int64_t B, slab_rows, n_flat;
+    int prefix[MLP_MAXL + 2];      // workgroups (dW tiles) of layer l = 1 .. L start at prefix[l]; prefix[L + 1] = all
+    int itiles[MLP_MAXL + 1];
+    const __bf16* dz[MLP_MAXL + 1]; const __bf16* act[MLP_MAXL + 1];
+    int64_t off_w[MLP_MAXL + 1], off_b[MLP_MAXL + 1];
+    float* slabs; MlpIn xin;
+};
+// LDS: NP planes of 4352 B per operand; per block of the tile dZ A over the step's rows (mlp_mma); db = the column sums of dZ (split plan: of hi + lo, exact in
+// fp32) in row order; layer 1's A operand is the batch's rows, fetched as k_mlp_in fetched them
+template <bool X3, bool SERIES> __global__ __launch_bounds__(256) void k_mlp_wgrad(WgArgs a) {
+    constexpr int NP = mlp_np<X3>;
+    __shared__ __attribute__((aligned(16))) __bf16 sdz[NP][MLP_TILE * WG_LD];
+    __shared__ __attribute__((aligned(16))) __bf16 sx[NP][MLP_TILE * WG_LD];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, g = lane >> 4, c = lane & 15;
     const int per_slab = a.prefix[a.L + 1];
     const int slab = (int)(blockIdx.x / per_slab), r = (int)(blockIdx.x - (unsigned)slab * per_slab);
@@ -727,7 +493,6 @@ __global__ __launch_bounds__(256) void k_mlp_wgrad_x3(WgArgs a) {
     const int Jd = l == a.L ? a.out : a.H, zs = l == a.L ? MLP_OPAD : a.H, Id = l == 1 ? a.in : a.H;
     const __bf16* dz = a.dz[l];
     const __bf16* ap = a.act[l - 1];      // (l == 1: null, the rows come from xin)
-    const float* xf = reinterpret_cast<const float*>(a.xin.x);
     const int64_t r0 = (int64_t)slab * a.slab_rows, r1 = min(r0 + a.slab_rows, a.B);
     const int srow = tid >> 3, ch = tid & 7;
     const int jcol = jt * WG_T + ch * 8, icol = it * WG_T + ch * 8;
@@ -737,46 +502,56 @@ __global__ __launch_bounds__(256) void k_mlp_wgrad_x3(WgArgs a) {
     float bsum = 0.f;
     for (int64_t rb = r0; rb < r1; rb += MLP_TILE) {
         const int64_t b = rb + srow;
-        u32x4 vz[2], vx[2];
-        vz[0] = vz[1] = vx[0] = vx[1] = u32x4{0, 0, 0, 0};
+        Octs<NP> vz, vx;
+#pragma unroll
+        for (int h = 0; h < NP; ++h) vz.v[h] = vx.v[h] = u32x4{0, 0, 0, 0};
         if (b < r1) {
-            if (jcol < zs) { vz[0] = *reinterpret_cast<const u32x4*>(dz + (size_t)b * (2 * zs) + jcol); vz[1] = *reinterpret_cast<const u32x4*>(dz + (size_t)b * (2 * zs) + zs + jcol); }
-            if (l == 1) mlp_fetch8_x3(xf + b * a.xin.pitch, a.in, icol, vx[0], vx[1]);
-            else if (icol < a.H) { vx[0] = *reinterpret_cast<const u32x4*>(ap + (size_t)b * (2 * a.H) + icol); vx[1] = *reinterpret_cast<const u32x4*>(ap + (size_t)b * (2 * a.H) + a.H + icol); }
+            if (jcol < zs) {
+#pragma unroll
+                for (int h = 0; h < NP; ++h) vz.v[h] = *reinterpret_cast<const u32x4*>(dz + (size_t)b * (NP * zs) + h * zs + jcol);
+            }
+            if (l == 1) vx = mlp_fetch8<X3, SERIES>(a.xin, mlp_row<X3, SERIES>(a.xin, b), icol);
+            else if (icol < a.H) {
+#pragma unroll
+                for (int h = 0; h < NP; ++h) vx.v[h] = *reinterpret_cast<const u32x4*>(ap + (size_t)b * (NP * a.H) + h * a.H + icol);
+            }
         }
         __syncthreads();      // the previous step's reads are done
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            *reinterpret_cast<u32x2*>(sdz[h] + srow * WG_LD + ch * 8) = u32x2{vz[h][0], vz[h][1]};
-            *reinterpret_cast<u32x2*>(sdz[h] + srow * WG_LD + ch * 8 + 4) = u32x2{vz[h][2], vz[h][3]};
-            *reinterpret_cast<u32x2*>(sx[h] + srow * WG_LD + ch * 8) = u32x2{vx[h][0], vx[h][1]};
-            *reinterpret_cast<u32x2*>(sx[h] + srow * WG_LD + ch * 8 + 4) = u32x2{vx[h][2], vx[h][3]};
+        for (int h = 0; h < NP; ++h) {
+            *reinterpret_cast<u32x2*>(sdz[h] + srow * WG_LD + ch * 8) = u32x2{vz.v[h][0], vz.v[h][1]};
+            *reinterpret_cast<u32x2*>(sdz[h] + srow * WG_LD + ch * 8 + 4) = u32x2{vz.v[h][2], vz.v[h][3]};
+            *reinterpret_cast<u32x2*>(sx[h] + srow * WG_LD + ch * 8) = u32x2{vx.v[h][0], vx.v[h][1]};
+            *reinterpret_cast<u32x2*>(sx[h] + srow * WG_LD + ch * 8 + 4) = u32x2{vx.v[h][2], vx.v[h][3]};
         }
         __syncthreads();
         // operands of the row-reduction: element e of lane group g is row 8 g + e of the step
-        u32x4 zf[2];
+        u32x4 zf[NP];
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {
+        for (int h = 0; h < NP; ++h) {
             const unsigned short* zz = reinterpret_cast<const unsigned short*>(sdz[h]) + (8 * g) * WG_LD + wave * 16 + c;
 #pragma unroll
             for (int q = 0; q < 4; ++q) zf[h][q] = (unsigned)zz[(2 * q) * WG_LD] | ((unsigned)zz[(2 * q + 1) * WG_LD] << 16);
         }
 #pragma unroll
         for (int ib = 0; ib < 4; ++ib) {
-            u32x4 xq[2];
+            u32x4 xf[NP];
 #pragma unroll
-            for (int h = 0; h < 2; ++h) {
+            for (int h = 0; h < NP; ++h) {
                 const unsigned short* xx = reinterpret_cast<const unsigned short*>(sx[h]) + (8 * g) * WG_LD + ib * 16 + c;
 #pragma unroll
-                for (int q = 0; q < 4; ++q) xq[h][q] = (unsigned)xx[(2 * q) * WG_LD] | ((unsigned)xx[(2 * q + 1) * WG_LD] << 16);
+                for (int q = 0; q < 4; ++q) xf[h][q] = (unsigned)xx[(2 * q) * WG_LD] | ((unsigned)xx[(2 * q + 1) * WG_LD] << 16);
             }
-            acc[ib] = mfma_bf16(zf[0], xq[0], acc[ib]);
-            acc[ib] = mfma_bf16(zf[1], xq[0], acc[ib]);
-            acc[ib] = mfma_bf16(zf[0], xq[1], acc[ib]);
+            acc[ib] = mlp_mma<NP>(zf, xf, acc[ib]);
         }
         if (it == 0 && tid < WG_T) {
 #pragma unroll 8
-            for (int rw = 0; rw < MLP_TILE; ++rw) bsum += (float)sdz[0][rw * WG_LD + tid] + (float)sdz[1][rw * WG_LD + tid];
+            for (int rw = 0; rw < MLP_TILE; ++rw) {
+                float z = (float)sdz[0][rw * WG_LD + tid];
+#pragma unroll
+                for (int h = 1; h < NP; ++h) z += (float)sdz[h][rw * WG_LD + tid];
+                bsum += z;
+            }
         }
     }
     float* sl = a.slabs + (size_t)slab * a.n_flat;
@@ -816,9 +591,14 @@ __global__ __launch_bounds__(256) void k_mlp_reduce(const float* slabs, int nsla
     if (tid == 0) loss_out[0] = red[0] / denom;
 }
 
+// the kernels of a plan, chosen once where the plan is created; [series]
+struct MlpKernels { void (*pack)(PackArgs, const float*); void (*in[2])(InArgs); void (*stack)(StackArgs); void (*wgrad[2])(WgArgs); };
+const MlpKernels MLP_BF16 = {k_mlp_pack<false>, {k_mlp_in<false, false>, k_mlp_in<false, true>}, k_mlp_stack<false>, {k_mlp_wgrad<false, false>, k_mlp_wgrad<false, true>}};
+const MlpKernels MLP_X3 = {k_mlp_pack<true>, {k_mlp_in<true, false>, nullptr}, k_mlp_stack<true>, {k_mlp_wgrad<true, false>, nullptr}};      // (no series form: mlp_prepare_input refuses it)
+
 }  // namespace
 
-struct mshgnn_mlp_plan { mshgnn_mlp_desc d; mshgnn_mlp_info info; };
+struct mshgnn_mlp_plan { mshgnn_mlp_desc d; mshgnn_mlp_info info; const MlpKernels* k; };
 
 extern "C" int mshgnn_mlp_compile_host(const mshgnn_mlp_desc* desc, int loss_kind, mshgnn_mlp_info* info) {
     if (!info) return set_err(MSHGNN_EINVAL, "null argument to mshgnn_mlp_compile_host");
@@ -834,8 +614,8 @@ extern "C" int mshgnn_mlp_create(const mshgnn_mlp_desc* desc, mshgnn_mlp_plan** 
     if (!p) return set_err(MSHGNN_ENOMEM, "mshgnn_mlp_create: out of memory");
     p->d = *desc;
     mlp_fill_info(p->d, p->info);
-    const void* stack = desc->dtype == MSHGNN_BF16X3 ? reinterpret_cast<const void*>(k_mlp_stack_x3) : reinterpret_cast<const void*>(k_mlp_stack);
-    hipError_t e = hipFuncSetAttribute(stack, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->info.lds_bytes);
+    p->k = desc->dtype == MSHGNN_BF16X3 ? &MLP_X3 : &MLP_BF16;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(p->k->stack), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->info.lds_bytes);
     if (e != hipSuccess) { delete p; return set_err(MSHGNN_EHIP, std::string("mshgnn_mlp_create: hipFuncSetAttribute: ") + hipGetErrorString(e)); }
     *plan_out = p;
     return MSHGNN_OK;
@@ -869,7 +649,7 @@ int mlp_prepare_input(const mshgnn_mlp_plan* p, const mshgnn_mlp_input* in, int6
         const int need = (p->d.in_channels + 7) / 8 * 8;
         if (((uintptr_t)in->x & 15) || in->pitch % 8 || in->pitch < need)
             return set_err(MSHGNN_EINVAL, std::string(who) + ": dense rows must be 16-byte aligned at a pitch that is a multiple of 8 and >= in_channels rounded up to 8");
-        mi.x = reinterpret_cast<const __bf16*>(in->x); mi.pitch = in->pitch;
+        mi.x = in->x; mi.pitch = in->pitch;
         return MSHGNN_OK;
     }
     const mshgnn_window_desc* d = in->desc;
@@ -914,7 +694,9 @@ int mlp_run(const mshgnn_mlp_plan* p, const mshgnn_mlp_input* in, int mode, int 
     const mshgnn_mlp_desc& d = p->d;
     const mshgnn_mlp_info& info = p->info;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const bool training = mode != MODE_INFER, x3 = d.dtype == MSHGNN_BF16X3;
+    const MlpKernels& k = *p->k;
+    const bool training = mode != MODE_INFER;
+    const int64_t n_terms = loss_kind == 1 ? batch * (d.out_channels / 2) : batch * d.out_channels;
     const MlpWs w = mlp_layout(d, info.n_flat, batch, training);
     char* ws = reinterpret_cast<char*>(workspace);
     const int L = d.num_layers, H = d.hidden;
@@ -940,23 +722,19 @@ int mlp_run(const mshgnn_mlp_plan* p, const mshgnn_mlp_input* in, int mode, int 
             if (training) region(w.wtp[l], H, l == L ? MLP_GK : H, l, 1);
         }
         pa.prefix[n] = tot; pa.n = n;
-        if (x3) hipLaunchKernelGGL(k_mlp_pack_x3, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, pa, params);
-        else hipLaunchKernelGGL(k_mlp_pack, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, pa, params);
+        hipLaunchKernelGGL(k.pack, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, pa, params);
         // input layer
         InArgs ia; memset(&ia, 0, sizeof(ia));
         ia.in = mi; ia.w1p = reinterpret_cast<const __bf16*>(ws + w.w1p); ia.K1p = w.K1p; ia.bias = params + info.off_b[0];
         ia.act1 = reinterpret_cast<__bf16*>(ws + w.act[1]); ia.H = H; ia.lab = lab;
         ia.lab_blocks = series ? (int)((lab.B + 255) / 256) : 0;
         const unsigned grid = (unsigned)(w.ntiles * (H / 128) + ia.lab_blocks);
-        if (x3) hipLaunchKernelGGL(k_mlp_in_x3, dim3(grid), dim3(256), 0, st, ia);
-        else if (series) hipLaunchKernelGGL(k_mlp_in<true>, dim3(grid), dim3(256), 0, st, ia);
-        else hipLaunchKernelGGL(k_mlp_in<false>, dim3(grid), dim3(256), 0, st, ia);
+        hipLaunchKernelGGL(k.in[series], dim3(grid), dim3(256), 0, st, ia);
     }
     // stack
     {
         StackArgs sa; memset(&sa, 0, sizeof(sa));
         sa.H = H; sa.out = d.out_channels; sa.L = L; sa.mode = mode; sa.loss_kind = loss_kind; sa.B = batch;
-        const int64_t n_terms = loss_kind == 1 ? batch * (d.out_channels / 2) : batch * d.out_channels;
         sa.inv = 1.0f / (float)n_terms;
         sa.params = params;
         for (int l = 1; l <= L; ++l) {
@@ -972,8 +750,7 @@ int mlp_run(const mshgnn_mlp_plan* p, const mshgnn_mlp_input* in, int mode, int 
             else sa.labels = targets ? reinterpret_cast<const int32_t*>(targets) : in->labels_out;
         }
         sa.loss_part = training ? reinterpret_cast<float*>(ws + w.loss_part) : nullptr;
-        if (x3) hipLaunchKernelGGL(k_mlp_stack_x3, dim3((unsigned)w.ntiles), dim3(256), (size_t)info.lds_bytes, st, sa);
-        else hipLaunchKernelGGL(k_mlp_stack, dim3((unsigned)w.ntiles), dim3(256), (size_t)info.lds_bytes, st, sa);
+        hipLaunchKernelGGL(k.stack, dim3((unsigned)w.ntiles), dim3(256), (size_t)info.lds_bytes, st, sa);
     }
     if (mode == MODE_STEP || mode == MODE_BWD) {
         WgArgs wa; memset(&wa, 0, sizeof(wa));
@@ -990,12 +767,9 @@ int mlp_run(const mshgnn_mlp_plan* p, const mshgnn_mlp_input* in, int mode, int 
         wa.prefix[L + 1] = tot;
         wa.slabs = reinterpret_cast<float*>(ws + w.slabs); wa.xin = mi;
         const unsigned grid = (unsigned)tot * (unsigned)w.nslab;
-        if (x3) hipLaunchKernelGGL(k_mlp_wgrad_x3, dim3(grid), dim3(256), 0, st, wa);
-        else if (series) hipLaunchKernelGGL(k_mlp_wgrad<true>, dim3(grid), dim3(256), 0, st, wa);
-        else hipLaunchKernelGGL(k_mlp_wgrad<false>, dim3(grid), dim3(256), 0, st, wa);
+        hipLaunchKernelGGL(k.wgrad[series], dim3(grid), dim3(256), 0, st, wa);
         const int grad_blocks = (int)((info.n_flat + 255) / 256);
         const bool with_loss = mode == MODE_STEP;
-        const int64_t n_terms = loss_kind == 1 ? batch * (d.out_channels / 2) : batch * d.out_channels;
         hipLaunchKernelGGL(k_mlp_reduce, dim3((unsigned)(grad_blocks + (with_loss ? 1 : 0))), dim3(256), 0, st, wa.slabs, w.nslab, info.n_flat, grad, grad_blocks,
                            reinterpret_cast<const float*>(ws + w.loss_part), w.ntiles, (float)n_terms, loss_out);
     }
