@@ -21,8 +21,10 @@ using namespace mshgnn::gen;
 using T16 = __bf16;
 using P16 = Prec<__bf16>;
 
+struct GenKernels;
 struct mshgnn_gen_state {      // device side of a generic plan
     GenPlan gp;
+    const GenKernels* k = nullptr;      // the kernels of the plan's arithmetic (GEN_BF16 / GEN_X3 below)
     int* d_tables = nullptr; uint8_t* d_signs = nullptr; float* d_out_mask = nullptr; PackDesc* d_packs = nullptr; BiasDesc* d_biases = nullptr;
 };
 
@@ -508,10 +510,7 @@ template <bool SPLIT, int MB, int NW> __global__ __launch_bounds__(64 * NW) void
 // vectors of step t are dead after it and chunk k + 1's are requested into the same registers right there, three K steps ahead of their use.  No more registers
 // than k_gstep4 + the 10 of the rows in flight.  Every accumulator still receives its products in k_gstep4's order (chunks in order, K steps 0..3): identical bits.
 // Chunks that are not one plain row (sums of two rows, raw inputs) are gathered at staging time as before.
-constexpr int GS5_MAX_TERMS = 16, GS5_TERM_BYTES = 32;      // k_gstep5's term table in LDS (behind the two tile sets)
-#ifndef GS5_MB_SPLIT
-#define GS5_MB_SPLIT 6      // 16-window row blocks per tile of the split arithmetic's k_gstep5 (96 windows: 253 registers, none spilled; 128: spills; 64: 7.67 vs 7.54 ms on the 32-limb model)
-#endif
+constexpr int GS5_TERM_BYTES = 32;      // k_gstep5's term table in LDS (behind the two tile sets): GS5_MAX_TERMS entries (mshgnn_gen_plan.hpp, with GS5_MB_SPLIT)
 constexpr int gs5_lds_bytes(bool split, int mb) { return 2 * (split ? 2 : 1) * mb * P16::BLK + GS5_MAX_TERMS * GS5_TERM_BYTES; }
 // SPLIT (the split-bf16 arithmetic of section 4b: rows [hi Hd | lo Hd], three products per term, hi x hi, lo-weights x hi, hi-weights x lo) runs it on 96-window tiles
 // (MB = GS5_MB_SPLIT = 6): twice the planes in the weight ring, the rows in flight and the window fragments.
@@ -1397,35 +1396,6 @@ __global__ __launch_bounds__(256) void k_gfinalize(GFinArgs a) {
 // ------------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------------
-int gen_create(mshgnn_plan* p, const mshgnn_desc* desc) {
-    mshgnn_gen_state* g = new (std::nothrow) mshgnn_gen_state();
-    if (!g) return set_err(MSHGNN_ENOMEM, "out of host memory");
-    if (!compile_gen_plan(desc, g->gp)) {
-        const std::string m = g->gp.err; delete g;
-        return set_err(m.find("not supported") != std::string::npos ? MSHGNN_EUNSUPPORTED : MSHGNN_EINVAL, m);
-    }
-    p->gen = g;
-    GenPlan& gp = g->gp;
-    auto up = [&](void** dptr, const void* src, size_t bytes) -> int {
-        HIPCHK(hipMalloc(dptr, std::max<size_t>(bytes, 16)));
-        if (bytes) HIPCHK(hipMemcpy(*dptr, src, bytes, hipMemcpyHostToDevice));
-        return MSHGNN_OK;
-    };
-    int rc;
-    if ((rc = up((void**)&g->d_tables, gp.tables.data(), gp.tables.size() * 4)) != 0 ||
-        (rc = up((void**)&g->d_signs, gp.signs.data(), gp.signs.size())) != 0 ||
-        (rc = up((void**)&g->d_out_mask, gp.out_mask_f.data(), gp.out_mask_f.size() * 4)) != 0 ||
-        (rc = up((void**)&g->d_packs, gp.packs.data(), gp.packs.size() * sizeof(PackDesc))) != 0 ||
-        (rc = up((void**)&g->d_biases, gp.biases.data(), gp.biases.size() * sizeof(BiasDesc))) != 0) return rc;
-    const int dec_lds = 16 * 8 * TW * 4;
-    if ((rc = set_lds_attr(k_gdec_bwd<false>, dec_lds)) || (rc = set_lds_attr(k_gdec_bwd<true>, dec_lds)) ||
-        (rc = set_lds_attr(k_gstep<true, 8, 8>, 16 * P16::BLK)) || (rc = set_lds_attr(k_ggradw<true, 1>, ggw_lds_bytes(true, 1))) ||
-        (rc = set_lds_attr(k_ggradw<true, 2, GGW_NWV_SPLIT2>, ggw_lds_bytes(true, 2))) || (rc = set_lds_attr(k_ggradw<true, 2, GGW_NWV_SPLIT2, true>, ggw_lds_bytes(true, 2, true))) ||
-        (rc = set_lds_attr(k_ggradw<true, 1, 8, true>, ggw_lds_bytes(true, 1, true))) || (rc = set_lds_attr(k_ggradw<false, 2, GGW_NWV_BF16, true>, ggw_lds_bytes(false, 2, true))) || (rc = set_lds_attr(k_ggradw<false, 2, GGW_NWV_BF16>, ggw_lds_bytes(false, 2))) || (rc = set_lds_attr(k_gstep5<false, 8, true>, gs5_lds_bytes(false, 8))) || (rc = set_lds_attr(k_gstep5<false, 8, false, 4, true>, gs5_lds_bytes(false, 8))) || (rc = set_lds_attr(k_gstep5<false, 8, false, 8, true>, gs5_lds_bytes(false, 8))) || (rc = set_lds_attr(k_gstep5<false, 8, true, 4>, gs5_lds_bytes(false, 8))) || (rc = set_lds_attr(k_gstep5<false, 8, false, 4>, gs5_lds_bytes(false, 8))) || (rc = set_lds_attr(k_gstep5<false, 8, false>, gs5_lds_bytes(false, 8))) ||
-        (rc = set_lds_attr(k_gstep5<true, GS5_MB_SPLIT, true>, gs5_lds_bytes(true, GS5_MB_SPLIT))) || (rc = set_lds_attr(k_gstep5<true, GS5_MB_SPLIT, false>, gs5_lds_bytes(true, GS5_MB_SPLIT)))) return rc;
-    return MSHGNN_OK;
-}
-
 void gen_destroy(mshgnn_plan* p) {
     mshgnn_gen_state* g = p->gen;
     if (!g) return;
@@ -1558,120 +1528,106 @@ static bool g_raw_ok(const GenPlan& gp, const GArgs& a) {
         if (a.vb[t] < 16 || (a.pitch[t] & 7) != 0 || (uint64_t)a.B * (uint64_t)a.nodes[t] * (uint64_t)a.pitch[t] * 2 >= (1ull << 32)) return false;
     return true;
 }
-static bool g_forced_tile() { const char* e = getenv("MSHGNN_GEN_TILE"); return e && atoi(e) >= 0; }
-static int g_tile_blocks(int B, bool split) {
-    const char* e = getenv("MSHGNN_GEN_TILE");      // (kernel experiments; read per launch so that a test can compare modes in one process)
-    const int forced = e ? atoi(e) : -1;
-    if (forced >= 0 && forced <= 9 && forced != 7) return forced;
-    // bf16: 16 waves; on 128-window tiles (k_gstep5: the software pipeline of 8 waves; k_gstep4) once the batch has two of them -- half the weight stream per window, 250-258 / 252-314 us per layer launch
-    // against 285-292 / 303-357 on the 32-limb model; split arithmetic: k_gstep4 at 16 waves on 64-window tiles (720-740 / 673-766 us against 803-813 / 814-925
-    // for k_gstep at 8 waves, whose 16-wave form spills)
-    return split ? 8 : (B >= 256 ? 8 : 3);      // (split, hidden % 512 != 0: the dispatch falls back to k_gstep at 8 / 4 waves; 8: k_gstep5 on the launches whose terms are all plain rows, k_gstep4 on the others)
+// The kernels of a plan's arithmetic, chosen once in gen_create.
+struct GenKernels { void (*agg)(GArgs, int, int); void (*dec_fwd)(GDecArgs); void (*dec_bwd)(GDecArgs); };
+static const GenKernels GEN_BF16 = {k_gagg<false>, k_gdec_fwd<false>, k_gdec_bwd<false>}, GEN_X3 = {k_gagg<true>, k_gdec_fwd<true>, k_gdec_bwd<true>};
+constexpr int GDEC_BWD_LDS = 16 * 8 * TW * 4;
+
+// The launch tables of the job and weight-gradient kernels, row i for value i of GJobKernel / GGradwKernel (mshgnn_gen_plan.hpp: pick_job_kernel / pick_gradw_kernel
+// say which row a launch takes): the instantiation, its block size and its dynamic LDS.
+struct GKernel { int id; void (*fn)(GArgs); int threads, lds; };
+#define GJ(id) (int)GJobKernel::id
+#define GW(id) (int)GGradwKernel::id
+static const GKernel G_JOB_TAB[] = {
+    {GJ(GSTEP_4W), k_gstep<false, 4, 4>, 256, 4 * P16::BLK}, {GJ(GSTEP_8W), k_gstep<false, 4, 8>, 512, 4 * P16::BLK},
+    {GJ(GSTEP_8W_T128), k_gstep<false, 8, 8>, 512, 8 * P16::BLK}, {GJ(GSTEP_16W), k_gstep<false, 4, 16>, 1024, 4 * P16::BLK},
+    {GJ(GSTEP_X3_4W), k_gstep<true, 4, 4>, 256, 2 * 4 * P16::BLK}, {GJ(GSTEP_X3_8W), k_gstep<true, 4, 8>, 512, 2 * 4 * P16::BLK},
+    {GJ(GSTEP_X3_8W_T128), k_gstep<true, 8, 8>, 512, 2 * 8 * P16::BLK}, {GJ(GSTEP_X3_16W), k_gstep<true, 4, 16>, 1024, 2 * 4 * P16::BLK},
+    {GJ(GSTEP4), k_gstep4<false, 8, 16>, 1024, 8 * P16::BLK}, {GJ(GSTEP4_X3), k_gstep4<true, 4, 16>, 1024, 2 * 4 * P16::BLK},
+    {GJ(GSTEP5_8W), k_gstep5<false, 8, false>, 512, gs5_lds_bytes(false, 8)}, {GJ(GSTEP5_8W_MASKED), k_gstep5<false, 8, true>, 512, gs5_lds_bytes(false, 8)},
+    {GJ(GSTEP5_4W), k_gstep5<false, 8, false, 4>, 256, gs5_lds_bytes(false, 8)}, {GJ(GSTEP5_4W_MASKED), k_gstep5<false, 8, true, 4>, 256, gs5_lds_bytes(false, 8)},
+    {GJ(GSTEP5_X3), k_gstep5<true, GS5_MB_SPLIT, false>, 512, gs5_lds_bytes(true, GS5_MB_SPLIT)}, {GJ(GSTEP5_X3_MASKED), k_gstep5<true, GS5_MB_SPLIT, true>, 512, gs5_lds_bytes(true, GS5_MB_SPLIT)},
+    {GJ(GSTEP5_RAW_8W), k_gstep5<false, 8, false, 8, true>, 512, gs5_lds_bytes(false, 8)}, {GJ(GSTEP5_RAW_4W), k_gstep5<false, 8, false, 4, true>, 256, gs5_lds_bytes(false, 8)},
+};
+static const GKernel G_GRADW_TAB[] = {
+    {GW(BF16_OS1), k_ggradw<false, 1>, 512, ggw_lds_bytes(false, 1)}, {GW(BF16_OS2), k_ggradw<false, 2, GGW_NWV_BF16>, 64 * GGW_NWV_BF16, ggw_lds_bytes(false, 2)},
+    {GW(X3_OS1), k_ggradw<true, 1>, 512, ggw_lds_bytes(true, 1)}, {GW(X3_OS2), k_ggradw<true, 2, GGW_NWV_SPLIT2>, 64 * GGW_NWV_SPLIT2, ggw_lds_bytes(true, 2)},
+    {GW(BF16_OS1_NOMASK), k_ggradw<false, 1, 8, true>, 512, ggw_lds_bytes(false, 1, true)}, {GW(BF16_OS2_NOMASK), k_ggradw<false, 2, GGW_NWV_BF16, true>, 64 * GGW_NWV_BF16, ggw_lds_bytes(false, 2, true)},
+    {GW(X3_OS1_NOMASK), k_ggradw<true, 1, 8, true>, 512, ggw_lds_bytes(true, 1, true)}, {GW(X3_OS2_NOMASK), k_ggradw<true, 2, GGW_NWV_SPLIT2, true>, 64 * GGW_NWV_SPLIT2, ggw_lds_bytes(true, 2, true)},
+};
+#undef GJ
+#undef GW
+constexpr int G_N_JOB_KERNELS = sizeof(G_JOB_TAB) / sizeof(GKernel), G_N_GRADW_KERNELS = sizeof(G_GRADW_TAB) / sizeof(GKernel);
+static_assert(G_N_JOB_KERNELS == (int)GJobKernel::COUNT && G_N_GRADW_KERNELS == (int)GGradwKernel::COUNT, "one table row per enum value");
+
+// Every row is where its enum value says; a launch above the default LDS limit (or at it: a kernel's static LDS comes on top) is registered with the runtime.
+static int g_register_lds(const GKernel* tab, int n) {
+    constexpr int LDS_DEFAULT_LIMIT = 64 * 1024;
+    for (int i = 0; i < n; ++i) {
+        if (tab[i].id != i) return set_err(MSHGNN_EINVAL, "generic engine: a launch table is out of the order of its enum");
+        if (tab[i].lds >= LDS_DEFAULT_LIMIT) if (int rc = set_lds_attr(tab[i].fn, tab[i].lds)) return rc;
+    }
+    return MSHGNN_OK;
 }
 
-#ifdef GEN_TIMELINE
-static long long* gen_tl(const char* which) {      // MSHGNN_GEN_TL = "<launch name>:<hex device address>"
-    const char* e = TUNE_ENV("MSHGNN_GEN_TL");
-    if (!e) return nullptr;
-    const char* c = strchr(e, ':');
-    if (!c || strncmp(e, which, (size_t)(c - e)) != 0 || strlen(which) != (size_t)(c - e)) return nullptr;
+int gen_create(mshgnn_plan* p, const mshgnn_desc* desc) {
+    mshgnn_gen_state* g = new (std::nothrow) mshgnn_gen_state();
+    if (!g) return set_err(MSHGNN_ENOMEM, "out of host memory");
+    if (!compile_gen_plan(desc, g->gp)) {
+        const std::string m = g->gp.err; delete g;
+        return set_err(m.find("not supported") != std::string::npos ? MSHGNN_EUNSUPPORTED : MSHGNN_EINVAL, m);
+    }
+    p->gen = g;
+    GenPlan& gp = g->gp;
+    g->k = gp.split ? &GEN_X3 : &GEN_BF16;
+    auto up = [&](void** dptr, const void* src, size_t bytes) -> int {
+        HIPCHK(hipMalloc(dptr, std::max<size_t>(bytes, 16)));
+        if (bytes) HIPCHK(hipMemcpy(*dptr, src, bytes, hipMemcpyHostToDevice));
+        return MSHGNN_OK;
+    };
+    int rc;
+    if ((rc = up((void**)&g->d_tables, gp.tables.data(), gp.tables.size() * 4)) != 0 ||
+        (rc = up((void**)&g->d_signs, gp.signs.data(), gp.signs.size())) != 0 ||
+        (rc = up((void**)&g->d_out_mask, gp.out_mask_f.data(), gp.out_mask_f.size() * 4)) != 0 ||
+        (rc = up((void**)&g->d_packs, gp.packs.data(), gp.packs.size() * sizeof(PackDesc))) != 0 ||
+        (rc = up((void**)&g->d_biases, gp.biases.data(), gp.biases.size() * sizeof(BiasDesc))) != 0) return rc;
+    if ((rc = set_lds_attr(GEN_BF16.dec_bwd, GDEC_BWD_LDS)) || (rc = set_lds_attr(GEN_X3.dec_bwd, GDEC_BWD_LDS)) ||
+        (rc = g_register_lds(G_JOB_TAB, G_N_JOB_KERNELS)) || (rc = g_register_lds(G_GRADW_TAB, G_N_GRADW_KERNELS))) return rc;
+    return MSHGNN_OK;
+}
+
+#if defined(GEN_TIMELINE) || defined(GGW_STAMPS)
+static long long* g_named_addr(const char* e, const char* which) {      // e = "<launch name>:<hex device address>": the address if the name is `which`
+    const char* c = e ? strchr(e, ':') : nullptr;
+    if (!c || strlen(which) != (size_t)(c - e) || strncmp(e, which, (size_t)(c - e)) != 0) return nullptr;
     return reinterpret_cast<long long*>(strtoull(c + 1, nullptr, 16));
 }
 #endif
+static void g_launch_aggs(const mshgnn_plan* p, const Launch& ln, const GArgs& a, hipStream_t st) {      // the launch's aggregates of many rows
+    ProfScope ps(p, p->gen->gp.ks_agg, st);
+    const int row_blocks = (a.B + GA_ROWS - 1) / GA_ROWS;
+    hipLaunchKernelGGL(p->gen->k->agg, dim3((unsigned)ln.n_agg * row_blocks), dim3(GA_THREADS), 0, st, a, ln.agg0, row_blocks);
+}
 static void g_launch_jobs(const mshgnn_plan* p, const Launch& ln, GArgs a, hipStream_t st) {
     const GenPlan& gp = p->gen->gp;
     a.job0 = ln.job0;
-    if (ln.n_agg > 0) {      // the launch's aggregates of many rows
-        ProfScope ps(p, gp.ks_agg, st);
-        const int row_blocks = (a.B + GA_ROWS - 1) / GA_ROWS;
-        if (gp.split) hipLaunchKernelGGL(k_gagg<true>, dim3((unsigned)ln.n_agg * row_blocks), dim3(GA_THREADS), 0, st, a, ln.agg0, row_blocks);
-        else hipLaunchKernelGGL(k_gagg<false>, dim3((unsigned)ln.n_agg * row_blocks), dim3(GA_THREADS), 0, st, a, ln.agg0, row_blocks);
-    }
+    if (ln.n_agg > 0) g_launch_aggs(p, ln, a, st);
 #ifdef GEN_TIMELINE
-    a.tl = gen_tl(gp.kstats[ln.ks].name);
+    a.tl = g_named_addr(TUNE_ENV("MSHGNN_GEN_TL"), gp.kstats[ln.ks].name);
 #endif
 #ifdef GGW_STAMPS
-    {   // MSHGNN_GS4_STAMPS = "<launch name>:<hex device address>" (tools/stamps_gstep4.py)
-        const char* e = getenv("MSHGNN_GS4_STAMPS"); const char* c = e ? strchr(e, ':') : nullptr; const char* nm = gp.kstats[ln.ks].name;
-        a.stamps = (c && strlen(nm) == (size_t)(c - e) && strncmp(e, nm, (size_t)(c - e)) == 0) ? reinterpret_cast<long long*>(strtoull(c + 1, nullptr, 16)) : nullptr;
-    }
+    a.stamps = g_named_addr(getenv("MSHGNN_GS4_STAMPS"), gp.kstats[ln.ks].name);      // (tools/stamps_gstep4.py)
 #endif
-    // windows per workgroup: a packed weight fragment (8 KB per wave and K chunk, from L2) is reused for every 16-window row block of the tile
-    // output tile of a workgroup: 64 windows x (32 NW) columns.  The staged A tile is shared by all NW waves, so wider tiles re-read the
-    // activations fewer times (hidden / (32 NW) column groups per row of jobs): measured at h=512, B=1024: layer_fwd bf16 515 / 354 / 296 us at
-    // 4 / 8 / 16 waves, split 870 / 799 / 1012 us (16 waves: 128 VGPRs, spills); 128-window tiles lose (fewer resident workgroups hide less
-    // of the staging latency: 495 us at 8 waves, 389 us at 16 waves with 56 B of scratch)
-    const int mode = g_tile_blocks(a.B, gp.split);      // 0: 4 waves; 1: 8 waves, 128 windows; 2: 8 waves; 3: 16 waves; 6: k_gstep4 (bf16, hidden % 512 == 0; the default from 256 windows)
-    // k_gstep5 at 4 waves (256 columns per workgroup, two workgroups per CU) when the launch has more (job, tile) pairs than CUs: half-size workgroups halve the
-    // launch's tail (1 032 pairs on 256 CUs: 209 -> 189 us; 1 024: equal; 256 pairs, a single round: 42 -> 46 us, so those keep 8 waves).  Same bits.  (=9 / =8 force one.)
-    // The raw-input (encoder) launch on k_gstep5<RAW>: bf16 arithmetic, every input tensor 16-byte aligned with a pitch of whole chunks, row offsets inside 32 bits
-    if ((mode == 8 || mode == 9) && !gp.split && gp.NCT % 2 == 0 && ln.all_raw && g_raw_ok(gp, a)) {
-        a.tiles = (a.B + 127) / 128; a.njt = ln.n_jobs * a.tiles;
-        ProfScope ps(p, ln.ks, st);
-        if (gp.NCT % 4 != 0 || mode == 9 || (!g_forced_tile() && a.njt > p->n_cu)) {
-            const int nctg = gp.NCT / 2;
-            hipLaunchKernelGGL((k_gstep5<false, 8, false, 4, true>), dim3((unsigned)((a.njt + 7) / 8) * 8 * nctg), dim3(256), gs5_lds_bytes(false, 8), st, a);
-        } else hipLaunchKernelGGL((k_gstep5<false, 8, false, 8, true>), dim3((unsigned)a.njt * (a.NCT / 4)), dim3(512), gs5_lds_bytes(false, 8), st, a);
-        return;
-    }
-    // Widths that are a multiple of 256 but not of 512 (hidden = 256, 768: the reference's --hidden_size) only have the 4-wave form.
-    const bool half_only = gp.NCT % 4 != 0;
-    if ((mode == 9 || (mode == 8 && !g_forced_tile() && (half_only || ln.n_jobs * ((a.B + 127) / 128) > p->n_cu))) && !gp.split && gp.NCT % 2 == 0 && ln.all_plain && ln.max_terms <= GS5_MAX_TERMS) {
-        a.tiles = (a.B + 127) / 128; a.njt = ln.n_jobs * a.tiles;
-        const int nctg = gp.NCT / 2;
-        const unsigned grid9 = (unsigned)((a.njt + 7) / 8) * 8 * nctg;
-        ProfScope ps(p, ln.ks, st);
-        if (ln.any_mask) hipLaunchKernelGGL((k_gstep5<false, 8, true, 4>), dim3(grid9), dim3(256), gs5_lds_bytes(false, 8), st, a);
-        else hipLaunchKernelGGL((k_gstep5<false, 8, false, 4>), dim3(grid9), dim3(256), gs5_lds_bytes(false, 8), st, a);
-        return;
-    }
-    if ((mode == 8 || mode == 9) && gp.NCT % 4 == 0 && ln.all_plain && ln.max_terms <= GS5_MAX_TERMS) {      // k_gstep5: k_gstep4's tile, software-pipelined (launches whose every term is one plain row)
-        a.tiles = gp.split ? (a.B + 16 * GS5_MB_SPLIT - 1) / (16 * GS5_MB_SPLIT) : (a.B + 127) / 128;
-        const unsigned grid4 = (unsigned)ln.n_jobs * a.tiles * (a.NCT / 4);
-        ProfScope ps(p, ln.ks, st);
-        if (gp.split) {
-            if (ln.any_mask) hipLaunchKernelGGL((k_gstep5<true, GS5_MB_SPLIT, true>), dim3(grid4), dim3(512), gs5_lds_bytes(true, GS5_MB_SPLIT), st, a);
-            else hipLaunchKernelGGL((k_gstep5<true, GS5_MB_SPLIT, false>), dim3(grid4), dim3(512), gs5_lds_bytes(true, GS5_MB_SPLIT), st, a);
-        } else {
-            if (ln.any_mask) hipLaunchKernelGGL((k_gstep5<false, 8, true>), dim3(grid4), dim3(512), gs5_lds_bytes(false, 8), st, a);
-            else hipLaunchKernelGGL((k_gstep5<false, 8, false>), dim3(grid4), dim3(512), gs5_lds_bytes(false, 8), st, a);
-        }
-        return;
-    }
-    if (mode >= 6 && !gp.split && gp.NCT % 4 == 0) {      // k_gstep4: 16 waves on 128-window tiles (hidden a multiple of 512)
-        a.tiles = (a.B + 127) / 128;
-        const unsigned grid4 = (unsigned)ln.n_jobs * a.tiles * (a.NCT / 4);
-        ProfScope ps(p, ln.ks, st);
-        hipLaunchKernelGGL((k_gstep4<false, 8, 16>), dim3(grid4), dim3(1024), 8 * P16::BLK, st, a);
-        return;
-    }
-    // (hidden = 256: the 8-wave form of k_gstep4 measured 1.51 against 1.47 ms/step for k_gstep on A1-C2, 8192 windows -- tools/time_h256.py; not dispatched)
-    if (mode >= 6 && gp.split && gp.NCT % 4 == 0) {       // the split arithmetic: the same kernel at 16 waves on 64-window tiles
-        a.tiles = (a.B + 63) / 64;
-        const unsigned grid4 = (unsigned)ln.n_jobs * a.tiles * (a.NCT / 4);
-        ProfScope ps(p, ln.ks, st);
-        hipLaunchKernelGGL((k_gstep4<true, 4, 16>), dim3(grid4), dim3(1024), 2 * 4 * P16::BLK, st, a);
-        return;
-    }
-    int nw = 4;
-    if ((mode == 1 || mode == 2) && gp.NCT % 2 == 0) nw = 8;
-    if (mode >= 3) nw = gp.NCT % 4 == 0 ? 16 : (gp.NCT % 2 == 0 ? 8 : 4);
-    const int mb = (nw == 8 && mode == 1) ? 8 : 4;
-    a.tiles = (a.B + mb * 16 - 1) / (mb * 16);
-    const unsigned grid = (unsigned)ln.n_jobs * a.tiles * (a.NCT / (nw / 4));
-    const int lds = mb * P16::BLK * (gp.split ? 2 : 1);
+    GJobQuery q;
+    q.forced = parse_gen_tile(getenv("MSHGNN_GEN_TILE"));      // (kernel experiments; read per launch so that a test can compare modes in one process)
+    q.split = gp.split; q.NCT = gp.NCT; q.B = a.B; q.n_cu = p->n_cu;
+    q.n_jobs = ln.n_jobs; q.all_raw = ln.all_raw; q.all_plain = ln.all_plain; q.any_mask = ln.any_mask; q.max_terms = ln.max_terms;
+    q.raw_ok = ln.all_raw && g_raw_ok(gp, a);
+    const GJobPick pick = pick_job_kernel(q);
+    a.tiles = pick.tiles; a.njt = pick.njt;
+    const GKernel& k = G_JOB_TAB[(int)pick.k];
     ProfScope ps(p, ln.ks, st);
-    if (gp.split) {
-        if (nw == 16) hipLaunchKernelGGL((k_gstep<true, 4, 16>), dim3(grid), dim3(1024), lds, st, a);
-        else if (nw == 8 && mb == 8) hipLaunchKernelGGL((k_gstep<true, 8, 8>), dim3(grid), dim3(512), lds, st, a);
-        else if (nw == 8) hipLaunchKernelGGL((k_gstep<true, 4, 8>), dim3(grid), dim3(512), lds, st, a);
-        else hipLaunchKernelGGL((k_gstep<true, 4, 4>), dim3(grid), dim3(256), lds, st, a);
-    } else {
-        if (nw == 16) hipLaunchKernelGGL((k_gstep<false, 4, 16>), dim3(grid), dim3(1024), lds, st, a);
-        else if (nw == 8 && mb == 8) hipLaunchKernelGGL((k_gstep<false, 8, 8>), dim3(grid), dim3(512), lds, st, a);
-        else if (nw == 8) hipLaunchKernelGGL((k_gstep<false, 4, 8>), dim3(grid), dim3(512), lds, st, a);
-        else hipLaunchKernelGGL((k_gstep<false, 4, 4>), dim3(grid), dim3(256), lds, st, a);
-    }
+    hipLaunchKernelGGL(k.fn, dim3(pick.grid), dim3(k.threads), k.lds, st, a);
 }
 
 int gen_forward(const mshgnn_plan* p, StepCall& c) {      // (no fused tail on this engine: the loss, if any, is the backward's; c.dec_done / c.stack_done stay false)
@@ -1696,8 +1652,7 @@ int gen_forward(const mshgnn_plan* p, StepCall& c) {      // (no fused tail on t
         da.B = B; da.Hd = gp.Hd; da.node0 = gp.type_base[d.out_type]; da.n_out = d.type_nodes[d.out_type]; da.dout = d.out_channels;
         const int64_t rows = (int64_t)B * da.n_out;
         ProfScope ps(p, gp.ks_dec_fwd, st);
-        if (gp.split) hipLaunchKernelGGL(k_gdec_fwd<true>, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, st, da);
-        else hipLaunchKernelGGL(k_gdec_fwd<false>, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, st, da);
+        hipLaunchKernelGGL(g->k->dec_fwd, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, st, da);
     }
     HIPCHK(hipGetLastError());
     return MSHGNN_OK;
@@ -1720,10 +1675,8 @@ int gen_backward(const mshgnn_plan* p, const StepCall& c) {
         da.B = B; da.Hd = gp.Hd; da.node0 = gp.type_base[d.out_type]; da.n_out = n_out; da.dout = d.out_channels;
         if (y) { da.y = y; da.out = c.out; da.inv_n = 1.0f / (float)((int64_t)B * n_out * d.out_channels); }
         if (labels) { da.labels = labels; da.out = c.out; da.inv_n = 1.0f / (float)((int64_t)B * n_out); }
-        const int dec_lds = 16 * 8 * TW * 4;
         ProfScope ps(p, gp.ks_dec_bwd, st);
-        if (gp.split) hipLaunchKernelGGL(k_gdec_bwd<true>, dim3(NWG_DEC), dim3(256), dec_lds, st, da);
-        else hipLaunchKernelGGL(k_gdec_bwd<false>, dim3(NWG_DEC), dim3(256), dec_lds, st, da);
+        hipLaunchKernelGGL(g->k->dec_bwd, dim3(NWG_DEC), dim3(256), GDEC_BWD_LDS, st, da);
     }
     GArgs a{};
     int rc = g_fill(p, lay, c.x, c.x_pitch, ws, B, 1, a);
@@ -1745,18 +1698,10 @@ int gen_backward(const mshgnn_plan* p, const StepCall& c) {
         { const char* e = getenv("MSHGNN_GGW_STAMPS"); a.stamps = e ? reinterpret_cast<long long*>(strtoull(e, nullptr, 16)) : nullptr; }
 #endif
 #ifdef GEN_TIMELINE
-        a.tl = gen_tl("gradw");
+        a.tl = g_named_addr(TUNE_ENV("MSHGNN_GEN_TL"), "gradw");
 #endif
-        // (gp.dhm: no P operand carries relu bits -- the NOMASK instantiations)
-        if (gp.dhm) {
-            if (gp.split && gp.su_os == 2) hipLaunchKernelGGL((k_ggradw<true, 2, GGW_NWV_SPLIT2, true>), dim3(grid), dim3(64 * GGW_NWV_SPLIT2), ggw_lds_bytes(true, 2, true), st, a);
-            else if (gp.split) hipLaunchKernelGGL((k_ggradw<true, 1, 8, true>), dim3(grid), dim3(512), ggw_lds_bytes(true, 1, true), st, a);
-            else if (gp.su_os == 2) hipLaunchKernelGGL((k_ggradw<false, 2, GGW_NWV_BF16, true>), dim3(grid), dim3(64 * GGW_NWV_BF16), ggw_lds_bytes(false, 2, true), st, a);
-            else hipLaunchKernelGGL((k_ggradw<false, 1, 8, true>), dim3(grid), dim3(512), ggw_lds_bytes(false, 1, true), st, a);
-        } else if (gp.split && gp.su_os == 2) hipLaunchKernelGGL((k_ggradw<true, 2, GGW_NWV_SPLIT2>), dim3(grid), dim3(64 * GGW_NWV_SPLIT2), ggw_lds_bytes(true, 2), st, a);
-        else if (gp.split) hipLaunchKernelGGL((k_ggradw<true, 1>), dim3(grid), dim3(512), ggw_lds_bytes(true, 1), st, a);
-        else if (gp.su_os == 2) hipLaunchKernelGGL((k_ggradw<false, 2, GGW_NWV_BF16>), dim3(grid), dim3(64 * GGW_NWV_BF16), ggw_lds_bytes(false, 2), st, a);
-        else hipLaunchKernelGGL((k_ggradw<false, 1>), dim3(grid), dim3(512), ggw_lds_bytes(false, 1), st, a);
+        const GKernel& k = G_GRADW_TAB[(int)pick_gradw_kernel(gp.split, gp.su_os, gp.dhm)];
+        hipLaunchKernelGGL(k.fn, dim3(grid), dim3(k.threads), k.lds, st, a);
     }
     {
         GFinArgs fa{g->d_tables + gp.fin_off, reinterpret_cast<const float*>(ws + lay.slabs), reinterpret_cast<const float*>(ws + lay.dec_slabs), c.grad_params,

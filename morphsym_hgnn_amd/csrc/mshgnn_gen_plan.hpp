@@ -9,7 +9,8 @@
 // K loop runs over TERMS = (weight pack, sources to aggregate).  Aggregation happens while a term's A tile is staged (sum / mean of
 // the source rows in fp32 -- the reference's own order: aggregate, then lin_rel), so a node with in-degree 32 costs one block GEMM
 // per relation, not 32.  The backward pass is the same job machinery on the transposed graph; weight gradients are split-K
-// 128x128 tiles dW = P^T Q with Q aggregated the same way.  No HIP calls in this file.
+// 128x128 tiles dW = P^T Q with Q aggregated the same way.  At the end of the file: which kernel instantiation a launch gets (pick_job_kernel,
+// pick_gradw_kernel).  No HIP calls in this file.
 #pragma once
 #include "mshgnn_plan.hpp"
 #include <climits>
@@ -705,6 +706,106 @@ inline void layout_gen_workspace(const GenPlan& p, int64_t B, int training, mshg
     o->loss = take(64);
     o->total = off;
 }
+
+// ------------------------------------------------------------------------------------------------------
+// Which kernel a launch gets.  The rules are stated here once, host only and without HIP types (tests/test_gen_pick.py drives them through
+// libmshgnn_hostplan.so); mshgnn_gen.hip keeps one table per enum below, in the enum's order, with the kernel's address, block size and dynamic LDS.
+// ------------------------------------------------------------------------------------------------------
+constexpr int GS5_MAX_TERMS = 16;      // k_gstep5's term table in LDS (behind the two tile sets)
+#ifndef GS5_MB_SPLIT
+#define GS5_MB_SPLIT 6      // 16-window row blocks per tile of the split arithmetic's k_gstep5 (96 windows: 253 registers, none spilled; 128: spills; 64: 7.67 vs 7.54 ms on the 32-limb model)
+#endif
+
+// The job-kernel instantiations, X(id, kernel).  Order matters to pick_job_kernel: the split form of a k_gstep is 4 behind its bf16 form, the MASKED form of a k_gstep5
+// one behind the unmasked one.
+#define MSHGNN_GJOB_KERNELS(X) \
+    X(GSTEP_4W, "k_gstep<false,4,4>") X(GSTEP_8W, "k_gstep<false,4,8>") X(GSTEP_8W_T128, "k_gstep<false,8,8>") X(GSTEP_16W, "k_gstep<false,4,16>") \
+    X(GSTEP_X3_4W, "k_gstep<true,4,4>") X(GSTEP_X3_8W, "k_gstep<true,4,8>") X(GSTEP_X3_8W_T128, "k_gstep<true,8,8>") X(GSTEP_X3_16W, "k_gstep<true,4,16>") \
+    X(GSTEP4, "k_gstep4<false,8,16>") X(GSTEP4_X3, "k_gstep4<true,4,16>") \
+    X(GSTEP5_8W, "k_gstep5<false,8,false,8,false>") X(GSTEP5_8W_MASKED, "k_gstep5<false,8,true,8,false>") \
+    X(GSTEP5_4W, "k_gstep5<false,8,false,4,false>") X(GSTEP5_4W_MASKED, "k_gstep5<false,8,true,4,false>") \
+    X(GSTEP5_X3, "k_gstep5<true,GS5_MB_SPLIT,false,8,false>") X(GSTEP5_X3_MASKED, "k_gstep5<true,GS5_MB_SPLIT,true,8,false>") \
+    X(GSTEP5_RAW_8W, "k_gstep5<false,8,false,8,true>") X(GSTEP5_RAW_4W, "k_gstep5<false,8,false,4,true>")
+enum class GJobKernel : int {
+#define X(id, name) id,
+    MSHGNN_GJOB_KERNELS(X)
+#undef X
+    COUNT
+};
+constexpr const char* GJOB_KERNEL_NAMES[] = {
+#define X(id, name) name,
+    MSHGNN_GJOB_KERNELS(X)
+#undef X
+};
+
+struct GJobQuery {
+    int forced = -1;      // MSHGNN_GEN_TILE: 0 / 1 / 2 / 3 / 6 / 8 / 9, or -1 (unset, or any other text)
+    bool split = false;
+    int NCT = 0;
+    int n_jobs = 0; bool all_raw = false, all_plain = false, any_mask = false; int max_terms = 0;      // of the Launch
+    int B = 0, n_cu = 0;
+    bool raw_ok = false;  // the caller's input tensors suit k_gstep5<RAW> (g_raw_ok, mshgnn_gen.hip)
+};
+// nw waves of 64 lanes; tiles of tile_windows windows; njt: the (job, tile) pairs, where the kernel decodes its workgroup id with them (else 0)
+struct GJobPick { GJobKernel k; int nw, tile_windows, tiles, njt; unsigned grid; };
+
+// MSHGNN_GEN_TILE as documented: 0: k_gstep at 4 waves; 1: 8 waves, 128-window tiles; 2: 8 waves; 3: the widest k_gstep; 6: k_gstep4; 8 / 9: k_gstep5 at 8 / 4 waves.
+inline int parse_gen_tile(const char* e) {
+    if (!e || e[0] < '0' || e[0] > '9' || e[1] != 0) return -1;
+    const int v = e[0] - '0';
+    return (v <= 3 || v == 6 || v == 8 || v == 9) ? v : -1;
+}
+
+inline GJobPick pick_job_kernel(const GJobQuery& q) {
+    const bool forced = q.forced >= 0, quad = q.NCT % 4 == 0, pair = q.NCT % 2 == 0;
+    // bf16: 16 waves; on 128-window tiles (k_gstep5: the software pipeline of 8 waves; k_gstep4) once the batch has two of them -- half the weight stream per window, 250-258 / 252-314 us per layer launch
+    // against 285-292 / 303-357 on the 32-limb model; split arithmetic: k_gstep4 at 16 waves on 64-window tiles (720-740 / 673-766 us against 803-813 / 814-925
+    // for k_gstep at 8 waves, whose 16-wave form spills)
+    const int mode = forced ? q.forced : (q.split ? 8 : (q.B >= 256 ? 8 : 3));
+    // a workgroup of k_gstep / k_gstep4 covers nw / 4 column tiles of 128, one of k_gstep5 nw / 2 (each wave two 32-column slices)
+    auto pick = [&](GJobKernel k, int nw, int tile_windows, int col_tiles, bool by_pairs) {
+        GJobPick r{k, nw, tile_windows, (q.B + tile_windows - 1) / tile_windows, 0, 0u};
+        const int njt = q.n_jobs * r.tiles;
+        if (by_pairs) r.njt = njt;
+        // k_gstep5 at 4 waves: the column groups of a (job, tile) pair sit 8 workgroups apart, so the grid is padded to whole groups of 8 pairs
+        r.grid = nw == 4 && by_pairs ? (unsigned)((njt + 7) / 8) * 8 * (q.NCT / col_tiles) : (unsigned)q.n_jobs * r.tiles * (q.NCT / col_tiles);
+        return r;
+    };
+    auto variant = [](GJobKernel base, int step) { return static_cast<GJobKernel>(static_cast<int>(base) + step); };
+    const bool gs5 = mode == 8 || mode == 9;
+    // k_gstep5 at 4 waves (256 columns per workgroup, two workgroups per CU) when the launch has more (job, tile) pairs than CUs: half-size workgroups halve the
+    // launch's tail (1 032 pairs on 256 CUs: 209 -> 189 us; 1 024: equal; 256 pairs, a single round: 42 -> 46 us, so those keep 8 waves).  Same bits.  (=9 / =8 force one.)
+    const bool crowded = !forced && q.n_jobs * ((q.B + 127) / 128) > q.n_cu;
+    // 1. The raw-input (encoder) launch on k_gstep5<RAW>: bf16 arithmetic, every input tensor 16-byte aligned with a pitch of whole chunks, row offsets inside 32 bits
+    //    (raw_ok).  Widths that are a multiple of 256 but not of 512 (hidden = 256, 768: the reference's --hidden_size) only have the 4-wave form.
+    //    (all_raw: at most GS5_MAX_TERMS terms per job, compile_gen_plan.)
+    if (gs5 && !q.split && pair && q.all_raw && q.raw_ok)
+        return (!quad || mode == 9 || crowded) ? pick(GJobKernel::GSTEP5_RAW_4W, 4, 128, 2, true) : pick(GJobKernel::GSTEP5_RAW_8W, 8, 128, 4, true);
+    // 2. k_gstep5: k_gstep4's tile, software-pipelined, on the launches whose every term is one plain row -- at 4 waves (a forced 8 never: at hidden % 512 != 0 it leaves
+    //    those launches to k_gstep) ...
+    const bool plain5 = q.all_plain && q.max_terms <= GS5_MAX_TERMS;
+    if (plain5 && !q.split && pair && (mode == 9 || (mode == 8 && !forced && (!quad || crowded))))
+        return pick(variant(GJobKernel::GSTEP5_4W, q.any_mask), 4, 128, 2, true);
+    // 3. ... and at 8 waves; the split arithmetic on 96-window tiles
+    if (plain5 && gs5 && quad)
+        return q.split ? pick(variant(GJobKernel::GSTEP5_X3, q.any_mask), 8, 16 * GS5_MB_SPLIT, 4, false) : pick(variant(GJobKernel::GSTEP5_8W, q.any_mask), 8, 128, 4, false);
+    // 4. k_gstep4 on the other launches at hidden % 512 == 0: 16 waves on 128-window tiles; the split arithmetic the same kernel on 64-window tiles
+    //    (hidden = 256: the 8-wave form of k_gstep4 measured 1.51 against 1.47 ms/step for k_gstep on A1-C2, 8192 windows -- tools/time_h256.py; not dispatched)
+    if (mode >= 6 && quad) return q.split ? pick(GJobKernel::GSTEP4_X3, 16, 64, 4, false) : pick(GJobKernel::GSTEP4, 16, 128, 4, false);
+    // 5. k_gstep.  Windows per workgroup: a packed weight fragment (8 KB per wave and K chunk, from L2) is reused for every 16-window row block of the tile
+    //    output tile of a workgroup: 64 windows x (32 NW) columns.  The staged A tile is shared by all NW waves, so wider tiles re-read the
+    //    activations fewer times (hidden / (32 NW) column groups per row of jobs): measured at h=512, B=1024: layer_fwd bf16 515 / 354 / 296 us at
+    //    4 / 8 / 16 waves, split 870 / 799 / 1012 us (16 waves: 128 VGPRs, spills); 128-window tiles lose (fewer resident workgroups hide less
+    //    of the staging latency: 495 us at 8 waves, 389 us at 16 waves with 56 B of scratch)
+    const int nw = mode >= 3 ? (quad ? 16 : pair ? 8 : 4) : ((mode == 1 || mode == 2) && pair) ? 8 : 4;
+    const GJobKernel k = nw == 16 ? GJobKernel::GSTEP_16W : nw == 4 ? GJobKernel::GSTEP_4W : mode == 1 ? GJobKernel::GSTEP_8W_T128 : GJobKernel::GSTEP_8W;
+    return pick(variant(k, q.split ? 4 : 0), nw, k == GJobKernel::GSTEP_8W_T128 ? 128 : 64, nw / 4, false);
+}
+
+// k_ggradw<SPLIT, OS, NWV, NOMASK>: the plan's arithmetic, its super-unit size (su_os: 1 = 128 x 128, 2 = 256 x 256) and whether any P operand carries relu bits
+// (dhm: none does -- the NOMASK instantiations)
+enum class GGradwKernel : int { BF16_OS1, BF16_OS2, X3_OS1, X3_OS2, BF16_OS1_NOMASK, BF16_OS2_NOMASK, X3_OS1_NOMASK, X3_OS2_NOMASK, COUNT };
+inline GGradwKernel pick_gradw_kernel(bool split, int su_os, bool dhm) { return static_cast<GGradwKernel>((dhm ? 4 : 0) + (split ? 2 : 0) + (su_os == 2 ? 1 : 0)); }
 
 }  // namespace gen
 }  // namespace mshgnn

@@ -2,7 +2,8 @@
 //   * tools/gen_spec_tables.py dumps the slab tables of the BASELINE topologies through it -> mshgnn_spec_tables.inc (the compile-time programs of the
 //     specialised step kernels);
 //   * tests/test_plan_property.py drives it with hypothesis-generated topologies, also as an AddressSanitizer / UBSan build (`make asan-host`): the
-//     index tables every kernel trusts are bounds-checked here, on the CPU.
+//     index tables every kernel trusts are bounds-checked here, on the CPU;
+//   * tests/test_gen_pick.py asks it which kernel, grid and tiles a launch of the generic engine gets (pick_job_kernel, mshgnn_gen_plan.hpp).
 // Not part of the drop-in boundary (include/mshgnn.h): test / build infrastructure around mshgnn_plan.hpp and mshgnn_gen_plan.hpp.
 #include "mshgnn_plan.hpp"
 #include "mshgnn_gen_plan.hpp"
@@ -207,5 +208,22 @@ int mshgnn_hostplan_gen_tables(const mshgnn_desc* desc, int32_t* tables, int cap
     if (tables) std::memcpy(tables, gp.tables.data(), sizeof(int32_t) * std::min<size_t>(cap > 0 ? cap : 0, gp.tables.size()));
     return (int)gp.tables.size();
 }
+
+// The generic engine's kernel picks (mshgnn_gen_plan.hpp; tests/test_gen_pick.py), n queries a call.  A query is 11 ints: forced (the MSHGNN_GEN_TILE mode or -1), split,
+// NCT, n_jobs, all_raw, all_plain, any_mask, max_terms, B, n_cu, raw_ok; a pick 6: kernel (an index for mshgnn_hostplan_gen_kernel_name), waves, windows per tile,
+// tiles, (job, tile) pairs handed to the kernel, grid.
+void mshgnn_hostplan_gen_pick(const int32_t* query, int32_t* pick, int n) {
+    for (int i = 0; i < n; ++i, query += 11, pick += 6) {
+        gen::GJobQuery q;
+        q.forced = query[0]; q.split = query[1] != 0; q.NCT = query[2]; q.n_jobs = query[3]; q.all_raw = query[4] != 0; q.all_plain = query[5] != 0; q.any_mask = query[6] != 0;
+        q.max_terms = query[7]; q.B = query[8]; q.n_cu = query[9]; q.raw_ok = query[10] != 0;
+        const gen::GJobPick r = gen::pick_job_kernel(q);
+        pick[0] = (int)r.k; pick[1] = r.nw; pick[2] = r.tile_windows; pick[3] = r.tiles; pick[4] = r.njt; pick[5] = (int32_t)r.grid;
+    }
+}
+int mshgnn_hostplan_gen_kernel_count() { return (int)gen::GJobKernel::COUNT; }
+const char* mshgnn_hostplan_gen_kernel_name(int k) { return k >= 0 && k < (int)gen::GJobKernel::COUNT ? gen::GJOB_KERNEL_NAMES[k] : ""; }
+int mshgnn_hostplan_gen_tile_mode(const char* text) { return gen::parse_gen_tile(text); }      // what a value of MSHGNN_GEN_TILE forces (-1: nothing)
+int mshgnn_hostplan_gen_gradw_pick(int split, int su_os, int dhm) { return (int)gen::pick_gradw_kernel(split != 0, su_os, dhm != 0); }
 
 }  // extern "C"
