@@ -389,9 +389,11 @@ typedef struct mshgnn_window_desc {
     int32_t n_types, dtype, history, normalize;
     int32_t type_nodes[MSHGNN_MAX_TYPES], type_width[MSHGNN_MAX_TYPES];
     int32_t n_src, n_runs, n_rows;
-    int32_t fast_layout;      /* != 0: the caller states that the runs of every node row all have one length and follow each other from the row's first run's
-                               * feature on (what a recipe of T-long variables gives): with 16-byte aligned output rows and no standardisation the
-                               * gather then runs as one 16-byte store per output chunk (k_assemble_windows_fast)                              */
+    int32_t fast_layout;      /* != 0: the caller states that the runs of every node row all have one length and follow each other from FEATURE 0 on
+                               * (first feature of the row's first run == 0; what a recipe of T-long variables gives): with 16-byte aligned output
+                               * rows and no standardisation the gather then runs as one 16-byte store per output chunk (k_assemble_windows_fast),
+                               * which also zeroes the pad columns up to the end of a row's last chunk.  The tables live on the device: the
+                               * statement is not checked                                                                                      */
     const int32_t* runs;
     const int32_t* rows;
     int32_t n_label, label_src, label_rotate, quat_src;      /* quat_src = -1: none */

@@ -45,8 +45,9 @@ template <typename T, int NSET, bool ORBIT = false> __global__ __launch_bounds__
         if constexpr (NSET == 1) return __builtin_amdgcn_readlane(v[0], r);
         else return r < 64 ? __builtin_amdgcn_readlane(v[0], r & 63) : __builtin_amdgcn_readlane(v[NSET - 1], r & 63);
     };
-    // lane handles the element pairs (2 lane + 128 j, +1), j = 0, 1: one packed store per pair (runs start at even features
-    // and node rows are 16-byte aligned, so pairs are 4-byte (bf16) / 8-byte (fp32) aligned); lengths up to 256
+    // lane handles the element pairs (2 lane + 128 j, +1), j = 0, 1: one packed store per pair where the run's first destination element sits at an
+    // even ELEMENT ADDRESS and its length is even, so pairs are 4-byte (bf16) / 8-byte (fp32) aligned whatever the pitch, the batch index and the
+    // base pointer are (the entry point only asks for element-aligned rows); two scalar stores otherwise.  Uniform per run.  Lengths up to 256
     for (int row = wv; row < a.n_rows; row += 4) {
         const int r_begin = a.rows[2 * row], r_end = a.rows[2 * row + 1];
         for (int rb = r_begin; rb < r_end; rb += WIN_ROW_RUNS) {
@@ -81,7 +82,7 @@ template <typename T, int NSET, bool ORBIT = false> __global__ __launch_bounds__
 #pragma unroll
                     for (int q = 0; q < 4; ++q) v[i][q] = standardise_one(v[i][q], rs.mean, rs.sd);
                 }
-                const bool even = ((doff | len) & 1) == 0;
+                const bool even = ((((uintptr_t)dst / sizeof(T)) | (uintptr_t)len) & 1) == 0;
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
                     const int k = 2 * lane + 128 * j;
