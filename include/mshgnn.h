@@ -642,6 +642,35 @@ int mshgnn_mlp_backward(const mshgnn_mlp_plan* plan, const mshgnn_mlp_input* inp
 int mshgnn_mlp_step(const mshgnn_mlp_plan* plan, const mshgnn_mlp_input* input, int loss_kind, const void* targets, const float* params, float* out,
                     float* loss_out, float* grad_params, void* workspace, int64_t batch, void* stream);
 
+/* ---- symmetrisation over a group orbit (csrc/mshgnn_orbit.hip) -------------------------------------------------------------------------------------------
+ * f_sym(x) = 1/|G| sum_g rho_out(g)^-1 f(rho_in(g) x) makes any model exactly equivariant; the reference has no such layer (its symmetric models are
+ * equivariant by architecture, its other models are trained on the augmented ConcatDataset([ds, ds_gs, ...])).  An ORBIT-COMPLETE batch has K * windows rows in
+ * element-major order -- row e * windows + w is element e of base window w, the order of ConcatDataset -- K = n_elements in [1, MSHGNN_WINDOW_MAX_ELEMENTS].
+ * The OUTPUT ACTION of element e is a pair of HOST tables perm[e][k], sign[e][k] in {+1, -1} over n_units units (<= 64) of `width` consecutive floats
+ * (1 .. 16), meaning what a recipe's label tables mean: y_e[k] = sign[e][k] y[perm[e][k]].  Element 0 must be the identity with +1.  With
+ * out fp32 [K windows][n_units width] and pinv_e the inverse of perm[e]:
+ *   mshgnn_orbit_average:           avg[w][j width + s] = (t_0 + t_1 + ... + t_{K-1}) * fl32(1 / K),  t_e = out[e windows + w][pinv_e[j] width + s] with its sign
+ *                                   bit flipped when sign[e][pinv_e[j]] = -1: fp32 adds in element order starting from t_0, then the one multiply (K = 1
+ *                                   reproduces out bit for bit).
+ *   mshgnn_orbit_average_backward:  the exact transpose, grad_out[e windows + w][k width + s] = sign[e][k] (grad_avg[w][perm[e][k] width + s] * fl32(1 / K)).
+ *   mshgnn_orbit_defect:            per element e the differences d = t_e - out[w][.] (fp32, t_e as above) over all windows; an fp64 state double[K][4] =
+ *                                   {sum d^2, sum out_0^2, max |d|, count} is ADDED TO (max: maxed into) `state` -- a sweep accumulates, the caller zeroes;
+ *                                   row 0 gets zeros for sum d^2 and max |d|.  One workgroup per element, every thread adds its elements in index order, then
+ *                                   a fixed tree: bit-reproducible, no floating-point atomic.
+ * One launch each on `stream`, nothing allocated, nothing read back: the call validates the tables and packs them into a by-value kernel argument (576 bytes),
+ * so there are no device tables and a captured graph holds them.  One thread per output element, 16-byte stores where n_units width % 4 == 0 and both pointers
+ * are 16-byte aligned (16-byte loads too where width % 4 == 0), element-wise otherwise -- the same bits; grid-stride loops with 64-bit indices: any `windows`.
+ * MSHGNN_EINVAL with nothing launched: a null pointer, n_elements outside [1, 8], n_units outside [1, 64], width outside [1, 16], windows < 1, a row of
+ * perm that is no permutation of [0, n_units), a sign other than +-1, element 0 not the identity with +1, windows * n_elements * 2^10 beyond the 64-bit element
+ * index, a `state` that is not 8-byte aligned.
+ * morphsym_hgnn_amd/symmetrise.py: OutputAction, orbit_average, EquivarianceDefect, Symmetrised.                                                              */
+int mshgnn_orbit_average(const int32_t* perm, const int32_t* sign, int32_t n_elements, int32_t n_units, int32_t width, const float* out, int64_t windows,
+                         float* avg, void* stream);
+int mshgnn_orbit_average_backward(const int32_t* perm, const int32_t* sign, int32_t n_elements, int32_t n_units, int32_t width, const float* grad_avg,
+                                  int64_t windows, float* grad_out, void* stream);
+int mshgnn_orbit_defect(const int32_t* perm, const int32_t* sign, int32_t n_elements, int32_t n_units, int32_t width, const float* out, int64_t windows,
+                        double* state, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -111,6 +111,7 @@ EXPORTS = [
     "mshgnn_sgd_step", "mshgnn_adamw_step", "mshgnn_grad_norm_scratch_bytes", "mshgnn_grad_norm", "mshgnn_grad_clip",
     "mshgnn_mlp_compile_host", "mshgnn_mlp_create", "mshgnn_mlp_destroy", "mshgnn_mlp_info_get", "mshgnn_mlp_workspace_bytes", "mshgnn_mlp_stash_offset",
     "mshgnn_mlp_forward", "mshgnn_mlp_backward", "mshgnn_mlp_step",
+    "mshgnn_orbit_average", "mshgnn_orbit_average_backward", "mshgnn_orbit_defect",
 ]
 ABI_VERSION = 6      # include/mshgnn.h MSHGNN_ABI_VERSION: the ctypes structures above mirror THAT header
 
@@ -242,6 +243,12 @@ def load_library():
     lib.mshgnn_mlp_backward.argtypes = [C.c_void_p, C.POINTER(MshgnnMlpInput), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     lib.mshgnn_mlp_step.argtypes = [C.c_void_p, C.POINTER(MshgnnMlpInput), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_int64, C.c_void_p]
+    # symmetrisation over a group orbit (csrc/mshgnn_orbit.hip): host tables, plain arguments
+    if hasattr(lib, "mshgnn_orbit_average"):      # (absent from older builds of the library handed over through MSHGNN_LIB for A/B runs)
+        orbit9 = [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        lib.mshgnn_orbit_average.argtypes = list(orbit9)
+        lib.mshgnn_orbit_average_backward.argtypes = list(orbit9)
+        lib.mshgnn_orbit_defect.argtypes = list(orbit9)
     lib.mshgnn_struct_size.restype = C.c_size_t
     lib.mshgnn_struct_size.argtypes = [C.c_int]
     lib.mshgnn_comm_unique_id.argtypes = [C.c_char_p, C.c_void_p]

@@ -408,6 +408,7 @@ class SequenceStore:
             self.n_elements = 1
             all_runs, all_lab = runs, lab
         self.operators = [None]      # (`orbit` names its elements)
+        self.element_recipes = list(elements) if elements is not None else [recipe]      # (symmetrise.OutputAction.from_store reads the elements' label tables)
         self.runs = torch.tensor(all_runs, dtype=torch.int32, device=self.device)
         self.rows = torch.tensor(rows, dtype=torch.int32, device=self.device)
         self.label_cols = torch.tensor(all_lab, dtype=torch.int32, device=self.device)
@@ -484,6 +485,25 @@ class SequenceStore:
         elif self.n_elements <= 1:
             raise ValueError("this store has one group element: device `elements` belong to an `orbit` store")
         return rows | (el << ELEMENT_SHIFT)
+
+    def orbit_batch(self, rows, edge_index_dict) -> "WindowBatch":
+        """The ORBIT-COMPLETE batch of the base windows `rows` of an `orbit` store: K * len(rows) windows in element-major order, window e * B + w = element e
+        of base window rows[w] -- the order of `orbit_index_split` / ConcatDataset([ds, ds_gs, ...]) and what `symmetrise.orbit_average` takes.  rows: start
+        rows, a host sequence / tensor (checked here) or a device int64 tensor (trusted, as in `WindowBatch`); the starts are packed on the device with
+        torch integer ops on the current stream: capturable like `pack_starts`."""
+        K = self.n_elements
+        if K < 2:
+            raise ValueError("orbit_batch needs an `orbit` store (this store has one group element)")
+        st = rows if isinstance(rows, torch.Tensor) else torch.as_tensor(np.asarray(rows), dtype=torch.int64)
+        st = st.flatten().to(torch.int64)
+        if st.numel() < 1:
+            raise ValueError("no window indices")
+        if not st.is_cuda:
+            if int(st.min()) < 0 or int(st.max()) + self.recipe.history > self.n_rows:
+                raise IndexError("window index out of range")
+            st = st.to(self.device)
+        el = torch.arange(K, dtype=torch.int64, device=st.device).repeat_interleave(st.numel())
+        return WindowBatch(self, (st & ROW_MASK).repeat(K) | (el << ELEMENT_SHIFT), edge_index_dict)
 
     def __len__(self) -> int:
         """Number of windows (the reference's dataset length: rows - history + 1)."""
@@ -896,6 +916,25 @@ class DatasetView:
         ix = indices if isinstance(indices, torch.Tensor) else torch.as_tensor(np.asarray(indices), dtype=torch.int64)
         wb.indices = ix.reshape(-1).to(st.device, torch.int64)
         return wb
+
+    def orbit_batch(self, indices, edge_index_dict) -> WindowBatch:
+        """The ORBIT-COMPLETE batch (`SequenceStore.orbit_batch`) of the BASE windows `indices` in [0, n_windows) of a view of an `orbit` dataset: the view's
+        indices e * n_windows + indices[w], element-major, through `batch`.  Host indices are checked here; a device index outside [0, n_windows) reaches
+        the mapping kernel as -1 under every element (row 0, element 0, the `bad` word is set)."""
+        K, n = self.n_elements, self.n_windows
+        if K < 2:
+            raise ValueError("orbit_batch needs a view of an `orbit` dataset (this dataset has one group element)")
+        ix = indices if isinstance(indices, torch.Tensor) else torch.as_tensor(np.asarray(indices), dtype=torch.int64)
+        ix = ix.reshape(-1).to(torch.int64)
+        if ix.numel() < 1:
+            raise ValueError("no window indices")
+        if not ix.is_cuda:
+            if int(ix.min()) < 0 or int(ix.max()) >= n:
+                raise IndexError(f"base window index out of range [0, {n})")
+            ix = ix.to(self.dataset.device)
+        off = torch.arange(K, dtype=torch.int64, device=ix.device).repeat_interleave(ix.numel()) * n
+        rep = ix.repeat(K)
+        return self.batch(torch.where((rep >= 0) & (rep < n), rep + off, torch.full_like(rep, -1)), edge_index_dict)
 
     def epoch(self, batch_size: int, generator: Optional[torch.Generator] = None, shuffle: bool = True, drop_last: bool = False):
         """Device index tensors of one pass over the view: ONE torch.randperm per epoch (on the device; with a host generator it is drawn on the host

@@ -765,16 +765,9 @@ class GraphedTrainingStep:
         return self.loss
 
 
-def _evaluation_sweep(wrapper, store, edge_index_dict, batch_size: int, stride: int, per_batch=None, test_only_on_z: bool = False):
-    """The loop `evaluate_sequence` and `evaluate_table` share: (predictions in index order, the view swept or None).  per_batch(lo, batch, y, y_pred) runs
-    after the wrapper's own metrics of every batch; lo: the batch's position in the swept indices 0, stride, 2 stride, ..."""
-    if batch_size < 1 or stride < 1:
-        raise ValueError("batch_size and stride must be >= 1")
-    from .windows import DatasetView, ResidentDataset
-    view = store.view() if isinstance(store, ResidentDataset) else store if isinstance(store, DatasetView) else None
-    if view is not None:
-        store = view.dataset
-    starts = torch.arange(0, len(view if view is not None else store), stride, dtype=torch.int64, device=store.device)      # (a view: its indices)
+def tiled_edges(store, edge_index_dict):
+    """batch size -> edge_index_dict for the sweeps over a store (`evaluate_sequence`, `evaluate_table`, `symmetrise.evaluate_sequence_symmetrised`): the edges of ONE
+    window tiled per batch size (made once per size), or the caller's own callable batch size -> edge_index_dict."""
     r = store.recipe
     edges = {}
 
@@ -789,6 +782,20 @@ def _evaluation_sweep(wrapper, store, edge_index_dict, batch_size: int, stride: 
                     off = torch.stack([torch.arange(B, device=store.device) * r.num_nodes[et[0]], torch.arange(B, device=store.device) * r.num_nodes[et[2]]])
                     edges[B][et] = (ei[:, None, :] + off[:, :, None]).reshape(2, -1)
         return edges[B]
+    return edges_for
+
+
+def _evaluation_sweep(wrapper, store, edge_index_dict, batch_size: int, stride: int, per_batch=None, test_only_on_z: bool = False):
+    """The loop `evaluate_sequence` and `evaluate_table` share: (predictions in index order, the view swept or None).  per_batch(lo, batch, y, y_pred) runs
+    after the wrapper's own metrics of every batch; lo: the batch's position in the swept indices 0, stride, 2 stride, ..."""
+    if batch_size < 1 or stride < 1:
+        raise ValueError("batch_size and stride must be >= 1")
+    from .windows import DatasetView, ResidentDataset
+    view = store.view() if isinstance(store, ResidentDataset) else store if isinstance(store, DatasetView) else None
+    if view is not None:
+        store = view.dataset
+    starts = torch.arange(0, len(view if view is not None else store), stride, dtype=torch.int64, device=store.device)      # (a view: its indices)
+    edges_for = tiled_edges(store, edge_index_dict)
 
     preds = []
     with torch.no_grad():
