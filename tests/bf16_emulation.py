@@ -6,7 +6,7 @@ With quant=False it must reproduce the oracle to ~1e-13 (tests/test_bf16_emulati
 restructuring; with quant=True it is what the bf16 HIP path must match up to fp32-accumulation effects."""
 import torch
 
-from morphsym_hgnn_amd.spec import rel_key
+from morphsym_hgnn_amd.spec import rel_key, relation_aggr
 
 
 class _Q(torch.autograd.Function):
@@ -48,9 +48,15 @@ def emulate_step(spec, params, x_dict, y, B, quant=True, loss_grad=None):
             H = X[t] @ qw(w_root).t() + b_sum
             for et in rels:
                 w = qw(P[f"convs.{l}.convs.{rel_key(et)}.lin_rel.weight"])
-                for (j, i) in spec.topology.edges(et):
+                edges = spec.topology.edges(et)
+                deg = {}
+                for (_, i) in edges:
+                    deg[i] = deg.get(i, 0) + 1
+                for (j, i) in edges:
                     upd = torch.zeros_like(H)
                     upd[:, i, :] = X[et[0]][:, j, :] @ w.t()
+                    if relation_aggr(spec.kind, et) == "mean" and deg[i] != 1:      # (the generic-width engine's 1 / in-degree; every robot's degree is 1)
+                        upd = upd / deg[i]
                     H = H + upd
             if spec.has_base_transform and t == "base":
                 hb = q(H)

@@ -22,7 +22,7 @@ import math
 import numpy as np
 import torch
 
-from morphsym_hgnn_amd.spec import rel_key
+from morphsym_hgnn_amd.spec import rel_key, relation_aggr
 from oracle import ms_hgnn_oracle as orc
 from tests import helpers
 from tests.bf16_emulation import emulate_step
@@ -46,8 +46,13 @@ def _signed_rows(g, out_f, in_f, scales, density=1.0):
 
 
 def exact_case(spec, B, seed, x_range=2, bias_range=(-1, 1), rel_scales=(0.5, 1.0), density=1.0, per_matrix=False, gout_range=2, mse=None,
-               enc_cover=False):
+               enc_cover=False, thin=None, gain=None):
     """Rounding-free inputs, parameters and output gradient for `spec` at batch size B.
+    thin: {destination type: row density} for the lin_rel weights of every relation INTO that type (the other matrices keep `density`): a sum over the
+    many in-edges of one node (the base of a many-limb robot) then reaches only that share of the destination's features, and what it feeds back into
+    its sources stays within bf16's 8 significant bits over the layers.
+    gain: {relation name: power of two} multiplying the lin_rel weights of the relations of that name: a 'mean' relation over in-degrees up to 4 with gain 4
+    hands its destination whole numbers (W . mean = 4 . sum / degree), where quarters would use up two of bf16's bits in every layer that follows.
     enc_cover: dense encoder columns over zero inputs (`_cover_encoder_tiles`) -- with one entry per row, the few features that carry dY_enc reach only
     a few input columns, and the input gradient of a 900-wide input would be zero in most of its column tiles.
     Returns a dict: x (reference convention, fp64 [B*n_t, F_t]), params, gout (fp64 [B*n_out*d], k * 2^-14), and for the one-call MSE step (mse=True, default
@@ -55,13 +60,19 @@ def exact_case(spec, B, seed, x_range=2, bias_range=(-1, 1), rel_scales=(0.5, 1.
     every element a short dyadic number (`_mse_targets`)."""
     g = torch.Generator().manual_seed(seed)
     params = {}
+    thinned = {f"convs.{l}.convs.{rel_key(et)}.lin_rel.weight": d for et in spec.edge_types for l in range(spec.num_layers)
+               for t, d in (thin or {}).items() if et[2] == t}
     for name, shape in spec.param_shapes().items():
         if len(shape) == 2:
             rel = ".lin_rel." in name or ".lin_root." in name
             sc = (rel_scales[int(torch.randint(0, len(rel_scales), (1,), generator=g))],) if (rel and per_matrix) else (rel_scales if rel else (1.0,))
-            params[name] = _signed_rows(g, shape[0], shape[1], sc, 1.0 if name.startswith(("encoder.", "decoder.")) else density)
+            params[name] = _signed_rows(g, shape[0], shape[1], sc, 1.0 if name.startswith(("encoder.", "decoder.")) else thinned.get(name, density))
         else:
             params[name] = torch.randint(bias_range[0], bias_range[1] + 1, shape, generator=g).double()
+    for et in spec.edge_types:
+        if et[1] in (gain or {}):
+            for l in range(spec.num_layers):
+                params[f"convs.{l}.convs.{rel_key(et)}.lin_rel.weight"] *= float(gain[et[1]])
     x = {t: torch.randint(-x_range, x_range + 1, (B * spec.num_nodes[t], spec.widths[t]), generator=g).double() for t in spec.node_types}
     if enc_cover:
         _cover_encoder_tiles(spec, params, x, seed)
@@ -190,7 +201,11 @@ def _kernel_algebra(spec, P, x_dict, B, relu_masks=None, reseed=None):
                 if not e:
                     continue
                 js = torch.tensor([j for j, _ in e]); is_ = torch.tensor([i for _, i in e])
-                H = H.index_add(1, is_, X[et[0]][:, js, :] @ P[f"convs.{l}.convs.{rel_key(et)}.lin_rel.weight"].t())
+                msg = X[et[0]][:, js, :] @ P[f"convs.{l}.convs.{rel_key(et)}.lin_rel.weight"].t()
+                sc = mean_scales(spec, et)
+                if sc is not None:      # ('mean' over an in-degree above 1: the generic engine's 1 / in-degree, per edge)
+                    msg = msg * torch.tensor(sc, dtype=msg.dtype).view(1, -1, 1)
+                H = H.index_add(1, is_, msg)
             H = keep(f"H{l}.{t}", H)
             if spec.has_base_transform and t == "base":
                 t1 = keep(f"T1pre{l}", H @ P["base_transform.0.weight"].t() + P["base_transform.0.bias"])
@@ -205,6 +220,45 @@ def _kernel_algebra(spec, P, x_dict, B, relu_masks=None, reseed=None):
     out = X[spec.out_type] @ P["decoder.weight"].t() + P["decoder.bias"]
     out = (out * spec.output_mask().unsqueeze(0)).reshape(-1)
     return out, inter, masks, zeros
+
+
+def mean_scales(spec, et):
+    """Per edge of relation `et` the 1 / in-degree of its destination (repeated edges counted as often as they are listed, as PyG's mean does), or None
+    where every scale is 1: an 'add' relation, or a 'mean' one whose destinations all have in-degree 1 (every robot of the reference)."""
+    if relation_aggr(spec.kind, et) != "mean":
+        return None
+    e = spec.topology.edges(et)
+    deg = {}
+    for _, i in e:
+        deg[i] = deg.get(i, 0) + 1
+    sc = [1.0 / deg[i] for _, i in e]
+    return sc if any(v != 1.0 for v in sc) else None
+
+
+def aggregates_not_bf16(spec, inter, B):
+    """The generic-width engine stages a relation's aggregate (the sum or mean of a destination's source rows, and in the backward pass of the dH rows of a
+    source's destinations) as ONE bf16 operand row in front of the product, where the LDS-resident kernels add the products in fp32.  Names of the aggregates
+    of live destinations that are not bf16 values (empty: the engine rounds nothing there either).  `inter`: the intermediates of `_kernel_algebra` after
+    its backward."""
+    live, _ = spec.node_liveness()
+    bad = []
+    for l in range(spec.num_layers):
+        for et in spec.edge_types:
+            e = spec.topology.edges(et)
+            if not e or f"H{l}.{et[2]}" not in inter:
+                continue
+            sc = mean_scales(spec, et) or [1.0] * len(e)
+            Xs, dH = inter[f"X{l}.{et[0]}"].detach(), inter[f"H{l}.{et[2]}"].grad
+            fwd, bwd = {}, {}
+            for (j, i), s in zip(e, sc):
+                if i not in live[l][et[2]]:
+                    continue
+                fwd[i] = fwd.get(i, 0) + s * Xs[:, j]
+                if dH is not None:
+                    bwd[j] = bwd.get(j, 0) + s * dH[:, i]
+            bad += [f"sum of X{l}.{et[0]} rows into {et[2]} node {i} ({rel_key(et)})" for i, v in fwd.items() if not bf16_exact(v)]
+            bad += [f"sum of dH{l}.{et[2]} rows into {et[0]} node {j} ({rel_key(et)})" for j, v in bwd.items() if not bf16_exact(v)]
+    return bad
 
 
 class _Reseed(torch.autograd.Function):
@@ -305,6 +359,7 @@ def check_exact(spec, case, gout=None, stats=None, input_grads=False):
             assert bf16_exact(v), f"(a) activation {name} is not a bf16 value"
         if v.grad is not None:
             assert bf16_exact(v.grad), f"(a) activation gradient d{name} is not a bf16 value"
+    stats["aggregates_not_bf16"] = aggregates_not_bf16(spec, inter, B)      # (asserted empty by the generic engine's cases: tests/test_exact_data.py)
     # (b) fp32 closure
     acts = [case["x"][t] for t in spec.node_types] + [v for v in inter.values()]
     weights = [v for k, v in case["params"].items() if v.dim() == 2] + [v for k, v in inter.items() if k.startswith("wroot")]

@@ -33,6 +33,55 @@ def make_spec(kind, topo_name, cfg_name, hidden, layers, regression=True, grf=3)
                      regression=regression, grf_dimension=grf, group=group)
 
 
+NARROW_WIDTHS = {"base": 24, "joint": 9, "foot": 5}      # (MI inputs of 3 time steps: the host oracle stays cheap at any hidden width)
+
+
+def make_limbs_spec(limbs, hidden, layers):
+    """MI-HGNN (no symmetry group, one output per foot) on the synthetic robot of `limbs` three-joint limbs, at the reference's input widths: 1 base
+    node, the destination of `limbs` hip-joint rows -- live, as a destination of layer 0, from 5 layers on."""
+    return ModelSpec(kind="mi", topology=topology.synthetic_limbs(limbs), hidden=hidden, num_layers=layers, widths=synth.feature_widths("mi", True),
+                     regression=True, grf_dimension=1)
+
+
+def random_topology(seed, nb, nj, nf):
+    """A topology no robot has: random edge lists over the five relation types of the MI graph -- repeated edges, nodes without in-edges, in-degrees up to
+    the node count, one relation left empty (never the one into the decoder's type: a signal path stays)."""
+    import random
+    rng = random.Random(seed)
+    n = {"base": nb, "joint": nj, "foot": nf}
+    rels = []
+    for k, (s_, d_) in enumerate((("base", "joint"), ("joint", "base"), ("joint", "joint"), ("foot", "joint"), ("joint", "foot"))):
+        ne = 0 if (k == seed % 5 and k != 4) else rng.randint(1, 2 * max(n[s_], n[d_]))
+        pairs = [[rng.randrange(n[s_]), rng.randrange(n[d_])] for _ in range(ne)]
+        if pairs and rng.random() < 0.7:
+            pairs.append(list(pairs[0]))                      # a repeated edge: PyG sums it twice
+        rels.append(((s_, "connect", d_), pairs))
+    return topology.RobotTopology(name=f"random{seed}", num_nodes=n, relations=rels)
+
+
+def make_random_topology_spec(seed, nb, nj, nf, hidden, layers):
+    """MI-HGNN over `random_topology`, narrow inputs (the model of tests/test_generic_gpu.py's test_random_topologies_match_the_oracle)."""
+    return ModelSpec(kind="mi", topology=random_topology(seed, nb, nj, nf), hidden=hidden, num_layers=layers, widths=dict(NARROW_WIDTHS), regression=True,
+                     grf_dimension=1, group=None, num_timesteps=3)
+
+
+MEAN_DEGREE_EDGES = [[1, 0], [2, 0], [0, 1], [2, 1], [3, 1], [0, 1], [1, 2], [0, 3], [2, 3]]      # in-degrees 2, 4 (one edge repeated), 1, 2
+
+
+def make_mean_degree_spec(layers, regression, hidden=128):
+    """MiniCheetah-K4 with its base -> base 'gt' relation (mean aggregation) given in-degrees 2, 4, 1 and 2 (tests/test_generic_gpu.py's
+    test_mean_aggregation_with_in_degree_above_one, its edge list changed to power-of-two degrees: 1 / in-degree is then exact).  The LDS-resident kernels
+    reject such a relation; the generic-width engine takes it at every hidden width."""
+    topo = topology.mini_cheetah_k4()
+    rel = dict(topo.relations)
+    assert ("base", "gt", "base") in rel
+    rel[("base", "gt", "base")] = [list(e) for e in MEAN_DEGREE_EDGES]
+    topo.relations = [(k, rel[k]) for k, _ in topo.relations]
+    group, _ = load_group("mini_cheetah-k4")
+    return ModelSpec(kind="k4", topology=topo, hidden=hidden, num_layers=layers, widths=synth.feature_widths("k4", regression), regression=regression,
+                     grf_dimension=1, group=group)
+
+
 def load_case(name):
     fx = np.load(os.path.join(GOLDEN, name + ".npz"))
     case = json.loads(str(fx["config"]))

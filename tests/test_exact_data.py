@@ -1,13 +1,17 @@
 """The rounding-free data of tests/test_exact_gpu.py, tests/test_exact_families_gpu.py and tests/test_input_grad_exact_gpu.py, checked on the host: for
 every (model, batch size) the GPU files use, check_exact proves bf16 closure, fp32 closure and coverage (tests/exact_data.py), for the last file also
 input-gradient closure and coverage; the families' cases have the live base nodes their names claim, with non-zero gradients on the base paths -- and the
-comparison the GPU files rely on flags a single-ulp change, and a single wrong element of a base row or of a base-path gradient."""
+comparison the GPU files rely on flags a single-ulp change, and a single wrong element of a base row or of a base-path gradient.
+For tests/test_exact_generic_gpu.py (the generic-width engine) also: every aggregate the engine stages as one operand row is a bf16 value, the base node of
+a many-limb model is a live destination of as many rows as its name says, the random topologies hold a repeated edge, an empty relation and a node without
+in-edges -- and the comparison flags one dropped row of a long sum, a repeated edge counted once and a mean scaled by the wrong degree."""
 import pytest
 import torch
 
 from tests import exact_data as xd
 from tests import helpers
 from tests import test_exact_families_gpu as fam
+from tests import test_exact_generic_gpu as gen
 from tests import test_exact_gpu as gx
 from tests import test_input_grad_exact_gpu as igx
 from tests import ops_reference as opr
@@ -110,6 +114,164 @@ def test_comparison_flags_one_element_of_the_base_destination_path(model):
     flat[offs[key][0] + i] = -flat[offs[key][0] + i]
     gx._compare_grads(bad, "negated", spec, flat, ref)
     assert len(bad) == 1 and f"grad {key}:" in bad[0] and "1 of " in bad[0], bad
+
+
+# ---------------------------------------------------------------------------------------------------
+# the generic-width engine's cases (tests/test_exact_generic_gpu.py)
+# ---------------------------------------------------------------------------------------------------
+def _edges_into(spec, t):
+    return [(et, j, i) for et in spec.edge_types if et[2] == t for j, i in spec.topology.edges(et)]
+
+
+@pytest.mark.parametrize("model,B", gen.CASES)
+def test_generic_engine_case_is_rounding_free_and_covering(model, B):
+    """(a)-(c) for every (model, batch, seed) of tests/test_exact_generic_gpu.py; and what check_exact does not ask of the LDS-resident kernels' cases: the
+    generic engine stages a relation's aggregate (forward: the sum or mean of a destination's source rows; backward: of a source's destinations' dH rows)
+    as one operand row in the plan's storage, so every such sum of a live destination must itself be a bf16 value."""
+    spec, case, ref, stats = gx._reference.__wrapped__(model, B)
+    assert stats["nonzero_gout"] > 0 and stats["zero_decisions"] > 0
+    assert stats["fwd_sum_bound"] <= 1.0 and stats["bwd_sum_bound"] <= 1.0
+    assert stats["aggregates_not_bf16"] == [], stats["aggregates_not_bf16"][:5]
+    if spec.regression:
+        assert float(((ref["out"] - case["y"]) ** 2).mean()) == ref["loss"]
+    if model in gen.LIMBS:      # the base node is a live destination of as many rows as the name says, and the paths through it carry gradient
+        live, need = spec.node_liveness()
+        assert live[0]["base"] == [0] and need[0]["base"] == [0], model
+        into = _edges_into(spec, "base")
+        assert len(into) == gen.LIMBS[model] and len({j for _, j, _ in into}) == gen.LIMBS[model] and {et for et, _, _ in into} == {("joint", "connect", "base")}
+        assert len([1 for et in spec.edge_types if et[0] == "base" for j, _ in spec.topology.edges(et)]) == gen.LIMBS[model]      # (the backward sum's rows)
+        for k in ("convs.0.convs.<joint___connect___base>.lin_rel.weight", "convs.1.convs.<base___connect___joint>.lin_rel.weight", "encoder.lins.base.weight"):
+            assert float(ref["grads"][k].abs().max()) > 0, f"{model}: {k} has a zero gradient"
+
+
+def test_random_topology_cases_hold_what_no_robot_has():
+    """Between them the random topologies of the GPU file have a repeated edge INTO A LIVE NODE (one the plan computes: a repeated edge elsewhere changes
+    nothing that is compared), an empty relation, and a live node without in-edges."""
+    seen = set()
+    for model, B in gen.RANDOM_CASES:
+        spec = gx._spec(model)
+        live, _ = spec.node_liveness()
+        for et in spec.edge_types:
+            e = [tuple(p) for p in spec.topology.edges(et)]
+            if not e:
+                seen.add("an empty relation")
+            if any(e.count(p) > 1 and any(p[1] in live[l][et[2]] for l in range(spec.num_layers)) for p in e):
+                seen.add("a repeated edge into a live node")
+        for t in spec.node_types:
+            fed = {i for _, _, i in _edges_into(spec, t)}
+            if any(set(live[l][t]) - fed for l in range(spec.num_layers)):
+                seen.add("a live node without in-edges")
+    assert seen == {"an empty relation", "a repeated edge into a live node", "a live node without in-edges"}, seen
+
+
+class _Stash:      # (an engine whose stash holds given hidden states)
+    def __init__(self, hidden):
+        self.hidden = hidden
+
+    def hidden_state(self, B, l):
+        return self.hidden[l]
+
+
+def _flagged(spec, ref, B, got):
+    """What the GPU files' comparisons report when `got` (a reference of another model: out, hidden, grads) stands in for an engine's results."""
+    bad_h, bad_g = [], []
+    gx._compare_hidden(bad_h, "got", _Stash([h.double() for h in got["hidden"]]), spec, ref, B, range(spec.num_layers + 1))
+    offs = spec.param_offsets()
+    flat = torch.zeros(spec.flat_size(), dtype=torch.float64)
+    for k, (off, n) in offs.items():
+        flat[off:off + n] = got["grads"][k].reshape(-1)
+    gx._compare_grads(bad_g, "got", spec, flat, ref)
+    return bad_h, bad_g
+
+
+def _without_edge(spec, et, pair):
+    """`spec` with one occurrence of edge `pair` of relation `et` removed."""
+    import copy
+    import dataclasses
+    topo = copy.deepcopy(spec.topology)
+    rels = []
+    for k, e in topo.relations:
+        e = [list(p) for p in e]
+        if k == tuple(et):
+            e.remove(list(pair))
+        rels.append((k, e))
+    topo.relations = rels
+    return dataclasses.replace(spec, topology=topo)
+
+
+@pytest.mark.parametrize("model,B", sorted({("limbs8_h128_L5", 17)} | {(m, B) for m, B, _, _ in gen.MANY_ROW_CASES}))
+def test_comparison_flags_one_dropped_row_of_the_sum_into_the_base(model, B):
+    """The oracle evaluated with ONE of the in-edges into the base node removed -- what an aggregate that drops a row computes -- against the true
+    reference, through the comparisons of the GPU files: a hidden state (X1[base], which that sum feeds) and at least one gradient differ in bits.
+    (The reference compared with itself is clean.)"""
+    spec, case, ref, _ = gx._reference.__wrapped__(model, B)
+    assert _flagged(spec, ref, B, ref) == ([], [])
+    et, j, i = _edges_into(spec, "base")[-1]
+    got = xd.reference(_without_edge(spec, et, (j, i)), case, ref["gout"])
+    bad_h, bad_g = _flagged(spec, ref, B, got)
+    assert any("X1[base]" in b for b in bad_h) and bad_g, (bad_h[:3], bad_g[:3])
+
+
+def test_comparison_flags_a_repeated_edge_counted_once():
+    """The same for a repeated edge into a live node of a random topology, counted once (PyG sums it twice)."""
+    done = 0
+    for model, B in gen.RANDOM_CASES:
+        spec, case, ref, _ = gx._reference.__wrapped__(model, B)
+        live, _ = spec.node_liveness()
+        for et in spec.edge_types:
+            e = [tuple(p) for p in spec.topology.edges(et)]
+            rep = [p for p in e if e.count(p) > 1 and p[1] in live[0][et[2]]]
+            if not rep:
+                continue
+            got = xd.reference(_without_edge(spec, et, rep[0]), case, ref["gout"])
+            bad_h, bad_g = _flagged(spec, ref, B, got)
+            assert any(f"X1[{et[2]}]" in b for b in bad_h) and bad_g, (model, et, bad_h[:3], bad_g[:3])
+            done += 1
+    assert done > 0
+
+
+def _algebra_reference(spec, case, gout):
+    """out, hidden states and parameter gradients of the kernels' algebra (exact_data._kernel_algebra: the oracle's bits, check_exact (a)) in the layout
+    of xd.reference."""
+    B = case["B"]
+    P = {k: v.clone().requires_grad_(True) for k, v in case["params"].items()}
+    out, inter, _, _ = xd._kernel_algebra(spec, P, case["x"], B)
+    out.backward(gout)
+    X = {t: inter[f"X0.{t}"].detach() for t in spec.node_types}
+    hidden = [torch.cat([X[t] for t in spec.node_types], dim=1)]
+    for l in range(spec.num_layers):
+        X = {t: (inter[f"X{l + 1}.{t}"].detach() if f"X{l + 1}.{t}" in inter else X[t]) for t in spec.node_types}
+        hidden.append(torch.cat([X[t] for t in spec.node_types], dim=1))
+    return {"out": out.detach(), "hidden": hidden, "grads": {k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in P.items()}}
+
+
+@pytest.mark.parametrize("model,B", gen.MEAN_CASES)
+def test_comparison_flags_a_mean_scaled_by_the_wrong_degree(monkeypatch, model, B):
+    """The 'mean' case has live destinations of in-degree 1, 2 and 4 (one edge repeated) on its mean relation -- and the kernels' algebra with the
+    in-degree-4 node scaled by 1 / 2 instead of 1 / 4 differs from the reference in a hidden state (X1[base]) and in at least one gradient, where
+    with the true scales it is the reference's bits."""
+    spec, case, ref, _ = gx._reference.__wrapped__(model, B)
+    et = ("base", "gt", "base")
+    live, _ = spec.node_liveness()
+    deg = {}
+    for _, i in spec.topology.edges(et):
+        deg[i] = deg.get(i, 0) + 1
+    e = [tuple(p) for p in spec.topology.edges(et)]
+    assert sorted(deg[i] for i in live[0]["base"]) == [1, 2, 2, 4] and any(e.count(p) > 1 for p in e)
+    assert xd.mean_scales(spec, et) is not None and {xd.mean_scales(spec, k) is None for k in spec.edge_types if k != et} == {True}
+    assert _flagged(spec, ref, B, _algebra_reference(spec, case, ref["gout"])) == ([], [])
+    true = xd.mean_scales
+    monkeypatch.setattr(xd, "mean_scales", lambda s, k: None if true(s, k) is None else [0.5 if v == 0.25 else v for v in true(s, k)])
+    bad_h, bad_g = _flagged(spec, ref, B, _algebra_reference(spec, case, ref["gout"]))
+    assert any("X1[base]" in b for b in bad_h) and bad_g, (bad_h[:3], bad_g[:3])
+
+
+def test_mean_scale_leaves_the_in_degree_one_cases_alone():
+    """Every 'mean' relation of the reference's robots has in-degree 1: no scale is applied (the emulation and the algebra are what they were)."""
+    for name in ("a1c2_L3", "mck4_cls_L3"):
+        spec = gx._spec(name)
+        assert any(xd.relation_aggr(spec.kind, et) == "mean" for et in spec.edge_types)
+        assert all(xd.mean_scales(spec, et) is None for et in spec.edge_types)
 
 
 def test_check_exact_refuses_a_rounding_case():

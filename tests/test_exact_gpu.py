@@ -25,6 +25,7 @@ Matrix of tests/test_exact_families_gpu.py (this file's table, comparisons and r
   * MiniCheetah-C2 classification at 4 layers, MiniCheetah-K4 classification at 5 layers, MiniCheetah-K4 regression at 3 layers.
   * MI-HGNN at 5 layers (no symmetry group); Solo K4 (also 8193 windows), C2 (4 layers) and S4 (5 layers) centroidal momentum: decoder on the base nodes.
   * Every one of them at 17 windows through the generic engine forced at hidden 128; A1-C2 L4 and Solo K4 COM L4 at hidden 256.
+Matrix of tests/test_exact_generic_gpu.py (this file's table, comparisons and routes): every kernel form of the generic-width engine -- see that file.
 Not covered, and why:
   * 8-layer models (A1-C2 L=8, MiniCheetah-K4 L=8, Solo-12 K4 COM): with at most one signed entry per weight row, the residual and base_transform paths grow
     values past bf16's 8 significant bits within 8 layers for every generator setting tried (weight scales 1, 0.5, 0.25 per row or per matrix, row densities
@@ -81,7 +82,8 @@ SWITCHES = ("MSHGNN_SPEC", "MSHGNN_STASH_NT", "MSHGNN_SLAB", "MSHGNN_FUSED", "MS
 
 
 def _spec(model):
-    return helpers.make_spec(*MODELS[model]["spec"])
+    m = MODELS[model]      # ("build": a spec builder of tests/helpers.py with its arguments, for the models helpers.make_spec does not name)
+    return m["build"][0](*m["build"][1:]) if "build" in m else helpers.make_spec(*m["spec"])
 
 
 def _seed(model, B):

@@ -108,7 +108,8 @@ def test_launches_the_pipelined_kernel_does_not_take(lib, kernels):
 @pytest.mark.parametrize("split", [0, 1])
 def test_forced_modes(lib, kernels, split):
     """MSHGNN_GEN_TILE at an odd (3, hidden 384) and an even (4, hidden 512) NCT on 300 windows, the table of tests/test_widths_gpu.py
-    (test_forced_tile_modes_match_the_oracle): plain launches, masked or not, and the raw-input launch."""
+    (test_forced_tile_modes_match_the_oracle) and of tests/test_exact_generic_gpu.py (test_forced_mode_is_the_oracle_bit_for_bit): plain launches, masked or not, and
+    the raw-input launch."""
     s = "true" if split else "false"
     for kw in (dict(all_plain=1), dict(all_plain=1, any_mask=1), dict(all_raw=1)):
         plain, m = "all_plain" in kw, "true" if kw.get("any_mask") else "false"
@@ -175,6 +176,36 @@ def test_invariants_over_the_query_space(lib, kernels):
     names = np.array([kr[0] for kr in kernels])
     assert set(names[np.unique(k)]) == set(names) == UNFORCED | FORCED_ONLY
     assert set(names[np.unique(k[Q["forced"] < 0])]) == UNFORCED
+
+
+def test_the_bit_exact_matrix_reaches_every_kernel_the_library_dispatches(lib, kernels):
+    """tests/test_exact_generic_gpu.py meets the oracle bit for bit on the (arithmetic, NCT, batch, MSHGNN_GEN_TILE) of its matrix; here: the kernels those
+    queries pick.  A launch's job count and plain / raw flags are the plan's (not visible from Python), so each query is asked for the launch classes this
+    model class has -- the raw-input launch (the encoder, padded rows: raw_ok), launches of plain rows, launches with a term of several sources -- at 1, 16
+    and 32 jobs (the 8-limb model has 33 nodes) and up to 16 terms, and the union is asserted.  Reached: every kernel of UNFORCED | FORCED_ONLY except
+      * the three MASKED k_gstep5 forms: a launch takes one only when a source of its jobs carries relu bits (any_mask), which no plan of the product
+        library has -- the producer of dX writes the masked row (GenPlan::dhm; MSHGNN_GEN_DHM=0 exists only under -DMSHGNN_TUNING).
+    k_gstep4<false,8,16> is reached by MSHGNN_GEN_TILE=6, not by a launch of more than GS5_MAX_TERMS terms: a job has one term for its root weights and one
+    per relation into its node (two where a sum of two rows is split), 7 at most on the MI graph, whatever the in-degree -- many rows are ONE term of many
+    sources or one aggregate row.  That fallback stays on this file's own query (test_launches_the_pipelined_kernel_does_not_take)."""
+    from tests import test_exact_gpu as gx
+    from tests import test_exact_generic_gpu as gen
+    points = {(m, B, -1) for m, B in gen.DEFAULT_CASES + gen.RANDOM_CASES + gen.MEAN_CASES} | {(gen.THRESHOLD_MODEL, B, -1) for B in gen.THRESHOLD_BATCHES}
+    points |= {(m, B, int(mode)) for m, B, mode in gen.FORCED_CASES} | {(m, B, -1) for m, B, _, _ in gen.AGGREGATE_CASES + gen.MANY_ROW_CASES}
+    nct = {m: gx._spec(m).hidden // 128 for m in {p[0] for p in points}}
+    seen, by_point = set(), {}
+    for m, B, forced in sorted(points):
+        for split in (0, 1):
+            for kw in (dict(all_raw=1), dict(all_plain=1), dict()):
+                for n_jobs in (1, 16, 32):
+                    for max_terms in (1, 16):
+                        name, _ = _one(lib, kernels, forced=forced, split=split, NCT=nct[m], B=B, n_jobs=n_jobs, max_terms=max_terms, **kw)
+                        seen.add(name)
+                        by_point.setdefault(name, (m, B, forced, split, kw))
+    masked = {k for k in UNFORCED if re.fullmatch(r"k_gstep5<[^,]+,[^,]+,true,.*", k)}
+    assert len(masked) == 3
+    assert seen == (UNFORCED | FORCED_ONLY) - masked, ((UNFORCED | FORCED_ONLY) - masked - seen, seen & masked)
+    print("\n" + "\n".join(f"{k}: first reached by {v}" for k, v in sorted(by_point.items())))
 
 
 def test_weight_gradient_pick(lib):

@@ -72,7 +72,8 @@ def test_aggregate_launch_on_the_32_limb_golden_case(monkeypatch):
 @pytest.mark.parametrize("dtype", ["x3", "bf16"])
 def test_base_node_of_many_limbs_goes_through_the_aggregate_launch(dtype):
     """More than 32 rows into one destination (the base node of a 40-limb robot: 40 hip joints, forward; their 40 gradients, backward): the sums are
-    computed by their own launch (k_gagg) per layer and direction, and the forward ones feed the weight-gradient item of that relation as well."""
+    computed by their own launch (k_gagg) per layer and direction, and the forward ones feed the weight-gradient item of that relation as well.
+    (At a tolerance here; the same 40-limb robot meets the oracle bit for bit in tests/test_exact_generic_gpu.py.)"""
     from morphsym_hgnn_amd import engine as eng, synth, topology
     from morphsym_hgnn_amd.spec import ModelSpec
     topo = topology.synthetic_limbs(40)
@@ -157,22 +158,9 @@ def test_random_topologies_match_the_oracle(seed, nb, nj, nf, hidden, layers):
     repeated edges, nodes without in-edges, in-degrees up to the node count, one relation left empty -- on whichever engine plan creation picks
     (the LDS-resident kernels up to 20 nodes at h = 128, else the generic-width engine), parity arithmetic, 1e-4.  hidden = 512 / 1024: the pipelined job kernel
     (k_gstep5, one / two column groups per tile) with a ragged second 64-window tile, sums of two rows as two terms, longer ones through the aggregate launch."""
-    import random
     from morphsym_hgnn_amd import engine as eng, synth
-    from morphsym_hgnn_amd.spec import ModelSpec
-    from morphsym_hgnn_amd.topology import RobotTopology
-    rng = random.Random(seed)
-    n = {"base": nb, "joint": nj, "foot": nf}
-    rels = []
-    for k, (s_, d_) in enumerate((("base", "joint"), ("joint", "base"), ("joint", "joint"), ("foot", "joint"), ("joint", "foot"))):
-        ne = 0 if (k == seed % 5 and k != 4) else rng.randint(1, 2 * max(n[s_], n[d_]))      # (never the relation into the decoder's type: keep a signal path)
-        pairs = [[rng.randrange(n[s_]), rng.randrange(n[d_])] for _ in range(ne)]
-        if pairs and rng.random() < 0.7:
-            pairs.append(list(pairs[0]))                      # a repeated edge: PyG sums it twice
-        rels.append(((s_, "connect", d_), pairs))
-    topo = RobotTopology(name=f"random{seed}", num_nodes=n, relations=rels)
-    spec = ModelSpec(kind="mi", topology=topo, hidden=hidden, num_layers=layers, widths={"base": 24, "joint": 9, "foot": 5}, regression=True,
-                     grf_dimension=1, group=None, num_timesteps=3)
+    spec = helpers.make_random_topology_spec(seed, nb, nj, nf, hidden, layers)      # (tests/test_exact_generic_gpu.py meets the oracle bit for bit on those that close)
+    topo = spec.topology
     B = 21 if hidden < 512 else 70
     x_dict, y = synth.make_windows(seed, B, spec.num_nodes, spec.widths, spec.out_channels * nf)
     params = synth.make_params(seed, spec.param_shapes())
@@ -207,7 +195,9 @@ def test_job_kernels_of_the_generic_engine_agree_bit_for_bit(monkeypatch):
     """The generic engine's job kernels on the synthetic 32-limb model (h = 512): the 16-wave kernel on 64-window tiles (MSHGNN_GEN_TILE=3, small batches), on
     128-window tiles (k_gstep4, MSHGNN_GEN_TILE=6) and the software-pipelined kernel on the same tiles (k_gstep5 at 8 waves, =8, and at 4 waves with two workgroups
     per CU, =9: the default from 256 windows picks between the two per launch) --
-    same operands in the same order per accumulator, so outputs, loss and every gradient are identical bits (full and ragged 128-window tiles)."""
+    same operands in the same order per accumulator, so outputs, loss and every gradient are identical bits (full and ragged 128-window tiles).
+    (The kernels agree with ONE ANOTHER here, on random data; what ties each of them to the oracle's bits, mode by mode and in both arithmetics, is
+    tests/test_exact_generic_gpu.py on rounding-free data.)"""
     from morphsym_hgnn_amd import engine as eng, synth
     case, spec, *_ = helpers.load_case("synth32_mi_h512_L6_B2")
     n_y = spec.out_channels * spec.num_nodes[spec.out_type]

@@ -117,7 +117,8 @@ def test_forced_tile_modes_match_the_oracle(mode, hidden, dtype, monkeypatch):
     """MSHGNN_GEN_TILE (read per launch) forces each job-kernel form at an odd (384) and an even (512) NCT on 300 windows: 0 -> k_gstep<*,4,4>;
     1 -> k_gstep<*,8,8> (128-window tiles, even NCT) / <*,4,4> (odd); 2 -> k_gstep<*,4,8> / <*,4,4>; 3 -> the widest k_gstep the NCT allows;
     6 -> k_gstep4 (NCT % 4 == 0); 8 -> k_gstep5 at 8 waves (the RAW encoder too, bf16); 9 -> k_gstep5 at 4 waves -- each against the oracle under its own
-    decisions (the split forms are not bit-identical to each other: tests/test_generic_gpu.py, test_job_kernels_of_the_generic_engine_agree_bit_for_bit)."""
+    decisions (the split forms are not bit-identical to each other: tests/test_generic_gpu.py, test_job_kernels_of_the_generic_engine_agree_bit_for_bit).
+    Tolerances over whole tensors here; the same table of modes meets the oracle bit for bit, on rounding-free data, in tests/test_exact_generic_gpu.py."""
     monkeypatch.setenv("MSHGNN_GEN_TILE", mode)
     spec = mi_spec(hidden, 2, 2)
     e = _generic(spec, dtype)
