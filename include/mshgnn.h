@@ -540,6 +540,20 @@ int mshgnn_op_aggregate(const float* x, int64_t ldx, const int32_t* rowptr, cons
 int64_t mshgnn_op_colsum_workspace(int64_t M, int64_t N);
 int mshgnn_op_colsum(const float* X, int64_t ldx, float* out, int64_t M, int64_t N, void* workspace, void* stream);
 
+/* The same operators over `double` buffers (csrc/mshgnn_ops_f64.hip), for a caller who keeps the reference's precision (torch.set_default_dtype(torch.float64),
+ * gnnLightning.py:1183) on the device: ops.compute_dtype("f64"), model.set_precision("f64").  Contracts, argument meaning (element strides, accumulate, bias,
+ * ldc, K == 0, M == 0 / N == 0) and every MSHGNN_EINVAL refusal are those of the fp32 entry points above; no value is narrowed to fp32 on the way.
+ * mshgnn_op_gemm_f64: the inner product is v_mfma_f64_16x16x4_f64; the split-K rule is mshgnn_op_gemm_workspace's (the same split count for the same shape),
+ * partials are doubles in ws[z][M][N] (mshgnn_op_gemm_f64_workspace bytes) and are added in ascending z, then bias, then C when accumulating.
+ * mshgnn_op_aggregate_f64: edges in CSR order; edge_scale[e] * x and the add round separately.  mshgnn_op_colsum_f64: 512-row blocks, then the blocks in order. */
+int64_t mshgnn_op_gemm_f64_workspace(int64_t M, int64_t N, int64_t K, int32_t* splits_out);
+int mshgnn_op_gemm_f64(const double* A, int64_t sAm, int64_t sAk, const double* B, int64_t sBn, int64_t sBk, const double* bias,
+                       double* C, int64_t ldc, int64_t M, int64_t N, int64_t K, int accumulate, void* workspace, void* stream);
+int mshgnn_op_aggregate_f64(const double* x, int64_t ldx, const int32_t* rowptr, const int32_t* col, const double* edge_scale,
+                            double* out, int64_t ldo, int64_t n_rows, int64_t width, void* stream);
+int64_t mshgnn_op_colsum_f64_workspace(int64_t M, int64_t N);
+int mshgnn_op_colsum_f64(const double* X, int64_t ldx, double* out, int64_t M, int64_t N, void* workspace, void* stream);
+
 /* ---- the reference's own input tensors, uncast ---------------------------------------------------------------------------------------------------
  * The reference's datasets hand the model fp64 tensors at the dense pitch (torch.set_default_dtype(float64), gnnLightning.py:1183; x_dict[type] is
  * [B n_t, F_t]).  These three entry points are mshgnn_forward / mshgnn_step_mse / mshgnn_step_ce for such tensors: src[t] = device pointer to the caller's

@@ -235,6 +235,8 @@ def flat_data_parallel(module, group=None, weight_by_windows: bool = False, live
     if not getattr(model, "_fused_activation", True):
         raise RuntimeError("flat_data_parallel: this model runs operator by operator (an activation other than ReLU): its gradients never pass the engine's "
                            "flat buffer -- wrap it in torch.nn.parallel.DistributedDataParallel")
+    if getattr(model, "_precision", None) == "f64":
+        raise RuntimeError("flat_data_parallel: a model at precision 'f64' has fp64 parameters and no flat fp32 buffer; data-parallel fp64 training is not supported")
     p0 = model._params_in_flat_order()[0]
     if p0.device.type != "cuda":
         raise RuntimeError("flat_data_parallel: move the model to its GPU first")

@@ -112,6 +112,7 @@ EXPORTS = [
     "mshgnn_mlp_compile_host", "mshgnn_mlp_create", "mshgnn_mlp_destroy", "mshgnn_mlp_info_get", "mshgnn_mlp_workspace_bytes", "mshgnn_mlp_stash_offset",
     "mshgnn_mlp_forward", "mshgnn_mlp_backward", "mshgnn_mlp_step",
     "mshgnn_orbit_average", "mshgnn_orbit_average_backward", "mshgnn_orbit_defect",
+    "mshgnn_op_gemm_f64", "mshgnn_op_gemm_f64_workspace", "mshgnn_op_aggregate_f64", "mshgnn_op_colsum_f64", "mshgnn_op_colsum_f64_workspace",
 ]
 ABI_VERSION = 6      # include/mshgnn.h MSHGNN_ABI_VERSION: the ctypes structures above mirror THAT header
 
@@ -206,6 +207,14 @@ def load_library():
     lib.mshgnn_op_colsum_workspace.restype = C.c_int64
     lib.mshgnn_op_colsum_workspace.argtypes = [C.c_int64, C.c_int64]
     lib.mshgnn_op_colsum.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "mshgnn_op_gemm_f64"):      # the fp64 operators (absent from older builds of the library handed over through MSHGNN_LIB for A/B runs)
+        lib.mshgnn_op_gemm_f64_workspace.restype = C.c_int64
+        lib.mshgnn_op_gemm_f64_workspace.argtypes = list(lib.mshgnn_op_gemm_workspace.argtypes)
+        lib.mshgnn_op_gemm_f64.argtypes = list(lib.mshgnn_op_gemm.argtypes)
+        lib.mshgnn_op_aggregate_f64.argtypes = list(lib.mshgnn_op_aggregate.argtypes)
+        lib.mshgnn_op_colsum_f64_workspace.restype = C.c_int64
+        lib.mshgnn_op_colsum_f64_workspace.argtypes = list(lib.mshgnn_op_colsum_workspace.argtypes)
+        lib.mshgnn_op_colsum_f64.argtypes = list(lib.mshgnn_op_colsum.argtypes)
     src6 = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
     lib.mshgnn_forward_src.argtypes = src6 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
     lib.mshgnn_step_mse_src.argtypes = src6 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]

@@ -8,7 +8,8 @@ All arithmetic runs in the HIP engine behind the C-ABI (engine.py / include/mshg
 recovers the per-window topology from the PyG-batched `edge_index_dict`, verifies the batch really is B copies
 of one graph, and compiles a plan; later calls reuse it.  Precision: `MSHGNN_DTYPE=x3` (default: the split-bf16 parity plan,
 <= 1.4e-5 of the fp64 reference against the north_star's 1e-4, at 3.6x the speed of `f32`), `f32` (exact fp32 MFMA, 1e-6) or `bf16`
-(throughput mode, 4.6e-3); `model.set_precision("bf16")` switches at run time.
+(throughput mode, 4.6e-3); `model.set_precision("bf16")` switches at run time.  A fourth precision, `f64`, is the reference's own (fp64 parameters, fp64 MFMA
+operators under `_forward_operators`, no fused engine): `_MSHGNNBase.set_precision`.
 """
 from __future__ import annotations
 
@@ -252,7 +253,7 @@ class _MSHGNNBase(nn.Module):
         self._gviews = None
         self._anchor = None
         self._checked_batches = set()
-        self._precision = os.environ.get("MSHGNN_DTYPE", "x3")
+        self._precision = os.environ.get("MSHGNN_DTYPE", "x3")      # ("f64": the constructors finish with _adopt_env_precision, once the parameters exist)
         self._group = None
 
     # ---- copy / pickle: compiled plans (ctypes handles) and device scratch never travel; they are rebuilt lazily ----
@@ -358,10 +359,38 @@ class _MSHGNNBase(nn.Module):
             self.convs.append(pnn.HeteroConv(conv_dict, aggr="sum"))
 
     def set_precision(self, dtype: str):
-        if dtype not in ("f32", "bf16", "x3"):
-            raise ValueError("precision must be 'f32', 'bf16' or 'x3'")
+        """"x3" / "f32" / "bf16": the plan of the fused engine (fp32 master parameters in one flat buffer).
+        "f64": the reference's own precision (torch.set_default_dtype(torch.float64), gnnLightning.py:1183).  The parameters become fp64 (`self.double()`: a
+        load_state_dict of a reference checkpoint then keeps every bit) and no engine is compiled: forward() is `_forward_operators` under
+        `ops.compute_dtype("f64")` -- every Linear / GraphConv on the fp64 MFMA operators of csrc/mshgnn_ops_f64.hip, with the model's own activation module,
+        autograd for the parameter and the input gradients.  fp64 inputs are read as they are, other dtypes are widened; the output is fp64.  The one-call
+        and series routes (`fused_training_step`, `fused_training_step_windows`, `forward_windows`) return None, so their callers assemble and call forward().
+        Leaving "f64" calls `self.float()`: the parameters are rounded to fp32 ONCE (f64 -> x3 is not a round trip for parameters that were loaded or trained
+        in fp64; x3 -> f64 -> x3 without an update in between is, fp32 -> fp64 being exact), and the next forward re-establishes the flat fp32 buffer."""
+        if dtype not in ("f32", "bf16", "x3", "f64"):
+            raise ValueError("precision must be 'f32', 'bf16', 'x3' or 'f64'")
+        was = self._precision
         self._precision = dtype
+        if dtype == "f64":
+            self.double()
+        elif was == "f64":
+            self.float()
         return self
+
+    def _adopt_env_precision(self):
+        """MSHGNN_DTYPE=f64 at construction: the parameters exist now, make them fp64 (before any load_state_dict)."""
+        if self._precision == "f64":
+            self.double()
+
+    def _fused_ok(self) -> bool:
+        """The fused engines serve this model: nn.ReLU() and a precision they have a plan for ("f64" has none)."""
+        return self._fused_activation and self._precision != "f64"
+
+    def _operator_mode(self):
+        """The compute dtype of the operator route: fp64 operators for "f64", else whatever the caller has set (the default: fp32)."""
+        import contextlib
+        from . import ops
+        return ops.compute_dtype("f64") if self._precision == "f64" else contextlib.nullcontext()
 
     def reset_parameters(self):
         """Reset all learnable parameters (hgnn_c2.py:286-293)."""
@@ -435,7 +464,7 @@ class _MSHGNNBase(nn.Module):
                 raise ValueError(f"x_dict['{t}'] does not match the compiled topology "
                                  f"({nn_[t]} nodes x {x_dict[t].shape[1]} vs {spec.num_nodes[t]} x {spec.widths[t]})")
         self._check_edges(edge_index_dict, B)
-        if not self._fused_activation:
+        if not self._fused_ok():
             return spec, B, None, None
         pdev = self.decoder.weight.device
         if pdev.type != "cuda":
@@ -538,7 +567,7 @@ class _MSHGNNBase(nn.Module):
         """The engine for `fused_training_step_windows` (training) or `forward_windows` (evaluation) on this batch, or None when the batch takes the assembled
         route instead.  Cheap checks first (_window_recipe_ok), then the parameters' device and the grad mode; the engine is looked up only after those pass."""
         store, r = batch.store, batch.store.recipe
-        if not self._fused_activation or not _window_recipe_ok(self._spec, r, store.desc, store.dtype, training):
+        if not self._fused_ok() or not _window_recipe_ok(self._spec, r, store.desc, store.dtype, training):
             return None
         params = self._params_in_flat_order()
         if params[0].device.type != "cuda" or params[0].device != store.device or torch.is_grad_enabled() != training:
@@ -564,7 +593,8 @@ class _MSHGNNBase(nn.Module):
     def forward(self, x_dict, edge_index_dict):
         spec, B, e, pdev = self._prepare(x_dict, edge_index_dict)
         if e is None:
-            return self._forward_operators(x_dict, edge_index_dict, B)
+            with self._operator_mode():
+                return self._forward_operators(x_dict, edge_index_dict, B)
         in_dev, in_dtype = x_dict[self._node_types[0]].device, x_dict[self._node_types[0]].dtype
         xs = e.cast_inputs(x_dict)
         grad_on = torch.is_grad_enabled()
@@ -581,18 +611,30 @@ class _MSHGNNBase(nn.Module):
 
     def _forward_operators(self, x_dict, edge_index_dict, B):
         """The reference's forward (hgnn_c2.py:133-182, hgnn_k4.py:146-196, hgnn.py:57-62, hgnn_*_com.py) operator by operator, for models built with
-        an activation_fn other than nn.ReLU(): every Linear / GraphConv runs on the HIP operators of ops.py with autograd, the activation itself
-        is the caller's module.  Inputs and parameters must be on the device."""
+        an activation_fn other than nn.ReLU() and for the "f64" precision: every Linear / GraphConv runs on the HIP operators of ops.py with autograd (in the
+        compute dtype forward() sets: fp64 for "f64"), the activation itself is the caller's module.  Inputs and parameters must be on the device."""
         from . import ops
         spec, act = self._spec, self.activation
         dev = x_dict[self._node_types[0]].device
         if dev.type != "cuda":
             raise RuntimeError("the operator path of a non-ReLU model runs on a HIP device (inputs are on the host); there is no CPU fallback")
+        wide = self._precision == "f64"
         if self.decoder.weight.device != dev:
+            home = self.decoder.weight.device
+            if wide and home.type == "cpu" and not torch.is_grad_enabled():
+                # "f64", host parameters, no autograd (the wrappers' lazy-initialising call, gnnLightning.py:593-595): as on the engine route the arithmetic
+                # still runs on the device, with the parameters there for the duration of the call (a round trip of fp64 tensors: every bit kept)
+                self.to(dev)
+                try:
+                    return self._forward_operators(x_dict, edge_index_dict, B)
+                finally:
+                    self.to(home)
             raise RuntimeError("move the model to the inputs' device first (model.to(device))")
         x = {}
         for t, m in spec.input_masks().items():                # apply_symmetry (hgnn_c2.py:191-284) as its net +-1 masks
             v = x_dict[t]
+            if wide:      # "f64": fp64 inputs as they are, anything else widened (exact); rows at an engine pitch (a windows.WindowBatch: _prepare checked it) lose their pad columns
+                v = v[:, :spec.widths[t]].to(torch.float64)
             if v.shape[1] != spec.widths[t]:
                 raise ValueError(f"x_dict['{t}'] must have the reference's width {spec.widths[t]} on the operator path")
             n = m.shape[0]
@@ -689,6 +731,7 @@ class GRF_HGNN_C2(_SymmetryHelpers, _MSHGNNBase):
         self.decoder = pnn.Linear(h, self.out_channels_per_foot)
         coeffs = ModelSpec.symmetry_coefficients(self._coeff_probe())
         self.joints_linear_weights, self.feet_linear_weights, self.base_coefficients_lin, self.base_coefficients_ang = coeffs
+        self._adopt_env_precision()
 
     def _coeff_probe(self):
         class _P:  # minimal duck-type for ModelSpec.symmetry_coefficients
@@ -720,6 +763,7 @@ class GRF_HGNN_K4(_SymmetryHelpers, _MSHGNNBase):
         self.decoder = pnn.Linear(h, self.out_channels_per_foot)
         coeffs = ModelSpec.symmetry_coefficients(GRF_HGNN_C2._coeff_probe(self))
         self.joints_linear_weights, self.feet_linear_weights, self.base_coefficients_lin, self.base_coefficients_ang = coeffs
+        self._adopt_env_precision()
 
 
 class GRF_HGNN(_MSHGNNBase):
@@ -740,6 +784,7 @@ class GRF_HGNN(_MSHGNNBase):
         else:
             self.out_channels_per_foot = 2
         self.decoder = pnn.Linear(hidden_channels, self.out_channels_per_foot)
+        self._adopt_env_precision()
 
 
 class _COMSymBase(_MSHGNNBase):
@@ -762,6 +807,7 @@ class _COMSymBase(_MSHGNNBase):
         self.decoder = pnn.Linear(h, self.num_dimensions_per_base)
         coeffs = ModelSpec.symmetry_coefficients(GRF_HGNN_C2._coeff_probe(self))
         self.joints_linear_weights, _, self.base_coefficients_lin, self.base_coefficients_ang = coeffs
+        self._adopt_env_precision()
 
     def morphological_symmetry_decoder(self, x):
         """The reference's output mask as a standalone helper (hgnn_k4_com.py:157-165); forward() already applies it
@@ -799,6 +845,7 @@ class COM_HGNN_S4(_MSHGNNBase):
         self.num_dimensions_per_base = 6
         self._build_convs(mean_rels=())
         self.decoder = pnn.Linear(hidden_channels, self.num_dimensions_per_base)
+        self._adopt_env_precision()
 
 
 class COM_HGNN(_MSHGNNBase):
@@ -813,6 +860,7 @@ class COM_HGNN(_MSHGNNBase):
         self.num_dimensions_per_base = com_dimension
         self._build_convs(mean_rels=())
         self.decoder = pnn.Linear(hidden_channels, self.num_dimensions_per_base)
+        self._adopt_env_precision()
 
 
 # ---- the MLP baseline (gnnLightning.py:363-413, gnnLightning_com.py:234-287) ---------------------------------------------------------------------------
@@ -897,6 +945,7 @@ class MLP(_MSHGNNBase):
                 self.add_module(str(2 * i + 1), activation_fn)
         self._spec = _MLPSpec(in_channels, hidden_channels, out_channels, num_layers, regression)
         self._fwd_id = 0
+        self._adopt_env_precision()
 
     def linears(self):
         return [getattr(self, str(2 * i)) for i in range(self.num_layers)]
@@ -943,16 +992,19 @@ class MLP(_MSHGNNBase):
         return out.to(x.dtype) if x.dtype in (torch.float64, torch.float32) and out.dtype != x.dtype else out
 
     def _forward_operators_mlp(self, x, dev):
-        """Operator by operator on ops.linear (fp32 MFMA, autograd through ops._Linear): the parity route."""
+        """Operator by operator on ops.linear (fp32 MFMA, autograd through ops._Linear): the parity route.  Precision "f64": the same on the fp64 MFMA
+        operators, without the casts -- fp64 parameters, inputs widened to fp64, an fp64 output."""
         from . import ops
         lin = self.linears()
         if lin[0].weight.device != dev:
             raise RuntimeError("move the model to the inputs' device first (model.to(device))")
-        a = x.to(dev, torch.float32)
-        for i, m in enumerate(lin):
-            a = ops.linear(a, m.weight.to(torch.float32), m.bias.to(torch.float32))
-            if i < len(lin) - 1:
-                a = self.activation(a)
+        dt = torch.float64 if self._precision == "f64" else torch.float32
+        a = x.to(dev, dt)
+        with self._operator_mode():
+            for i, m in enumerate(lin):
+                a = ops.linear(a, m.weight.to(dt), m.bias.to(dt))
+                if i < len(lin) - 1:
+                    a = self.activation(a)
         return a
 
     # ---- the one-call routes of the wrappers on a windows.WindowBatch ----

@@ -10,8 +10,10 @@ so reference checkpoints load unchanged and `model.convs[i].convs[edge_type].lin
 (hgnn_c2.py:295-306) keeps working.  The model classes in models.py hand all parameters to the fused HIP engine and
 never call these forwards.  Called on their own (a maintainer who swaps only the PyG import) they run PyG 2.5.0's
 semantics -- `forward(x)`, `forward(x_dict)`, `forward(x | (x_src, x_dst), edge_index)`, `forward(x_dict,
-edge_index_dict)` -- on the stand-alone HIP operators of ops.py (fp32 MFMA, autograd), for any graph and width.  There
-is no eager / CPU implementation: tensors off the HIP device raise.
+edge_index_dict)` -- on the stand-alone HIP operators of ops.py (fp32 MFMA, autograd), for any graph and width.  They take no precision
+argument of their own: under `ops.set_compute_dtype("f64")` / `with ops.compute_dtype("f64"):` every one of them runs the fp64
+kernels (fp64 MFMA; fp64 tensors used as they are), which is how a caller that keeps the reference's float64 default gets float64
+arithmetic.  There is no eager / CPU implementation: tensors off the HIP device raise.
 """
 from __future__ import annotations
 

@@ -67,6 +67,36 @@ def _model_forward(wrapper, batch):
     return wrapper.model(x_dict=batch.x_dict, edge_index_dict=batch.edge_index_dict)
 
 
+def _at_f64(wrapper) -> bool:
+    """The wrapper's model runs at precision "f64" (models.set_precision): fp64 parameters, fp64 operators, no fused engine."""
+    return getattr(getattr(wrapper, "model", None), "_precision", None) == "f64"
+
+
+def _f64_step_loss(regression: bool, y: torch.Tensor, y_pred: torch.Tensor) -> torch.Tensor:
+    """The step loss of an "f64" model in fp64 torch operations on [batch, out] (the GEMMs are the hot path, not this): the MSE over every element, or the
+    mean cross entropy of the per-foot [stable, contact] logits against the contact flags (y != 0) -- what the metric kernels compute in fp32.  Carries
+    autograd to y_pred; an fp64 tensor with an fp64 gradient."""
+    yp = y_pred.to(torch.float64)
+    if regression:
+        return torch.mean((yp - y.detach().to(yp.device, torch.float64).reshape(yp.shape)) ** 2)
+    logits = yp.reshape(-1, 2)
+    return torch.nn.functional.cross_entropy(logits, (y.detach().to(yp.device) != 0).to(torch.long).reshape(-1))
+
+
+def _losses_step(wrapper, y, y_pred):
+    """calculate_losses_step of every wrapper.  A model at "f64": the published / returned loss is `_f64_step_loss` (it never passes the fp32 loss kernel),
+    while the LOGGED metric values (rmse, l1, accuracy, F1, the epoch sums) keep coming from the metric kernels on an fp32 copy of the predictions."""
+    if _at_f64(wrapper) and torch.is_grad_enabled() and y_pred.requires_grad:
+        wrapper._m().calculate_losses_step(y, y_pred.detach())
+        wrapper._m().set_step_loss(_f64_step_loss(wrapper.regression, y, y_pred))
+    elif _at_f64(wrapper):
+        wrapper._m().calculate_losses_step(y, y_pred)
+        with torch.no_grad():
+            wrapper._m().set_step_loss(_f64_step_loss(wrapper.regression, y, y_pred))
+    else:
+        wrapper._m().calculate_losses_step(y, y_pred)
+
+
 class Base_Lightning(_Base):
     """Steps, epoch hooks, logging and the optimizer shared by every wrapper (gnnLightning.py:28-348)."""
 
@@ -119,8 +149,9 @@ class Base_Lightning(_Base):
                 self.log(f"{step_name}_F1_Score_Leg_{k}", f1[k], on_step=on_step, on_epoch=on_epoch)
 
     def calculate_losses_step(self, y: torch.Tensor, y_pred: torch.Tensor):
-        """gnnLightning.py:124-151.  Classification: `y_pred` [batch, 8] logits, `y` [batch, 4] contact flags."""
-        self._m().calculate_losses_step(y, y_pred)
+        """gnnLightning.py:124-151.  Classification: `y_pred` [batch, 8] logits, `y` [batch, 4] contact flags.  A model at precision "f64": the loss is
+        computed in fp64 (`_losses_step`); the other logged values come from the fp32 metric kernels."""
+        _losses_step(self, y, y_pred)
 
     def calculate_losses_epoch(self) -> None:
         self._m().calculate_losses_epoch()
@@ -177,6 +208,7 @@ class Base_Lightning(_Base):
     def configure_optimizers(self):
         model = getattr(self, "model", None)
         flat = isinstance(model, models._MSHGNNBase) and len(list(self.parameters())) == len(list(model.parameters()))
+        flat = flat and not _at_f64(self)      # (the flat optimizers step fp32 flat buffers; an "f64" model's fp64 parameters get torch's own optimizer)
         on_device = dict(graph_safe=bool(getattr(self, "graph_safe_optimizer", False)),      # (graph_safe: GraphedTrainingStep)
                          device_lr=bool(getattr(self, "device_lr_optimizer", False)))      # (device_lr: a captured step follows a scheduler)
         if self.optimizer == "adam":
@@ -433,7 +465,7 @@ class COM_Base_Lightning(_Base):
             self.log(f"{step_name}_{label}", getattr(self, attr), on_step=on_step, on_epoch=not on_step)
 
     def calculate_losses_step(self, y: torch.Tensor, y_pred: torch.Tensor):
-        self._m().calculate_losses_step(y, y_pred)
+        _losses_step(self, y, y_pred)
 
     def calculate_losses_epoch(self) -> None:
         self._m().calculate_losses_epoch()
@@ -658,6 +690,9 @@ class GraphedTrainingStep:
     def __init__(self, wrapper, optimizer, example_batch, warmup: int = 3, index_source=None, max_grad_norm=None):
         import copy
         from .optim import _FlatMixin
+        if _at_f64(wrapper):
+            raise ValueError("GraphedTrainingStep: the model is at precision 'f64' -- its operator route builds the CSR views of the graph with host "
+                             "synchronisations, which a HIP graph capture cannot contain; capture a step at 'x3', 'f32' or 'bf16'")
         flat_opt = isinstance(optimizer, _FlatMixin)      # FlatAdam, FlatAdamW, FlatSGD
         if flat_opt and not optimizer._graph_safe:
             raise ValueError(f"GraphedTrainingStep needs {type(optimizer).__name__}(graph_safe=True): set wrapper.graph_safe_optimizer = True before "
