@@ -313,11 +313,13 @@ int mshgnn_ce_loss(const float* logits, const int32_t* labels, int64_t rows, flo
  * fp64, a fixed reduction order (bit-reproducible).
  *
  * regression (calculate_losses_step, gnnLightning.py:124-130 / :633-639): state double[3]:
- *   [0] += sum (y_pred - y)^2   [1] += sum |y_pred - y|   [2] += n        => MSE = [0]/[2], RMSE = sqrt(MSE), L1 = [1]/[2] */
+ *   [0] += sum (y_pred - y)^2   [1] += sum |y_pred - y|   [2] += n        => MSE = [0]/[2], RMSE = sqrt(MSE), L1 = [1]/[2]
+ * MSHGNN_EINVAL before any launch (this call and every call below, down to mshgnn_metrics_com_step): a null pointer where none is allowed,
+ * n / batch / n_bases < 1, a double / int64 state or a scratch that is not 8-byte aligned (the kernels run 64-bit atomics on them).         */
 int mshgnn_metrics_regression(const float* y_pred, const float* y, int64_t n, double* state, void* stream);
 
 /* classification (gnnLightning.py:132-151, 285-348): logits fp32 [batch*4][2] (per foot: no-contact, contact), labels int32
- * [batch][4] in {0,1}.  ce_state double[2]: [0] += sum of per-foot cross entropies, [1] += 4*batch.  counts int64[18]:
+ * [batch][4] in {0,1} (read as `!= 0`: any nonzero label is a stable contact, as mshgnn_ce_loss reads it).  ce_state double[2]: [0] += sum of per-foot cross entropies, [1] += 4*batch.  counts int64[18]:
  *   [0] += batch, [1] += windows whose 16-class argmax (classification_conversion_16_class, :306-348) equals the label
  *   state 8 y0 + 4 y1 + 2 y2 + y3, [2 + 4k .. 5 + 4k] += tp, fp, fn, tn of leg k (BinaryF1Score, customMetrics.py:26-54). */
 int mshgnn_metrics_classification(const float* logits, const int32_t* y, int64_t batch, double* ce_state, int64_t* counts,

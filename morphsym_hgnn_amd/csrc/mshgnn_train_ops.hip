@@ -935,6 +935,7 @@ static int met_blocks(int64_t items, int per_thread) {
 
 extern "C" int mshgnn_metrics_regression(const float* y_pred, const float* y, int64_t n, double* state, void* stream) {
     if (!y_pred || !y || !state || n < 1) return set_err(MSHGNN_EINVAL, "bad argument to mshgnn_metrics_regression");
+    if ((uintptr_t)state & 7) return set_err(MSHGNN_EINVAL, "mshgnn_metrics_regression: the state must be 8-byte aligned");
     hipLaunchKernelGGL(k_metrics_reg<1024>, dim3(1), dim3(1024), 0, (hipStream_t)stream, y_pred, y, n, (double*)nullptr, state, (float*)nullptr, (MetScratch*)nullptr);
     HIPCHK(hipGetLastError());
     return MSHGNN_OK;
@@ -943,6 +944,8 @@ extern "C" int mshgnn_metrics_regression(const float* y_pred, const float* y, in
 extern "C" int mshgnn_metrics_regression_step(const float* y_pred, const float* y, int64_t n, double* batch_state, double* epoch_state, float* grad_out,
                                               void* scratch, void* stream) {
     if (!y_pred || !y || (!batch_state && !epoch_state) || !scratch || n < 1) return set_err(MSHGNN_EINVAL, "bad argument to mshgnn_metrics_regression_step");
+    if (((uintptr_t)batch_state | (uintptr_t)epoch_state | (uintptr_t)scratch) & 7)
+        return set_err(MSHGNN_EINVAL, "mshgnn_metrics_regression_step: the states and the scratch must be 8-byte aligned");
     hipLaunchKernelGGL(k_metrics_reg<MET_THREADS>, dim3(met_blocks(n, 16)), dim3(MET_THREADS), 0, (hipStream_t)stream, y_pred, y, n, batch_state, epoch_state, grad_out,
                        reinterpret_cast<MetScratch*>(scratch));
     HIPCHK(hipGetLastError());
@@ -951,6 +954,7 @@ extern "C" int mshgnn_metrics_regression_step(const float* y_pred, const float* 
 
 extern "C" int mshgnn_metrics_classification(const float* logits, const int32_t* y, int64_t batch, double* ce_state, int64_t* counts, void* stream) {
     if (!logits || !y || !ce_state || !counts || batch < 1) return set_err(MSHGNN_EINVAL, "bad argument to mshgnn_metrics_classification");
+    if (((uintptr_t)ce_state | (uintptr_t)counts) & 7) return set_err(MSHGNN_EINVAL, "mshgnn_metrics_classification: the states must be 8-byte aligned");
     hipLaunchKernelGGL(k_metrics_cls<1024>, dim3(1), dim3(1024), 0, (hipStream_t)stream, logits, y, batch, (double*)nullptr, (long long*)nullptr, ce_state,
                        reinterpret_cast<long long*>(counts), (float*)nullptr, (MetScratch*)nullptr);
     HIPCHK(hipGetLastError());
@@ -961,6 +965,8 @@ extern "C" int mshgnn_metrics_classification_step(const float* logits, const int
                                                   double* epoch_ce, int64_t* epoch_counts, float* grad_out, void* scratch, void* stream) {
     if (!logits || !y || batch < 1 || !scratch || (!batch_ce != !batch_counts) || (!epoch_ce != !epoch_counts) || (!batch_ce && !epoch_ce))
         return set_err(MSHGNN_EINVAL, "bad argument to mshgnn_metrics_classification_step");
+    if (((uintptr_t)batch_ce | (uintptr_t)batch_counts | (uintptr_t)epoch_ce | (uintptr_t)epoch_counts | (uintptr_t)scratch) & 7)
+        return set_err(MSHGNN_EINVAL, "mshgnn_metrics_classification_step: the states and the scratch must be 8-byte aligned");
     hipLaunchKernelGGL(k_metrics_cls<MET_THREADS>, dim3(met_blocks(batch, 1)), dim3(MET_THREADS), 0, (hipStream_t)stream, logits, y, batch, batch_ce,
                        reinterpret_cast<long long*>(batch_counts), epoch_ce, reinterpret_cast<long long*>(epoch_counts), grad_out,
                        reinterpret_cast<MetScratch*>(scratch));
@@ -972,6 +978,8 @@ extern "C" int mshgnn_metrics_com_step(const float* y_pred, const float* y, int6
                                        double* batch_state, double* epoch_state, void* scratch, void* stream) {
     if (!y_pred || !y || !y_mean || !y_std || batch < 1 || n_bases < 1 || !scratch || (!batch_state && !epoch_state))
         return set_err(MSHGNN_EINVAL, "bad argument to mshgnn_metrics_com_step");
+    if (((uintptr_t)batch_state | (uintptr_t)epoch_state | (uintptr_t)scratch) & 7)
+        return set_err(MSHGNN_EINVAL, "mshgnn_metrics_com_step: the states and the scratch must be 8-byte aligned");
     ComStats st;
     for (int k = 0; k < 6; ++k) { st.mean[k] = y_mean[k]; st.std[k] = y_std[k]; }
     hipLaunchKernelGGL(k_metrics_com, dim3(met_blocks(batch, 1)), dim3(MET_THREADS), 0, (hipStream_t)stream, y_pred, y, batch, n_bases, st, batch_state,
