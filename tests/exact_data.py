@@ -4,7 +4,8 @@ Every weight matrix has one signed entry per row (+-1, the relation weights scal
 output gradient a few units of 2^-14.  On such data every value the kernels store in bf16 is exactly representable and every fp32 accumulation is exact
 in any order, so the bf16, split (x3) and fp32 plans must reproduce the fp64 oracle BIT FOR BIT -- at any batch size, on every kernel set.  A single wrong
 element anywhere (a dropped 16-window tile, a mis-indexed 32-feature column slice) is then a failure, where the bf16 plan's tolerance tests
-(tests/test_bf16_emulation.py, 1.5e-2 L2) cannot see it.
+(tests/test_bf16_emulation.py, 1.5e-2 L2) cannot see it.  Every operand being a bf16 value, every lo half of the split plan is ZERO on this data: its cross
+products, lo planes and lo weight images are held by tests/x3_emulation.py (this generator with one operand class widened) and tests/test_x3_exact_gpu.py.
 
 `check_exact` proves the three preconditions on the host before it hands out the fp64 reference:
   (a) bf16 closure: the rounding-point emulation with and without rounding and the oracle agree bit for bit, and every activation and activation gradient

@@ -1,9 +1,10 @@
 """Gradients with respect to the inputs (mshgnn_input_grad, Engine.input_grad, models._EngineFn) against the fp64 oracle BIT FOR BIT, on rounding-free
 data (tests/exact_data.py with enc_cover=True: on it dx = m . (dY_enc @ W_enc) is a short sum of exact products in every plan's operand form, and every
 input type's dx is non-zero in every 16-column tile -- tests/test_exact_data.py proves that, (a)-(d), on the host for every (model, batch) used here).
-A wrong column chunk, a dropped K block, a mis-indexed node row or a missing sign flip is then a failure, where a tolerance could miss it.  The split
-plan's hi.lo and lo.hi products are NOT seen here: dY_enc and W_enc are bf16 values on this data, so every lo half is zero.  Those products are held by
-the own-operand tests of tests/test_input_grad_gpu.py (helpers.check_input_grad_against_own_operands), on random data.
+A wrong column chunk, a dropped K block, a mis-indexed node row or a missing sign flip is then a failure, where a tolerance could miss it.  On this
+data dY_enc and W_enc are bf16 values, so every lo half is zero: the split plan's hi.lo and lo.hi products are pinned bit for bit by
+tests/test_x3_exact_gpu.py (wide_gout / wide_dec: dY_enc carries lo halves; wide_enc: W_enc does; split and fp32 plans, the generic engine at hidden 256),
+and on random data by the own-operand tests of tests/test_input_grad_gpu.py (helpers.check_input_grad_against_own_operands).
 
 Matrix:
   * A1-C2 at 4 layers (the shallowest depth whose base rows -- 2 nodes, F = 900, 15 column chunks, signed masks -- are live) and at 3 layers (base dead:
