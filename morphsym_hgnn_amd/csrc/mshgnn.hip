@@ -1327,37 +1327,40 @@ __global__ __launch_bounds__(256) void k_finalize(FinArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------------
-// Kernel selection: the slab kernel of a plan and a launch -- a compile-time program's where a shard (or the plan's attached program) has one, else the interpreter
+// Launch tables: row k of a family is what pick_stack / pick_enc (mshgnn_pick.hpp) call k.  Which row a launch takes is decided there and nowhere else.
 // ------------------------------------------------------------------------------------------------------
-static StackKernel slab_fwd_kernel(const HostPlan& hp) {
-    if (hp.sl_hb <= SL_HB) return hp.n_mlp <= 2 ? k_slab_fwd<__bf16, 2, SL_HB> : k_slab_fwd<__bf16, 4, SL_HB>;
-    return hp.n_mlp <= 2 ? k_slab_fwd<__bf16, 2, SL_HB_MAX> : k_slab_fwd<__bf16, 4, SL_HB_MAX>;
-}
-using SpecSelector = StackKernel (*)(const HostPlan& hp, int kind, int tr, int nt, int full, const char** name);
-static StackKernel spec_kernel(const HostPlan& hp, int kind, int tr, int nt, int full, const char** name = nullptr) {
-    const char* nm = nullptr;      // (a shard that holds the plan's program sets the name even where it has no kernel of that kind: stop there)
+static constexpr StackKernel STACK8_TABLE[pick::STACK8_ROWS] = {k_stack_fwd<__bf16>, k_stack_bwd<__bf16>, k_stack_step<__bf16>};
+#define SLAB_ROWS_OF(K) K<__bf16, 2, SL_HB>, K<__bf16, 2, SL_HB_MAX>, K<__bf16, 4, SL_HB>, K<__bf16, 4, SL_HB_MAX>
+static constexpr StackKernel SLAB_TABLE[pick::SLAB_ROWS] = {SLAB_ROWS_OF(k_slab_fwd), SLAB_ROWS_OF(k_slab_bwd), SLAB_ROWS_OF(k_slab_step)};      // [what][NM][HB]: pick::slab_row
+#undef SLAB_ROWS_OF
+static_assert(pick::STACK8_THREADS == LAYER_THREADS, "the pick's block size of the 8-wave kernels");
+// the encoder of the fp32 / bf16 plans by pick::EncForm; the fp32 plan has no source routes (plan_traits<float>.src_routes is false: pick_enc never names those rows)
+using EncKernel = void (*)(EncArgs, SeriesSrc, WideSrc);
+template <typename T> static constexpr EncKernel ENC_TABLE[pick::ENC_FORMS] = {k_enc_fwd<T, false>, k_enc_fwd<T, true>};
+template <> constexpr EncKernel ENC_TABLE<__bf16>[pick::ENC_FORMS] = {
+    k_enc_fwd<__bf16, false>, k_enc_fwd<__bf16, true>, k_enc_fwd<__bf16, true, false, 4>, k_enc_fwd<__bf16, true, false, 8>,
+    k_enc_fwd<__bf16, true, true>, k_enc_fwd<__bf16, true, true, 0, true>, k_enc_fwd<__bf16, true, true, 0, false, true>, k_enc_fwd<__bf16, true, true, 0, true, true>,
+    k_enc_fwd<__bf16, true, true, 0, false, true, true>, k_enc_fwd<__bf16, true, true, 0, true, true, true>};
+// the kernels over the plan's compile-time program: row `form` (pick::SpecForm) of the table of the shard -- or of the program attached after the build -- whose tables
+// are the plan's; name: that program's
+using SpecSelector = StackKernel (*)(const HostPlan& hp, int form, const char** name);
+static StackKernel spec_kernel(const HostPlan& hp, int form, const char** name = nullptr) {
+    const char* nm = nullptr;
     if (hp.jit_prog) {             // a program compiled for this plan after the build
-        StackKernel kk = reinterpret_cast<SpecSelector>(hp.jit_prog)(hp, kind, tr, nt, full, &nm);
+        StackKernel kk = reinterpret_cast<SpecSelector>(hp.jit_prog)(hp, form, &nm);
         if (nm) { if (name) *name = nm; return kk; }
     }
-#define SPEC_SHARD_TRY(k) { StackKernel kk = spec_shard##k(hp, kind, tr, nt, full, &nm); if (nm) { if (name) *name = nm; return kk; } }
+#define SPEC_SHARD_TRY(k) { StackKernel kk = spec_shard##k(hp, form, &nm); if (nm) { if (name) *name = nm; return kk; } }
     SPEC_SHARD_LIST(SPEC_SHARD_TRY)
 #undef SPEC_SHARD_TRY
     return nullptr;
 }
-inline bool whole_tiles(int64_t B) { return B > 0 && B % TILE_ROWS == 0; }
-static StackKernel slab_step_spec_kernel(const HostPlan& hp, int nt, const char** name = nullptr, bool full = true) { return spec_kernel(hp, 0, 1, nt, full, name); }
-static StackKernel slab_fwd_spec_kernel(const HostPlan& hp, int training, int nt, bool full = true) { return spec_kernel(hp, 1, training, nt, full); }
-static StackKernel slab_bwd_spec_kernel(const HostPlan& hp, int nt, bool full = true) { return spec_kernel(hp, 2, 1, nt, full); }
-// the step kernel of a launch: the specialised one where the plan has one and the batch is whole tiles (its stores are unpredicated), else the interpreter
-static StackKernel slab_step_kernel(const HostPlan& hp, int64_t B = -1, int nt = 0, bool use_spec = false) {
-    if (use_spec && B > 0) if (StackKernel k = slab_step_spec_kernel(hp, nt, nullptr, whole_tiles(B))) return k;
-    if (hp.sl_hb <= SL_HB) return hp.n_mlp <= 2 ? k_slab_step<__bf16, 2, SL_HB> : k_slab_step<__bf16, 4, SL_HB>;
-    return hp.n_mlp <= 2 ? k_slab_step<__bf16, 2, SL_HB_MAX> : k_slab_step<__bf16, 4, SL_HB_MAX>;
+static StackKernel stack_kernel(const HostPlan& hp, const pick::StackPick& pk) {
+    return pk.family == pick::STACK8 ? STACK8_TABLE[pk.k] : pk.family == pick::SLAB ? SLAB_TABLE[pk.k] : pk.family == pick::SLAB_SPEC ? spec_kernel(hp, pk.k) : nullptr;
 }
-static StackKernel slab_bwd_kernel(const HostPlan& hp) {
-    if (hp.sl_hb <= SL_HB) return hp.n_mlp <= 2 ? k_slab_bwd<__bf16, 2, SL_HB> : k_slab_bwd<__bf16, 4, SL_HB>;
-    return hp.n_mlp <= 2 ? k_slab_bwd<__bf16, 2, SL_HB_MAX> : k_slab_bwd<__bf16, 4, SL_HB_MAX>;
+template <typename K, size_t N> static int set_lds_attrs(const K (&table)[N], int bytes) {      // every row a table has
+    for (K k : table) if (k) if (int rc = set_lds_attr(k, bytes)) return rc;
+    return MSHGNN_OK;
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -1366,20 +1369,12 @@ static StackKernel slab_bwd_kernel(const HostPlan& hp) {
 
 // the kernels over this plan's compile-time program, if one exists (built in, or attached): their dynamic-LDS attribute, the program's name; else use_spec = false
 static int set_spec_attrs(mshgnn_plan* p, int flds) {
-    const HostPlan& hp = p->hp;
-    int rc;
     const char* nm = nullptr;
-    for (int nt = 0; nt < 2; ++nt)
-        if (StackKernel k = slab_step_spec_kernel(hp, nt, &nm)) if ((rc = set_lds_attr(k, flds))) return rc;
+    for (int form = 0; form < pick::SPEC_FORMS; ++form)
+        if (StackKernel k = spec_kernel(p->hp, form, &nm)) { if (int rc = set_lds_attr(k, flds)) return rc; } else if (!nm) break;      // (no program: no form)
     if (!nm) { p->use_spec = false; return MSHGNN_OK; }
     p->spec_name_buf = strncmp(nm, "spec::", 6) == 0 ? nm + 6 : nm;
     p->spec_name = p->spec_name_buf.c_str();
-    for (int v = 0; v < 3; ++v)
-        if (StackKernel k = slab_fwd_spec_kernel(hp, v > 0, v - 1)) if ((rc = set_lds_attr(k, flds))) return rc;
-    for (int nt = 0; nt < 2; ++nt)
-        if (StackKernel k = slab_bwd_spec_kernel(hp, nt)) if ((rc = set_lds_attr(k, flds))) return rc;
-    if (StackKernel k = slab_step_spec_kernel(hp, 0, nullptr, false)) if ((rc = set_lds_attr(k, flds))) return rc;      // (ragged batches)
-    if (StackKernel k = slab_fwd_spec_kernel(hp, 0, 0, false)) if ((rc = set_lds_attr(k, flds))) return rc;
     return MSHGNN_OK;
 }
 
@@ -1392,7 +1387,7 @@ extern "C" int mshgnn_plan_attach_program(mshgnn_plan* p, void* selector) {
     void* const prev = p->hp.jit_prog;
     p->hp.jit_prog = selector;
     const char* nm = nullptr;
-    if (!reinterpret_cast<SpecSelector>(selector)(p->hp, 0, 1, 0, 1, &nm) || !nm) {
+    if (!reinterpret_cast<SpecSelector>(selector)(p->hp, pick::SF_STEP, &nm) || !nm) {
         p->hp.jit_prog = prev;
         return set_err(MSHGNN_EINVAL, "the program's tables are not this plan's");
     }
@@ -1467,21 +1462,20 @@ extern "C" int mshgnn_plan_create(const mshgnn_desc* desc, mshgnn_plan** out) {
         if ((rc = x3_set_attrs(p))) { mshgnn_plan_destroy(p); return rc; }
     } else if (hp.d.dtype == MSHGNN_F32) {
         if ((rc = set_lds_attr(k_layer_fwd<float>, lds)) || (rc = set_lds_attr(k_layer_bwd<float>, lds)) ||
-            (rc = set_lds_attr(k_enc_fwd<float, true>, Prec<float>::ENC_MB * Prec<float>::BLK)) || (rc = set_lds_attr(k_enc_fwd<float, false>, Prec<float>::ENC_MB * Prec<float>::BLK))) { mshgnn_plan_destroy(p); return rc; }
+            (rc = set_lds_attrs(ENC_TABLE<float>, Prec<float>::ENC_MB * Prec<float>::BLK))) { mshgnn_plan_destroy(p); return rc; }
     } else {
         if ((rc = set_lds_attr(k_layer_fwd<__bf16>, lds)) || (rc = set_lds_attr(k_layer_bwd<__bf16>, lds)) ||
-            (rc = set_lds_attr(k_enc_fwd<__bf16, true>, Prec<__bf16>::ENC_MB * Prec<__bf16>::BLK)) || (rc = set_lds_attr(k_enc_fwd<__bf16, true, true>, Prec<__bf16>::ENC_MB * Prec<__bf16>::BLK)) || (rc = set_lds_attr(k_enc_fwd<__bf16, true, false, 8>, Prec<__bf16>::ENC_MB * Prec<__bf16>::BLK)) || (rc = set_lds_attr(k_enc_fwd<__bf16, true, false, 4>, Prec<__bf16>::ENC_MB * Prec<__bf16>::BLK)) || (rc = set_lds_attr(k_enc_fwd<__bf16, false>, Prec<__bf16>::ENC_MB * Prec<__bf16>::BLK))) { mshgnn_plan_destroy(p); return rc; }
+            (rc = set_lds_attrs(ENC_TABLE<__bf16>, Prec<__bf16>::ENC_MB * Prec<__bf16>::BLK))) { mshgnn_plan_destroy(p); return rc; }
         const char* e = getenv("MSHGNN_FUSED");
         p->use_fused = hp.fused && !(e && atoi(e) == 0);
         if (p->use_fused) {
             const int flds = (hp.fs_blk + FS_EXTRA_BLK) * Prec<__bf16>::BLK;
-            if ((rc = set_lds_attr(k_stack_fwd<__bf16>, flds)) || (rc = set_lds_attr(k_stack_bwd<__bf16>, flds)) || (rc = set_lds_attr(k_stack_step<__bf16>, flds))) { mshgnn_plan_destroy(p); return rc; }
+            if ((rc = set_lds_attrs(STACK8_TABLE, flds))) { mshgnn_plan_destroy(p); return rc; }
             const char* es = getenv("MSHGNN_SLAB");
             p->use_slab = hp.slab && !(es && atoi(es) == 0);       // default on where the plan allows it; MSHGNN_SLAB=0 selects the 8-wave kernels
             p->slab_force = es && atoi(es) == 2;                   // MSHGNN_SLAB=2: also for batches that do not fill the chip
             { int dev = 0, cus = 256; if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev); p->n_cu = cus > 0 ? cus : 256; }
-            if (p->use_slab && ((rc = set_lds_attr(slab_fwd_kernel(hp), flds)) || (rc = set_lds_attr(slab_bwd_kernel(hp), flds)) ||
-                                (rc = set_lds_attr(slab_step_kernel(hp), flds)))) { mshgnn_plan_destroy(p); return rc; }
+            if (p->use_slab && (rc = set_lds_attrs(SLAB_TABLE, flds))) { mshgnn_plan_destroy(p); return rc; }
             { const char* esp = getenv("MSHGNN_SPEC"); p->use_spec = p->use_slab && !(esp && atoi(esp) == 0); }
             if (p->use_spec && (rc = set_spec_attrs(p, flds))) { mshgnn_plan_destroy(p); return rc; }
             { const char* et = getenv("MSHGNN_STEP_KERNEL"); p->use_step = !(et && atoi(et) == 0); }      // one-call steps: forward + backward sweep in one launch
@@ -1613,25 +1607,11 @@ static int forward_impl(const mshgnn_plan* p, StepCall& c) {
     int rc;
     // 1. weight images (bf16 plan with few packs: the layer packs by extra workgroups of the encoder launch, enc_prep_split), 2. encoder
     {
-        EncArgs a{}; unsigned enc_grid = 0; EncRoute route;
+        EncArgs a{}; unsigned enc_grid = 0; int form = 0;
         if ((rc = prep_and_enc_args(p, c, lay, tr, launch_prep_t<T>, a, enc_grid))) return rc;
         ProfScope ps(p, hp.ks_enc, st);
-        if ((rc = pick_enc_route(c, a, tr, enc_grid, route))) return rc;
-        unsigned enc_lds = tr.enc_lds;
-        auto enc = [&](auto kernel, const SeriesSrc& ser, const WideSrc& wsrc) { hipLaunchKernelGGL(kernel, dim3(enc_grid), dim3(256), enc_lds, st, a, ser, wsrc); };
-        if (route == EncRoute::ALIGNED) enc(k_enc_fwd<T, true>, SeriesSrc{}, WideSrc{});
-        else if (route == EncRoute::ELEMENTWISE) enc(k_enc_fwd<T, false>, SeriesSrc{}, WideSrc{});
-        else if constexpr (sizeof(T) == 2) {      // (plan_traits<float>.src_routes is false: the fp32 plan takes no other route)
-            const bool orbit = (route == EncRoute::SERIES_STD || route == EncRoute::SERIES) && (c.series->sign >> MSHGNN_WINDOW_ELEMENTS_SHIFT) != 0;      // K > 1: a group element per window
-            if (route == EncRoute::SERIES_STD && orbit) enc(k_enc_fwd<T, true, true, 0, true, true, true>, *c.series, WideSrc{});
-            else if (route == EncRoute::SERIES && orbit) enc(k_enc_fwd<T, true, true, 0, false, true, true>, *c.series, WideSrc{});
-            else if (route == EncRoute::SERIES_STD && c.series->sign) enc(k_enc_fwd<T, true, true, 0, true, true>, *c.series, WideSrc{});
-            else if (route == EncRoute::SERIES && c.series->sign) enc(k_enc_fwd<T, true, true, 0, false, true>, *c.series, WideSrc{});
-            else if (route == EncRoute::SERIES_STD) enc(k_enc_fwd<T, true, true, 0, true>, *c.series, WideSrc{});
-            else if (route == EncRoute::SERIES) enc(k_enc_fwd<T, true, true>, *c.series, WideSrc{});
-            else if (route == EncRoute::WIDE8) enc(k_enc_fwd<T, true, false, 8>, SeriesSrc{}, *c.wide);      // (x may be null: nothing written on the side)
-            else enc(k_enc_fwd<T, true, false, 4>, SeriesSrc{}, *c.wide);
-        }
+        if ((rc = pick_enc_form(c, a, tr, enc_grid, form))) return rc;
+        hipLaunchKernelGGL(ENC_TABLE<T>[form], dim3(enc_grid), dim3(256), tr.enc_lds, st, a, enc_series_src(c, form), enc_wide_src(c, form));
     }
     // 3. layers (+ decoder): one fused launch on the bf16 plan, else one kernel per layer and the decoder kernel
     const int tiles = (B + Prec<T>::ROWS - 1) / Prec<T>::ROWS;
@@ -1641,36 +1621,12 @@ static int forward_impl(const mshgnn_plan* p, StepCall& c) {
             fill_stack_common(p, c, lay, a);
             fill_stack_tail(p, c, lay, a);
             a.tile_in = ws + lay.x[0]; a.training = training; a.dbg = p->dbg;
-            for (int l = 0; l < hp.L; ++l) a.prog_off[l] = hp.fs_fwd_off[l];
             a.stamps = stamp_ptr("MSHGNN_STAMPS");
-            a.stagger = p->slab_for(tiles) && tiles > p->n_cu ? p->stagger : 0;
-            if (!training) a.stash_nt = 0;      // (an evaluation stashes nothing; the split plan leaves the policy set there)
-            const bool want_step = p->use_step && c.dec_done;
-            // Slab or 8-wave kernels: the 8-wave ones take batches of at most one tile per CU -- unless the one-call step has a compile-time program for this plan
-            // (whole tiles): a single tile's chain on the specialised slab kernel is 37-42 us where the interpreting 8-wave kernel takes 57-62 (A1-C2, 32 .. 4 096 windows;
-            // 8 layers: 140-166 against 202-209), so the specialised step runs at every batch size.  MSHGNN_SLAB=0 / MSHGNN_SPEC=0 keep the 8-wave kernels there.
-            bool step_slab = p->slab_for(tiles);
-            const bool spec_small = !step_slab && want_step && p->use_slab && p->use_spec && slab_step_spec_kernel(hp, a.stash_nt, nullptr, whole_tiles(B)) != nullptr;
-            auto lds_of = [&](bool slab) { return (size_t)((slab ? hp.sl_blk : hp.fs_blk) + FS_EXTRA_BLK) * tr.blk; };
-            auto red_fits = [&](bool slab) {      // the tail's reduction scratch of a one-launch step on that kernel family fits beside the out-type blocks (and is placed)
-                return place_red_scratch(a.node0, a.n_out, tr.blk, (size_t)((slab ? SL_THREADS : LAYER_THREADS) / 64) * DEC_SLAB_FLOATS * sizeof(float), lds_of(slab), a); };
-            if (spec_small && red_fits(true)) step_slab = true;
-            const bool step = want_step && red_fits(step_slab);
-            // the forward launch alone (evaluation / two-call training) on its compile-time program, at every whole-tile batch size
-            const StackKernel fwd_spec = (!step && p->use_slab && p->use_spec) ? slab_fwd_spec_kernel(hp, training, a.stash_nt, whole_tiles(B)) : nullptr;
-            if (fwd_spec) step_slab = true;
-            if (step_slab) for (int l = 0; l < hp.L; ++l) a.prog_off[l] = hp.sl_fwd_off[l];
-            if (step) {      // the backward sweep in the same launch
-                for (int l = 0; l < hp.L; ++l) a.prog_off_b[l] = step_slab ? hp.sl_bwd_off[l] : hp.fs_bwd_off[l];
-                a.mask0_off = lay.dd[0];
-                c.stack_done = true;
-            }
-            ProfScope ps(p, step ? hp.ks_stack_step : hp.ks_stack_fwd, st);
-            if (step_slab) hipLaunchKernelGGL(step ? slab_step_kernel(hp, B, a.stash_nt, p->use_spec) : fwd_spec ? fwd_spec : slab_fwd_kernel(hp), dim3(tiles), dim3(SL_THREADS), lds_of(true), st, a);
-            else if (step) hipLaunchKernelGGL(k_stack_step<T>, dim3(tiles), dim3(LAYER_THREADS), lds_of(false), st, a);
-            else hipLaunchKernelGGL(k_stack_fwd<T>, dim3(tiles), dim3(LAYER_THREADS), lds_of(false), st, a);
-            HIPCHK(hipGetLastError());
-            return MSHGNN_OK;
+            const pick::StackPick pk = pick::pick_stack(stack_query(p, c, pick::PLAN_BF16, forward_op(c), tr.blk, a));
+            apply_stack_pick(hp, pk, lay, a);
+            if (pk.what == pick::STEP) c.stack_done = true;      // the backward sweep runs in the same launch
+            ProfScope ps(p, pk.what == pick::STEP ? hp.ks_stack_step : hp.ks_stack_fwd, st);
+            return launch_stack(stack_kernel(hp, pk), pk, st, a);
         }
     }
     for (int l = 0; l < hp.L; ++l) {
@@ -1715,17 +1671,12 @@ static int backward_impl(const mshgnn_plan* p, const StepCall& c) {
         if (p->use_fused && !fused_done) {
             StackArgs a{};
             fill_stack_common(p, c, lay, a);
-            a.tile_in = ws + lay.dx[hp.L]; a.training = 1; a.mask0_off = lay.dd[0]; a.dbg = p->dbg;
-            for (int l = 0; l < hp.L; ++l) a.prog_off[l] = hp.fs_bwd_off[l];
+            a.tile_in = ws + lay.dx[hp.L]; a.training = 1; a.dbg = p->dbg;
             a.stamps = stamp_ptr("MSHGNN_STAMPS_BWD");
-            a.stagger = p->slab_for(tiles) && tiles > p->n_cu ? p->stagger : 0;
+            const pick::StackPick pk = pick::pick_stack(stack_query(p, c, pick::PLAN_BF16, pick::OP_BWD, tr.blk, a));
+            apply_stack_pick(hp, pk, lay, a);
             ProfScope ps(p, hp.ks_stack_bwd, st);
-            const StackKernel bwd_spec = (p->use_slab && p->use_spec) ? slab_bwd_spec_kernel(hp, a.stash_nt, whole_tiles(B)) : nullptr;      // (at every whole-tile batch size, like the forward)
-            if (bwd_spec || p->slab_for(tiles)) {
-                for (int l = 0; l < hp.L; ++l) a.prog_off[l] = hp.sl_bwd_off[l];
-                hipLaunchKernelGGL(bwd_spec ? bwd_spec : slab_bwd_kernel(hp), dim3(tiles), dim3(SL_THREADS), (hp.sl_blk + FS_EXTRA_BLK) * Prec<T>::BLK, st, a);
-            } else
-            hipLaunchKernelGGL(k_stack_bwd<T>, dim3(tiles), dim3(LAYER_THREADS), (hp.fs_blk + FS_EXTRA_BLK) * Prec<T>::BLK, st, a);
+            if (int rc = launch_stack(stack_kernel(hp, pk), pk, st, a)) return rc;
             fused_done = true;
         }
     }

@@ -3,10 +3,12 @@
 //     specialised step kernels);
 //   * tests/test_plan_property.py drives it with hypothesis-generated topologies, also as an AddressSanitizer / UBSan build (`make asan-host`): the
 //     index tables every kernel trusts are bounds-checked here, on the CPU;
-//   * tests/test_gen_pick.py asks it which kernel, grid and tiles a launch of the generic engine gets (pick_job_kernel, mshgnn_gen_plan.hpp).
+//   * tests/test_gen_pick.py asks it which kernel, grid and tiles a launch of the generic engine gets (pick_job_kernel, mshgnn_gen_plan.hpp);
+//   * tests/test_resident_pick.py the same of the LDS-resident engine's stack and encoder launches (pick_stack / pick_enc, mshgnn_pick.hpp).
 // Not part of the drop-in boundary (include/mshgnn.h): test / build infrastructure around mshgnn_plan.hpp and mshgnn_gen_plan.hpp.
 #include "mshgnn_plan.hpp"
 #include "mshgnn_gen_plan.hpp"
+#include "mshgnn_pick.hpp"
 
 using namespace mshgnn;
 
@@ -225,5 +227,38 @@ int mshgnn_hostplan_gen_kernel_count() { return (int)gen::GJobKernel::COUNT; }
 const char* mshgnn_hostplan_gen_kernel_name(int k) { return k >= 0 && k < (int)gen::GJobKernel::COUNT ? gen::GJOB_KERNEL_NAMES[k] : ""; }
 int mshgnn_hostplan_gen_tile_mode(const char* text) { return gen::parse_gen_tile(text); }      // what a value of MSHGNN_GEN_TILE forces (-1: nothing)
 int mshgnn_hostplan_gen_gradw_pick(int split, int su_os, int dhm) { return (int)gen::pick_gradw_kernel(split != 0, su_os, dhm != 0); }
+
+
+// The LDS-resident engine's stack-launch picks (mshgnn_pick.hpp; tests/test_resident_pick.py), n queries a call.  A query is 21 ints, StackQuery's fields in order: plan, op, B,
+// n_cu, use_fused, use_slab, slab_force, use_spec, use_step, stash_nt, gw_phase, n_mlp, sl_hb, sl_blk, fs_blk, x3_alias, node0, n_out, blk, stagger, extra_blk; a pick 16,
+// StackPick's: family, what, NM, HB, NT, TR, FULL, ALIAS, k (a row for mshgnn_hostplan_stack_kernel_name), threads, lds, tiles, slab_prog, red_off, stash_nt, stagger.
+void mshgnn_hostplan_stack_pick(const int32_t* query, int32_t* out, int n) {
+    for (int i = 0; i < n; ++i, query += 21, out += 16) {
+        pick::StackQuery q;
+        q.plan = query[0]; q.op = query[1]; q.B = query[2]; q.n_cu = query[3]; q.use_fused = query[4] != 0; q.use_slab = query[5] != 0; q.slab_force = query[6] != 0;
+        q.use_spec = query[7] != 0; q.use_step = query[8] != 0; q.stash_nt = query[9]; q.gw_phase = query[10]; q.n_mlp = query[11]; q.sl_hb = query[12]; q.sl_blk = query[13];
+        q.fs_blk = query[14]; q.x3_alias = query[15] != 0; q.node0 = query[16]; q.n_out = query[17]; q.blk = query[18]; q.stagger = query[19]; q.extra_blk = query[20];
+        const pick::StackPick r = pick::pick_stack(q);
+        const int32_t v[16] = {r.family, r.what, r.NM, r.HB, r.NT, r.TR, r.FULL, r.ALIAS, r.k, r.threads, r.lds, r.tiles, r.slab_prog, r.red_off, r.stash_nt, r.stagger};
+        std::memcpy(out, v, sizeof v);
+    }
+}
+int mshgnn_hostplan_stack_kernel_count(int family) { return pick::family_rows(family); }
+const char* mshgnn_hostplan_stack_kernel_name(int family, int k) { return pick::kernel_name(family, k); }
+int mshgnn_hostplan_spec_form(int plan, int kind, int tr, int nt, int full) { return pick::spec_form(plan, kind, tr, nt, full); }
+int64_t mshgnn_hostplan_red_need(int threads) { return pick::red_need(threads); }
+// The encoder pick.  facts: 10 ints, EncFacts' fields in order (series, stats, sign, label_rows, wide_bytes, x_given, aligned, src_routes, wide_needs_rows, 0); out: form,
+// label workgroups, error code (include/mshgnn.h).
+void mshgnn_hostplan_enc_pick(const int32_t* facts, int32_t* out, int n) {
+    for (int i = 0; i < n; ++i, facts += 10, out += 3) {
+        pick::EncFacts f;
+        f.series = facts[0] != 0; f.stats = facts[1] != 0; f.sign = facts[2]; f.label_rows = facts[3]; f.wide_bytes = facts[4]; f.x_given = facts[5] != 0; f.aligned = facts[6] != 0;
+        f.src_routes = facts[7] != 0; f.wide_needs_rows = facts[8] != 0;
+        const pick::EncPick r = pick::pick_enc(f);
+        out[0] = r.form; out[1] = (int32_t)r.label_wgs; out[2] = r.err;
+    }
+}
+int mshgnn_hostplan_enc_form_count() { return pick::ENC_FORMS; }
+const char* mshgnn_hostplan_enc_form_name(int form) { return form >= 0 && form < pick::ENC_FORMS ? pick::ENC_FORM_NAMES[form] : ""; }
 
 }  // extern "C"

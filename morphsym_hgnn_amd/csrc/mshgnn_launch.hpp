@@ -1,8 +1,10 @@
 // The host side of a launch, once for the three precisions of the LDS-resident engine: what turns a StepCall into kernel arguments.  The fp32 / bf16 plans
-// (forward_impl / backward_impl, mshgnn.hip) and the split-bf16 plan (x3_forward / x3_backward, mshgnn_x3.hip) keep their own kernel selection and their own
-// launches; every argument struct they pass is filled here.  What differs between the plans is a LaunchTraits constant, never a second copy of a fill.
+// (forward_impl / backward_impl, mshgnn.hip) and the split-bf16 plan (x3_forward / x3_backward, mshgnn_x3.hip) keep their own launch tables; every argument struct they
+// pass is filled here, and which row of a table a launch takes is mshgnn_pick.hpp's decision (pick_stack / pick_enc), queried and applied here.  What differs between the
+// plans is a LaunchTraits constant, never a second copy of a fill.
 #pragma once
 #include "mshgnn_device.hpp"
+#include "mshgnn_pick.hpp"
 
 struct LaunchTraits {
     int in_bytes;           // element size of the encoder's input rows (the split plan reads fp32)
@@ -94,21 +96,22 @@ inline int prep_and_enc_args(const mshgnn_plan* p, const StepCall& c, const mshg
     return MSHGNN_OK;
 }
 
-// where the encoder's rows come from: the plan's kernel ladder switches on this.  Adds the label workgroups of a series route to the grid.
-enum class EncRoute { SERIES_STD, SERIES, WIDE8, WIDE4, ALIGNED, ELEMENTWISE };
-inline int pick_enc_route(const StepCall& c, const EncArgs& a, const LaunchTraits& tr, unsigned& grid, EncRoute& route) {
-    route = a.aligned ? EncRoute::ALIGNED : EncRoute::ELEMENTWISE;
-    if (!tr.src_routes) return c.wide ? set_err(MSHGNN_EUNSUPPORTED, "wide source rows: not on the fp32 plan (cast the inputs)") : MSHGNN_OK;
-    if (c.series) {      // inputs gathered from the sequence's series; x = the window buffers the rows are materialised into (may be null)
-        if (c.x && !a.aligned) return set_err(MSHGNN_EINVAL, tr.series_rows_err);
-        grid += (unsigned)((c.series->lab.B + 255) / 256);      // the label workgroups
-        route = c.series->stats ? EncRoute::SERIES_STD : EncRoute::SERIES;
-    } else if (c.wide) {      // (mshgnn_*_src) the caller's fp64 / fp32 rows: converted by the encoder, plan-dtype rows written to x on the side
-        if ((c.x || tr.wide_needs_rows) && !a.aligned) return set_err(MSHGNN_EINVAL, tr.wide_rows_err);
-        route = c.wide->bytes == 8 ? EncRoute::WIDE8 : EncRoute::WIDE4;
-    }
+// where the encoder's rows come from: the facts of the call for pick_enc (mshgnn_pick.hpp), its refusals in this plan's words.  Adds the label workgroups of a series
+// route to the grid; form: the row of the plan's encoder table (pick::EncForm).
+inline int pick_enc_form(const StepCall& c, const EncArgs& a, const LaunchTraits& tr, unsigned& grid, int& form) {
+    pick::EncFacts f;
+    f.series = c.series != nullptr; f.wide_bytes = c.wide ? (c.wide->bytes == 8 ? 8 : 4) : 0; f.x_given = c.x != nullptr; f.aligned = a.aligned != 0;
+    if (c.series) { f.stats = c.series->stats != nullptr; f.sign = c.series->sign; f.label_rows = (int)c.series->lab.B; }
+    f.src_routes = tr.src_routes; f.wide_needs_rows = tr.wide_needs_rows;
+    const pick::EncPick pk = pick::pick_enc(f);
+    if (pk.err == MSHGNN_EUNSUPPORTED) return set_err(pk.err, "wide source rows: not on the fp32 plan (cast the inputs)");
+    if (pk.err) return set_err(pk.err, c.series ? tr.series_rows_err : tr.wide_rows_err);
+    grid += pk.label_wgs; form = pk.form;
     return MSHGNN_OK;
 }
+// the sources an encoder form reads (the others stay empty)
+inline SeriesSrc enc_series_src(const StepCall& c, int form) { return pick::enc_form_series(form) ? *c.series : SeriesSrc{}; }
+inline WideSrc enc_wide_src(const StepCall& c, int form) { return pick::enc_form_wide(form) ? *c.wide : WideSrc{}; }
 
 // ---- decoder backward (the launch of its own: two-call training, plans without a fused tail)
 inline void fill_dec_bwd_args(const mshgnn_plan* p, const StepCall& c, const mshgnn_ws_layout& lay, DecArgs& a) {
@@ -147,15 +150,33 @@ inline void fill_stack_tail(const mshgnn_plan* p, StepCall& c, const mshgnn_ws_l
     }
     c.dec_done = c.y_fused() || c.labels_fused();
 }
-// One-launch step: the tail's reduction scratch (red_need bytes: one decoder slab per wave) must not touch the out-type nodes' blocks, which receive dX_L for the backward
-// sweep.  It sits in the blocks in front of them, or (models whose out type comes first: the centroidal-momentum ones) in the blocks behind them, inside lds_extent
-// (bf16: the launch's LDS; split plan: the hi plane).  False: neither fits, no one-launch step.
-inline bool place_red_scratch(int node0, int n_out, int blk_bytes, size_t red_need, size_t lds_extent, StackArgs& a) {
-    const size_t red_back = (size_t)(node0 + n_out) * blk_bytes;
-    const bool red_front_ok = (size_t)node0 * blk_bytes >= red_need, red_back_ok = red_back + red_need <= lds_extent;
-    if (!red_front_ok && !red_back_ok) return false;
-    a.red_off = red_front_ok ? 0 : (int)red_back;
-    return true;
+// ---- the stack launch: the pick's query from the plan and the call (every use_* / slab / program switch of the plan is read here and nowhere else on the launch path),
+// the pick's fields into the kernel arguments, the launch of the picked row
+using StackKernelFn = void (*)(StackArgs);
+inline pick::StackQuery stack_query(const mshgnn_plan* p, const StepCall& c, int plan, int op, int blk, const StackArgs& a) {
+    const HostPlan& hp = p->hp;
+    pick::StackQuery q;
+    q.plan = plan; q.op = op; q.B = (int)c.batch; q.n_cu = p->n_cu;
+    q.use_fused = p->use_fused; q.use_slab = p->use_slab; q.slab_force = p->slab_force; q.use_spec = p->use_spec; q.use_step = p->use_step;
+    q.stash_nt = a.stash_nt; q.gw_phase = c.gw_phase;
+    q.n_mlp = hp.n_mlp; q.sl_hb = hp.sl_hb; q.sl_blk = hp.sl_blk; q.fs_blk = hp.fs_blk; q.x3_alias = hp.x3_alias;
+    q.node0 = a.node0; q.n_out = a.n_out; q.blk = blk; q.stagger = p->stagger; q.extra_blk = FS_EXTRA_BLK;
+    return q;
+}
+inline int forward_op(const StepCall& c) { return c.dec_done ? pick::OP_FWD_LOSS : c.training ? pick::OP_FWD_TRAIN : pick::OP_FWD_EVAL; }
+// program tables, scratch offset, store policy and stagger of the picked launch
+inline void apply_stack_pick(const HostPlan& hp, const pick::StackPick& pk, const mshgnn_ws_layout& lay, StackArgs& a) {
+    const int* fwd = pk.slab_prog ? hp.sl_fwd_off : hp.fs_fwd_off;
+    const int* bwd = pk.slab_prog ? hp.sl_bwd_off : hp.fs_bwd_off;
+    for (int l = 0; l < hp.L; ++l) { a.prog_off[l] = pk.what == pick::BWD ? bwd[l] : fwd[l]; if (pk.what == pick::STEP) a.prog_off_b[l] = bwd[l]; }
+    if (pk.what != pick::FWD) a.mask0_off = lay.dd[0];
+    a.red_off = pk.red_off; a.stash_nt = pk.stash_nt; a.stagger = pk.stagger;
+}
+inline int launch_stack(StackKernelFn kernel, const pick::StackPick& pk, hipStream_t st, const StackArgs& a) {
+    if (!kernel) return set_err(MSHGNN_EHIP, std::string("no kernel in the launch table for ") + pick::kernel_name(pk.family, pk.k));
+    hipLaunchKernelGGL(kernel, dim3(pk.tiles), dim3(pk.threads), pk.lds, st, a);
+    HIPCHK(hipGetLastError());
+    return MSHGNN_OK;
 }
 
 // ---- weight gradients: every lane of the step, or the lanes of one phase of a two-phase step (c.gw_phase)

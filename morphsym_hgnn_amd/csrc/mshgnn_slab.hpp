@@ -700,6 +700,7 @@ template <typename T, int NM, int HB, class SP, int TR, int NT, bool FULL = true
 }
 // The kernels over the compile-time programs are instantiated in their own translation units -- mshgnn_spec_shard.hip compiled with -DMSHGNN_SPEC_SHARD=1..7 (csrc/Makefile:
 // mshgnn_spec<k>.o), one program each (MSHGNN_SPEC_LIST_<k>), side by side with the rest of the library.  A shard exports one
-// selector: kind 0 = one-call step, 1 = forward alone (tr: training), 2 = backward alone; nt = the launch's stash store policy (stash_nt_for); name: the program's name.
-#define SPEC_SHARD_DECL(k) StackKernel spec_shard##k(const HostPlan& hp, int kind, int tr, int nt, int full, const char** name);
+// selector: row `form` (pick::SpecForm: which forms exist is pick::spec_form's rule, mshgnn_pick.hpp) of the launch table of the program whose tables are the plan's, and
+// that program's name; nullptr and no name where the shard's program is another plan's.
+#define SPEC_SHARD_DECL(k) StackKernel spec_shard##k(const HostPlan& hp, int form, const char** name);
 SPEC_SHARD_LIST(SPEC_SHARD_DECL)

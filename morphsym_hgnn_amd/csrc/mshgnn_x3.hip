@@ -85,15 +85,15 @@ __global__ __launch_bounds__(LAYER_THREADS, 2) void k_stack_bwd_x3(StackArgs a) 
     stack_bwd_x3_body<false>(a, smem);
 }
 
-using SpecSelectorX3 = StackKernelX3 (*)(const HostPlan& hp, int kind, const char** name);
-static StackKernelX3 x3_spec_kernel(const HostPlan& hp, int kind, const char** name = nullptr) {
-    if (hp.jit_prog) if (StackKernelX3 kk = reinterpret_cast<SpecSelectorX3>(hp.jit_prog)(hp, kind, name)) return kk;      // a program compiled for this plan after the build
-#define X3_SHARD_TRY(k) if (StackKernelX3 kk = x3_spec_shard##k(hp, kind, name)) return kk;
+// row `form` (pick::SpecFormX3) of the launch table of the program whose tables are the plan's (a shard's, or the program attached after the build); name: the program's
+using SpecSelectorX3 = StackKernelX3 (*)(const HostPlan& hp, int form, const char** name);
+static StackKernelX3 x3_spec_kernel(const HostPlan& hp, int form, const char** name = nullptr) {
+    if (hp.jit_prog) if (StackKernelX3 kk = reinterpret_cast<SpecSelectorX3>(hp.jit_prog)(hp, form, name)) return kk;      // a program compiled for this plan after the build
+#define X3_SHARD_TRY(k) if (StackKernelX3 kk = x3_spec_shard##k(hp, form, name)) return kk;
     SPEC_SHARD_LIST(X3_SHARD_TRY)
 #undef X3_SHARD_TRY
     return nullptr;
 }
-static StackKernelX3 x3_step_spec_kernel(const HostPlan& hp, const char** name = nullptr) { return x3_spec_kernel(hp, 0, name); }
 
 
 // ------------------------------------------------------------------------------------------------------
@@ -396,19 +396,32 @@ void x3_launch_prep(const PrepArgs& a, bool biases, hipStream_t st) {
     else hipLaunchKernelGGL(k_prep_x3, dim3(prep_grid(a, 8, biases)), dim3(256), 0, st, a);
 }
 
+// launch tables: row k is what pick_stack / pick_enc (mshgnn_pick.hpp) call k on this plan
+static constexpr StackKernelX3 X3_TABLE[pick::X3_ROWS] = {k_stack_fwd_x3<false>, k_stack_fwd_x3<true>, k_stack_bwd_x3, k_stack_step_x3<false>, k_stack_step_x3<true>};
+using EncKernelX3 = void (*)(EncArgs, int, SeriesSrc, WideSrc);
+static constexpr EncKernelX3 ENC_X3_TABLE[pick::ENC_FORMS] = {      // by pick::EncForm
+    k_enc_x3<false>, k_enc_x3<true>, k_enc_x3<true, false, 4>, k_enc_x3<true, false, 8>,
+    k_enc_x3<true, true>, k_enc_x3<true, true, 0, true>, k_enc_x3<true, true, 0, false, true>, k_enc_x3<true, true, 0, true, true>,
+    k_enc_x3<true, true, 0, false, true, true>, k_enc_x3<true, true, 0, true, true, true>};
+static_assert(pick::STACK8_THREADS == LAYER_THREADS, "the pick's block size of this plan's stack kernels");
+template <typename K, size_t N> static int set_lds_attrs(const K (&table)[N], int bytes) {
+    for (K k : table) if (int rc = set_lds_attr(k, bytes)) return rc;
+    return MSHGNN_OK;
+}
+static StackKernelX3 x3_stack_kernel(const HostPlan& hp, const pick::StackPick& pk) {
+    return pk.family == pick::X3 ? X3_TABLE[pk.k] : pk.family == pick::X3_SPEC ? x3_spec_kernel(hp, pk.k) : nullptr;
+}
+
 static int x3_lds_stack(const HostPlan& hp) { return 2 * hp.fs_blk * P16::BLK; }
 
 // the kernels over this plan's compile-time program, if it has one (built in, or attached): dynamic-LDS attribute, name; else use_spec = false
 static int x3_set_spec_attrs(mshgnn_plan* p) {
-    int rc;
-    const int flds = x3_lds_stack(p->hp);
     const char* nm = nullptr;
-    if (StackKernelX3 k = x3_step_spec_kernel(p->hp, &nm)) {
-        if ((rc = set_lds_attr(k, flds)) || (rc = set_lds_attr(x3_spec_kernel(p->hp, 1), flds)) || (rc = set_lds_attr(x3_spec_kernel(p->hp, 2), flds))) return rc;
-        p->spec_name_buf = strncmp(nm, "spec::", 6) == 0 ? nm + 6 : nm;
-        p->spec_name = p->spec_name_buf.c_str();
-    }
-    else p->use_spec = false;
+    for (int form = 0; form < pick::SPEC_FORMS_X3; ++form)
+        if (StackKernelX3 k = x3_spec_kernel(p->hp, form, &nm)) { if (int rc = set_lds_attr(k, x3_lds_stack(p->hp))) return rc; } else break;      // (no program: no form)
+    if (!nm) { p->use_spec = false; return MSHGNN_OK; }
+    p->spec_name_buf = strncmp(nm, "spec::", 6) == 0 ? nm + 6 : nm;
+    p->spec_name = p->spec_name_buf.c_str();
     return MSHGNN_OK;
 }
 // mshgnn_plan_attach_program on a split plan: `selector` is the mshgnn_jit_program_x3 of a program compiled for this plan
@@ -416,7 +429,7 @@ int x3_attach_program(mshgnn_plan* p, void* selector) {
     void* const prev = p->hp.jit_prog;
     p->hp.jit_prog = selector;
     const char* nm = nullptr;
-    if (!reinterpret_cast<SpecSelectorX3>(selector)(p->hp, 0, &nm) || !nm) { p->hp.jit_prog = prev; return set_err(MSHGNN_EINVAL, "the program's tables are not this plan's"); }
+    if (!reinterpret_cast<SpecSelectorX3>(selector)(p->hp, pick::SFX_STEP, &nm) || !nm) { p->hp.jit_prog = prev; return set_err(MSHGNN_EINVAL, "the program's tables are not this plan's"); }
     p->use_spec = true;
     const int rc = x3_set_spec_attrs(p);
     if (rc || !p->use_spec) { p->hp.jit_prog = prev; p->use_spec = false; return rc ? rc : set_err(MSHGNN_EINVAL, "no kernel of the attached program could be used"); }
@@ -427,10 +440,7 @@ int x3_set_attrs(mshgnn_plan* p) {
     const int flds = x3_lds_stack(p->hp);
     { const char* esp = getenv("MSHGNN_SPEC"); p->use_spec = !(esp && atoi(esp) == 0); }
     if (p->use_spec && (rc = x3_set_spec_attrs(p))) return rc;
-    if ((rc = set_lds_attr(k_stack_fwd_x3<false>, flds)) || (rc = set_lds_attr(k_stack_fwd_x3<true>, flds)) || (rc = set_lds_attr(k_stack_bwd_x3, flds)) ||
-        (rc = set_lds_attr(k_stack_step_x3<false>, flds)) || (rc = set_lds_attr(k_stack_step_x3<true>, flds)) ||
-        (rc = set_lds_attr(k_enc_x3<true>, 8 * P16::BLK)) || (rc = set_lds_attr(k_enc_x3<false>, 8 * P16::BLK)) ||
-        (rc = set_lds_attr(k_enc_x3<true, true>, 8 * P16::BLK)) || (rc = set_lds_attr(k_enc_x3<true, false, 8>, 8 * P16::BLK)) || (rc = set_lds_attr(k_enc_x3<true, false, 4>, 8 * P16::BLK))) return rc;
+    if ((rc = set_lds_attrs(X3_TABLE, flds)) || (rc = set_lds_attrs(ENC_X3_TABLE, 8 * P16::BLK))) return rc;
     return MSHGNN_OK;
 }
 
@@ -454,52 +464,25 @@ int x3_forward(const mshgnn_plan* p, StepCall& c) {
     hipStream_t st = c.stream;
     int rc;
     {   // 1. hi / lo weight images (few packs: the layer packs under the encoder's tail, enc_prep_split), 2. encoder (fp32 inputs)
-        EncArgs a{}; unsigned enc_grid = 0; EncRoute route;
+        EncArgs a{}; unsigned enc_grid = 0; int form = 0;
         if ((rc = prep_and_enc_args(p, c, lay, tr, x3_launch_prep, a, enc_grid))) return rc;
         ProfScope ps(p, hp.ks_enc, st);
-        if ((rc = pick_enc_route(c, a, tr, enc_grid, route))) return rc;
-        unsigned enc_lds = tr.enc_lds;
-        auto enc = [&](auto kernel, const SeriesSrc& ser, const WideSrc& wsrc) { hipLaunchKernelGGL(kernel, dim3(enc_grid), dim3(256), enc_lds, st, a, hp.n_img, ser, wsrc); };
-        const bool orbit = (route == EncRoute::SERIES_STD || route == EncRoute::SERIES) && (c.series->sign >> MSHGNN_WINDOW_ELEMENTS_SHIFT) != 0;      // K > 1: a group element per window
-        if (route == EncRoute::SERIES_STD && orbit) enc(k_enc_x3<true, true, 0, true, true, true>, *c.series, WideSrc{});
-        else if (route == EncRoute::SERIES && orbit) enc(k_enc_x3<true, true, 0, false, true, true>, *c.series, WideSrc{});
-        else if (route == EncRoute::SERIES_STD && c.series->sign) enc(k_enc_x3<true, true, 0, true, true>, *c.series, WideSrc{});
-        else if (route == EncRoute::SERIES && c.series->sign) enc(k_enc_x3<true, true, 0, false, true>, *c.series, WideSrc{});
-        else if (route == EncRoute::SERIES_STD) enc(k_enc_x3<true, true, 0, true>, *c.series, WideSrc{});
-        else if (route == EncRoute::SERIES) enc(k_enc_x3<true, true>, *c.series, WideSrc{});
-        else if (route == EncRoute::WIDE8) enc(k_enc_x3<true, false, 8>, SeriesSrc{}, *c.wide);
-        else if (route == EncRoute::WIDE4) enc(k_enc_x3<true, false, 4>, SeriesSrc{}, *c.wide);
-        else if (route == EncRoute::ALIGNED) enc(k_enc_x3<true>, SeriesSrc{}, WideSrc{});
-        else enc(k_enc_x3<false>, SeriesSrc{}, WideSrc{});
+        if ((rc = pick_enc_form(c, a, tr, enc_grid, form))) return rc;
+        hipLaunchKernelGGL(ENC_X3_TABLE[form], dim3(enc_grid), dim3(256), tr.enc_lds, st, a, hp.n_img, enc_series_src(c, form), enc_wide_src(c, form));
     }
     {   // 3. all layers + decoder (+ loss and decoder backward with a fused loss)
         StackArgs a{};
         x3_stack_args(p, c, lay, a);
         fill_stack_tail(p, c, lay, a);
         a.tile_in = c.ws + lay.x[0]; a.training = c.training;
-        for (int l = 0; l < hp.L; ++l) a.prog_off[l] = hp.fs_fwd_off[l];
-        const int tiles = ((int)c.batch + P16::ROWS - 1) / P16::ROWS;
         a.stamps = stamp_ptr("MSHGNN_STAMPS");
-        // one-call step: the backward sweep in the same launch, the tail's reduction scratch in the hi plane (place_red_scratch)
-        // (a two-phase step, c.gw_phase >= 0, keeps the backward sweep a launch of its own on this plan; the bf16 plan has no such condition)
-        const bool step = c.gw_phase < 0 && c.dec_done && p->use_step &&
-                          place_red_scratch(a.node0, a.n_out, tr.blk, (size_t)(LAYER_THREADS / 64) * DEC_SLAB_FLOATS * sizeof(float), (size_t)hp.fs_blk * tr.blk, a);
-        ProfScope ps(p, step ? hp.ks_stack_step : hp.ks_stack_fwd, st);
-        if (step) {
-            a.mask0_off = lay.dd[0];
-            for (int l = 0; l < hp.L; ++l) a.prog_off_b[l] = hp.fs_bwd_off[l];
-            StackKernelX3 ks = p->use_spec ? x3_step_spec_kernel(hp) : nullptr;      // (predicated stores: ragged batches run it too)
-            if (ks) hipLaunchKernelGGL(ks, dim3(tiles), dim3(LAYER_THREADS), x3_lds_stack(hp), st, a);
-            else if (hp.x3_alias) hipLaunchKernelGGL(k_stack_step_x3<true>, dim3(tiles), dim3(LAYER_THREADS), x3_lds_stack(hp), st, a);
-            else hipLaunchKernelGGL(k_stack_step_x3<false>, dim3(tiles), dim3(LAYER_THREADS), x3_lds_stack(hp), st, a);
-            c.stack_done = true;
-        } else
-        if (StackKernelX3 kf = p->use_spec ? x3_spec_kernel(hp, 1) : nullptr) hipLaunchKernelGGL(kf, dim3(tiles), dim3(LAYER_THREADS), x3_lds_stack(hp), st, a);
-        else if (hp.x3_alias) hipLaunchKernelGGL(k_stack_fwd_x3<true>, dim3(tiles), dim3(LAYER_THREADS), x3_lds_stack(hp), st, a);
-        else hipLaunchKernelGGL(k_stack_fwd_x3<false>, dim3(tiles), dim3(LAYER_THREADS), x3_lds_stack(hp), st, a);
+        // (a one-call step: the backward sweep in the same launch, the tail's reduction scratch in the hi plane)
+        const pick::StackPick pk = pick::pick_stack(stack_query(p, c, pick::PLAN_X3, forward_op(c), tr.blk, a));
+        apply_stack_pick(hp, pk, lay, a);
+        if (pk.what == pick::STEP) c.stack_done = true;
+        ProfScope ps(p, pk.what == pick::STEP ? hp.ks_stack_step : hp.ks_stack_fwd, st);
+        return launch_stack(x3_stack_kernel(hp, pk), pk, st, a);
     }
-    HIPCHK(hipGetLastError());
-    return MSHGNN_OK;
 }
 
 int x3_backward(const mshgnn_plan* p, const StepCall& c) {
@@ -517,12 +500,11 @@ int x3_backward(const mshgnn_plan* p, const StepCall& c) {
     if (c.gw_phase != 1 && !c.stack_done) {
         StackArgs a{};
         x3_stack_args(p, c, lay, a);
-        a.tile_in = c.ws + lay.dx[hp.L]; a.training = 1; a.mask0_off = lay.dd[0];
-        for (int l = 0; l < hp.L; ++l) a.prog_off[l] = hp.fs_bwd_off[l];
-        const int tiles = (B + P16::ROWS - 1) / P16::ROWS;
+        a.tile_in = c.ws + lay.dx[hp.L]; a.training = 1;
+        const pick::StackPick pk = pick::pick_stack(stack_query(p, c, pick::PLAN_X3, pick::OP_BWD, tr.blk, a));
+        apply_stack_pick(hp, pk, lay, a);
         ProfScope ps(p, hp.ks_stack_bwd, st);
-        if (StackKernelX3 kb = p->use_spec ? x3_spec_kernel(hp, 2) : nullptr) hipLaunchKernelGGL(kb, dim3(tiles), dim3(LAYER_THREADS), x3_lds_stack(hp), st, a);
-        else hipLaunchKernelGGL(k_stack_bwd_x3, dim3(tiles), dim3(LAYER_THREADS), x3_lds_stack(hp), st, a);
+        if (int rc = launch_stack(x3_stack_kernel(hp, pk), pk, st, a)) return rc;
     }
     const int gw_parts = gw_parts_for(hp.n_parts, hp.n_lanes, hp.gw_ipl, B, tr.gw_windows, p->n_cu);      // window parts of this batch's weight-gradient launch (32-window steps)
     if (c.grad_params) {      // (NULL: activation backward only)

@@ -450,5 +450,5 @@ template <class SP> static bool spec_matches_x3(const HostPlan& hp) {
     }
     return true;
 }
-#define X3_SHARD_DECL(k) StackKernelX3 x3_spec_shard##k(const HostPlan& hp, int kind, const char** name);      // kind 0: one-call step, 1: forward alone, 2: backward alone
+#define X3_SHARD_DECL(k) StackKernelX3 x3_spec_shard##k(const HostPlan& hp, int form, const char** name);      // form: pick::SpecFormX3 (mshgnn_pick.hpp)
 SPEC_SHARD_LIST(X3_SHARD_DECL)
