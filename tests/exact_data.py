@@ -431,3 +431,162 @@ def _check_input_grads(spec, case, ref, inter, stats):
     if any(bool((masks[t] < 0).any()) for t in spec.node_types if need[0][t]):
         assert neg > 0, "(d) no negative symmetry sign meets a non-zero input gradient"
     stats.update(xgrad_sum_bound=bound, xgrad_negative=neg)
+
+
+# ---------------------------------------------------------------------------------------------------
+# the fused cross-entropy steps: cases on which the softmax gradient itself is exact
+# ---------------------------------------------------------------------------------------------------
+CE_SHIFT = 7            # the decoder's weight and bias times 2^CE_SHIFT: logits that differ at all differ by >= 128
+CE_TILE = 16            # windows per tile of the LDS-resident kernels
+
+
+def _pow2(n):
+    return n > 0 and n & (n - 1) == 0
+
+
+def ce_gout(logits, labels, inv_n):
+    """dL/dlogit as the kernels evaluate it in fp32 (m = fmaxf(l0, l1); e_i = expf(l_i - m); se = e0 + e1; g_i = (e_i / se - onehot_i) * inv_n), on the
+    host and in the two regimes ONLY in which no correct expf rounds: a tie (e0 = e1 = 1, se = 2, e_i / se = 0.5) and a saturated pair (|l0 - l1| >= 128:
+    the smaller exponential is exactly 0 -- e^-128 is far below fp32's smallest denormal -- so se = 1 and e_i / se is 1 or 0).  logits fp64 [R, 2] (fp32
+    values), labels [R] in {0, 1}, inv_n an np.float32.  Returns fp64 [R, 2]; any other row raises."""
+    f32 = np.float32
+    l = logits.numpy().astype(f32)
+    assert np.array_equal(l.astype(np.float64), logits.numpy()), "a logit is not an fp32 value"
+    d = l[:, 0].astype(np.float64) - l[:, 1].astype(np.float64)
+    tie, sat = d == 0, np.abs(d) >= 128.0
+    assert bool((tie | sat).all()), f"{int((~(tie | sat)).sum())} logit pairs are neither a tie nor 128 apart: the softmax would round"
+    p0 = np.where(tie, f32(0.5), np.where(d > 0, f32(1.0), f32(0.0))).astype(f32)      # e0 / se
+    p1 = np.where(tie, f32(0.5), np.where(d < 0, f32(1.0), f32(0.0))).astype(f32)
+    lab = labels.numpy().astype(bool)
+    g0 = (p0 - np.where(lab, f32(0.0), f32(1.0)).astype(f32)) * inv_n
+    g1 = (p1 - np.where(lab, f32(1.0), f32(0.0)).astype(f32)) * inv_n
+    return torch.from_numpy(np.stack([g0, g1], axis=1).astype(np.float64))
+
+
+def ce_regimes(logits, labels):
+    """Per row (fp64 logits [R, 2], labels [R]): tie, right (the label is the larger logit), wrong -- boolean tensors."""
+    d = logits[:, 0] - logits[:, 1]
+    tie = d == 0
+    larger = (d < 0).long()
+    right = ~tie & (labels.long() == larger)
+    return tie, right, ~tie & ~right
+
+
+def ce_case(spec, B, seed, wrong_share=0.5, label_seed=0, flip_row=None, **knobs):
+    """`exact_case` for the one-call cross-entropy step of a two-logit classification model: the decoder's weight and bias times 2^CE_SHIFT, so that
+    every (window, output node) is a tie or saturated (asserted), labels drawn per (window, node) from a generator of their own (a saturated row
+    is labelled with its smaller logit with probability `wrong_share`, a tie with either), and
+      gout_ce  the gradient the kernels' fp32 formula gives there (`ce_gout`: 0, +-1 or +-2 units of 0.5 * inv_n, inv_n = fl32(1 / (B n_out))), asserted
+               within 2^-149 per element of the fp64 softmax gradient of the same logits (the true distance is e^-128 / N: fp64 keeps what fp32 drops),
+      loss_ce  the fp64 mean cross entropy, loss_terms its fp64 terms,
+      labels   int32 [B, n_out], counts {"ties", "right", "wrong"}.
+    flip_row: a row of the decoder's weight to negate.  The decoder has one signed entry per row; where l0 - l1 has one sign in every row of a batch (the
+    families' seeds: `check_exact_ce` (ii) refuses that), negating one row changes no magnitude -- closure is what it was -- and gives both signs."""
+    assert spec.out_channels == 2 and not spec.regression, "a two-logit classification model"
+    case = exact_case(spec, B, seed, mse=False, **knobs)
+    case["params"]["decoder.weight"] = case["params"]["decoder.weight"] * 2.0 ** CE_SHIFT
+    if flip_row is not None:
+        case["params"]["decoder.weight"][flip_row] *= -1.0
+    case["params"]["decoder.bias"] = case["params"]["decoder.bias"] * 2.0 ** CE_SHIFT
+    n_out = spec.num_nodes[spec.out_type]
+    logits = reference(spec, case)["out"].view(B * n_out, 2)
+    g = torch.Generator().manual_seed(seed * 7907 + 31 + label_seed)
+    coin = torch.randint(0, 2, (B * n_out,), generator=g)
+    wrong = torch.rand(B * n_out, generator=g, dtype=torch.float64) < wrong_share
+    d = logits[:, 0] - logits[:, 1]
+    larger = (d < 0).long()
+    labels = torch.where(d == 0, coin, torch.where(wrong, 1 - larger, larger))
+    inv_n = np.float32(1.0) / np.float32(B * n_out)
+    gout = ce_gout(logits, labels, inv_n)
+    lg = logits.clone().requires_grad_(True)
+    terms = torch.nn.functional.cross_entropy(lg, labels, reduction="none")
+    terms.mean().backward()
+    err = float((lg.grad - gout).abs().max())
+    assert err <= 2.0 ** -149, f"the fp32 softmax gradient is {err} from the fp64 one"
+    tie, right, wr = ce_regimes(logits, labels)
+    case.update(labels=labels.to(torch.int32).view(B, n_out), gout_ce=gout.reshape(-1), loss_ce=float(terms.detach().mean()), loss_terms=terms.detach(),
+                counts=dict(ties=int(tie.sum()), right=int(right.sum()), wrong=int(wr.sum())), ce_gout_err=err, wrong_share=wrong_share)
+    return case
+
+
+def ce_loss_bound(case):
+    """What the fused fp32 loss may differ from `loss_ce` by, relative to it.  Without ties every term (m + logf(1)) - l_label is 0 or a multiple of 128 and
+    the mean a short dyadic number: 0 (the kernels' loss must be `loss_ce`).  With ties: (gamma_{n+4} + 2^-23), gamma_k = k u / (1 - k u), u = 2^-24, n the
+    number of rows -- an fp32 sum of non-negative terms in any fixed order, and one rounding of logf(2) per tie."""
+    if case["counts"]["ties"] == 0:
+        return 0.0
+    u, k = 2.0 ** -24, case["loss_terms"].numel() + 4
+    return k * u / (1 - k * u) + 2.0 ** -23
+
+
+def check_exact_ce(spec, case, ties, stats=None):
+    """`check_exact` with the case's cross-entropy gradient, plus the coverage that gradient needs:
+      (i)   B * n_out is a power of two (inv_n is one: every non-zero element of gout_ce is +-0.5 inv_n or +-inv_n);
+      (ii)  every output node sees both labels; right and wrong rows each occur with both signs of l0 - l1; a case declared `ties` has a tie under
+            each label, one declared without has none;
+      (iii) from 32 windows on, every regime the case has occurs in the first and in the last 16-window tile;
+    and, for the loss, that the sum of the terms is an fp32 value where the test asks for equality (no ties)."""
+    B = case["B"]
+    n_out = spec.num_nodes[spec.out_type]
+    stats = {} if stats is None else stats
+    assert _pow2(B * n_out), f"(i) B * n_out = {B * n_out} is not a power of two"
+    assert bool((spec.output_mask() == 1).all()), "an output mask other than ones: gout_ce does not model it"
+    ref = check_exact(spec, case, gout=case["gout_ce"], stats=stats)
+    logits = ref["out"].view(B * n_out, 2)
+    labels = case["labels"].reshape(-1).long()
+    assert torch.equal(ce_gout(logits, labels, np.float32(1.0) / np.float32(B * n_out)).reshape(-1), case["gout_ce"]), "gout_ce is not this case's"
+    tie, right, wrong = ce_regimes(logits, labels)
+    pos = logits[:, 0] > logits[:, 1]
+    lab2 = labels.view(B, n_out)
+    for f in range(n_out):
+        assert set(lab2[:, f].tolist()) == {0, 1}, f"(ii) output node {f} sees one label only"
+    for name, reg in (("right", right), ("wrong", wrong)):
+        assert bool((reg & pos).any()) and bool((reg & ~pos).any()), f"(ii) no {name} row with l0 {'>' if not bool((reg & pos).any()) else '<'} l1"
+    if ties:
+        assert bool((tie & (labels == 0)).any()) and bool((tie & (labels == 1)).any()), "(ii) declared with ties: no tie under each label"
+    else:
+        assert not bool(tie.any()), "(ii) declared without ties, yet it has some"
+    if B >= 2 * CE_TILE:
+        for name, reg in (("tie", tie), ("right", right), ("wrong", wrong)):
+            r = reg.view(B, n_out)
+            if bool(reg.any()):
+                assert bool(r[:CE_TILE].any()) and bool(r[(B - 1) // CE_TILE * CE_TILE:].any()), f"(iii) no {name} row in the first or in the last tile"
+    t = case["loss_terms"]
+    if not ties:
+        s = float(t.sum())
+        assert bool((t == torch.round(t / 128.0) * 128.0).all()) and s <= 2.0 ** 24 * 128.0, "the loss terms are not multiples of 128 whose sum fp32 holds"
+        assert float(np.float32(case["loss_ce"])) == case["loss_ce"], "the mean loss is not an fp32 value"
+    else:      # the bound covers a tie's own roundings too: (m + logf(2)) - m rounds at m's magnitude (half an ulp of |m| + 1), logf within 2 ulps of log 2
+        u, s = 2.0 ** -24, float(t.sum())
+        own = float(((logits[tie, 0].abs() + 1.0) * u + 2 * u).sum())
+        n = t.numel()
+        assert own + (n - 1) * u / (1 - (n - 1) * u) * s <= ce_loss_bound(case) * s, "the ties' own roundings do not fit the loss bound"
+    stats.update(case["counts"], loss_bound=ce_loss_bound(case))
+    ref["loss"] = case["loss_ce"]
+    return ref
+
+
+def ce_damaged_variants(spec, case):
+    """(name, gout) of what a subtly wrong cross-entropy tail would hand the backward pass on this case -- each is run through the reference and must change a
+    compared gradient (tests/test_exact_data.py).  The output mask of channel dd taken for dd ^ 1 is not among them: `check_exact_ce` asserts that the mask
+    is all ones on every model with two logits, so that exchange changes nothing there."""
+    B = case["B"]
+    n_out = spec.num_nodes[spec.out_type]
+    N = B * n_out
+    inv_n = np.float32(1.0) / np.float32(N)
+    logits = reference(spec, case)["out"].view(N, 2)
+    labels = case["labels"].long()
+    good = case["gout_ce"].view(B, n_out, 2)
+    tile = (B - 1) // CE_TILE      # the last tile (the only one below 17 windows)
+    rows = slice(tile * CE_TILE, min(B, (tile + 1) * CE_TILE))
+
+    lab = labels.clone()      # one foot's labels from the next window, on one tile
+    lab[rows, 1] = torch.roll(labels[:, 1], -1, 0)[rows]
+    yield "labels of one foot from the next window on one tile", ce_gout(logits, lab.reshape(-1), inv_n).reshape(-1)
+    g = good.clone()
+    g[:, 2] = good[:, 2].flip(-1)
+    yield "the two logits' gradients exchanged on one foot", g.reshape(-1)
+    yield "inv_n of a 64-window sub-step", ce_gout(logits, labels.reshape(-1), np.float32(1.0) / np.float32(64 * n_out)).reshape(-1)
+    g = good.clone()
+    g[rows] = 0.0
+    yield "one 16-window tile left out", g.reshape(-1)

@@ -281,3 +281,89 @@ def rel_max(a, b):
 
 def rel_l2(a, b):
     return float((a.double().cpu() - b.double()).norm() / b.double().norm().clamp_min(1e-30))
+
+
+# ---------------------------------------------------------------------------------------------------
+# the fused cross-entropy tail: cases on which the softmax gradient itself is exact (tests/exact_data.ce_case's construction)
+# ---------------------------------------------------------------------------------------------------
+CE_MATRIX = [      # (row of EXACT_MATRIX, B, seed, wrong share, ties): rows whose number of logit pairs is a power of two, at power-of-two batches
+    ((35, 7, 128, 3, 4), 16, 2, 0.5, True),
+    ((35, 7, 128, 3, 4), 1024, 1, 0.5, True),
+    ((450, 150, 128, 3, 4), 16, 2, 0.5, False),      # (the first seed that closes; it has no ties)
+    ((450, 150, 128, 3, 4), 1024, 1, 0.5, True),
+    ((450, 150, 384, 3, 8), 16, 1, 0.5, True),
+    ((450, 150, 384, 3, 8), 1024, 1, 0.5, True),
+    ((1200, 8, 256, 8, 8), 16, 1, 0.5, False),
+    ((1200, 8, 256, 8, 8), 1024, 2, 0.5, False),
+    ((8100, 150, 128, 8, 8), 16, 1, 0.5, False),
+    ((8100, 150, 128, 8, 8), 1024, 1, 0.5, True),
+    ((8100, 150, 512, 2, 4), 16, 1, 0.5, False),
+    ((8100, 150, 512, 2, 4), 1024, 2, 0.5, False),
+]
+CE_LEFT_OUT = {}      # (row, B): the condition no seed of 1..12 meets -- none: every row of EXACT_MATRIX with 2 or 4 logit pairs closes at seed 1 or 2
+
+
+def ce_case(shape, B, seed, wrong_share=0.5):
+    """`exact_case` with the last layer times 2^CE_SHIFT, labels [B, out / 2] and gout_ce, the gradient the loss tail of k_mlp_stack computes in fp32
+    (inv = fl32(1 / (B out / 2)), csrc/mshgnn_mlp.hip) where every logit pair is a tie or saturated (asserted), held to the fp64 softmax gradient within 2^-149
+    per element; loss_ce the fp64 mean cross entropy, loss_terms its terms, counts per regime."""
+    from tests import exact_data as xd
+    case = exact_case(*shape, B, seed=seed)
+    out_channels = shape[4]
+    W, b = case["params"][-1]
+    case["params"][-1] = (W * 2.0 ** xd.CE_SHIFT, b * 2.0 ** xd.CE_SHIFT)
+    N = B * out_channels // 2
+    logits = reference(case["params"], case["x"])["out"].reshape(N, 2)
+    g = torch.Generator().manual_seed(seed * 7907 + 57)
+    coin = torch.randint(0, 2, (N,), generator=g)
+    wrong = torch.rand(N, generator=g, dtype=torch.float64) < wrong_share
+    d = logits[:, 0] - logits[:, 1]
+    larger = (d < 0).long()
+    labels = torch.where(d == 0, coin, torch.where(wrong, 1 - larger, larger))
+    gout = xd.ce_gout(logits, labels, np.float32(1.0) / np.float32(N))
+    lg = logits.clone().requires_grad_(True)
+    terms = nn.functional.cross_entropy(lg, labels, reduction="none")
+    terms.mean().backward()
+    err = float((lg.grad - gout).abs().max())
+    assert err <= 2.0 ** -149, f"the fp32 softmax gradient is {err} from the fp64 one"
+    tie, right, wr = xd.ce_regimes(logits, labels)
+    case.update(labels=labels.to(torch.int32).view(B, out_channels // 2), gout_ce=gout.view(B, out_channels), loss_ce=float(terms.detach().mean()),
+                loss_terms=terms.detach(), counts=dict(ties=int(tie.sum()), right=int(right.sum()), wrong=int(wr.sum())), ce_gout_err=err)
+    del case["y"], case["gout_mse"]      # (the MSE targets belong to the unscaled last layer)
+    return case
+
+
+def check_exact_ce(case, ties):
+    """`check_exact` for gout_ce, plus: the number of logit pairs is a power of two; every pair column sees both labels; right and wrong pairs each occur with
+    both signs of l0 - l1; a case declared `ties` has a tie under each label, one declared without has none; from 32 rows on every regime occurs in the first
+    and in the last 16-row tile; without ties the loss terms are multiples of 128 and their mean an fp32 value."""
+    from tests import exact_data as xd
+    B, pairs = case["labels"].shape
+    N = B * pairs
+    assert N & (N - 1) == 0, f"{N} logit pairs: not a power of two"
+    ref = check_exact(case, "gout_ce")
+    logits, labels = ref["out"].reshape(N, 2), case["labels"].reshape(-1).long()
+    assert torch.equal(xd.ce_gout(logits, labels, np.float32(1.0) / np.float32(N)).view_as(case["gout_ce"]), case["gout_ce"])
+    tie, right, wrong = xd.ce_regimes(logits, labels)
+    pos = logits[:, 0] > logits[:, 1]
+    for p in range(pairs):
+        assert set(case["labels"][:, p].tolist()) == {0, 1}, f"logit pair {p} sees one label only"
+    for name, reg in (("right", right), ("wrong", wrong)):
+        assert bool((reg & pos).any()) and bool((reg & ~pos).any()), f"{name} pairs have one sign of l0 - l1 only"
+    if ties:
+        assert bool((tie & (labels == 0)).any()) and bool((tie & (labels == 1)).any()), "declared with ties: no tie under each label"
+    else:
+        assert not bool(tie.any()), "declared without ties, yet it has some"
+        t = case["loss_terms"]
+        assert bool((t == torch.round(t / 128.0) * 128.0).all()) and float(np.float32(case["loss_ce"])) == case["loss_ce"]
+    if ties:      # the loss bound covers a tie's own roundings: (logf(2) + m) - m rounds at m's magnitude, logf within 2 ulps of log 2 (exact_data.check_exact_ce)
+        u, t = 2.0 ** -24, case["loss_terms"]
+        own = float(((logits[tie, 0].abs() + 1.0) * u + 2 * u).sum())
+        assert own + (N - 1) * u / (1 - (N - 1) * u) * float(t.sum()) <= xd.ce_loss_bound(case) * float(t.sum()), "the ties' own roundings do not fit the loss bound"
+    if B >= 32:
+        for name, reg in (("tie", tie), ("right", right), ("wrong", wrong)):
+            r = reg.view(B, pairs)
+            if bool(reg.any()):
+                assert bool(r[:16].any()) and bool(r[(B - 1) // 16 * 16:].any()), f"no {name} pair in the first or in the last tile"
+    ref["loss"] = case["loss_ce"]
+    return ref

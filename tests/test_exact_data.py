@@ -4,12 +4,15 @@ input-gradient closure and coverage; the families' cases have the live base node
 comparison the GPU files rely on flags a single-ulp change, and a single wrong element of a base row or of a base-path gradient.
 For tests/test_exact_generic_gpu.py (the generic-width engine) also: every aggregate the engine stages as one operand row is a bf16 value, the base node of
 a many-limb model is a live destination of as many rows as its name says, the random topologies hold a repeated edge, an empty relation and a node without
-in-edges -- and the comparison flags one dropped row of a long sum, a repeated edge counted once and a mean scaled by the wrong degree."""
+in-edges -- and the comparison flags one dropped row of a long sum, a repeated edge counted once and a mean scaled by the wrong degree.
+For tests/test_exact_ce_gpu.py (the fused cross-entropy steps): every (model, batch, seed, wrong share) closes with the softmax gradient the kernels' fp32 formula
+gives, covers both labels per foot and every regime (tie, right, wrong) it declares -- and what a subtly wrong cross-entropy tail would compute changes a gradient."""
 import pytest
 import torch
 
 from tests import exact_data as xd
 from tests import helpers
+from tests import test_exact_ce_gpu as cex
 from tests import test_exact_families_gpu as fam
 from tests import test_exact_generic_gpu as gen
 from tests import test_exact_gpu as gx
@@ -332,3 +335,48 @@ def test_operator_path_case_closes_in_the_operator_algebra(model, B):
     top = max(max(w.values()) for w in worst.values())
     assert 0 < top < 1.0
     print(f"\n{model} B={B}: {len(worst)} operator calls, largest sum of |terms| {top:.2e} of the fp32 limit")
+
+
+# ---------------------------------------------------------------------------------------------------
+# the fused cross-entropy steps' cases (tests/test_exact_ce_gpu.py)
+# ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("model,B", sorted(cex.CE_CASES))
+def test_ce_case_is_rounding_free_and_covering(model, B):
+    """(a)-(c) with the cross-entropy gradient and (i)-(iii) of exact_data.check_exact_ce for every (model, batch, seed, wrong share) of the GPU file; the
+    gradient is the fp64 softmax's to 2^-149 per element; the generic engine's cases stage bf16 aggregates only."""
+    c = cex.CE_CASES[(model, B)]
+    spec, case, ref, stats = cex._reference.__wrapped__(model, B)
+    assert stats["fwd_sum_bound"] <= 1.0 and stats["bwd_sum_bound"] <= 1.0 and stats["zero_decisions"] > 0
+    assert case["ce_gout_err"] <= 2.0 ** -149 and bool(c["ties"]) == (stats["ties"] > 0)
+    assert stats["ties"] + stats["right"] + stats["wrong"] == B * spec.num_nodes[spec.out_type] and stats["right"] > 0 and stats["wrong"] > 0
+    assert ref["loss"] == case["loss_ce"] > 0 and (stats["loss_bound"] == 0.0) == (not c["ties"])
+    if (model, B) in cex.GENERIC_CASES:
+        assert stats["aggregates_not_bf16"] == [], stats["aggregates_not_bf16"][:5]
+    print(f"\n{model} B={B}: seed {c['seed']}, wrong share {c['wrong_share']}, label seed {c['label_seed']}, flip_row {c.get('flip_row')}: ties / right / wrong = {stats['ties']} / {stats['right']} / "
+          f"{stats['wrong']}, bwd_sum_bound {stats['bwd_sum_bound']:.3f}, |fp64 softmax gradient - gout| <= {case['ce_gout_err']:.1e}, loss {case['loss_ce']!r}")
+
+
+def test_ce_matrix_has_the_cases_with_ties_it_must():
+    assert all(cex.CE_CASES[(cex.LDS_MODEL, B)]["ties"] for B in (16, 1024))
+    assert any(c["ties"] for (m, B), c in cex.CE_CASES.items() if "_h256_" in m or "_h384_" in m)
+    assert not set(cex.CE_CASES) & set(cex.LEFT_OUT)
+    assert {(cex.LDS_MODEL, B) for B in cex.LDS_BATCHES} | set(cex.FAMILY_CASES) | set(cex.GENERIC_CASES) == set(cex.CE_CASES)
+
+
+@pytest.mark.parametrize("B", [16, 1024])
+def test_comparison_flags_a_damaged_cross_entropy_tail(B):
+    """What a wrong softmax tail would hand the backward pass (exact_data.ce_damaged_variants: one foot's labels from the next window on one tile, the two
+    logits' gradients exchanged on one foot, the inv_n of a 64-window sub-step, one 16-window tile left out), run through the oracle, changes at least
+    one gradient tensor the GPU file compares; the undamaged gradient changes none.  The output mask of channel dd taken for dd ^ 1 cannot show: the mask of
+    every two-logit model is all ones (asserted)."""
+    spec, case, ref, _ = cex._reference.__wrapped__(cex.LDS_MODEL, B)
+    assert bool((spec.output_mask() == 1).all())
+    assert _flagged(spec, ref, B, dict(hidden=ref["hidden"], grads=xd.reference(spec, case, case["gout_ce"])["grads"])) == ([], [])
+    names = []
+    for name, gout in xd.ce_damaged_variants(spec, case):
+        assert not torch.equal(gout, case["gout_ce"]), name
+        got = xd.reference(spec, case, gout)
+        bad_h, bad_g = _flagged(spec, ref, B, got)
+        assert bad_h == [] and bad_g, name
+        names.append(name)
+    assert len(names) == 4

@@ -18,7 +18,7 @@ Batches: every family at 17 windows (one whole tile plus one window) and at 1000
 COM L4, at 8193 (past the slab threshold; the stash store policy and the tile staircase change the launch there).
 Routes: regression families run the one-call step on the bf16 plan's default kernels, MSHGNN_SLAB=0, MSHGNN_FUSED=0, MSHGNN_STASH_NT=1, the split plan and
 the fp32 plan, then the two-call route, the two-phase step and the fp64-source step on the bf16 and split defaults.  Classification families run logits,
-hidden states and backward(gout) (the softmax step is not exact and stays on the tolerance tests).  Every family also runs at 17 windows through the
+hidden states and backward(gout) (their one-call cross-entropy step: tests/test_exact_ce_gpu.py, on cases where the softmax gradient is exact).  Every family also runs at 17 windows through the
 generic-width engine forced with MSHGNN_ENGINE=generic (bf16 and split), A1-C2 L4 and Solo K4 COM L4 at hidden 256 as well.
 Not covered, and why:
   * MiniCheetah-C2 classification at 5 layers: none of seeds 1..12 closes it at 17 windows (X4.joint leaves bf16), so its base-destination path is

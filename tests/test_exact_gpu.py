@@ -17,8 +17,8 @@ Matrix of this file (3 layers: the base nodes are dead, need[0]["base"] == []):
   * The generic-width engine (mshgnn_gen.hip), bf16 and split arithmetic, at hidden 256 (50 and 300 windows: 64- and 128-window tiles, ragged ones) and 1024
     (70 windows; the width whose seed-6 random case test_generic_gpu.py had to swap out: a cancelling gradient needs no tolerance here).
   * The padded engine at hidden 200 (zero-padded to 256, which the generic engine serves: no two-phase step there), bf16 and split.
-  * MiniCheetah-K4 contact classification at 3 layers: logits and backward(gout) (the one-call cross-entropy step is not exact -- softmax -- and stays on the
-    tolerance tests).
+  * MiniCheetah-K4 contact classification at 3 layers: logits and backward(gout).  The fused cross-entropy steps (step_ce, backward_ce) are pinned by
+    tests/test_exact_ce_gpu.py on cases whose every logit pair is a tie or saturated, where the fp32 softmax gradient itself is exact.
 Matrix of tests/test_exact_families_gpu.py (this file's table, comparisons and routes; base nodes live), at 17 and 1000 windows unless said otherwise:
   * A1-C2 at 4 layers (base encoder and base -> joint relations; also 16 and 8193 windows, also MSHGNN_PRUNE=0) and at 5 layers (the base is a destination:
     relations into base, base_transform, base rows of a stack layer; also over the programs compiled on demand, jit.py).
@@ -33,7 +33,10 @@ Not covered, and why:
     indirectly: tests/test_spec_gpu.py pins a program to the interpreter bit for bit, and the interpreter is what these two files pin to the oracle.
   * MiniCheetah-C2 classification at 5 layers: none of seeds 1..12 closes it at 17 windows (X4.joint leaves bf16); it stops at 4 layers, where its base is a
     source only.  Its base-destination kernels are those MiniCheetah-K4 L5 and A1-C2 L5 run.
-  * The one-call cross-entropy step of the classification families (softmax: not exact).
+  * Of the cross-entropy steps, what tests/test_exact_ce_gpu.py cannot reach: batch sizes that are not powers of two (inv_n then has 24 significant bits and the
+    first bf16 store of dX_L rounds it), the compile-time DecFacts tail with two output channels (only the 8-layer classification programs instantiate it,
+    check_exact refuses 8 layers: pinned to the interpreter by tests/test_spec_gpu.py), the series step_ce routes (pinned to assemble + step_ce by torch.equal
+    in tests/test_windows.py), and the (model, batch) of its LEFT_OUT.
   * The series step (step_mse_series): tests/test_windows.py already pins it to store.assemble(starts) + step_mse bit for bit, which this file pins to the
     oracle.
 No (family, batch) of the two matrices is left out for want of a seed: tests/test_exact_data.py proves every one on the host.
