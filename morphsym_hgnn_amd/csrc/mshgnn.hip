@@ -1057,10 +1057,14 @@ template <bool ALIGNED, bool SERIES = false> __global__ __launch_bounds__(256, G
     __shared__ __attribute__((aligned(16))) u32x4 qsign_t[GW_IPL][16];    // raw Q: symmetry sign XOR of (item, column chunk)
     __shared__ unsigned long long sbase[GW_IPL][4];                       // per item: stream bases of P, relu bytes, Q at the part's first window
     __shared__ unsigned long long sser[SERIES ? GW_IPL : 1][16][2];       // SERIES, raw Q: per (item, column chunk) the run pointers (at the chunk's time offset) of its two pieces
+    // extra workgroups carry the finalize ops that read no slab (zero fills, decoder sums, loss: GwSide): first in the grid, so that they run under the launch's body
+    const int sw = (int)blockIdx.x - a.side.wg0;
+    if (sw >= 0 && sw < a.side.n_grid) { if (sw < a.side.n) gw_side_workgroup(a.side, sw); return; }
+    const int bx = (int)blockIdx.x - a.side.main0;
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     mlut[tid] = chunk_mask_bits<__bf16>(u32x4{0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu}, (unsigned)tid);   // (visible after the first barrier)
     const int wr = wv >> 1, wc = wv & 1;
-    const int ln = a.lane_order[blockIdx.x % a.n_pad], part = blockIdx.x / a.n_pad;
+    const int ln = a.lane_order[bx % a.n_pad], part = bx / a.n_pad;
     if (ln < 0) return;
     const int* lh = a.lanes + ln * LANE_INTS;
     const int it0 = lh[0], nit = lh[1] - lh[0], bias_flag = lh[3];
@@ -1252,13 +1256,68 @@ template <bool ALIGNED, bool SERIES = false> __global__ __launch_bounds__(256, G
     }
 }
 
-// k_finalize: sum split-K slabs in fixed order into the flat gradient buffer (every parameter written once)
+// finalize: sum split-K slabs in fixed order into the flat gradient buffer (every parameter written once)
 
 #ifndef FIN_LB
-#define FIN_LB 4       // lanes per load batch of k_finalize (x 4 parts = 16 slab loads in flight per thread; 8 / 16 lanes measured: A1-C2 18.7 -> 18.6 / 17.9 us,
-                       // MiniCheetah-K4 L=8 19.3 -> 20.5 / 23.6 us)
+#define FIN_LB 4       // lanes per load batch of the finalize kernels (x 4 parts = 16 slab loads in flight per thread; 8 / 16 lanes measured on the whole finalize: A1-C2 18.7 ->
+                       // 18.6 / 17.9 us, MiniCheetah-K4 L=8 19.3 -> 20.5 / 23.6 us)
 #endif
-__global__ __launch_bounds__(256) void k_finalize(FinArgs a) {
+// k_finalize (bf16 / split plans): the slab sums and nothing else -- the ops that read no slab ran in the weight-gradient launch (gw_side_workgroup).  One FSLAB_INTS
+// record per workgroup, so the first load behind the record is slab data; a thread owns FOUR CONSECUTIVE columns of one destination row (slab rows are H floats: 16-byte
+// loads) and sums each of them exactly as the whole finalize below does: lane-major batches of FIN_LB lanes x 4 parts, (v0 + v1) + (v2 + v3) per lane.
+__global__ __launch_bounds__(256) void k_finalize(FinSlabArgs a) {
+    const int* f = a.recs + (size_t)blockIdx.x * FSLAB_INTS;
+    const int64_t dst = (int64_t)(unsigned)f[0] | ((int64_t)f[1] << 32);
+    const int row0 = f[2], rows = f[3], cols = f[4], ld = f[5], l0 = f[6], nl = f[7], kind = f[9];
+    const int* more = f[8] ? a.fin0 + f[8] : nullptr;      // further destinations of the same sum: {n, dst_lo, dst_hi, ...}
+    const int rr = threadIdx.x >> 5, c0 = (threadIdx.x & 31) * 4;
+    if (rr >= rows || c0 >= cols) return;
+    const int r = row0 + rr;
+    const float* sp = a.slabs + (size_t)l0 * SLAB_FLOATS + (kind == FIN_MATRIX ? r * H : H * H) + c0;
+    const size_t pstride = (size_t)a.n_lanes * SLAB_FLOATS;
+    float4 s = float4{0.f, 0.f, 0.f, 0.f};
+    for (int j0 = 0; j0 < nl; j0 += FIN_LB)
+        for (int p0 = 0; p0 < a.n_parts; p0 += 4) {
+            float4 v[FIN_LB][4];
+#pragma unroll
+            for (int jj = 0; jj < FIN_LB; ++jj)
+#pragma unroll
+                for (int pp = 0; pp < 4; ++pp)
+                    v[jj][pp] = (j0 + jj < nl && p0 + pp < a.n_parts) ? *reinterpret_cast<const float4*>(sp + (size_t)(j0 + jj) * SLAB_FLOATS + (size_t)(p0 + pp) * pstride)
+                                                                       : float4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int jj = 0; jj < FIN_LB; ++jj) {
+                s.x += (v[jj][0].x + v[jj][1].x) + (v[jj][2].x + v[jj][3].x);
+                s.y += (v[jj][0].y + v[jj][1].y) + (v[jj][2].y + v[jj][3].y);
+                s.z += (v[jj][0].z + v[jj][1].z) + (v[jj][2].z + v[jj][3].z);
+                s.w += (v[jj][0].w + v[jj][1].w) + (v[jj][2].w + v[jj][3].w);
+            }
+        }
+    const int64_t at = (int64_t)r * ld + c0;
+    float* g = a.grad + dst + at;
+    // stores as wide as the destination allows: encoder chunks have widths such as 66 and leading dimension 450 (scalar stores there)
+    const bool full = c0 + 4 <= cols;
+    float e[4] = {s.x, s.y, s.z, s.w};
+    if (a.accumulate) {      // (a later sub-step of a chunked step; the further destinations of a shared sum held the same value)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) if (c0 + k < cols) e[k] += g[k];
+    }
+    auto put = [&](float* q) {
+        if (full && ((uintptr_t)q & 15) == 0) *reinterpret_cast<float4*>(q) = float4{e[0], e[1], e[2], e[3]};
+        else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) if (c0 + k < cols) q[k] = e[k];
+        }
+    };
+    put(g);
+    if (more) {
+        const int nm = more[0];
+        for (int m = 0; m < nm; ++m) put(a.grad + (((int64_t)(unsigned)more[1 + 2 * m] | ((int64_t)more[2 + 2 * m] << 32)) + at));
+    }
+}
+
+// k_finalize_whole (fp32 plan; the loss alone of an activation-only backward on every plan): every op of the fin table, 64 workgroups per op
+__global__ __launch_bounds__(256) void k_finalize_whole(FinArgs a) {
     const int* f = a.fin + blockIdx.x * FIN_INTS;
     const int64_t dst = (int64_t)(unsigned)f[0] | ((int64_t)f[1] << 32);
     const int rows = f[2], cols = f[3], ld = f[4], tg = f[5], kind = f[6];
@@ -1568,20 +1627,27 @@ int run_finalize(const mshgnn_plan* p, const StepCall& c, const mshgnn_ws_layout
     const int B = (int)c.batch, gw_phase = c.gw_phase;
     float* loss = c.loss != LossKind::NONE ? c.loss_out : nullptr;
     FinArgs a{p->d_tables + hp.fin_off, p->d_tables + hp.fin_off, p->d_tables + hp.tgt_off, reinterpret_cast<const float*>(ws + lay.slabs),
-              reinterpret_cast<const float*>(ws + lay.dec_slabs), gparams, hp.n_lanes, gw_parts, loss,
-              1.0f / (float)(c.total_windows() * d.type_nodes[d.out_type] * (c.loss == LossKind::CE ? 1 : d.out_channels)),
-              c.dec_done ? (int)((B + TILE_ROWS - 1) / TILE_ROWS) : NWG_DEC, c.accumulates()};
-    int f0 = 0, nf = hp.n_fin;
-    if (gw_phase == 0) nf = hp.n_fin_ph0;
-    if (gw_phase == 1) { f0 = hp.n_fin_ph0; nf = hp.n_fin - hp.n_fin_ph0; a.loss = nullptr; }
-    a.fin += (size_t)f0 * FIN_INTS;
+              reinterpret_cast<const float*>(ws + lay.dec_slabs), gparams, hp.n_lanes, gw_parts, loss, fin_inv_n(hp, c), fin_n_dec(c), c.accumulates()};
     if (!gparams) {      // activation backward only: no gradient to finalize, one workgroup for the fused loss (if any)
-        if (loss) hipLaunchKernelGGL(k_finalize, dim3(1, 1), dim3(256), 0, st, a);
+        if (loss) hipLaunchKernelGGL(k_finalize_whole, dim3(1, 1), dim3(256), 0, st, a);
         HIPCHK(hipGetLastError());
         return MSHGNN_OK;
     }
     ProfScope ps(p, hp.ks_fin, st);
-    if (nf > 0) hipLaunchKernelGGL(k_finalize, dim3(nf, 64), dim3(256), 0, st, a);
+    if (fin_split(hp)) {      // bf16 / split plan: the slab sums of this phase; everything else ran in the weight-gradient launch (fill_gradw_side)
+        FinSlabArgs s{p->d_tables + hp.fslab_off, p->d_tables + hp.fin_off, a.slabs, gparams, hp.n_lanes, gw_parts, c.accumulates()};
+        int n = hp.n_fslab;
+        if (gw_phase == 0) n = hp.n_fslab_ph0;
+        if (gw_phase == 1) { s.recs += (size_t)hp.n_fslab_ph0 * FSLAB_INTS; n = hp.n_fslab - hp.n_fslab_ph0; }
+        if (n > 0) hipLaunchKernelGGL(k_finalize, dim3(n), dim3(256), 0, st, s);
+        HIPCHK(hipGetLastError());
+        return MSHGNN_OK;
+    }
+    int f0 = 0, nf = hp.n_fin;
+    if (gw_phase == 0) nf = hp.n_fin_ph0;
+    if (gw_phase == 1) { f0 = hp.n_fin_ph0; nf = hp.n_fin - hp.n_fin_ph0; a.loss = nullptr; }
+    a.fin += (size_t)f0 * FIN_INTS;
+    if (nf > 0) hipLaunchKernelGGL(k_finalize_whole, dim3(nf, 64), dim3(256), 0, st, a);
     HIPCHK(hipGetLastError());
     return MSHGNN_OK;
 }
@@ -1698,8 +1764,9 @@ static int backward_impl(const mshgnn_plan* p, const StepCall& c) {
         // (round 6, measured and not kept: phase 1's lanes on a side stream BESIDE phase 0's -- forked behind the stack launch, joined by phase 1's finalize.  On a
         //  1-rank RCCL group the two-phase step took 0.306 ms that way against 0.268 back to back and 0.186 for the plain step: two concurrent sweeps of the batch
         //  evict each other's shared rows.)
-        const dim3 grid(std::max(a.n_pad, 0) * gw_parts);
-        if (a.n_pad <= 0) {}      // (a phase without lanes)
+        const dim3 grid(a.side.n_grid + std::max(a.n_pad, 0) * gw_parts);      // the slab-free finalize workgroups first (bf16 plan; fp32: none)
+        a.n_pad = std::max(a.n_pad, 1);      // (a phase without lanes: only those workgroups)
+        if (grid.x == 0) {}
         else if constexpr (sizeof(T) == 4) hipLaunchKernelGGL(k_gradw_f32, grid, dim3(256), 0, st, a);
         else if (c.gradw_from_series && c.series) hipLaunchKernelGGL((k_gradw_bf16_lean<true, true>), grid, dim3(256), 0, st, a);      // raw operands from the series
         else if (a.aligned) hipLaunchKernelGGL(k_gradw_bf16_lean<true>, grid, dim3(256), 0, st, a);

@@ -1473,7 +1473,13 @@ struct DecArgs {
 };
 
 
+// The finalize ops that read no weight-gradient slab, riding in extra workgroups of a bf16 / split-plan weight-gradient launch (SIDE_INTS records of the plan,
+// mshgnn_plan.hpp; gw_side_workgroup below): workgroups [wg0, wg0 + n_grid) of the grid, the first n of them one record each; the launch's own workgroups start at main0.
+// n_grid == 0: none (the fp32 plan finalizes whole).
+struct GwSide { const int* recs; int n, n_grid, wg0, main0; const float* dec_slabs; float* grad; float* loss; float inv_n; int n_dec; int accumulate; };
+
 struct GradwArgs {
+    GwSide side;
     const char* ws; size_t buf_off[BUF_COUNT];
     const void* x[MSHGNN_MAX_TYPES]; int64_t pitch[MSHGNN_MAX_TYPES]; int nodes[MSHGNN_MAX_TYPES]; int vb[MSHGNN_MAX_TYPES];
     const int* items; const int* lanes; const int* lane_order; const uint8_t* signs; float* slabs; int B, n_lanes, n_parts, n_pad;
@@ -1506,6 +1512,51 @@ __device__ __forceinline__ bf16x8 tr_frag(const __bf16* tile, int w_base, int co
 
 struct FinArgs { const int* fin; const int* fin0; const int* targets; const float* slabs; const float* dec_slabs; float* grad; int n_lanes, n_parts; float* loss; float inv_n;
                  int n_dec; int accumulate; };   // decoder partial slabs: NWG_DEC (k_dec_bwd) or one per tile (fused forward)
+// k_finalize of the bf16 / split plans: one FSLAB_INTS record per workgroup (fin0: the fin table, which the records' destination lists are counted from)
+struct FinSlabArgs { const int* recs; const int* fin0; const float* slabs; float* grad; int n_lanes, n_parts, accumulate; };
+
+// One extra workgroup (256 threads) of a weight-gradient launch: side record `wg`.  Nothing here reads what the launch's other workgroups write, and nothing they read is
+// written here: the zero fills and the decoder sums (whose partials the stack launch or k_dec_bwd left) only touch the caller's gradient, the loss sum its one float.
+// The decoder sums and the loss keep the arithmetic of the whole finalize (k_finalize_whole, mshgnn.hip): 8 partials per lane, the same adds, the same xor-shuffle tree.
+__device__ __forceinline__ void gw_side_workgroup(const GwSide& s, int wg) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    if (s.loss && wg == 0 && tid < 64) {      // fused loss: the per-block partials in fixed order
+        float l = 0.f;
+        for (int b = tid; b < s.n_dec; b += 64) l += s.dec_slabs[(size_t)b * DEC_SLAB_FLOATS + 8 * H + 8];
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) l += __shfl_xor(l, m, 64);
+        if (tid == 0) *s.loss = l * s.inv_n + (s.accumulate ? *s.loss : 0.f);      // (accumulate: a later sub-step of a chunked step, StepChunk)
+    }
+    const int* f = s.recs + (size_t)wg * SIDE_INTS;
+    const int64_t dst = (int64_t)(unsigned)f[0] | ((int64_t)f[1] << 32);
+    const int cols = f[3], ld = f[4], kind = f[5];
+    if (kind == FIN_ZERO) {      // (never part of an accumulating sub-step's launch)
+        const int rows = f[2];
+        const bool v4 = (((uintptr_t)s.grad | (uintptr_t)dst | (uintptr_t)ld) & 3) == 0 && ((uintptr_t)s.grad & 15) == 0;      // every row starts on 16 bytes
+        const int nv = v4 ? cols >> 2 : 0;
+        for (int r = 0; r < rows; ++r) {
+            float* g = s.grad + dst + (int64_t)r * ld;
+            for (int i = tid; i < nv; i += 256) reinterpret_cast<float4*>(g)[i] = float4{0.f, 0.f, 0.f, 0.f};
+            for (int i = 4 * nv + tid; i < cols; i += 256) g[i] = 0.f;
+        }
+        return;
+    }
+    const bool is_mat = kind == FIN_DEC_W;
+    for (int e = f[2] + (tid >> 6); e < f[6]; e += 4) {      // one WAVE per element
+        const int r = e / cols, cidx = e % cols;
+        const int src = is_mat ? r * H + cidx : 8 * H + cidx;
+        float sum = 0.f;
+        for (int b0 = 0; b0 < s.n_dec; b0 += 512) {       // 8 slabs per lane in flight; lane-strided, fixed order
+            float v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) { const int b = b0 + lane + 64 * u; v[u] = b < s.n_dec ? s.dec_slabs[(size_t)b * DEC_SLAB_FLOATS + src] : 0.f; }
+            sum += ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
+        }
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) sum += __shfl_xor(sum, m, 64);
+        if (lane == 0) { float* gp = s.grad + dst + (int64_t)r * ld + cidx; *gp = s.accumulate ? *gp + sum : sum; }
+    }
+}
 
 struct mshgnn_gen_state;      // generic-width engine (mshgnn_gen.hip)
 struct ProfRec { int slot; hipEvent_t a, b; };

@@ -156,7 +156,9 @@ extern "C" {
 const char* mshgnn_hostplan_last_error() { return g_hp_err.c_str(); }
 
 enum { HPM_OK = 0, HPM_L, HPM_NN, HPM_NMLP, HPM_FUSED, HPM_SLAB, HPM_SL_HB, HPM_SL_BLK, HPM_FS_BLK, HPM_NTABLES, HPM_NPACKS, HPM_NBIASES, HPM_SL_ALIAS, HPM_NITEMS, HPM_NLANES, HPM_NFIN,
-       HPM_SL_FWD = 16, HPM_SL_BWD = 32, HPM_FS_FWD = 48, HPM_FS_BWD = 64, HPM_LIVE = 80 /* [l] low / high 32 bits of the node bit mask: 2 ints per layer */, HPM_NEED = 112, HPM_X3_ALIAS = 144, HPM_SPLIT = 145, HPM_COUNT = 160 };
+       HPM_SL_FWD = 16, HPM_SL_BWD = 32, HPM_FS_FWD = 48, HPM_FS_BWD = 64, HPM_LIVE = 80 /* [l] low / high 32 bits of the node bit mask: 2 ints per layer */, HPM_NEED = 112, HPM_X3_ALIAS = 144, HPM_SPLIT = 145,
+       // the finalize tables (tests/test_finalize_records.py): the fin table, the slab-free records of the weight-gradient launch, k_finalize's records
+       HPM_FIN_OFF = 146, HPM_NFIN_PH0, HPM_SIDE_OFF, HPM_NSIDE_DEC, HPM_NSIDE_Z0, HPM_NSIDE_Z1, HPM_FSLAB_OFF, HPM_NFSLAB, HPM_NFSLAB_PH0, HPM_TGT_OFF, HPM_SPLIT_LO, HPM_SPLIT_HI, HPM_COUNT = 160 };
 
 // Compile the LDS-resident plan of `desc` on the host.  tables (may be null): receives min(cap, n) table ints; meta: HPM_COUNT ints (layout above).
 // Returns the number of table ints, or -1 (mshgnn_hostplan_last_error()).  check != 0: also bounds-check every index table (error text names the first violation).
@@ -170,6 +172,10 @@ int mshgnn_hostplan_compile(const mshgnn_desc* desc, int32_t* tables, int cap, i
         meta[HPM_SL_BLK] = hp.sl_blk; meta[HPM_FS_BLK] = hp.fs_blk; meta[HPM_NTABLES] = (int)hp.tables.size(); meta[HPM_NPACKS] = (int)hp.packs.size(); meta[HPM_NBIASES] = (int)hp.biases.size();
         meta[HPM_X3_ALIAS] = hp.x3_alias; meta[HPM_SPLIT] = hp.split;
         meta[HPM_SL_ALIAS] = hp.sl_alias; meta[HPM_NITEMS] = hp.n_items; meta[HPM_NLANES] = hp.n_lanes; meta[HPM_NFIN] = hp.n_fin;
+        meta[HPM_FIN_OFF] = hp.fin_off; meta[HPM_NFIN_PH0] = hp.n_fin_ph0; meta[HPM_SIDE_OFF] = hp.side_off; meta[HPM_NSIDE_DEC] = hp.n_side_dec;
+        meta[HPM_NSIDE_Z0] = hp.n_side_zero[0]; meta[HPM_NSIDE_Z1] = hp.n_side_zero[1]; meta[HPM_FSLAB_OFF] = hp.fslab_off; meta[HPM_NFSLAB] = hp.n_fslab;
+        meta[HPM_NFSLAB_PH0] = hp.n_fslab_ph0; meta[HPM_TGT_OFF] = hp.tgt_off;
+        meta[HPM_SPLIT_LO] = (int32_t)(uint32_t)(hp.grad_split & 0xffffffff); meta[HPM_SPLIT_HI] = (int32_t)(hp.grad_split >> 32);
         for (int l = 0; l < hp.L; ++l) {
             meta[HPM_SL_FWD + l] = hp.sl_fwd_off[l]; meta[HPM_SL_BWD + l] = hp.sl_bwd_off[l]; meta[HPM_FS_FWD + l] = hp.fs_fwd_off[l]; meta[HPM_FS_BWD + l] = hp.fs_bwd_off[l];
             uint64_t lv = 0, nd = 0;

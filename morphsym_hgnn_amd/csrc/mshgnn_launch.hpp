@@ -180,6 +180,33 @@ inline int launch_stack(StackKernelFn kernel, const pick::StackPick& pk, hipStre
 }
 
 // ---- weight gradients: every lane of the step, or the lanes of one phase of a two-phase step (c.gw_phase)
+// ---- finalize work of a step: the mean the fused loss is scaled by, and how many decoder partial slabs there are (one per tile from a fused forward, else k_dec_bwd's)
+inline float fin_inv_n(const HostPlan& hp, const StepCall& c) {
+    const mshgnn_desc& d = hp.d;
+    return 1.0f / (float)(c.total_windows() * d.type_nodes[d.out_type] * (c.loss == LossKind::CE ? 1 : d.out_channels));
+}
+inline int fin_n_dec(const StepCall& c) { return c.dec_done ? (int)((c.batch + TILE_ROWS - 1) / TILE_ROWS) : NWG_DEC; }
+inline bool fin_split(const HostPlan& hp) { return hp.d.dtype != MSHGNN_F32; }      // bf16 / split plan: slab-free ops in the weight-gradient launch, k_finalize sums slabs only
+
+// The slab-free finalize ops of this call's finalize range as extra workgroups of its weight-gradient launch: the decoder sums and the loss where the whole step or
+// phase 0 runs, the zero fills of the range unless a sub-step of a chunked step accumulates (the first sub-step has written them).
+// They come FIRST in the grid, padded to a multiple of 8 workgroups: the launch's own workgroups keep their index modulo 8, which is the XCD the plan placed each lane on
+// (lane_order; unpadded, 122 of them in front of A1-C2's 448 cost the launch 66.8 -> 70.6 us: HISTORY.md).  n_main: the launch's own workgroups.
+inline void fill_gradw_side(const mshgnn_plan* p, const StepCall& c, const mshgnn_ws_layout& lay, int n_main, GwSide& s) {
+    const HostPlan& hp = p->hp;
+    s = GwSide{};
+    if (!fin_split(hp) || !c.grad_params) return;
+    int first = 0, n = hp.n_side_dec;      // records: [decoder sums | zero fills of phase 0 | zero fills of phase 1]
+    if (!c.accumulates()) n += hp.n_side_zero[0] + (c.gw_phase == 0 ? 0 : hp.n_side_zero[1]);
+    if (c.gw_phase == 1) { first = hp.n_side_dec + hp.n_side_zero[0]; n = c.accumulates() ? 0 : hp.n_side_zero[1]; }
+    static const int where = [] { const char* e = TUNE_ENV("MSHGNN_GW_SIDE"); return e ? atoi(e) : 0; }();      // (A/B runs: 1 = last in the grid, 2 = first without the padding)
+    s.recs = p->d_tables + hp.side_off + (size_t)first * SIDE_INTS; s.n = n;
+    s.n_grid = where == 0 ? (n + 7) / 8 * 8 : n; s.wg0 = where == 1 ? n_main : 0; s.main0 = where == 1 ? 0 : s.n_grid;
+    s.dec_slabs = reinterpret_cast<const float*>(c.ws + lay.dec_slabs); s.grad = c.grad_params;
+    s.loss = c.loss != LossKind::NONE && c.gw_phase != 1 ? c.loss_out : nullptr;
+    s.inv_n = fin_inv_n(hp, c); s.n_dec = fin_n_dec(c); s.accumulate = c.accumulates();
+}
+
 inline void fill_gradw_args(const mshgnn_plan* p, const StepCall& c, const mshgnn_ws_layout& lay, const LaunchTraits& tr, int gw_parts, GradwArgs& a) {
     const HostPlan& hp = p->hp;
     const mshgnn_desc& d = hp.d;
@@ -197,5 +224,6 @@ inline void fill_gradw_args(const mshgnn_plan* p, const StepCall& c, const mshgn
     a.items = p->d_tables + hp.item_off; a.lanes = p->d_tables + hp.lane_off; a.lane_order = p->d_tables + hp.lane_order_off; a.n_pad = hp.n_lanes_pad;
     if (c.gw_phase >= 0) { a.lane_order = p->d_tables + hp.order_ph_off[c.gw_phase]; a.n_pad = hp.npad_ph[c.gw_phase]; }
     a.signs = p->d_signs; a.slabs = reinterpret_cast<float*>(c.ws + lay.slabs); a.B = (int)c.batch; a.n_lanes = hp.n_lanes; a.n_parts = gw_parts;
+    fill_gradw_side(p, c, lay, std::max(a.n_pad, 0) * gw_parts, a.side);
     // (dbg / stamps stay zero: no weight-gradient kernel of this engine reads them)
 }

@@ -123,6 +123,17 @@ constexpr int LANE_INTS = 4;    // item_begin item_end target bias_flag
 constexpr int FIN_INTS = 8;     // dst_lo dst_hi rows cols dst_ld target kind extra (0, or the offset -- in ints, from the fin table's start -- of {n, dst_lo, dst_hi, ...}: further
                                 // destinations of the same shape that receive the same slab sum: lin_root.weight / lin_rel.bias of every relation into one destination type)
 enum { FIN_MATRIX = 0, FIN_BIAS = 1, FIN_ZERO = 2, FIN_DEC_W = 3, FIN_DEC_B = 4 };
+// The bf16 and split plans run the finalize ops from two tables of one record per WORKGROUP, written behind the fin table (which the fp32 plan's whole finalize keeps reading):
+//   * the ops that read no weight-gradient slab (zero fills, decoder sums) ride in extra workgroups at the front of the weight-gradient launch (gw_side_workgroup,
+//     mshgnn_device.hpp), order [decoder sums | zero fills of phase 0 | zero fills of phase 1];
+//   * k_finalize sums slabs and nothing else: FSLAB_ROWS destination rows per workgroup, phase 0 first.
+constexpr int SIDE_INTS = 8;    // dst_lo dst_hi (rows | first element) cols dst_ld kind (0 | one past the last element) pad.  FIN_ZERO: `rows` rows of `cols` zeros from dst;
+                                // FIN_DEC_W / FIN_DEC_B: elements [first, last) of the op at dst, element e = (e / cols, e % cols)
+constexpr int FSLAB_INTS = 10;  // dst_lo dst_hi row0 rows cols dst_ld lane_begin lanes extra kind: rows [row0, row0 + rows) of a FIN_MATRIX / FIN_BIAS op (dst = the op's; extra as in the fin table)
+constexpr int FSLAB_ROWS = 8;         // 256 threads x 4 consecutive columns = 8 slab rows of H floats
+constexpr int SIDE_DEC_ELEMS = 8;     // decoder elements per side workgroup (one wave per element, two rounds)
+constexpr int SIDE_ZERO_ELEMS = 8192; // zeros per side workgroup (contiguous ops), SIDE_ZERO_ROWS rows of a strided op
+constexpr int SIDE_ZERO_ROWS = 64;
 
 struct PackDesc {       // one packed 128x128 B-operand image (weights as the MFMA wants them)
     int orient;         // 0: B[k][c] = W[c][k]  (forward: out = A W^T)   1: B[k][c] = W[k][c]  (backward: dA = dH W)
@@ -192,6 +203,8 @@ struct HostPlan {
     int order_ph_off[2]{}, npad_ph[2]{}, n_fin_ph0 = 0;
     int64_t grad_split = -1;     // flat offset where the phase-0 parameters start ([0, grad_split) = encoder = phase 1); -1: no split
     int fin_off = 0, n_fin = 0;
+    int side_off = 0, n_side_dec = 0, n_side_zero[2]{};      // SIDE_INTS records: decoder sums, then the zero fills of phase 0 and of phase 1
+    int fslab_off = 0, n_fslab = 0, n_fslab_ph0 = 0;         // FSLAB_INTS records, phase 0 first
     int enc_tile_mb = 4;
     int n_slabs = 0;
     std::vector<float> out_mask_f;
@@ -1118,6 +1131,38 @@ inline bool compile_plan(const mshgnn_desc* din, HostPlan& p) {
         }
         T.insert(T.end(), extra.begin(), extra.end());
         if (p.grad_split < 0) p.n_fin_ph0 = p.n_fin;
+        // the same ops, one record per workgroup (SIDE_INTS / FSLAB_INTS above).  The op order, and so the phase split, is the fin table's.
+        auto lo32 = [](int64_t v) { return (int32_t)(v & 0xffffffff); };
+        auto hi32 = [](int64_t v) { return (int32_t)(v >> 32); };
+        p.side_off = (int)T.size(); p.n_side_dec = 0; p.n_side_zero[0] = p.n_side_zero[1] = 0;
+        auto side = [&](int64_t dst, int a, int cols, int ld, int kind, int last) { T.insert(T.end(), {lo32(dst), hi32(dst), a, cols, ld, kind, last, 0}); };
+        for (auto& f : fins)
+            if (f.kind == FIN_DEC_W || f.kind == FIN_DEC_B)
+                for (int e0 = 0; e0 < f.rows * f.cols; e0 += SIDE_DEC_ELEMS) { side(f.dst, e0, f.cols, f.ld, f.kind, std::min(f.rows * f.cols, e0 + SIDE_DEC_ELEMS)); ++p.n_side_dec; }
+        for (int ph = 0; ph < 2; ++ph)
+            for (size_t i = 0; i < fins.size(); ++i) {
+                const FinRec& f = fins[i];
+                if (f.kind != FIN_ZERO || ((int)i >= p.n_fin_ph0) != (ph == 1)) continue;
+                if (f.rows == 1 || f.cols == f.ld) {      // one contiguous run
+                    const int64_t n = (int64_t)f.rows * f.cols;
+                    for (int64_t o = 0; o < n; o += SIDE_ZERO_ELEMS) { const int m = (int)std::min<int64_t>(SIDE_ZERO_ELEMS, n - o); side(f.dst + o, 1, m, m, FIN_ZERO, 0); ++p.n_side_zero[ph]; }
+                } else {
+                    for (int r0 = 0; r0 < f.rows; r0 += SIDE_ZERO_ROWS) { side(f.dst + (int64_t)r0 * f.ld, std::min(SIDE_ZERO_ROWS, f.rows - r0), f.cols, f.ld, FIN_ZERO, 0); ++p.n_side_zero[ph]; }
+                }
+            }
+        p.fslab_off = (int)T.size(); p.n_fslab = p.n_fslab_ph0 = 0;
+        size_t xoff = fins.size() * FIN_INTS;      // (the destination lists: same offsets as in the fin records)
+        for (size_t i = 0; i < fins.size(); ++i) {
+            const FinRec& f = fins[i];
+            const int more = f.more.empty() ? 0 : (int32_t)xoff;
+            if (!f.more.empty()) xoff += 1 + 2 * f.more.size();
+            if (f.kind != FIN_MATRIX && f.kind != FIN_BIAS) continue;
+            for (int r0 = 0; r0 < f.rows; r0 += FSLAB_ROWS) {
+                T.insert(T.end(), {lo32(f.dst), hi32(f.dst), r0, std::min(FSLAB_ROWS, f.rows - r0), f.cols, f.ld, tgt_lane_begin[f.target], tgt_lane_end[f.target] - tgt_lane_begin[f.target], more, f.kind});
+                ++p.n_fslab;
+                if ((int)i < p.n_fin_ph0) ++p.n_fslab_ph0;
+            }
+        }
     }
 
     // ---- info ---------------------------------------------------------------------------------------

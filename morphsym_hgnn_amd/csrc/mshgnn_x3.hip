@@ -205,10 +205,14 @@ template <bool ALIGNED> __global__ __launch_bounds__(256, GWX3_WPS) void k_gradw
     __shared__ __attribute__((aligned(16))) u32x4 qfix[16][2];            // raw-input items: per column chunk c the keep masks of its two fp32 halves
     __shared__ __attribute__((aligned(16))) u32x4 qsign_t[GW_IPL][16][2]; // ... and per (item, column chunk) the symmetry sign XORs
     __shared__ unsigned long long sbase[GW_IPL][4];                       // per item: stream bases of P, relu bytes, Q at the part's first window
+    // extra workgroups carry the finalize ops that read no slab (GwSide; as in k_gradw_bf16_lean, mshgnn.hip)
+    const int sw = (int)blockIdx.x - a.side.wg0;
+    if (sw >= 0 && sw < a.side.n_grid) { if (sw < a.side.n) gw_side_workgroup(a.side, sw); return; }
+    const int bx = (int)blockIdx.x - a.side.main0;
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     mlut[tid] = chunk_mask_bits<__bf16>(u32x4{0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu}, (unsigned)tid);   // (visible after the first barrier)
     const int wr = wv >> 1, wc = wv & 1;
-    const int ln = a.lane_order[blockIdx.x % a.n_pad], part = blockIdx.x / a.n_pad;
+    const int ln = a.lane_order[bx % a.n_pad], part = bx / a.n_pad;
     if (ln < 0) return;
     const int* lh = a.lanes + ln * LANE_INTS;
     const int it0 = lh[0], nit = lh[1] - lh[0], bias_flag = lh[3];
@@ -511,9 +515,11 @@ int x3_backward(const mshgnn_plan* p, const StepCall& c) {
         GradwArgs a{};
         fill_gradw_args(p, c, lay, tr, gw_parts, a);
         ProfScope ps(p, hp.ks_gradw, st);
-        if (a.n_pad <= 0) {}      // (a phase without lanes)
-        else if (a.aligned) hipLaunchKernelGGL(k_gradw_x3_lean<true>, dim3(a.n_pad * gw_parts), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL(k_gradw_x3_lean<false>, dim3(a.n_pad * gw_parts), dim3(256), 0, st, a);
+        const dim3 grid(a.side.n_grid + std::max(a.n_pad, 0) * gw_parts);      // the slab-free finalize workgroups first
+        a.n_pad = std::max(a.n_pad, 1);      // (a phase without lanes: only those workgroups)
+        if (grid.x == 0) {}
+        else if (a.aligned) hipLaunchKernelGGL(k_gradw_x3_lean<true>, grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL(k_gradw_x3_lean<false>, grid, dim3(256), 0, st, a);
     }
     return run_finalize(p, c, lay, gw_parts);
 }
