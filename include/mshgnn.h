@@ -372,6 +372,23 @@ int mshgnn_metrics_regression_segmented(const float* y_pred, const float* y, int
 int mshgnn_metrics_classification_segmented(const float* logits, const int32_t* y, int64_t batch, const int32_t* segment, int32_t n_segments,
                                             double* ce_state, int64_t* counts, void* scratch, void* stream);
 
+/* The centroidal-momentum sums per SEGMENT (the rows of research/evaluator_regression-com.py:50-76: Test Loss, Cos Sim Lin, Cos Sim Ang per
+ * symmetry operator): y_pred / y / y_mean / y_std as mshgnn_metrics_com_step takes them, segment / n_segments / the overflow row n_segments as the
+ * two segmented calls above define them.  state double[n_segments + 1][8], row s in the layout of mshgnn_metrics_com_step over the windows of
+ * segment s: [0] += sq err of the lin halves, [1] += of the ang halves, [2] and [3] += 3 n_bases windows, [4] / [5] += the cosines of base node
+ * 0's lin / ang vectors after un-standardising, [6] += windows, [7] untouched.  A window's terms are formed with the operations of
+ * mshgnn_metrics_com_step in its order: the squared differences over (base, k) in index order, then each cosine as
+ * sum (a / max(|a|, 1e-8)) (b / max(|b|, 1e-8)).  The discipline of the segmented calls: one launch, asynchronous, nothing allocated, fp64, no
+ * floating-point atomic, bit-reproducible for any arrangement of ids and any arrival order (lane, wave butterfly per id, last workgroup merges
+ * in (slot, entry) order).
+ * scratch: mshgnn_metrics_com_segmented_scratch_bytes(batch) = 16 + 2568 * ceil(batch / 64) bytes (a ticket, then per 64 windows one slot of an
+ * entry count and 64 entries of id, windows and FOUR sums), 8-byte aligned, zeroed once by the caller and then owned by this call; it serves
+ * every batch up to the one it was sized for; one scratch per stream; not interchangeable with the scratch of the two calls above.
+ * MSHGNN_EINVAL before any launch: a null pointer, batch < 1, n_bases < 1, n_segments < 1, a state or scratch that is not 8-byte aligned.     */
+size_t mshgnn_metrics_com_segmented_scratch_bytes(int64_t batch);
+int mshgnn_metrics_com_segmented(const float* y_pred, const float* y, int64_t batch, int n_bases, const double* y_mean, const double* y_std,
+                                 const int32_t* segment, int32_t n_segments, double* state, void* scratch, void* stream);
+
 /* body_frame_to_world_frame (gnnLightning.py:663-676) without the per-step CPU/scipy round trip: quat fp32 [batch][4] is
  * the world->body rotation, scalar-last (x, y, z, w) as scipy.Rotation.from_quat takes it; grf fp32 [batch][4][3].       */
 int mshgnn_grf_body_to_world(const float* quat, const float* grf_body, float* grf_world, int64_t batch, void* stream);

@@ -579,33 +579,37 @@ struct MetScratchCom { unsigned int ticket, pad; double f[MET_BLOCKS][4]; };
 static_assert(sizeof(MetScratchCom) <= MSHGNN_METRICS_SCRATCH_BYTES, "include/mshgnn.h promises this scratch size");
 struct ComStats { double mean[6], std[6]; };
 
+// window w's terms added into a = {sq lin, sq ang, cos lin, cos ang}: the squared differences over (base, k) in index order, then each cosine
+// (shared by the whole-batch kernel and the segmented one below: one statement of a window's operations)
+__device__ __forceinline__ void com_window_add(const float* pred, const float* y, int64_t w, int nb, const ComStats& st, double (&a)[4]) {
+    for (int b = 0; b < nb; ++b)
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+            const double d = (double)pred[(w * nb + b) * 6 + k] - (double)y[(w * nb + b) * 6 + k];
+            a[k < 3 ? 0 : 1] += d * d;
+        }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        double pp = 0.0, yy = 0.0, py = 0.0, pv[3], yv[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            pv[k] = (double)pred[w * nb * 6 + 3 * h + k] * st.std[3 * h + k] + st.mean[3 * h + k];
+            yv[k] = (double)y[w * nb * 6 + 3 * h + k] * st.std[3 * h + k] + st.mean[3 * h + k];
+            pp += pv[k] * pv[k]; yy += yv[k] * yv[k];
+        }
+        const double pn = fmax(sqrt(pp), 1e-8), yn = fmax(sqrt(yy), 1e-8);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) py += (pv[k] / pn) * (yv[k] / yn);
+        a[2 + h] += py;
+    }
+}
+
 __global__ __launch_bounds__(MET_THREADS) void k_metrics_com(const float* pred, const float* y, int64_t B, int nb, ComStats st, double* batch, double* epoch,
                                                              MetScratchCom* sc) {
     __shared__ double r[MET_THREADS / 64][4], pf[MET_BLOCKS][4];
     __shared__ int s_last;
     double a[4] = {0.0, 0.0, 0.0, 0.0};      // sq lin, sq ang, cos lin, cos ang
-    for (int64_t w = (int64_t)blockIdx.x * MET_THREADS + threadIdx.x; w < B; w += (int64_t)gridDim.x * MET_THREADS) {
-        for (int b = 0; b < nb; ++b)
-#pragma unroll
-            for (int k = 0; k < 6; ++k) {
-                const double d = (double)pred[(w * nb + b) * 6 + k] - (double)y[(w * nb + b) * 6 + k];
-                a[k < 3 ? 0 : 1] += d * d;
-            }
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            double pp = 0.0, yy = 0.0, py = 0.0, pv[3], yv[3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                pv[k] = (double)pred[w * nb * 6 + 3 * h + k] * st.std[3 * h + k] + st.mean[3 * h + k];
-                yv[k] = (double)y[w * nb * 6 + 3 * h + k] * st.std[3 * h + k] + st.mean[3 * h + k];
-                pp += pv[k] * pv[k]; yy += yv[k] * yv[k];
-            }
-            const double pn = fmax(sqrt(pp), 1e-8), yn = fmax(sqrt(yy), 1e-8);
-#pragma unroll
-            for (int k = 0; k < 3; ++k) py += (pv[k] / pn) * (yv[k] / yn);
-            a[2 + h] += py;
-        }
-    }
+    for (int64_t w = (int64_t)blockIdx.x * MET_THREADS + threadIdx.x; w < B; w += (int64_t)gridDim.x * MET_THREADS) com_window_add(pred, y, w, nb, st, a);
 #pragma unroll
     for (int k = 0; k < 4; ++k) a[k] = wave_sum(a[k]);
     if ((threadIdx.x & 63) == 0)
@@ -929,6 +933,146 @@ __global__ __launch_bounds__(SEG_THREADS) void k_metrics_cls_seg(const float* lo
     if (threadIdx.x == 0) __hip_atomic_store(&sc->ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// ---- four sums per entry: the centroidal-momentum sums per segment --------------------------------------------------------------------------
+// The same three steps with a slot type of its own (an entry = id, windows and NF sums) and the merge's stage depth as a template parameter: at
+// four sums SEG_STAGE entries of s_f plus the mask rows would pass 64 KB of static LDS, 512 fit in 38 KB.  The merge always takes the
+// staged walk, STAGE entries at a time (the two-entry prefetch of seg_merge is a tuning of the evaluation sweeps' regression table, not part of
+// the order of additions): thread t adds the entries of the ids == t (mod SEG_THREADS) in (slot, entry) order and hands every finished id to
+// `flush_row(row, sums, windows)`.
+template <int NF> struct SegSlotN { unsigned int n, pad; int id[64]; int cnt[64]; double f[64][NF]; };
+using SegSlotCom = SegSlotN<4>;
+static_assert(sizeof(SegSlotCom) == 2568, "include/mshgnn.h documents 16 + 2568 * ceil(batch / 64) bytes");
+
+template <int NF> __device__ __forceinline__ void seg_wave_emit_n(SegSlotN<NF>* slot, bool valid, int id, const double (&f)[NF]) {
+    const int lane = threadIdx.x & 63;
+    unsigned long long rem = __ballot(valid);
+    int e = 0, e_id = 0, e_cnt = 0;
+    double ef[NF];
+#pragma unroll
+    for (int k = 0; k < NF; ++k) ef[k] = 0.0;
+    while (rem) {
+        const int leader = __ffsll((unsigned long long)rem) - 1;
+        const int row = __shfl(id, leader, 64);
+        const bool mine = valid && id == row;
+        const unsigned long long m = __ballot(mine);
+        const int cnt = __popcll(m);
+        double s[NF];
+#pragma unroll
+        for (int k = 0; k < NF; ++k) s[k] = cnt == 1 ? __shfl(f[k], leader, 64) : wave_sum(mine ? f[k] : 0.0);
+        if (lane == e) {
+            e_id = row; e_cnt = cnt;
+#pragma unroll
+            for (int k = 0; k < NF; ++k) ef[k] = s[k];
+        }
+        ++e;
+        rem &= ~m;
+    }
+    if (lane < e) {          // e <= 64: every pass retires at least the leader's lane
+        met_store(&slot->id[lane], e_id); met_store(&slot->cnt[lane], e_cnt);
+#pragma unroll
+        for (int k = 0; k < NF; ++k) met_store(&slot->f[lane][k], ef[k]);
+    }
+    if (lane == 0) met_store(&slot->n, (unsigned)e);
+}
+
+template <int NF, int STAGE, class Flush>
+__device__ __forceinline__ void seg_merge_n(const SegSlotN<NF>* slots, int64_t n_slots, int32_t n_segments, Flush&& flush_row) {
+    static_assert(STAGE % 32 == 0 && STAGE >= 64, "whole mask words, and room for one slot's entries");
+    __shared__ int s_off[SEG_THREADS + 1], s_wave[SEG_THREADS / 64], s_id[STAGE], s_cnt[STAGE];
+    __shared__ double s_f[STAGE][NF];
+    __shared__ unsigned int s_mask[SEG_THREADS][STAGE / 32 + 1];          // (+ 1: the rows start in different banks)
+    const int t = threadIdx.x, lane = t & 63;
+    for (int w = 0; w < STAGE / 32; ++w) s_mask[t][w] = 0;          // (its own row; the others set bits in it behind the next barrier)
+    int cur = -1;
+    long long ccnt = 0;
+    double a[NF];
+#pragma unroll
+    for (int k = 0; k < NF; ++k) a[k] = 0.0;
+    auto slot_of = [&](int e) {          // s_off[lo] <= e < s_off[lo + 1]: the last slot that starts at or before e holds it
+        int lo = 0, hi = SEG_THREADS;
+        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (s_off[mid] <= e) lo = mid; else hi = mid; }
+        return lo;
+    };
+    auto consume = [&](int te) {
+        for (int w = 0; w < (te + 31) >> 5; ++w) {
+            unsigned int m = s_mask[t][w];
+            if (!m) continue;
+            s_mask[t][w] = 0;
+            while (m) {
+                const int j = (w << 5) + __ffs(m) - 1;
+                m &= m - 1;
+                const int id = s_id[j];
+                if (id != cur) {
+                    if (cur >= 0) flush_row(cur, a, ccnt);
+                    cur = id; ccnt = 0;
+#pragma unroll
+                    for (int k = 0; k < NF; ++k) a[k] = 0.0;
+                }
+#pragma unroll
+                for (int k = 0; k < NF; ++k) a[k] += s_f[j][k];
+                ccnt += s_cnt[j];
+            }
+        }
+    };
+    for (int64_t c0 = 0; c0 < n_slots; c0 += SEG_THREADS) {
+        const bool have = c0 + t < n_slots;
+        const int n = have ? (int)min(met_load(&slots[c0 + t].n), 64u) : 0;
+        int incl = n;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) { const int v = __shfl_up(incl, d, 64); if (lane >= d) incl += v; }
+        if (lane == 63) s_wave[t >> 6] = incl;
+        __syncthreads();
+        for (int w = 0; w < (t >> 6); ++w) incl += s_wave[w];
+        s_off[t + 1] = incl;
+        if (t == 0) s_off[0] = 0;
+        __syncthreads();
+        const int total = s_off[SEG_THREADS];
+        for (int e0 = 0; e0 < total; e0 += STAGE) {
+            const int te = min(STAGE, total - e0);
+            for (int j = t; j < te; j += SEG_THREADS) {
+                const int lo = slot_of(e0 + j), k = e0 + j - s_off[lo];          // (k < the slot's n <= 64; a slot past n_slots has n = 0 and holds no e)
+                const SegSlotN<NF>* sl = slots + c0 + lo;
+                const int id = seg_row(met_load(&sl->id[k]), n_segments);
+                s_id[j] = id; s_cnt[j] = met_load(&sl->cnt[k]);
+#pragma unroll
+                for (int q = 0; q < NF; ++q) s_f[j][q] = met_load(&sl->f[k][q]);
+                atomicOr(&s_mask[id & (SEG_THREADS - 1)][j >> 5], 1u << (j & 31));
+            }
+            __syncthreads();
+            consume(te);
+            __syncthreads();
+        }
+    }
+    if (cur >= 0) flush_row(cur, a, ccnt);
+}
+
+// centroidal-momentum sums per segment: row s of state [n_segments + 1][8] in the layout of k_metrics_com, a window's terms from com_window_add
+__global__ __launch_bounds__(SEG_THREADS) void k_metrics_com_seg(const float* pred, const float* y, int64_t batch, int nb, ComStats st, const int32_t* segment,
+                                                                 int32_t n_segments, double* state, SegScratch* sc) {
+    SegSlotCom* slots = reinterpret_cast<SegSlotCom*>(sc + 1);
+    const int64_t n_slots = (batch + 63) / 64;
+    for (int64_t base = (int64_t)blockIdx.x * SEG_THREADS; base < batch; base += (int64_t)gridDim.x * SEG_THREADS) {
+        const int64_t w = base + threadIdx.x, wave0 = base + (threadIdx.x & ~63);
+        if (wave0 >= batch) continue;          // (wave-uniform: this wave has no window, and no slot)
+        const bool valid = w < batch;
+        double a[4] = {0.0, 0.0, 0.0, 0.0};
+        int id = 0;
+        if (valid) {
+            id = seg_row(segment[w], n_segments);
+            com_window_add(pred, y, w, nb, st, a);
+        }
+        seg_wave_emit_n<4>(slots + (wave0 >> 6), valid, id, a);
+    }
+    if (!seg_last_block(sc)) return;
+    const double n3 = 3.0 * (double)nb;
+    seg_merge_n<4, 512>(slots, n_slots, n_segments, [&](int row, const double (&a)[4], long long cnt) {
+        double* r = state + (int64_t)row * 8;
+        const double c = (double)cnt;
+        r[0] += a[0]; r[1] += a[1]; r[2] += n3 * c; r[3] += n3 * c; r[4] += a[2]; r[5] += a[3]; r[6] += c;
+    });
+    if (threadIdx.x == 0) __hip_atomic_store(&sc->ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 static int met_blocks(int64_t items, int per_thread) {
     return (int)std::max<int64_t>(1, std::min<int64_t>(MET_BLOCKS, (items + per_thread * MET_THREADS - 1) / (per_thread * MET_THREADS)));
 }
@@ -1012,6 +1156,23 @@ extern "C" int mshgnn_metrics_classification_segmented(const float* logits, cons
     if ((uintptr_t)scratch & 7) return set_err(MSHGNN_EINVAL, "mshgnn_metrics_classification_segmented: the scratch must be 8-byte aligned");
     hipLaunchKernelGGL(k_metrics_cls_seg, dim3(seg_blocks(batch)), dim3(SEG_THREADS), 0, (hipStream_t)stream, logits, y, batch, segment, n_segments, ce_state,
                        reinterpret_cast<long long*>(counts), reinterpret_cast<SegScratch*>(scratch));
+    HIPCHK(hipGetLastError());
+    return MSHGNN_OK;
+}
+
+extern "C" size_t mshgnn_metrics_com_segmented_scratch_bytes(int64_t batch) {
+    return batch < 1 ? 0 : sizeof(SegScratch) + sizeof(SegSlotCom) * (size_t)((batch + 63) / 64);
+}
+
+extern "C" int mshgnn_metrics_com_segmented(const float* y_pred, const float* y, int64_t batch, int n_bases, const double* y_mean, const double* y_std,
+                                            const int32_t* segment, int32_t n_segments, double* state, void* scratch, void* stream) {
+    if (!y_pred || !y || !y_mean || !y_std || !segment || !state || !scratch) return set_err(MSHGNN_EINVAL, "null argument to mshgnn_metrics_com_segmented");
+    if (batch < 1 || n_bases < 1 || n_segments < 1) return set_err(MSHGNN_EINVAL, "mshgnn_metrics_com_segmented: batch, n_bases and n_segments must be >= 1");
+    if (((uintptr_t)state | (uintptr_t)scratch) & 7) return set_err(MSHGNN_EINVAL, "mshgnn_metrics_com_segmented: the state and the scratch must be 8-byte aligned");
+    ComStats st;
+    for (int k = 0; k < 6; ++k) { st.mean[k] = y_mean[k]; st.std[k] = y_std[k]; }
+    hipLaunchKernelGGL(k_metrics_com_seg, dim3(seg_blocks(batch)), dim3(SEG_THREADS), 0, (hipStream_t)stream, y_pred, y, batch, n_bases, st, segment, n_segments,
+                       state, reinterpret_cast<SegScratch*>(scratch));
     HIPCHK(hipGetLastError());
     return MSHGNN_OK;
 }

@@ -108,6 +108,7 @@ EXPORTS = [
     "mshgnn_input_grad", "mshgnn_forward_series", "mshgnn_forward_series_stats_bytes", "mshgnn_step_mse_series_std", "mshgnn_step_ce_series_std",
     "mshgnn_dataset_starts",
     "mshgnn_metrics_segmented_scratch_bytes", "mshgnn_metrics_regression_segmented", "mshgnn_metrics_classification_segmented",
+    "mshgnn_metrics_com_segmented_scratch_bytes", "mshgnn_metrics_com_segmented",
     "mshgnn_sgd_step", "mshgnn_adamw_step", "mshgnn_grad_norm_scratch_bytes", "mshgnn_grad_norm", "mshgnn_grad_clip",
     "mshgnn_mlp_compile_host", "mshgnn_mlp_create", "mshgnn_mlp_destroy", "mshgnn_mlp_info_get", "mshgnn_mlp_workspace_bytes", "mshgnn_mlp_stash_offset",
     "mshgnn_mlp_forward", "mshgnn_mlp_backward", "mshgnn_mlp_step",
@@ -238,6 +239,11 @@ def load_library():
         lib.mshgnn_metrics_regression_segmented.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.mshgnn_metrics_classification_segmented.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                                                 C.c_void_p]
+    if hasattr(lib, "mshgnn_metrics_com_segmented"):
+        lib.mshgnn_metrics_com_segmented_scratch_bytes.restype = C.c_size_t
+        lib.mshgnn_metrics_com_segmented_scratch_bytes.argtypes = [C.c_int64]
+        lib.mshgnn_metrics_com_segmented.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p, C.c_int32,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p]
     # the MLP baselines (csrc/mshgnn_mlp.hip)
     lib.mshgnn_mlp_compile_host.argtypes = [C.POINTER(MshgnnMlpDesc), C.c_int, C.POINTER(MshgnnMlpInfo)]
     lib.mshgnn_mlp_create.argtypes = [C.POINTER(MshgnnMlpDesc), C.POINTER(C.c_void_p)]

@@ -11,7 +11,7 @@ loss a `training_step` returns (`mse_loss` / `ce_loss`, gnnLightning.py:709-722)
 launch of `mshgnn_mse_loss` / `mshgnn_ce_loss` (dL/dy_pred on the device), so a wrapper built on this class trains without torch's
 elementwise loss kernels.
 
-There is no CPU implementation: without a HIP device every method raises (`segmented_reference`, the numpy mirror the tests use as their yardstick, aside).
+There is no CPU implementation: without a HIP device every method raises (`segmented_reference` / `com_segmented_reference`, the numpy mirrors the tests use as their yardstick, aside).
 """
 from __future__ import annotations
 
@@ -301,12 +301,7 @@ def segmented_reference(y, y_pred, segment, n_segments: int, regression: bool = 
     n_segments = int(n_segments)
     if n_segments < 1:
         raise ValueError("n_segments must be >= 1")
-    seg = np.asarray(segment.cpu() if isinstance(segment, torch.Tensor) else segment).astype(np.int64).reshape(-1)
-    B = seg.shape[0]
-    row = np.where((seg >= 0) & (seg < n_segments), seg, n_segments)
-    order = np.argsort(row, kind="stable")
-    bounds = np.searchsorted(row[order], np.arange(n_segments + 2))
-    groups = [order[bounds[s]:bounds[s + 1]] for s in range(n_segments + 1)]
+    B, groups = _segment_groups(segment, n_segments)
     to_np = lambda a: np.asarray(a.detach().cpu() if isinstance(a, torch.Tensor) else a)
     if regression:
         yp = to_np(y_pred).astype(np.float32).reshape(B, -1).astype(np.float64)
@@ -328,6 +323,73 @@ def segmented_reference(y, y_pred, segment, n_segments: int, regression: bool = 
             ce_state[s] = (math.fsum(ce[g].ravel()), float(4 * g.size))
             counts[s] = c[g].sum(0)
     return ce_state, counts
+
+
+def _segment_groups(segment, n_segments: int):
+    """(batch, the window indices of every row 0 .. n_segments): an id outside [0, n_segments) belongs to the overflow row n_segments."""
+    import numpy as np
+    seg = np.asarray(segment.cpu() if isinstance(segment, torch.Tensor) else segment).astype(np.int64).reshape(-1)
+    row = np.where((seg >= 0) & (seg < n_segments), seg, n_segments)
+    order = np.argsort(row, kind="stable")
+    bounds = np.searchsorted(row[order], np.arange(n_segments + 2))
+    return seg.shape[0], [order[bounds[s]:bounds[s + 1]] for s in range(n_segments + 1)]
+
+
+def com_window_terms(y, y_pred, num_bases: int, y_mean, y_std):
+    """Per-window terms of the centroidal-momentum sums in float64, operation by operation as the kernels' `com_window_add` forms them (numpy: no fused
+    multiply-add): (sq [B][num_bases][6] squared differences, cos [B][2] the cosines of base node 0's lin / ang vectors after un-standardising,
+    sum (a / max(|a|, 1e-8)) (b / max(|b|, 1e-8)) with every sum of three in index order)."""
+    import numpy as np
+    to_np = lambda a: np.asarray(a.detach().cpu() if isinstance(a, torch.Tensor) else a)
+    nb = int(num_bases)
+    yp = to_np(y_pred).astype(np.float32).reshape(-1, nb, 6).astype(np.float64)
+    yy = to_np(y).astype(np.float32).reshape(-1, nb, 6).astype(np.float64)
+    if yp.shape != yy.shape:
+        raise ValueError("y and y_pred must hold batch x num_bases x 6 values")
+    mean, std = np.asarray(y_mean, dtype=np.float64).reshape(6), np.asarray(y_std, dtype=np.float64).reshape(6)
+    d = yp - yy
+    cos = np.empty((yp.shape[0], 2), dtype=np.float64)
+    for h in range(2):
+        pv = yp[:, 0, 3 * h:3 * h + 3] * std[3 * h:3 * h + 3] + mean[3 * h:3 * h + 3]
+        yv = yy[:, 0, 3 * h:3 * h + 3] * std[3 * h:3 * h + 3] + mean[3 * h:3 * h + 3]
+        pp = (pv[:, 0] * pv[:, 0] + pv[:, 1] * pv[:, 1]) + pv[:, 2] * pv[:, 2]
+        yq = (yv[:, 0] * yv[:, 0] + yv[:, 1] * yv[:, 1]) + yv[:, 2] * yv[:, 2]
+        pn, yn = np.maximum(np.sqrt(pp), 1e-8), np.maximum(np.sqrt(yq), 1e-8)
+        t = (pv / pn[:, None]) * (yv / yn[:, None])
+        cos[:, h] = (t[:, 0] + t[:, 1]) + t[:, 2]
+    return d * d, cos
+
+
+def com_segmented_reference(y, y_pred, segment, n_segments: int, num_bases: int, y_mean, y_std):
+    """Host mirror of one `SegmentedComMetrics.update` (numpy; no GPU), beside `segmented_reference`: the raw state float64 [n_segments + 1][8] the kernel
+    would ADD, overflow row included, in the layout of mshgnn_metrics_com_step -- [0] / [1] squared error of the lin / ang halves, [2] = [3] =
+    3 num_bases windows, [4] / [5] the cosine sums, [6] windows, [7] 0.  Terms: `com_window_terms`; every sum is `math.fsum`."""
+    import math
+
+    import numpy as np
+    n_segments, nb = int(n_segments), int(num_bases)
+    if n_segments < 1 or nb < 1:
+        raise ValueError("n_segments and num_bases must be >= 1")
+    B, groups = _segment_groups(segment, n_segments)
+    sq, cos = com_window_terms(y, y_pred, nb, y_mean, y_std)
+    if sq.shape[0] != B:
+        raise ValueError("one segment id per window")
+    state = np.zeros((n_segments + 1, 8), dtype=np.float64)
+    for s, g in enumerate(groups):
+        if g.size:
+            n3 = float(3 * nb * g.size)
+            state[s] = (math.fsum(sq[g][:, :, :3].ravel()), math.fsum(sq[g][:, :, 3:].ravel()), n3, n3, math.fsum(cos[g, 0]), math.fsum(cos[g, 1]),
+                        float(g.size), 0.0)
+    return state
+
+
+def com_table_from_state(state):
+    """The published values per segment from raw centroidal-momentum sums [..., 8] (torch float64, any device; the overflow row already cut off): `MSE`
+    (= ([0] + [1]) / ([2] + [3]): the mean over all 6 num_bases values), `MSE_lin`, `MSE_ang`, `cos_sim_lin`, `cos_sim_ang`, `avg_cos_sim`, `n` (windows).
+    An empty segment's means are NaN (0 / 0)."""
+    lin, ang = state[..., 4] / state[..., 6], state[..., 5] / state[..., 6]
+    return {"MSE": (state[..., 0] + state[..., 1]) / (state[..., 2] + state[..., 3]), "MSE_lin": state[..., 0] / state[..., 2],
+            "MSE_ang": state[..., 1] / state[..., 3], "cos_sim_lin": lin, "cos_sim_ang": ang, "avg_cos_sim": (lin + ang) / 2, "n": state[..., 6]}
 
 
 _SEG_REG_COLUMNS = ("MSE", "RMSE", "L1", "n")
@@ -423,3 +485,65 @@ class SegmentedMetrics:
         self.state.zero_()
         if self.counts is not None:
             self.counts.zero_()
+
+
+class SegmentedComMetrics:
+    """The sums of `ComStepMetrics` per segment (mshgnn_metrics_com_segmented, include/mshgnn.h): `update(y, y_pred, segment)` adds every window's squared
+    errors of the lin / ang halves and the two cosines of base node 0 to the row its id names, in ONE launch, bit-reproducibly (no floating-point
+    atomic).  The interface of `SegmentedMetrics`; `state` is fp64 [n_segments + 1][8] in the layout of mshgnn_metrics_com_step, the last row the overflow row."""
+
+    def __init__(self, n_segments: int, num_bases: int, y_mean, y_std, device=None):
+        if int(n_segments) < 1 or int(num_bases) < 1:
+            raise ValueError("n_segments and num_bases must be >= 1")
+        self.n_segments, self.num_bases = int(n_segments), int(num_bases)
+        mean = [float(v) for v in torch.as_tensor(y_mean, dtype=torch.float64).flatten().tolist()]
+        std = [float(v) for v in torch.as_tensor(y_std, dtype=torch.float64).flatten().tolist()]
+        if len(mean) != 6 or len(std) != 6:
+            raise ValueError("y_mean and y_std must have 6 entries (lin(3) | ang(3))")
+        self._mean, self._std = (C.c_double * 6)(*mean), (C.c_double * 6)(*std)
+        self.device = _device(device)
+        self.lib = eng.load_library()
+        if not hasattr(self.lib, "mshgnn_metrics_com_segmented"):
+            raise eng.MshgnnError("this build of the library has no mshgnn_metrics_com_segmented")
+        self.state = torch.zeros(self.n_segments + 1, 8, dtype=torch.float64, device=self.device)
+        self._scratch, self._scratch_batch = None, 0
+
+    def reserve(self, batch: int) -> None:
+        """The scratch for batches of up to `batch` windows (`update` grows it when needed; reserve before capturing `update` in a graph)."""
+        if batch > self._scratch_batch:
+            nbytes = int(self.lib.mshgnn_metrics_com_segmented_scratch_bytes(int(batch)))
+            self._scratch = torch.zeros((nbytes + 7) // 8, dtype=torch.int64, device=self.device)      # zeroed once; the calls own it from here
+            self._scratch_batch = int(batch)
+
+    def update(self, y: torch.Tensor, y_pred: torch.Tensor, segment: torch.Tensor) -> None:
+        """y / y_pred: batch x num_bases x 6 values as `ComStepMetrics.calculate_losses_step` takes them, segment: int32 [batch] on the device."""
+        dev = self.device
+        seg = segment.detach().to(dev, torch.int32).reshape(-1).contiguous()
+        batch = int(seg.numel())
+        if batch < 1:
+            raise ValueError("no windows")
+        yp = y_pred.detach().to(dev, torch.float32).reshape(-1).contiguous()
+        yy = y.detach().to(dev, torch.float32).reshape(-1).contiguous()
+        if yp.numel() != yy.numel() or yp.numel() != batch * self.num_bases * 6:
+            raise ValueError(f"y and y_pred must hold {self.num_bases} x 6 values for each of the {batch} segment ids")
+        self.reserve(batch)
+        with torch.cuda.device(dev):
+            eng._check(self.lib, self.lib.mshgnn_metrics_com_segmented(yp.data_ptr(), yy.data_ptr(), batch, self.num_bases, self._mean, self._std, seg.data_ptr(),
+                                                                       self.n_segments, self.state.data_ptr(), self._scratch.data_ptr(), _stream(dev)),
+                       "mshgnn_metrics_com_segmented")
+
+    def table(self) -> dict:
+        """fp64 device tensors [n_segments] (`com_table_from_state`); no synchronisation."""
+        return com_table_from_state(self.state[:self.n_segments])
+
+    def overflow(self) -> int:
+        """Windows whose id was outside [0, n_segments) since the last reset (one host synchronisation)."""
+        return int(round(float(self.state[self.n_segments, 6].item())))
+
+    def check(self) -> None:
+        n = self.overflow()
+        if n:
+            raise IndexError(f"{n} windows carried a segment id outside [0, {self.n_segments})")
+
+    def reset(self) -> None:
+        self.state.zero_()

@@ -72,8 +72,10 @@ class OutputAction:
         """The action on the labels of an `orbit` store (or a `DatasetView` of an orbit dataset), read off its element recipes -- not off the group file again:
         perm[e][k] = the position in element 0's `label_cols` of element e's `label_cols[k]`, sign[e][k] = element e's `label_signs[k]` times element 0's at
         that position.  One rule for 3-D GRFs ('fs' tables: 12 units with reflections), 1-D GRFs and contact flags ('ls': 4 units) and the MLP recipes.
-        ValueError: a store with one element, an orbit made with identity=False, a recipe without labels, duplicate label columns in element 0 (the Solo
-        recipes), a -1 sign with regression=False (logit pairs have no sign to flip)."""
+        Recipes that all carry `label_slots` (the Solo centroidal-momentum recipes made with symmetry=True, whose label columns repeat once per base node) are read by
+        slot instead of by column: 6, 12 or 24 units of width 1.
+        ValueError: a store with one element, an orbit made with identity=False, a recipe without labels, duplicate label columns in element 0 without slot
+        tracking (the default Solo recipes), a -1 sign with regression=False (logit pairs have no sign to flip)."""
         store = getattr(orbit_store, "dataset", orbit_store)
         recipes = list(getattr(store, "element_recipes", []) or [])
         if int(getattr(store, "n_elements", 1)) < 2 or len(recipes) < 2:
@@ -92,15 +94,19 @@ class OutputAction:
         lab0 = [int(c) for c in recipes[0].label_cols]
         if not lab0:
             raise ValueError("the store's recipe has no labels: the output action is read off the label tables")
-        if len(set(lab0)) != len(lab0):
-            raise ValueError("element 0 has duplicate label columns (the Solo centroidal-momentum recipes): no permutation can be read off them")
-        where = {c: k for k, c in enumerate(lab0)}
+        slotted = all(getattr(r, "label_slots", None) is not None for r in recipes)
+        # recipes that track their label slots (the Solo recipes made with symmetry=True: the 6 columns of Y repeat once per base node) name a label by its
+        # slot; every other recipe by its column, which must then be unique
+        key0 = [int(s) for s in recipes[0].label_slots] if slotted else lab0
+        if len(set(key0)) != len(key0):
+            raise ValueError("element 0 has duplicate label columns (the Solo centroidal-momentum recipes without symmetry=True): no permutation can be read off them")
+        where = {c: k for k, c in enumerate(key0)}
         sg0 = [int(x) for x in (recipes[0].label_signs or [1] * len(lab0))]
         perm, sign = [], []
         for e, r in enumerate(recipes):
-            lab = [int(c) for c in r.label_cols]
-            if sorted(lab) != sorted(lab0):
-                raise ValueError(f"element {e}: its label columns are not a permutation of element 0's")
+            lab = [int(c) for c in (r.label_slots if slotted else r.label_cols)]
+            if sorted(lab) != sorted(key0):
+                raise ValueError(f"element {e}: its label {'slots' if slotted else 'columns'} are not a permutation of element 0's")
             sg = [int(x) for x in (r.label_signs or [1] * len(lab))]
             perm.append([where[c] for c in lab])
             sign.append([sg[k] * sg0[perm[e][k]] for k in range(len(lab))])
@@ -221,13 +227,24 @@ def Symmetrised(wrapper, action: OutputAction):
     `MLP_Lightning`) whose `step_helper_function` runs the wrapped model on an ORBIT-COMPLETE batch and returns the labels of its first B windows with the
     orbit-averaged prediction: `training_step` / `validation_step` / `test_step` / `predict_step`, the metric state and the flat optimizers work on it unchanged,
     the backward reaches the engine through the two-call route.  The view shares the model (its parameters) with `wrapper` and keeps metric state and `logged`
-    of its own; `view.raw` is `wrapper`.  `fused_training_step` is off: that step's loss is the raw model's.  The centroidal-momentum wrappers are refused (their
-    recipes have no orbit), and so is `grf_body_to_world_frame` (the world-frame metrics would pair K . B quaternions with B predictions)."""
+    of its own; `view.raw` is `wrapper`.  `fused_training_step` is off: that step's loss is the raw model's.  `grf_body_to_world_frame` is refused (the
+    world-frame metrics would pair K . B quaternions with B predictions).
+
+    The centroidal-momentum wrappers (`COM_HGNN_SYM_Lightning`, `COM_HGNN_Lightning`, `COM_MLP_Lightning`) are taken with the action of a Solo orbit made from
+    `symmetry=True` recipes: width 1 and a row of `num_bases * 6` units; the labels of the first B windows and the averaged prediction go through
+    `ComStepMetrics` as any batch does.  Of these models only `COM_HGNN_K4` (gs, gt, gr) and `COM_HGNN_C2` (gs) are equivariant ARCHITECTURES, and only on the
+    dataset's zero base series (the COM models mask the joints only): their symmetrised view changes nothing but rounding.  `COM_HGNN_S4`, `COM_HGNN` and the
+    MLP are the baselines one symmetrises."""
     from . import wrappers
     if isinstance(wrapper, wrappers.COM_Base_Lightning):
-        raise ValueError("Symmetrised does not take the centroidal-momentum (COM) wrappers: the Solo recipes have no orbit")
-    if not isinstance(wrapper, (wrappers._HGNNWrapper, wrappers.MLP_Lightning)):
-        raise TypeError(f"Symmetrised takes a GRF wrapper or MLP_Lightning, not {type(wrapper).__name__}")
+        if not isinstance(action, OutputAction):
+            raise TypeError("action must be an OutputAction")
+        row = int(wrapper.model.num_bases) * 6
+        if action.width != 1 or action.row != row:
+            raise ValueError(f"this centroidal-momentum (COM) wrapper has {row} outputs per window (num_bases * 6): it needs an output action of width 1 over "
+                             f"{row} units (a Solo orbit of symmetry=True recipes), not {action.n_units} units of width {action.width}")
+    elif not isinstance(wrapper, (wrappers._HGNNWrapper, wrappers.MLP_Lightning)):
+        raise TypeError(f"Symmetrised takes a GRF wrapper, a COM wrapper or MLP_Lightning, not {type(wrapper).__name__}")
     if getattr(wrapper, "body_to_world_frame", False):
         raise ValueError("Symmetrised does not take grf_body_to_world_frame=True: evaluate the symmetrised predictions in the body frame")
     if not isinstance(action, OutputAction):

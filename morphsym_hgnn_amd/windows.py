@@ -38,9 +38,33 @@ class WindowRecipe:
     quat_series: Optional[str] = None
     normalize: bool = False                                 # per-window standardisation (flexibleDataset.py:390-396)
     # group-transformed windows (`transformed`): which part of the morphological symmetry group acts on a series' columns, and the +-1 a run / a label carries
-    symmetry_parts: Optional[Dict[str, str]] = None         # series name -> "js" | "fs" | "bs_lin" | "bs_ang" | "ls"
+    symmetry_parts: Optional[Dict[str, str]] = None         # series name -> "js" | "fs" | "bs_lin" | "bs_ang" | "ls" (labels also: the compound "bs_linang")
     variable_signs: Optional[Dict[str, List[List[List[int]]]]] = None      # per type: [variable][node][axis] of +-1, mirroring `variables` (None: all +1)
     label_signs: Optional[List[int]] = None                 # [n_label] of +-1 (None: all +1)
+    # the position of every label in the UNTRANSFORMED recipe, permuted with the labels by `transformed` (host-only: not in `tables()` or the descriptor).
+    # It names a label where its column cannot: the Solo labels repeat the 6 columns of Y once per base node (`symmetrise.OutputAction.from_recipes`)
+    label_slots: Optional[List[int]] = None
+
+    def _linang_table(self, operator: str, group: "GroupAction", mode: str) -> Tuple[List[int], List[int]]:
+        """(P, c) of the compound label part "bs_linang" over this recipe's labels [n_base][lin(3) | ang(3)]: slot 6 node + a takes entry 3 node + a of the
+        'bs_lin' table for a < 3 and entry 3 node + (a - 3) of 'bs_ang' otherwise -- the base nodes permuted by `permutation_Q_bs`, the lin halves reflected by
+        `reflection_Q_bs_lin`, the ang halves by `reflection_Q_bs_ang`.  ONE copy (6 labels) against tables tiled over 2 or 4 base nodes: the copy's own
+        reflection, no permutation (the `one_node` rule of the variables)."""
+        n = len(self.label_cols)
+        (P, cl), (_, ca) = group.table("bs_lin", operator, mode), group.table("bs_ang", operator, mode)
+        if n % 6 or len(P) % 3:
+            raise ValueError(f"labels '{self.label_series}': the 'bs_linang' part acts on [n_base][lin(3) | ang(3)] labels, not on {n}")
+        nb, nt = n // 6, len(P) // 3
+        if any(P[3 * j + i] != P[3 * j] + i or P[3 * j] % 3 for j in range(nt) for i in range(3)):
+            raise ValueError("bs_linang: the base permutation must map node triples to node triples in axis order")
+        if nb == 1 and nt != 1 and all(c[k] == c[k % 3] for c in (cl, ca) for k in range(len(P))):
+            nodes = [0]
+        elif nb == nt:
+            nodes = [P[3 * j] // 3 for j in range(nb)]
+        else:
+            raise ValueError(f"labels '{self.label_series}': {nb} base nodes, but the group's 'bs' tables have {nt}")
+        return ([6 * nodes[k // 6] + k % 6 for k in range(n)],
+                [int(cl[3 * (k // 6) + k % 6] if k % 6 < 3 else ca[3 * (k // 6) + k % 6 - 3]) for k in range(n)])
 
     def transformed(self, operator: str, group: "GroupAction", mode: str = "MorphSym") -> "WindowRecipe":
         """The recipe of g . window for g = operator in ("gs", "gt", "gr"): what the reference's dataset classes build with `symmetry_operator`
@@ -66,8 +90,9 @@ class WindowRecipe:
         if mode not in GroupAction.MODES:
             raise ValueError(f"unknown symmetry mode {mode!r}: one of {GroupAction.MODES}")
         if self.symmetry_parts is None:
-            raise ValueError("this recipe does not say which part of the group acts on its series (symmetry_parts is None); the Solo-12 recipes are out of "
-                             "scope: the reference's own loader hands apply_symmetry a Python list there (soloDataset.py:619-623, 722-739)")
+            raise ValueError("this recipe does not say which part of the group acts on its series (symmetry_parts is None); the Solo-12 recipes name theirs only "
+                             "when made with symmetry=True: the reference's own loader cannot run there, it hands apply_symmetry a Python list "
+                             "(soloDataset.py:619-623, 722-739)")
         variables, signs = {}, {}
         for t in self.node_types:
             variables[t], signs[t] = [], []
@@ -83,18 +108,23 @@ class WindowRecipe:
                 nsig = [int(c[k]) * int(fsig[P[k]]) for k in range(len(flat))]
                 variables[t].append((s, [nflat[i:i + na] for i in range(0, len(nflat), na)]))
                 signs[t].append([nsig[i:i + na] for i in range(0, len(nsig), na)])
-        label_cols, label_signs = list(self.label_cols), self.label_signs
+        label_cols, label_signs, label_slots = list(self.label_cols), self.label_signs, self.label_slots
         if self.label_cols:
             if self.label_series not in self.symmetry_parts:
                 raise ValueError(f"label series '{self.label_series}' has no entry in symmetry_parts")
-            P, c = table(self.symmetry_parts[self.label_series], len(self.label_cols), f"labels '{self.label_series}'")
+            if self.symmetry_parts[self.label_series] == "bs_linang":
+                P, c = self._linang_table(operator, group, mode)
+            else:
+                P, c = table(self.symmetry_parts[self.label_series], len(self.label_cols), f"labels '{self.label_series}'")
             if self.label_rotate and any(P[3 * j + i] != P[3 * j] + i or P[3 * j] % 3 for j in range(len(P) // 3) for i in range(3)):
                 # the rotation acts on whole (x, y, z) triples of one foot BEFORE the transform: the permuted columns must still be such triples
                 raise ValueError("label_rotate: the label permutation must map foot triples to foot triples in axis order")
             old = self.label_signs or [1] * len(self.label_cols)
             label_cols = [self.label_cols[P[k]] for k in range(len(P))]
             label_signs = [int(c[k]) * int(old[P[k]]) for k in range(len(P))]
-        return dataclasses.replace(self, variables=variables, variable_signs=signs, label_cols=label_cols, label_signs=label_signs)
+            if self.label_slots is not None:
+                label_slots = [self.label_slots[P[k]] for k in range(len(P))]
+        return dataclasses.replace(self, variables=variables, variable_signs=signs, label_cols=label_cols, label_signs=label_signs, label_slots=label_slots)
 
     def width(self, t: str) -> int:
         w = sum(len(cols[0]) * self.history for _, cols in self.variables.get(t, []))
@@ -293,16 +323,24 @@ def minicheetah_k4_recipe(joint_perm: Sequence[int], foot_perm: Sequence[int], h
         symmetry_parts={"imu_acc": "bs_lin", "imu_omega": "bs_ang", "q": "js", "qd": "js", "p": "fs", "v": "fs", "contacts": "ls"})
 
 
-def solo_com_recipe(kind: str, joint_perm: Sequence[int], history: int = 1) -> WindowRecipe:
+# What the group acts on in the Solo recipes made with symmetry=True (cfg/solo-k4.yaml, cfg/solo-c2.yaml): q / qd by the `js` tables, the base series by `bs`
+# with its lin / ang reflections, the labels [n_base][lin(3) | ang(3)] by the compound part "bs_linang" (`WindowRecipe._linang_table`).
+SOLO_SYMMETRY_PARTS = {"q": "js", "qd": "js", "base_lin": "bs_lin", "base_ang": "bs_ang", "Y": "bs_linang"}
+
+
+def solo_com_recipe(kind: str, joint_perm: Sequence[int], history: int = 1, symmetry: bool = False) -> WindowRecipe:
     """The Solo-12 centroidal-momentum dataset (BASELINE configs[3] data format) on the K4 / C2 / S4 graphs: joint = (q, qd) in graph
     order, base = the (all-zero) IMU series tiled to the base nodes, labels = the 6-D base velocity of the window's last row, once per
-    base node as [lin(3) | ang(3)] (soloDataset.py:235-300, 382-400, 546-717).  Series: `solo_com_arrays(X, Y)`."""
+    base node as [lin(3) | ang(3)] (soloDataset.py:235-300, 382-400, 546-717).  Series: `solo_com_arrays(X, Y)`.
+    symmetry=True: the recipe names the group parts of its series (`SOLO_SYMMETRY_PARTS`) and tracks its label slots, so `transformed` / `orbit` and
+    `symmetrise.OutputAction.from_recipes` take it; the default recipe stays the reference's (its own loader cannot transform these windows)."""
     nb = {"k4_com": 4, "c2_com": 2, "s4_com": 1}[kind]
     return WindowRecipe(
         node_types=["base", "joint"], num_nodes={"base": nb, "joint": len(joint_perm)}, history=history,
         variables={"base": [("base_lin", [[0, 1, 2]] * nb), ("base_ang", [[0, 1, 2]] * nb)],
                    "joint": [(s, [[int(j)] for j in joint_perm]) for s in ("q", "qd")]},
-        label_series="Y", label_cols=[0, 1, 2, 3, 4, 5] * nb)
+        label_series="Y", label_cols=[0, 1, 2, 3, 4, 5] * nb,
+        symmetry_parts=dict(SOLO_SYMMETRY_PARTS) if symmetry else None, label_slots=list(range(6 * nb)) if symmetry else None)
 
 
 MLP_NODE_TYPE = "mlp"
@@ -343,11 +381,12 @@ def minicheetah_mlp_recipe(joint_perm: Sequence[int], foot_perm: Sequence[int], 
                       False, None, normalize, g.symmetry_parts)
 
 
-def solo_com_mlp_recipe(joint_perm: Sequence[int], history: int = 1) -> WindowRecipe:
+def solo_com_mlp_recipe(joint_perm: Sequence[int], history: int = 1, symmetry: bool = False) -> WindowRecipe:
     """The Solo-12 centroidal-momentum dataset as the MLP baseline reads it (gnnLightning_com.py:234-287): in = history x 24 (q | qd), labels = the 6-D base
-    velocity of the window's last row; series names of `solo_com_recipe` / `solo_com_arrays`."""
+    velocity of the window's last row; series names of `solo_com_recipe` / `solo_com_arrays`; symmetry: as there (6 labels: one copy's reflection)."""
     jp = [int(j) for j in joint_perm]
-    return mlp_recipe([("q", jp), ("qd", jp)], history, "Y", [0, 1, 2, 3, 4, 5])
+    r = mlp_recipe([("q", jp), ("qd", jp)], history, "Y", [0, 1, 2, 3, 4, 5], symmetry_parts=dict(SOLO_SYMMETRY_PARTS) if symmetry else None)
+    return dataclasses.replace(r, label_slots=list(range(6))) if symmetry else r
 
 
 def solo_com_arrays(X: np.ndarray, Y: np.ndarray) -> Dict[str, np.ndarray]:

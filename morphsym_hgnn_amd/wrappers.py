@@ -868,19 +868,28 @@ class EvaluationTable:
     """What `evaluate_table` returns: `predictions` (exactly `evaluate_sequence`'s), `table` -- a dict of fp64 tensors [K][n_sequences], one row per
     operator and one column per sequence (`metrics.table_from_state`: regression MSE / RMSE / L1 / n, classification CE / accuracy / f1_leg_0..3 /
     f1_avg_legs / n) --, `operators` ("None", then the orbit's), `names` (the sequences') and, for classification, `totals`: the same values per
-    operator over ALL sequences, [K].  With `grf_body_to_world_frame` wrappers `table_world` holds the world-frame values."""
+    operator over ALL sequences, [K].  With `grf_body_to_world_frame` wrappers `table_world` holds the world-frame values.
 
-    def __init__(self, predictions, table, operators, names, regression: bool = True, totals=None, table_world=None):
+    The centroidal-momentum form (`com=True`): `table` holds `metrics.com_table_from_state`'s values (MSE, MSE_lin, MSE_ang, cos_sim_lin, cos_sim_ang,
+    avg_cos_sim, n) per (operator, sequence), `totals` the same per operator over all sequences, and the CSV is the reference's
+    (research/evaluator_regression-com.py:50-76): one row per operator with Test Loss (= MSE), Test Cos Sim Lin and Test Cos Sim Ang."""
+
+    def __init__(self, predictions, table, operators, names, regression: bool = True, totals=None, table_world=None, com: bool = False):
         self.predictions, self.table, self.operators, self.names = predictions, table, list(operators), list(names)
-        self.regression, self.totals, self.table_world = bool(regression), totals, table_world
+        self.regression, self.totals, self.table_world, self.com = bool(regression), totals, table_world, bool(com)
 
     def header(self):
+        if self.com:             # evaluator_regression-com.py:50
+            return ["Symmetry Operator", "Test Loss", "Test Cos Sim Lin", "Test Cos Sim Ang"]
         if self.regression:      # evaluator_regression-grf_c2.py:170-179
             return ["Swap"] + [f"{name}-{m}" for name in self.names for m in ("MSE", "RMSE", "L1")]
         return ["Symmetry Operator", "Model Accuracy", "Rear-Left", "Front-Left", "Rear-Right", "Front-Right", "F1 Avg"]      # evaluator_classification_k4.py:52
 
     def rows(self):
         """One list per operator: its name, then the header's values as Python floats (one device -> host copy per column)."""
+        if self.com:
+            cols = [self.totals[m].detach().cpu().tolist() for m in ("MSE", "cos_sim_lin", "cos_sim_ang")]
+            return [[op] + [c[k] for c in cols] for k, op in enumerate(self.operators)]
         if self.regression:
             cols = {m: self.table[m].detach().cpu().tolist() for m in ("MSE", "RMSE", "L1")}
             return [[op] + [cols[m][k][s] for s in range(len(self.names)) for m in ("MSE", "RMSE", "L1")] for k, op in enumerate(self.operators)]
@@ -891,7 +900,8 @@ class EvaluationTable:
 
     def to_csv(self, path) -> None:
         """One row per operator, the evaluators' columns (regression: per sequence `<name>-MSE`, `<name>-RMSE`, `<name>-L1`; classification: accuracy, the
-        four per-leg F1 scores and their average over all sequences).  path: a file name or an open text stream."""
+        four per-leg F1 scores and their average over all sequences; centroidal momentum: loss and the two cosine similarities over all sequences).  path: a
+        file name or an open text stream."""
         import csv
         if hasattr(path, "write"):
             w = csv.writer(path, lineterminator="\n")
@@ -908,20 +918,27 @@ def evaluate_table(wrapper, view_or_dataset, edge_index_dict, batch_size: int, s
     its sums to that row -- the evaluators' whole table (one CSV row per symmetry operator, research/evaluator_regression-grf_c2.py:170-221,
     evaluator_classification_k4.py:57-89) out of one pass over an `orbit` view, with no host read until the sweep is over.  The wrapper's own epoch metrics
     are left in its state as `evaluate_sequence` leaves them.  With `grf_body_to_world_frame` a second table is kept on the rotated pairs (`test_only_on_z`
-    as in `calculate_losses_step_worldframe`)."""
-    from .metrics import SegmentedMetrics, table_from_state
+    as in `calculate_losses_step_worldframe`).
+
+    The centroidal-momentum (COM) wrappers, over a view of Solo recipes (an `orbit` of `symmetry=True` recipes, or a plain dataset: one row): the same sweep
+    with `metrics.SegmentedComMetrics` per (operator, sequence) -- the table research/evaluator_regression-com.py:50-76 writes, one row per operator."""
+    from .metrics import SegmentedComMetrics, SegmentedMetrics, com_table_from_state, table_from_state
     from .windows import DatasetView, ResidentDataset
-    if isinstance(wrapper, COM_Base_Lightning):
-        raise ValueError("evaluate_table does not take the centroidal-momentum (COM) wrappers: their recipes have no orbit and segmented cosine sums are not kept")
+    com = isinstance(wrapper, COM_Base_Lightning)
     if isinstance(view_or_dataset, ResidentDataset):
         view_or_dataset = view_or_dataset.view()
     if not isinstance(view_or_dataset, DatasetView):
+        if com:
+            raise ValueError("evaluate_table takes the centroidal-momentum (COM) wrappers over a windows.DatasetView or a windows.ResidentDataset only")
         raise TypeError("evaluate_table takes a windows.DatasetView or a windows.ResidentDataset")
     view = view_or_dataset
     K, S = view.segment_shape
     regression = bool(wrapper.regression)
     world = bool(getattr(wrapper, "body_to_world_frame", False))
-    seg_m = SegmentedMetrics(K * S, regression, device=view.dataset.device)
+    if com:
+        seg_m = SegmentedComMetrics(K * S, wrapper.model.num_bases, *wrapper.__dict__["_stats"], device=view.dataset.device)
+    else:
+        seg_m = SegmentedMetrics(K * S, regression, device=view.dataset.device)
     seg_w = SegmentedMetrics(K * S, True, device=view.dataset.device) if world else None
     seg_m.reserve(batch_size)
     if world:
@@ -944,10 +961,12 @@ def evaluate_table(wrapper, view_or_dataset, edge_index_dict, batch_size: int, s
     seg_m.check()
     shape = lambda t: {k: v.view(K, S) for k, v in t.items()}
     totals = None
-    if not regression:
+    if com:
+        totals = com_table_from_state(seg_m.state[:K * S].view(K, S, 8).sum(1))
+    elif not regression:
         n = K * S
         totals = table_from_state(seg_m.state[:n].view(K, S, 2).sum(1), seg_m.counts[:n].view(K, S, 18).sum(1))
     ops = ["None" if op is None else str(op) for op in getattr(view.dataset, "operators", [None])]
-    res = EvaluationTable(preds, shape(seg_m.table()), ops, view.names, regression, totals, shape(seg_w.table()) if world else None)
+    res = EvaluationTable(preds, shape(seg_m.table()), ops, view.names, regression, totals, shape(seg_w.table()) if world else None, com)
     res.metrics, res.metrics_world = seg_m, seg_w
     return res
