@@ -235,6 +235,32 @@ int mshgnn_step_mse_phase(const mshgnn_plan* plan, const void* const* x, const i
                           const float* y, float* out, float* loss_out, float* grad_params, void* workspace, int64_t batch,
                           int phase, void* stream);
 
+/* The regression loss of a plan: MSE (the default of a fresh plan), L1 or Huber -- torch.nn.MSELoss / L1Loss / HuberLoss(delta), mean reduction (the reference trains
+ * on MSE alone and has its L1 metric commented out, gnnLightning_com.py:66,77,103).  Per output element, d = out - y in fp32, inv_n the fp32 reciprocal of the element
+ * count of the WHOLE batch (chunked steps included), mask the plan's output mask:
+ *   MSE   (0): term = d d,                                                      g = 2 d inv_n mask
+ *   L1    (1): term = |d|,                                                      g = (d > 0 ? inv_n : d < 0 ? -inv_n : d inv_n) mask   (0 at d == 0; NaN for a NaN d)
+ *   Huber (2): term = |d| <= delta ? 0.5 d d : delta (|d| - 0.5 delta),         g = (d < -delta ? -delta : d > delta ? delta : d) inv_n mask
+ * loss = (sum of terms) inv_n, summed in the fixed order of the MSE path.
+ * EVERY ENTRY POINT WITH `mse` IN ITS NAME -- mshgnn_step_mse, _step_mse_src, _step_mse_phase (both phases), _backward_mse, _step_mse_series, _step_mse_series_std -- AND
+ * mshgnn_mlp_step(loss_kind 0) COMPUTES THE PLAN'S REGRESSION LOSS: with the default these are the MSE instructions on the MSE operands, unchanged.  THE SETTING IS READ
+ * WHEN THE CALL IS MADE AND PASSED BY VALUE in the kernel arguments: a captured graph keeps the kind and delta it was captured with, whatever the plan is set to later.
+ * delta is read for Huber only (finite and > 0) and ignored otherwise.  MSHGNN_EINVAL, with the function's name in mshgnn_last_error(): a null plan / pointer, an
+ * unknown kind, a Huber delta that is not finite and > 0.  A plan carries no task: the cross-entropy entry points never read the setting (the Python models refuse
+ * it on a classification model).  The setters are not thread-safe against calls in flight on the same plan.                                                          */
+#define MSHGNN_REG_LOSS_MSE 0
+#define MSHGNN_REG_LOSS_L1 1
+#define MSHGNN_REG_LOSS_HUBER 2
+int mshgnn_plan_set_regression_loss(mshgnn_plan* plan, int kind, float delta);
+int mshgnn_plan_get_regression_loss(const mshgnn_plan* plan, int32_t* kind_out, float* delta_out);
+/* (mshgnn_mlp_set_regression_loss / _get_regression_loss, the same pair for an MLP plan: with the MLP entry points below) */
+/* The same losses stand-alone, for the two-call routes: loss_out (device float[1]) = (sum of terms) / n and grad_out (nullable) [n] = g as above without a mask, in ONE
+ * launch for all three kinds.  No floating-point atomic and nothing to clear: every workgroup leaves its partial sum in `scratch`, the one that finishes last adds them
+ * in index order -- two runs give the same bits.  scratch: mshgnn_regression_loss_scratch_bytes(n) bytes (<= 1040) of device memory, 16-byte aligned, zeroed ONCE by
+ * the caller (every call leaves it ready for the next one on the same stream).  Kind 0 evaluates the expressions of mshgnn_mse_loss, which stays as it is.            */
+size_t mshgnn_regression_loss_scratch_bytes(int64_t n);
+int mshgnn_regression_loss(const float* out, const float* y, int64_t n, int kind, float delta, float* loss_out, float* grad_out, void* scratch, void* stream);
+
 /* Backward with the classification wrapper's cross entropy fused in (gnnLightning.py:640-648: CrossEntropyLoss over the
  * batch*4 per-foot logit pairs, mean).  `out` = the forward's logits [batch][n_out][2], labels int32 [batch][n_out] in
  * {0,1}; loss_out (device float[1]) receives the mean cross entropy.  Only for plans with out_channels == 2.            */
@@ -674,6 +700,10 @@ int mshgnn_mlp_backward(const mshgnn_mlp_plan* plan, const mshgnn_mlp_input* inp
  * and input->labels_out for loss_kind 1).  loss_out: device float[1].                                                                                      */
 int mshgnn_mlp_step(const mshgnn_mlp_plan* plan, const mshgnn_mlp_input* input, int loss_kind, const void* targets, const float* params, float* out,
                     float* loss_out, float* grad_params, void* workspace, int64_t batch, void* stream);
+/* What loss_kind 0 computes on this plan: mshgnn_plan_set_regression_loss / _get_regression_loss for an MLP plan (same kinds, same checks, a fresh plan is MSE; read
+ * when mshgnn_mlp_step is called and passed by value). */
+int mshgnn_mlp_set_regression_loss(mshgnn_mlp_plan* plan, int kind, float delta);
+int mshgnn_mlp_get_regression_loss(const mshgnn_mlp_plan* plan, int32_t* kind_out, float* delta_out);
 
 /* ---- symmetrisation over a group orbit (csrc/mshgnn_orbit.hip) -------------------------------------------------------------------------------------------
  * f_sym(x) = 1/|G| sum_g rho_out(g)^-1 f(rho_in(g) x) makes any model exactly equivariant; the reference has no such layer (its symmetric models are

@@ -159,15 +159,28 @@ def model_from_checkpoint(ckpt, model_type: str, data_metadata=None, **overrides
         kw["grf_dimension"] = hp.get("grf_dimension", 3 if cls is models.GRF_HGNN_C2 else 1)
     model = cls(int(hp["hidden_channels"]), int(hp["num_layers"]), meta, **kw)
     load_into(model, ckpt, strict=True)
+    _restore_regression_loss(model, hp)
     return model
+
+
+def _restore_regression_loss(model, hp) -> None:
+    """`regression_loss` / `huber_delta` of the hyper-parameters (written only when not the default, `to_lightning_checkpoint`) back onto the model."""
+    if hp.get("regression_loss", "mse") != "mse":
+        model.set_regression_loss(str(hp["regression_loss"]), float(hp.get("huber_delta", 1.0)))
 
 
 def to_lightning_checkpoint(model: nn.Module, hyper_parameters: Optional[dict] = None, prefix: str = "model.") -> dict:
     """The inverse: a dict in Lightning's layout whose `state_dict` the reference's wrappers load by name.  The reference's
     constructors need `dummy_batch` (gnnLightning.py:564-596), which is not stored here: pass it to `load_from_checkpoint`
     as a keyword argument next to the path, as `evaluate_model` passes its other overrides."""
+    hp = dict(hyper_parameters or {})
+    kind, delta = getattr(model, "regression_loss", ("mse", 1.0))      # (models.set_regression_loss; the reference's wrappers ignore unknown hyper-parameters' absence)
+    if kind != "mse":      # only when not the default: a default model's checkpoint is what it always was
+        hp.setdefault("regression_loss", kind)
+        if kind == "huber":
+            hp.setdefault("huber_delta", float(delta))
     return {"state_dict": {prefix + k: v.detach().cpu() for k, v in model.state_dict().items()},
-            "hyper_parameters": dict(hyper_parameters or {}), "pytorch-lightning_version": "2.1.0", "epoch": 0, "global_step": 0}
+            "hyper_parameters": hp, "pytorch-lightning_version": "2.1.0", "epoch": 0, "global_step": 0}
 
 
 # ---- the MLP baselines: `mlp_model.*` (MLP_Lightning, gnnLightning.py:407) / `model.*` (COM_MLP_Lightning, gnnLightning_com.py:279) -----------------------
@@ -204,4 +217,5 @@ def mlp_from_checkpoint(ckpt, model_type: str = "mlp", **overrides) -> nn.Module
             raise ValueError(f"hyper_parameters[{k!r}] = {hp[k]} but the weights say {v}")
     model = models.MLP(regression=bool(hp.get("regression", True)), **dims)
     model.load_state_dict(sd, strict=True)
+    _restore_regression_loss(model, hp)
     return model

@@ -888,8 +888,14 @@ template <typename T> __global__ __launch_bounds__(256) void k_dec_bwd(DecArgs a
                 if (a.labels) go = ce_g[d & 1];
                 else if (a.y) {   // wrapper MSE fused (gnnLightning.py:633-639): dL/dout = 2 (out - y) / n
                     const float dlt = a.out[r * a.dout + d] - a.y[r * a.dout + d];
-                    go = 2.0f * dlt * a.inv_n;
-                    if (c == 0) lsum += dlt * dlt;
+                    if (a.reg_kind == MSHGNN_REG_LOSS_MSE) {
+                        go = 2.0f * dlt * a.inv_n;
+                        if (c == 0) lsum += dlt * dlt;
+                    } else {      // L1 / Huber: the plan's regression loss
+                        float term;
+                        reg_loss_terms(dlt, a.inv_n, a.reg_kind, a.reg_delta, go, term);
+                        if (c == 0) lsum += term;
+                    }
                 } else go = a.gout[r * a.dout + d];
                 const float g = go * a.out_mask[f * a.dout + d];
                 accb[d] += g;
@@ -1584,6 +1590,25 @@ extern "C" int mshgnn_profile_read(mshgnn_plan* p, mshgnn_kernel_stat* stats, in
 }
 
 extern "C" const char* mshgnn_plan_specialised(const mshgnn_plan* p) { return p && !p->gen && p->use_spec ? p->spec_name : ""; }
+
+// The regression loss of the plan's `mse` entry points (include/mshgnn.h): checked here, read by value when a call is made (backward_mse, step_call, step_series).
+int check_regression_loss(int kind, float delta, const char* who) {
+    if (kind != MSHGNN_REG_LOSS_MSE && kind != MSHGNN_REG_LOSS_L1 && kind != MSHGNN_REG_LOSS_HUBER)
+        return set_err(MSHGNN_EINVAL, std::string(who) + ": kind must be MSHGNN_REG_LOSS_MSE, _L1 or _HUBER");
+    if (kind == MSHGNN_REG_LOSS_HUBER && !(std::isfinite(delta) && delta > 0.f)) return set_err(MSHGNN_EINVAL, std::string(who) + ": Huber's delta must be finite and > 0");
+    return MSHGNN_OK;
+}
+extern "C" int mshgnn_plan_set_regression_loss(mshgnn_plan* p, int kind, float delta) {
+    if (!p) return set_err(MSHGNN_EINVAL, "null argument to mshgnn_plan_set_regression_loss");
+    if (const int rc = check_regression_loss(kind, delta, "mshgnn_plan_set_regression_loss")) return rc;
+    p->reg_kind = kind; p->reg_delta = kind == MSHGNN_REG_LOSS_HUBER ? delta : 1.0f;
+    return MSHGNN_OK;
+}
+extern "C" int mshgnn_plan_get_regression_loss(const mshgnn_plan* p, int32_t* kind_out, float* delta_out) {
+    if (!p || !kind_out || !delta_out) return set_err(MSHGNN_EINVAL, "null argument to mshgnn_plan_get_regression_loss");
+    *kind_out = p->reg_kind; *delta_out = p->reg_delta;
+    return MSHGNN_OK;
+}
 extern "C" int mshgnn_plan_info(const mshgnn_plan* p, mshgnn_info* info) {
     if (!p || !info) return set_err(MSHGNN_EINVAL, "null argument");
     *info = p->gen ? *gen_info(p) : p->hp.info;
@@ -1896,6 +1921,7 @@ extern "C" int mshgnn_backward_mse(const mshgnn_plan* p, const void* const* x, c
     StepCall c;
     if (const int rc = backward_entry(p, x, x_pitch, params, grad_params, workspace, batch, stream, c)) return rc;
     c.loss = LossKind::MSE; c.out = const_cast<float*>(out); c.y = y; c.loss_out = loss_out;      // (the backward only reads out)
+    c.reg_kind = p->reg_kind; c.reg_delta = p->reg_delta;
     return run_backward(p, c);
 }
 
@@ -1917,7 +1943,8 @@ static int step_call(const mshgnn_plan* p, const char* who, const void* const* x
     if (batch < 1 || batch > (1 << 24)) return set_err(MSHGNN_EINVAL, "batch must be in [1, 2^24]");
     c.x = x; c.x_pitch = x_pitch; c.params = params; c.out = out; c.ws = (char*)workspace; c.batch = batch; c.training = 1; c.stream = (hipStream_t)stream;
     c.loss = kind; c.loss_out = loss_out; c.grad_params = grad_params;
-    if (kind == LossKind::MSE) c.y = static_cast<const float*>(target); else c.labels = static_cast<const int32_t*>(target);
+    if (kind == LossKind::MSE) { c.y = static_cast<const float*>(target); c.reg_kind = p->reg_kind; c.reg_delta = p->reg_delta; }
+    else c.labels = static_cast<const int32_t*>(target);
     return MSHGNN_OK;
 }
 static int step_entry(const mshgnn_plan* p, const WideSrc* wide, const void* const* x, const int64_t* x_pitch, const float* params, LossKind kind, const void* target,
@@ -2154,6 +2181,7 @@ static int step_series(const mshgnn_plan* p, const SeriesArgs& s, bool std_route
     StepCall c;
     c.x = x_out; c.x_pitch = x_pitch; c.params = params; c.out = out; c.ws = (char*)workspace; c.batch = s.batch; c.training = 1; c.stream = (hipStream_t)stream;
     c.loss = ce ? LossKind::CE : LossKind::MSE; c.y = s.y_out; c.labels = s.labels_out; c.loss_out = loss_out; c.grad_params = grad_params;
+    if (!ce) { c.reg_kind = p->reg_kind; c.reg_delta = p->reg_delta; }
     c.series = &ser;
     c.gradw_from_series = !x_out;      // no materialised windows at all (plain bf16 route only, see above): the weight-gradient kernel gathers its raw-input operands from the series as well
     return run_step(p, c);

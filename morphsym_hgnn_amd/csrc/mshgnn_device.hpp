@@ -882,6 +882,7 @@ struct StackArgs {
                          // runs 11 % faster when the stack launch's writes do not allocate on their way out (stash_nt_for); a uniform choice per launch, same bits
     int stagger;         // two workgroups per CU: the second half of the grid starts this many cycles late, so that one workgroup's MAC phases
                          // (matrix pipe) run beside the other's epilogues (stores) instead of both competing for the same unit (0: off)
+    int reg_kind; float reg_delta;      // with y: the plan's regression loss when the call was made (MSHGNN_REG_LOSS_*; 0 = MSE) and Huber's delta, by value
 };
 // The arguments as the kernel of a compile-time program sees them: the same member names (references into the kernel-argument segment), except the scalars
 // that every node's stores read -- batch size, store policy, training flag -- which are COPIES pinned in SGPRs.  hipcc otherwise re-loads those from the
@@ -1268,6 +1269,24 @@ __device__ __forceinline__ void decoder_ops_load(const StackArgs& a, int tid, in
         }
     }
 }
+// The robust regression losses of the fused steps (mshgnn_plan_set_regression_loss), per output element, d = out - y in fp32 and inv_n the mean's factor of the MSE path:
+//   L1    (kind 1): term = |d|, g = sign(d) inv_n -- 0 at d == 0, NaN for a NaN d (the ordered compares are false, d inv_n is left)
+//   Huber (kind 2): term = |d| <= delta ? d^2 / 2 : delta (|d| - delta / 2), g = clamp(d, -delta, delta) inv_n -- a NaN d reaches g the same way
+// (torch.nn.L1Loss / HuberLoss(delta), mean reduction).  Written ONCE: the decoder tail, the three decoder backwards, the MLP tail and the stand-alone operator all call
+// this for kinds 1 and 2, so their gradients agree bit for bit by construction.  Every operation rounds on its own (no contraction): the host mirror of the tests
+// (tests/loss_reference.py) evaluates the same expressions left to right.  kind and delta are wave-uniform kernel arguments: a scalar branch.  MSE (kind 0) never comes here.
+__device__ __forceinline__ void reg_loss_terms(float d, float inv_n, int kind, float delta, float& g, float& term) {
+#pragma clang fp contract(off)
+    const float ad = __builtin_fabsf(d);
+    if (kind == MSHGNN_REG_LOSS_L1) {
+        term = ad;
+        g = d > 0.f ? inv_n : (d < 0.f ? -inv_n : d * inv_n);
+    } else {
+        term = ad <= delta ? 0.5f * d * d : delta * (ad - 0.5f * delta);
+        const float c = d < -delta ? -delta : (d > delta ? delta : d);
+        g = c * inv_n;
+    }
+}
 template <typename T, int THREADS, int DMAX, bool SPLIT = false, bool TOLDS = false, int NPP = 2, bool PRE = false, class K = DecDyn>      // DMAX: compile-time bound on the output channels (4 or 8): loops, loads and registers scale with it; NPP: nodes per pass; PRE: *pre holds pass 0's operands; K: DecDyn / DecFacts
 __device__ __forceinline__ void decoder_tail_impl(const StackArgs& a, char* smem, int tid, int lane, int wv, int w0, int B, DecOps<DMAX, NPP>* pre = nullptr) {
     // decoder on the out-type rows of X_L (hgnn_c2.py:176-189): thread = (node, row, 8-column chunk).  With y (mshgnn_step_mse) the
@@ -1340,8 +1359,18 @@ __device__ __forceinline__ void decoder_tail_impl(const StackArgs& a, char* smem
                             if (ce) g = ce_g[dd & 1] * mk[i][dd];
                             else {
                                 const float dlt = ov[i][dd] - yv[i][dd];
-                                g = 2.0f * dlt * a.inv_n * mk[i][dd];
-                                if (c == 0) lsum = __builtin_fmaf(dlt, dlt, lsum);
+                                // The tails compiled for a program (KS: the tuned kernels of the bf16 plan's compile-time programs) are MSE ONLY -- with the L1 / Huber arm
+                                // in them the MiniCheetah-K4 L = 8 step spilled 43 SGPRs instead of 28 and ran 1.3 % slower on MSE.  A call at another kind never picks
+                                // them: stack_query (mshgnn_launch.hpp) sends it to the interpreting kernels, whose tail (DecDyn) has both arms.
+                                if (KS || a.reg_kind == MSHGNN_REG_LOSS_MSE) {
+                                    g = 2.0f * dlt * a.inv_n * mk[i][dd];
+                                    if (c == 0) lsum = __builtin_fmaf(dlt, dlt, lsum);
+                                } else {      // L1 / Huber (mshgnn_plan_set_regression_loss): uniform, off the MSE path
+                                    float gr, term;
+                                    reg_loss_terms(dlt, a.inv_n, a.reg_kind, a.reg_delta, gr, term);
+                                    g = gr * mk[i][dd];
+                                    if (c == 0) lsum += term;
+                                }
                             }
                             accb[dd] += g;
 #pragma unroll
@@ -1470,6 +1499,7 @@ struct DecArgs {
     int64_t off_w, off_b; int B, NN, node0, n_out, dout, slab0;
     const float* y; float* loss; float inv_n;   // fused MSE: gout = 2 (out - y) / n computed on the fly, loss accumulated
     const int32_t* labels;                      // fused cross entropy (dout == 2): gout = (softmax(out) - onehot) / rows
+    int reg_kind; float reg_delta;              // with y: MSHGNN_REG_LOSS_* (0 = MSE, the expressions above) and Huber's delta (reg_loss_terms)
 };
 
 
@@ -1582,6 +1612,8 @@ struct mshgnn_plan {
     int n_types = 0;
     mshgnn_gen_state* gen = nullptr;    // set: this plan runs on the generic-width engine (hidden != 128, many nodes, ...), hp is unused
     int dbg = 0;                        // timing ablations (instrumented builds only: read once from MSHGNN_DBG at plan creation)
+    int reg_kind = MSHGNN_REG_LOSS_MSE; // what the entry points with `mse` in their name compute (mshgnn_plan_set_regression_loss): read when a call is made, by value into its StepCall
+    float reg_delta = 1.0f;             //   Huber's delta
 };
 
 // in-kernel stamp buffers of the instrumented builds (tools/stamps_*.py pass a device pointer through the environment)
@@ -1661,6 +1693,8 @@ struct StepCall {
     // what the backward starts from: the output's gradient, or a loss fused into the decoder backward (forward: into its tail, where the engine has one)
     const float* grad_out = nullptr;
     LossKind loss = LossKind::NONE;
+    int reg_kind = MSHGNN_REG_LOSS_MSE;   // LossKind::MSE: the plan's regression loss when the call was made (mshgnn_plan_set_regression_loss), by value into the kernels
+    float reg_delta = 1.0f;               //   Huber's delta
     const float* y = nullptr;             // LossKind::MSE
     const int32_t* labels = nullptr;      // LossKind::CE
     float* loss_out = nullptr;
@@ -1687,6 +1721,7 @@ struct StepCall {
 #define SPEC_CAT2(a, b) a##b
 #define SPEC_CAT(a, b) SPEC_CAT2(a, b)
 
+int check_regression_loss(int kind, float delta, const char* who);      // (mshgnn.hip: the setters of both plan types and mshgnn_regression_loss)
 // k_finalize launch of a step (mshgnn.hip): fixed-order slab sums -> flat gradient (+ fused loss)
 int run_finalize(const mshgnn_plan* p, const StepCall& c, const mshgnn_ws_layout& lay, int gw_parts);
 // split-bf16 parity plan (mshgnn_x3.hip)

@@ -757,6 +757,7 @@ struct GDecArgs {
     const void* xl; void* dxl; void* dhl; const uint8_t* maskb; int dh_only; const float* params; const float* out_mask; float* out; const float* gout; float* slabs;
     int64_t off_w, off_b; int B, Hd, node0, n_out, dout;
     const float* y; const int32_t* labels; float inv_n;
+    int reg_kind; float reg_delta;      // with y: MSHGNN_REG_LOSS_* (0 = MSE) and Huber's delta (reg_loss_terms, mshgnn_device.hpp)
 };
 template <bool SPLIT> __device__ __forceinline__ void g_load8(const T16* p, int Hd, float (&v)[8]) {
     load8<T16>(p, v);
@@ -836,8 +837,14 @@ template <bool SPLIT> __global__ __launch_bounds__(256) void k_gdec_bwd(GDecArgs
                     if (a.labels) go = ce_g[d & 1];
                     else if (a.y) {   // wrapper MSE (gnnLightning.py:633-639): dL/dout = 2 (out - y) / n
                         const float dlt = a.out[r * a.dout + d] - a.y[r * a.dout + d];
-                        go = 2.0f * dlt * a.inv_n;
-                        if (c == 0 && cg == 0) lsum += dlt * dlt;
+                        if (a.reg_kind == MSHGNN_REG_LOSS_MSE) {
+                            go = 2.0f * dlt * a.inv_n;
+                            if (c == 0 && cg == 0) lsum += dlt * dlt;
+                        } else {      // L1 / Huber: the plan's regression loss
+                            float term;
+                            reg_loss_terms(dlt, a.inv_n, a.reg_kind, a.reg_delta, go, term);
+                            if (c == 0 && cg == 0) lsum += term;
+                        }
                     } else go = a.gout[r * a.dout + d];
                     const float g = go * a.out_mask[f * a.dout + d];
                     if (cg == 0) accb[d] += g;
@@ -1673,7 +1680,7 @@ int gen_backward(const mshgnn_plan* p, const StepCall& c) {
         if (gp.dhm && gp.L >= 1 && !((d.flags & MSHGNN_FLAG_BASE_MLP) && d.out_type == d.mlp_type)) { da.dhl = ws + lay.dh[gp.L - 1]; da.maskb = reinterpret_cast<const uint8_t*>(ws + lay.mask[gp.L - 1]); da.dh_only = (d.flags & MSHGNN_FLAG_RESIDUAL) ? 0 : 1; }
         da.slabs = reinterpret_cast<float*>(ws + lay.dec_slabs); da.off_w = d.off_dec_w; da.off_b = d.off_dec_b;
         da.B = B; da.Hd = gp.Hd; da.node0 = gp.type_base[d.out_type]; da.n_out = n_out; da.dout = d.out_channels;
-        if (y) { da.y = y; da.out = c.out; da.inv_n = 1.0f / (float)((int64_t)B * n_out * d.out_channels); }
+        if (y) { da.y = y; da.out = c.out; da.inv_n = 1.0f / (float)((int64_t)B * n_out * d.out_channels); da.reg_kind = c.reg_kind; da.reg_delta = c.reg_delta; }
         if (labels) { da.labels = labels; da.out = c.out; da.inv_n = 1.0f / (float)((int64_t)B * n_out); }
         ProfScope ps(p, gp.ks_dec_bwd, st);
         hipLaunchKernelGGL(g->k->dec_bwd, dim3(NWG_DEC), dim3(256), GDEC_BWD_LDS, st, da);

@@ -121,7 +121,7 @@ inline void fill_dec_bwd_args(const mshgnn_plan* p, const StepCall& c, const msh
     a.xl = ws + lay.x[hp.L]; a.dxl = ws + lay.dx[hp.L]; a.params = c.params; a.out_mask = p->d_out_mask; a.gout = c.grad_out;
     a.slabs = reinterpret_cast<float*>(ws + lay.dec_slabs); a.off_w = d.off_dec_w; a.off_b = d.off_dec_b;
     a.B = (int)c.batch; a.NN = hp.NN; a.node0 = hp.type_base[d.out_type]; a.n_out = d.type_nodes[d.out_type]; a.dout = d.out_channels; a.slab0 = 0;
-    if (c.loss == LossKind::MSE) { a.y = c.y; a.out = c.out; a.loss = c.loss_out; a.inv_n = 1.0f / (float)(c.total_windows() * a.n_out * a.dout); }
+    if (c.loss == LossKind::MSE) { a.y = c.y; a.out = c.out; a.loss = c.loss_out; a.inv_n = 1.0f / (float)(c.total_windows() * a.n_out * a.dout); a.reg_kind = c.reg_kind; a.reg_delta = c.reg_delta; }
     if (c.loss == LossKind::CE) { a.labels = c.labels; a.out = c.out; a.loss = c.loss_out; a.inv_n = 1.0f / (float)(c.total_windows() * a.n_out); }
 }
 
@@ -144,6 +144,7 @@ inline void fill_stack_tail(const mshgnn_plan* p, StepCall& c, const mshgnn_ws_l
     if (c.y_fused()) {
         a.y = c.y_fused(); a.dec_slabs = reinterpret_cast<float*>(c.ws + lay.dec_slabs);
         a.inv_n = 1.0f / (float)(c.total_windows() * a.n_out * a.dout);
+        a.reg_kind = c.reg_kind; a.reg_delta = c.reg_delta;
     } else if (c.labels_fused()) {      // mshgnn_step_ce: cross entropy over the per-foot logit pairs, mean over B * n_out rows
         a.labels = c.labels_fused(); a.dec_slabs = reinterpret_cast<float*>(c.ws + lay.dec_slabs);
         a.inv_n = 1.0f / (float)(c.total_windows() * a.n_out);
@@ -158,6 +159,10 @@ inline pick::StackQuery stack_query(const mshgnn_plan* p, const StepCall& c, int
     pick::StackQuery q;
     q.plan = plan; q.op = op; q.B = (int)c.batch; q.n_cu = p->n_cu;
     q.use_fused = p->use_fused; q.use_slab = p->use_slab; q.slab_force = p->slab_force; q.use_spec = p->use_spec; q.use_step = p->use_step;
+    // L1 / Huber on the bf16 plan: the interpreting kernels.  The compile-time programs' tails are compiled for MSE and cross entropy alone (decoder_tail_impl, KS), so that the
+    // MSE path of the tuned kernels carries nothing of the other kinds; same tables, same stashes, same bits (tests/test_spec_gpu.py), so a forward over the program and a
+    // backward_mse over the interpreter go together.
+    if (plan == pick::PLAN_BF16 && c.loss == LossKind::MSE && c.reg_kind != MSHGNN_REG_LOSS_MSE) q.use_spec = false;
     q.stash_nt = a.stash_nt; q.gw_phase = c.gw_phase;
     q.n_mlp = hp.n_mlp; q.sl_hb = hp.sl_hb; q.sl_blk = hp.sl_blk; q.fs_blk = hp.fs_blk; q.x3_alias = hp.x3_alias;
     q.node0 = a.node0; q.n_out = a.n_out; q.blk = blk; q.stagger = p->stagger; q.extra_blk = FS_EXTRA_BLK;

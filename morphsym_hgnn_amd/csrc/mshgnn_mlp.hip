@@ -332,6 +332,7 @@ template <bool X3, bool SERIES> __global__ __launch_bounds__(256) void k_mlp_in(
 // ---- stack ----
 struct StackArgs {
     int H, out, L, mode, loss_kind; int64_t B; float inv;
+    int reg_kind; float reg_delta;      // loss_kind 0: the plan's regression loss when the call was made (MSHGNN_REG_LOSS_*; 0 = MSE) and Huber's delta
     const float* params; int64_t off_b[MLP_MAXL + 1];      // bias of layer l = 1 .. L
     const __bf16* wp[MLP_MAXL + 1]; const __bf16* wtp[MLP_MAXL + 1]; __bf16* act[MLP_MAXL + 1]; __bf16* dz[MLP_MAXL + 1];
     float* out_p; const float* y; const int32_t* labels; const float* gout; float* loss_part;
@@ -420,9 +421,13 @@ template <bool X3> __global__ __launch_bounds__(256) void k_mlp_stack(StackArgs 
         if (b < a.B) {
             if (a.mode == MODE_STEP) {
                 const float o0 = obuf[row * MLP_OPAD + f0], o1 = obuf[row * MLP_OPAD + f0 + 1];
-                if (a.loss_kind == 0) {
+                if (a.loss_kind == 0 && a.reg_kind == MSHGNN_REG_LOSS_MSE) {
                     if (f0 < a.out) { const float d = o0 - a.y[(size_t)b * a.out + f0]; g0 = 2.0f * d * a.inv; term = d * d; }
                     if (f0 + 1 < a.out) { const float d = o1 - a.y[(size_t)b * a.out + f0 + 1]; g1 = 2.0f * d * a.inv; term += d * d; }
+                } else if (a.loss_kind == 0) {      // L1 / Huber: the plan's regression loss (reg_loss_terms, mshgnn_device.hpp)
+                    float t1 = 0.f;
+                    if (f0 < a.out) reg_loss_terms(o0 - a.y[(size_t)b * a.out + f0], a.inv, a.reg_kind, a.reg_delta, g0, term);
+                    if (f0 + 1 < a.out) { reg_loss_terms(o1 - a.y[(size_t)b * a.out + f0 + 1], a.inv, a.reg_kind, a.reg_delta, g1, t1); term += t1; }
                 } else if (f0 + 1 < a.out) {
                     const int cls = a.labels[(size_t)b * (a.out / 2) + p] != 0;
                     const float m = fmaxf(o0, o1), e0 = expf(o0 - m), e1 = expf(o1 - m), s = e0 + e1;
@@ -598,7 +603,7 @@ const MlpKernels MLP_X3 = {k_mlp_pack<true>, {k_mlp_in<true, false>, nullptr}, k
 
 }  // namespace
 
-struct mshgnn_mlp_plan { mshgnn_mlp_desc d; mshgnn_mlp_info info; const MlpKernels* k; };
+struct mshgnn_mlp_plan { mshgnn_mlp_desc d; mshgnn_mlp_info info; const MlpKernels* k; int reg_kind = MSHGNN_REG_LOSS_MSE; float reg_delta = 1.0f; };      // reg_*: what mshgnn_mlp_step(loss_kind 0) computes
 
 extern "C" int mshgnn_mlp_compile_host(const mshgnn_mlp_desc* desc, int loss_kind, mshgnn_mlp_info* info) {
     if (!info) return set_err(MSHGNN_EINVAL, "null argument to mshgnn_mlp_compile_host");
@@ -735,6 +740,7 @@ int mlp_run(const mshgnn_mlp_plan* p, const mshgnn_mlp_input* in, int mode, int 
     {
         StackArgs sa; memset(&sa, 0, sizeof(sa));
         sa.H = H; sa.out = d.out_channels; sa.L = L; sa.mode = mode; sa.loss_kind = loss_kind; sa.B = batch;
+        if (mode == MODE_STEP && loss_kind == 0) { sa.reg_kind = p->reg_kind; sa.reg_delta = p->reg_delta; }      // (read now, by value: a captured graph keeps it)
         sa.inv = 1.0f / (float)n_terms;
         sa.params = params;
         for (int l = 1; l <= L; ++l) {
@@ -789,6 +795,18 @@ extern "C" int mshgnn_mlp_backward(const mshgnn_mlp_plan* plan, const mshgnn_mlp
     if (!plan || !input || !params || !gout || !grad_params || !workspace) return set_err(MSHGNN_EINVAL, "null argument to mshgnn_mlp_backward");
     return mlp_run(plan, input, MODE_BWD, -1, nullptr, gout, params, nullptr, nullptr, grad_params, workspace, batch, stream, "mshgnn_mlp_backward");
 }
+extern "C" int mshgnn_mlp_set_regression_loss(mshgnn_mlp_plan* plan, int kind, float delta) {
+    if (!plan) return set_err(MSHGNN_EINVAL, "null argument to mshgnn_mlp_set_regression_loss");
+    if (const int rc = check_regression_loss(kind, delta, "mshgnn_mlp_set_regression_loss")) return rc;
+    plan->reg_kind = kind; plan->reg_delta = kind == MSHGNN_REG_LOSS_HUBER ? delta : 1.0f;
+    return MSHGNN_OK;
+}
+extern "C" int mshgnn_mlp_get_regression_loss(const mshgnn_mlp_plan* plan, int32_t* kind_out, float* delta_out) {
+    if (!plan || !kind_out || !delta_out) return set_err(MSHGNN_EINVAL, "null argument to mshgnn_mlp_get_regression_loss");
+    *kind_out = plan->reg_kind; *delta_out = plan->reg_delta;
+    return MSHGNN_OK;
+}
+
 extern "C" int mshgnn_mlp_step(const mshgnn_mlp_plan* plan, const mshgnn_mlp_input* input, int loss_kind, const void* targets, const float* params, float* out,
                                float* loss_out, float* grad_params, void* workspace, int64_t batch, void* stream) {
     if (!plan || !input || !params || !out || !loss_out || !grad_params || !workspace) return set_err(MSHGNN_EINVAL, "null argument to mshgnn_mlp_step");

@@ -381,6 +381,77 @@ __global__ __launch_bounds__(NORM_THREADS) void k_grad_norm(const float* g, int6
 }
 static_assert(NORM_BLOCKS <= NORM_THREADS, "the last workgroup loads one partial per thread");
 
+// ------------------------------------------------------------------------------------------------------
+// mshgnn_regression_loss: MSE / L1 / Huber with their gradient for the two-call routes, ONE launch with the ticket pattern above (no memset, no floating-point atomic:
+// two runs give the same bits).  Kind 0 evaluates k_mse's expressions, kinds 1 and 2 reg_loss_terms (mshgnn_device.hpp) -- the function the fused tails call.
+// A lane adds the terms of its grid-stride quads in ascending order (fp32), a wave reduces in the fixed butterfly, thread 0 adds the four waves in order; the workgroup that
+// finishes last adds the workgroups' partials in index order and multiplies by inv_n once.  VEC: all three pointers are 16-byte aligned (16-byte loads and stores; the same bits).
+// ------------------------------------------------------------------------------------------------------
+constexpr int REGL_THREADS = 256, REGL_BLOCKS = 256;
+struct RegLossScratch {
+    unsigned int ticket, pad[3];
+    float part[REGL_BLOCKS];
+};
+static int regl_blocks(int64_t n) { return (int)std::min<int64_t>(((n + 3) / 4 + REGL_THREADS - 1) / REGL_THREADS, REGL_BLOCKS); }
+__device__ __forceinline__ void regl_elem(float o, float y, float inv, int kind, float delta, float& g, float& s) {
+    const float dlt = o - y;
+    if (kind == MSHGNN_REG_LOSS_MSE) { s += dlt * dlt; g = 2.0f * dlt * inv; }
+    else { float term; reg_loss_terms(dlt, inv, kind, delta, g, term); s += term; }
+}
+template <bool VEC> __global__ __launch_bounds__(REGL_THREADS) void k_reg_loss(const float* out, const float* y, int64_t n, int kind, float delta, float* loss, float* gout,
+                                                                               RegLossScratch* sc) {
+    __shared__ float r[REGL_THREADS / 64], pf[REGL_BLOCKS];
+    __shared__ int s_last;
+    const float inv = 1.0f / (float)n;
+    float s = 0.f;
+    for (int64_t i = ((int64_t)blockIdx.x * REGL_THREADS + threadIdx.x) * 4; i < n; i += (int64_t)gridDim.x * REGL_THREADS * 4) {
+        if (VEC && i + 4 <= n) {
+            const f32x4 o = *reinterpret_cast<const f32x4*>(out + i), t = *reinterpret_cast<const f32x4*>(y + i);
+            f32x4 g;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { float ge; regl_elem(o[e], t[e], inv, kind, delta, ge, s); g[e] = ge; }
+            if (gout) *reinterpret_cast<f32x4*>(gout + i) = g;
+        } else {
+            for (int64_t k = i; k < min(i + 4, n); ++k) { float ge; regl_elem(out[k], y[k], inv, kind, delta, ge, s); if (gout) gout[k] = ge; }
+        }
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
+    if ((threadIdx.x & 63) == 0) r[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float t = 0.f;
+        for (int k = 0; k < REGL_THREADS / 64; ++k) t += r[k];
+        __hip_atomic_store(reinterpret_cast<unsigned int*>(&sc->part[blockIdx.x]), __float_as_uint(t), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        s_last = met_last_ticket(&sc->ticket) ? 1 : 0;
+    }
+    __syncthreads();
+    if (!s_last) return;
+    __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    if (threadIdx.x < gridDim.x)      // (gridDim.x <= REGL_BLOCKS == REGL_THREADS: one partial per thread)
+        pf[threadIdx.x] = __uint_as_float(__hip_atomic_load(reinterpret_cast<const unsigned int*>(&sc->part[threadIdx.x]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    __syncthreads();
+    if (threadIdx.x == 0) {      // index order
+        float t = 0.f;
+        for (unsigned b = 0; b < gridDim.x; ++b) t += pf[b];
+        __hip_atomic_store(&sc->ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        *loss = t * inv;
+    }
+}
+static_assert(REGL_BLOCKS <= REGL_THREADS, "the last workgroup loads one partial per thread");
+
+extern "C" size_t mshgnn_regression_loss_scratch_bytes(int64_t n) { return n < 1 ? 0 : sizeof(RegLossScratch); }
+extern "C" int mshgnn_regression_loss(const float* out, const float* y, int64_t n, int kind, float delta, float* loss_out, float* grad_out, void* scratch, void* stream) {
+    if (!out || !y || !loss_out || !scratch || n < 1) return set_err(MSHGNN_EINVAL, "bad argument to mshgnn_regression_loss");
+    if (const int rc = check_regression_loss(kind, delta, "mshgnn_regression_loss")) return rc;
+    if ((uintptr_t)scratch & 15) return set_err(MSHGNN_EINVAL, "mshgnn_regression_loss: the scratch must be 16-byte aligned");
+    const bool vec = (((uintptr_t)out | (uintptr_t)y | (uintptr_t)grad_out) & 15) == 0;
+    hipLaunchKernelGGL(vec ? k_reg_loss<true> : k_reg_loss<false>, dim3(regl_blocks(n)), dim3(REGL_THREADS), 0, (hipStream_t)stream, out, y, n, kind, delta, loss_out,
+                       grad_out, reinterpret_cast<RegLossScratch*>(scratch));
+    HIPCHK(hipGetLastError());
+    return MSHGNN_OK;
+}
+
 // g *= c, c = fl32(min(1, max_norm / (norm + 1e-6))) formed in fp64 by one thread of the workgroup (a NaN norm gives a NaN coefficient, as torch's clamp does)
 __global__ void k_grad_clip(float* g, int64_t n, const double* norm, float max_norm) {
     __shared__ float s_c;

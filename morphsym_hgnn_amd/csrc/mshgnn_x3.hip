@@ -139,8 +139,14 @@ __global__ __launch_bounds__(256) void k_dec_bwd_x3(DecArgs a) {
                 if (a.labels) go = ce_g[d & 1];
                 else if (a.y) {   // wrapper MSE fused (gnnLightning.py:633-639): dL/dout = 2 (out - y) / n
                     const float dlt = a.out[r * a.dout + d] - a.y[r * a.dout + d];
-                    go = 2.0f * dlt * a.inv_n;
-                    if (c == 0) lsum += dlt * dlt;
+                    if (a.reg_kind == MSHGNN_REG_LOSS_MSE) {
+                        go = 2.0f * dlt * a.inv_n;
+                        if (c == 0) lsum += dlt * dlt;
+                    } else {      // L1 / Huber: the plan's regression loss
+                        float term;
+                        reg_loss_terms(dlt, a.inv_n, a.reg_kind, a.reg_delta, go, term);
+                        if (c == 0) lsum += term;
+                    }
                 } else go = a.gout[r * a.dout + d];
                 const float g = go * a.out_mask[f * a.dout + d];
                 accb[d] += g;

@@ -114,7 +114,10 @@ EXPORTS = [
     "mshgnn_mlp_forward", "mshgnn_mlp_backward", "mshgnn_mlp_step",
     "mshgnn_orbit_average", "mshgnn_orbit_average_backward", "mshgnn_orbit_defect",
     "mshgnn_op_gemm_f64", "mshgnn_op_gemm_f64_workspace", "mshgnn_op_aggregate_f64", "mshgnn_op_colsum_f64", "mshgnn_op_colsum_f64_workspace",
+    "mshgnn_plan_set_regression_loss", "mshgnn_plan_get_regression_loss", "mshgnn_mlp_set_regression_loss", "mshgnn_mlp_get_regression_loss",
+    "mshgnn_regression_loss_scratch_bytes", "mshgnn_regression_loss",
 ]
+REG_LOSS_KINDS = {"mse": 0, "l1": 1, "huber": 2}      # include/mshgnn.h MSHGNN_REG_LOSS_*
 ABI_VERSION = 6      # include/mshgnn.h MSHGNN_ABI_VERSION: the ctypes structures above mirror THAT header
 
 _lib = None
@@ -258,6 +261,13 @@ def load_library():
     lib.mshgnn_mlp_backward.argtypes = [C.c_void_p, C.POINTER(MshgnnMlpInput), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     lib.mshgnn_mlp_step.argtypes = [C.c_void_p, C.POINTER(MshgnnMlpInput), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_int64, C.c_void_p]
+    if hasattr(lib, "mshgnn_regression_loss"):      # (absent from older builds of the library handed over through MSHGNN_LIB for A/B runs)
+        for pre in ("mshgnn_plan", "mshgnn_mlp"):
+            getattr(lib, pre + "_set_regression_loss").argtypes = [C.c_void_p, C.c_int, C.c_float]
+            getattr(lib, pre + "_get_regression_loss").argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_float)]
+        lib.mshgnn_regression_loss_scratch_bytes.restype = C.c_size_t
+        lib.mshgnn_regression_loss_scratch_bytes.argtypes = [C.c_int64]
+        lib.mshgnn_regression_loss.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     # symmetrisation over a group orbit (csrc/mshgnn_orbit.hip): host tables, plain arguments
     if hasattr(lib, "mshgnn_orbit_average"):      # (absent from older builds of the library handed over through MSHGNN_LIB for A/B runs)
         orbit9 = [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
@@ -431,7 +441,61 @@ class WideInputs(list):
         self.gen = None      # generation of the engine's row buffers this object's rows were written as (set when the encoder materialises them)
 
 
-class Engine:
+def reg_loss_code(kind: str, delta: float = 1.0) -> Tuple[int, float]:
+    """("mse" | "l1" | "huber", delta) -> the C-ABI's (kind, delta), checked as the library checks them."""
+    if kind not in REG_LOSS_KINDS:
+        raise ValueError("the regression loss is 'mse', 'l1' or 'huber'")
+    delta = float(delta)
+    if kind == "huber" and not (delta > 0.0 and delta != float("inf")):
+        raise ValueError("Huber's delta must be finite and > 0")
+    return REG_LOSS_KINDS[kind], delta if kind == "huber" else 1.0
+
+
+def regression_loss(lib, device, out: torch.Tensor, y: torch.Tensor, kind: str = "mse", delta: float = 1.0, want_grad: bool = True, scratch: Optional[torch.Tensor] = None):
+    """(loss[1], dL / d out or None) of mshgnn_regression_loss: mean MSE / L1 / Huber(delta) over all elements, one launch, bit-reproducible.  `scratch`: the zeroed
+    buffer of an earlier call on the same stream (default: a fresh one)."""
+    code, delta = reg_loss_code(kind, delta)
+    n = out.numel()
+    if y.numel() != n or y.dtype != torch.float32 or out.dtype != torch.float32 or not out.is_contiguous() or not y.is_contiguous():
+        raise ValueError("out and y must be contiguous fp32 tensors with the same number of elements")
+    if scratch is None:
+        scratch = torch.zeros((lib.mshgnn_regression_loss_scratch_bytes(n) + 15) // 16 * 2, dtype=torch.int64, device=device)
+    loss = torch.empty(1, dtype=torch.float32, device=device)
+    g = torch.empty_like(out) if want_grad else None
+    stream = torch.cuda.current_stream(device).cuda_stream
+    with torch.cuda.device(device):
+        _check(lib, lib.mshgnn_regression_loss(out.data_ptr(), y.data_ptr(), n, code, delta, loss.data_ptr(), g.data_ptr() if g is not None else None,
+                                               scratch.data_ptr(), stream), "mshgnn_regression_loss")
+    return loss, g
+
+
+class _RegressionLoss:
+    """What the `mse` entry points of a plan compute (mshgnn_plan_set_regression_loss / mshgnn_mlp_set_regression_loss): shared by Engine and MLPEngine."""
+    _REG_PREFIX = "mshgnn_plan"
+
+    def set_regression_loss(self, kind: str, delta: float = 1.0):
+        """"mse" (the default of a fresh plan), "l1" or "huber" with `delta`: torch.nn.MSELoss / L1Loss / HuberLoss(delta).  Every later `*_mse*` call of this engine
+        computes it; the setting is read when a call is made, so a captured graph keeps the kind it was captured with."""
+        code, delta = reg_loss_code(kind, delta)
+        name = self._REG_PREFIX + "_set_regression_loss"
+        _check(self.lib, getattr(self.lib, name)(self._plan, code, delta), name)
+
+    @property
+    def regression_loss(self) -> Tuple[str, float]:
+        kind, delta = C.c_int32(), C.c_float()
+        name = self._REG_PREFIX + "_get_regression_loss"
+        _check(self.lib, getattr(self.lib, name)(self._plan, C.byref(kind), C.byref(delta)), name)
+        return {v: k for k, v in REG_LOSS_KINDS.items()}[kind.value], float(delta.value)
+
+    def reg_loss(self, out: torch.Tensor, y: torch.Tensor, want_grad: bool = True):
+        """The plan's regression loss stand-alone, for the two-call routes (mshgnn_regression_loss): (loss[1], dL / d out or None)."""
+        kind, delta = self.regression_loss
+        if getattr(self, "_reg_scratch", None) is None:      # zeroed once; every call leaves it ready for the next one on the same stream
+            self._reg_scratch = torch.zeros(self.lib.mshgnn_regression_loss_scratch_bytes(1) // 8 + 1, dtype=torch.int64, device=self.device)
+        return regression_loss(self.lib, self.device, out, y, kind, delta, want_grad, self._reg_scratch)
+
+
+class Engine(_RegressionLoss):
     """One compiled plan (topology x model dims x precision) on one GPU."""
 
     def __init__(self, spec: ModelSpec, dtype: str = "f32", device: Optional[torch.device] = None):
@@ -1140,6 +1204,16 @@ class PaddedEngine:
     def mse_loss(self, out, y, want_grad=True):
         return self.inner.mse_loss(out, y, want_grad)
 
+    def set_regression_loss(self, kind: str, delta: float = 1.0):
+        self.inner.set_regression_loss(kind, delta)
+
+    @property
+    def regression_loss(self):
+        return self.inner.regression_loss
+
+    def reg_loss(self, out, y, want_grad=True):
+        return self.inner.reg_loss(out, y, want_grad)
+
     def adam_step(self, params_flat, grad_flat, exp_avg, exp_avg_sq, step, lr, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0):
         """Adam is elementwise: it runs on the caller's TRUE-size flat buffers as they are (the inner engine's own check would demand the padded size)."""
         n = self.spec.flat_size()
@@ -1209,13 +1283,15 @@ def mlp_compile_host(in_channels: int, hidden: int, out_channels: int, num_layer
     return info
 
 
-class MLPEngine:
+class MLPEngine(_RegressionLoss):
     """The reference's MLP baseline (gnnLightning.py:391-405) on one GPU: a ctypes mirror of the mshgnn_mlp_* entry points.  Parameters and gradients are one
     flat fp32 buffer in torch's state_dict order of the nn.Sequential (`offsets()`).  dtype "bf16": the bf16 arithmetic; "x3": the split-bf16 parity plan (every
     operand a hi / lo pair of bf16, 1e-4 of fp64).  Dense rows: bf16 [B, pitch] ("x3": fp32) from `cast_input`; the series methods take a
     `windows.SequenceStore` / `ResidentDataset` of an `mlp_recipe` and device `starts`, and gather the rows inside the kernels -- where the library's series
     form refuses (standardised recipes, `transformed` / `orbit` stores, fp32 stores, and every store on an "x3" engine, which has no series form) they assemble
     the windows and run the dense form: same bits."""
+
+    _REG_PREFIX = "mshgnn_mlp"
 
     def __init__(self, in_channels: int, hidden: int, out_channels: int, num_layers: int, dtype: str = "bf16", device: Optional[torch.device] = None):
         if dtype not in ("bf16", "x3"):

@@ -58,6 +58,23 @@ class _StepLoss(torch.autograd.Function):
         return g.to(device=in_dev, dtype=dtype).view(shape), None, None
 
 
+class _RegStepLoss(torch.autograd.Function):
+    """The L1 / Huber training loss of a regression step as an autograd node over `mshgnn_regression_loss` (one launch, bit-reproducible).  forward: the loss
+    (fp32, 0-dim), keeping dL/dy_pred; backward: that gradient times the upstream scalar."""
+
+    @staticmethod
+    def forward(ctx, y_pred, y, metrics):
+        loss, g = metrics._reg_launch(y, y_pred, True)
+        ctx.g, ctx.meta = g, (y_pred.shape, y_pred.dtype, y_pred.device)
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, gl):
+        shape, dtype, in_dev = ctx.meta
+        g = ctx.g * gl.to(ctx.g.device)
+        return g.to(device=in_dev, dtype=dtype).view(shape), None, None
+
+
 _REG_NAMES = ("mse_loss", "rmse_loss", "l1_loss")
 _CLS_NAMES = ("ce_loss", "acc", "f1_leg0", "f1_leg1", "f1_leg2", "f1_leg3")
 
@@ -79,6 +96,41 @@ class StepMetrics:
         self._loss = None         # the last step's loss when it carries autograd
         self._vals = {}
         self._from_step = False
+        self.reg_loss = ("mse", 1.0)      # set_regression_loss: what `loss` (the value a training_step returns) is; the metric values never depend on it
+        self._train = None                # the last step's L1 / Huber training loss
+        self._train_args = None           # ... or what it is computed from when somebody reads `loss` (a step without autograd: validation, or a fused step about to publish its own)
+        self._reg_scratch = None
+
+    def set_regression_loss(self, kind: str, delta: float = 1.0) -> None:
+        """The training loss of a regression wrapper: "mse" (the default: `loss` is `mse_loss`, everything as before), "l1" or "huber" with `delta`."""
+        if not self.regression:
+            raise ValueError("set_regression_loss: classification metrics (cross entropy)")
+        eng.reg_loss_code(kind, delta)
+        self.reg_loss, self._train, self._train_args = (kind, float(delta) if kind == "huber" else 1.0), None, None
+
+    @property
+    def _robust(self) -> bool:
+        return self.regression and self.reg_loss[0] != "mse"
+
+    @property
+    def loss(self):
+        """The training loss of the last step: `mse_loss` / `ce_loss`, or with set_regression_loss("l1" / "huber") that loss (after an epoch reduction there
+        is none: `mse_loss`, the epoch's value, as with "mse")."""
+        if not self.regression:
+            return self.ce_loss
+        if self._robust and self._train is None and self._train_args is not None:      # first read after a step without autograd: one launch, now
+            self._train, self._train_args = self._reg_launch(*self._train_args, False)[0].view(()), None
+        return self._train if self._robust and self._train is not None else self.mse_loss
+
+    def _reg_launch(self, y: torch.Tensor, y_pred: torch.Tensor, want_grad: bool):
+        dev = self.device
+        yp = y_pred.detach().to(dev, torch.float32).flatten().contiguous()
+        yy = y.detach().to(dev, torch.float32).flatten().contiguous()
+        if yp.numel() != yy.numel():
+            raise ValueError("y and y_pred must have the same number of elements")
+        if self._reg_scratch is None:
+            self._reg_scratch = torch.zeros(self.lib.mshgnn_regression_loss_scratch_bytes(1) // 8 + 1, dtype=torch.int64, device=dev)
+        return eng.regression_loss(self.lib, dev, yp, yy, self.reg_loss[0], self.reg_loss[1], want_grad, self._reg_scratch)
 
     @property
     def _epoch_f(self):
@@ -160,20 +212,29 @@ class StepMetrics:
     def calculate_losses_step(self, y: torch.Tensor, y_pred: torch.Tensor):
         """Metrics of this batch (published as attributes) and accumulation into the epoch state.  When `y_pred` carries autograd, so does
         the published `mse_loss` / `ce_loss` -- what the reference's `training_step` returns for backward (gnnLightning.py:709-722)."""
-        if torch.is_grad_enabled() and y_pred.requires_grad:
+        grad = torch.is_grad_enabled() and y_pred.requires_grad
+        if grad and not self._robust:
             self._loss = _StepLoss.apply(y_pred, y, self)
         else:
             self._loss = None
             self._cur, _ = self._launch(y, y_pred, False)
+        if self._robust:      # the metric values above are the metric kernel's at every kind; the training loss is a launch of its own -- with autograd now,
+            # without (validation; a fused step, which publishes the engine's loss through set_step_loss) only if `loss` is read
+            self._train, self._train_args = (_RegStepLoss.apply(y_pred, y, self), None) if grad else (None, (y.detach(), y_pred.detach()))
         self._vals, self._from_step = {}, True
 
     def set_step_loss(self, loss: torch.Tensor) -> None:
-        """Publish `loss` (a differentiable scalar the caller computed for this step, e.g. the fused engine step's) as `mse_loss` / `ce_loss`."""
+        """Publish `loss` (a differentiable scalar the caller computed for this step, e.g. the fused engine step's) as `mse_loss` / `ce_loss`; with
+        set_regression_loss("l1" / "huber") as `loss` instead -- `mse_loss` stays the metric kernel's value."""
+        if self._robust:
+            self._train, self._train_args = loss, None
+            return
         self._loss = loss
         self._vals.pop("mse_loss" if self.regression else "ce_loss", None)
 
     def calculate_losses_epoch(self) -> None:
         self._cur, self._loss, self._vals, self._from_step = self._epoch.clone(), None, {}, False
+        self._train = self._train_args = None
 
     def reset_all_metrics(self) -> None:
         self._epoch.zero_()
@@ -207,7 +268,7 @@ class StepMetrics:
 class ComStepMetrics(StepMetrics):
     """Metric bookkeeping of the centroidal-momentum wrappers (`COM_Base_Lightning`, gnnLightning_com.py:28-232): the regression values of
     `StepMetrics` (`mse_loss` differentiable, `rmse_loss`) plus `mse_loss_lin`, `mse_loss_ang`, `cos_sim_lin`, `cos_sim_ang`, `avg_cos_sim`
-    and `loss` (= `mse_loss`, :121).  `y_mean` / `y_std`: the 6 label statistics of the dataset's `Standarizer` (soloDataset.py:12-46) --
+    and `loss` (`StepMetrics.loss`: `mse_loss`, as gnnLightning_com.py:121 has it, unless set_regression_loss chose L1 / Huber).  `y_mean` / `y_std`: the 6 label statistics of the dataset's `Standarizer` (soloDataset.py:12-46) --
     the cosine similarities are taken on base node 0 after un-standardising.  Two launches per step."""
 
     def __init__(self, num_bases: int, y_mean, y_std, device=None):
@@ -253,7 +314,7 @@ class ComStepMetrics(StepMetrics):
     cos_sim_lin = property(lambda self: self._com(4, 6))
     cos_sim_ang = property(lambda self: self._com(5, 6))
     avg_cos_sim = property(lambda self: None if self._com_cur is None else (self.cos_sim_lin + self.cos_sim_ang) / 2)
-    loss = property(lambda self: self.mse_loss)
+    # (`loss` is inherited: StepMetrics.loss)
 
 
 # ---- per-segment sums: one row per (group element, sequence) out of one evaluation sweep ----------------------------------------------------------

@@ -255,6 +255,7 @@ class _MSHGNNBase(nn.Module):
         self._checked_batches = set()
         self._precision = os.environ.get("MSHGNN_DTYPE", "x3")      # ("f64": the constructors finish with _adopt_env_precision, once the parameters exist)
         self._group = None
+        self._reg_loss = ("mse", 1.0)    # set_regression_loss: what the regression routes train on (kept here for the "f64" precision and for engines compiled later)
 
     # ---- copy / pickle: compiled plans (ctypes handles) and device scratch never travel; they are rebuilt lazily ----
     def __getstate__(self):
@@ -377,6 +378,23 @@ class _MSHGNNBase(nn.Module):
             self.float()
         return self
 
+    def set_regression_loss(self, kind: str, delta: float = 1.0):
+        """What a regression model trains on: "mse" (the default, the reference's), "l1" or "huber" with `delta` -- torch.nn.MSELoss / L1Loss / HuberLoss(delta).
+        Every fused route of the model (`fused_training_step`, `fused_training_step_windows`, the engines' `*_mse*` calls) then computes it; at precision "f64"
+        there is no engine and the kind is kept here for the wrappers' fp64 loss.  ValueError on a classification model."""
+        from .engine import reg_loss_code
+        if not self.regression:
+            raise ValueError("set_regression_loss: this is a classification model (cross entropy)")
+        reg_loss_code(kind, delta)
+        self._reg_loss = (kind, float(delta) if kind == "huber" else 1.0)
+        for e in self._engines.values():
+            e.set_regression_loss(*self._reg_loss)
+        return self
+
+    @property
+    def regression_loss(self) -> Tuple[str, float]:
+        return getattr(self, "_reg_loss", ("mse", 1.0))
+
     def _adopt_env_precision(self):
         """MSHGNN_DTYPE=f64 at construction: the parameters exist now, make them fp64 (before any load_state_dict)."""
         if self._precision == "f64":
@@ -435,6 +453,8 @@ class _MSHGNNBase(nn.Module):
         key = (self._precision, str(device))
         if key not in self._engines:
             self._engines[key] = make_engine(self._spec, dtype=self._precision, device=device)
+            if self.regression_loss[0] != "mse":
+                self._engines[key].set_regression_loss(*self.regression_loss)
         return self._engines[key]
 
     # ---- forward --------------------------------------------------------------------------------------
@@ -966,6 +986,8 @@ class MLP(_MSHGNNBase):
         key = (self._precision, str(device))
         if key not in self._engines:
             self._engines[key] = eng.MLPEngine(self.in_channels, self.hidden_channels, self.out_channels, self.num_layers, self._precision, device)
+            if self.regression_loss[0] != "mse":
+                self._engines[key].set_regression_loss(*self.regression_loss)
         return self._engines[key]
 
     def _device_of(self, x):

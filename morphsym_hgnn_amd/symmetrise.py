@@ -227,7 +227,9 @@ def Symmetrised(wrapper, action: OutputAction):
     `MLP_Lightning`) whose `step_helper_function` runs the wrapped model on an ORBIT-COMPLETE batch and returns the labels of its first B windows with the
     orbit-averaged prediction: `training_step` / `validation_step` / `test_step` / `predict_step`, the metric state and the flat optimizers work on it unchanged,
     the backward reaches the engine through the two-call route.  The view shares the model (its parameters) with `wrapper` and keeps metric state and `logged`
-    of its own; `view.raw` is `wrapper`.  `fused_training_step` is off: that step's loss is the raw model's.  `grf_body_to_world_frame` is refused (the
+    of its own; `view.raw` is `wrapper`.  `fused_training_step` is off: that step's loss is the raw model's.  The training loss is the shared model's
+    (`set_regression_loss` on the wrapper, the view or the model: one setting, kept on the model, which every wrapper over it reads per step): L1 / Huber on the
+    AVERAGED prediction, through the stand-alone loss operator.  `grf_body_to_world_frame` is refused (the
     world-frame metrics would pair K . B quaternions with B predictions).
 
     The centroidal-momentum wrappers (`COM_HGNN_SYM_Lightning`, `COM_HGNN_Lightning`, `COM_MLP_Lightning`) are taken with the action of a Solo orbit made from

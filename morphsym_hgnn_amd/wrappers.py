@@ -72,15 +72,44 @@ def _at_f64(wrapper) -> bool:
     return getattr(getattr(wrapper, "model", None), "_precision", None) == "f64"
 
 
-def _f64_step_loss(regression: bool, y: torch.Tensor, y_pred: torch.Tensor) -> torch.Tensor:
-    """The step loss of an "f64" model in fp64 torch operations on [batch, out] (the GEMMs are the hot path, not this): the MSE over every element, or the
+def _f64_step_loss(regression: bool, y: torch.Tensor, y_pred: torch.Tensor, reg_loss=("mse", 1.0)) -> torch.Tensor:
+    """The step loss of an "f64" model in fp64 torch operations on [batch, out] (the GEMMs are the hot path, not this): the MSE over every element -- with
+    `reg_loss` ("l1", _) / ("huber", delta) the mean L1 / Huber loss (set_regression_loss) --, or the
     mean cross entropy of the per-foot [stable, contact] logits against the contact flags (y != 0) -- what the metric kernels compute in fp32.  Carries
     autograd to y_pred; an fp64 tensor with an fp64 gradient."""
     yp = y_pred.to(torch.float64)
     if regression:
-        return torch.mean((yp - y.detach().to(yp.device, torch.float64).reshape(yp.shape)) ** 2)
+        yy = y.detach().to(yp.device, torch.float64).reshape(yp.shape)
+        if reg_loss[0] == "l1":
+            return torch.nn.functional.l1_loss(yp, yy)
+        if reg_loss[0] == "huber":
+            return torch.nn.functional.huber_loss(yp, yy, delta=float(reg_loss[1]))
+        return torch.mean((yp - yy) ** 2)
     logits = yp.reshape(-1, 2)
     return torch.nn.functional.cross_entropy(logits, (y.detach().to(yp.device) != 0).to(torch.long).reshape(-1))
+
+
+def _reg_loss_of(wrapper):
+    """(kind, delta) of the wrapper's training loss: the MODEL's (models.set_regression_loss), the one place it is kept -- so `model.set_regression_loss`, the
+    wrapper's own and a `Symmetrised` view's (same model) all mean the same thing to every wrapper over that model."""
+    return getattr(getattr(wrapper, "model", None), "regression_loss", ("mse", 1.0))
+
+
+def _set_regression_loss(wrapper, kind: str, delta: float = 1.0):
+    """`set_regression_loss` of every regression wrapper: the model's (its fused engines, or the kind kept for "f64"); the step metrics follow per step (`_synced`)."""
+    wrapper.model.set_regression_loss(kind, delta)      # (ValueError on a classification model, a bad kind or delta)
+    return wrapper
+
+
+def _synced(wrapper, metrics):
+    """The wrapper's step metrics told the model's kind (every `_m()`: each step passes here before it publishes anything)."""
+    if metrics.regression and metrics.reg_loss != _reg_loss_of(wrapper) and getattr(wrapper, "regression", True):
+        metrics.set_regression_loss(*_reg_loss_of(wrapper))
+    return metrics
+
+
+def _robust(wrapper) -> bool:
+    return wrapper.regression and _reg_loss_of(wrapper)[0] != "mse"
 
 
 def _losses_step(wrapper, y, y_pred):
@@ -88,11 +117,11 @@ def _losses_step(wrapper, y, y_pred):
     while the LOGGED metric values (rmse, l1, accuracy, F1, the epoch sums) keep coming from the metric kernels on an fp32 copy of the predictions."""
     if _at_f64(wrapper) and torch.is_grad_enabled() and y_pred.requires_grad:
         wrapper._m().calculate_losses_step(y, y_pred.detach())
-        wrapper._m().set_step_loss(_f64_step_loss(wrapper.regression, y, y_pred))
+        wrapper._m().set_step_loss(_f64_step_loss(wrapper.regression, y, y_pred, _reg_loss_of(wrapper)))
     elif _at_f64(wrapper):
         wrapper._m().calculate_losses_step(y, y_pred)
         with torch.no_grad():
-            wrapper._m().set_step_loss(_f64_step_loss(wrapper.regression, y, y_pred))
+            wrapper._m().set_step_loss(_f64_step_loss(wrapper.regression, y, y_pred, _reg_loss_of(wrapper)))
     else:
         wrapper._m().calculate_losses_step(y, y_pred)
 
@@ -128,7 +157,15 @@ class Base_Lightning(_Base):
         key = "_metrics_world" if world else "_metrics"
         if self.__dict__[key] is None:
             self.__dict__[key] = StepMetrics(regression=True if world else self.regression)
-        return self.__dict__[key]
+        return self.__dict__[key] if world else _synced(self, self.__dict__[key])
+
+    def set_regression_loss(self, kind: str, delta: float = 1.0):
+        """Train on "mse" (the default, the reference's), "l1" or "huber" with `delta` (torch.nn.L1Loss / HuberLoss(delta)): `training_step` returns that loss on
+        the fused and on the two-call route and logs it as "train_loss" next to the metric values, which stay what they are (`mse_loss`, `rmse_loss`, `l1_loss`);
+        `validation_step` / `test_step` keep returning `mse_loss`.  ValueError on a classification wrapper."""
+        return _set_regression_loss(self, kind, delta)
+
+    loss = property(lambda self: None if self.__dict__.get("_metrics") is None else self.__dict__["_metrics"].loss)
 
     if _L is None:
         def log(self, name, value, on_step: bool = False, on_epoch: bool = True, **_):
@@ -140,6 +177,8 @@ class Base_Lightning(_Base):
         if self.regression:
             for label, attr in _REG:
                 self.log(f"{step_name}_{label}", getattr(self, attr), on_step=on_step, on_epoch=on_epoch)
+            if _robust(self) and on_step:      # the L1 / Huber training loss of the step (no epoch value: validation and test report the metrics)
+                self.log(f"{step_name}_loss", self.loss, on_step=on_step, on_epoch=on_epoch)
         else:
             self.log(step_name + "_CE_loss", self.ce_loss, on_step=on_step, on_epoch=on_epoch)
             self.log(step_name + "_Accuracy", self.acc, on_step=on_step, on_epoch=on_epoch)
@@ -162,12 +201,15 @@ class Base_Lightning(_Base):
     def _loss(self):
         return self.mse_loss if self.regression else self.ce_loss
 
+    def _train_loss(self):
+        return self.loss if _robust(self) else self._loss()
+
     # ---- steps (gnnLightning.py:179-256) -----------------------------------------------------------------------------
     def training_step(self, batch, batch_idx):
         y, y_pred = self.step_helper_function(batch)
         self.calculate_losses_step(y, y_pred)
         self.log_losses("train", on_step=True)
-        return self._loss()
+        return self._train_loss()
 
     def on_validation_epoch_start(self):
         self.reset_all_metrics()
@@ -396,7 +438,7 @@ class HGNN_C2_Lightning_Reg(_HGNNWrapper):
                 self.calculate_losses_step_original(y, y_pred)
             self._m().set_step_loss(loss)
         (self.log_losses_worldframe if self.body_to_world_frame else self.log_losses)("train", on_step=True)
-        return self._loss()
+        return self._train_loss()
 
     def validation_step(self, batch, batch_idx):
         self._step(batch)
@@ -454,7 +496,11 @@ class COM_Base_Lightning(_Base):
         if self.__dict__["_metrics"] is None:
             from .metrics import ComStepMetrics
             self.__dict__["_metrics"] = ComStepMetrics(self.model.num_bases, *self.__dict__["_stats"])
-        return self.__dict__["_metrics"]
+        return _synced(self, self.__dict__["_metrics"])
+
+    def set_regression_loss(self, kind: str, delta: float = 1.0):
+        """Base_Lightning.set_regression_loss for the centroidal-momentum wrappers: `loss` (what training_step returns and logs) becomes the L1 / Huber loss."""
+        return _set_regression_loss(self, kind, delta)
 
     if _L is None:
         def log(self, name, value, on_step: bool = False, on_epoch: bool = True, **_):
@@ -494,7 +540,7 @@ class COM_Base_Lightning(_Base):
     def validation_step(self, batch, batch_idx):
         y, y_pred = self.step_helper_function(batch)
         self.calculate_losses_step(y, y_pred)
-        return self.loss
+        return self.mse_loss if _robust(self) else self.loss      # (validation and test report the MSE at every training loss, as the reference does)
 
     def on_validation_epoch_end(self):
         self.calculate_losses_epoch()
