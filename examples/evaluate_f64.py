@@ -5,7 +5,7 @@ the default split-bf16 plan ("x3") is from it.
 
 The reference trains and stores its parameters in float64 (torch.set_default_dtype(torch.float64), gnnLightning.py:1183).  `set_precision("f64")` makes
 the model's parameters fp64 BEFORE the state dict is loaded, so every bit of the checkpoint is kept, and runs every Linear / GraphConv on the fp64 MFMA
-operators (csrc/mshgnn_ops_f64.hip).  Without --checkpoint a synthetic fp64 state dict in the reference's layout (the model's own parameter names,
+operators (csrc/mshgnn_ops.hip).  Without --checkpoint a synthetic fp64 state dict in the reference's layout (the model's own parameter names,
 values that are not fp32 numbers) stands in.  Synthetic A1 series stand in for a recorded sequence."""
 import argparse
 import copy

@@ -585,7 +585,7 @@ int mshgnn_op_aggregate(const float* x, int64_t ldx, const int32_t* rowptr, cons
 int64_t mshgnn_op_colsum_workspace(int64_t M, int64_t N);
 int mshgnn_op_colsum(const float* X, int64_t ldx, float* out, int64_t M, int64_t N, void* workspace, void* stream);
 
-/* The same operators over `double` buffers (csrc/mshgnn_ops_f64.hip), for a caller who keeps the reference's precision (torch.set_default_dtype(torch.float64),
+/* The same operators over `double` buffers (csrc/mshgnn_ops.hip), for a caller who keeps the reference's precision (torch.set_default_dtype(torch.float64),
  * gnnLightning.py:1183) on the device: ops.compute_dtype("f64"), model.set_precision("f64").  Contracts, argument meaning (element strides, accumulate, bias,
  * ldc, K == 0, M == 0 / N == 0) and every MSHGNN_EINVAL refusal are those of the fp32 entry points above; no value is narrowed to fp32 on the way.
  * mshgnn_op_gemm_f64: the inner product is v_mfma_f64_16x16x4_f64; the split-K rule is mshgnn_op_gemm_workspace's (the same split count for the same shape),

@@ -38,63 +38,7 @@ extern "C" size_t mshgnn_struct_size(int which) {
     }
 }
 
-// ------------------------------------------------------------------------------------------------------
-// k_prep: pack weights into MFMA B-fragment images (root-sum, transpose, dtype) and sum biases
-// ------------------------------------------------------------------------------------------------------
-
-// Few packs (A1-C2 at L = 3: ~100): one thread per output vector, gathers straight from global memory -- more workgroups than packs, two memory
-// round trips.  Many packs (K4 at L = 8, the generic-width engine): k_prep_tiled (mshgnn_device.hpp), one workgroup per half pack through LDS
-// (measured: A1-C2 L=3 10.7 vs 17.1 us, K4 L=8 18.5 vs 16.2, synthetic 32-limb h=512 97 vs 52).
-// output vector `idx` of this launch's pack range, or (idx past the packs) one bias sum
-template <typename T> __device__ __forceinline__ void prep_one(const PrepArgs& a, int idx, bool with_bias) {
-    constexpr int EPC = Prec<T>::EPC, NBV = Prec<T>::NBV;
-    const int vec_per_pack = H * H / EPC;
-    const int npk = a.pack_n < 0 ? a.n_packs : a.pack_n;
-    const int total = npk * vec_per_pack;
-    if (idx < total) {
-        const int pack = a.pack0 + idx / vec_per_pack, r = idx % vec_per_pack;
-        const int gid = pack * vec_per_pack + r;
-        const int lane = r % 64, v = (r / 64) % NBV, wv = r / (64 * NBV);
-        const PackDesc pd = a.packs[pack];
-        T out[EPC];
-        float g[8][EPC];     // up to 8 source matrices (root-sum), every gather issued before the first add
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-            for (int x = 0; x < EPC; ++x) {
-                int k, col;
-                // MFMA row i = lane & 15 of the wave's 16-row block fb carries output feature 8 (i / 4) + 4 fb + i % 4
-                const int i16 = lane & 15;
-                if constexpr (sizeof(T) == 4) { k = 32 * (lane >> 4) + 4 * (v & 7) + x; col = wv * 32 + 8 * (i16 >> 2) + 4 * (v >> 3) + (i16 & 3); }
-                else { k = 32 * (lane >> 4) + 8 * (v & 3) + x; col = wv * 32 + 8 * (i16 >> 2) + 4 * (v >> 2) + (i16 & 3); }
-                g[i][x] = 0.f;
-                if (i < pd.n_src) {
-                    if (pd.orient == 0) { if (k < pd.ncols) g[i][x] = a.params[pd.src[i] + (int64_t)col * pd.ld + pd.col0 + k]; }
-                    else g[i][x] = a.params[pd.src[i] + (int64_t)k * pd.ld + col];
-                }
-            }
-#pragma unroll
-        for (int x = 0; x < EPC; ++x) {
-            float sum = 0.f;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) sum += g[i][x];     // fixed order: same value every step
-            out[x] = from_f32<T>(sum);
-        }
-        T* dst = reinterpret_cast<T*>(a.wpack) + (size_t)gid * EPC;
-#pragma unroll
-        for (int x = 0; x < EPC; ++x) dst[x] = out[x];
-    } else if (with_bias) {
-        const int b = idx - total;
-        if (b < a.n_biases * H) {
-            const BiasDesc bd = a.biases[b / H];
-            float s = 0.f;
-            for (int i = 0; i < bd.n_src; ++i) s += a.params[bd.src[i] + (b % H)];
-            a.bias[b] = s;
-        }
-    }
-}
-template <typename T> __global__ void k_prep(PrepArgs a) { prep_one<T>(a, blockIdx.x * blockDim.x + threadIdx.x, true); }
-
+// (k_prep / k_prep_tiled, the weight-image packing of every plan: mshgnn_device.hpp)
 // (k_enc_fwd, the encoder of these plans, and splice8: defined in mshgnn_enc.hpp, beside the split plan's k_enc_x3)
 
 // ------------------------------------------------------------------------------------------------------
@@ -851,83 +795,7 @@ template <typename T> __global__ __launch_bounds__(256) void k_dec_fwd(DecArgs a
     }
 }
 
-template <typename T> __global__ __launch_bounds__(256) void k_dec_bwd(DecArgs a) {
-    __shared__ float red[16][DEC_SLAB_FLOATS];
-    const int c = threadIdx.x & 15, rg = threadIdx.x >> 4;
-    const int64_t rows = (int64_t)a.B * a.n_out;
-    const int64_t per = ((rows + gridDim.x - 1) / gridDim.x + 15) / 16 * 16;
-    const int64_t r_begin = (int64_t)blockIdx.x * per, r_end = min(rows, r_begin + per);
-    const T* xl = reinterpret_cast<const T*>(a.xl);
-    T* dxl = reinterpret_cast<T*>(a.dxl);
-    const float* W = a.params + a.off_w;
-    float accw[8][8], accb[8];
-#pragma unroll
-    for (int d = 0; d < 8; ++d) { accb[d] = 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) accw[d][e] = 0.f; }
-    float lsum = 0.f;
-    for (int64_t r = r_begin + rg; r < r_end; r += 16) {
-        const int w = (int)(r / a.n_out), f = (int)(r % a.n_out);
-        const size_t idx = act_idx(w, a.node0 + f, a.B) + c * 8;
-        float x[8], dx[8];
-        load8<T>(xl + idx, x);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) dx[e] = 0.f;
-        float ce_g[2] = {0.f, 0.f};
-        if (a.labels) {   // wrapper cross entropy fused (gnnLightning.py:640-648, mean over the batch * 4 feet): dL/dlogit = (p - onehot) / rows
-            const float l0 = a.out[r * 2], l1 = a.out[r * 2 + 1];
-            const float m = fmaxf(l0, l1), e0 = expf(l0 - m), e1 = expf(l1 - m), se = e0 + e1;
-            const int lab = a.labels[r] != 0;
-            ce_g[0] = (e0 / se - (lab ? 0.f : 1.f)) * a.inv_n; ce_g[1] = (e1 / se - (lab ? 1.f : 0.f)) * a.inv_n;
-            if (c == 0) lsum += (m + logf(se)) - (lab ? l1 : l0);
-        }
-#pragma unroll
-        for (int d = 0; d < 8; ++d) {
-            if (d < a.dout) {
-                float go;
-                if (a.labels) go = ce_g[d & 1];
-                else if (a.y) {   // wrapper MSE fused (gnnLightning.py:633-639): dL/dout = 2 (out - y) / n
-                    const float dlt = a.out[r * a.dout + d] - a.y[r * a.dout + d];
-                    if (a.reg_kind == MSHGNN_REG_LOSS_MSE) {
-                        go = 2.0f * dlt * a.inv_n;
-                        if (c == 0) lsum += dlt * dlt;
-                    } else {      // L1 / Huber: the plan's regression loss
-                        float term;
-                        reg_loss_terms(dlt, a.inv_n, a.reg_kind, a.reg_delta, go, term);
-                        if (c == 0) lsum += term;
-                    }
-                } else go = a.gout[r * a.dout + d];
-                const float g = go * a.out_mask[f * a.dout + d];
-                accb[d] += g;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) { accw[d][e] += g * x[e]; dx[e] += g * W[d * H + c * 8 + e]; }
-            }
-        }
-        store8<T>(dxl + idx, dx);
-    }
-#pragma unroll
-    for (int d = 0; d < 8; ++d) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) red[rg][d * H + c * 8 + e] = accw[d][e];
-        if (c == 0) red[rg][8 * H + d] = accb[d];
-    }
-    __syncthreads();
-    float* slab = a.slabs + (size_t)blockIdx.x * DEC_SLAB_FLOATS;
-    {   // per-block loss partial rides in the slab (summed in fixed order by k_finalize: no atomics, deterministic)
-        __shared__ float lred[4];
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) lsum += __shfl_xor(lsum, m, 64);
-        if ((threadIdx.x & 63) == 0) lred[threadIdx.x >> 6] = lsum;
-        __syncthreads();
-        if (threadIdx.x == 0) slab[8 * H + 8] = (lred[0] + lred[1]) + (lred[2] + lred[3]);
-    }
-    for (int i = threadIdx.x; i < 8 * H + 8; i += 256) {
-        float s2 = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s2 += red[r][i];
-        slab[i] = s2;
-    }
-}
+// (k_dec_bwd<T, false>, the decoder backward of these plans: mshgnn_device.hpp, beside the split plan's instantiation)
 
 // ------------------------------------------------------------------------------------------------------
 // k_gradw: all weight gradients of the step as one split-K MFMA launch.  dW[o][k] = sum_w P[w][o] Q[w][k]
@@ -1638,7 +1506,7 @@ extern "C" int mshgnn_workspace_layout(const mshgnn_plan* p, int64_t batch, int 
 // the weight-image launch of a plan of element type T: the tiled kernel from PREP_TILED_MIN packs up, else one thread per output vector of the launch's packs
 template <typename T> static void launch_prep_t(const PrepArgs& a, bool biases, hipStream_t st) {
     if (prep_use_tiled(a.n_packs)) hipLaunchKernelGGL((k_prep_tiled<T, false>), dim3(prep_tiled_grid(a.n_packs, a.n_biases)), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(k_prep<T>, dim3(prep_grid(a, Prec<T>::EPC, biases)), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((k_prep<T, false>), dim3(prep_grid(a, Prec<T>::EPC, biases)), dim3(256), 0, st, a);
 }
 int launch_prep(const PrepArgs& a, bool split, hipStream_t st) {
     if (split) x3_launch_prep(a, true, st); else launch_prep_t<__bf16>(a, true, st);
@@ -1754,7 +1622,7 @@ static int backward_impl(const mshgnn_plan* p, const StepCall& c) {
         DecArgs a{};
         fill_dec_bwd_args(p, c, lay, a);
         ProfScope ps(p, hp.ks_dec_bwd, st);
-        hipLaunchKernelGGL(k_dec_bwd<T>, dim3(NWG_DEC), dim3(256), 0, st, a);
+        hipLaunchKernelGGL((k_dec_bwd<T, false>), dim3(NWG_DEC), dim3(256), 0, st, a);
     }
     const int tiles = (B + Prec<T>::ROWS - 1) / Prec<T>::ROWS;
     bool fused_done = gw_phase == 1 || c.stack_done;      // (stack_done: k_slab_step already ran the backward sweep of the stack, forward_impl)
@@ -2005,20 +1873,8 @@ extern "C" int mshgnn_step_mse_phase(const mshgnn_plan* p, const void* const* x,
 // the one thing mshgnn_step_*_series needs before its encoder launch: the base pointer of every run's series column (one workgroup).  The windows'
 // labels (and the int32 contact flags of the classification step) are computed by extra workgroups of the encoder launch itself (SeriesSrc.lab):
 // a launch of their own cost 13.6 us of dependent round trips in front of the encoder, there they run under its tail.
-__global__ void k_series_run_ptrs(const int* runs, int n_runs, WindowArgs wa, int elem_bytes, unsigned long long* run_ptr) {
-    const int r = threadIdx.x;
-    if (r >= n_runs) return;
-    bool neg;
-    const int sc = run_source(runs[(size_t)r * 5 + 3], wa.sign, neg);
-    unsigned long long p = 0ull;
-#pragma unroll
-    for (int k = 0; k < WIN_MAX_SRC; ++k)
-        if (sc >= 0 && (sc >> 8) == k) p = (unsigned long long)(reinterpret_cast<const char*>(wa.src[k]) + (size_t)(sc & 0xff) * wa.src_cstride[k] * elem_bytes);
-    run_ptr[r] = p | (neg && p ? RUN_PTR_SIGN : 0ull);      // a negated run: the flag rides in bit 63, masked off by every gather (run_ptr_addr)
-}
-
-// K > 1 group elements (orbit descriptors): all K blocks of `runs`, n_total = K * n_runs <= 8 * 128 pointers, in the same one workgroup
-__global__ void k_series_run_ptrs_orbit(const int* runs, int n_total, WindowArgs wa, int elem_bytes, unsigned long long* run_ptr) {
+// (K > 1 group elements, orbit descriptors: all K blocks of `runs`, n_total = K * n_runs <= 8 * 128 pointers, in the same one workgroup; K == 1: a single pass)
+__global__ void k_series_run_ptrs(const int* runs, int n_total, WindowArgs wa, int elem_bytes, unsigned long long* run_ptr) {
     for (int r = threadIdx.x; r < n_total; r += blockDim.x) {
         bool neg;
         const int sc = run_source(runs[(size_t)r * 5 + 3], wa.sign, neg);
@@ -2026,7 +1882,7 @@ __global__ void k_series_run_ptrs_orbit(const int* runs, int n_total, WindowArgs
 #pragma unroll
         for (int k = 0; k < WIN_MAX_SRC; ++k)
             if (sc >= 0 && (sc >> 8) == k) p = (unsigned long long)(reinterpret_cast<const char*>(wa.src[k]) + (size_t)(sc & 0xff) * wa.src_cstride[k] * elem_bytes);
-        run_ptr[r] = p | (neg && p ? RUN_PTR_SIGN : 0ull);
+        run_ptr[r] = p | (neg && p ? RUN_PTR_SIGN : 0ull);      // a negated run: the flag rides in bit 63, masked off by every gather (run_ptr_addr)
     }
 }
 
@@ -2101,11 +1957,9 @@ static int check_series_sources(const SeriesArgs& s, bool fp32_gather, WindowArg
 // workgroups of the encoder launch (want_y / want_q; a test sequence without labels: none).
 static void fill_series_src(const SeriesArgs& s, const WindowArgs& wa, bool fp32_gather, bool want_q, hipStream_t st, SeriesSrc& ser) {
     const mshgnn_window_desc* d = s.d;
-    static_assert(WIN_MAX_RUNS <= 256, "k_series_run_ptrs resolves the runs in one 256-thread workgroup");
     const int K = desc_elements(d);
     if (!d->run_ptrs_ready) {    // (the caller vouches for the scratch's contents otherwise: same descriptor, same source arrays as the call that filled it)
-        if (K > 1) hipLaunchKernelGGL(k_series_run_ptrs_orbit, dim3(1), dim3(256), 0, st, d->runs, K * d->n_runs, wa, fp32_gather ? 4 : 2, reinterpret_cast<unsigned long long*>(s.run_ptrs));
-        else hipLaunchKernelGGL(k_series_run_ptrs, dim3(1), dim3(256), 0, st, d->runs, d->n_runs, wa, fp32_gather ? 4 : 2, reinterpret_cast<unsigned long long*>(s.run_ptrs));
+        hipLaunchKernelGGL(k_series_run_ptrs, dim3(1), dim3(256), 0, st, d->runs, K * d->n_runs, wa, fp32_gather ? 4 : 2, reinterpret_cast<unsigned long long*>(s.run_ptrs));
     }
     const bool want_y = s.y_out != nullptr;
     if (want_y || want_q) {
@@ -2125,15 +1979,39 @@ static void fill_series_src(const SeriesArgs& s, const WindowArgs& wa, bool fp32
 // the plans the series routes run on: the bf16 plan with the fused stack kernels and the split plan
 static bool series_plan_ok(const mshgnn_plan* p) { return !p->gen && (p->hp.d.dtype == MSHGNN_BF16X3 || (p->hp.d.dtype == MSHGNN_BF16 && p->use_fused)); }
 
-// the statistics pre-pass of the standardised routes (defined with mshgnn_forward_series below)
-__global__ __launch_bounds__(256) void k_series_stats(const int* runs, int n_runs, const unsigned long long* run_ptr, const int64_t* starts, int64_t B, double* stats);
-__global__ __launch_bounds__(256) void k_series_stats_orbit(const int* runs, int n_runs, int K, const unsigned long long* run_ptr, const int64_t* starts, int64_t B, double* stats);
+// the statistics pre-pass of the standardised routes: {mean, sd} of every (window, run), one wave each.  ORBIT (K > 1 group elements): the statistics of window b's
+// run r are those of ITS element's run -- run pointer (and sign) from block `element` of the table; the layout of `stats` stays [B][n_runs][2] (a window has exactly
+// one element) and the lengths are element 0's, which are every element's.
+template <bool ORBIT>
+__global__ __launch_bounds__(256) void k_series_stats(const int* runs, int n_runs, int K, const unsigned long long* run_ptr, const int64_t* starts, int64_t B, double* stats) {
+    const int lane = threadIdx.x & 63;
+    const int64_t idx = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);      // (window, run): one wave each
+    if (idx >= B * n_runs) return;
+    const int64_t b = idx / n_runs; const int r = (int)(idx - b * n_runs);
+    const int len = runs[(size_t)r * 5 + 4];
+    int64_t sw = 0;
+    if constexpr (ORBIT) sw = starts[b];
+    const unsigned long long p = run_ptr[ORBIT ? (size_t)start_element(sw, K) * n_runs + r : (size_t)r];
+    RunStats rs{0.0, 1.0};      // constant-one runs are left alone (never applied)
+    if (p) {
+        const float* sp = reinterpret_cast<const float*>(run_ptr_addr(p)) + (ORBIT ? start_row(sw) : starts[b]);
+        const bool neg = (p & RUN_PTR_SIGN) != 0;      // the statistics of the NEGATED run, as mshgnn_assemble_windows computes them
+        float v[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int k = 2 * lane + 128 * (q >> 1) + (q & 1);
+            v[q] = 1.0f;
+            if (k < len) v[q] = xor_sign(sp[k], neg);
+        }
+        rs = run_stats(v, len, lane);
+    }
+    if (lane == 0) *reinterpret_cast<f64x2*>(stats + (size_t)idx * 2) = f64x2{rs.mean, rs.sd};
+}
 static void launch_series_stats(const mshgnn_window_desc* d, const SeriesSrc& ser, const int64_t* starts, int64_t batch, void* stats, hipStream_t st) {
     const int64_t waves = batch * d->n_runs;
     const dim3 grid((unsigned)((waves + 3) / 4));
     const int K = desc_elements(d);
-    if (K > 1) hipLaunchKernelGGL(k_series_stats_orbit, grid, dim3(256), 0, st, d->runs, d->n_runs, K, ser.run_ptr, starts, batch, reinterpret_cast<double*>(stats));
-    else hipLaunchKernelGGL(k_series_stats, grid, dim3(256), 0, st, d->runs, d->n_runs, ser.run_ptr, starts, batch, reinterpret_cast<double*>(stats));
+    hipLaunchKernelGGL(K > 1 ? k_series_stats<true> : k_series_stats<false>, grid, dim3(256), 0, st, d->runs, d->n_runs, K, ser.run_ptr, starts, batch, reinterpret_cast<double*>(stats));
 }
 
 // std_route (mshgnn_step_*_series_std): a standardised recipe -- k_series_stats leaves {mean, sd} of every (window, run) in `stats`, the NORM encoders apply them to the
@@ -2228,55 +2106,6 @@ extern "C" int mshgnn_step_ce_series_std(const mshgnn_plan* p, const mshgnn_wind
 // (window, run) in the caller's scratch (k_series_stats: one wave per run, the per-lane partial sums and the wave_sum order of k_assemble_windows -- the same
 // function, run_stats), the NORM encoders apply them to the fp32 series (standardise_one).
 // ------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_series_stats(const int* runs, int n_runs, const unsigned long long* run_ptr, const int64_t* starts, int64_t B, double* stats) {
-    const int lane = threadIdx.x & 63;
-    const int64_t idx = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);      // (window, run): one wave each
-    if (idx >= B * n_runs) return;
-    const int64_t b = idx / n_runs; const int r = (int)(idx - b * n_runs);
-    const int len = runs[(size_t)r * 5 + 4];
-    const unsigned long long p = run_ptr[r];
-    RunStats rs{0.0, 1.0};      // constant-one runs are left alone (never applied)
-    if (p) {
-        const float* sp = reinterpret_cast<const float*>(run_ptr_addr(p)) + starts[b];
-        const bool neg = (p & RUN_PTR_SIGN) != 0;      // the statistics of the NEGATED run, as mshgnn_assemble_windows computes them
-        float v[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int k = 2 * lane + 128 * (q >> 1) + (q & 1);
-            v[q] = 1.0f;
-            if (k < len) v[q] = xor_sign(sp[k], neg);
-        }
-        rs = run_stats(v, len, lane);
-    }
-    if (lane == 0) *reinterpret_cast<f64x2*>(stats + (size_t)idx * 2) = f64x2{rs.mean, rs.sd};
-}
-
-// K > 1 group elements: the statistics of window b's run r are those of ITS element's run -- run pointer (and sign) from block `element` of the table; the layout of
-// `stats` stays [B][n_runs][2] (a window has exactly one element) and the lengths are element 0's, which are every element's.
-__global__ __launch_bounds__(256) void k_series_stats_orbit(const int* runs, int n_runs, int K, const unsigned long long* run_ptr, const int64_t* starts, int64_t B, double* stats) {
-    const int lane = threadIdx.x & 63;
-    const int64_t idx = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);      // (window, run): one wave each
-    if (idx >= B * n_runs) return;
-    const int64_t b = idx / n_runs; const int r = (int)(idx - b * n_runs);
-    const int len = runs[(size_t)r * 5 + 4];
-    const int64_t sw = starts[b];
-    const unsigned long long p = run_ptr[(size_t)start_element(sw, K) * n_runs + r];
-    RunStats rs{0.0, 1.0};      // constant-one runs are left alone (never applied)
-    if (p) {
-        const float* sp = reinterpret_cast<const float*>(run_ptr_addr(p)) + start_row(sw);
-        const bool neg = (p & RUN_PTR_SIGN) != 0;      // the statistics of the NEGATED run, as mshgnn_assemble_windows computes them
-        float v[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int k = 2 * lane + 128 * (q >> 1) + (q & 1);
-            v[q] = 1.0f;
-            if (k < len) v[q] = xor_sign(sp[k], neg);
-        }
-        rs = run_stats(v, len, lane);
-    }
-    if (lane == 0) *reinterpret_cast<f64x2*>(stats + (size_t)idx * 2) = f64x2{rs.mean, rs.sd};
-}
-
 extern "C" int64_t mshgnn_forward_series_stats_bytes(const mshgnn_window_desc* d, int64_t batch) {
     if (!d || batch < 1 || d->n_runs < 1 || !d->normalize) return 0;
     return batch * (int64_t)d->n_runs * 2 * (int64_t)sizeof(double);

@@ -858,6 +858,67 @@ inline bool prep_use_tiled(int n_packs) {      // MSHGNN_PREP_TILED=0 / 1 forces
 }
 inline unsigned prep_tiled_grid(int n_packs, int n_biases) { return (unsigned)(2 * n_packs + (n_biases * H + 255) / 256); }
 
+// k_prep, per thread.  Few packs (A1-C2 at L = 3: ~100): one thread per output vector, gathers straight from global memory -- more workgroups than packs, two memory
+// round trips.  Many packs (K4 at L = 8, the generic-width engine): k_prep_tiled above
+// (measured: A1-C2 L=3 10.7 vs 17.1 us, K4 L=8 18.5 vs 16.2, synthetic 32-limb h=512 97 vs 52).
+// Output vector `idx` of this launch's pack range, or (idx past the packs) one bias sum.  T / SPLIT_OUT as in prep_pack_half.  The encoders of the bf16 and the split
+// plan inline it too (EncArgs.prep, mshgnn_enc.hpp).
+template <typename T, bool SPLIT_OUT> __device__ __forceinline__ void prep_one(const PrepArgs& a, int idx, bool with_bias) {
+    constexpr int EPC = Prec<T>::EPC, NBV = Prec<T>::NBV;
+    const int vec_per_pack = H * H / EPC;
+    const int npk = a.pack_n < 0 ? a.n_packs : a.pack_n;
+    const int total = npk * vec_per_pack;
+    if (idx < total) {
+        const int pack = a.pack0 + idx / vec_per_pack, r = idx % vec_per_pack;
+        const int gid = pack * vec_per_pack + r;
+        const int lane = r % 64, v = (r / 64) % NBV, wv = r / (64 * NBV);
+        const PackDesc pd = a.packs[pack];
+        float g[8][EPC];     // up to 8 source matrices (root-sum), every gather issued before the first add
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+#pragma unroll
+            for (int x = 0; x < EPC; ++x) {
+                int k, col;
+                // MFMA row i = lane & 15 of the wave's 16-row block fb carries output feature 8 (i / 4) + 4 fb + i % 4
+                const int i16 = lane & 15;
+                if constexpr (sizeof(T) == 4) { k = 32 * (lane >> 4) + 4 * (v & 7) + x; col = wv * 32 + 8 * (i16 >> 2) + 4 * (v >> 3) + (i16 & 3); }
+                else { k = 32 * (lane >> 4) + 8 * (v & 3) + x; col = wv * 32 + 8 * (i16 >> 2) + 4 * (v >> 2) + (i16 & 3); }
+                g[i][x] = 0.f;
+                if (i < pd.n_src) {
+                    if (pd.orient == 0) { if (k < pd.ncols) g[i][x] = a.params[pd.src[i] + (int64_t)col * pd.ld + pd.col0 + k]; }
+                    else g[i][x] = a.params[pd.src[i] + (int64_t)k * pd.ld + col];
+                }
+            }
+        float sum[EPC];
+#pragma unroll
+        for (int x = 0; x < EPC; ++x) {
+            sum[x] = 0.f;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) sum[x] += g[i][x];     // fixed order: same value every step
+        }
+        if constexpr (SPLIT_OUT) {
+            u32x4 hi, lo;
+            split_oct(f32x4{sum[0], sum[1], sum[2], sum[3]}, f32x4{sum[4], sum[5], sum[6], sum[7]}, hi, lo);
+            u32x4* dst = reinterpret_cast<u32x4*>(a.wpack);
+            dst[gid] = hi;
+            dst[(size_t)a.n_packs * vec_per_pack + gid] = lo;
+        } else {
+            T* dst = reinterpret_cast<T*>(a.wpack) + (size_t)gid * EPC;
+#pragma unroll
+            for (int x = 0; x < EPC; ++x) dst[x] = from_f32<T>(sum[x]);
+        }
+    } else if (with_bias) {
+        const int b = idx - total;
+        if (b < a.n_biases * H) {
+            const BiasDesc bd = a.biases[b / H];
+            float s = 0.f;
+            for (int i = 0; i < bd.n_src; ++i) s += a.params[bd.src[i] + (b % H)];
+            a.bias[b] = s;
+        }
+    }
+}
+template <typename T, bool SPLIT_OUT> __global__ void k_prep(PrepArgs a) { prep_one<T, SPLIT_OUT>(a, blockIdx.x * blockDim.x + threadIdx.x, true); }
+
 struct StackArgs {
     static constexpr bool full = false;           // (StackView: every tile of the launch is complete)
     static constexpr int nt_mode = -1;            // (StackView: the stash store policy is a template parameter; -1: read stash_nt)
@@ -1502,6 +1563,98 @@ struct DecArgs {
     int reg_kind; float reg_delta;              // with y: MSHGNN_REG_LOSS_* (0 = MSE, the expressions above) and Huber's delta (reg_loss_terms)
 };
 
+// k_dec_bwd: decoder backward (+ fused wrapper MSE / L1 / Huber / cross entropy) on the rows of X_L -> dX_L rows, the decoder's partial gradients and the loss partial in
+// this workgroup's slab.  SPLIT (the split plan, T = bf16): X_L is read as hi + lo planes and dX_L written as both.  Used by mshgnn_backward / _mse / _ce where the
+// stack kernel has no fused tail.
+template <typename T, bool SPLIT> __global__ __launch_bounds__(256) void k_dec_bwd(DecArgs a) {
+    __shared__ float red[16][DEC_SLAB_FLOATS];
+    const int c = threadIdx.x & 15, rg = threadIdx.x >> 4;
+    const int64_t rows = (int64_t)a.B * a.n_out;
+    const int64_t per = ((rows + gridDim.x - 1) / gridDim.x + 15) / 16 * 16;
+    const int64_t r_begin = (int64_t)blockIdx.x * per, r_end = min(rows, r_begin + per);
+    const T* xl = reinterpret_cast<const T*>(a.xl);
+    T* dxl = reinterpret_cast<T*>(a.dxl);
+    const float* W = a.params + a.off_w;
+    float accw[8][8], accb[8];
+#pragma unroll
+    for (int d = 0; d < 8; ++d) { accb[d] = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) accw[d][e] = 0.f; }
+    float lsum = 0.f;
+    for (int64_t r = r_begin + rg; r < r_end; r += 16) {
+        const int w = (int)(r / a.n_out), f = (int)(r % a.n_out);
+        const size_t idx = (SPLIT ? x3_idx(w, a.node0 + f, a.B) : act_idx(w, a.node0 + f, a.B)) + c * 8;
+        float x[8], dx[8];
+        load8<T>(xl + idx, x);
+        if constexpr (SPLIT) {
+            float xlo[8];
+            load8<T>(xl + idx + H, xlo);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) x[e] += xlo[e];
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) dx[e] = 0.f;
+        float ce_g[2] = {0.f, 0.f};
+        if (a.labels) {   // wrapper cross entropy fused (gnnLightning.py:640-648, mean over the batch * 4 feet): dL/dlogit = (p - onehot) / rows
+            const float l0 = a.out[r * 2], l1 = a.out[r * 2 + 1];
+            const float m = fmaxf(l0, l1), e0 = expf(l0 - m), e1 = expf(l1 - m), se = e0 + e1;
+            const int lab = a.labels[r] != 0;
+            ce_g[0] = (e0 / se - (lab ? 0.f : 1.f)) * a.inv_n; ce_g[1] = (e1 / se - (lab ? 1.f : 0.f)) * a.inv_n;
+            if (c == 0) lsum += (m + logf(se)) - (lab ? l1 : l0);
+        }
+#pragma unroll
+        for (int d = 0; d < 8; ++d) {
+            if (d < a.dout) {
+                float go;
+                if (a.labels) go = ce_g[d & 1];
+                else if (a.y) {   // wrapper MSE fused (gnnLightning.py:633-639): dL/dout = 2 (out - y) / n
+                    const float dlt = a.out[r * a.dout + d] - a.y[r * a.dout + d];
+                    if (a.reg_kind == MSHGNN_REG_LOSS_MSE) {
+                        go = 2.0f * dlt * a.inv_n;
+                        if (c == 0) lsum += dlt * dlt;
+                    } else {      // L1 / Huber: the plan's regression loss
+                        float term;
+                        reg_loss_terms(dlt, a.inv_n, a.reg_kind, a.reg_delta, go, term);
+                        if (c == 0) lsum += term;
+                    }
+                } else go = a.gout[r * a.dout + d];
+                const float g = go * a.out_mask[f * a.dout + d];
+                accb[d] += g;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) { accw[d][e] += g * x[e]; dx[e] += g * W[d * H + c * 8 + e]; }
+            }
+        }
+        if constexpr (SPLIT) {
+            u32x4 hi, lo;
+            split_oct(f32x4{dx[0], dx[1], dx[2], dx[3]}, f32x4{dx[4], dx[5], dx[6], dx[7]}, hi, lo);
+            *reinterpret_cast<u32x4*>(dxl + idx) = hi;
+            *reinterpret_cast<u32x4*>(dxl + idx + H) = lo;
+        } else store8<T>(dxl + idx, dx);
+    }
+#pragma unroll
+    for (int d = 0; d < 8; ++d) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) red[rg][d * H + c * 8 + e] = accw[d][e];
+        if (c == 0) red[rg][8 * H + d] = accb[d];
+    }
+    __syncthreads();
+    float* slab = a.slabs + (size_t)blockIdx.x * DEC_SLAB_FLOATS;
+    {   // per-block loss partial rides in the slab (summed in fixed order by k_finalize: no atomics, deterministic)
+        __shared__ float lred[4];
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) lsum += __shfl_xor(lsum, m, 64);
+        if ((threadIdx.x & 63) == 0) lred[threadIdx.x >> 6] = lsum;
+        __syncthreads();
+        if (threadIdx.x == 0) slab[8 * H + 8] = (lred[0] + lred[1]) + (lred[2] + lred[3]);
+    }
+    for (int i = threadIdx.x; i < 8 * H + 8; i += 256) {
+        float s2 = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) s2 += red[r][i];
+        slab[i] = s2;
+    }
+}
+
 
 // The finalize ops that read no weight-gradient slab, riding in extra workgroups of a bf16 / split-plan weight-gradient launch (SIDE_INTS records of the plan,
 // mshgnn_plan.hpp; gw_side_workgroup below): workgroups [wg0, wg0 + n_grid) of the grid, the first n of them one record each; the launch's own workgroups start at main0.
@@ -1730,7 +1883,7 @@ int x3_attach_program(mshgnn_plan* p, void* selector);
 int x3_forward(const mshgnn_plan* p, StepCall& c);
 int x3_backward(const mshgnn_plan* p, const StepCall& c);
 void x3_launch_prep(const PrepArgs& a, bool biases, hipStream_t st);      // (biases: the grid of the per-thread kernel covers the bias sums too)
-// weight-image packing for the other engines (mshgnn.hip): k_prep<__bf16> or the hi / lo images of k_prep_x3
+// weight-image packing for the other engines (mshgnn.hip): k_prep<__bf16, false> or the hi / lo images of k_prep<__bf16, true>
 int launch_prep(const PrepArgs& a, bool split, hipStream_t st);
 // generic-width engine (mshgnn_gen.hip)
 int gen_create(mshgnn_plan* p, const mshgnn_desc* desc);

@@ -25,9 +25,6 @@
 // chunk divides between two runs (j, off, n0, whether a run has a source column) is the row structure, which all elements share.  Only the ORBIT instantiations pay for it.
 #pragma once
 #include "mshgnn_device.hpp"
-// the embedded layer-pack prep of each plan (EncArgs.prep): defined beside k_prep in mshgnn.hip / k_prep_x3 in mshgnn_x3.hip
-template <typename T> __device__ __forceinline__ void prep_one(const PrepArgs& a, int idx, bool with_bias);
-__device__ __forceinline__ void prep_one_x3(const PrepArgs& a, int idx, bool with_bias);
 __device__ __forceinline__ u32x4 splice8(u32x4 A, u32x4 B, int n0) {      // bf16 elements A[0 .. n0) ++ B[0 .. 8 - n0), 0 < n0 < 8
     const unsigned __int128 a = ((unsigned __int128)(((unsigned long long)A[3] << 32) | A[2]) << 64) | (((unsigned long long)A[1] << 32) | A[0]);
     const unsigned __int128 b = ((unsigned __int128)(((unsigned long long)B[3] << 32) | B[2]) << 64) | (((unsigned long long)B[1] << 32) | B[0]);
@@ -141,7 +138,7 @@ template <typename T, bool ALIGNED, bool SERIES = false, int SRC = 0, bool NORM 
     EncRole r;
     const EncWg role = enc_role<SERIES, ORBIT>(a, ser, tid, r);
     if (role != ENC_WG_ENCODE) {
-        if constexpr (sizeof(T) == 2 && ALIGNED && !SERIES) if (role == ENC_WG_PREP) prep_one<T>(a.prep, r.prep_wg * 256 + tid, false);      // (bf16 plan; see EncArgs.prep)
+        if constexpr (sizeof(T) == 2 && ALIGNED && !SERIES) if (role == ENC_WG_PREP) prep_one<T, false>(a.prep, r.prep_wg * 256 + tid, false);      // (bf16 plan; see EncArgs.prep)
         return;
     }
     const int t = r.t, node = r.node, F = r.F, nt = r.nt, nkc = r.nkc;
@@ -342,7 +339,7 @@ template <bool ALIGNED, bool SERIES = false, int SRC = 0, bool NORM = false, boo
     EncRole r;
     const EncWg role = enc_role<SERIES, ORBIT>(a, ser, tid, r);
     if (role != ENC_WG_ENCODE) {
-        if constexpr (ALIGNED && !SERIES) if (role == ENC_WG_PREP) prep_one_x3(a.prep, r.prep_wg * 256 + tid, false);
+        if constexpr (ALIGNED && !SERIES) if (role == ENC_WG_PREP) prep_one<__bf16, true>(a.prep, r.prep_wg * 256 + tid, false);
         return;
     }
     const int t = r.t, node = r.node, F = r.F, nt = r.nt, nkc = r.nkc;

@@ -763,9 +763,12 @@ __global__ void k_grf_to_world(const float* quat, const float* body, float* worl
 // has one or two ids per wave: one or two entries per slot, a merge of 2 .. 3 entries per 64 windows.
 // ------------------------------------------------------------------------------------------------------
 constexpr int SEG_THREADS = 256, SEG_MAX_BLOCKS = 1024, SEG_STAGE = 1024;
-struct SegSlot { unsigned int n, pad; int id[64]; int cnt[64]; double f[64][2]; };
+template <int NF> struct SegSlotN { unsigned int n, pad; int id[64]; int cnt[64]; double f[64][NF]; };      // an entry = id, windows and NF sums
+using SegSlot = SegSlotN<2>;         // the regression table (squared and absolute error) and the classification table (cross entropy: the first sum alone)
+using SegSlotCom = SegSlotN<4>;      // the centroidal-momentum table
 struct SegScratch { unsigned int ticket, pad[3]; };      // followed by SegSlot[ceil(batch / 64)]
 static_assert(sizeof(SegSlot) == 1544 && sizeof(SegScratch) == 16, "include/mshgnn.h documents 16 + 1544 * ceil(batch / 64) bytes");
+static_assert(sizeof(SegSlotCom) == 2568, "include/mshgnn.h documents 16 + 2568 * ceil(batch / 64) bytes");
 
 __device__ __forceinline__ void met_store(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ int met_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -1005,14 +1008,12 @@ __global__ __launch_bounds__(SEG_THREADS) void k_metrics_cls_seg(const float* lo
 }
 
 // ---- four sums per entry: the centroidal-momentum sums per segment --------------------------------------------------------------------------
-// The same three steps with a slot type of its own (an entry = id, windows and NF sums) and the merge's stage depth as a template parameter: at
+// The same three steps with a wave step and a merge of their own (kept separate from the two-sum ones above: HISTORY.md, "Twin kernels") and the merge's stage depth as a
+// template parameter: at
 // four sums SEG_STAGE entries of s_f plus the mask rows would pass 64 KB of static LDS, 512 fit in 38 KB.  The merge always takes the
 // staged walk, STAGE entries at a time (the two-entry prefetch of seg_merge is a tuning of the evaluation sweeps' regression table, not part of
 // the order of additions): thread t adds the entries of the ids == t (mod SEG_THREADS) in (slot, entry) order and hands every finished id to
 // `flush_row(row, sums, windows)`.
-template <int NF> struct SegSlotN { unsigned int n, pad; int id[64]; int cnt[64]; double f[64][NF]; };
-using SegSlotCom = SegSlotN<4>;
-static_assert(sizeof(SegSlotCom) == 2568, "include/mshgnn.h documents 16 + 2568 * ceil(batch / 64) bytes");
 
 template <int NF> __device__ __forceinline__ void seg_wave_emit_n(SegSlotN<NF>* slot, bool valid, int id, const double (&f)[NF]) {
     const int lane = threadIdx.x & 63;

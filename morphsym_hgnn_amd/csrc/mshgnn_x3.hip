@@ -17,59 +17,7 @@
 #include "mshgnn_enc.hpp"
 #include "mshgnn_launch.hpp"
 
-// ------------------------------------------------------------------------------------------------------
-// k_prep_x3: hi and lo MFMA B-fragment images of every weight pack (root-sum, transpose) + bias sums
-// ------------------------------------------------------------------------------------------------------
-// (many packs: k_prep_tiled<__bf16, true>, mshgnn_device.hpp)
-// output vector `idx` of this launch's pack range (hi and lo images), or (idx past the packs) one bias sum
-__device__ __forceinline__ void prep_one_x3(const PrepArgs& a, int idx, bool with_bias) {
-    constexpr int EPC = 8, NBV = 8;
-    const int vec_per_pack = H * H / EPC;
-    const int npk = a.pack_n < 0 ? a.n_packs : a.pack_n;
-    const int total = npk * vec_per_pack;
-    if (idx < total) {
-        const int pack = a.pack0 + idx / vec_per_pack, r = idx % vec_per_pack;
-        const int gid = pack * vec_per_pack + r;
-        const int lane = r % 64, v = (r / 64) % NBV, wv = r / (64 * NBV);
-        const PackDesc pd = a.packs[pack];
-        float g[8][EPC];     // up to 8 source matrices (root-sum), every gather issued before the first add
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-            for (int x = 0; x < EPC; ++x) {
-                // same element map as k_prep<__bf16>: MFMA row i = lane & 15 of the wave's 16-row block fb carries output feature 8 (i / 4) + 4 fb + i % 4
-                const int i16 = lane & 15;
-                const int k = 32 * (lane >> 4) + 8 * (v & 3) + x, col = wv * 32 + 8 * (i16 >> 2) + 4 * (v >> 2) + (i16 & 3);
-                g[i][x] = 0.f;
-                if (i < pd.n_src) {
-                    if (pd.orient == 0) { if (k < pd.ncols) g[i][x] = a.params[pd.src[i] + (int64_t)col * pd.ld + pd.col0 + k]; }
-                    else g[i][x] = a.params[pd.src[i] + (int64_t)k * pd.ld + col];
-                }
-            }
-        float sum[EPC];
-#pragma unroll
-        for (int x = 0; x < EPC; ++x) {
-            sum[x] = 0.f;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) sum[x] += g[i][x];     // fixed order: same value every step
-        }
-        u32x4 hi, lo;
-        split_oct(f32x4{sum[0], sum[1], sum[2], sum[3]}, f32x4{sum[4], sum[5], sum[6], sum[7]}, hi, lo);
-        u32x4* dst = reinterpret_cast<u32x4*>(a.wpack);
-        dst[gid] = hi;
-        dst[(size_t)a.n_packs * vec_per_pack + gid] = lo;
-    } else if (with_bias) {
-        const int b = idx - total;
-        if (b < a.n_biases * H) {
-            const BiasDesc bd = a.biases[b / H];
-            float s = 0.f;
-            for (int i = 0; i < bd.n_src; ++i) s += a.params[bd.src[i] + (b % H)];
-            a.bias[b] = s;
-        }
-    }
-}
-__global__ void k_prep_x3(PrepArgs a) { prep_one_x3(a, blockIdx.x * blockDim.x + threadIdx.x, true); }
-
+// (k_prep<__bf16, true> / k_prep_tiled<__bf16, true>, the hi and lo MFMA B-fragment images of every weight pack + bias sums: mshgnn_device.hpp)
 // (k_enc_x3, the encoder of this plan: defined in mshgnn_enc.hpp, beside k_enc_fwd of the fp32 / bf16 plans)
 
 // ------------------------------------------------------------------------------------------------------
@@ -96,92 +44,8 @@ static StackKernelX3 x3_spec_kernel(const HostPlan& hp, int form, const char** n
 }
 
 
-// ------------------------------------------------------------------------------------------------------
-// k_dec_bwd_x3: decoder backward (+ fused wrapper MSE / cross entropy) on the hi/lo planes of X_L -> dX_L planes
-// (k_dec_bwd of mshgnn.hip; used by mshgnn_backward / _mse / _ce -- mshgnn_step_mse takes the fused tail of k_stack_fwd_x3)
-// ------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_dec_bwd_x3(DecArgs a) {
-    using T = T16;
-    __shared__ float red[16][DEC_SLAB_FLOATS];
-    const int c = threadIdx.x & 15, rg = threadIdx.x >> 4;
-    const int64_t rows = (int64_t)a.B * a.n_out;
-    const int64_t per = ((rows + gridDim.x - 1) / gridDim.x + 15) / 16 * 16;
-    const int64_t r_begin = (int64_t)blockIdx.x * per, r_end = min(rows, r_begin + per);
-    const T* xl = reinterpret_cast<const T*>(a.xl);
-    T* dxl = reinterpret_cast<T*>(a.dxl);
-    const float* W = a.params + a.off_w;
-    float accw[8][8], accb[8];
-#pragma unroll
-    for (int d = 0; d < 8; ++d) { accb[d] = 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) accw[d][e] = 0.f; }
-    float lsum = 0.f;
-    for (int64_t r = r_begin + rg; r < r_end; r += 16) {
-        const int w = (int)(r / a.n_out), f = (int)(r % a.n_out);
-        const size_t idx = x3_idx(w, a.node0 + f, a.B) + c * 8;
-        float x[8], xlo[8], dx[8];
-        load8<T>(xl + idx, x);
-        load8<T>(xl + idx + H, xlo);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { x[e] += xlo[e]; dx[e] = 0.f; }
-        float ce_g[2] = {0.f, 0.f};
-        if (a.labels) {   // wrapper cross entropy fused (gnnLightning.py:640-648, mean over the batch * 4 feet): dL/dlogit = (p - onehot) / rows
-            const float l0 = a.out[r * 2], l1 = a.out[r * 2 + 1];
-            const float m = fmaxf(l0, l1), e0 = expf(l0 - m), e1 = expf(l1 - m), se = e0 + e1;
-            const int lab = a.labels[r] != 0;
-            ce_g[0] = (e0 / se - (lab ? 0.f : 1.f)) * a.inv_n; ce_g[1] = (e1 / se - (lab ? 1.f : 0.f)) * a.inv_n;
-            if (c == 0) lsum += (m + logf(se)) - (lab ? l1 : l0);
-        }
-#pragma unroll
-        for (int d = 0; d < 8; ++d) {
-            if (d < a.dout) {
-                float go;
-                if (a.labels) go = ce_g[d & 1];
-                else if (a.y) {   // wrapper MSE fused (gnnLightning.py:633-639): dL/dout = 2 (out - y) / n
-                    const float dlt = a.out[r * a.dout + d] - a.y[r * a.dout + d];
-                    if (a.reg_kind == MSHGNN_REG_LOSS_MSE) {
-                        go = 2.0f * dlt * a.inv_n;
-                        if (c == 0) lsum += dlt * dlt;
-                    } else {      // L1 / Huber: the plan's regression loss
-                        float term;
-                        reg_loss_terms(dlt, a.inv_n, a.reg_kind, a.reg_delta, go, term);
-                        if (c == 0) lsum += term;
-                    }
-                } else go = a.gout[r * a.dout + d];
-                const float g = go * a.out_mask[f * a.dout + d];
-                accb[d] += g;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) { accw[d][e] += g * x[e]; dx[e] += g * W[d * H + c * 8 + e]; }
-            }
-        }
-        u32x4 hi, lo;
-        split_oct(f32x4{dx[0], dx[1], dx[2], dx[3]}, f32x4{dx[4], dx[5], dx[6], dx[7]}, hi, lo);
-        *reinterpret_cast<u32x4*>(dxl + idx) = hi;
-        *reinterpret_cast<u32x4*>(dxl + idx + H) = lo;
-    }
-#pragma unroll
-    for (int d = 0; d < 8; ++d) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) red[rg][d * H + c * 8 + e] = accw[d][e];
-        if (c == 0) red[rg][8 * H + d] = accb[d];
-    }
-    __syncthreads();
-    float* slab = a.slabs + (size_t)blockIdx.x * DEC_SLAB_FLOATS;
-    {   // per-block loss partial rides in the slab (summed in fixed order by k_finalize: no atomics, deterministic)
-        __shared__ float lred[4];
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) lsum += __shfl_xor(lsum, m, 64);
-        if ((threadIdx.x & 63) == 0) lred[threadIdx.x >> 6] = lsum;
-        __syncthreads();
-        if (threadIdx.x == 0) slab[8 * H + 8] = (lred[0] + lred[1]) + (lred[2] + lred[3]);
-    }
-    for (int i = threadIdx.x; i < 8 * H + 8; i += 256) {
-        float s2 = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s2 += red[r][i];
-        slab[i] = s2;
-    }
-}
+// (k_dec_bwd<T16, true>, the decoder backward on the hi/lo planes of X_L -> dX_L planes: mshgnn_device.hpp; used by mshgnn_backward / _mse / _ce -- mshgnn_step_mse takes
+// the fused tail of k_stack_fwd_x3)
 
 // ------------------------------------------------------------------------------------------------------
 // weight gradients: all of the step as one split-K MFMA launch, dW[o][k] = sum_w P[w][o] Q[w][k] with P = P_hi + P_lo, Q = Q_hi + Q_lo: four staged tiles
@@ -403,7 +267,7 @@ template <bool ALIGNED> __global__ __launch_bounds__(256, GWX3_WPS) void k_gradw
 // ------------------------------------------------------------------------------------------------------
 void x3_launch_prep(const PrepArgs& a, bool biases, hipStream_t st) {
     if (prep_use_tiled(a.n_packs)) hipLaunchKernelGGL((k_prep_tiled<__bf16, true>), dim3(prep_tiled_grid(a.n_packs, a.n_biases)), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(k_prep_x3, dim3(prep_grid(a, 8, biases)), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((k_prep<__bf16, true>), dim3(prep_grid(a, 8, biases)), dim3(256), 0, st, a);
 }
 
 // launch tables: row k is what pick_stack / pick_enc (mshgnn_pick.hpp) call k on this plan
@@ -505,7 +369,7 @@ int x3_backward(const mshgnn_plan* p, const StepCall& c) {
         DecArgs a{};
         fill_dec_bwd_args(p, c, lay, a);
         ProfScope ps(p, hp.ks_dec_bwd, st);
-        hipLaunchKernelGGL(k_dec_bwd_x3, dim3(NWG_DEC), dim3(256), 0, st, a);
+        hipLaunchKernelGGL((k_dec_bwd<T16, true>), dim3(NWG_DEC), dim3(256), 0, st, a);
     }
     if (c.gw_phase != 1 && !c.stack_done) {
         StackArgs a{};

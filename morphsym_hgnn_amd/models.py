@@ -363,7 +363,7 @@ class _MSHGNNBase(nn.Module):
         """"x3" / "f32" / "bf16": the plan of the fused engine (fp32 master parameters in one flat buffer).
         "f64": the reference's own precision (torch.set_default_dtype(torch.float64), gnnLightning.py:1183).  The parameters become fp64 (`self.double()`: a
         load_state_dict of a reference checkpoint then keeps every bit) and no engine is compiled: forward() is `_forward_operators` under
-        `ops.compute_dtype("f64")` -- every Linear / GraphConv on the fp64 MFMA operators of csrc/mshgnn_ops_f64.hip, with the model's own activation module,
+        `ops.compute_dtype("f64")` -- every Linear / GraphConv on the fp64 MFMA operators of csrc/mshgnn_ops.hip, with the model's own activation module,
         autograd for the parameter and the input gradients.  fp64 inputs are read as they are, other dtypes are widened; the output is fp64.  The one-call
         and series routes (`fused_training_step`, `fused_training_step_windows`, `forward_windows`) return None, so their callers assemble and call forward().
         Leaving "f64" calls `self.float()`: the parameters are rounded to fp32 ONCE (f64 -> x3 is not a round trip for parameters that were loaded or trained

@@ -9,7 +9,7 @@ path of a maintainer who swaps only the PyG import.  Arithmetic: fp32 operands, 
 gnnLightning.py:1183) are cast in and the results cast back: by default an fp64 caller gets fp32 arithmetic behind fp64-typed tensors.
 
 `set_compute_dtype("f64")` / `with compute_dtype("f64"):` switch every operator here (and with them the modules of nn.py) to the fp64 kernels of
-csrc/mshgnn_ops_f64.hip (v_mfma_f64_16x16x4_f64, the same fixed summation orders): fp64 device tensors are used as they are (no copy where they are
+csrc/mshgnn_ops.hip (v_mfma_f64_16x16x4_f64, the same fixed summation orders): fp64 device tensors are used as they are (no copy where they are
 contiguous), any other floating dtype is widened to fp64 (exact), the tensors saved for the backward are fp64, and results still come back in the
 caller's dtype -- an fp64 caller then sees no narrowing anywhere.  A backward runs in the arithmetic of its forward, whatever the mode is by then.
 The default, "f32", is bit for bit what it was before the mode existed.  There is no CPU implementation: tensors that are not on a HIP device raise.
@@ -73,7 +73,7 @@ def _entry(lib, name: str, dt: torch.dtype):
         return getattr(lib, name), name
     name += "_f64"
     if not hasattr(lib, name):
-        raise RuntimeError(f"this build of libmshgnn.so has no {name}: the 'f64' compute dtype needs the fp64 operators (csrc/mshgnn_ops_f64.hip)")
+        raise RuntimeError(f"this build of libmshgnn.so has no {name}: the 'f64' compute dtype needs the fp64 operators (csrc/mshgnn_ops.hip)")
     return getattr(lib, name), name
 
 

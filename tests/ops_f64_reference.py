@@ -1,4 +1,4 @@
-"""Host-side references, data and checkers for the fp64 stand-alone operators (csrc/mshgnn_ops_f64.hip behind ops.compute_dtype("f64")): test
+"""Host-side references, data and checkers for the fp64 stand-alone operators (csrc/mshgnn_ops.hip behind ops.compute_dtype("f64")): test
 infrastructure, no GPU.  The discipline is tests/ops_reference.py's with u = 2^-53; its shape tables are reused by import.
 
 Three data families for the GEMM, each stored as int64 tensors on a dyadic grid (value = int * 2^exp, exact in fp64):

@@ -1,5 +1,5 @@
 """Precision "f64" on the module surface: `set_precision("f64")` (and MSHGNN_DTYPE=f64) on the MS-HGNN models, models.MLP and the wrappers -- fp64
-parameters, every Linear / GraphConv on the fp64 MFMA operators (csrc/mshgnn_ops_f64.hip), autograd for the gradients, an fp64 loss.
+parameters, every Linear / GraphConv on the fp64 MFMA operators (csrc/mshgnn_ops.hip), autograd for the gradients, an fp64 loss.
 
 Tolerance 1e-9 against the fp64 oracle, DERIVED, not measured: the longest reduction of these cases is under 1e3 terms (n u ~ 1e-13), the worst
 cancellation this project has seen on a gradient (the decoder-bias case noted in tests/test_generic_gpu.py) costs about two orders, which leaves two more.

@@ -1,5 +1,5 @@
-"""The fp64 stand-alone operators (csrc/mshgnn_ops_f64.hip: k_op_gemm_f64 on v_mfma_f64_16x16x4_f64, k_op_splitk_sum_f64, k_op_aggregate_f64,
-k_op_colsum1/2_f64 behind mshgnn_op_gemm_f64 / _aggregate_f64 / _colsum_f64; ops.compute_dtype("f64")) ELEMENT BY ELEMENT, on the matrix of
+"""The fp64 stand-alone operators (csrc/mshgnn_ops.hip: k_op_gemm_f64 on v_mfma_f64_16x16x4_f64 and the double instantiations of k_op_splitk_sum, k_op_aggregate,
+k_op_colsum1/2 behind mshgnn_op_gemm_f64 / _aggregate_f64 / _colsum_f64; ops.compute_dtype("f64")) ELEMENT BY ELEMENT, on the matrix of
 tests/test_ops_exact_gpu.py with the data of tests/ops_f64_reference.py:
   * wide_sum (integers whose sums reach 2^52: wrong under any fp32 accumulation) and wide_operand (26-bit operands, one term per sum: wrong under any
     narrowing of an operand) must be the exact integer result BIT FOR BIT; dyadic random data must lie within gamma_{2K+4}(2^-53) sum |terms| of the

@@ -135,7 +135,8 @@ def _cls_inputs(B, seed):
     return logits, labels
 
 
-@pytest.mark.parametrize("B,n_seg,pattern", [(1000, 5, "runs"), (1000, 5, "overflow"), (257, 300, "shuffled"), (64, 1, "equal"), (513, 2, "alternate")])
+@pytest.mark.parametrize("B,n_seg,pattern", [(1000, 5, "runs"), (1000, 5, "overflow"), (257, 300, "shuffled"), (64, 1, "equal"), (513, 2, "alternate"),
+                                                (1153, 1200, "shuffled")])      # (19 slots with 1153 entries: more than one stage of the merge, the staged walk)
 def test_classification_counters_are_exact_and_the_cross_entropy_within_the_bound(B, n_seg, pattern):
     logits, labels = _cls_inputs(B, B + n_seg)
     seg = _ids(pattern, B, n_seg, 9)

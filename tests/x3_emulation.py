@@ -10,13 +10,13 @@ single product is the sum of the three terms) must still reproduce the fp64 orac
                      product a (hi, lo) pair, every product hi.hi + lo.hi + hi.lo (left factor: the activation or activation gradient; right factor: the
                      weight image, or the layer input of a weight gradient).  The rounding points, read off the kernels:
                        * the masked fp32 inputs are split while they are staged (k_enc_x3; again by k_gradw_x3_lean and mshgnn_input_grad's W_enc image);
-                       * every weight pack is split AFTER the root weights of a destination type are summed in fp32 (prep_one_x3); the transposed images
+                       * every weight pack is split AFTER the root weights of a destination type are summed in fp32 (prep_one<__bf16, true>); the transposed images
                          of the backward sweep hold the same pairs;
                        * X_0 = split(relu(acc)) (k_enc_x3); X_{l+1} = split(f(H) + (hi + lo of X_l)) (x3_fwd_layer); the ReLU bits are taken from the fp32
                          accumulator (relu_with_bits), on closed data the same as [hi > 0];
                        * base_transform: H is split into LDS and the stash, T1 = split(relu(.)), both products through mlp_mac3; the backward masks dT1
                          with [T1_hi > 0] (the hi half carries the sign), dU and dH are split;
-                       * the decoder, its backward and every bias sum are plain fp32 on hi + lo (decoder_tail, k_dec_bwd_x3): no cross term exists there;
+                       * the decoder, its backward and every bias sum are plain fp32 on hi + lo (decoder_tail, k_dec_bwd<__bf16, true>): no cross term exists there;
                        * dX_L = split(g W_dec); dX_l = split(residual + products), layer 0 masked by the encoder's ReLU bits; dH of a ReLU node is both
                          planes of dX_{l+1} masked (chunk_mask_bits);
                        * k_gradw_x3_lean: dW = P_hi Q_hi + P_hi Q_lo + P_lo Q_hi over the stashed planes;

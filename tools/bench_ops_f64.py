@@ -1,4 +1,4 @@
-"""Measure the fp64 operators (csrc/mshgnn_ops_f64.hip) on one GPU: reported, not gated; bench.py stays the project's benchmark.
+"""Measure the fp64 operators (csrc/mshgnn_ops.hip) on one GPU: reported, not gated; bench.py stays the project's benchmark.
 
 1. mshgnn_op_gemm_f64 on the three products of the model at 8192 A1 windows (12 joints: 98 304 rows):
      98 304 x 128 x 450   (the joint encoder, y = x W^T + b)

@@ -1,7 +1,9 @@
 """gfx950 device code of two builds compared kernel by kernel: text size, SHA-256 of every __global__ symbol's bytes and the resource metadata of the code
 object's notes -- the report format of profiles/enc_shared_device_text.txt.  A template that gained trailing defaulted parameters keeps its code but not its
 mangled name: a kernel of the second build that the first does not have is paired with the first build's kernel whose mangled name is the same without one
-trailing `false` template argument ("Lb0E" in front of the argument list's end) and marked '~'.
+trailing `false` template argument ("Lb0E" in front of the argument list's end) and marked '~'.  A kernel that was renamed outright (a copy that became an
+instantiation of a shared template) is paired with a kernel of the same object that only the first build has and whose (size, SHA-256, resource tuple) are
+equal, and marked '@' (no such kernel in the same object: one of any object, for a kernel whose source file was merged into another).
 usage: python tools/device_text_diff.py PARENT_BUILD_DIR THIS_BUILD_DIR > profiles/NAME.txt"""
 import glob, hashlib, os, re, subprocess, sys, tempfile
 
@@ -56,7 +58,8 @@ def main():
     print("# extraction: llvm-objcopy --only-section=.hip_fatbin | clang-offload-bundler --unbundle --targets=hipv4-amdgcn-amd-amdhsa--gfx950 | the .text bytes of every FUNC GLOBAL symbol")
     print("# per __global__ symbol: text size, SHA-256 of the symbol's bytes, and the resource metadata of the code object's notes")
     print("# (" + " ".join(k[1:] for k in KEYS) + ")")
-    print("# kernels are paired by mangled name; a template that gained a trailing defaulted `false` parameter is paired with its parent name ('~')")
+    print("# kernels are paired by mangled name; a template that gained a trailing defaulted `false` parameter is paired with its parent name ('~');")
+    print("# a kernel that only this change has is paired with a kernel that only the parent has (of the same object, else of any) when their size, bytes and resources are equal ('@')")
     print("#\n# object                 text bytes  parent .text SHA-256[:16]  this .text SHA-256[:16]  kernels (parent/this)")
     P, Tk = {}, {}
     for obj in sorted(glob.glob(os.path.join(this_dir, "*.o"))):
@@ -73,28 +76,59 @@ def main():
             P[k] = (base,) + v
         same = p is not None and p[1] == t[1]
         print(f"{base:24s} {t[2]:10d}  {(p[1][:16] if p else '-'):24s}  {t[1][:16]:22s}  {'equal  ' if same else 'DIFFERS'}  kernels {len(p[0]) if p else 0}/{len(t[0])}")
+    for pobj in sorted(glob.glob(os.path.join(parent_dir, "*.o"))):      # an object only the parent has (its source file went into another): its kernels still pair by bytes
+        base = os.path.basename(pobj)
+        if os.path.exists(os.path.join(this_dir, base)):
+            continue
+        p = kernels_of(pobj, tmp)
+        print(f"{base:24s} {(p[2] if p else 0):10d}  {(p[1][:16] if p else '-'):24s}  {'-':22s}  {'GONE   '}  kernels {len(p[0]) if p else 0}/0")
+        for k, v in (p[0] if p else {}).items():
+            P[k] = (base,) + v
     dp, dt = demangle(list(P)), demangle(list(Tk))
     key_t = {k: (k if k in P or k.replace("Lb0EEv", "Ev", 1) not in P else k.replace("Lb0EEv", "Ev", 1)) for k in Tk}
     by_name_p = {k: k for k in P}
     paired, new = [], []
     for k in sorted(Tk, key=lambda k: (Tk[k][0], key_t[k])):
         (paired if key_t[k] in by_name_p else new).append(k)
-    gone = sorted(set(by_name_p) - {key_t[k] for k in paired})
+    # renamed outright: a kernel only this build has, paired by its bytes with a kernel that only the parent has (each parent kernel once): one of the same object,
+    # else -- its source file went into another -- one of any object
+    unclaimed = sorted(set(by_name_p) - {key_t[k] for k in paired})
+    by_bytes = {}
+    for same_object in (True, False):
+        for k in list(new):
+            for q in unclaimed:
+                if P[q][1:] == Tk[k][1:] and (P[q][0] == Tk[k][0] or not same_object):
+                    by_bytes[k] = q
+                    unclaimed.remove(q)
+                    new.remove(k)
+                    break
+    gone = sorted(set(by_name_p) - {key_t[k] for k in paired} - set(by_bytes.values()))
     differ = [k for k in paired if Tk[k][1:] != P[by_name_p[key_t[k]]][1:]]
     renamed = [k for k in paired if k != by_name_p[key_t[k]]]
     print(f"#\n# kernel symbols: parent {len(P)}, this change {len(Tk)}; only in parent: {gone}; only in this change: {len(new)} (listed below as 'new')")
     print(f"# kernels in both: {len(paired)}; with a size, byte or resource difference: {len(differ)}; same bytes under a longer mangled name: {len(renamed)}")
-    print("#\n# size  sha256[:16]  resources  object  symbol     ('=' : size, bytes and resources equal the parent's; '~' : equal, the mangled name gained defaulted parameters; '*' : differs; 'new')")
+    print(f"# kernels under a new name whose size, bytes and resources equal those of a kernel only the parent has: {len(by_bytes)}")
+    print("#\n# size  sha256[:16]  resources  object  symbol     ('=' : size, bytes and resources equal the parent's; '~' : equal, the mangled name gained defaulted parameters;")
+    print("#                                                    '@' : equal to the parent kernel named on the next line, paired by its bytes; '*' : differs; 'new')")
     for k in sorted(Tk, key=lambda k: (Tk[k][0], dt[k])):
         base, n, h, res = Tk[k]
         if k in new:
             mark = "new"
+        elif k in by_bytes:
+            mark = "@"
         else:
             mark = "*" if k in differ else ("~" if k in renamed else "=")
         print(f"{n:8d}  {h[:16]}  {' '.join(res)}  {base:20s} {mark:3s}  {dt[k][:170]}")
         if mark == "*":
             pb, pn, ph, pres = P[by_name_p[key_t[k]]]
             print(f"{pn:8d}  {ph[:16]}  {' '.join(pres)}  (parent)")
+        if mark == "@":
+            print(f"{'':8s}  {'':16s}  (parent, {P[by_bytes[k]][0]}: {dp[by_bytes[k]][:170]})")
+    if gone:
+        print("#\n# only in the parent (renamed here with other bytes, or removed): their size, bytes and resources, to read a renamed kernel's 'new' line against")
+        for k in sorted(gone, key=lambda k: (P[k][0], dp[k])):
+            base, n, h, res = P[k]
+            print(f"{n:8d}  {h[:16]}  {' '.join(res)}  {base:20s} gone {dp[k][:170]}")
 
 
 if __name__ == "__main__":
